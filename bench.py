@@ -5,7 +5,11 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N = 1 — configs[1], the configuration the metric is quoted on: a step is ONE Homotopy solve of one signal
-(A 8192 x 65536 fp32, k = 64) with inputs resident in HBM; `value` = signals/s; `roofline` = the METRIC'S kernel, SURVEY 8d's
+(A 8192 x 65536 fp32, k = 64) with inputs resident in HBM; `value` = signals/s, `ms_per_step` = milliseconds per solve.  A plain
+run does only what that figure needs: set-up, warm-up, the timed solves (no profiling events in them), the recovery check of the
+timed signals and the result line.
+
+--full adds everything else, in the same run: the timed solves then carry HIP events (every 4th solve), `roofline` = the METRIC'S kernel, SURVEY 8d's
 fp32 correlation GEMV c = A^T y (k_sweep, 2 147 778 560 bytes per launch), timed with HIP events on the solver's stream and its
 `traffic` measured in the same run (child runs of tools/pmc_probe.py under `rocprofv3 --pmc`; profiles/traffic.json only as the
 labelled fallback) — `in_timed_solve: false`: a certified solve of the shipped default (the screened form, csrc/screen.hip +
@@ -29,6 +33,11 @@ weak scaling, `value` = N * 4096 * K / elapsed.  (The N = 1 line carries the sam
 rate under `batched`: that, not the single-signal `value`, is the base of a scaling ratio.)
 
 One process per GPU; prints ONE JSON line on rank 0.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller as DIR/<name>.npy: configs[1]
+`x` (float32, n), `iterations` and `solution_error` (float64, one each); the batched workload the records of every rank, decoded
+(`signal`, `K`, `iter`, `err` float64 (S,); `idx` float64 (S, 96), -1 past K; `val` float32 (S, 96), 0 past K; a fixed sample of
+the signals where all of them would pass 60 MiB).  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -247,7 +256,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the drop-in, OMP and fp64 (configs[4]) extras (single-GPU runs only)")
     ap.add_argument("--cpu-budget-s", type=float, default=24.0)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the profiled timed region and rooflines, the live traffic, the untimed comparison runs, the "
+                         "extras, configs[2], configs[4], IRLS and the CPU baseline (the --no-* and --batch switches apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -285,7 +301,7 @@ def main():
         A = torch.empty((M, N), device=dev, dtype=torch.float32)
     if use_dist:
         dist.broadcast(A, src=0)
-    if not (rank == 0 and world == 1 and workload == "single" and not args.no_cpu_baseline):
+    if not (rank == 0 and world == 1 and workload == "single" and args.full and not args.no_cpu_baseline):
         A_host = None
     h = sship.Homotopy(A, device=local_rank)
     if args.variant is not None:
@@ -304,6 +320,15 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: array} -> d/<name>.npy (float32 / float64 only)"""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def run_batched(args, h, A, dev, rank, world, use_dist, torch, dist, sharding):
@@ -353,6 +378,17 @@ def run_batched(args, h, A, dev, rank, world, use_dist, torch, dist, sharding):
     h.close()
     if rank != 0:
         return None
+    if args.dump_outputs:
+        r = allrec.cpu().numpy().reshape(world * B, rb).view(sharding.record_dtype(KMAX_RECORD, np.float32)).reshape(-1)
+        # (at most 60 MiB: beyond that a fixed sample of the signals, `signal` = their global indices)
+        keep = 60 * 2 ** 20 // (KMAX_RECORD * 12 + 32)
+        rows = np.arange(len(r)) if len(r) <= keep else np.sort(np.random.default_rng(0).choice(len(r), keep, replace=False))
+        r = r[rows]
+        past_k = np.arange(KMAX_RECORD)[None, :] >= r["K"][:, None]
+        dump_outputs(args.dump_outputs, {
+            "signal": rows.astype(np.float64),
+            "K": r["K"].astype(np.float64), "iter": r["iter"].astype(np.float64), "err": r["err"].astype(np.float64),
+            "idx": np.where(past_k, -1.0, r["idx"].astype(np.float64)), "val": np.where(past_k, np.float32(0), r["val"])})
     cq_ms = st["cq_ms"] / max(1, st["cq_launches"])
     cq_gbs = st["cq_bytes"] / (st["cq_ms"] * 1e-3) / 1e9 if st["cq_ms"] > 0 else 0.0
     subset = st["subset_signals"] > 0
@@ -431,11 +467,12 @@ def run_single(args, h, A, A_host, dev, rank, local_rank, world, use_dist, torch
     for s in range(args.warmup):
         h.solve(sigs[s][0], TOL, MAX_ITER, out=xw)
 
-    h.set_profiling(True)
-    h.set_option("profile_every", args.profile_every)
-    # the roofline's launch durations come from HIP events inside the timed region: on every 4th solve (each event costs
-    # stream time; `launches_timed` says how many launches the average is over)
-    h.set_option("profile_solve_every", 4 if args.steps >= 8 else 1)
+    if args.full:
+        h.set_profiling(True)
+        h.set_option("profile_every", args.profile_every)
+        # the roofline's launch durations come from HIP events inside the timed region: on every 4th solve (each event costs
+        # stream time; `launches_timed` says how many launches the average is over)
+        h.set_option("profile_solve_every", 4 if args.steps >= 8 else 1)
     h.reset_stats()
     torch.cuda.synchronize()
     if use_dist:
@@ -474,6 +511,40 @@ def run_single(args, h, A, A_host, dev, rank, local_rank, world, use_dist, torch
     recovered_total = int(rc.item())
     st = h.stats()
     single_value = world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": Xh[args.steps - 1], "iterations": np.array([iters[-1]], np.float64),
+                                         "solution_error": np.array([errs[-1]], np.float64)})
+    ms_per_step = elapsed / args.steps * 1e3
+    head = {
+        "metric": "signals recovered/sec (Homotopy l1, m=8192 n=65536 k=64 fp32)",
+        "value": single_value,
+        "unit": "signals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "configs[1]: one signal per solve, A 8192x65536 fp32 = default_rng(1234).standard_normal/sqrt(m) "
+                        "(SURVEY 8d recipe), k=64 positive coefficients, tol 1e-3, max_iter 256; shipped defaults "
+                        "(reference behaviour: tie_guard 0, zero_on_removal 0)",
+            "m": M, "n": N, "k": K_SPARSE, "signals_per_step_per_gpu": 1,
+            "sharding": "one GPU (with --gpus N --workload single: independent replicas, one signal per rank and step)",
+            "sweep_variant": h.get_option("sweep_variant"), "engine": h.get_option("engine"),
+        },
+    }
+    if not args.full:
+        h.close()
+        if rank != 0:
+            return None
+        head.update({"screened_form": {"signals_certified": int(st["screen_signals"]), "signals_redone_in_the_default_engine": int(st["screen_redone"])},
+                     "iterations_mean": float(iters.mean()),
+                     "recovered": {"signals": world * args.steps, "support_exact": recovered_total, "max_rel_coef_err_rank0": coef_err}})
+        return head
 
     # outside the timed region: the same signals through the engine the screened form stands in for (three fp32 passes over A),
     # with its lookahead sweep timed — what the headline was before csrc/screen.hip, and what an uncertified signal falls back to
@@ -997,32 +1068,12 @@ def run_single(args, h, A, A_host, dev, rank, local_rank, world, use_dist, torch
                             "launches_timed": launches}
             else:
                 hbm_roof = None
-        ms_per_step = elapsed / args.steps * 1e3
         first_ms = st["sweep64_ms"] / max(1, st["sweep64_launches"]) if st["sweep64_launches"] else 0.0
         # (device counter: sweeps of all widths; the first one of each solve is the 64-column pass when it ran)
         n32 = st["lookahead_sweeps"] / max(1, st["solves"]) - (1.0 if st["sweep64_launches"] else 0.0)
         la_ms = (first_ms + avg_ms * max(0.0, n32)) if engine >= 1 else None
-        out = {
-            "metric": "signals recovered/sec (Homotopy l1, m=8192 n=65536 k=64 fp32)",
-            "value": single_value,
-            "unit": "signals/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": "configs[1]: one signal per solve, A 8192x65536 fp32 = default_rng(1234).standard_normal/sqrt(m) "
-                            "(SURVEY 8d recipe), k=64 positive coefficients, tol 1e-3, max_iter 256; shipped defaults "
-                            "(reference behaviour: tie_guard 0, zero_on_removal 0)",
-                "m": M, "n": N, "k": K_SPARSE, "signals_per_step_per_gpu": 1,
-                "sharding": "one GPU (with --gpus N --workload single: independent replicas, one signal per rank and step)",
-                "sweep_variant": h.get_option("sweep_variant"), "engine": engine,
-            },
+        out = dict(head)
+        out.update({
             "roofline": roof,
             # the two HBM passes a certified solve actually runs (over the fp16 copy of A), the longer one first
             "fp16_passes_longest_first": (sorted([kk for kk, vv in (("screening_pass", scr_roof), (fp_key, first_pass_roof)) if vv],
@@ -1103,7 +1154,7 @@ def run_single(args, h, A, A_host, dev, rank, local_rank, world, use_dist, torch
                        if h.get_option("la_fused") >= 3 else "lookahead (cached Gram columns), resident iteration kernel") if engine >= 1 else "one fused sweep per iteration",
             "recovered": {"signals": world * args.steps, "support_exact": recovered_total,
                           "max_rel_coef_err_rank0": coef_err},
-        }
+        })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         if batched is not None:
             h.set_option("gram_single", 0)              # parity run of the headline path: Gram-column cache, not G

@@ -196,7 +196,7 @@ def test_product_sharded_batch_two_ranks_one_gpu(tmp_path, B):
 
 
 @pytest.mark.gpu
-def test_bench_multi_gpu_launch_rehearsed_on_one_gpu():
+def test_bench_multi_gpu_launch_rehearsed_on_one_gpu(tmp_path):
     """configs[3]'s launch line, rehearsed on the one GPU a test box has: `python -m torch.distributed.run --nproc-per-node 1 bench.py
     --workload batched ...` with SS_BENCH_DIST=1 walks everything an N > 1 launch executes — RCCL init, the broadcast of A from rank 0,
     the barriers, the per-step all_gather of the records, the all_reduce of the timing — and prints the one JSON line the driver
@@ -209,7 +209,7 @@ def test_bench_multi_gpu_launch_rehearsed_on_one_gpu():
     port = 29500 + (os.getpid() % 400)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "batched", "--batch", "1536",
-           "--steps", "2", "--warmup", "1"]
+           "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -220,3 +220,7 @@ def test_bench_multi_gpu_launch_rehearsed_on_one_gpu():
     assert out["roofline"]["frac"] > 0 and out["roofline"]["bound"] in ("hbm", "mfma")
     assert out["recovered"]["support_exact"] == out["recovered"]["signals_checked"] == 1536
     assert "configs[3]" in out["config"]["workload"]
+    # --dump-outputs: the last step's records, decoded
+    K, idx, val = (np.load(tmp_path / "out" / (f + ".npy")) for f in ("K", "idx", "val"))
+    assert K.shape == (1536,) and idx.shape == val.shape == (1536, 96) and idx.dtype == np.float64 and val.dtype == np.float32
+    assert np.all(K == 64) and np.array_equal((idx >= 0).sum(axis=1), K) and np.array_equal((val != 0).sum(axis=1), K)

@@ -36,7 +36,7 @@ def main():
     os.makedirs(dst, exist_ok=True)
     out = {"tag": tag}
     lines = ["# rocprofv3 summary `%s`" % tag, "",
-             "command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras`", ""]
+             "command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras`", ""]
 
     stats = glob.glob(os.path.join(src, "trace", "*", "*_kernel_stats.csv"))
     if stats:
