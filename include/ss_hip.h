@@ -221,7 +221,10 @@ typedef struct ss_hip_stats {
     double   sweep1_ms;
     uint64_t sweep1_bytes;         /* m*n*s + m*s + n*s                                         */
     double   solve_ms;             /* HIP-event time of whole solves (upload of y .. x ready)  */
-    uint64_t batch_rounds;         /* lock-step rounds run by the batched (MFMA) path          */
+    uint64_t batch_rounds;         /* lock-step rounds run by the batched (MFMA) path — as the host
+                                      enqueues them, up to "lookahead" rounds ahead of the device: the
+                                      rounds queued after the last signal finished are no-ops, and how
+                                      many there are depends on timing, not on the signals            */
     uint64_t lookahead_sweeps;     /* 32-RHS lookahead sweeps run by the fp32 single-signal engine */
     uint64_t sweep32_launches;     /* ... of which timed with HIP events (profiling on)         */
     double   sweep32_ms;           /* sum of their durations                                    */
@@ -565,8 +568,10 @@ int ss_hip_get_option(ss_hip_ctx* ctx, const char* key, long* value);
 /*
  * The homotopy path of the LAST solve when option "trace" is on: entry 0 is the initial
  * pick, entry t the column toggled by iteration t (added = 1 insert / 0 remove), the step
- * length gamma taken and lambda = ||c||_inf at the start of that iteration.  Writes up to
- * `capacity` entries into each non-NULL array; *count receives the number available.
+ * length gamma taken and lambda = ||c||_inf at the start of that iteration.  OMP
+ * (ss_hip_omp_solve_*) has no initial pick: its entry 0 is all zeros and entry t is the
+ * column picked by iteration t.  Writes up to `capacity` entries into each non-NULL array;
+ * *count receives the number available.
  */
 int ss_hip_get_trace(ss_hip_ctx* ctx, uint32_t capacity, uint32_t* idx, uint8_t* added,
                      double* gamma, double* c_inf, uint32_t* count);

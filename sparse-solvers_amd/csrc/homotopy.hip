@@ -1361,6 +1361,9 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             HIPCHK(hipMalloc(&ws.trace, (size_t)want_trace * sizeof(TraceEntry)));
             ws.trace_cap = want_trace;
         }
+        // (OMP does not write entry 0 — it has no initial pick —: a traced solve starts from zeros, not from whatever an earlier
+        // allocation left in the buffer, so that a context's trace does not depend on its history)
+        if (ctx->tracing) HIPCHK(hipMemsetAsync(ws.trace, 0, (size_t)want_trace * sizeof(TraceEntry), st));
         TraceEntry* const trace_keep = ws.trace;
         if (!ctx->tracing) ws.trace = nullptr;          // kernels skip the stores
         struct Restore { Workspace<T>& w; TraceEntry* p; ~Restore() { w.trace = p; } } restore{ ws, trace_keep };

@@ -395,3 +395,89 @@ def test_native_column_sharded_over_rccl_one_rank(tmp_path, dtype):
     p = np.load(tmp_path / "rccl.npz")
     assert int(p["it"]) == it1 and float(p["err"]) == e1 and np.array_equal(p["x"], x1)
     assert np.array_equal(p["idx"], t1["idx"]) and np.array_equal(p["gamma"], t1["gamma"])
+
+
+def _history_signals(A, which):
+    """three signals for one column-sharded context: the problem's own, and two more with their own supports (the second with the
+    trace on and a max_iter large enough that the replicated active set and the shard's workspace regrow)"""
+    _, y0, tol, mi = _native_problem(which, A.dtype)
+    out = [(y0, mi, False)]
+    for s, (big, tr) in enumerate(((True, True), (False, False))):
+        rng = np.random.default_rng(950 + s)
+        x0 = np.zeros(A.shape[1])
+        x0[rng.choice(A.shape[1], 14, replace=False)] = 1 + np.abs(rng.standard_normal(14))
+        out.append(((A.astype(np.float64) @ x0).astype(A.dtype), 200 if big else mi, tr))
+    return out, tol
+
+
+def _history_rank(rank, world, port, tmpdir, dtype):
+    """one rank of three solves on ONE column-sharded context (world 1: no transport; world 2: host collectives over gloo)"""
+    import faulthandler
+    faulthandler.enable()
+    import torch
+    import sship
+    A, _, _, _ = _native_problem(0, dtype)
+    sigs, tol = _history_signals(A, 0)
+    lo, hi = _bounds(A.shape[1], world, 0)[rank]
+    allreduce = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+
+        def allreduce(buf, op):
+            t = torch.from_numpy(buf.view(np.int64) if buf.dtype == np.uint64 else buf)
+            dist.all_reduce(t, op={"max": dist.ReduceOp.MAX, "min": dist.ReduceOp.MIN, "sum": dist.ReduceOp.SUM}[op])
+    shard = torch.from_numpy(np.ascontiguousarray(A[:, lo:hi])).to("cuda:0")
+    res = {}
+    with sship.ColumnSharded(shard, lo, A.shape[1], rank=rank, world=world, allreduce=allreduce) as h:
+        for i, (y, mi, tr) in enumerate(sigs):
+            h.set_option("trace", 1 if tr else 0)
+            x, it, err = h.solve(torch.from_numpy(y).to("cuda:0"), tol, mi)
+            t = h.trace()
+            res.update({"x%d" % i: x.copy(), "it%d" % i: it, "err%d" % i: err, "idx%d" % i: t["idx"], "added%d" % i: t["added"],
+                        "gamma%d" % i: t["gamma"]})
+    np.savez(os.path.join(tmpdir, "hist_rank%d.npz" % rank), lo=lo, hi=hi, **res)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("world", [1, 2], ids=["world1", "world2_gloo"])
+def test_native_column_sharded_solves_more_than_once(tmp_path, world, dtype):
+    """Three solves on one column-sharded context, in a child process (faulthandler on: a host crash fails this test with a
+    stack): a first signal; a second with the trace on and max_iter = 200, so that cs_ensure and the shard's workspace regrow; a
+    third with the trace off.  Each equals — bit for bit — a fresh world-1 context's solve of that signal, takes the oracle's path,
+    and an untraced solve reports no path."""
+    import oracle
+    import sship
+    import torch.multiprocessing as mp
+    port = 37100 + (os.getpid() % 1000) + world + (20 if dtype == np.float64 else 0)
+    mp.spawn(_history_rank, args=(world, port, str(tmp_path), dtype), nprocs=world, join=True)
+    A, _, _, _ = _native_problem(0, dtype)
+    sigs, tol = _history_signals(A, 0)
+    parts = [np.load(tmp_path / ("hist_rank%d.npz" % r)) for r in range(world)]
+    for i, (y, mi, tr) in enumerate(sigs):
+        with sship.ColumnSharded(A, 0, A.shape[1]) as f:
+            f.set_option("trace", 1)
+            x1, it1, e1 = f.solve(y, tol, mi)
+            t1 = f.trace()
+        x = np.zeros(A.shape[1], dtype)
+        for p in parts:
+            x[int(p["lo"]):int(p["hi"])] = p["x%d" % i]
+            assert int(p["it%d" % i]) == it1 and float(p["err%d" % i]) == e1, (i, int(p["it%d" % i]), it1)
+            if tr:
+                assert np.array_equal(p["idx%d" % i], t1["idx"]) and np.array_equal(p["added%d" % i], t1["added"])
+                assert np.array_equal(p["gamma%d" % i], t1["gamma"])
+            else:
+                assert len(p["idx%d" % i]) == 0, (i, "an untraced solve reports a path")
+        assert np.array_equal(x, x1), (i, "the long-lived context's solve differs from a fresh one's")
+        xo, ito, eo, tro = oracle.homotopy(A, y, tol, mi, trace=True)
+        assert it1 == ito, (i, it1, ito)
+        assert np.array_equal(t1["idx"][:-1], tro["idx"][:-1]) and np.array_equal(t1["added"][:-1], tro["added"][:-1])
+        assert np.array_equal(np.abs(x1) > 1e-4, np.abs(xo) > 1e-4)
+        rel = 1e-5 if dtype == np.float32 else 1e-10
+        assert np.abs(x1 - xo).max() <= rel * np.abs(xo).max()
