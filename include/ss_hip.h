@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define SS_HIP_ABI_VERSION 6     /* (5: the per-reason counters of round 4; 6: screen_rescued / screen_rescue_tried, the colshard _f64 entry points) */
+#define SS_HIP_ABI_VERSION 7     /* (5: the per-reason counters of round 4; 6: screen_rescued / screen_rescue_tried, the colshard _f64 entry points;
+                                    7: the OMP batch entry points and their counters) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -147,6 +148,46 @@ int ss_hip_homotopy_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, si
                                             ptrdiff_t y_stride, ptrdiff_t incy,
                                             double tol, uint32_t max_iter, uint32_t kmax,
                                             void* records, char* err, size_t errlen);
+
+/*
+ * OMP batch (ABI version 7): B signals sharing the context's sensing matrix, solved by orthogonal matching pursuit
+ * (ss_hip_omp_solve_*).  Arguments, record layout and validation are those of the Homotopy batch above
+ * (SS_HIP_ETYPE on a dtype mismatch; SS_HIP_EINVAL on an IRLS context, max_iter == 0, a tolerance outside
+ * [eps, 1), non-positive increments, null pointers; B == 0 returns SS_HIP_OK).  The report is {iterations,
+ * ||A^T r||_inf at exit}.
+ * CONTRACT: signal b's result is what ss_hip_omp_solve_* returns for it alone — the same picks, support and
+ * iteration count, coefficients equal to rounding; a signal no chunk form certifies is solved alone by the
+ * single-signal ladder, and then its result is that solve's bit for bit.
+ * Forms, in this order (ss_hip_stats::omp_batch_signals / omp_batch_redone count what the chunks of all of them certify / hand on):
+ *   fp32, B >= 4, G = A^T A at hand (option "gram_full_after", or an earlier batch formed it), or B >= max("batch_gram_min", 1536)
+ *         and G fits the budget: the Gram form (csrc/ompbatch.hip), chunks of 256 — c0 by the batch GEMM, every signal's path
+ *         on its 448 best-ranked columns with their Gram matrix gathered from G, every logged state certified against all
+ *         columns by one MFMA pass over the rows of G at the signal's support (omp_gram_signals);
+ *   fp32, B >= 4, dictionaries the screened form takes ("batch_screen"): chunks of 64 in the screened form in OMP mode —
+ *         the same path on the subset, every state certified by the pass over the fp16 copy (screen_signals / screen_redone);
+ *   fp64, B >= 4: the resident tier's batch in OMP mode (screen_signals, screen_resident; screen_tier2 for what it hands on);
+ *   everything else (B < 4, a trace requested, engine 3, shapes the forms refuse): one signal at a time, ss_hip_omp_solve_*.
+ */
+int ss_hip_omp_solve_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B,
+                               ptrdiff_t y_stride, ptrdiff_t incy,
+                               float tol, uint32_t max_iter,
+                               float* X, ptrdiff_t x_stride, ptrdiff_t incx,
+                               uint32_t* iter_out, double* err_out,
+                               char* err, size_t errlen);
+int ss_hip_omp_solve_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B,
+                               ptrdiff_t y_stride, ptrdiff_t incy,
+                               double tol, uint32_t max_iter,
+                               double* X, ptrdiff_t x_stride, ptrdiff_t incx,
+                               uint32_t* iter_out, double* err_out,
+                               char* err, size_t errlen);
+int ss_hip_omp_solve_batch_compact_f32(ss_hip_ctx* ctx, const float* Y, size_t B,
+                                       ptrdiff_t y_stride, ptrdiff_t incy,
+                                       float tol, uint32_t max_iter, uint32_t kmax,
+                                       void* records, char* err, size_t errlen);
+int ss_hip_omp_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, size_t B,
+                                       ptrdiff_t y_stride, ptrdiff_t incy,
+                                       double tol, uint32_t max_iter, uint32_t kmax,
+                                       void* records, char* err, size_t errlen);
 
 /*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
@@ -307,6 +348,13 @@ typedef struct ss_hip_stats {
     uint64_t screen_rescued;       /* screened signals (fp32 and fp64 resident tier) certified by the RESCUE: the first attempt declined — a planted column was ranked out
                                       of the subset — its log named the missing columns, the second attempt held them (option "screen_rescue")  */
     uint64_t screen_rescue_tried;  /* rescues attempted                                                                                  */
+    /* ABI version 7 */
+    uint64_t omp_batch_signals;    /* OMP batches (ss_hip_omp_solve_batch_*): signals a batch CHUNK certified — fp32 Gram or screened form, fp64 resident tier
+                                      (not the signals it ran one at a time, nor those it handed to the single-signal ladder)              */
+    uint64_t omp_batch_redone;     /* ... signals a chunk declined or could not certify: solved again alone by the single-signal ladder       */
+    uint64_t omp_gram_signals;     /* ... of omp_batch_signals, those certified by the Gram form (csrc/ompbatch.hip: the path on the 448-column subset
+                                      with its Gram matrix gathered from G = A^T A, every state checked against all columns by the MFMA pass
+                                      over the rows of G at the signal's support)                                                        */
 } ss_hip_stats;
 
 /* ---- IRLS: the reference's second solver (src/solvers/irls-cpu.cpp:63-124) ----------------------

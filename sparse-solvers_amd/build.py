@@ -49,6 +49,8 @@ HIP_UNITS = [
     ("screen.hip", []),
     # the resident subset solve (one workgroup, Gram values in registers): scalar bookkeeping rounds like the reference's
     ("resident.hip", ["-ffp-contract=off"]),
+    # OMP batches in the Gram form: the subset Gram matrices gathered from G, the MFMA certificate over all columns (bounds only)
+    ("ompbatch.hip", []),
 ]
 
 

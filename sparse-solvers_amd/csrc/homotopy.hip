@@ -2409,8 +2409,10 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
 }
 
 // fp64 batch, resident tier, in chunks of screen64_batch_cap() signals
+// (omp: OMP batches — ss_hip_omp_solve_batch_f64 — the same tier with k_res_solve<double, OMP> and OMP's certificate)
 int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol, uint32_t max_iter, double* X,
-                      ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax)
+                      ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax,
+                      bool omp = false)
 {
     if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
     if (!(tol >= std::numeric_limits<double>::epsilon() && tol < 1.0)) { set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1"); return SS_HIP_EINVAL; }
@@ -2432,7 +2434,7 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
             for (uint32_t b = 0; b < nb; ++b) copy_in<double>(ctx, ws.y + (size_t)b * ctx->ldm, Y + (ptrdiff_t)(b0 + b) * y_stride, incy, m);
             HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)nb * ctx->n_pad * sizeof(double), st));
             HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)nb * sizeof(DevState), st));
-            HIPCHK(launch_screen64_batch(ctx, ws, nb, tol, max_iter));
+            HIPCHK(launch_screen64_batch(ctx, ws, nb, tol, max_iter, omp));
             const unsigned char* stage = rec_out ? pack_records<double>(ctx, ws, nb, kmax) : nullptr;
             HIPCHK(hipMemcpyAsync(hst.data(), ws.st, (size_t)nb * sizeof(DevState), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -2442,6 +2444,7 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
                 if (!good) {
                     redo.push_back(b0 + b);
                     ctx->stats.screen_tier2 += 1;
+                    if (omp) ctx->stats.omp_batch_redone += 1;
                     count_reasons(ctx, hs.sub_reason, hs.tie_stall != 0 || hs.status == kStatusTieRerun);
                     continue;
                 }
@@ -2453,6 +2456,7 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
                 ctx->stats.iterations += hs.iter;
                 ctx->stats.screen_signals += 1;
                 ctx->stats.screen_resident += 1;
+                if (omp) ctx->stats.omp_batch_signals += 1;
             }
             HIPCHK(hipStreamSynchronize(st));
         }
@@ -2467,7 +2471,7 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
     for (size_t b : redo) {
         uint32_t it = 0;
         double e = 0.0;
-        Route r; r.no_res = true;                          // (the batch's resident tier has declined it: the tiers behind)
+        Route r; r.no_res = true; r.omp = omp;             // (the batch's resident tier has declined it: the tiers behind)
         const int rc = solve_impl<double>(ctx, Y + (ptrdiff_t)b * y_stride, incy, tol, max_iter, X ? X + (ptrdiff_t)b * x_stride : nullptr, incx, &it, &e, err, errlen,
                                           r, rec_out ? static_cast<unsigned char*>(rec_out) + b * rb : nullptr, kmax);
         if (rc != SS_HIP_OK) return rc;
@@ -2512,6 +2516,204 @@ int solve_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
     }
     if (B == 0) return SS_HIP_OK;
     return solve_batch_dispatch(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+}
+
+// ---- OMP batches (ss_hip_omp_solve_batch_*) --------------------------------------------------------------------------------
+// Signal b's result is what ss_hip_omp_solve_* returns for it alone (the same picks, support and iteration count; coefficients to
+// rounding).  A slot a chunk does not certify is solved again alone by the single-signal ladder, and nothing of it is written
+// before: its result is that ladder's bit for bit.
+int solve_omp_seq(ss_hip_ctx* ctx, const float* Y, const double* Yd, const size_t* sig, size_t count, ptrdiff_t y_stride, ptrdiff_t incy, double tol,
+                  uint32_t max_iter, float* X, double* Xd, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen,
+                  void* rec_out, uint32_t kmax, bool no_res)
+{
+    const size_t rb = record_bytes(kmax, Yd ? sizeof(double) : sizeof(float));
+    for (size_t i = 0; i < count; ++i) {
+        const size_t b = sig ? sig[i] : i;
+        uint32_t it = 0;
+        double e = 0.0;
+        Route r; r.omp = true; r.no_res = no_res;
+        void* rec = rec_out ? static_cast<unsigned char*>(rec_out) + b * rb : nullptr;
+        const int rc = Yd ? solve_impl<double>(ctx, Yd + (ptrdiff_t)b * y_stride, incy, tol, max_iter, Xd ? Xd + (ptrdiff_t)b * x_stride : nullptr, incx,
+                                               &it, &e, err, errlen, r, rec, kmax)
+                          : solve_impl<float>(ctx, Y + (ptrdiff_t)b * y_stride, incy, (float)tol, max_iter, X ? X + (ptrdiff_t)b * x_stride : nullptr, incx,
+                                              &it, &e, err, errlen, r, rec, kmax);
+        if (rc != SS_HIP_OK) return rc;
+        if (iter_out) iter_out[b] = it;
+        if (err_out) err_out[b] = e;
+    }
+    return SS_HIP_OK;
+}
+
+// fp32 chunks: c0 of every slot by the batch GEMM, then the Gram form (gram: ompbatch.hip, 256 slots per chunk) or the screened form in
+// OMP mode (screen.hip: launch_screen_batch, 64 slots per chunk)
+int solve_omp_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol, uint32_t max_iter, float* X,
+                        ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax,
+                        bool gram)
+{
+    using T = float;
+    const size_t rb = record_bytes(kmax, sizeof(T));
+    std::vector<size_t> redo;
+    try {
+        HIPCHK(hipSetDevice(ctx->device));
+        const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
+        const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
+        const size_t chunk = gram ? (size_t)omp_gram_cap() : (size_t)screen_batch_cap();
+        hipStream_t st = ctx->stream;
+        std::vector<DevState> hs;
+        for (size_t b0 = 0; b0 < B; b0 += chunk) {
+            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+            ensure_workspace<T>(ctx, Bc, kcap);
+            Workspace<T>& ws = *ws_of<T>(ctx);
+            TraceEntry* const trace_keep = ws.trace;
+            ws.trace = nullptr;                                  // (no trace in these forms)
+            struct RestoreTrace { Workspace<T>& w; TraceEntry* p; ~RestoreTrace() { w.trace = p; } } restore_trace{ ws, trace_keep };
+            const uint32_t rows = (Bc + 127u) / 128u * 128u;     // GEMM rows of the block
+            const size_t bp = ws.dims.b_pad;
+            T* const Rblk = ws.rhs;
+            const T* Yc = Y + (ptrdiff_t)b0 * y_stride;
+            HIPCHK(hipMemsetAsync(ws.y, 0, (size_t)Bc * ldm * sizeof(T), st));
+            if (incy == 1) {
+                HIPCHK(hipMemcpy2DAsync(ws.y, ldm * sizeof(T), Yc, (size_t)y_stride * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
+            } else {
+                for (uint32_t b = 0; b < Bc; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, Yc + (ptrdiff_t)b * y_stride, incy, m);
+            }
+            HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)Bc * np * sizeof(T), st));
+            HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)Bc * np * sizeof(T), st));
+            HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)Bc * np, st));
+            HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)Bc * sizeof(DevState), st));
+            HIPCHK(hipMemsetAsync(ws.ndone, 0, sizeof(uint32_t), st));
+            HIPCHK(hipMemsetAsync(ws.rhs, 0, 2 * bp * ldm * sizeof(T), st));
+            HIPCHK(hipMemcpyAsync(Rblk, ws.y, (size_t)Bc * ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
+            uint32_t nparts = 0;
+            HIPCHK(launch_gemm_tn_f32(ctx, Rblk, rows, (uint32_t)ldm, ws.c, (uint32_t)np, nullptr));
+            HIPCHK(launch_absmax<T>(ctx, ws, Bc, &nparts));
+            HIPCHK(launch_init<T>(ctx, ws, Bc, nparts, tol));
+            if (ctx->c0_batch_rows < bp) {
+                if (ctx->c0_batch) HIPCHK(hipFree(ctx->c0_batch));
+                ctx->c0_batch = nullptr;
+                ctx->c0_batch_rows = 0;
+                HIPCHK(hipMalloc(&ctx->c0_batch, bp * np * sizeof(T)));
+                ctx->c0_batch_rows = bp;
+            }
+            HIPCHK(hipMemcpyAsync(ctx->c0_batch, ws.c, (size_t)Bc * np * sizeof(T), hipMemcpyDeviceToDevice, st));
+            const size_t need = sub_buffer_bytes(Bc);
+            if (ctx->sub_buf_bytes < need) {
+                if (ctx->sub_buf) HIPCHK(hipFree(ctx->sub_buf));
+                ctx->sub_buf = nullptr;
+                ctx->sub_buf_bytes = 0;
+                HIPCHK(hipMalloc(&ctx->sub_buf, need));
+                ctx->sub_buf_bytes = need;
+            }
+            if (gram) HIPCHK(launch_omp_gram_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter));
+            else HIPCHK(launch_screen_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, true));
+            hs.resize(Bc);
+            HIPCHK(hipMemcpyAsync(hs.data(), ws.st, (size_t)Bc * sizeof(DevState), hipMemcpyDeviceToHost, st));
+            const unsigned char* stage = rec_out ? pack_records<T>(ctx, ws, Bc, kmax) : nullptr;
+            HIPCHK(hipStreamSynchronize(st));
+            uint32_t certified = 0;
+            for (uint32_t b = 0; b < Bc; ++b) certified += (hs[b].done && hs[b].status == 0 && hs[b].tie_stall == 0) ? 1u : 0u;
+            // (every slot certified, unit increments: the chunk's rows of X in one copy)
+            const bool whole = X != nullptr && incx == 1 && certified == Bc;
+            if (whole)
+                HIPCHK(hipMemcpy2DAsync(X + (ptrdiff_t)b0 * x_stride, (size_t)x_stride * sizeof(T), ws.x, np * sizeof(T), n * sizeof(T), Bc,
+                                        hipMemcpyDefault, st));
+            for (uint32_t b = 0; b < Bc; ++b) {
+                const bool good = hs[b].done && hs[b].status == 0 && hs[b].tie_stall == 0;
+                if (!good) {
+                    redo.push_back(b0 + b);                      // (nothing of it is written: solved again alone)
+                    count_reasons(ctx, hs[b].sub_reason, hs[b].tie_stall != 0 || hs[b].status == kStatusTieRerun);
+                    continue;
+                }
+                if (X && !whole) copy_out<T>(ctx, X + (ptrdiff_t)(b0 + b) * x_stride, incx, ws.x + (size_t)b * np, n);
+                if (rec_out) HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + (b0 + b) * rb, stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
+                if (iter_out) iter_out[b0 + b] = hs[b].iter;
+                if (err_out) err_out[b0 + b] = hs[b].c_inf;
+                ctx->stats.solves += 1;
+                ctx->stats.iterations += hs[b].iter;
+            }
+            HIPCHK(hipStreamSynchronize(st));
+            ctx->stats.omp_batch_signals += certified;
+            ctx->stats.omp_batch_redone += Bc - certified;
+            if (gram) {
+                ctx->stats.omp_gram_signals += certified;
+            } else {
+                ctx->stats.screen_signals += certified;
+                ctx->stats.screen_resident += certified;
+                ctx->stats.screen_redone += Bc - certified;
+            }
+        }
+    } catch (const HipFail& f) {
+        set_err(err, errlen, hip_msg(f));
+        return SS_HIP_ERUNTIME;
+    } catch (const std::bad_alloc&) {
+        set_err(err, errlen, "solve_batch: out of host memory");
+        return SS_HIP_ENOMEM;
+    }
+    return solve_omp_seq(ctx, Y, nullptr, redo.data(), redo.size(), y_stride, incy, tol, max_iter, X, nullptr, x_stride, incx, iter_out, err_out,
+                         err, errlen, rec_out, kmax, false);
+}
+
+// The forms an OMP batch takes, in this order: (a) fp32 from 4 signals with G = A^T A at hand, or a batch large enough to form it (the
+// Homotopy batch's rule: max(batch_gram_min, 1536) where the screened form applies): the Gram form, chunks of 256; (b) fp32 from 4 signals
+// on dictionaries the screened form takes ("batch_screen"): chunks of 64 in that form; (c) fp64 from 4 signals: the resident tier's batch;
+// (d) everything else one signal at a time through the single-signal ladder.
+int omp_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol, uint32_t max_iter, float* X,
+                       ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax)
+{
+    if (B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->screen_resident) {
+        try {
+            HIPCHK(hipSetDevice(ctx->device));
+            if (ctx->batch_gram_min > 0 && res_solve_usable<float>()) {
+                const bool scr_batches = !ctx->gram_full && ctx->batch_screen && screen_form_usable(ctx);
+                const size_t gram_min = scr_batches ? std::max<size_t>((size_t)ctx->batch_gram_min, 1536) : (size_t)ctx->batch_gram_min;
+                if ((ctx->gram_full || B >= gram_min) && ensure_full_gram(ctx) && omp_gram_usable(ctx))
+                    return solve_omp_batch_f32(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, true);
+            }
+            if (ctx->batch_screen && ctx->la_fused >= 3 && ctx->early_solo && ctx->solo_subset == 256 && res_solve_usable<float>() && screen_form_usable(ctx))
+                return solve_omp_batch_f32(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, false);
+        } catch (const HipFail& f) {
+            set_err(err, errlen, hip_msg(f));
+            return SS_HIP_ERUNTIME;
+        }
+    }
+    return solve_omp_seq(ctx, Y, nullptr, nullptr, B, y_stride, incy, tol, max_iter, X, nullptr, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax,
+                         false);
+}
+
+int omp_batch_dispatch(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol, uint32_t max_iter, double* X,
+                       ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax)
+{
+    if (B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 &&
+        ctx->res_off_solves == 0) {
+        bool usable = false;
+        try { HIPCHK(hipSetDevice(ctx->device)); usable = screen64_batch_usable(ctx); } catch (const HipFail&) { usable = false; }
+        if (usable) return solve_batch_res64(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, true);
+    }
+    return solve_omp_seq(ctx, nullptr, Y, nullptr, B, y_stride, incy, tol, max_iter, nullptr, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax,
+                         false);
+}
+
+template <typename T>
+int omp_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, T tol, uint32_t max_iter, T* X, ptrdiff_t x_stride,
+                   ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
+{
+    // (the Homotopy batch's validation, message for message)
+    if (!ctx) { set_err(err, errlen, "solve_batch: null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 0) { set_err(err, errlen, "solve_batch: this context was created for IRLS"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "solve_batch: element type mismatch"); return SS_HIP_ETYPE; }
+    if (!Y || (!X && !rec_out)) { set_err(err, errlen, "solve_batch: Y and the output must not be null"); return SS_HIP_EINVAL; }
+    if (rec_out && (kmax == 0 || kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(rec_out) & 7u))) {
+        set_err(err, errlen, "solve_batch_compact: kmax must be 1..4096 and records 8-byte aligned");
+        return SS_HIP_EINVAL;
+    }
+    if (B == 0) return SS_HIP_OK;
+    if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
+    if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) {
+        set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1");
+        return SS_HIP_EINVAL;
+    }
+    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "solve_batch: increments must be positive"); return SS_HIP_EINVAL; }
+    return omp_batch_dispatch(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
 }
 
 template <typename T>
@@ -2797,6 +2999,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     if (ctx->gram_reserved) (void)hipFree(ctx->gram_reserved);
     if (ctx->gram_full) (void)hipFree(ctx->gram_full);
     if (ctx->c0_batch) (void)hipFree(ctx->c0_batch);
+    sship::omp_gram_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);
@@ -2873,7 +3076,33 @@ int ss_hip_homotopy_solve_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
                                     iter_out, err_out, err, errlen);
 }
 
+int ss_hip_omp_solve_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol, uint32_t max_iter,
+                               float* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen)
+{
+    return omp_batch_impl<float>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen);
+}
+
+int ss_hip_omp_solve_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol, uint32_t max_iter,
+                               double* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen)
+{
+    return omp_batch_impl<double>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen);
+}
+
 size_t ss_hip_record_bytes(uint32_t kmax, int is_f64) { return record_bytes(kmax, is_f64 ? 8 : 4); }
+
+int ss_hip_omp_solve_batch_compact_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       float tol, uint32_t max_iter, uint32_t kmax, void* records, char* err, size_t errlen)
+{
+    if (!records) { set_err(err, errlen, "solve_batch_compact: records must not be null"); return SS_HIP_EINVAL; }
+    return omp_batch_impl<float>(ctx, Y, B, y_stride, incy, tol, max_iter, nullptr, 0, 1, nullptr, nullptr, err, errlen, records, kmax);
+}
+
+int ss_hip_omp_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       double tol, uint32_t max_iter, uint32_t kmax, void* records, char* err, size_t errlen)
+{
+    if (!records) { set_err(err, errlen, "solve_batch_compact: records must not be null"); return SS_HIP_EINVAL; }
+    return omp_batch_impl<double>(ctx, Y, B, y_stride, incy, tol, max_iter, nullptr, 0, 1, nullptr, nullptr, err, errlen, records, kmax);
+}
 
 int ss_hip_homotopy_solve_batch_compact_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
                                             float tol, uint32_t max_iter, uint32_t kmax, void* records, char* err, size_t errlen)

@@ -1867,8 +1867,10 @@ static size_t scr_gemm_b_lds()
 // instead of a 330-us sweep each).
 uint32_t screen_batch_cap() { return kScrBatch; }
 
-hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter)
+hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter, bool omp)
 {
+    // (omp: the batch callers make sure the resident kernel runs — k_sub_solve has no OMP statement)
+    if (omp && !(ctx->screen_resident && res_solve_usable<float>())) return hipErrorInvalidConfiguration;
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || ctx->sub_buf == nullptr || nslots == 0 || nslots > kScrBatch) return hipErrorInvalidConfiguration;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
@@ -1900,12 +1902,13 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
     if (ctx->screen_resident && res_solve_usable<float>()) {
         const ResLog<float> log{ B.hdr, nullptr, B.pcol, B.LX, B.LD };
         (void)launch_res_solve<float>(ctx, nslots, (const float*)S->b_gs, kSbS, (size_t)kSbS * kSbS, c0_all, np, (const uint32_t*)B.sub, tol, max_iter, ws.dims.kcap, log,
-                                      ws.x, np, ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap, false);
+                                      ws.x, np, ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
     } else
         (void)launch_sub_solve(ctx, ws, B, nslots, (const float*)S->b_gs, kSbS, 1, c0_all, tol, max_iter, kSbS * kSbS);
     hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u, nslots), dim3(256), 0, s, At, ldm, n, (const float*)ws.y,
                        (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
-                       (const float*)S->meta, S->b_r16, S->b_rn2p, S->b_tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, 0, (uint32_t*)nullptr);
+                       (const float*)S->meta, S->b_r16, S->b_rn2p, S->b_tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, 0, (uint32_t*)nullptr,
+                       omp ? 1 : 0);
     static const bool b_attr = [] {
         const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm_b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scr_gemm_b_lds()) == hipSuccess;
         if (!ok) (void)hipGetLastError();
@@ -2242,7 +2245,7 @@ bool screen64_batch_usable(ss_hip_ctx* ctx)
 uint32_t screen64_batch_cap() { return kS64Batch; }
 
 // the chunk's signals are in ws.y ([nslots][ldm], zero padded), x / states / lists of the slots in ws; returns with everything queued
-hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_t nslots, double tol, uint32_t max_iter)
+hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_t nslots, double tol, uint32_t max_iter, bool omp)
 {
     typedef ResCfg<double> RC;
     ScreenState* S = scr_of(ctx);
@@ -2295,9 +2298,9 @@ hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_
     { const hipError_t eg = launch_sgram64(ctx, Bq->sub, Y, Bq->gs_part, Bq->gs, Bq->c0, nslots, np); if (eg != hipSuccess) return eg; }
     const ResLog<double> log{ Bq->hdr, Bq->H, Bq->pcol, Bq->X, nullptr };
     { const hipError_t es = launch_res_solve<double>(ctx, nslots, Bq->gs, (uint32_t)RC::S, (size_t)RC::S * RC::S, Bq->c0, np, Bq->sub, tol, max_iter, ws.dims.kcap, log,
-                                                     ws.x, np, ws.gam, ws.touched, ws.st, (TraceEntry*)nullptr, 0u, false);
+                                                     ws.x, np, ws.gam, ws.touched, ws.st, (TraceEntry*)nullptr, 0u, omp);
       if (es != hipSuccess) return es; }
-    (void)launch_res_residuals64(ctx, Y, log, tol, S->meta, Bq->r16, Bq->rn2p, Bq->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, true, false, nslots,
+    (void)launch_res_residuals64(ctx, Y, log, tol, S->meta, Bq->r16, Bq->rn2p, Bq->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, true, omp, nslots,
                                  Bq->ymeta);
     for (uint32_t b = 0; b < nslots; ++b) {
         const __half* r16 = Bq->r16 + (size_t)b * kS64Rhs * ldm;

@@ -259,6 +259,8 @@ struct ss_hip_ctx {
     float* gram_reserved = nullptr;          // what that thread obtained (read after join)
     int gram_reserve = 1;
     float* c0_batch = nullptr;
+    float* omp_gs = nullptr;          // OMP batches in the Gram form (ompbatch.hip): the subset Gram matrices of a chunk
+    float* omp_norm = nullptr;        // ... and the column norms ||a_j|| (the certificate's scale)
     void* sub_buf = nullptr;          // subset form (subbatch.hip): subsets, first picks, breakpoint logs of a chunk
     size_t sub_buf_bytes = 0;
     int sub_attr_set = -1;
@@ -459,7 +461,15 @@ uint32_t screen_rescue_cap();
 // a batch chunk of nslots <= screen_batch_cap() signals in the screened form: c0 = A^T y of every slot in c0_all ([nslots][n_pad]), the
 // signals in ws.y; the slots' verdicts in their states (k_sub_finish) like the subset form's
 uint32_t screen_batch_cap();
-hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter);
+// (omp: orthogonal matching pursuit — k_res_solve<float, OMP> and the OMP certificate of k_scr_residuals: ss_hip_omp_solve_batch_f32)
+hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter, bool omp = false);
+// OMP batches in the Gram form (ompbatch.hip): the subset's Gram matrix gathered from G = A^T A, the path on it, every logged state
+// certified against all columns by k_omp_gverify (rows of G at the slot's positions, MFMA, rigorous bound on its rounding)
+bool omp_gram_usable(ss_hip_ctx* ctx);
+uint32_t omp_gram_cap();
+hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter);
+void omp_gram_free(ss_hip_ctx* ctx);
+
 void screen_free(ss_hip_ctx* ctx);
 // fp64: the path is solved by the fp64 engine on a sub-dictionary (a context of its own: the kS64Sub columns with the largest
 // |A^T y|), its states are logged (ss_hip_ctx::slog) and certified against all columns by the same fp16 pass
@@ -479,7 +489,7 @@ hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, d
 // columns, the chunk's paths run side by side, each signal's states are certified by a screening pass of its own; verdicts in the slots' states
 bool screen64_batch_usable(ss_hip_ctx* ctx);
 uint32_t screen64_batch_cap();
-hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_t nslots, double tol, uint32_t max_iter);
+hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_t nslots, double tol, uint32_t max_iter, bool omp = false);
 void screen_debug_recheck(ss_hip_ctx* ctx);               // developer aid (SS_HIP_SUB_DEBUG)
 double screen_read_headroom(ss_hip_ctx* ctx);             // largest (|c~| + eps) / bound of the last screened solve (synchronises)
 hipError_t launch_sub_form(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0, float tol, uint32_t max_iter,

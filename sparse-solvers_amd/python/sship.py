@@ -26,6 +26,8 @@ SYMBOLS = [
     "ss_hip_omp_solve_f32", "ss_hip_omp_solve_f64",
     "ss_hip_homotopy_solve_batch_f32", "ss_hip_homotopy_solve_batch_f64",
     "ss_hip_record_bytes", "ss_hip_homotopy_solve_batch_compact_f32", "ss_hip_homotopy_solve_batch_compact_f64",
+    "ss_hip_omp_solve_batch_f32", "ss_hip_omp_solve_batch_f64",
+    "ss_hip_omp_solve_batch_compact_f32", "ss_hip_omp_solve_batch_compact_f64",
     "ss_hip_gemv_t_f32", "ss_hip_gemv_t_f64", "ss_hip_gemm_t_f32", "ss_hip_gram_cols_f32", "ss_hip_gram_cols_f64",
     "ss_hip_subset_gram_f32",
     "ss_hip_reconstruct_f32", "ss_hip_reconstruct_f64", "ss_hip_norm_l1_f32", "ss_hip_norm_l1_f64",
@@ -122,6 +124,9 @@ class Stats(ctypes.Structure):
         ("res_solve_ms", ctypes.c_double),
         ("screen_rescued", ctypes.c_uint64),
         ("screen_rescue_tried", ctypes.c_uint64),
+        ("omp_batch_signals", ctypes.c_uint64),
+        ("omp_batch_redone", ctypes.c_uint64),
+        ("omp_gram_signals", ctypes.c_uint64),
     ]
 
 
@@ -158,6 +163,12 @@ def lib():
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, cp, sz]
         f = getattr(L, "ss_hip_homotopy_solve_batch_compact_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, cp, sz]
+        f = getattr(L, "ss_hip_omp_solve_batch_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, cp, sz]
+        f = getattr(L, "ss_hip_omp_solve_batch_compact_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
@@ -343,7 +354,16 @@ class Homotopy:
         self._check(rc, err)
         return out, int(it.value), float(e.value)
 
-    def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None):
+    def solve_omp_batch(self, Y, tolerance=None, max_iterations=100, out=None):
+        """OMP for every row of Y: (B, m) -> X (B, n), iters (B,), errors (B,); each row's result is solve_omp's for it
+        (include/ss_hip.h, ss_hip_omp_solve_batch_*); Y / out may live on the device"""
+        return self.solve_batch(Y, tolerance, max_iterations, out, _entry="ss_hip_omp_solve_batch_")
+
+    def solve_omp_batch_compact(self, Y, tolerance=None, max_iterations=100, kmax=96, out=None):
+        """OMP for every row of Y with compact records (the layout of solve_batch_compact)"""
+        return self.solve_batch_compact(Y, tolerance, max_iterations, kmax, out, _entry="ss_hip_omp_solve_batch_compact_")
+
+    def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None, _entry="ss_hip_homotopy_solve_batch_"):
         """Y: (B, m) -> X (B, n), iters (B,), errors (B,); Y / out may live on the device"""
         Yp, shape, strides, dt, keep = _describe(Y)
         if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
@@ -359,7 +379,7 @@ class Homotopy:
         errs = np.zeros(B, dtype=np.float64)
         err = ctypes.create_string_buffer(512)
         _sync_producers(Y, X)
-        fn = getattr(lib(), "ss_hip_homotopy_solve_batch_" + self.suffix)
+        fn = getattr(lib(), _entry + self.suffix)
         rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations),
                 Xp, xstr[0], xstr[1], iters.ctypes.data, errs.ctypes.data, err, len(err))
         self._check(rc, err)
@@ -368,7 +388,8 @@ class Homotopy:
     def record_bytes(self, kmax):
         return int(lib().ss_hip_record_bytes(int(kmax), 1 if self.dtype == np.float64 else 0))
 
-    def solve_batch_compact(self, Y, tolerance=None, max_iterations=100, kmax=96, out=None):
+    def solve_batch_compact(self, Y, tolerance=None, max_iterations=100, kmax=96, out=None,
+                            _entry="ss_hip_homotopy_solve_batch_compact_"):
         """Y: (B, m) -> records (B, record_bytes) uint8: {u32 K, u32 iter, f64 err, u32 idx[kmax], T val[kmax]}
         per signal (include/ss_hip.h), packed on the device.  `out`: a uint8 numpy array or torch tensor
         (host or device) of that shape; default a numpy array.  Decode with sharding.unpack_records."""
@@ -392,7 +413,7 @@ class Homotopy:
             raise ValueError("out must be a contiguous (B, %d) uint8 array" % rb)
         err = ctypes.create_string_buffer(512)
         _sync_producers(Y, out)
-        fn = getattr(lib(), "ss_hip_homotopy_solve_batch_compact_" + self.suffix)
+        fn = getattr(lib(), _entry + self.suffix)
         rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations), int(kmax),
                 rp, err, len(err))
         self._check(rc, err)
