@@ -27,7 +27,9 @@ extern "C" {
 #endif
 
 #define SS_HIP_ABI_VERSION 7     /* (5: the per-reason counters of round 4; 6: screen_rescued / screen_rescue_tried, the colshard _f64 entry points;
-                                    7: the OMP batch entry points and their counters) */
+                                    7: the OMP batch entry points and their counters; added under 7 since: the IRLS batch
+                                    entry points ss_hip_irls_solve_batch_*, option "irls_batch_max", and the counters
+                                    irls_batch_signals / irls_batch_rounds at the end of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -158,6 +160,7 @@ int ss_hip_homotopy_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, si
  * CONTRACT: signal b's result is what ss_hip_omp_solve_* returns for it alone — the same picks, support and
  * iteration count, coefficients equal to rounding; a signal no chunk form certifies is solved alone by the
  * single-signal ladder, and then its result is that solve's bit for bit.
+ * (The IRLS batch, ss_hip_irls_solve_batch_* below, is bit for bit for every signal: see there.)
  * Forms, in this order (ss_hip_stats::omp_batch_signals / omp_batch_redone count what the chunks of all of them certify / hand on):
  *   fp32, B >= 4, G = A^T A at hand (option "gram_full_after", or an earlier batch formed it), or B >= max("batch_gram_min", 1536)
  *         and G fits the budget: the Gram form (csrc/ompbatch.hip), chunks of 256 — c0 by the batch GEMM, every signal's path
@@ -355,6 +358,9 @@ typedef struct ss_hip_stats {
     uint64_t omp_gram_signals;     /* ... of omp_batch_signals, those certified by the Gram form (csrc/ompbatch.hip: the path on the 448-column subset
                                       with its Gram matrix gathered from G = A^T A, every state checked against all columns by the MFMA pass
                                       over the rows of G at the signal's support)                                                        */
+    /* ABI version 7, added with the IRLS batch */
+    uint64_t irls_batch_signals;   /* IRLS batches (ss_hip_irls_solve_batch_*): signals solved (each also counts in solves, its iterations in iterations) */
+    uint64_t irls_batch_rounds;    /* ... lock-step Newton rounds run by the blocked batch form (n >= 96), one host read of the live-slot count each */
 } ss_hip_stats;
 
 /* ---- IRLS: the reference's second solver (src/solvers/irls-cpu.cpp:63-124) ----------------------
@@ -376,6 +382,26 @@ int ss_hip_irls_solve_f32(ss_hip_ctx* ctx, const float* y, ptrdiff_t incy, float
 int ss_hip_irls_solve_f64(ss_hip_ctx* ctx, const double* y, ptrdiff_t incy, double tolerance, uint32_t max_iterations,
                           double* x, ptrdiff_t incx, uint32_t* iter_out, double* solution_error_out,
                           int* spd_failure_out, char* err, size_t errlen);
+/*
+ * IRLS batch (added under ABI version 7): B signals against the context's factorised matrix.  Signal b is
+ * Y[b*y_stride + i*incy], its solution X[b*x_stride + j*incx]; Y and X may be host or device pointers.  iter_out,
+ * solution_error_out and spd_failure_out (each [B], may be NULL) receive every signal's irls_report.  Validation is the
+ * single solve's: SS_HIP_EINVAL for a Homotopy context, a null Y or X, max_iterations == 0 or non-positive increments;
+ * SS_HIP_ETYPE on a dtype mismatch; B == 0 returns SS_HIP_OK and touches nothing.
+ * CONTRACT: signal b's x, iter, solution_error and spd_failure are BIT FOR BIT what ss_hip_irls_solve_* returns for it alone
+ * on the same context — for every B, every chunking (option "irls_batch_max"), both dtypes and whatever the context did
+ * before: the batch kernels (csrc/irlsbatch.hip) run the single solve's statements in its order per signal.
+ * Forms: the single solve's choice for this n — n < 96 (or SS_HIP_IRLS_FUSED): one workgroup per signal, one launch per
+ * chunk; otherwise the blocked chain with every launch covering the chunk's live signals and one host read per Newton round
+ * (ss_hip_stats::irls_batch_rounds).  A batch adds B to ss_hip_stats::solves and its iterations to iterations, as a loop of
+ * single solves would, and B to irls_batch_signals.
+ */
+int ss_hip_irls_solve_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                float tolerance, uint32_t max_iterations, float* X, ptrdiff_t x_stride, ptrdiff_t incx,
+                                uint32_t* iter_out, double* solution_error_out, int* spd_failure_out, char* err, size_t errlen);
+int ss_hip_irls_solve_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                double tolerance, uint32_t max_iterations, double* X, ptrdiff_t x_stride, ptrdiff_t incx,
+                                uint32_t* iter_out, double* solution_error_out, int* spd_failure_out, char* err, size_t errlen);
 void ss_hip_irls_destroy(ss_hip_ctx* ctx);
 
 /* ---- one signal over a COLUMN-SHARDED dictionary (csrc/colshard.hip) -------------------------------
@@ -559,6 +585,8 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *   "batch_min"      smallest fp32 batch that takes the lock-step MFMA path (default 192: below
  *                    that, one lookahead solve per signal is faster)
  *   "batch_chunk"    signals processed together by the batched path (default 4096)
+ *   "irls_batch_max" IRLS contexts: most signals one chunk of ss_hip_irls_solve_batch_* holds (default 256; 1..65535); chunks are
+ *                    also bounded by 1 GiB of per-signal state (n^2 + 5 n + 2 ldm elements each).  Never changes a result
  *   "batch_gram_min" (where the screened batch form applies — "batch_screen" — G pays later and is formed for a batch of at
  *                    least max(batch_gram_min, 1536) signals, or once the context has received 3072 signals in batches)
  *                    smallest lock-step batch that forms G = A^T A (n^2 fp32, 2 m n^2 flops once) and then

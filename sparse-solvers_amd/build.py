@@ -36,6 +36,8 @@ HIP_UNITS = [
     ("persist.hip", ["-ffp-contract=off"]),
     ("solo.hip", ["-ffp-contract=off"]),
     ("irls.hip", ["-ffp-contract=off"]),
+    # IRLS batches: irls.hip's statements per signal, so the same flags (the results are the single solve's bit for bit)
+    ("irlsbatch.hip", ["-ffp-contract=off"]),
     ("gemm.hip", []),
     ("homotopy.hip", []),
     ("utils.hip", ["-ffp-contract=off"]),

@@ -2920,6 +2920,56 @@ int irls_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t
     return SS_HIP_OK;
 }
 
+// ---- IRLS batches (irlsbatch.hip): chunks of slots, each signal's words those of irls_solve_impl for it alone ----------
+template <typename T>
+int irls_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, T tol, uint32_t max_iter,
+                    T* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, int* spd_failure,
+                    char* err, size_t errlen)
+{
+    // (the single solve's checks, in its order)
+    if (!ctx) { set_err(err, errlen, "irls_solve_batch: null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 1) { set_err(err, errlen, "irls_solve_batch: this context was not created for IRLS"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64 != (sizeof(T) == 8)) {
+        set_err(err, errlen, "irls_solve_batch: element type of the call does not match the context");
+        return SS_HIP_ETYPE;
+    }
+    if (!Y || !X) { set_err(err, errlen, "irls_solve_batch: Y and X must not be null"); return SS_HIP_EINVAL; }
+    if (max_iter == 0) { set_err(err, errlen, "irls_solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
+    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "irls_solve_batch: vector increments must be positive"); return SS_HIP_EINVAL; }
+    if (B == 0) return SS_HIP_OK;
+    try {
+        HIPCHK(hipSetDevice(ctx->device));
+        uint32_t chunk = 0;
+        HIPCHK(irls_batch_reserve<T>(ctx, B, &chunk));
+        const T *Qt, *R, *G0;
+        irls_factors<T>(ctx, &Qt, &R, &G0);
+        std::vector<IrlsResult> res(chunk);
+        for (size_t b0 = 0; b0 < B; b0 += chunk) {
+            const uint32_t nb = (uint32_t)std::min<size_t>(chunk, B - b0);
+            for (uint32_t b = 0; b < nb; ++b)
+                copy_in<T>(ctx, irls_batch_y<T>(ctx, b), Y + (ptrdiff_t)(b0 + b) * y_stride, incy, ctx->m);
+            uint64_t rounds = 0;
+            HIPCHK(irls_batch_run<T>(ctx, Qt, R, G0, nb, tol, max_iter, res.data(), &rounds));
+            for (uint32_t b = 0; b < nb; ++b)
+                copy_out<T>(ctx, X + (ptrdiff_t)(b0 + b) * x_stride, incx, irls_batch_x<T>(ctx, b), ctx->n);
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+            for (uint32_t b = 0; b < nb; ++b) {
+                if (iter_out) iter_out[b0 + b] = res[b].iter;
+                if (err_out) err_out[b0 + b] = res[b].solution_error;
+                if (spd_failure) spd_failure[b0 + b] = (int)res[b].spd_failure;
+                ctx->stats.iterations += res[b].iter;
+            }
+            ctx->stats.solves += nb;
+            ctx->stats.irls_batch_signals += nb;
+            ctx->stats.irls_batch_rounds += rounds;
+        }
+    } catch (const HipFail& f) {
+        set_err(err, errlen, hip_msg(f));
+        return SS_HIP_ERUNTIME;
+    }
+    return SS_HIP_OK;
+}
+
 }  // namespace
 
 // ---- C-ABI ----------------------------------------------------------------------------
@@ -2972,6 +3022,22 @@ int ss_hip_irls_solve_f64(ss_hip_ctx* ctx, const double* y, ptrdiff_t incy, doub
                           ptrdiff_t incx, uint32_t* iter_out, double* err_out, int* spd_failure, char* err, size_t errlen)
 {
     return irls_solve_impl<double>(ctx, y, incy, tol, max_iter, x, incx, iter_out, err_out, spd_failure, err, errlen);
+}
+
+int ss_hip_irls_solve_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol,
+                                uint32_t max_iter, float* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
+                                double* err_out, int* spd_failure_out, char* err, size_t errlen)
+{
+    return irls_batch_impl<float>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, spd_failure_out,
+                                  err, errlen);
+}
+
+int ss_hip_irls_solve_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol,
+                                uint32_t max_iter, double* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
+                                double* err_out, int* spd_failure_out, char* err, size_t errlen)
+{
+    return irls_batch_impl<double>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, spd_failure_out,
+                                   err, errlen);
 }
 
 void ss_hip_irls_destroy(ss_hip_ctx* ctx) { ss_hip_homotopy_destroy(ctx); }
@@ -3249,6 +3315,7 @@ int ss_hip_set_option(ss_hip_ctx* ctx, const char* key, long value)
     if (!std::strcmp(key, "gram_single"))   { ctx->gram_single = value ? 1 : 0; return SS_HIP_OK; }
     if (!std::strcmp(key, "gram_symmetric")) { ctx->gram_symmetric = value ? 1 : 0; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_chunk"))   { ctx->batch_chunk = (int)std::max<long>(4, value); return SS_HIP_OK; }
+    if (!std::strcmp(key, "irls_batch_max")) { ctx->irls_batch_max = (int)std::max<long>(1, std::min<long>(65535, value)); return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_single")) {
         // (setting the option also forgets what the context has learnt about its signals: the step-aside counters start again)
         ctx->screen_single = (int)std::max<long>(0, std::min<long>(2, value));
@@ -3335,6 +3402,7 @@ int ss_hip_get_option(ss_hip_ctx* ctx, const char* key, long* value)
     if (!std::strcmp(key, "gram_single"))   { *value = ctx->gram_single; return SS_HIP_OK; }
     if (!std::strcmp(key, "gram_symmetric")) { *value = ctx->gram_symmetric; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_chunk"))   { *value = ctx->batch_chunk; return SS_HIP_OK; }
+    if (!std::strcmp(key, "irls_batch_max")) { *value = ctx->irls_batch_max; return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_single")) { *value = ctx->screen_single; return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_first16")) { *value = ctx->screen_first16; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_screen"))  { *value = ctx->batch_screen; return SS_HIP_OK; }

@@ -1177,6 +1177,14 @@ hipError_t irls_solve(ss_hip_ctx* ctx, T tol, uint32_t max_iter, IrlsResult* res
 
 template <typename T> T* irls_y_buffer(ss_hip_ctx* ctx) { return state_of<T>(ctx)->vec + 5 * ctx->n + ctx->ldm; }
 template <typename T> T* irls_x_buffer(ss_hip_ctx* ctx) { return state_of<T>(ctx)->vec + 4 * ctx->n; }
+template <typename T>
+void irls_factors(ss_hip_ctx* ctx, const T** Qt, const T** R, const T** G0)
+{
+    const IrlsState<T>* S = state_of<T>(ctx);
+    *Qt = S->Qt;
+    *R = S->R;
+    *G0 = S->G0;
+}
 
 template <typename T>
 static void free_state(IrlsState<T>* S)
@@ -1191,6 +1199,7 @@ static void free_state(IrlsState<T>* S)
 
 void irls_free(ss_hip_ctx* ctx)
 {
+    irls_batch_free(ctx);
     if (!ctx->irls) return;
     if (ctx->is_f64) free_state(static_cast<IrlsState<double>*>(ctx->irls));
     else free_state(static_cast<IrlsState<float>*>(ctx->irls));
@@ -1205,5 +1214,7 @@ template float* irls_y_buffer<float>(ss_hip_ctx*);
 template double* irls_y_buffer<double>(ss_hip_ctx*);
 template float* irls_x_buffer<float>(ss_hip_ctx*);
 template double* irls_x_buffer<double>(ss_hip_ctx*);
+template void irls_factors<float>(ss_hip_ctx*, const float**, const float**, const float**);
+template void irls_factors<double>(ss_hip_ctx*, const double**, const double**, const double**);
 
 }  // namespace sship

@@ -329,6 +329,8 @@ struct ss_hip_ctx {
     void* colshard = nullptr;    // sship::ColShard* of a column-sharded context (colshard.hip): shard description, communicator, replicated active set
     int kind = 0;            // 0 = Homotopy / OMP context, 1 = IRLS context
     void* irls = nullptr;    // sship::IrlsState<T>* of an IRLS context
+    void* irls_batch = nullptr;   // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
+    int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
     int device = 0;
     int is_f64 = 0;
     size_t m = 0, n = 0;
@@ -627,7 +629,20 @@ template <typename T> hipError_t irls_factor(ss_hip_ctx* ctx);
 template <typename T> hipError_t irls_solve(ss_hip_ctx* ctx, T tol, uint32_t max_iter, IrlsResult* res_host);
 template <typename T> T* irls_y_buffer(ss_hip_ctx* ctx);
 template <typename T> T* irls_x_buffer(ss_hip_ctx* ctx);
-void irls_free(ss_hip_ctx* ctx);
+// the factorisation's device arrays: Q^T [n][ldm], R [n][n], tril(Q^T Q) [n][n]
+template <typename T> void irls_factors(ss_hip_ctx* ctx, const T** Qt, const T** R, const T** G0);
+void irls_free(ss_hip_ctx* ctx);   // (releases the batch workspace too)
+
+// ---- IRLS batches (irlsbatch.hip): every signal's words are the single solve's (irls_solve) bit for bit ----------
+// the chunk size for a batch of B signals (irls_batch_max, a byte budget, a failed allocation halves it), the workspace grown to it
+template <typename T> hipError_t irls_batch_reserve(ss_hip_ctx* ctx, size_t B, uint32_t* chunk);
+template <typename T> T* irls_batch_y(ss_hip_ctx* ctx, uint32_t slot);   // [m] contiguous
+template <typename T> T* irls_batch_x(ss_hip_ctx* ctx, uint32_t slot);   // [n] contiguous
+// one chunk of nb slots, y in irls_batch_y; x left in irls_batch_x, reports copied to res_host[nb] (stream-ordered);
+// *rounds = lock-step rounds of the blocked form (one host read each; 0 for the one-workgroup form)
+template <typename T> hipError_t irls_batch_run(ss_hip_ctx* ctx, const T* Qt, const T* R, const T* G0, uint32_t nb, T tol,
+                                                uint32_t max_iter, IrlsResult* res_host, uint64_t* rounds);
+void irls_batch_free(ss_hip_ctx* ctx);
 
 // the same pass in fp64 (v_mfma_f64_16x16x4_f64), 32 or 64 right-hand sides
 hipError_t launch_gemm32_tn_f64(const ss_hip_ctx* ctx, const uint32_t* rcols, const uint32_t* drows,

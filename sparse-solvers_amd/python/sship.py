@@ -34,7 +34,7 @@ SYMBOLS = [
     "ss_hip_set_profiling", "ss_hip_get_stats", "ss_hip_reset_stats",
     "ss_hip_set_option", "ss_hip_get_option", "ss_hip_get_trace", "ss_hip_ctx_info",
     "ss_hip_irls_create_f32", "ss_hip_irls_create_f64", "ss_hip_irls_solve_f32", "ss_hip_irls_solve_f64",
-    "ss_hip_irls_destroy",
+    "ss_hip_irls_destroy", "ss_hip_irls_solve_batch_f32", "ss_hip_irls_solve_batch_f64",
     "ss_hip_comm_unique_id", "ss_hip_homotopy_colshard_create_f32", "ss_hip_homotopy_colshard_solve_f32",
     "ss_hip_homotopy_colshard_create_f64", "ss_hip_homotopy_colshard_solve_f64",
 ]
@@ -127,6 +127,8 @@ class Stats(ctypes.Structure):
         ("omp_batch_signals", ctypes.c_uint64),
         ("omp_batch_redone", ctypes.c_uint64),
         ("omp_gram_signals", ctypes.c_uint64),
+        ("irls_batch_signals", ctypes.c_uint64),
+        ("irls_batch_rounds", ctypes.c_uint64),
     ]
 
 
@@ -187,6 +189,9 @@ def lib():
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, pd, ct, u32, vp, pd, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_double),
                       ctypes.POINTER(ctypes.c_int), cp, sz]
+        f = getattr(L, "ss_hip_irls_solve_batch_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, vp, cp, sz]
     L.ss_hip_subset_gram_f32.restype = ctypes.c_int
     L.ss_hip_subset_gram_f32.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
     L.ss_hip_record_bytes.restype = sz
@@ -662,3 +667,48 @@ class Irls:
         if rc != 0:
             raise SsHipError(rc, err.value.decode())
         return out, int(it.value), float(e.value), bool(spd.value)
+
+    def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None):
+        """Y: (B, m) -> X (B, n), iters (B,) uint32, errors (B,) float64, spd (B,) bool; each row's result is solve's for it
+        bit for bit (include/ss_hip.h, ss_hip_irls_solve_batch_*); Y / out may live on the device or be strided"""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        B = int(shape[0])
+        if tolerance is None:
+            tolerance = float(np.finfo(self.dtype).eps) * 10
+        X = np.empty((B, self.n), dtype=self.dtype) if out is None else out
+        Xp, xshape, xstr, xdt, keepx = _describe(X)
+        if xdt != self.dtype or tuple(xshape) != (B, self.n):
+            raise ValueError("out must be (B, n) of the matrix dtype")
+        iters = np.zeros(B, dtype=np.uint32)
+        errs = np.zeros(B, dtype=np.float64)
+        spd = np.zeros(B, dtype=np.intc)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(Y, X)
+        fn = getattr(lib(), "ss_hip_irls_solve_batch_" + self.suffix)
+        rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations),
+                Xp, xstr[0], xstr[1], iters.ctypes.data, errs.ctypes.data, spd.ctypes.data, err, len(err))
+        if rc != 0:
+            raise SsHipError(rc, err.value.decode())
+        return X, iters, errs, spd.astype(bool)
+
+    def reset_stats(self):
+        lib().ss_hip_reset_stats(self._h)
+
+    def stats(self):
+        s = Stats()
+        lib().ss_hip_get_stats(self._h, ctypes.byref(s))
+        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+
+    def set_option(self, key, value):
+        rc = lib().ss_hip_set_option(self._h, key.encode(), int(value))
+        if rc != 0:
+            raise SsHipError(rc, "unknown option %r" % key)
+
+    def get_option(self, key):
+        v = ctypes.c_long(0)
+        rc = lib().ss_hip_get_option(self._h, key.encode(), ctypes.byref(v))
+        if rc != 0:
+            raise SsHipError(rc, "unknown option %r" % key)
+        return int(v.value)

@@ -1,0 +1,94 @@
+"""CPU-only checks of the IRLS batch entry points (include/ss_hip.h, added under ABI version 7): the header declares them,
+the library exports them, the ctypes binding gives them the header's argument types, the statistics gain their two
+counters at the end, and the chunk option is documented.  No compute calls (no GPU here)."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "sparse-solvers_amd", "python"))
+
+IRLS_BATCH = ["ss_hip_irls_solve_batch_f32", "ss_hip_irls_solve_batch_f64"]
+
+
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as ge
+    ge.build()
+    return True
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "ss_hip.h")).read()
+
+
+def _prototype(name):
+    """the parameter types of `name` as the header declares them, in order"""
+    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
+    assert m, "%s is not declared" % name
+    params = [" ".join(p.split()) for p in m.group(1).split(",")]
+    return [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in params]
+
+
+_CTYPE = {
+    "ss_hip_ctx*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "const double*": ctypes.c_void_p, "float*": ctypes.c_void_p,
+    "double*": ctypes.c_void_p, "uint32_t*": ctypes.c_void_p, "int*": ctypes.c_void_p,
+    "char*": ctypes.c_char_p, "size_t": ctypes.c_size_t, "ptrdiff_t": ctypes.c_ssize_t, "float": ctypes.c_float, "double": ctypes.c_double,
+    "uint32_t": ctypes.c_uint32,
+}
+
+
+def test_header_declares_the_irls_batch():
+    for name, t in zip(IRLS_BATCH, ("float", "double")):
+        p = _prototype(name)
+        assert p == ["ss_hip_ctx*", "const %s*" % t, "size_t", "ptrdiff_t", "ptrdiff_t", t, "uint32_t", "%s*" % t, "ptrdiff_t",
+                     "ptrdiff_t", "uint32_t*", "double*", "int*", "char*", "size_t"], (name, p)
+
+
+def test_library_exports_the_irls_batch(built):
+    import sship
+    L = ctypes.CDLL(sship.LIB_PATH)
+    for name in IRLS_BATCH:
+        assert hasattr(L, name), name
+        assert name in sship.SYMBOLS
+
+
+def test_binding_argtypes_match_the_header(built):
+    import sship
+    L = sship.lib()
+    for name in IRLS_BATCH:
+        want = [_CTYPE[p] for p in _prototype(name)]
+        got = list(getattr(L, name).argtypes)
+        # (pointers to the uint32 / double / int outputs are bound as void pointers: numpy addresses are passed)
+        assert len(got) == len(want), name
+        for g, w in zip(got, want):
+            assert g == w or (w is ctypes.c_void_p and issubclass(g, (ctypes.c_void_p, ctypes._Pointer))), (name, g, w)
+        assert getattr(L, name).restype == ctypes.c_int
+
+
+def test_python_surface_has_the_irls_batch():
+    import sship
+    for meth in ("solve_batch", "set_option", "get_option", "stats", "reset_stats"):
+        assert callable(getattr(sship.Irls, meth, None)), meth
+
+
+def test_irls_batch_counters_end_the_statistics():
+    hdr = _header()
+    body = hdr[hdr.index("typedef struct ss_hip_stats"):hdr.index("} ss_hip_stats;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(uint64_t|double|uint32_t|float)\s+([a-z0-9_]+)\s*;", body)
+    assert fields[-2:] == [("uint64_t", "irls_batch_signals"), ("uint64_t", "irls_batch_rounds")]
+    import sship
+    assert [f[0] for f in sship.Stats._fields_[-2:]] == ["irls_batch_signals", "irls_batch_rounds"]
+
+
+def test_irls_batch_max_is_documented():
+    assert '"irls_batch_max"' in _header()
+    src = open(os.path.join(ROOT, "sparse-solvers_amd", "csrc", "homotopy.hip")).read()
+    body = src[src.index("int ss_hip_set_option"):src.index("int ss_hip_get_option")]
+    assert 'strcmp(key, "irls_batch_max")' in body
