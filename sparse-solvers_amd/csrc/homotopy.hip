@@ -57,6 +57,22 @@ std::string hip_msg(const HipFail& f)
     return std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what;
 }
 
+// Runs `body` (which returns a status) and turns what it throws into the C-ABI's codes: a failed HIP call (HIPCHK) into
+// SS_HIP_ERUNTIME with the call's text, std::bad_alloc into SS_HIP_ENOMEM with "<prefix>: out of host memory".
+template <typename F>
+int guarded(char* err, size_t errlen, const char* prefix, F&& body)
+{
+    try {
+        return body();
+    } catch (const HipFail& f) {
+        set_err(err, errlen, hip_msg(f));
+        return SS_HIP_ERUNTIME;
+    } catch (const std::bad_alloc&) {
+        set_err(err, errlen, std::string(prefix) + ": out of host memory");
+        return SS_HIP_ENOMEM;
+    }
+}
+
 template <typename T>
 Workspace<T>* ws_of(ss_hip_ctx* ctx) { return static_cast<Workspace<T>*>(ctx->ws); }
 
@@ -801,19 +817,79 @@ hipEvent_t prof_event(ss_hip_ctx* ctx, size_t i)
     return ctx->prof_events[i];
 }
 
+// Grow-only device buffer: `have` and `need` count units of `unit_bytes`.  A buffer that is too small is freed and allocated anew
+// (its contents are not kept); pointer and size are left null / 0 when the new allocation fails.  try_grow_device returns the
+// allocation's error instead of throwing it (a failed hipFree throws in both).
+template <typename P, typename N>
+hipError_t try_grow_device(P*& ptr, N& have, size_t need, size_t unit_bytes)
+{
+    if (have >= need) return hipSuccess;
+    if (ptr) HIPCHK(hipFree(ptr));
+    ptr = nullptr;
+    have = 0;
+    const hipError_t e = hipMalloc(&ptr, need * unit_bytes);
+    if (e == hipSuccess) have = (N)need;
+    else ptr = nullptr;
+    return e;
+}
+template <typename P, typename N>
+void grow_device(P*& ptr, N& have, size_t need, size_t unit_bytes, const char* what)
+{
+    const hipError_t e = try_grow_device(ptr, have, need, unit_bytes);
+    if (e != hipSuccess) throw HipFail{ e, what };
+}
+
+// The trace buffer for the extent of a solve or a chunk: room for `want` entries, or — want = 0 — hidden from the kernels, which
+// then skip their stores.  The workspace gets its pointer back when the window goes out of scope.
+template <typename T>
+struct TraceWindow {
+    Workspace<T>& ws;
+    TraceEntry* keep;
+    TraceWindow(Workspace<T>& w, uint32_t want) : ws(w)
+    {
+        grow_device(ws.trace, ws.trace_cap, want, sizeof(TraceEntry), "hipMalloc(trace)");
+        keep = ws.trace;
+        if (want == 0u) ws.trace = nullptr;
+    }
+    ~TraceWindow() { ws.trace = keep; }
+    TraceWindow(const TraceWindow&) = delete;
+    TraceWindow& operator=(const TraceWindow&) = delete;
+};
+
+// the traced path of a solve that took `iter` iterations into ctx->last_trace (entry 0 = the initial pick, entry t = the toggle of iteration t)
+template <typename T>
+void fetch_trace(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t iter)
+{
+    const size_t cnt = std::min<size_t>((size_t)iter + 1, ws.trace_cap);
+    ctx->last_trace.resize(cnt);
+    HIPCHK(hipMemcpy(ctx->last_trace.data(), ws.trace, cnt * sizeof(TraceEntry), hipMemcpyDeviceToHost));
+}
+
+// The lookahead wait of the round loops: round `round` is queued once the device has reached round - L (host_flags[0]) or the
+// stream has drained.  false: the device raised `done` (host_flags[1]) — leave the loop.
+inline bool wait_round(ss_hip_ctx* ctx, uint64_t round, uint32_t L, const char* what)
+{
+    if (round <= L) return true;
+    volatile uint32_t* hf = ctx->host_flags;
+    const uint32_t need = (uint32_t)(round - L);
+    uint32_t spins = 0;
+    while (hf[1] == 0 && hf[0] < need) {
+        if ((++spins & 0x3ffu) == 0) {
+            const hipError_t q = hipStreamQuery(ctx->stream);
+            if (q == hipSuccess) break;               // queue drained
+            if (q != hipErrorNotReady) throw HipFail{ q, what };
+        }
+        std::this_thread::yield();
+    }
+    return hf[1] == 0;
+}
+
 // compact output: pack the records of `nslots` finished slots into the context's staging buffer (device)
 template <typename T>
 unsigned char* pack_records(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nslots, uint32_t kmax)
 {
     const size_t rb = record_bytes(kmax, sizeof(T));
-    const size_t need = rb * nslots;
-    if (ctx->rec_stage_bytes < need) {
-        if (ctx->rec_stage) HIPCHK(hipFree(ctx->rec_stage));
-        ctx->rec_stage = nullptr;
-        ctx->rec_stage_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->rec_stage, need));
-        ctx->rec_stage_bytes = need;
-    }
+    grow_device(ctx->rec_stage, ctx->rec_stage_bytes, rb * nslots, 1, "hipMalloc(rec_stage)");
     hipLaunchKernelGGL((k_pack_records<T>), dim3(nslots), dim3(256), 0, ctx->stream, (const T*)ws.x, (const uint32_t*)ws.gam,
                        (const uint32_t*)ws.touched, (const DevState*)ws.st, ws.dims, ctx->zero_on_removal ? 0 : 1, kmax,
                        ctx->rec_stage, rb);
@@ -824,14 +900,7 @@ unsigned char* pack_records(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nslots, 
 // one signal in the subset form (subbatch.hip) when G = A^T A is at hand: c0 is in ws.c0
 inline hipError_t sub_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter)
 {
-    const size_t need = sub_buffer_bytes(1);
-    if (ctx->sub_buf_bytes < need) {
-        if (ctx->sub_buf) HIPCHK(hipFree(ctx->sub_buf));
-        ctx->sub_buf = nullptr;
-        ctx->sub_buf_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->sub_buf, need));
-        ctx->sub_buf_bytes = need;
-    }
+    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
     return launch_sub_form(ctx, ws, 1, ws.c0, tol, max_iter);
 }
 inline hipError_t sub_single(ss_hip_ctx*, Workspace<double>&, double, uint32_t) { return hipErrorInvalidConfiguration; }
@@ -840,14 +909,7 @@ inline hipError_t sub_single(ss_hip_ctx*, Workspace<double>&, double, uint32_t) 
 inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, hipEvent_t e0, hipEvent_t e1,
                              hipEvent_t e2, hipEvent_t e3, hipEvent_t e4, hipEvent_t e5, bool omp, bool rescue)
 {
-    const size_t need = sub_buffer_bytes(1);
-    if (ctx->sub_buf_bytes < need) {
-        if (ctx->sub_buf) HIPCHK(hipFree(ctx->sub_buf));
-        ctx->sub_buf = nullptr;
-        ctx->sub_buf_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->sub_buf, need));
-        ctx->sub_buf_bytes = need;
-    }
+    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
     if (ctx->sub_dbg == nullptr && std::getenv("SS_HIP_SUB_STAMPS")) {
         HIPCHK(hipMalloc(&ctx->sub_dbg, 16 * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(ctx->sub_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
@@ -990,23 +1052,10 @@ void pump_rounds(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bo
 {
     hipStream_t st = ctx->stream;
     const uint32_t L = (uint32_t)std::max(1, std::min(ctx->lookahead, 64));
-    volatile uint32_t* hf = ctx->host_flags;
     const uint64_t last_round = (uint64_t)max_iter + 1;
     size_t& nprof = ps.nprof;
     for (uint64_t round = 1; round <= last_round; ++round) {
-        if (round > L) {
-            const uint32_t need = (uint32_t)(round - L);
-            uint32_t spins = 0;
-            while (hf[1] == 0 && hf[0] < need) {
-                if ((++spins & 0x3ffu) == 0) {
-                    const hipError_t q = hipStreamQuery(st);
-                    if (q == hipSuccess) break;               // queue drained
-                    if (q != hipErrorNotReady) throw HipFail{ q, "hipStreamQuery(solve loop)" };
-                }
-                std::this_thread::yield();
-            }
-            if (hf[1] != 0) break;
-        }
+        if (!wait_round(ctx, round, L, "hipStreamQuery(solve loop)")) break;
         if (la) {
             // the launch is a no-op unless a column without cached Gram column enters: time
             // every `profile_every`-th launch and keep the ones that did work (see below)
@@ -1337,6 +1386,21 @@ int solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
                ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen,
                Route route = Route(), void* rec_out = nullptr, uint32_t kmax = 0);
 
+// The preconditions the reference asserts on a solve's arguments (homotopy-cpu.cpp:193-199, irls-cpu.cpp:78), in the order every
+// entry point reports them: max_iterations, then the tolerance (with_tol: IRLS takes any), then the increments.  `prefix` names
+// the entry point in the message.
+template <typename T>
+int check_solve_args(const char* prefix, uint32_t max_iter, T tol, bool with_tol, ptrdiff_t incy, ptrdiff_t incx, char* err, size_t errlen)
+{
+    const char* what = nullptr;
+    if (max_iter == 0) what = ": max_iterations must be > 0";
+    else if (with_tol && !(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) what = ": tolerance must satisfy eps <= tolerance < 1";
+    else if (incy <= 0 || incx <= 0) what = ": vector increments must be positive";
+    if (!what) return SS_HIP_OK;
+    set_err(err, errlen, std::string(prefix) + what);
+    return SS_HIP_EINVAL;
+}
+
 // One attempt.  Returns the status of the solve, or — with *again set — the route of the next attempt in *next.
 template <typename T>
 int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_iter, T* x,
@@ -1345,7 +1409,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
 {
     const bool omp = route.omp, force_residual = route.force_residual, no_solo = route.no_solo;
     auto retry = [&](const Route& r) { *next = r; *again = true; return SS_HIP_OK; };
-    try {
+    return guarded(err, errlen, "solve", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(
@@ -1354,19 +1418,10 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         Workspace<T>& ws = *ws_of<T>(ctx);
         hipStream_t st = ctx->stream;
         const uint32_t want_trace = ctx->tracing ? (uint32_t)std::min<uint64_t>((uint64_t)max_iter + 2, 1u << 20) : 0u;
-        if (want_trace > ws.trace_cap) {
-            if (ws.trace) HIPCHK(hipFree(ws.trace));
-            ws.trace = nullptr;
-            ws.trace_cap = 0;
-            HIPCHK(hipMalloc(&ws.trace, (size_t)want_trace * sizeof(TraceEntry)));
-            ws.trace_cap = want_trace;
-        }
+        TraceWindow<T> trace_window(ws, want_trace);
         // (OMP does not write entry 0 — it has no initial pick —: a traced solve starts from zeros, not from whatever an earlier
         // allocation left in the buffer, so that a context's trace does not depend on its history)
         if (ctx->tracing) HIPCHK(hipMemsetAsync(ws.trace, 0, (size_t)want_trace * sizeof(TraceEntry), st));
-        TraceEntry* const trace_keep = ws.trace;
-        if (!ctx->tracing) ws.trace = nullptr;          // kernels skip the stores
-        struct Restore { Workspace<T>& w; TraceEntry* p; ~Restore() { w.trace = p; } } restore{ ws, trace_keep };
         // (option profile_solve_every = k: with profiling on, only every k-th solve carries the HIP events — each costs
         // stream time, ~0.07 ms per solve in all at 8192 x 65536)
         const bool prof = ctx->profiling != 0 && (ctx->profile_solve_every <= 1 || (ctx->prof_solve_tick++ % (uint64_t)ctx->profile_solve_every) == 0);
@@ -1668,12 +1723,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             }
         }
         ctx->last_trace.clear();
-        if (ctx->tracing && ws.trace) {
-            // entry 0 = the initial pick, entry t = the toggle of iteration t
-            const size_t cnt = std::min<size_t>((size_t)hs.iter + 1, ws.trace_cap);
-            ctx->last_trace.resize(cnt);
-            HIPCHK(hipMemcpy(ctx->last_trace.data(), ws.trace, cnt * sizeof(TraceEntry), hipMemcpyDeviceToHost));
-        }
+        if (ctx->tracing && ws.trace) fetch_trace(ctx, ws, hs.iter);
 
         ctx->stats.solves += 1;
         ctx->single_solves += 1;
@@ -1693,14 +1743,8 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         if (la || la_omp) ctx->stats.lookahead_sweeps += hs.nsweeps;
         if (ro) ctx->stats.ro_resweeps += hs.nsweeps;
         if (prof) account_profile<T>(ctx, nprof, scr_launches, hs);
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "solve: out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 // The solve: validate once, then attempts until one of them reports (at most one per rung of the ladder: every retry sets a
@@ -1717,16 +1761,7 @@ int solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         return SS_HIP_ETYPE;
     }
     if (!y || (!x && !rec_out)) { set_err(err, errlen, "solve: y and x must not be null"); return SS_HIP_EINVAL; }
-    // preconditions the reference asserts (homotopy-cpu.cpp:193-199)
-    if (max_iter == 0) { set_err(err, errlen, "solve: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) {
-        set_err(err, errlen, "solve: tolerance must satisfy eps <= tolerance < 1");
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || incx <= 0) {
-        set_err(err, errlen, "solve: vector increments must be positive");
-        return SS_HIP_EINVAL;
-    }
+    if (const int rc = check_solve_args<T>("solve", max_iter, tol, true, incy, incx, err, errlen)) return rc;
     // (a retry in the plain speculative form runs — with everything it may fall back to in turn — with option early_solo off)
     struct EarlyKeep { ss_hip_ctx* c; int keep; bool on = false; ~EarlyKeep() { if (on) c->early_solo = keep; } } early_keep{ ctx, ctx->early_solo };
     for (int attempt = 0; attempt < 16; ++attempt) {
@@ -1745,10 +1780,9 @@ int solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
 // Per round the 2*B correlation GEMVs are two MFMA GEMMs ([c] = R·Atᵀ, [q] = P·Atᵀ, gemm.hip);
 // the active-set tail runs for all signals at once (grid.y = slot).  A signal that has
 // terminated turns its kernels into no-ops; the solve ends when every slot is done.
-// the full Gram matrix G = A^T A for the batched Gram form: one GEMM of 2 m n^2 flops on the MFMA units
-// (0.55 s at C2), kept in the context for later batches; false if it does not fit the budget
-// G's memory ahead of time, on a helper thread (ss_hip_ctx::gram_reserve_thread): started by the first batch of >= 4 signals a
-// context receives, where G would fit the budget and is at most an eighth of the device's memory
+
+// Reserves the memory of G = A^T A ahead of time, on a helper thread (ss_hip_ctx::gram_reserve_thread): started by the first batch
+// of >= 4 signals a context receives, where G would fit the budget and is at most an eighth of the device's memory.
 void gram_reserve_start(ss_hip_ctx* ctx, size_t B)
 {
     if (!ctx->gram_reserve || ctx->gram_full || ctx->gram_reserve_thread || B < 4 || ctx->engine < 1 || ctx->batch_gram_min <= 0) return;
@@ -1768,6 +1802,8 @@ void gram_reserve_start(ss_hip_ctx* ctx, size_t B)
     ctx->gram_reserve_thread = th;
 }
 
+// The full Gram matrix G = A^T A for the batched Gram form: one GEMM of 2 m n^2 flops on the MFMA units (0.55 s at C2), kept in
+// the context for later batches.  false if it does not fit the budget.
 bool ensure_full_gram(ss_hip_ctx* ctx)
 {
     if (ctx->gram_full) return true;
@@ -1854,22 +1890,137 @@ bool ensure_bcol(ss_hip_ctx* ctx, size_t per, uint32_t max_iter)
     return true;
 }
 
+// ---- what the batch drivers share --------------------------------------------------------------------------------------------
+// What a batch entry point received.  Signal g is y(g); its outputs are x(g) (null without X), rec(g) (null without compact
+// records) and report(g, ...).
+template <typename T>
+struct BatchCall {
+    const T* Y;
+    size_t B;
+    ptrdiff_t y_stride, incy;
+    T tol;
+    uint32_t max_iter;
+    T* X;
+    ptrdiff_t x_stride, incx;
+    uint32_t* iter_out;
+    double* err_out;
+    char* err;
+    size_t errlen;
+    void* rec_out;
+    uint32_t kmax;
+
+    const T* y(size_t g) const { return Y + (ptrdiff_t)g * y_stride; }
+    T* x(size_t g) const { return X ? X + (ptrdiff_t)g * x_stride : nullptr; }
+    unsigned char* rec(size_t g) const { return rec_out ? static_cast<unsigned char*>(rec_out) + g * record_bytes(kmax, sizeof(T)) : nullptr; }
+    void report(size_t g, uint32_t iter, double e) const
+    {
+        if (iter_out) iter_out[g] = iter;
+        if (err_out) err_out[g] = e;
+    }
+};
+
+// The argument checks of a Homotopy / OMP batch entry, in the order they are reported: null context, a context made for IRLS, the
+// element type (SS_HIP_ETYPE; every other one is SS_HIP_EINVAL), null Y or no output, kmax and the alignment of the records; then,
+// for a batch that has signals (B = 0 is SS_HIP_OK and nothing to do), max_iterations, the tolerance and the increments.
+// (The _compact entry points report null records before any of these.)
+template <typename T>
+int check_batch_call(const ss_hip_ctx* ctx, const BatchCall<T>& c)
+{
+    if (!ctx) { set_err(c.err, c.errlen, "solve_batch: null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 0) { set_err(c.err, c.errlen, "solve_batch: this context was created for IRLS"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(c.err, c.errlen, "solve_batch: element type mismatch"); return SS_HIP_ETYPE; }
+    if (!c.Y || (!c.X && !c.rec_out)) { set_err(c.err, c.errlen, "solve_batch: Y and the output must not be null"); return SS_HIP_EINVAL; }
+    if (c.rec_out && (c.kmax == 0 || c.kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(c.rec_out) & 7u))) {
+        set_err(c.err, c.errlen, "solve_batch_compact: kmax must be 1..4096 and records 8-byte aligned");
+        return SS_HIP_EINVAL;
+    }
+    if (c.B == 0) return SS_HIP_OK;
+    return check_solve_args<T>("solve_batch", c.max_iter, c.tol, true, c.incy, c.incx, c.err, c.errlen);
+}
+
+// Signal g of a batch alone, through solve_impl with this route; its outputs go to index g.  (solve_impl sets `err` itself.)
+template <typename T>
+int solve_alone(ss_hip_ctx* ctx, const BatchCall<T>& c, size_t g, const Route& route)
+{
+    uint32_t it = 0;
+    double e = 0.0;
+    const int rc = solve_impl<T>(ctx, c.y(g), c.incy, c.tol, c.max_iter, c.x(g), c.incx, &it, &e, c.err, c.errlen, route, c.rec(g), c.kmax);
+    if (rc == SS_HIP_OK) c.report(g, it, e);
+    return rc;
+}
+
+// Signals b0 .. b0 + Bc - 1 into the rows of ws.y: one 2-D copy when their elements are contiguous, else row by row
+template <typename T>
+void upload_chunk(ss_hip_ctx* ctx, Workspace<T>& ws, const BatchCall<T>& c, size_t b0, uint32_t Bc)
+{
+    const size_t m = ctx->m, ldm = ctx->ldm;
+    if (c.incy == 1) {
+        HIPCHK(hipMemcpy2DAsync(ws.y, ldm * sizeof(T), c.y(b0), (size_t)c.y_stride * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, ctx->stream));
+    } else {
+        for (uint32_t b = 0; b < Bc; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, c.y(b0 + b), c.incy, m);
+    }
+}
+
+// ... and the rows of ws.x to the caller's X (which must not be null), the same way
+template <typename T>
+void download_chunk(ss_hip_ctx* ctx, Workspace<T>& ws, const BatchCall<T>& c, size_t b0, uint32_t Bc)
+{
+    const size_t n = ctx->n, np = ctx->n_pad;
+    if (c.incx == 1) {
+        HIPCHK(hipMemcpy2DAsync(c.x(b0), (size_t)c.x_stride * sizeof(T), ws.x, np * sizeof(T), n * sizeof(T), Bc, hipMemcpyDefault, ctx->stream));
+    } else {
+        for (uint32_t b = 0; b < Bc; ++b) copy_out<T>(ctx, c.x(b0 + b), c.incx, ws.x + (size_t)b * np, n);
+    }
+}
+
+// The start of a chunk of Bc signals (already in ws.y) in the fp32 forms that take c0 from the batch GEMM: the slots' state
+// cleared, Rblk = y, c_b = A^T y_b for every signal (residual_vector with x = 0, homotopy-cpu.cpp:215), the first picks.
+// Returns the number of partials of the absmax pass.  time_c0: the events ev_c0a / ev_c0b around the GEMM.
+inline uint32_t begin_gemm_chunk(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t Bc, float tol, bool time_c0)
+{
+    using T = float;
+    hipStream_t st = ctx->stream;
+    const size_t ldm = ctx->ldm, np = ctx->n_pad, bp = ws.dims.b_pad;
+    const uint32_t rows = (Bc + 127u) / 128u * 128u;          // GEMM rows of the block
+    HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)Bc * np * sizeof(T), st));
+    HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)Bc * np * sizeof(T), st));
+    HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)Bc * np, st));
+    HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)Bc * sizeof(DevState), st));
+    HIPCHK(hipMemsetAsync(ws.ndone, 0, sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(ws.rhs, 0, 2 * bp * ldm * sizeof(T), st));
+    HIPCHK(hipMemcpyAsync(ws.rhs, ws.y, (size_t)Bc * ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
+    uint32_t nparts = 0;
+    if (time_c0 && !ctx->ev_c0a) { HIPCHK(hipEventCreate(&ctx->ev_c0a)); HIPCHK(hipEventCreate(&ctx->ev_c0b)); }
+    if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0a, st));
+    HIPCHK(launch_gemm_tn_f32(ctx, ws.rhs, rows, (uint32_t)ldm, ws.c, (uint32_t)np, nullptr));
+    if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0b, st));
+    HIPCHK(launch_absmax<T>(ctx, ws, Bc, &nparts));
+    HIPCHK(launch_init<T>(ctx, ws, Bc, nparts, tol));
+    return nparts;
+}
+
+// What a slot of a lock-step chunk reported: it must have terminated, with a clean status
+inline int check_slot_status(const DevState& hs, char* err, size_t errlen)
+{
+    if (!hs.done) { set_err(err, errlen, "solve_batch: internal error, a signal did not terminate"); return SS_HIP_ERUNTIME; }
+    if (hs.status != 0) {
+        set_err(err, errlen, hs.status == SS_HIP_ECAPACITY ? "solve_batch: active set outgrew the workspace capacity"
+                                                           : "solve_batch: internal error, a device-side wait expired");
+        return (int)hs.status;
+    }
+    return SS_HIP_OK;
+}
+
 // Several signals in the reference-order engine at once (reforder.hip): up to ro_slots_max() of them share every pass
 // over A — the sweep carries [r, p] of each — and run in lock-step like the batched forms; each signal's words are
 // exactly those of a solve on its own (the slots share nothing but the dictionary tile in LDS).  Used for a batch's tie
-// re-runs and for batches in engine 3.  sig: the signals' indices into Y / X / the outputs (nullptr: 0 .. count-1).
+// re-runs and for batches in engine 3.  sig: the `count` signals' indices into the call (nullptr: 0 .. count-1).
 template <typename T>
-int solve_batch_ro(ss_hip_ctx* ctx, const T* Y, const size_t* sig, size_t count, ptrdiff_t y_stride, ptrdiff_t incy, T tol,
-                   uint32_t max_iter, T* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out,
-                   char* err, size_t errlen, void* rec_out, uint32_t kmax)
+int solve_batch_ro(ss_hip_ctx* ctx, const BatchCall<T>& c, const size_t* sig, size_t count)
 {
-    if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) {
-        set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1");
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "solve_batch: increments must be positive"); return SS_HIP_EINVAL; }
-    try {
+    const T tol = c.tol;
+    const uint32_t max_iter = c.max_iter;
+    return guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
@@ -1883,21 +2034,12 @@ int solve_batch_ro(ss_hip_ctx* ctx, const T* Y, const size_t* sig, size_t count,
             ensure_workspace<T>(ctx, Rg, kcap);
             Workspace<T>& ws = *ws_of<T>(ctx);
             const uint32_t want_trace = (ctx->tracing && gidx(0) == 0) ? (uint32_t)std::min<uint64_t>((uint64_t)max_iter + 2, 1u << 20) : 0u;
-            if (want_trace > ws.trace_cap) {
-                if (ws.trace) HIPCHK(hipFree(ws.trace));
-                ws.trace = nullptr;
-                ws.trace_cap = 0;
-                HIPCHK(hipMalloc(&ws.trace, (size_t)want_trace * sizeof(TraceEntry)));
-                ws.trace_cap = want_trace;
-            }
-            TraceEntry* const trace_keep = ws.trace;
-            if (want_trace == 0u) ws.trace = nullptr;
-            struct RestoreTrace { Workspace<T>& w; TraceEntry* p; ~RestoreTrace() { w.trace = p; } } restore_trace{ ws, trace_keep };
+            TraceWindow<T> trace_window(ws, want_trace);
 
             ctx->host_flags[0] = 0;
             ctx->host_flags[1] = 0;
             HIPCHK(hipMemsetAsync(ws.y, 0, (size_t)Rg * ldm * sizeof(T), st));
-            for (uint32_t b = 0; b < R; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, Y + (ptrdiff_t)gidx(b) * y_stride, incy, m);
+            for (uint32_t b = 0; b < R; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, c.y(gidx(b)), c.incy, m);
             HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)R * np * sizeof(T), st));
             HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)R * np * sizeof(T), st));
             HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)R * np, st));
@@ -1915,83 +2057,46 @@ int solve_batch_ro(ss_hip_ctx* ctx, const T* Y, const size_t* sig, size_t count,
                                       ws.st, false));
             HIPCHK(launch_ro_init<T>(ctx, ws, R, nparts, tol));
             const uint32_t L = (uint32_t)std::max(1, std::min(ctx->lookahead, 64));
-            volatile uint32_t* hf = ctx->host_flags;
             const uint64_t last_round = (uint64_t)max_iter + 1;
             for (uint64_t round = 1; round <= last_round; ++round) {
-                if (round > L) {
-                    const uint32_t need = (uint32_t)(round - L);
-                    uint32_t spins = 0;
-                    while (hf[1] == 0 && hf[0] < need) {
-                        if ((++spins & 0x3ffu) == 0) {
-                            const hipError_t q = hipStreamQuery(st);
-                            if (q == hipSuccess) break;
-                            if (q != hipErrorNotReady) throw HipFail{ q, "hipStreamQuery(reference-order batch loop)" };
-                        }
-                        std::this_thread::yield();
-                    }
-                    if (hf[1] != 0) break;
-                }
+                if (!wait_round(ctx, round, L, "hipStreamQuery(reference-order batch loop)")) break;
                 HIPCHK(launch_ro_round<T>(ctx, ws, R, (uint32_t)round, nparts, tol, max_iter));
             }
             hs.resize(R);
             HIPCHK(hipMemcpyAsync(hs.data(), ws.st, (size_t)R * sizeof(DevState), hipMemcpyDeviceToHost, st));
-            if (rec_out) {
-                const size_t rb = record_bytes(kmax, sizeof(T));
-                const unsigned char* stage = pack_records<T>(ctx, ws, R, kmax);
-                for (uint32_t b = 0; b < R; ++b)
-                    HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + gidx(b) * rb, stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
+            if (c.rec_out) {
+                const size_t rb = record_bytes(c.kmax, sizeof(T));
+                const unsigned char* stage = pack_records<T>(ctx, ws, R, c.kmax);
+                for (uint32_t b = 0; b < R; ++b) HIPCHK(hipMemcpyAsync(c.rec(gidx(b)), stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
             }
-            if (X)
-                for (uint32_t b = 0; b < R; ++b) copy_out<T>(ctx, X + (ptrdiff_t)gidx(b) * x_stride, incx, ws.x + (size_t)b * np, n);
+            if (c.X)
+                for (uint32_t b = 0; b < R; ++b) copy_out<T>(ctx, c.x(gidx(b)), c.incx, ws.x + (size_t)b * np, n);
             HIPCHK(hipStreamSynchronize(st));
-            if (want_trace != 0u && ws.trace) {
-                const size_t cnt = std::min<size_t>((size_t)hs[0].iter + 1, ws.trace_cap);
-                ctx->last_trace.resize(cnt);
-                HIPCHK(hipMemcpy(ctx->last_trace.data(), ws.trace, cnt * sizeof(TraceEntry), hipMemcpyDeviceToHost));
-            }
+            if (want_trace != 0u && ws.trace) fetch_trace(ctx, ws, hs[0].iter);
             for (uint32_t b = 0; b < R; ++b) {
-                if (!hs[b].done) { set_err(err, errlen, "solve_batch: internal error, a signal did not terminate"); return SS_HIP_ERUNTIME; }
-                if (hs[b].status != 0) {
-                    set_err(err, errlen, hs[b].status == SS_HIP_ECAPACITY ? "solve_batch: active set outgrew the workspace capacity"
-                                                                          : "solve_batch: internal error, a device-side wait expired");
-                    return (int)hs[b].status;
-                }
-                if (iter_out) iter_out[gidx(b)] = hs[b].iter;
-                if (err_out) err_out[gidx(b)] = hs[b].c_inf;
+                if (const int rc = check_slot_status(hs[b], c.err, c.errlen)) return rc;
+                c.report(gidx(b), hs[b].iter, hs[b].c_inf);
                 ctx->stats.iterations += hs[b].iter;
                 ctx->stats.ro_resweeps += hs[b].nsweeps;
             }
             ctx->stats.solves += R;
         }
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "solve_batch: out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
-// `gram`: Gram form — the correlations of every signal come from rows of G = A^T A
-// (c = c0 - sum_j x_j G[j], q = sum_j d_j G[j]) instead of two GEMMs per round
-int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
-                         float tol, uint32_t max_iter, float* X, ptrdiff_t x_stride, ptrdiff_t incx,
-                         uint32_t* iter_out, double* err_out, char* err, size_t errlen, int form = 0,
-                         void* rec_out = nullptr, uint32_t kmax = 0, bool no_subset = false)
+// form: 0 = two GEMMs per round (residual form), 1 = Gram form on the full G = A^T A — the correlations of every signal come from
+// rows of G (c = c0 - sum_j x_j G[j], q = sum_j d_j G[j]) instead of two GEMMs per round —, 2 = column form: Gram form on a cache
+// of the entering columns' Gram columns, formed round by round (mid-size batches, no G), 3 = screened form (screen.hip): c0 by the
+// batch GEMM, one workgroup per signal on its subset's own Gram matrix, one screening launch per chunk
+int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 0, bool no_subset = false)
 {
-    // form: 0 = two GEMMs per round (residual form), 1 = Gram form on the full G = A^T A, 2 = column form: Gram form
-    // on a cache of the entering columns' Gram columns, formed round by round (mid-size batches, no G), 3 = screened form
-    // (screen.hip): c0 by the batch GEMM, one workgroup per signal on its subset's own Gram matrix, one screening launch per chunk
     using T = float;
     const bool gram = form != 0, cols_form = form == 2;
-    if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) {
-        set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1");
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "solve_batch: increments must be positive"); return SS_HIP_EINVAL; }
-    try {
+    const size_t B = c.B;
+    const T tol = c.tol;
+    const uint32_t max_iter = c.max_iter;
+    return guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
@@ -2009,16 +2114,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             Workspace<T>& ws = *ws_of<T>(ctx);
             // option "trace": the path of the batch's FIRST signal (slot 0 of the first chunk) is recorded like a single solve's
             const uint32_t want_trace = (ctx->tracing && b0 == 0) ? (uint32_t)std::min<uint64_t>((uint64_t)max_iter + 2, 1u << 20) : 0u;
-            if (want_trace > ws.trace_cap) {
-                if (ws.trace) HIPCHK(hipFree(ws.trace));
-                ws.trace = nullptr;
-                ws.trace_cap = 0;
-                HIPCHK(hipMalloc(&ws.trace, (size_t)want_trace * sizeof(TraceEntry)));
-                ws.trace_cap = want_trace;
-            }
-            TraceEntry* const trace_keep = ws.trace;
-            if (want_trace == 0u) ws.trace = nullptr;
-            struct RestoreTrace { Workspace<T>& w; TraceEntry* p; ~RestoreTrace() { w.trace = p; } } restore_trace{ ws, trace_keep };
+            TraceWindow<T> trace_window(ws, want_trace);
             const uint32_t rows = (Bc + 127u) / 128u * 128u;          // GEMM rows of each block
             const size_t bp = ws.dims.b_pad;
             T* const Rblk = ws.rhs;
@@ -2026,30 +2122,8 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
 
             ctx->host_flags[0] = 0;
             ctx->host_flags[1] = 0;
-            const T* Yc = Y + (ptrdiff_t)b0 * y_stride;
-            if (incy == 1) {
-                HIPCHK(hipMemcpy2DAsync(ws.y, ldm * sizeof(T), Yc, (size_t)y_stride * sizeof(T), m * sizeof(T), Bc,
-                                        hipMemcpyDefault, st));
-            } else {
-                for (uint32_t b = 0; b < Bc; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, Yc + (ptrdiff_t)b * y_stride, incy, m);
-            }
-            HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)Bc * np * sizeof(T), st));
-            HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)Bc * np * sizeof(T), st));
-            HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)Bc * np, st));
-            HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)Bc * sizeof(DevState), st));
-            HIPCHK(hipMemsetAsync(ws.ndone, 0, sizeof(uint32_t), st));
-            HIPCHK(hipMemsetAsync(ws.rhs, 0, 2 * bp * ldm * sizeof(T), st));
-            HIPCHK(hipMemcpyAsync(Rblk, ws.y, (size_t)Bc * ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
-
-            // c_b = A^T y_b for every signal (residual_vector with x = 0, homotopy-cpu.cpp:215)
-            uint32_t nparts = 0;
-            const bool time_c0 = ctx->profiling != 0;
-            if (time_c0 && !ctx->ev_c0a) { HIPCHK(hipEventCreate(&ctx->ev_c0a)); HIPCHK(hipEventCreate(&ctx->ev_c0b)); }
-            if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0a, st));
-            HIPCHK(launch_gemm_tn_f32(ctx, Rblk, rows, (uint32_t)ldm, ws.c, (uint32_t)np, nullptr));
-            if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0b, st));
-            HIPCHK(launch_absmax<T>(ctx, ws, Bc, &nparts));
-            HIPCHK(launch_init<T>(ctx, ws, Bc, nparts, tol));
+            upload_chunk<T>(ctx, ws, c, b0, Bc);
+            uint32_t nparts = begin_gemm_chunk(ctx, ws, Bc, tol, ctx->profiling != 0);
             bool gram_chunk = gram;
             if (gram_chunk && ctx->engine == 1) {
                 // the tolerance guard of engine 1, for every signal of the chunk at once
@@ -2060,13 +2134,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             }
             if (gram_chunk) {
                 // keep c0 = A^T y of every signal: the Gram-form rounds subtract from it
-                if (ctx->c0_batch_rows < bp) {
-                    if (ctx->c0_batch) HIPCHK(hipFree(ctx->c0_batch));
-                    ctx->c0_batch = nullptr;
-                    ctx->c0_batch_rows = 0;
-                    HIPCHK(hipMalloc(&ctx->c0_batch, bp * np * sizeof(T)));
-                    ctx->c0_batch_rows = bp;
-                }
+                grow_device(ctx->c0_batch, ctx->c0_batch_rows, bp, np * sizeof(T), "hipMalloc(c0_batch)");
                 HIPCHK(hipMemcpyAsync(ctx->c0_batch, ws.c, (size_t)Bc * np * sizeof(T), hipMemcpyDeviceToDevice, st));
             } else {
                 HIPCHK(launch_rp<T>(ctx, ws, Bc));
@@ -2101,20 +2169,13 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             if (sub_chunk && ctx->sub_off_chunks > 0) { ctx->sub_off_chunks -= 1; sub_chunk = false; }     // (it handed back too much lately)
             const bool scr_chunk = gram_chunk && scr_form && !no_subset;
             // (a chunk whose tolerance is too tight for Gram-form correlations runs the residual-form rounds below, as in every form)
-            if (sub_chunk || scr_chunk) {
-                const size_t need = sub_buffer_bytes(Bc);
-                if (ctx->sub_buf_bytes < need) {
-                    if (ctx->sub_buf) HIPCHK(hipFree(ctx->sub_buf));
-                    ctx->sub_buf = nullptr;
-                    ctx->sub_buf_bytes = 0;
-                    if (hipMalloc(&ctx->sub_buf, need) != hipSuccess) {
-                        (void)hipGetLastError(); ctx->sub_buf = nullptr; sub_chunk = false;
-                        if (scr_chunk) throw HipFail{ hipErrorOutOfMemory, "screened batch form: log buffers" };
-                    } else ctx->sub_buf_bytes = need;
-                }
+            if ((sub_chunk || scr_chunk) && try_grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1) != hipSuccess) {
+                // (the subset form steps aside for this chunk; the screened form has no other way to go)
+                (void)hipGetLastError();
+                sub_chunk = false;
+                if (scr_chunk) throw HipFail{ hipErrorOutOfMemory, "screened batch form: log buffers" };
             }
             const uint32_t L = (uint32_t)std::max(1, std::min(ctx->lookahead, 64));
-            volatile uint32_t* hf = ctx->host_flags;
             const uint64_t last_round = (uint64_t)max_iter + 1;
             uint64_t rounds_run = 0;
             size_t ncq = 0;                                  // timed k_la_cq launches of this chunk (profiling on)
@@ -2136,19 +2197,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             }
             if (scr_chunk) HIPCHK(launch_screen_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter));
             for (uint64_t round = 1; round <= last_round && !sub_chunk && !scr_chunk; ++round) {
-                if (round > L) {
-                    const uint32_t need = (uint32_t)(round - L);
-                    uint32_t spins = 0;
-                    while (hf[1] == 0 && hf[0] < need) {
-                        if ((++spins & 0x3ffu) == 0) {
-                            const hipError_t q = hipStreamQuery(st);
-                            if (q == hipSuccess) break;
-                            if (q != hipErrorNotReady) throw HipFail{ q, "hipStreamQuery(batch loop)" };
-                        }
-                        std::this_thread::yield();
-                    }
-                    if (hf[1] != 0) break;
-                }
+                if (!wait_round(ctx, round, L, "hipStreamQuery(batch loop)")) break;
                 if (gram_chunk) {
                     const bool timed_cq = ctx->profiling != 0 && ncq < 4096;
                     if (timed_cq) HIPCHK(hipEventRecord(prof_event(ctx, 2 * ncq), st));
@@ -2172,25 +2221,13 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             }
             hs.resize(Bc);
             HIPCHK(hipMemcpyAsync(hs.data(), ws.st, (size_t)Bc * sizeof(DevState), hipMemcpyDeviceToHost, st));
-            if (rec_out) {
-                const size_t rb = record_bytes(kmax, sizeof(T));
-                const unsigned char* stage = pack_records<T>(ctx, ws, Bc, kmax);
-                HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + b0 * rb, stage, rb * Bc, hipMemcpyDefault, st));
+            if (c.rec_out) {
+                const unsigned char* stage = pack_records<T>(ctx, ws, Bc, c.kmax);
+                HIPCHK(hipMemcpyAsync(c.rec(b0), stage, record_bytes(c.kmax, sizeof(T)) * Bc, hipMemcpyDefault, st));
             }
-            float* Xc = X ? X + (ptrdiff_t)b0 * x_stride : nullptr;
-            if (!X) {
-            } else if (incx == 1) {
-                HIPCHK(hipMemcpy2DAsync(Xc, (size_t)x_stride * sizeof(T), ws.x, np * sizeof(T), n * sizeof(T), Bc,
-                                        hipMemcpyDefault, st));
-            } else {
-                for (uint32_t b = 0; b < Bc; ++b) copy_out<T>(ctx, Xc + (ptrdiff_t)b * x_stride, incx, ws.x + (size_t)b * np, n);
-            }
+            if (c.X) download_chunk<T>(ctx, ws, c, b0, Bc);
             HIPCHK(hipStreamSynchronize(st));
-            if (want_trace != 0u && ws.trace) {
-                const size_t cnt = std::min<size_t>((size_t)hs[0].iter + 1, ws.trace_cap);
-                ctx->last_trace.resize(cnt);
-                HIPCHK(hipMemcpy(ctx->last_trace.data(), ws.trace, cnt * sizeof(TraceEntry), hipMemcpyDeviceToHost));
-            }
+            if (want_trace != 0u && ws.trace) fetch_trace(ctx, ws, hs[0].iter);
             // The fused scan's meeting of a signal's workgroups is a bounded wait (k_la_cqs): should it ever expire — the
             // workgroups of a signal not resident together — the slot carries SS_HIP_ERUNTIME; this context then goes on with
             // the two-kernel form and the chunk is solved again (nothing of it has been reported yet)
@@ -2207,8 +2244,8 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             std::vector<uint32_t> ties;                      // slots whose scan met a tie stall (DevState::tie_stall)
             uint32_t n_redo_chunk = 0;
             for (uint32_t b = 0; b < Bc; ++b) {
-                if (!hs[b].done) { set_err(err, errlen, "solve_batch: internal error, a signal did not terminate"); return SS_HIP_ERUNTIME; }
-                if (hs[b].status == kStatusSubsetDecline || hs[b].status == kStatusSubsetFail) {
+                // (a slot that did not terminate is neither handed on nor a tie: check_slot_status reports it)
+                if (hs[b].done && (hs[b].status == kStatusSubsetDecline || hs[b].status == kStatusSubsetFail)) {
                     if (std::getenv("SS_HIP_SUB_DEBUG"))
                         std::fprintf(stderr, "[subset form] signal %zu: status %u after %u iterations, %u breakpoints logged, K = %u, lambda %g\n",
                                      b0 + b, hs[b].status, hs[b].iter, hs[b].solo_nlog, hs[b].K, hs[b].c_inf);
@@ -2216,17 +2253,12 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
                     ++n_redo_chunk;
                     continue;
                 }
-                if (ctx->tie_rerun && !ctx->tie_guard && (hs[b].status == kStatusTieRerun || (hs[b].status == 0 && hs[b].tie_stall != 0))) {
+                if (hs[b].done && ctx->tie_rerun && !ctx->tie_guard && (hs[b].status == kStatusTieRerun || (hs[b].status == 0 && hs[b].tie_stall != 0))) {
                     ties.push_back(b);
                     continue;
                 }
-                if (hs[b].status != 0) {
-                    set_err(err, errlen, hs[b].status == SS_HIP_ECAPACITY ? "solve_batch: active set outgrew the workspace capacity"
-                                                                          : "solve_batch: internal error, a device-side wait expired");
-                    return (int)hs[b].status;
-                }
-                if (iter_out) iter_out[b0 + b] = hs[b].iter;
-                if (err_out) err_out[b0 + b] = hs[b].c_inf;
+                if (const int rc = check_slot_status(hs[b], c.err, c.errlen)) return rc;
+                c.report(b0 + b, hs[b].iter, hs[b].c_inf);
                 ctx->stats.iterations += hs[b].iter;
             }
             ctx->stats.solves += Bc - (uint32_t)ties.size() - n_redo_chunk;
@@ -2267,88 +2299,59 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             // (up to 4 share every pass over A: solve_batch_ro).  (A handful per 4096 signals at 8192 x 65536.)
             for (uint32_t b : ties) all_ties.push_back(b0 + b);
         }
-        if (!redo.empty() && scr_form) {
+        if (scr_form) {
             // screened batch form: what it hands back is solved by the default single-signal engine, one by one
-            const size_t rb = record_bytes(kmax, sizeof(T));
-            for (size_t g : redo) {
-                uint32_t it = 0;
-                double e = 0.0;
-                Route r; r.no_sub = true;                  // (the batch's screened form has declined it: the default engine)
-                const int rc = solve_impl<T>(ctx, Y + (ptrdiff_t)g * y_stride, incy, tol, max_iter, X ? X + (ptrdiff_t)g * x_stride : nullptr, incx, &it, &e,
-                                             err, errlen, r, rec_out ? static_cast<unsigned char*>(rec_out) + g * rb : nullptr, kmax);
-                if (rc != SS_HIP_OK) return rc;
-                if (iter_out) iter_out[g] = it;
-                if (err_out) err_out[g] = e;
-            }
+            Route r; r.no_sub = true;                      // (the batch's screened form has declined it: the default engine)
+            for (size_t g : redo)
+                if (const int rc = solve_alone(ctx, c, g, r)) return rc;
             redo.clear();
         }
         if (!redo.empty()) {
             // the signals the subset form did not vouch for, gathered and solved in the lock-step Gram form (their own ties
             // are arbitrated inside that call), results scattered back
-            const size_t nr = redo.size(), rb = record_bytes(kmax, sizeof(T));
+            const size_t nr = redo.size(), rb = record_bytes(c.kmax, sizeof(T));
             T* Yg = nullptr; T* Xg = nullptr; unsigned char* Rg = nullptr;
             struct FreeTmp { T*& a; T*& b; unsigned char*& c; ~FreeTmp() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } free_tmp{ Yg, Xg, Rg };
             HIPCHK(hipMalloc(&Yg, nr * m * sizeof(T)));
-            if (X) HIPCHK(hipMalloc(&Xg, nr * n * sizeof(T)));
-            if (rec_out) HIPCHK(hipMalloc(&Rg, nr * rb));
-            for (size_t r = 0; r < nr; ++r) copy_in<T>(ctx, Yg + r * m, Y + (ptrdiff_t)redo[r] * y_stride, incy, m);
+            if (c.X) HIPCHK(hipMalloc(&Xg, nr * n * sizeof(T)));
+            if (c.rec_out) HIPCHK(hipMalloc(&Rg, nr * rb));
+            for (size_t r = 0; r < nr; ++r) copy_in<T>(ctx, Yg + r * m, c.y(redo[r]), c.incy, m);
             HIPCHK(hipStreamSynchronize(st));
             std::vector<uint32_t> it_r(nr, 0u);
             std::vector<double> er_r(nr, 0.0);
-            const int rc = solve_batch_gemm_f32(ctx, Yg, nr, (ptrdiff_t)m, 1, tol, max_iter, Xg, (ptrdiff_t)n, 1, it_r.data(), er_r.data(), err, errlen,
-                                                form, Rg, kmax, true);
+            const BatchCall<T> gathered{ Yg, nr, (ptrdiff_t)m, 1, tol, max_iter, Xg, (ptrdiff_t)n, 1, it_r.data(), er_r.data(), c.err, c.errlen, Rg, c.kmax };
+            const int rc = solve_batch_gemm_f32(ctx, gathered, form, true);
             if (rc != SS_HIP_OK) return rc;
             for (size_t r = 0; r < nr; ++r) {
                 const size_t g = redo[r];
-                if (X) copy_out<T>(ctx, X + (ptrdiff_t)g * x_stride, incx, Xg + r * n, n);
-                if (rec_out) HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + g * rb, Rg + r * rb, rb, hipMemcpyDefault, st));
-                if (iter_out) iter_out[g] = it_r[r];
-                if (err_out) err_out[g] = er_r[r];
+                if (c.X) copy_out<T>(ctx, c.x(g), c.incx, Xg + r * n, n);
+                if (c.rec_out) HIPCHK(hipMemcpyAsync(c.rec(g), Rg + r * rb, rb, hipMemcpyDefault, st));
+                c.report(g, it_r[r], er_r[r]);
             }
             HIPCHK(hipStreamSynchronize(st));
         }
         if (!all_ties.empty()) {
             ctx->stats.tie_reruns += all_ties.size();
-            const int rc = solve_batch_ro<T>(ctx, Y, all_ties.data(), all_ties.size(), y_stride, incy, tol, max_iter, X, x_stride, incx,
-                                             iter_out, err_out, err, errlen, rec_out, kmax);
+            const int rc = solve_batch_ro<T>(ctx, c, all_ties.data(), all_ties.size());
             if (rc != SS_HIP_OK) return rc;
         }
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "solve_batch: out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 template <typename T>
-int solve_batch_seq(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, T tol,
-                    uint32_t max_iter, T* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
-                    double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
+int solve_batch_seq(ss_hip_ctx* ctx, const BatchCall<T>& c)
 {
-    const size_t rb = record_bytes(kmax, sizeof(T));
-    for (size_t b = 0; b < B; ++b) {
-        uint32_t it = 0;
-        double e = 0.0;
-        const int rc = solve_impl<T>(ctx, Y + (ptrdiff_t)b * y_stride, incy, tol, max_iter,
-                                     X ? X + (ptrdiff_t)b * x_stride : nullptr, incx, &it, &e, err, errlen, Route(),
-                                     rec_out ? static_cast<unsigned char*>(rec_out) + b * rb : nullptr, kmax);
-        if (rc != SS_HIP_OK) return rc;
-        if (iter_out) iter_out[b] = it;
-        if (err_out) err_out[b] = e;
-    }
+    for (size_t b = 0; b < c.B; ++b)
+        if (const int rc = solve_alone(ctx, c, b, Route())) return rc;
     return SS_HIP_OK;
 }
 
-int solve_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol,
-                         uint32_t max_iter, float* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
-                         double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
+int solve_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
 {
+    const size_t B = c.B;
     // reference-order engine: in lock-step, up to 4 signals per pass over A
-    if (ctx->engine == 3)
-        return solve_batch_ro<float>(ctx, Y, nullptr, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    if (ctx->engine == 3) return solve_batch_ro<float>(ctx, c, nullptr, B);
     // lock-step MFMA path once enough signals share the matrix (batch_min option, default 192) — or, with G = A^T A already
     // in HBM, from four signals on: the subset form then runs every signal on a workgroup of its own (subbatch.hip)
     const bool have_g = ctx->gram_full != nullptr && ctx->batch_subset && ctx->engine >= 1 && ctx->batch_gram_min > 0;
@@ -2370,7 +2373,7 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
             HIPCHK(hipSetDevice(ctx->device));
             if (ensure_full_gram(ctx)) form = 1;
         } catch (const HipFail& f) {
-            set_err(err, errlen, hip_msg(f));
+            set_err(c.err, c.errlen, hip_msg(f));
             return SS_HIP_ERUNTIME;
         }
     }
@@ -2390,7 +2393,7 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
         // signals per chunk: at most 448 (7 full passes per round), at most what the cache budget AND the free HBM hold
         // (the cache is (max_iter + 2) rows per signal: a large max_iter with many signals does not fit — such a batch
         // goes the old way instead of failing), whole passes
-        const double row_bytes = ((double)max_iter + 2.0) * (double)((ctx->n_pad + 1023) / 1024 * 1024) * 4.0;
+        const double row_bytes = ((double)c.max_iter + 2.0) * (double)((ctx->n_pad + 1023) / 1024 * 1024) * 4.0;
         double budget = (double)ctx->gram_full_gib * 1073741824.0;
         size_t free_b = 0, total_b = 0;
         if (hipSetDevice(ctx->device) == hipSuccess && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -2400,30 +2403,23 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_
         const double fit = budget / row_bytes;
         size_t per = (size_t)std::min<double>(448.0, std::max(0.0, fit));
         if (per >= B) per = B; else per = per / 64 * 64;
-        if ((per >= 64 || (per == B && per > 0)) && ensure_bcol(ctx, per, max_iter)) { form = 2; ctx->bcol_chunk = (int)std::max<size_t>(per, 1); }
+        if ((per >= 64 || (per == B && per > 0)) && ensure_bcol(ctx, per, c.max_iter)) { form = 2; ctx->bcol_chunk = (int)std::max<size_t>(per, 1); }
     }
-    if (lockstep || form == 2 || form == 3)
-        return solve_batch_gemm_f32(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, form,
-                                    rec_out, kmax);
-    return solve_batch_seq<float>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    if (lockstep || form == 2 || form == 3) return solve_batch_gemm_f32(ctx, c, form);
+    return solve_batch_seq<float>(ctx, c);
 }
 
 // fp64 batch, resident tier, in chunks of screen64_batch_cap() signals
 // (omp: OMP batches — ss_hip_omp_solve_batch_f64 — the same tier with k_res_solve<double, OMP> and OMP's certificate)
-int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol, uint32_t max_iter, double* X,
-                      ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax,
-                      bool omp = false)
+int solve_batch_res64(ss_hip_ctx* ctx, const BatchCall<double>& c, bool omp = false)
 {
-    if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (!(tol >= std::numeric_limits<double>::epsilon() && tol < 1.0)) { set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1"); return SS_HIP_EINVAL; }
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "solve_batch: vector increments must be positive"); return SS_HIP_EINVAL; }
-    const size_t rb = record_bytes(kmax, sizeof(double));
+    const size_t B = c.B, rb = record_bytes(c.kmax, sizeof(double));
     const uint32_t cap = screen64_batch_cap();
     std::vector<size_t> redo;
-    try {
+    const int rc = guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n;
-        const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
+        const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)c.max_iter + 1), kKcapLimit);
         std::vector<DevState> hst(cap);
         for (size_t b0 = 0; b0 < B; b0 += cap) {
             const uint32_t nb = (uint32_t)std::min<size_t>(cap, B - b0);
@@ -2431,11 +2427,11 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
             Workspace<double>& ws = *ws_of<double>(ctx);
             hipStream_t st = ctx->stream;
             HIPCHK(hipMemsetAsync(ws.y, 0, (size_t)cap * ctx->ldm * sizeof(double), st));
-            for (uint32_t b = 0; b < nb; ++b) copy_in<double>(ctx, ws.y + (size_t)b * ctx->ldm, Y + (ptrdiff_t)(b0 + b) * y_stride, incy, m);
+            for (uint32_t b = 0; b < nb; ++b) copy_in<double>(ctx, ws.y + (size_t)b * ctx->ldm, c.y(b0 + b), c.incy, m);
             HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)nb * ctx->n_pad * sizeof(double), st));
             HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)nb * sizeof(DevState), st));
-            HIPCHK(launch_screen64_batch(ctx, ws, nb, tol, max_iter, omp));
-            const unsigned char* stage = rec_out ? pack_records<double>(ctx, ws, nb, kmax) : nullptr;
+            HIPCHK(launch_screen64_batch(ctx, ws, nb, c.tol, c.max_iter, omp));
+            const unsigned char* stage = c.rec_out ? pack_records<double>(ctx, ws, nb, c.kmax) : nullptr;
             HIPCHK(hipMemcpyAsync(hst.data(), ws.st, (size_t)nb * sizeof(DevState), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             for (uint32_t b = 0; b < nb; ++b) {
@@ -2448,10 +2444,9 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
                     count_reasons(ctx, hs.sub_reason, hs.tie_stall != 0 || hs.status == kStatusTieRerun);
                     continue;
                 }
-                if (X) copy_out<double>(ctx, X + (ptrdiff_t)(b0 + b) * x_stride, incx, ws.x + (size_t)b * ctx->n_pad, n);
-                if (rec_out) HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + (b0 + b) * rb, stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
-                if (iter_out) iter_out[b0 + b] = hs.iter;
-                if (err_out) err_out[b0 + b] = hs.c_inf;
+                if (c.X) copy_out<double>(ctx, c.x(b0 + b), c.incx, ws.x + (size_t)b * ctx->n_pad, n);
+                if (c.rec_out) HIPCHK(hipMemcpyAsync(c.rec(b0 + b), stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
+                c.report(b0 + b, hs.iter, hs.c_inf);
                 ctx->stats.solves += 1;
                 ctx->stats.iterations += hs.iter;
                 ctx->stats.screen_signals += 1;
@@ -2460,45 +2455,31 @@ int solve_batch_res64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_st
             }
             HIPCHK(hipStreamSynchronize(st));
         }
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "solve_batch: out of host memory");
-        return SS_HIP_ENOMEM;
-    }
+        return SS_HIP_OK;
+    });
+    if (rc != SS_HIP_OK) return rc;
     // what the chunks did not report: alone, through the sub-dictionary tier and the engine behind it
-    for (size_t b : redo) {
-        uint32_t it = 0;
-        double e = 0.0;
-        Route r; r.no_res = true; r.omp = omp;             // (the batch's resident tier has declined it: the tiers behind)
-        const int rc = solve_impl<double>(ctx, Y + (ptrdiff_t)b * y_stride, incy, tol, max_iter, X ? X + (ptrdiff_t)b * x_stride : nullptr, incx, &it, &e, err, errlen,
-                                          r, rec_out ? static_cast<unsigned char*>(rec_out) + b * rb : nullptr, kmax);
-        if (rc != SS_HIP_OK) return rc;
-        if (iter_out) iter_out[b] = it;
-        if (err_out) err_out[b] = e;
-    }
+    Route r; r.no_res = true; r.omp = omp;             // (the batch's resident tier has declined it: the tiers behind)
+    for (size_t g : redo)
+        if (const int rc1 = solve_alone(ctx, c, g, r)) return rc1;
     return SS_HIP_OK;
 }
 
-int solve_batch_dispatch(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol,
-                         uint32_t max_iter, double* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
-                         double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
+int solve_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<double>& c)
 {
     // reference-order engine: in lock-step, up to 4 signals per pass over A
-    if (ctx->engine == 3)
-        return solve_batch_ro<double>(ctx, Y, nullptr, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    if (ctx->engine == 3) return solve_batch_ro<double>(ctx, c, nullptr, c.B);
     // fp64 batches of four signals or more on dictionaries the fp64 screened form takes: the resident tier with the signals of a chunk
     // side by side (screen.hip: launch_screen64_batch) — one pass over the fp16 copy ranks every signal's columns, the paths run in as
     // many workgroups at once, every signal's states are certified by a screening pass of its own; what a slot's certificate does not
     // cover is solved again alone, through the remaining tiers
-    if (B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 && ctx->res_off_solves == 0) {
+    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 && ctx->res_off_solves == 0) {
         bool usable = false;
         try { HIPCHK(hipSetDevice(ctx->device)); usable = screen64_batch_usable(ctx); } catch (const HipFail&) { usable = false; }
-        if (usable) return solve_batch_res64(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+        if (usable) return solve_batch_res64(ctx, c);
     }
     // otherwise one signal at a time
-    return solve_batch_seq<double>(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    return solve_batch_seq<double>(ctx, c);
 }
 
 template <typename T>
@@ -2506,56 +2487,38 @@ int solve_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
                      uint32_t max_iter, T* X, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out,
                      double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
 {
-    if (!ctx) { set_err(err, errlen, "solve_batch: null context"); return SS_HIP_EINVAL; }
-    if (ctx->kind != 0) { set_err(err, errlen, "solve_batch: this context was created for IRLS"); return SS_HIP_EINVAL; }
-    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "solve_batch: element type mismatch"); return SS_HIP_ETYPE; }
-    if (!Y || (!X && !rec_out)) { set_err(err, errlen, "solve_batch: Y and the output must not be null"); return SS_HIP_EINVAL; }
-    if (rec_out && (kmax == 0 || kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(rec_out) & 7u))) {
-        set_err(err, errlen, "solve_batch_compact: kmax must be 1..4096 and records 8-byte aligned");
-        return SS_HIP_EINVAL;
-    }
-    if (B == 0) return SS_HIP_OK;
-    return solve_batch_dispatch(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    const BatchCall<T> c{ Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax };
+    const int rc = check_batch_call(ctx, c);
+    if (rc != SS_HIP_OK || B == 0) return rc;
+    return solve_batch_dispatch(ctx, c);
 }
 
 // ---- OMP batches (ss_hip_omp_solve_batch_*) --------------------------------------------------------------------------------
 // Signal b's result is what ss_hip_omp_solve_* returns for it alone (the same picks, support and iteration count; coefficients to
 // rounding).  A slot a chunk does not certify is solved again alone by the single-signal ladder, and nothing of it is written
 // before: its result is that ladder's bit for bit.
-int solve_omp_seq(ss_hip_ctx* ctx, const float* Y, const double* Yd, const size_t* sig, size_t count, ptrdiff_t y_stride, ptrdiff_t incy, double tol,
-                  uint32_t max_iter, float* X, double* Xd, ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen,
-                  void* rec_out, uint32_t kmax, bool no_res)
+// sig: the `count` signals' indices into the call (nullptr: 0 .. count-1)
+template <typename T>
+int solve_omp_seq(ss_hip_ctx* ctx, const BatchCall<T>& c, const size_t* sig, size_t count)
 {
-    const size_t rb = record_bytes(kmax, Yd ? sizeof(double) : sizeof(float));
-    for (size_t i = 0; i < count; ++i) {
-        const size_t b = sig ? sig[i] : i;
-        uint32_t it = 0;
-        double e = 0.0;
-        Route r; r.omp = true; r.no_res = no_res;
-        void* rec = rec_out ? static_cast<unsigned char*>(rec_out) + b * rb : nullptr;
-        const int rc = Yd ? solve_impl<double>(ctx, Yd + (ptrdiff_t)b * y_stride, incy, tol, max_iter, Xd ? Xd + (ptrdiff_t)b * x_stride : nullptr, incx,
-                                               &it, &e, err, errlen, r, rec, kmax)
-                          : solve_impl<float>(ctx, Y + (ptrdiff_t)b * y_stride, incy, (float)tol, max_iter, X ? X + (ptrdiff_t)b * x_stride : nullptr, incx,
-                                              &it, &e, err, errlen, r, rec, kmax);
-        if (rc != SS_HIP_OK) return rc;
-        if (iter_out) iter_out[b] = it;
-        if (err_out) err_out[b] = e;
-    }
+    Route r; r.omp = true;
+    for (size_t i = 0; i < count; ++i)
+        if (const int rc = solve_alone(ctx, c, sig ? sig[i] : i, r)) return rc;
     return SS_HIP_OK;
 }
 
 // fp32 chunks: c0 of every slot by the batch GEMM, then the Gram form (gram: ompbatch.hip, 256 slots per chunk) or the screened form in
 // OMP mode (screen.hip: launch_screen_batch, 64 slots per chunk)
-int solve_omp_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol, uint32_t max_iter, float* X,
-                        ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax,
-                        bool gram)
+int solve_omp_batch_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, bool gram)
 {
     using T = float;
-    const size_t rb = record_bytes(kmax, sizeof(T));
+    const size_t B = c.B, rb = record_bytes(c.kmax, sizeof(T));
+    const T tol = c.tol;
+    const uint32_t max_iter = c.max_iter;
     std::vector<size_t> redo;
-    try {
+    const int rc = guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
-        const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
+        const size_t n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
         const size_t chunk = gram ? (size_t)omp_gram_cap() : (size_t)screen_batch_cap();
         hipStream_t st = ctx->stream;
@@ -2564,59 +2527,24 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_s
             const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
             ensure_workspace<T>(ctx, Bc, kcap);
             Workspace<T>& ws = *ws_of<T>(ctx);
-            TraceEntry* const trace_keep = ws.trace;
-            ws.trace = nullptr;                                  // (no trace in these forms)
-            struct RestoreTrace { Workspace<T>& w; TraceEntry* p; ~RestoreTrace() { w.trace = p; } } restore_trace{ ws, trace_keep };
-            const uint32_t rows = (Bc + 127u) / 128u * 128u;     // GEMM rows of the block
-            const size_t bp = ws.dims.b_pad;
-            T* const Rblk = ws.rhs;
-            const T* Yc = Y + (ptrdiff_t)b0 * y_stride;
+            TraceWindow<T> no_trace(ws, 0u);                     // (no trace in these forms)
             HIPCHK(hipMemsetAsync(ws.y, 0, (size_t)Bc * ldm * sizeof(T), st));
-            if (incy == 1) {
-                HIPCHK(hipMemcpy2DAsync(ws.y, ldm * sizeof(T), Yc, (size_t)y_stride * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
-            } else {
-                for (uint32_t b = 0; b < Bc; ++b) copy_in<T>(ctx, ws.y + (size_t)b * ldm, Yc + (ptrdiff_t)b * y_stride, incy, m);
-            }
-            HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)Bc * np * sizeof(T), st));
-            HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)Bc * np * sizeof(T), st));
-            HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)Bc * np, st));
-            HIPCHK(hipMemsetAsync(ws.st, 0, (size_t)Bc * sizeof(DevState), st));
-            HIPCHK(hipMemsetAsync(ws.ndone, 0, sizeof(uint32_t), st));
-            HIPCHK(hipMemsetAsync(ws.rhs, 0, 2 * bp * ldm * sizeof(T), st));
-            HIPCHK(hipMemcpyAsync(Rblk, ws.y, (size_t)Bc * ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
-            uint32_t nparts = 0;
-            HIPCHK(launch_gemm_tn_f32(ctx, Rblk, rows, (uint32_t)ldm, ws.c, (uint32_t)np, nullptr));
-            HIPCHK(launch_absmax<T>(ctx, ws, Bc, &nparts));
-            HIPCHK(launch_init<T>(ctx, ws, Bc, nparts, tol));
-            if (ctx->c0_batch_rows < bp) {
-                if (ctx->c0_batch) HIPCHK(hipFree(ctx->c0_batch));
-                ctx->c0_batch = nullptr;
-                ctx->c0_batch_rows = 0;
-                HIPCHK(hipMalloc(&ctx->c0_batch, bp * np * sizeof(T)));
-                ctx->c0_batch_rows = bp;
-            }
+            upload_chunk<T>(ctx, ws, c, b0, Bc);
+            (void)begin_gemm_chunk(ctx, ws, Bc, tol, false);
+            grow_device(ctx->c0_batch, ctx->c0_batch_rows, ws.dims.b_pad, np * sizeof(T), "hipMalloc(c0_batch)");
             HIPCHK(hipMemcpyAsync(ctx->c0_batch, ws.c, (size_t)Bc * np * sizeof(T), hipMemcpyDeviceToDevice, st));
-            const size_t need = sub_buffer_bytes(Bc);
-            if (ctx->sub_buf_bytes < need) {
-                if (ctx->sub_buf) HIPCHK(hipFree(ctx->sub_buf));
-                ctx->sub_buf = nullptr;
-                ctx->sub_buf_bytes = 0;
-                HIPCHK(hipMalloc(&ctx->sub_buf, need));
-                ctx->sub_buf_bytes = need;
-            }
+            grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1, "hipMalloc(sub_buf)");
             if (gram) HIPCHK(launch_omp_gram_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter));
             else HIPCHK(launch_screen_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, true));
             hs.resize(Bc);
             HIPCHK(hipMemcpyAsync(hs.data(), ws.st, (size_t)Bc * sizeof(DevState), hipMemcpyDeviceToHost, st));
-            const unsigned char* stage = rec_out ? pack_records<T>(ctx, ws, Bc, kmax) : nullptr;
+            const unsigned char* stage = c.rec_out ? pack_records<T>(ctx, ws, Bc, c.kmax) : nullptr;
             HIPCHK(hipStreamSynchronize(st));
             uint32_t certified = 0;
             for (uint32_t b = 0; b < Bc; ++b) certified += (hs[b].done && hs[b].status == 0 && hs[b].tie_stall == 0) ? 1u : 0u;
             // (every slot certified, unit increments: the chunk's rows of X in one copy)
-            const bool whole = X != nullptr && incx == 1 && certified == Bc;
-            if (whole)
-                HIPCHK(hipMemcpy2DAsync(X + (ptrdiff_t)b0 * x_stride, (size_t)x_stride * sizeof(T), ws.x, np * sizeof(T), n * sizeof(T), Bc,
-                                        hipMemcpyDefault, st));
+            const bool whole = c.X != nullptr && c.incx == 1 && certified == Bc;
+            if (whole) download_chunk<T>(ctx, ws, c, b0, Bc);
             for (uint32_t b = 0; b < Bc; ++b) {
                 const bool good = hs[b].done && hs[b].status == 0 && hs[b].tie_stall == 0;
                 if (!good) {
@@ -2624,10 +2552,9 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_s
                     count_reasons(ctx, hs[b].sub_reason, hs[b].tie_stall != 0 || hs[b].status == kStatusTieRerun);
                     continue;
                 }
-                if (X && !whole) copy_out<T>(ctx, X + (ptrdiff_t)(b0 + b) * x_stride, incx, ws.x + (size_t)b * np, n);
-                if (rec_out) HIPCHK(hipMemcpyAsync(static_cast<unsigned char*>(rec_out) + (b0 + b) * rb, stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
-                if (iter_out) iter_out[b0 + b] = hs[b].iter;
-                if (err_out) err_out[b0 + b] = hs[b].c_inf;
+                if (c.X && !whole) copy_out<T>(ctx, c.x(b0 + b), c.incx, ws.x + (size_t)b * np, n);
+                if (c.rec_out) HIPCHK(hipMemcpyAsync(c.rec(b0 + b), stage + (size_t)b * rb, rb, hipMemcpyDefault, st));
+                c.report(b0 + b, hs[b].iter, hs[b].c_inf);
                 ctx->stats.solves += 1;
                 ctx->stats.iterations += hs[b].iter;
             }
@@ -2642,78 +2569,55 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_s
                 ctx->stats.screen_redone += Bc - certified;
             }
         }
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "solve_batch: out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-    return solve_omp_seq(ctx, Y, nullptr, redo.data(), redo.size(), y_stride, incy, tol, max_iter, X, nullptr, x_stride, incx, iter_out, err_out,
-                         err, errlen, rec_out, kmax, false);
+        return SS_HIP_OK;
+    });
+    if (rc != SS_HIP_OK) return rc;
+    return solve_omp_seq<T>(ctx, c, redo.data(), redo.size());
 }
 
 // The forms an OMP batch takes, in this order: (a) fp32 from 4 signals with G = A^T A at hand, or a batch large enough to form it (the
 // Homotopy batch's rule: max(batch_gram_min, 1536) where the screened form applies): the Gram form, chunks of 256; (b) fp32 from 4 signals
 // on dictionaries the screened form takes ("batch_screen"): chunks of 64 in that form; (c) fp64 from 4 signals: the resident tier's batch;
 // (d) everything else one signal at a time through the single-signal ladder.
-int omp_batch_dispatch(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol, uint32_t max_iter, float* X,
-                       ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax)
+int omp_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
 {
-    if (B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->screen_resident) {
+    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->screen_resident) {
         try {
             HIPCHK(hipSetDevice(ctx->device));
             if (ctx->batch_gram_min > 0 && res_solve_usable<float>()) {
                 const bool scr_batches = !ctx->gram_full && ctx->batch_screen && screen_form_usable(ctx);
                 const size_t gram_min = scr_batches ? std::max<size_t>((size_t)ctx->batch_gram_min, 1536) : (size_t)ctx->batch_gram_min;
-                if ((ctx->gram_full || B >= gram_min) && ensure_full_gram(ctx) && omp_gram_usable(ctx))
-                    return solve_omp_batch_f32(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, true);
+                if ((ctx->gram_full || c.B >= gram_min) && ensure_full_gram(ctx) && omp_gram_usable(ctx)) return solve_omp_batch_f32(ctx, c, true);
             }
             if (ctx->batch_screen && ctx->la_fused >= 3 && ctx->early_solo && ctx->solo_subset == 256 && res_solve_usable<float>() && screen_form_usable(ctx))
-                return solve_omp_batch_f32(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, false);
+                return solve_omp_batch_f32(ctx, c, false);
         } catch (const HipFail& f) {
-            set_err(err, errlen, hip_msg(f));
+            set_err(c.err, c.errlen, hip_msg(f));
             return SS_HIP_ERUNTIME;
         }
     }
-    return solve_omp_seq(ctx, Y, nullptr, nullptr, B, y_stride, incy, tol, max_iter, X, nullptr, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax,
-                         false);
+    return solve_omp_seq<float>(ctx, c, nullptr, c.B);
 }
 
-int omp_batch_dispatch(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol, uint32_t max_iter, double* X,
-                       ptrdiff_t x_stride, ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out, uint32_t kmax)
+int omp_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<double>& c)
 {
-    if (B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 &&
+    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 &&
         ctx->res_off_solves == 0) {
         bool usable = false;
         try { HIPCHK(hipSetDevice(ctx->device)); usable = screen64_batch_usable(ctx); } catch (const HipFail&) { usable = false; }
-        if (usable) return solve_batch_res64(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax, true);
+        if (usable) return solve_batch_res64(ctx, c, true);
     }
-    return solve_omp_seq(ctx, nullptr, Y, nullptr, B, y_stride, incy, tol, max_iter, nullptr, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax,
-                         false);
+    return solve_omp_seq<double>(ctx, c, nullptr, c.B);
 }
 
 template <typename T>
 int omp_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, T tol, uint32_t max_iter, T* X, ptrdiff_t x_stride,
                    ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen, void* rec_out = nullptr, uint32_t kmax = 0)
 {
-    // (the Homotopy batch's validation, message for message)
-    if (!ctx) { set_err(err, errlen, "solve_batch: null context"); return SS_HIP_EINVAL; }
-    if (ctx->kind != 0) { set_err(err, errlen, "solve_batch: this context was created for IRLS"); return SS_HIP_EINVAL; }
-    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "solve_batch: element type mismatch"); return SS_HIP_ETYPE; }
-    if (!Y || (!X && !rec_out)) { set_err(err, errlen, "solve_batch: Y and the output must not be null"); return SS_HIP_EINVAL; }
-    if (rec_out && (kmax == 0 || kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(rec_out) & 7u))) {
-        set_err(err, errlen, "solve_batch_compact: kmax must be 1..4096 and records 8-byte aligned");
-        return SS_HIP_EINVAL;
-    }
-    if (B == 0) return SS_HIP_OK;
-    if (max_iter == 0) { set_err(err, errlen, "solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) {
-        set_err(err, errlen, "solve_batch: tolerance must satisfy eps <= tolerance < 1");
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "solve_batch: increments must be positive"); return SS_HIP_EINVAL; }
-    return omp_batch_dispatch(ctx, Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax);
+    const BatchCall<T> c{ Y, B, y_stride, incy, tol, max_iter, X, x_stride, incx, iter_out, err_out, err, errlen, rec_out, kmax };
+    const int rc = check_batch_call(ctx, c);
+    if (rc != SS_HIP_OK || B == 0) return rc;
+    return omp_batch_dispatch(ctx, c);
 }
 
 template <typename T>
@@ -2723,7 +2627,7 @@ int gemv_t_impl(ss_hip_ctx* ctx, const T* r, T* c, int repeats, float* ms_out, c
     if (!ctx || !r || !c) { set_err(err, errlen, "gemv_t: null argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "gemv_t: type mismatch"); return SS_HIP_ETYPE; }
     if (repeats < 1) repeats = 1;
-    try {
+    return guarded(err, errlen, "gemv_t", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         Workspace<T>& ws = *ws_of<T>(ctx);
         hipStream_t st = ctx->stream;
@@ -2743,11 +2647,8 @@ int gemv_t_impl(ss_hip_ctx* ctx, const T* r, T* c, int repeats, float* ms_out, c
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
         if (ms_out) *ms_out = ms / (float)repeats;
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 // C[b][:] = A^T R[b][:] for B right-hand sides through the MFMA GEMM (fp32 contexts)
@@ -2871,7 +2772,7 @@ int reconstruct_impl(ss_hip_ctx* ctx, const T* x, T* y, char* err, size_t errlen
     if (ctx && ctx->kind != 0) { set_err(err, errlen, "this entry point needs a Homotopy context (an IRLS context holds the factorised matrix)"); return SS_HIP_EINVAL; }
     if (!ctx || !x || !y) { set_err(err, errlen, "reconstruct: null argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "reconstruct: type mismatch"); return SS_HIP_ETYPE; }
-    try {
+    return guarded(err, errlen, "reconstruct", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         Workspace<T>& ws = *ws_of<T>(ctx);
         copy_in<T>(ctx, ws.q, x, 1, ctx->n);
@@ -2879,11 +2780,8 @@ int reconstruct_impl(ss_hip_ctx* ctx, const T* x, T* y, char* err, size_t errlen
         copy_out<T>(ctx, y, 1, ws.rhs, ctx->m);
         HIPCHK(hipStreamSynchronize(ctx->stream));
         // rhs padding must stay zero for the sweeps: rows >= m were not written
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 
@@ -2899,9 +2797,8 @@ int irls_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t
         return SS_HIP_ETYPE;
     }
     if (!y || !x) { set_err(err, errlen, "irls_solve: y and x must not be null"); return SS_HIP_EINVAL; }
-    if (max_iter == 0) { set_err(err, errlen, "irls_solve: max_iterations must be > 0"); return SS_HIP_EINVAL; }   // irls-cpu.cpp:78
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "irls_solve: vector increments must be positive"); return SS_HIP_EINVAL; }
-    try {
+    if (const int rc = check_solve_args<T>("irls_solve", max_iter, tol, false, incy, incx, err, errlen)) return rc;
+    return guarded(err, errlen, "irls_solve", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         copy_in<T>(ctx, irls_y_buffer<T>(ctx), y, incy, ctx->m);
         IrlsResult res{};
@@ -2913,11 +2810,8 @@ int irls_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t
         if (spd_failure) *spd_failure = (int)res.spd_failure;
         ctx->stats.solves += 1;
         ctx->stats.iterations += res.iter;
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 // ---- IRLS batches (irlsbatch.hip): chunks of slots, each signal's words those of irls_solve_impl for it alone ----------
@@ -2934,10 +2828,9 @@ int irls_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, p
         return SS_HIP_ETYPE;
     }
     if (!Y || !X) { set_err(err, errlen, "irls_solve_batch: Y and X must not be null"); return SS_HIP_EINVAL; }
-    if (max_iter == 0) { set_err(err, errlen, "irls_solve_batch: max_iterations must be > 0"); return SS_HIP_EINVAL; }
-    if (incy <= 0 || incx <= 0) { set_err(err, errlen, "irls_solve_batch: vector increments must be positive"); return SS_HIP_EINVAL; }
+    if (const int rc = check_solve_args<T>("irls_solve_batch", max_iter, tol, false, incy, incx, err, errlen)) return rc;
     if (B == 0) return SS_HIP_OK;
-    try {
+    return guarded(err, errlen, "irls_solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         uint32_t chunk = 0;
         HIPCHK(irls_batch_reserve<T>(ctx, B, &chunk));
@@ -2963,11 +2856,8 @@ int irls_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, p
             ctx->stats.irls_batch_signals += nb;
             ctx->stats.irls_batch_rounds += rounds;
         }
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    }
-    return SS_HIP_OK;
+        return SS_HIP_OK;
+    });
 }
 
 }  // namespace
