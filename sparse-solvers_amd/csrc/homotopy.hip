@@ -455,21 +455,34 @@ inline hipError_t launch_gemm32(const ss_hip_ctx* ctx, const uint32_t* rcols, co
 { return launch_gemm32_tn_f32(ctx, rcols, drows, D, ldd, st); }
 inline hipError_t launch_gemm32(const ss_hip_ctx* ctx, const uint32_t* rcols, const uint32_t* drows, double* D, uint32_t ldd, const DevState* st)
 { return launch_gemm32_tn_f64(ctx, rcols, drows, D, ldd, st); }
-inline hipError_t launch_persist(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, uint32_t lds_cols, bool after_solo = false)
-{ return launch_la_persist_f32(ctx, ws, tol, max_iter, lds_cols, after_solo); }
-inline hipError_t launch_persist(ss_hip_ctx*, Workspace<double>&, double, uint32_t, uint32_t, bool = false)
-{ return hipErrorInvalidConfiguration; }
-// speculative form (fp32 only): solo launch + verification + publication; seeding of the subset ranking
-inline hipError_t launch_solo_group(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter)
+// (fp32 only — the speculative and the resident form are never chosen in double precision: an error there)
+template <typename T>
+hipError_t launch_persist(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, uint32_t lds_cols, bool after_solo = false)
 {
-    const hipError_t e = launch_la_solo_f32(ctx, ws, tol, max_iter);
-    return e != hipSuccess ? e : launch_la_verify_f32(ctx, ws);
+    if constexpr (sizeof(T) == 4) return launch_la_persist_f32(ctx, ws, tol, max_iter, lds_cols, after_solo);
+    else return hipErrorInvalidConfiguration;
 }
-inline hipError_t launch_solo_group(ss_hip_ctx*, Workspace<double>&, double, uint32_t) { return hipErrorInvalidConfiguration; }
-inline hipError_t launch_cand_init(ss_hip_ctx* ctx, Workspace<float>& ws) { return launch_la_cand_init_f32(ctx, ws); }
-inline hipError_t launch_cand_init(ss_hip_ctx*, Workspace<double>&) { return hipErrorInvalidConfiguration; }
-inline hipError_t launch_top_cand(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nsel = 32) { return launch_la_top_cand_f32(ctx, ws, nsel); }
-inline hipError_t launch_top_cand(ss_hip_ctx*, Workspace<double>&, uint32_t = 32) { return hipErrorInvalidConfiguration; }
+// speculative form: solo launch + verification + publication; seeding of the subset ranking
+template <typename T>
+hipError_t launch_solo_group(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter)
+{
+    if constexpr (sizeof(T) == 4) {
+        const hipError_t e = launch_la_solo_f32(ctx, ws, tol, max_iter);
+        return e != hipSuccess ? e : launch_la_verify_f32(ctx, ws);
+    } else return hipErrorInvalidConfiguration;
+}
+template <typename T>
+hipError_t launch_cand_init(ss_hip_ctx* ctx, Workspace<T>& ws)
+{
+    if constexpr (sizeof(T) == 4) return launch_la_cand_init_f32(ctx, ws);
+    else return hipErrorInvalidConfiguration;
+}
+template <typename T>
+hipError_t launch_top_cand(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nsel = 32)
+{
+    if constexpr (sizeof(T) == 4) return launch_la_top_cand_f32(ctx, ws, nsel);
+    else return hipErrorInvalidConfiguration;
+}
 // the first lookahead sweep of a fp32 solve may fetch 64 Gram columns in one (MFMA-bound) pass
 inline hipError_t launch_gemm_first(const ss_hip_ctx* ctx, uint32_t nsel, const uint32_t* rcols, const uint32_t* drows, float* D, uint32_t ldd, const DevState* st)
 { return nsel > 32 ? launch_gemm64_tn_f32(ctx, rcols, drows, D, ldd, st) : launch_gemm32_tn_f32(ctx, rcols, drows, D, ldd, st); }
@@ -487,8 +500,8 @@ inline uint32_t miss_cols(const ss_hip_ctx* ctx, const Workspace<double>& ws, ui
 
 // early form of the speculative engine (fp32): the first solo launch runs on the subset Gram matrix beside the passes over A
 inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nparts, float tol, uint32_t max_iter, uint32_t lds_cols,
-                           hipEvent_t pe0, hipEvent_t pe1, hipEvent_t pe2 = nullptr, hipEvent_t pe3 = nullptr);
-inline void early_prologue(ss_hip_ctx*, Workspace<double>&, uint32_t, double, uint32_t, uint32_t, hipEvent_t, hipEvent_t, hipEvent_t = nullptr, hipEvent_t = nullptr)
+                           EventPair pass1, EventPair pass2);
+inline void early_prologue(ss_hip_ctx*, Workspace<double>&, uint32_t, double, uint32_t, uint32_t, EventPair, EventPair)
 { throw HipFail{ hipErrorInvalidConfiguration, "early_prologue<double>" }; }
 
 template <typename T> struct Lookahead {
@@ -543,37 +556,39 @@ template <typename T> struct Lookahead {
         if (!ws.cq_alt) HIPCHK(hipMalloc(&ws.cq_alt, 2 * (size_t)ctx->n_pad * sizeof(T)));
     }
 
-    // c0 = A^T y has been swept into ws.c0 (partials in pmax): first pick, first lookahead sweep
-    // returns the number of columns of the first sweep (0: none — full-G mode); ev0 / ev1: events around it
-    static uint32_t init(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nparts, T tol, bool solo = false,
-                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
+    // the columns of a solve's first lookahead sweep (0: none — full-G mode, every column is "cached": no sweep, ever): the entering
+    // column and the largest |c0| — 64 columns in one pass (fp32; MFMA-bound, ~0.45 ms at C2) instead of two 32-column passes and a
+    // round trip through the host in between
+    static uint32_t first_cols(const ss_hip_ctx* ctx, const Workspace<T>& ws)
     {
-        uint32_t first_cols = 0;
+        if (ws.gram_is_full) return 0;
+        if (sizeof(T) == 8) return miss_cols(ctx, ws);
+        return (ctx->first_sweep_cols > 32 && ctx->sweep32_variant == 0 && ws.gcap >= 128) ? 64u : 32u;
+    }
+
+    // c0 = A^T y has been swept into ws.c0 (partials in pmax): first pick, first lookahead sweep (ev: events around it)
+    static void init(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nparts, T tol, bool solo = false, EventPair ev = {})
+    {
         hipStream_t st = ctx->stream;
-        const bool full = ws.gram_is_full;                      // every column is "cached": no sweep, ever
+        const uint32_t nsel = first_cols(ctx, ws);
+        const bool full = nsel == 0;
         // (the slot map, the hand-off area of the resident kernel and the dense vectors were cleared by
         // k_la_reset before the sweep; the first sign is read from c0 itself)
         if (ws.la_dbg) HIPCHK(hipMemsetAsync(ws.la_dbg, 0, 2048 * 8 * sizeof(uint64_t), st));
         HIPCHK(launch_la_init_pick<T>(ctx, ws, nparts, tol, full));
         if (solo) HIPCHK(launch_cand_init(ctx, ws));           // per-block tops of |c0|: ranking of the first sweep and subset
         if (!full) {
-            // the first sweep: the entering column and the largest |c0| — 64 columns in one pass (fp32; MFMA-bound,
-            // ~0.45 ms at C2) instead of two 32-column passes and a round trip through the host in between
-            const uint32_t nsel = sizeof(T) == 8 ? miss_cols(ctx, ws)
-                                : ((ctx->first_sweep_cols > 32 && ctx->sweep32_variant == 0 && ws.gcap >= 128) ? 64u : 32u);
             if (solo && ctx->n > 32u * 512u) HIPCHK(launch_top_cand(ctx, ws, nsel));
             else HIPCHK(launch_la_top<T>(ctx, ws, 1, nsel));
-            if (ev0) HIPCHK(hipEventRecord(ev0, ctx->stream));
+            if (ev.a) HIPCHK(hipEventRecord(ev.a, ctx->stream));
             HIPCHK(launch_gemm_first(ctx, nsel, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, ws.st));
-            if (ev1) HIPCHK(hipEventRecord(ev1, ctx->stream));
-            first_cols = nsel;
+            if (ev.b) HIPCHK(hipEventRecord(ev.b, ctx->stream));
         }
         HIPCHK(launch_la_update<T>(ctx, ws, 0, tol));
-        if (ctx->la_fused) return first_cols;      // k_la_iter forms c and q itself
+        if (ctx->la_fused) return;      // k_la_iter forms c and q itself
         uint32_t np2 = 0;
         HIPCHK(launch_la_cq<T>(ctx, ws, &np2));
         ws.la_nparts = np2;
-        return first_cols;
     }
 
     // fused form: one launch per iteration ...
@@ -589,39 +604,37 @@ template <typename T> struct Lookahead {
     // that fetches it (plus 31 likely successors) and the inverse update that was waiting for it
     // from_cand: the speculative form is running — its verification has left the per-block candidate tops of
     // the scan that missed (wide dictionaries only: with few blocks the tops are too few to rank from)
-    static void fetch(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, bool from_cand = false,
-                      uint32_t fetch_index = 0)
+    static void fetch(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, EventPair ev = {}, bool from_cand = false, uint32_t fetch_index = 0)
     {
         const uint32_t nsel = miss_cols(ctx, ws, fetch_index);
         if (from_cand && ctx->n > 32u * 512u) HIPCHK(launch_top_cand(ctx, ws));
         else HIPCHK(launch_la_top<T>(ctx, ws, 0, nsel));
-        if (ev0) HIPCHK(hipEventRecord(ev0, ctx->stream));
+        if (ev.a) HIPCHK(hipEventRecord(ev.a, ctx->stream));
         HIPCHK(launch_gemm_first(ctx, nsel, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, ws.st));
-        if (ev1) HIPCHK(hipEventRecord(ev1, ctx->stream));
+        if (ev.b) HIPCHK(hipEventRecord(ev.b, ctx->stream));
         HIPCHK(launch_la_update<T>(ctx, ws, 1, tol));
     }
     // OMP: the next picks are the largest correlations; the pending update is k_gramupd in OMP mode
-    static void fetch_omp(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
+    static void fetch_omp(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, EventPair ev = {})
     {
         const uint32_t nsel = miss_cols(ctx, ws);
         HIPCHK(launch_la_top<T>(ctx, ws, 2, nsel));
-        if (ev0) HIPCHK(hipEventRecord(ev0, ctx->stream));
+        if (ev.a) HIPCHK(hipEventRecord(ev.a, ctx->stream));
         HIPCHK(launch_gemm_first(ctx, nsel, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, ws.st));
-        if (ev1) HIPCHK(hipEventRecord(ev1, ctx->stream));
+        if (ev.b) HIPCHK(hipEventRecord(ev.b, ctx->stream));
         HIPCHK(launch_la_omp_update<T>(ctx, ws, tol));
     }
 
     // one homotopy iteration: scan + select, (sweep if the entering column is not cached),
     // inverse update + direction from the cache, Gram-form c and q
-    static void round(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t rnd, T tol, uint32_t max_iter,
-                      hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr)
+    static void round(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t rnd, T tol, uint32_t max_iter, EventPair ev = {})
     {
         HIPCHK(launch_la_scansel<T>(ctx, ws, rnd, ws.la_nparts, tol, max_iter));
         const uint32_t nsel = miss_cols(ctx, ws);
         HIPCHK(launch_la_top<T>(ctx, ws, 0, nsel));
-        if (ev0) HIPCHK(hipEventRecord(ev0, ctx->stream));
+        if (ev.a) HIPCHK(hipEventRecord(ev.a, ctx->stream));
         HIPCHK(launch_gemm_first(ctx, nsel, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, ws.st));
-        if (ev1) HIPCHK(hipEventRecord(ev1, ctx->stream));
+        if (ev.b) HIPCHK(hipEventRecord(ev.b, ctx->stream));
         HIPCHK(launch_la_update<T>(ctx, ws, rnd, tol));
         uint32_t np2 = 0;
         HIPCHK(launch_la_cq<T>(ctx, ws, &np2));
@@ -640,7 +653,7 @@ template <typename T> struct Lookahead {
 // resident form for the last step of the path.  A solve that does not fit this mould (a pick outside the subset,
 // a miss, a failed check) simply continues in the plain pump below.
 inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nparts, float tol, uint32_t max_iter, uint32_t lds_cols,
-                           hipEvent_t pe0, hipEvent_t pe1, hipEvent_t pe2, hipEvent_t pe3)
+                           EventPair pass1, EventPair pass2)
 {
     hipStream_t st = ctx->stream;
     const int probe = ctx->early_probe;              // developer aid: 1 = no overlap (the passes first, then the solo launch)
@@ -734,9 +747,9 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
                                       ctx->se_count, se_quota));
             HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + kSeCount, early_se_wgs(ctx), ws.st));
         }
-        if (pe0) HIPCHK(hipEventRecord(pe0, ctx->stream2));
+        if (pass1.a) HIPCHK(hipEventRecord(pass1.a, ctx->stream2));
         HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, main_tiles));
-        if (pe1) HIPCHK(hipEventRecord(pe1, ctx->stream2));
+        if (pass1.b) HIPCHK(hipEventRecord(pass1.b, ctx->stream2));
         if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, se_last, range_last));
         // the second pass's 32 columns are chosen now, half a millisecond into the solo launch: what has entered
         // its support without a Gram row so far, then the columns closest to entering (k_pick_pass_b)
@@ -749,9 +762,9 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
             HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
             HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + (kSeCount + 2) + kSeCount, early_se_wgs(ctx), ws.st));
         }
-        if (pe2) HIPCHK(hipEventRecord(pe2, ctx->stream2));
+        if (pass2.a) HIPCHK(hipEventRecord(pass2.a, ctx->stream2));
         HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, main_tiles));
-        if (pe3) HIPCHK(hipEventRecord(pe3, ctx->stream2));
+        if (pass2.b) HIPCHK(hipEventRecord(pass2.b, ctx->stream2));
         if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, se_last, range_last));
         if (main_tiles) HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_join3, 0));
         HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
@@ -897,17 +910,36 @@ unsigned char* pack_records(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nslots, 
     return ctx->rec_stage;
 }
 
-// one signal in the subset form (subbatch.hip) when G = A^T A is at hand: c0 is in ws.c0
-inline hipError_t sub_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter)
+// The profiling events of one solve: pairs handed out in call order, each with what it brackets (account_profile books them).
+// A solve that is not profiled gets null pairs, and nothing is recorded.
+struct ProfSpans {
+    ss_hip_ctx* ctx;
+    bool on;
+    ProfSpans(ss_hip_ctx* c, bool profiled) : ctx(c), on(profiled) { ctx->prof_spans.clear(); }
+    EventPair span(ProfKind kind, uint32_t round = 0)
+    {
+        if (!on) return {};
+        const size_t i = ctx->prof_spans.size();
+        ctx->prof_spans.push_back({ kind, round });
+        return { prof_event(ctx, 2 * i), prof_event(ctx, 2 * i + 1) };
+    }
+};
+inline void record(hipEvent_t e, hipStream_t st) { if (e) HIPCHK(hipEventRecord(e, st)); }
+
+// c0 = A^T y (residual_vector with x = 0, homotopy-cpu.cpp:215) into `out` — ws.c0 for the forms on the Gram cache, ws.c for the
+// residual form —, the partial maxima in ws.pmax_* (*nparts of them); timed as the solve's first sweep
+template <typename T>
+void first_sweep(ss_hip_ctx* ctx, Workspace<T>& ws, T* out, ProfSpans& spans, uint32_t* nparts)
 {
-    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
-    return launch_sub_form(ctx, ws, 1, ws.c0, tol, max_iter);
+    const EventPair ev = spans.span(ProfKind::FirstSweep);
+    record(ev.a, ctx->stream);
+    HIPCHK(launch_sweep<T>(ctx, ws.rhs, (size_t)ws.dims.b_pad * ctx->ldm, 1, out, nullptr, ws.pmax_val, ws.pmax_idx, nparts, ws.st));
+    record(ev.b, ctx->stream);
 }
-inline hipError_t sub_single(ss_hip_ctx*, Workspace<double>&, double, uint32_t) { return hipErrorInvalidConfiguration; }
 
 // one signal in the screened form (screen.hip): no G — the subset's own Gram matrix from A, then one pass over the fp16 copy of A
-inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, hipEvent_t e0, hipEvent_t e1,
-                             hipEvent_t e2, hipEvent_t e3, hipEvent_t e4, hipEvent_t e5, bool omp, bool rescue)
+inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, EventPair first, EventPair screen, EventPair path,
+                             bool omp, bool rescue)
 {
     grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
     if (ctx->sub_dbg == nullptr && std::getenv("SS_HIP_SUB_STAMPS")) {
@@ -915,29 +947,8 @@ inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, u
         HIPCHK(hipMemsetAsync(ctx->sub_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
     }
     // (with the state mirrored to mapped host memory the epilogue launch applies the certificate's verdict: no k_sub_finish)
-    return launch_screen_form(ctx, ws, tol, max_iter, first16, ctx->hs_mapped == nullptr, e0, e1, e2, e3, e4, e5, omp, rescue);
+    return launch_screen_form(ctx, ws, tol, max_iter, first16, ctx->hs_mapped == nullptr, first, screen, path, omp, rescue);
 }
-inline hipError_t scr_rescue_scan(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, bool from_recheck, uint32_t* found) { return launch_screen_rescue_scan(ctx, ws, tol, from_recheck, found); }
-inline hipError_t scr_rescue_scan(ss_hip_ctx*, Workspace<double>&, double, bool, uint32_t*) { return hipErrorInvalidConfiguration; }
-inline hipError_t scr_single(ss_hip_ctx*, Workspace<double>&, double, uint32_t, bool, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, bool, bool) { return hipErrorInvalidConfiguration; }
-// (typed shims of the fp64 screened form: never reached for float)
-inline hipError_t scr64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, hipEvent_t e0, hipEvent_t e1) { return screen64_gather(ctx, c0, y, e0, e1); }
-inline hipError_t scr64_gather(ss_hip_ctx*, const float*, const float*, hipEvent_t, hipEvent_t) { return hipErrorInvalidConfiguration; }
-inline hipError_t scr64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double* y, uint32_t T, double tol, double c_inf, uint32_t K, hipEvent_t e2, hipEvent_t e3, bool omp,
-                                bool first16)
-{
-    return screen64_certify(ctx, ws, y, T, tol, c_inf, K, e2, e3, omp, first16);
-}
-inline hipError_t scr64_certify(ss_hip_ctx*, Workspace<float>&, const float*, uint32_t, float, double, uint32_t, hipEvent_t, hipEvent_t, bool, bool) { return hipErrorInvalidConfiguration; }
-
-inline hipError_t scr64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, uint32_t max_iter, bool first16, bool omp, hipEvent_t e0, hipEvent_t e1,
-                                 hipEvent_t e2, hipEvent_t e3, hipEvent_t e4, hipEvent_t e5, bool rescue)
-{
-    return launch_screen64_resident(ctx, ws, tol, max_iter, first16, omp, e0, e1, e2, e3, e4, e5, rescue);
-}
-inline hipError_t scr64_resident(ss_hip_ctx*, Workspace<float>&, float, uint32_t, bool, bool, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, hipEvent_t, bool) { return hipErrorInvalidConfiguration; }
-inline hipError_t scr64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, bool from_recheck, uint32_t* found) { return launch_screen64_rescue_scan(ctx, ws, tol, from_recheck, found); }
-inline hipError_t scr64_rescue_scan(ss_hip_ctx*, Workspace<float>&, float, bool, uint32_t*) { return hipErrorInvalidConfiguration; }
 
 // why a subset / screened solve was not reported: DevState::sub_reason's bits into the statistics
 inline void count_reasons(ss_hip_ctx* ctx, uint32_t r, bool tie)
@@ -964,27 +975,22 @@ struct PumpState {
     bool solo_started = false;
     bool early = false;           // early form: a solo group (and the resident launch behind it) is queued already
     uint32_t early_lds_cols = 0;
-    size_t nprof = 0;             // profiling events used so far
+    uint32_t ro_parts = 0;        // reference-order engine: partial maxima of its first sweep
     bool enqueued = false;        // the pump queued work behind a speculative epilogue
 };
 
 // Fused lookahead engine: every launch of k_la_iter performs the next iteration, or nothing while the device waits for a Gram
 // column (host_flags[2] counts those waits).  Returns false if the loop made no progress (internal error).
 template <typename T>
-bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bool la, bool la_omp, bool prof, PumpState& ps)
+bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bool la, bool la_omp, ProfSpans& spans, PumpState& ps)
 {
     hipStream_t st = ctx->stream;
     const uint32_t L = (uint32_t)std::max(1, std::min(ctx->lookahead, 64));
     volatile uint32_t* hf = ctx->host_flags;
-    bool& solo = ps.solo;
-    const bool solo_started = ps.solo_started, early = ps.early;
-    const uint32_t early_lds_cols = ps.early_lds_cols;
-    size_t& nprof = ps.nprof;
-    bool& pump_enqueued = ps.enqueued;
     // Fused lookahead engine: every launch of k_la_iter performs the next iteration, or
     // nothing while the device waits for a Gram column (hf[2] counts those waits).  The
     // host keeps L launches queued ahead and answers each wait with one fetch.
-    uint64_t enq = early ? (early_lds_cols != 0 ? 2u : 1u) : 0u;   // (early form: a solo group and the resident launch behind it are queued)
+    uint64_t enq = ps.early ? (ps.early_lds_cols != 0 ? 2u : 1u) : 0u;   // (early form: a solo group and the resident launch behind it are queued)
     uint32_t handled = 0, timed_fetches = 0;
     // resident kernel: LDS tier (support columns it can hold); 0 = one launch per iteration
     uint32_t lds_cols = 0;
@@ -1000,7 +1006,7 @@ bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, boo
         // (a solo group runs until the host has to act — fetch, hand-over, end — so one group in
         // flight is enough: every further one is three launches that find nothing to do; after
         // the hand-over, near the end of the path, two resident launches)
-        const uint32_t depth = solo ? 1u : (solo_started ? std::min<uint32_t>(L, 2u) : L);
+        const uint32_t depth = ps.solo ? 1u : (ps.solo_started ? std::min<uint32_t>(L, 2u) : L);
         while (hf[1] == 0 && hf[2] == handled && enq >= (uint64_t)hf[0] + depth) {
             if ((++spins & 0x3ffu) == 0) {
                 const hipError_t qs = hipStreamQuery(st);
@@ -1010,14 +1016,12 @@ bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, boo
             std::this_thread::yield();
         }
         if (hf[1] != 0) break;
-        pump_enqueued = true;
+        ps.enqueued = true;
         if (hf[2] != handled) {
-            const bool timed_la = prof && (timed_fetches++ % (uint32_t)std::max(1, ctx->profile_every) == 0);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (timed_la) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); }
-            if (la_omp) Lookahead<T>::fetch_omp(ctx, ws, tol, e0, e1);
-            else Lookahead<T>::fetch(ctx, ws, tol, e0, e1, solo, handled);
-            if (timed_la) { ctx->prof_kind.push_back(3); ++nprof; }
+            const bool timed_la = spans.on && (timed_fetches++ % (uint32_t)std::max(1, ctx->profile_every) == 0);
+            const EventPair ev = timed_la ? spans.span(ProfKind::Sweep32) : EventPair{};
+            if (la_omp) Lookahead<T>::fetch_omp(ctx, ws, tol, ev);
+            else Lookahead<T>::fetch(ctx, ws, tol, ev, ps.solo, handled);
             ++handled;
         }
         if (lds_cols != 0 && hf[3] > lds_cols) {
@@ -1026,11 +1030,11 @@ bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, boo
             lds_cols = (hf[3] <= big && big > lds_cols && la_persist_usable(ctx, big)) ? big : 0u;
         }
         if (enq >= max_launch) { stuck = true; break; }
-        if (solo && hf[4] != 0) solo = false;   // the device handed over to the resident / launch-per-iteration form
+        if (ps.solo && hf[4] != 0) ps.solo = false;   // the device handed over to the resident / launch-per-iteration form
         if (la_omp) HIPCHK(launch_la_omp<T>(ctx, ws, tol, max_iter));
-        else Lookahead<T>::iterate(ctx, ws, tol, max_iter, lds_cols, solo);
+        else Lookahead<T>::iterate(ctx, ws, tol, max_iter, lds_cols, ps.solo);
         ++enq;
-        if (solo && lds_cols != 0) {
+        if (ps.solo && lds_cols != 0) {
             // the resident form queued right behind the speculative group: a no-op unless that group hands
             // over (the last step of a path), which then costs no trip through the host
             HIPCHK(launch_persist(ctx, ws, tol, max_iter, lds_cols, true));
@@ -1047,23 +1051,19 @@ bool pump_fused(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, boo
 // One launch chain per round (engine 0: the fused sweep + tail; the lookahead engine without in-kernel grid synchronisation; the
 // reference-order engine; OMP in residual form).
 template <typename T>
-void pump_rounds(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bool la, bool ro, bool omp, uint32_t ro_parts,
-                 size_t rhs_stride, bool prof, PumpState& ps)
+void pump_rounds(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bool la, bool ro, bool omp, ProfSpans& spans, const PumpState& ps)
 {
     hipStream_t st = ctx->stream;
     const uint32_t L = (uint32_t)std::max(1, std::min(ctx->lookahead, 64));
     const uint64_t last_round = (uint64_t)max_iter + 1;
-    size_t& nprof = ps.nprof;
+    const size_t rhs_stride = (size_t)ws.dims.b_pad * ctx->ldm;   // r-block -> p-block
     for (uint64_t round = 1; round <= last_round; ++round) {
         if (!wait_round(ctx, round, L, "hipStreamQuery(solve loop)")) break;
         if (la) {
             // the launch is a no-op unless a column without cached Gram column enters: time
             // every `profile_every`-th launch and keep the ones that did work (see below)
-            const bool timed_la = prof && (round % (uint64_t)std::max(1, ctx->profile_every) == 0);
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (timed_la) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); }
-            Lookahead<T>::round(ctx, ws, (uint32_t)round, tol, max_iter, e0, e1);
-            if (timed_la) { ctx->prof_kind.push_back(3); ++nprof; }
+            const bool timed_la = spans.on && (round % (uint64_t)std::max(1, ctx->profile_every) == 0);
+            Lookahead<T>::round(ctx, ws, (uint32_t)round, tol, max_iter, timed_la ? spans.span(ProfKind::Sweep32) : EventPair{});
             continue;
         }
         if (ro) {
@@ -1071,7 +1071,7 @@ void pump_rounds(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bo
             // from the signs of c - gamma q), the fused sweep [c, q] = A^T [r, p], lambda + the while-test + the check of
             // those signs against the re-computed c (a mismatch rebuilds the direction; p and q are then formed again),
             // the scan + toggle + x update, the inverse update and the next direction
-            HIPCHK(launch_ro_round<T>(ctx, ws, 1u, (uint32_t)round, ro_parts, tol, max_iter));
+            HIPCHK(launch_ro_round<T>(ctx, ws, 1u, (uint32_t)round, ps.ro_parts, tol, max_iter));
             continue;
         }
         if (omp) {
@@ -1085,62 +1085,72 @@ void pump_rounds(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, uint32_t max_iter, bo
         uint32_t nb = 0;
         // HIP events cost tens of microseconds of stream time each: time every
         // `profile_every`-th fused sweep only (option), still inside the solve
-        const bool timed = prof && (round % (uint64_t)std::max(1, ctx->profile_every) == 0);
-        if (timed) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
+        const bool timed = spans.on && (round % (uint64_t)std::max(1, ctx->profile_every) == 0);
+        const EventPair ev = timed ? spans.span(ProfKind::FusedSweep, (uint32_t)round) : EventPair{};
+        record(ev.a, st);
         HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 2, ws.c, ws.q, ws.pmax_val, ws.pmax_idx, &nb, ws.st));
-        if (timed) {
-            HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st));
-            ctx->prof_kind.push_back((int)round + 16);     // >= 16: fused sweep of round (kind-16)
-            ++nprof;
-        }
+        record(ev.b, st);
         HIPCHK(launch_iteration_tail<T>(ctx, ws, 1, (uint32_t)round, nb, tol, max_iter));
     }
 }
 
-// The HIP events of a profiled solve into the context's statistics (prof_kind says what each pair bracketed)
+// The HIP events of a profiled solve into the context's statistics (ctx->prof_spans says what each pair bracketed)
 template <typename T>
-void account_profile(ss_hip_ctx* ctx, size_t nprof, uint32_t scr_launches, const DevState& hs)
+void account_profile(ss_hip_ctx* ctx, uint32_t scr_launches, const DevState& hs)
 {
+    ss_hip_stats& S = ctx->stats;
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
-    ctx->stats.solve_ms += ms;
-    // only sweeps that did real work: the initial one and rounds 1..done_round
-    for (size_t i = 0; i < nprof; ++i) {
+    S.solve_ms += ms;
+    for (size_t i = 0; i < ctx->prof_spans.size(); ++i) {
+        const ProfSpan sp = ctx->prof_spans[i];
         HIPCHK(hipEventElapsedTime(&ms, ctx->prof_events[2 * i], ctx->prof_events[2 * i + 1]));
-        if (ctx->prof_kind[i] == 1) {
-            ctx->stats.sweep1_launches += 1;
-            ctx->stats.sweep1_ms += ms;
-        } else if (ctx->prof_kind[i] == 6) {
+        switch (sp.kind) {
+        case ProfKind::FirstSweep:
+            S.sweep1_launches += 1;
+            S.sweep1_ms += ms;
+            break;
+        case ProfKind::Screen:
             // the screening pass: fp16 copy of A + the residual block (re-read from L2 by every workgroup: not counted) + norms
-            ctx->stats.screen_launches += scr_launches;
-            ctx->stats.screen_ms += ms;
-            ctx->stats.screen_bytes += (uint64_t)scr_launches * ((uint64_t)ctx->ldm * ctx->n_pad * 2ull + 96ull * ctx->ldm * 2ull + (uint64_t)ctx->n_pad * 4ull);
-        } else if (ctx->prof_kind[i] == 8) {
-            ctx->stats.res_solve_launches += 1;
-            ctx->stats.res_solve_ms += ms;
-        } else if (ctx->prof_kind[i] == 7) {
-            ctx->stats.first16_launches += 1;
-            ctx->stats.first16_ms += ms;
-            ctx->stats.first16_bytes += (uint64_t)ctx->ldm * ctx->n_pad * (uint64_t)ctx->first_pass_elem_bytes + (uint64_t)ctx->ldm * sizeof(T) + (uint64_t)ctx->n_pad * 4ull;
-        } else if (ctx->prof_kind[i] == 4) {
+            S.screen_launches += scr_launches;
+            S.screen_ms += ms;
+            S.screen_bytes += (uint64_t)scr_launches * ((uint64_t)ctx->ldm * ctx->n_pad * 2ull + 96ull * ctx->ldm * 2ull + (uint64_t)ctx->n_pad * 4ull);
+            break;
+        case ProfKind::PathKernel:
+            S.res_solve_launches += 1;
+            S.res_solve_ms += ms;
+            break;
+        case ProfKind::FirstReduced:
+            S.first16_launches += 1;
+            S.first16_ms += ms;
+            S.first16_bytes += (uint64_t)ctx->ldm * ctx->n_pad * (uint64_t)ctx->first_pass_elem_bytes + (uint64_t)ctx->ldm * sizeof(T) + (uint64_t)ctx->n_pad * 4ull;
+            break;
+        case ProfKind::Sweep64First:
             if (ms > 0.02f) {                          // (a launch of a solve that ended at the first pick is a no-op)
-                ctx->stats.sweep64_launches += 1;
-                ctx->stats.sweep64_ms += ms;
+                S.sweep64_launches += 1;
+                S.sweep64_ms += ms;
             }
-        } else if (ctx->prof_kind[i] == 3 || ctx->prof_kind[i] == 5) {
+            break;
+        case ProfKind::Sweep32:
+        case ProfKind::EarlyPass: {
             // lookahead sweep: a launch that found nothing to do returns in microseconds.  Bytes per EVENT: a
-            // plain pass (3) covers all n columns, the early form's main launch (5) its share of them
+            // plain pass covers all n columns, the early form's main launch its share of them
             const uint64_t sz = sizeof(T);
-            const uint64_t cols = ctx->prof_kind[i] == 5 ? ctx->stats.sweep32_timed_cols : (uint64_t)ctx->n;
+            const uint64_t cols = sp.kind == ProfKind::EarlyPass ? S.sweep32_timed_cols : (uint64_t)ctx->n;
             const uint64_t bytes = (uint64_t)ctx->m * cols * sz + 32ull * ctx->m * sz + 32ull * cols * sz;
             if ((double)bytes / (ms * 1e-3) < 50e12) {   // < 50 TB/s: it streamed A
-                ctx->stats.sweep32_launches += 1;
-                ctx->stats.sweep32_ms += ms;
-                ctx->stats.sweep32_bytes_timed += bytes;
+                S.sweep32_launches += 1;
+                S.sweep32_ms += ms;
+                S.sweep32_bytes_timed += bytes;
             }
-        } else if ((uint32_t)(ctx->prof_kind[i] - 16) <= hs.done_round) {
-            ctx->stats.sweep_launches += 1;
-            ctx->stats.sweep_ms += ms;
+            break;
+        }
+        case ProfKind::FusedSweep:
+            if (sp.round <= hs.done_round) {           // only sweeps that did real work: rounds 1 .. done_round
+                S.sweep_launches += 1;
+                S.sweep_ms += ms;
+            }
+            break;
         }
     }
 }
@@ -1245,6 +1255,15 @@ Forms choose_forms(ss_hip_ctx* ctx, const Route& route, const T* y, void* rec_ou
 //   Gram-form tolerance guard                  -> residual form                            (force_residual)
 //   a resident grid's wait expired             -> launch per iteration, then no in-kernel grid synchronisation (context options)
 // Every rung also keeps the statistics (ss_hip_stats) and the step-aside counters of its form.
+// the form did not report the signal: it declined or failed it, or its subset's view met a tie
+inline bool handed_back(const DevState& hs, bool scr_tie) { return hs.status == kStatusSubsetDecline || hs.status == kStatusSubsetFail || scr_tie; }
+// the reasons a rescue can answer (the path ran out of positions / states, or an outside column beat a state) and nothing else wrong
+inline bool rescuable_reasons(uint32_t rs)
+{
+    return (rs & (kReasonPositions | kReasonLog | kReasonColumn)) != 0u &&
+           (rs & (kReasonRemoval | kReasonIrregular | kReasonTie | kReasonGuard | kReasonNoCand | kReasonFirstState | kReasonOverflow)) == 0u;
+}
+
 template <typename T>
 int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const DevState& hs, Route* next, bool* again, bool* report,
                     char* err, size_t errlen)
@@ -1267,25 +1286,11 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
         Route r = route.after(); r.no_solo = no_solo; r.force_ro = true;
         return retry(r);
     }
-    if (sub1 || scr1 || scr64) {
-        // (a context whose signals the form hands back more often than not stops trying for a while)
-        ctx->sub_seen += 1;
-        if (hs.status == kStatusSubsetDecline || hs.status == kStatusSubsetFail || scr_tie) ctx->sub_failed += 1;
-        if (ctx->sub_seen >= 8) {
-            if (2 * ctx->sub_failed > ctx->sub_seen) ctx->sub_off_solves = 64;
-            ctx->sub_seen = 0;
-            ctx->sub_failed = 0;
-        }
-    }
+    const bool back = handed_back(hs, scr_tie);
+    // (a context whose signals the form hands back more often than not stops trying for a while)
+    if (sub1 || scr1 || scr64) ctx->sub_aside.note(back);
     if (scr64r) {
-        const bool back = hs.status == kStatusSubsetDecline || hs.status == kStatusSubsetFail || scr_tie;
-        ctx->res_seen += 1;
-        if (back) ctx->res_failed += 1;
-        if (ctx->res_seen >= 8) {
-            if (2 * ctx->res_failed > ctx->res_seen) ctx->res_off_solves = 64;
-            ctx->res_seen = 0;
-            ctx->res_failed = 0;
-        }
+        ctx->res_aside.note(back);
         if (back) {
             const uint32_t rs = hs.sub_reason;
             if (!route.rescue) count_reasons(ctx, rs, scr_tie);
@@ -1294,8 +1299,7 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
                              route.rescue ? ", rescue" : "", hs.status, hs.sub_reason, hs.iter, hs.solo_nlog, hs.K, hs.c_inf);
             // (the rescue, as in fp32: a column the ranking left out of the 256 — the tier once more with the columns its log names)
             const bool rescuable = !omp && !route.rescue && !scr_tie && ctx->screen_rescue && !ctx->tracing && screen_first16_usable(ctx) &&
-                                   (rs & (kReasonPositions | kReasonLog | kReasonColumn)) != 0u &&
-                                   (rs & (kReasonRemoval | kReasonIrregular | kReasonTie | kReasonGuard | kReasonNoCand | kReasonFirstState | kReasonOverflow)) == 0u;
+                                   rescuable_reasons(rs);
             if (rescuable) { Route r = route; r.rescue = true; r.rescue_why = rs; return retry(r); }
             // the resident tier does not report this signal: the sub-dictionary tier (2048 columns) takes it next
             ctx->stats.screen_tier2 += 1;
@@ -1305,7 +1309,7 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
         if (hs.status == 0 && route.rescue) ctx->stats.screen_rescued += 1;
         if (hs.status == 0) { ctx->stats.screen_signals += 1; ctx->stats.screen_resident += 1; }
     }
-    if ((scr1 || scr64) && (hs.status == kStatusSubsetDecline || hs.status == kStatusSubsetFail || scr_tie)) {
+    if ((scr1 || scr64) && back) {
         const uint32_t rs = hs.sub_reason;
         if (!route.rescue) count_reasons(ctx, rs, scr_tie);            // (why the FIRST attempt declined)
         if (std::getenv("SS_HIP_SUB_DEBUG")) {
@@ -1317,8 +1321,7 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
         // nothing else was wrong with it — typically a planted column the ranking left out of the subset.  The next attempt scans this
         // attempt's log for such columns (screen.hip: launch_screen_rescue_scan) and repeats the form with them; once.
         const bool rescuable = scr1 && !omp && !route.rescue && !scr_tie && ctx->screen_rescue && ctx->screen_resident && !ctx->tracing &&
-                               screen_first16_usable(ctx) && (rs & (kReasonPositions | kReasonLog | kReasonColumn)) != 0u &&
-                               (rs & (kReasonRemoval | kReasonIrregular | kReasonTie | kReasonGuard | kReasonNoCand | kReasonFirstState | kReasonOverflow)) == 0u;
+                               screen_first16_usable(ctx) && rescuable_reasons(rs);
         if (rescuable) { Route r = route; r.rescue = true; r.rescue_why = rs; return retry(r); }
         ctx->stats.screen_redone += 1;
         Route r = route; r.rescue = false; r.no_sub = true;
@@ -1335,7 +1338,7 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
         std::fprintf(stderr, "[k_sub_solve, cycles per round over %llu rounds] chain %.0f  max|c| %.0f  log+scan %.0f  arg-min %.0f  hand-shake+x %.0f  u1/u2 %.0f  "
                              "inverse+signs %.0f  direction %.0f\n", tp[8], tp[0] / r, tp[1] / r, tp[2] / r, tp[3] / r, tp[4] / r, tp[5] / r, tp[6] / r, tp[7] / r);
     }
-    if (sub1 && (hs.status == kStatusSubsetDecline || hs.status == kStatusSubsetFail)) {
+    if (sub1 && back) {
         ctx->stats.subset_redone += 1;
         count_reasons(ctx, hs.sub_reason, false);
         Route r = route; r.no_sub = true;
@@ -1401,13 +1404,41 @@ int check_solve_args(const char* prefix, uint32_t max_iter, T tol, bool with_tol
     return SS_HIP_EINVAL;
 }
 
+// The prologue of a rescue (route.rescue: the screened form — fp32 — or its resident tier — fp64 — declined the signal for a column its
+// ranking missed): the scan of the declined attempt's log for such columns — its state, logs and c~0 are still in place, nothing has been
+// reset yet.  true: the form runs once more with them.  false: there is nothing to rescue with, *next is the route that hands the signal
+// on (fp64: to the sub-dictionary tier, fp32: to the default engine).  scan = false: the form cannot run, nothing is scanned.
+template <typename T>
+bool rescue_prologue(ss_hip_ctx* ctx, Workspace<T>& ws, T tol, const Route& route, bool scan, Route* next)
+{
+    constexpr bool tier64 = sizeof(T) == 8;
+    uint32_t found = 0;
+    // (a decline by the exact re-check alone left the list of the columns that failed it: no scan)
+    const bool from_recheck = (route.rescue_why & kReasonRechecked) != 0u && (route.rescue_why & (kReasonPositions | kReasonLog)) == 0u;
+    if (scan) {
+        if constexpr (tier64) HIPCHK(launch_screen64_rescue_scan(ctx, ws, tol, from_recheck, &found));
+        else HIPCHK(launch_screen_rescue_scan(ctx, ws, tol, from_recheck, &found));
+    }
+    if (std::getenv("SS_HIP_SUB_DEBUG"))
+        std::fprintf(stderr, "[screened form%s, rescue] the scan lists %u columns the ranking missed\n", tier64 ? ", fp64 resident tier" : "", found);
+    if (scan && found >= 1u && found <= screen_rescue_cap()) {
+        ctx->stats.screen_rescue_tried += 1;
+        return true;
+    }
+    *next = route;
+    next->rescue = false;
+    if (tier64) { ctx->stats.screen_tier2 += 1; next->no_res = true; }
+    else { ctx->stats.screen_redone += 1; next->no_sub = true; }
+    return false;
+}
+
 // One attempt.  Returns the status of the solve, or — with *again set — the route of the next attempt in *next.
 template <typename T>
 int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_iter, T* x,
                ptrdiff_t incx, uint32_t* iter_out, double* err_out, char* err, size_t errlen,
                const Route& route, void* rec_out, uint32_t kmax, Route* next, bool* again)
 {
-    const bool omp = route.omp, force_residual = route.force_residual, no_solo = route.no_solo;
+    const bool omp = route.omp, no_solo = route.no_solo;
     auto retry = [&](const Route& r) { *next = r; *again = true; return SS_HIP_OK; };
     return guarded(err, errlen, "solve", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
@@ -1425,8 +1456,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         // (option profile_solve_every = k: with profiling on, only every k-th solve carries the HIP events — each costs
         // stream time, ~0.07 ms per solve in all at 8192 x 65536)
         const bool prof = ctx->profiling != 0 && (ctx->profile_solve_every <= 1 || (ctx->prof_solve_tick++ % (uint64_t)ctx->profile_solve_every) == 0);
-        size_t nprof = 0;
-        ctx->prof_kind.clear();
+        ProfSpans spans(ctx, prof);
 
         ctx->host_flags[0] = 0;     // the stream is idle here: the previous solve synchronised
         ctx->host_flags[1] = 0;
@@ -1434,38 +1464,28 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         ctx->host_flags[3] = 0;
         ctx->host_flags[4] = 0;
         if (prof) HIPCHK(hipEventRecord(ctx->ev_solve0, st));
-        Forms forms = choose_forms<T>(ctx, route, y, rec_out);
+        // ---- prepare: the forms of this attempt, the signal, the state ----
+        Forms f = choose_forms<T>(ctx, route, y, rec_out);
         // (lookahead engine with the signal on the device: k_la_reset reads it from the caller's buffer — no copy command)
-        const bool y_direct = forms.y_direct;
-        if (!y_direct) copy_in<T>(ctx, ws.y, y, incy, m);
-        // reference-order engine (reforder.hip; option engine = 3, and the arbiter of tie stalls): the reference's
-        // iteration with every reduction in the documented 8-partial order, two passes over A per iteration
-        const bool ro = forms.ro;
-        const bool la_path = forms.la;
-        if (!la_path) {
+        if (!f.y_direct) copy_in<T>(ctx, ws.y, y, incy, m);
+        const T* const y_dev = f.y_direct ? y : (const T*)nullptr;
+        if (!f.la) {
             HIPCHK(hipMemsetAsync(ws.x, 0, (size_t)ctx->n_pad * sizeof(T), st));
             HIPCHK(hipMemsetAsync(ws.d, 0, (size_t)ctx->n_pad * sizeof(T), st));
             HIPCHK(hipMemsetAsync(ws.insup, 0, (size_t)ctx->n_pad, st));
             HIPCHK(hipMemsetAsync(ws.st, 0, sizeof(DevState), st));
             HIPCHK(hipMemsetAsync(ws.ndone, 0, sizeof(uint32_t), st));
+            HIPCHK(hipMemcpyAsync(ws.rhs, ws.y, (size_t)ctx->ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
         }
-        if (!la_path) HIPCHK(hipMemcpyAsync(ws.rhs, ws.y, (size_t)ctx->ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
-        const size_t rhs_stride = (size_t)ws.dims.b_pad * ctx->ldm;   // r-block -> p-block
-
-        const bool la = forms.la;
-        // orthogonal matching pursuit in Gram form (k_la_omp): same cache, same sweeps
-        const bool la_omp = forms.la_omp;
-        bool solo = false, solo_started = false, early = false;
-        uint32_t early_lds_cols = 0, ro_parts = 0;
-        bool sub1 = forms.sub1, scr1 = forms.scr1, scr64 = forms.scr64, scr64r = forms.scr64r;
-        // (a context whose signals a form hands back more often than not steps that form aside for a while: the counters below)
-        if ((sub1 || scr1 || scr64 || scr64r) && ctx->sub_off_solves > 0) { ctx->sub_off_solves -= 1; sub1 = false; scr1 = false; scr64 = false; scr64r = false; }
-        if (scr64r && ctx->res_off_solves > 0) { ctx->res_off_solves -= 1; scr64r = false; }
-        if (route.rescue && !scr1 && !scr64r) ctx->stats.screen_redone += 1;      // (the form has stepped aside meanwhile: the signal is the default engine's after all)
-        if (scr64r) scr64 = false;
+        // (a context whose signals a form hands back more often than not steps that form aside for a while: attempt_verdict keeps the windows)
+        if ((f.sub1 || f.scr1 || f.scr64 || f.scr64r) && ctx->sub_aside.take()) { f.sub1 = false; f.scr1 = false; f.scr64 = false; f.scr64r = false; }
+        if (f.scr64r && ctx->res_aside.take()) f.scr64r = false;
+        if (route.rescue && !f.scr1 && !f.scr64r) ctx->stats.screen_redone += 1;      // (the form has stepped aside meanwhile: the signal is the default engine's after all)
+        if (f.scr64r) f.scr64 = false;
         uint32_t scr_launches = 1;
+        PumpState ps;
         // end of a solve: the device state to pinned memory, x (and the compact record) to the caller
-        bool spec_epilogue = false, pump_enqueued = false;
+        bool spec_epilogue = false;
         const bool x_on_device = x != nullptr && is_device_pointer(x);
         auto enqueue_epilogue = [&]() {
             if (ctx->hs_mapped != nullptr) {
@@ -1474,7 +1494,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
                 hipLaunchKernelGGL((k_epilogue<T>), dim3(std::max(1u, grid)), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(ws.st),
                                    static_cast<uint32_t*>(ctx->hs_mapped), (uint32_t)(sizeof(DevState) / 4), (const T*)ws.x,
                                    x_on_device ? x : (T*)nullptr, (long long)incx, (uint32_t)n,
-                                   (scr1 || scr64r) ? (uint32_t)(offsetof(DevState, status) / 4) : 0xffffffffu, (uint32_t)(offsetof(DevState, need_sweep) / 4));
+                                   (f.scr1 || f.scr64r) ? (uint32_t)(offsetof(DevState, status) / 4) : 0xffffffffu, (uint32_t)(offsetof(DevState, need_sweep) / 4));
                 HIPCHK(hipGetLastError());
                 if (x && !x_on_device) copy_out<T>(ctx, x, incx, ws.x, n);
             } else {
@@ -1513,50 +1533,43 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             ws.gram_is_full = true;
             full_view.on = true;
         };
-        if (scr64r) {
+        // ---- the first pass and the form's own launches ----
+        uint32_t nb1 = 0;
+        if (f.scr64r || f.sub1 || f.scr1) {
+            // the screened forms that queue everything in one go (fp64: the resident tier; fp32: the screened form, or the subset form on G)
             Lookahead<T>::ensure(ctx, ws, kcap);
-            bool rescue = false;
-            if (route.rescue) {
-                uint32_t found = 0;
-                const bool from_recheck = (route.rescue_why & kReasonRechecked) != 0u && (route.rescue_why & (kReasonPositions | kReasonLog)) == 0u;
-                HIPCHK(scr64_rescue_scan(ctx, ws, tol, from_recheck, &found));
-                rescue = found >= 1u && found <= screen_rescue_cap();
-                if (std::getenv("SS_HIP_SUB_DEBUG")) std::fprintf(stderr, "[screened form, fp64 resident tier, rescue] the scan lists %u columns the ranking missed\n", found);
-                if (!rescue) { ctx->stats.screen_tier2 += 1; Route r = route; r.rescue = false; r.no_res = true; return retry(r); }
-                ctx->stats.screen_rescue_tried += 1;
-            }
-            if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_direct ? y : (const T*)nullptr, incy));     // x, d, flags, DevState, r = y (OMP: done above)
-            const bool first16 = screen_first16_usable(ctx);
-            uint32_t nb1 = 0;
-            if (!first16) {
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-                HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c0, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
-            }
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, e4 = nullptr, e5 = nullptr;
-            if (prof && first16 && !rescue) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); ctx->prof_kind.push_back(7); ++nprof; }
-            if (prof) { e2 = prof_event(ctx, 2 * nprof); e3 = prof_event(ctx, 2 * nprof + 1); e4 = prof_event(ctx, 2 * nprof + 2); e5 = prof_event(ctx, 2 * nprof + 3); }
-            HIPCHK(scr64_resident(ctx, ws, tol, max_iter, first16, omp, e0, e1, e2, e3, e4, e5, rescue));
-            if (prof) { ctx->prof_kind.push_back(6); ctx->prof_kind.push_back(8); nprof += 2; }      // (6 = the screening pass, 8 = the path kernel)
-        } else if (scr64) {
-            Lookahead<T>::ensure(ctx, ws, kcap);
-            if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_direct ? y : (const T*)nullptr, incy));     // x, d, flags, DevState, r = y (OMP: done above)
-            // (the first pass — A^T y over all columns, which here only ranks them — over the fp16 copy: k_scr_first; 7 = that pass)
-            const bool first16 = screen_first16_usable(ctx);
-            uint32_t nb1 = 0;
-            if (first16) {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (prof) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); ctx->prof_kind.push_back(7); ++nprof; }
-                HIPCHK(scr64_gather(ctx, (const T*)nullptr, ws.rhs, e0, e1));
+            const bool screened = f.scr64r || f.scr1;
+            if (route.rescue && !rescue_prologue<T>(ctx, ws, tol, route, screened, next)) { *again = true; return SS_HIP_OK; }
+            const bool rescue = route.rescue;
+            if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_dev, incy));     // x, d, flags, DevState, r = y (OMP: done above)
+            // (the screened form's first pass — A^T y over all columns — reads the reduced-precision copy too: screen.hip, k_scr_first)
+            const bool first16 = screened && screen_first16_usable(ctx);
+            if (!first16) first_sweep<T>(ctx, ws, ws.c0, spans, &nb1);
+            if (f.sub1) {
+                if constexpr (sizeof(T) == 4) {
+                    // G = A^T A is at hand: the subset form (subbatch.hip) on c0 in ws.c0
+                    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
+                    HIPCHK(launch_sub_form(ctx, ws, 1, ws.c0, tol, max_iter));
+                }
             } else {
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-                HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c0, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
-                HIPCHK(scr64_gather(ctx, ws.c0, ws.rhs, nullptr, nullptr));
+                const EventPair first = (first16 && !rescue) ? spans.span(ProfKind::FirstReduced) : EventPair{};
+                const EventPair screen = spans.span(ProfKind::Screen), path = spans.span(ProfKind::PathKernel);
+                if constexpr (sizeof(T) == 8) HIPCHK(launch_screen64_resident(ctx, ws, tol, max_iter, first16, omp, first, screen, path, rescue));
+                else HIPCHK(scr_single(ctx, ws, tol, max_iter, first16, first, screen, path, omp, rescue));
             }
-            HIPCHK(hipStreamSynchronize(st));
-            bool handed_back = true;
+        } else if (f.scr64) {
             if constexpr (sizeof(T) == 8) {
+                Lookahead<T>::ensure(ctx, ws, kcap);
+                if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_dev, incy));     // x, d, flags, DevState, r = y (OMP: done above)
+                // (the first pass — A^T y over all columns, which here only ranks them — over the reduced-precision copy: k_scr_first)
+                const bool first16 = screen_first16_usable(ctx);
+                if (first16) {
+                    HIPCHK(screen64_gather(ctx, nullptr, ws.rhs, spans.span(ProfKind::FirstReduced)));
+                } else {
+                    first_sweep<T>(ctx, ws, ws.c0, spans, &nb1);
+                    HIPCHK(screen64_gather(ctx, ws.c0, ws.rhs));
+                }
+                HIPCHK(hipStreamSynchronize(st));
                 ss_hip_ctx* sub = screen64_sub(ctx);
                 sub->strict_sign = ctx->strict_sign; sub->zero_on_removal = ctx->zero_on_removal; sub->tie_guard = ctx->tie_guard;
                 sub->tie_rerun = ctx->tie_rerun; sub->engine = ctx->engine; sub->lookahead = ctx->lookahead;
@@ -1567,155 +1580,97 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
                 Route rs; rs.omp = omp; rs.no_sub = true;
                 const int rc_s = solve_impl<T>(sub, ws.rhs, 1, tol, max_iter, screen64_xsub(ctx), 1, &it_s, &e_s, err, errlen, rs, nullptr, 0);
                 HIPCHK(hipSetDevice(ctx->device));
+                const DevState hsub = *static_cast<const DevState*>(sub->hs_pinned);
                 const bool clean = rc_s == SS_HIP_OK && sub->stats.tie_reruns == ties0 && sub->stats.gram_fallbacks == gf0 &&
                                    sub->stats.persist_fallbacks == pf0 && it_s >= 1u && it_s <= 192u;
-                if (clean) {
-                    const DevState hsub = *static_cast<const DevState*>(sub->hs_pinned);
-                    hipEvent_t e2 = nullptr, e3 = nullptr;
-                    if (prof) { e2 = prof_event(ctx, 2 * nprof); e3 = prof_event(ctx, 2 * nprof + 1); }
-                    HIPCHK(scr64_certify(ctx, ws, ws.rhs, it_s, tol, e_s, hsub.K, e2, e3, omp, first16));
-                    if (prof) { ctx->prof_kind.push_back(6); ++nprof; }
-                    scr_launches = (it_s + 95u) / 96u;
-                    handed_back = false;
+                if (!clean) {
+                    // the sub-context's solve left its common path (a tie re-run, a residual-form retry, too many states): the usual engine
+                    if (std::getenv("SS_HIP_SUB_DEBUG"))
+                        std::fprintf(stderr, "[screened form, fp64] handed back: sub-context status %u iter %u K %u ties %llu gram fallbacks %llu persist fallbacks %llu (%s)\n",
+                                     hsub.status, hsub.iter, hsub.K, (unsigned long long)sub->stats.tie_reruns, (unsigned long long)sub->stats.gram_fallbacks,
+                                     (unsigned long long)sub->stats.persist_fallbacks, err ? err : "");
+                    ctx->stats.screen_redone += 1;
+                    Route r = route; r.no_sub = true;
+                    return retry(r);
                 }
+                HIPCHK(screen64_certify(ctx, ws, ws.rhs, it_s, tol, e_s, hsub.K, spans.span(ProfKind::Screen), omp, first16));
+                scr_launches = (it_s + 95u) / 96u;
             }
-            if (handed_back && std::getenv("SS_HIP_SUB_DEBUG")) {
-                ss_hip_ctx* sub = screen64_sub(ctx);
-                const DevState hsub = *static_cast<const DevState*>(sub->hs_pinned);
-                std::fprintf(stderr, "[screened form, fp64] handed back: sub-context status %u iter %u K %u ties %llu gram fallbacks %llu persist fallbacks %llu (%s)\n",
-                             hsub.status, hsub.iter, hsub.K, (unsigned long long)sub->stats.tie_reruns, (unsigned long long)sub->stats.gram_fallbacks,
-                             (unsigned long long)sub->stats.persist_fallbacks, err ? err : "");
-            }
-            if (handed_back) {
-                // the sub-context's solve left its common path (a tie re-run, a residual-form retry, too many states): the usual engine
-                ctx->stats.screen_redone += 1;
-                Route r = route; r.no_sub = true;
-                return retry(r);
-            }
-        } else if (la_omp && !scr1) {
+        } else if (f.la_omp) {
             Lookahead<T>::ensure(ctx, ws, kcap);
             enter_full_gram();
-            uint32_t nb1 = 0;
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-            HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c0, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
+            first_sweep<T>(ctx, ws, ws.c0, spans, &nb1);
             if (!ws.gram_is_full) HIPCHK(hipMemsetAsync(ws.slot_of, 0xff, (size_t)ctx->n_pad * sizeof(int32_t), st));   // nothing cached yet
-        } else if (sub1 || scr1) {
-            Lookahead<T>::ensure(ctx, ws, kcap);
-            bool rescue = false;
-            if (route.rescue) {
-                // the scan of the declined attempt's log — its state, logs and c~0 are still in place: nothing has been reset yet
-                uint32_t found = 0;
-                // (a decline by the exact re-check alone left the list of the columns that failed it: no scan)
-                const bool from_recheck = (route.rescue_why & kReasonRechecked) != 0u && (route.rescue_why & (kReasonPositions | kReasonLog)) == 0u;
-                if (scr1) HIPCHK(scr_rescue_scan(ctx, ws, tol, from_recheck, &found));
-                rescue = scr1 && found >= 1u && found <= screen_rescue_cap();
-                if (std::getenv("SS_HIP_SUB_DEBUG")) std::fprintf(stderr, "[screened form, rescue] the scan lists %u columns the ranking missed\n", found);
-                if (!rescue) { ctx->stats.screen_redone += 1; Route r = route; r.rescue = false; r.no_sub = true; return retry(r); }
-                ctx->stats.screen_rescue_tried += 1;
-            }
-            if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_direct ? y : (const T*)nullptr, incy));     // x, d, flags, DevState, r = y (OMP: done above)
-            // (the screened form's first pass — A^T y over all columns — reads the half-precision copy too: screen.hip, k_scr_first)
-            const bool first16 = scr1 && screen_first16_usable(ctx);
-            uint32_t nb1 = 0;
-            if (!first16) {
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-                HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c0, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-                if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
-            }
-            if (sub1) {
-                HIPCHK(sub_single(ctx, ws, tol, max_iter));
-            } else {
-                // (6 = the screening pass over the fp16 copy of A, 7 = the first pass when it runs there too)
-                hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, e4 = nullptr, e5 = nullptr;
-                if (prof && first16 && !rescue) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); ctx->prof_kind.push_back(7); ++nprof; }
-                if (prof) { e2 = prof_event(ctx, 2 * nprof); e3 = prof_event(ctx, 2 * nprof + 1); e4 = prof_event(ctx, 2 * nprof + 2); e5 = prof_event(ctx, 2 * nprof + 3); }
-                HIPCHK(scr_single(ctx, ws, tol, max_iter, first16, e0, e1, e2, e3, e4, e5, omp, rescue));
-                if (prof) { ctx->prof_kind.push_back(6); ctx->prof_kind.push_back(8); nprof += 2; }      // (6 = the screening pass, 8 = the path kernel)
-            }
-        } else if (la) {
+        } else if (f.la) {
             Lookahead<T>::ensure(ctx, ws, kcap);
             enter_full_gram();
-            HIPCHK(launch_la_reset<T>(ctx, ws, !ws.gram_is_full, y_direct ? y : (const T*)nullptr, incy));     // x, d, flags, slot map, exchange area, DevState, r = y
-            uint32_t nb1 = 0;
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-            HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c0, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
+            HIPCHK(launch_la_reset<T>(ctx, ws, !ws.gram_is_full, y_dev, incy));     // x, d, flags, slot map, exchange area, DevState, r = y
+            first_sweep<T>(ctx, ws, ws.c0, spans, &nb1);
             // Speculative form (fp32): the default
             // (la_fused = 3).  It also runs where the resident kernel cannot (dictionaries too wide for one
             // launch to own every column).
             const bool solo_wanted = ctx->la_fused >= 3;
             // (not with the full Gram matrix as the cache: there every entering column's row slice is a gather of
             // 256 scattered entries of a 256-KiB row in the iteration's chain — 1.81 ms per C2 solve against 1.55 ms)
-            solo = solo_wanted && !no_solo && ctx->solo_off_solves == 0 && sizeof(T) == 4 &&
-                   (!ws.gram_is_full || ctx->solo_full_gram) && la_solo_usable(ctx);
-            if (solo_wanted && !solo && ctx->solo_off_solves > 0 && !no_solo) ctx->solo_off_solves -= 1;
-            solo_started = solo;
-            early = solo && ctx->early_solo && sizeof(T) == 4 && !ws.gram_is_full && ctx->n > 32u * 512u && ws.gcap >= 160 &&
-                    ctx->sweep32_variant == 0 && ws.subg != nullptr && !ws.la_dbg;
-            if (early) {
+            ps.solo = solo_wanted && !no_solo && ctx->solo_off_solves == 0 && sizeof(T) == 4 &&
+                      (!ws.gram_is_full || ctx->solo_full_gram) && la_solo_usable(ctx);
+            if (solo_wanted && !ps.solo && ctx->solo_off_solves > 0 && !no_solo) ctx->solo_off_solves -= 1;
+            ps.solo_started = ps.solo;
+            ps.early = ps.solo && ctx->early_solo && sizeof(T) == 4 && !ws.gram_is_full && ctx->n > 32u * 512u && ws.gcap >= 160 &&
+                       ctx->sweep32_variant == 0 && ws.subg != nullptr && !ws.la_dbg;
+            if (ps.early) {
                 // resident tier of the launch queued behind the solo group (the last step of the path)
                 uint32_t lc = std::min<uint32_t>((ws.dims.kcap + 15u) & ~15u, kLaLdsSmall);
                 if (ctx->la_fused < 2 || !la_persist_usable(ctx, lc)) lc = 0;
-                early_lds_cols = lc;
-                hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-                if (prof) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); e2 = prof_event(ctx, 2 * nprof + 2); e3 = prof_event(ctx, 2 * nprof + 3); }
-                early_prologue(ctx, ws, nb1, tol, max_iter, lc, e0, e1, e2, e3);
-                // 5 = the main launch of an early-form pass (its share of the columns): both passes of the solve are timed
-                if (prof) { ctx->prof_kind.push_back(5); ctx->prof_kind.push_back(5); nprof += 2; }
+                ps.early_lds_cols = lc;
+                // (the main launch of each early-form pass covers its share of the columns: both passes of the solve are timed)
+                const EventPair pass1 = spans.span(ProfKind::EarlyPass), pass2 = spans.span(ProfKind::EarlyPass);
+                early_prologue(ctx, ws, nb1, tol, max_iter, lc, pass1, pass2);
                 // The typical solve is complete with what is queued now: its epilogue (state, x, record) goes right
                 // behind instead of after a trip through the host (host notices `done`, three enqueues: ~70 us).
                 // Should the pump below have to queue more work, the epilogue is simply issued again at the end.
                 enqueue_epilogue();
                 spec_epilogue = true;
             } else {
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (prof) { e0 = prof_event(ctx, 2 * nprof); e1 = prof_event(ctx, 2 * nprof + 1); }
-                const uint32_t fc = Lookahead<T>::init(ctx, ws, nb1, tol, solo, e0, e1);
-                // (events were recorded only if a sweep was launched; 4 = the 64-column first sweep, 3 = a 32-column one)
-                if (prof && fc != 0) { ctx->prof_kind.push_back(fc > 32 ? 4 : 3); ++nprof; }
+                // (a span only where a sweep is launched: none with the full Gram matrix as the cache)
+                const uint32_t fc = Lookahead<T>::first_cols(ctx, ws);
+                Lookahead<T>::init(ctx, ws, nb1, tol, ps.solo, fc == 0 ? EventPair{} : spans.span(fc > 32 ? ProfKind::Sweep64First : ProfKind::Sweep32));
             }
-        } else if (ro) {
+        } else if (f.ro) {
             // c = A^T y in reference order, first pick with the column norm as a chain dot product
-            HIPCHK(launch_ro_sweep<T>(ctx, ws.rhs, 0, ws.c, 0, ws.dims.n_pad, 1, 1u, ws.pmax_val, ws.pmax_idx, ws.dims.pmax_stride, &ro_parts, ws.st, false));
-            HIPCHK(launch_ro_init<T>(ctx, ws, 1u, ro_parts, tol));
+            HIPCHK(launch_ro_sweep<T>(ctx, ws.rhs, 0, ws.c, 0, ws.dims.n_pad, 1, 1u, ws.pmax_val, ws.pmax_idx, ws.dims.pmax_stride, &ps.ro_parts, ws.st, false));
+            HIPCHK(launch_ro_init<T>(ctx, ws, 1u, ps.ro_parts, tol));
         } else if (!omp) {
-            // c = A^T y  (residual_vector with x = 0, homotopy-cpu.cpp:215)
-            uint32_t nb1 = 0;
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof), st)); }
-            HIPCHK(launch_sweep<T>(ctx, ws.rhs, rhs_stride, 1, ws.c, nullptr, ws.pmax_val, ws.pmax_idx, &nb1, ws.st));
-            if (prof) { HIPCHK(hipEventRecord(prof_event(ctx, 2 * nprof + 1), st)); ctx->prof_kind.push_back(1); ++nprof; }
+            first_sweep<T>(ctx, ws, ws.c, spans, &nb1);
             HIPCHK(launch_init<T>(ctx, ws, 1, nb1, tol));
             HIPCHK(launch_rp<T>(ctx, ws, 1));
         }
 
-        PumpState ps;
-        ps.solo = solo; ps.solo_started = solo_started; ps.early = early; ps.early_lds_cols = early_lds_cols; ps.nprof = nprof;
-        if (sub1 || scr1 || scr64 || scr64r) {
+        // ---- pump: the rounds the host has to queue ----
+        if (f.sub1 || f.scr1 || f.scr64 || f.scr64r) {
             // (everything is queued: selection, the solve, the check)
-        } else if ((la && ctx->la_fused) || la_omp) {
-            if (!pump_fused<T>(ctx, ws, tol, max_iter, la, la_omp, prof, ps)) {
+        } else if ((f.la && ctx->la_fused) || f.la_omp) {
+            if (!pump_fused<T>(ctx, ws, tol, max_iter, f.la, f.la_omp, spans, ps)) {
                 set_err(err, errlen, "solve: internal error, lookahead loop made no progress");
                 return SS_HIP_ERUNTIME;
             }
         } else {
-            pump_rounds<T>(ctx, ws, tol, max_iter, la, ro, omp, ro_parts, rhs_stride, prof, ps);
+            pump_rounds<T>(ctx, ws, tol, max_iter, f.la, f.ro, omp, spans, ps);
         }
-        solo = ps.solo; nprof = ps.nprof; pump_enqueued = ps.enqueued;
 
-        if (!(spec_epilogue && !pump_enqueued)) enqueue_epilogue();
+        // ---- epilogue and verdict ----
+        if (!(spec_epilogue && !ps.enqueued)) enqueue_epilogue();
         HIPCHK(hipStreamSynchronize(st));
         const DevState hs = *static_cast<const DevState*>(ctx->hs_pinned);
-        Forms eff = forms;
-        eff.sub1 = sub1; eff.scr1 = scr1; eff.scr64 = scr64; eff.scr64r = scr64r;      // (after the step-aside counters)
         {
             bool report = false;
-            const int vrc = attempt_verdict<T>(ctx, route, eff, hs, next, again, &report, err, errlen);
+            const int vrc = attempt_verdict<T>(ctx, route, f, hs, next, again, &report, err, errlen);
             if (!report) return vrc;
         }
+        // ---- account: the caller's outputs, the statistics ----
         if (iter_out) *iter_out = hs.iter;
         if (err_out) *err_out = hs.c_inf;
-        if (la && ws.la_dbg && !scr64) {                 // (fp64 screened form: the stamps are the sub-context's, dumped by its solve)
+        if (f.la && ws.la_dbg && !f.scr64) {                 // (fp64 screened form: the stamps are the sub-context's, dumped by its solve)
             if (const char* path = std::getenv("SS_HIP_LA_DEBUG")) {
                 std::vector<uint64_t> tsb(2048 * 8);
                 HIPCHK(hipMemcpy(tsb.data(), ws.la_dbg, tsb.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -1727,7 +1682,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
 
         ctx->stats.solves += 1;
         ctx->single_solves += 1;
-        if (solo_started) {
+        if (ps.solo_started) {
             // Speculative launches that failed their check cost a replay and the rest of the solve in the
             // resident form; contexts whose problems do that on most solves stop speculating for a while.
             ctx->stats.solo_solves += 1;
@@ -1740,9 +1695,9 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             if (path != nullptr) dump_solo_debug<T>(ws, hs, path);
         }
         ctx->stats.iterations += hs.iter;
-        if (la || la_omp) ctx->stats.lookahead_sweeps += hs.nsweeps;
-        if (ro) ctx->stats.ro_resweeps += hs.nsweeps;
-        if (prof) account_profile<T>(ctx, nprof, scr_launches, hs);
+        if (f.la || f.la_omp) ctx->stats.lookahead_sweeps += hs.nsweeps;
+        if (f.ro) ctx->stats.ro_resweeps += hs.nsweeps;
+        if (prof) account_profile<T>(ctx, scr_launches, hs);
         return SS_HIP_OK;
     });
 }
@@ -2181,15 +2136,16 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
             size_t ncq = 0;                                  // timed k_la_cq launches of this chunk (profiling on)
             if (sub_chunk) {
                 const bool timed = ctx->profiling != 0;
-                hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-                if (timed) { e0 = prof_event(ctx, 0); e1 = prof_event(ctx, 1); e2 = prof_event(ctx, 2); if (!ctx->ev_sub_sel) HIPCHK(hipEventCreate(&ctx->ev_sub_sel)); }
-                HIPCHK(launch_sub_form(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, e0, e1, e2));
+                EventPair ev;
+                hipEvent_t verified = nullptr;
+                if (timed) { ev = { prof_event(ctx, 0), prof_event(ctx, 1) }; verified = prof_event(ctx, 2); if (!ctx->ev_sub_sel) HIPCHK(hipEventCreate(&ctx->ev_sub_sel)); }
+                HIPCHK(launch_sub_form(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, ev, verified));
                 if (timed) {
-                    HIPCHK(hipEventSynchronize(e2));
+                    HIPCHK(hipEventSynchronize(verified));
                     float ms = 0.f;
-                    HIPCHK(hipEventElapsedTime(&ms, e0, e1)); ctx->stats.sub_solve_ms += ms;
-                    if (std::getenv("SS_HIP_SUB_DEBUG")) { float ms2 = 0.f; HIPCHK(hipEventElapsedTime(&ms2, e0, ctx->ev_sub_sel)); std::fprintf(stderr, "[subset form] select %.3f ms, solve %.3f ms\n", ms2, ms - ms2); }
-                    HIPCHK(hipEventElapsedTime(&ms, e1, e2)); ctx->stats.sub_verify_ms += ms;
+                    HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b)); ctx->stats.sub_solve_ms += ms;
+                    if (std::getenv("SS_HIP_SUB_DEBUG")) { float ms2 = 0.f; HIPCHK(hipEventElapsedTime(&ms2, ev.a, ctx->ev_sub_sel)); std::fprintf(stderr, "[subset form] select %.3f ms, solve %.3f ms\n", ms2, ms - ms2); }
+                    HIPCHK(hipEventElapsedTime(&ms, ev.b, verified)); ctx->stats.sub_verify_ms += ms;
                     HIPCHK(hipEventElapsedTime(&ms, ctx->ev_c0a, ctx->ev_c0b));
                     ctx->stats.c0_gemm_ms += ms;
                     ctx->stats.c0_gemm_flops += 2.0 * (double)rows * (double)ldm * (double)np;
@@ -2473,7 +2429,7 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<double>& c)
     // side by side (screen.hip: launch_screen64_batch) — one pass over the fp16 copy ranks every signal's columns, the paths run in as
     // many workgroups at once, every signal's states are certified by a screening pass of its own; what a slot's certificate does not
     // cover is solved again alone, through the remaining tiers
-    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 && ctx->res_off_solves == 0) {
+    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_aside.off == 0 && ctx->res_aside.off == 0) {
         bool usable = false;
         try { HIPCHK(hipSetDevice(ctx->device)); usable = screen64_batch_usable(ctx); } catch (const HipFail&) { usable = false; }
         if (usable) return solve_batch_res64(ctx, c);
@@ -2601,8 +2557,8 @@ int omp_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
 
 int omp_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<double>& c)
 {
-    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_off_solves == 0 &&
-        ctx->res_off_solves == 0) {
+    if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->la_fused >= 1 && ctx->screen_resident && ctx->sub_aside.off == 0 &&
+        ctx->res_aside.off == 0) {
         bool usable = false;
         try { HIPCHK(hipSetDevice(ctx->device)); usable = screen64_batch_usable(ctx); } catch (const HipFail&) { usable = false; }
         if (usable) return solve_batch_res64(ctx, c, true);
@@ -3209,7 +3165,8 @@ int ss_hip_set_option(ss_hip_ctx* ctx, const char* key, long value)
     if (!std::strcmp(key, "screen_single")) {
         // (setting the option also forgets what the context has learnt about its signals: the step-aside counters start again)
         ctx->screen_single = (int)std::max<long>(0, std::min<long>(2, value));
-        ctx->sub_off_solves = 0; ctx->sub_seen = 0; ctx->sub_failed = 0; ctx->res_off_solves = 0; ctx->res_seen = 0; ctx->res_failed = 0;
+        ctx->sub_aside.reset();
+        ctx->res_aside.reset();
         return SS_HIP_OK;
     }
     if (!std::strcmp(key, "screen_first16")) { ctx->screen_first16 = value != 0 ? 1 : 0; return SS_HIP_OK; }

@@ -1663,7 +1663,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
 
 // r = y in ws.rhs (block 0); c0 = A^T y in ws.c0 — or, first16, nothing yet: the first pass runs here, over the fp16 copy
 // (k_scr_first; ws.c0 then holds c~0 with the subset's entries exact).  Everything on the context's stream.  Profiling events:
-// e0, e1 around the half-precision first pass, e2, e3 around the screening pass.
+// `first` around the half-precision first pass, `screen` around the screening pass, `path` around the path kernel.
 // (y in LDS: 4 ldm bytes + the reduction scratch — beyond 64 KiB the kernel's dynamic-LDS ceiling is raised first)
 template <typename TY>
 static bool scr_first_attr()
@@ -1741,8 +1741,8 @@ static hipError_t launch_scr_first(ss_hip_ctx* ctx, ScreenState* S, const TY* y,
     return hipGetLastError();
 }
 
-hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, hipEvent_t e0,
-                              hipEvent_t e1, hipEvent_t e2, hipEvent_t e3, hipEvent_t e4, hipEvent_t e5, bool omp, bool rescue)
+hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first,
+                              EventPair screen, EventPair path, bool omp, bool rescue)
 {
     // (rescue: the second attempt on a signal the first one declined — no first pass; the selection ranks S->rank, where the columns the
     // scan of the first attempt's log found missing sit on top: launch_screen_rescue_scan)
@@ -1760,9 +1760,9 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     constexpr uint32_t NT = kSbS / kSgT;
     uint32_t nwmax = 0;
     if (first16 && !rescue) {
-        if (e0) (void)hipEventRecord(e0, s);
+        if (first.a) (void)hipEventRecord(first.a, s);
         { const hipError_t ef = launch_scr_first<float>(ctx, S, (const float*)ws.rhs, ws.c0, S->wmax, &nwmax); if (ef != hipSuccess) return ef; }
-        if (e1) (void)hipEventRecord(e1, s);
+        if (first.b) (void)hipEventRecord(first.b, s);
     }
     if (rescue) {
         if (S->rank == nullptr || !first16) return hipErrorInvalidConfiguration;
@@ -1775,25 +1775,25 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     hipLaunchKernelGGL(k_sgram_sum, dim3((kSbS * kSbS + 255) / 256 + (first16 ? kSbS : 0u)), dim3(256), 0, s, (const float*)S->gs_part, nsplit, S->gs,
                        At, ldm, (const float*)ws.rhs, (const uint32_t*)B.sub, n, ws.c0);
     // the path on the subset: the resident kernel (resident.hip: Gram values in registers, four barriers per iteration) or, option
-    // screen_resident = 0, k_sub_solve (subbatch.hip) — the same log either way (e4, e5: profiling events around it)
-    if (e4) (void)hipEventRecord(e4, s);
+    // screen_resident = 0, k_sub_solve (subbatch.hip) — the same log either way (path: profiling events around it)
+    if (path.a) (void)hipEventRecord(path.a, s);
     if (ctx->screen_resident && res_solve_usable<float>()) {
         const ResLog<float> log{ B.hdr, nullptr, B.pcol, B.LX, B.LD };
         (void)launch_res_solve<float>(ctx, 1, (const float*)S->gs, kSbS, 0, (const float*)ws.c0, 0, (const uint32_t*)B.sub, tol, max_iter, ws.dims.kcap, log, ws.x, 0,
                                       ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
     } else
         (void)launch_sub_solve(ctx, ws, B, 1, (const float*)S->gs, kSbS, first16 ? 2 : 1, ws.c0, tol, max_iter);
-    if (e5) (void)hipEventRecord(e5, s);
+    if (path.b) (void)hipEventRecord(path.b, s);
     hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs,
                        (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
                        (const float*)S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, first16 ? 1 : 0,
                        fl, omp ? 1 : 0);
-    if (e2) (void)hipEventRecord(e2, s);
+    if (screen.a) (void)hipEventRecord(screen.a, s);
     hipLaunchKernelGGL(k_scr_gemm<3>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kSbS), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
                        (const float*)S->anorm, (const float*)S->rn2p, kScrRhs, (const float*)S->tab, (const uint32_t*)B.sub, kSbS, (const float*)S->meta,
                        ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 0u, fl,
                        first16 ? (const float*)ws.c0 : (const float*)nullptr);
-    if (e3) (void)hipEventRecord(e3, s);
+    if (screen.b) (void)hipEventRecord(screen.b, s);
     // the columns that pass left undecided, exactly (an empty list: the launch returns at once)
     if (fl != nullptr)
         hipLaunchKernelGGL((k_scr_recheck<float>), dim3(kScrRecheckWgs), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs, (const uint32_t*)B.hdr, (const float*)nullptr,
@@ -2022,7 +2022,7 @@ double* screen64_xsub(ss_hip_ctx* ctx) { return scr_of(ctx) ? scr_of(ctx)->xsub 
 // c0 = A^T y is in c0 (device): the kS64Sub columns with the largest |c0|, gathered into the sub-context's dictionary
 // (c0 == nullptr: the first pass runs here, over the fp16 copy — y = the signal (device, ldm entries): k_scr_first ranks the columns,
 // the selection reports what the columns left out stay below (meta[6]), k_s64_residuals certifies state 0)
-hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, hipEvent_t e0, hipEvent_t e1)
+hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, EventPair first)
 {
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || S->sub == nullptr) return hipErrorInvalidConfiguration;
@@ -2030,10 +2030,10 @@ hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, h
     const uint32_t n = (uint32_t)ctx->n, np = ctx->n_pad;
     if (c0 != nullptr) hipLaunchKernelGGL(k_s64_cabs, dim3((np + 255) / 256), dim3(256), 0, s, c0, n, np, S->cabs);
     else {
-        if (e0) (void)hipEventRecord(e0, s);
+        if (first.a) (void)hipEventRecord(first.a, s);
         const hipError_t ef = launch_scr_first<double>(ctx, S, y, S->cabs);
         if (ef != hipSuccess) return ef;
-        if (e1) (void)hipEventRecord(e1, s);
+        if (first.b) (void)hipEventRecord(first.b, s);
     }
     (void)launch_select_top(ctx, S->cabs, n, np, kS64Sub, S->sublist, S->sublist + kS64Sub, reinterpret_cast<float*>(S->sublist + kS64Sub + 1),
                             c0 == nullptr ? S->meta + 6 : nullptr);
@@ -2045,7 +2045,7 @@ hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, h
 // After the sub-context's solve (T iterations, synchronised): the certificate of its T states against all columns, the
 // solution scattered into x, the verdict into the slot's state.  y = the signal (device, ldm entries, zero padded).
 hipError_t screen64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double* y, uint32_t T, double tol, double c_inf, uint32_t K,
-                            hipEvent_t e2, hipEvent_t e3, bool omp, bool first16)
+                            EventPair screen, bool omp, bool first16)
 {
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || S->sub == nullptr || T == 0u || T > kS64Rhs) return hipErrorInvalidConfiguration;
@@ -2057,7 +2057,7 @@ hipError_t screen64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double
     hipLaunchKernelGGL(k_s64_residuals, dim3(ldm / 64u), dim3(256), 0, s, static_cast<const double*>(S->sub->At), ldm, y, slog, T,
                        (const double*)S->xd, tol, (const float*)S->meta, S->r16, S->rn2p, S->tab, S->ctl, reinterpret_cast<uint32_t*>(S->meta) + 3,
                        first16 ? 1 : 0);
-    if (e2) (void)hipEventRecord(e2, s);
+    if (screen.a) (void)hipEventRecord(screen.a, s);
     // (up to 160 states in ONE pass over the fp16 copy — five tiles of 32 per workgroup —, the rest in passes of 96)
     for (uint32_t k0 = 0; k0 < T;) {
         const bool wide = T - k0 > kScrRhs;
@@ -2080,7 +2080,7 @@ hipError_t screen64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double
                                ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, cnt, scr_skew(), 0u);
         k0 += cnt;
     }
-    if (e3) (void)hipEventRecord(e3, s);
+    if (screen.b) (void)hipEventRecord(screen.b, s);
     hipLaunchKernelGGL(k_s64_finish, dim3((kS64Sub + 255) / 256), dim3(256), 0, s, (const uint32_t*)S->sublist, (const double*)S->xsub, n, ws.x,
                        ws.st, (const uint32_t*)S->ctl, T, c_inf, K);
     return hipGetLastError();
@@ -2134,8 +2134,8 @@ hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, d
     return hipSuccess;
 }
 
-hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, uint32_t max_iter, bool first16, bool omp, hipEvent_t e0,
-                                    hipEvent_t e1, hipEvent_t e2, hipEvent_t e3, hipEvent_t e4, hipEvent_t e5, bool rescue)
+hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, uint32_t max_iter, bool first16, bool omp, EventPair first,
+                                    EventPair screen, EventPair path, bool rescue)
 {
     typedef ResCfg<double> RC;
     ScreenState* S = scr_of(ctx);
@@ -2149,10 +2149,10 @@ hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, doub
         hipLaunchKernelGGL(k_scr_rescue_rank, dim3(std::min<uint32_t>((np + 255u) / 256u, 1024u)), dim3(256), 0, s, (const float*)S->cabs, (const uint32_t*)S->fl,
                            S->rescue_first, S->rescue_count, S->rescue_first2, S->rescue_count2, n, np, S->rank);
     } else if (first16) {
-        if (e0) (void)hipEventRecord(e0, s);
+        if (first.a) (void)hipEventRecord(first.a, s);
         const hipError_t ef = launch_scr_first<double>(ctx, S, y, S->cabs);
         if (ef != hipSuccess) return ef;
-        if (e1) (void)hipEventRecord(e1, s);
+        if (first.b) (void)hipEventRecord(first.b, s);
     } else {
         hipLaunchKernelGGL(k_s64_cabs, dim3((np + 255) / 256), dim3(256), 0, s, (const double*)ws.c0, n, np, S->cabs);
     }
@@ -2160,21 +2160,21 @@ hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, doub
                             reinterpret_cast<float*>(S->sub256 + RC::S + 1), first16 ? S->meta + 6 : nullptr);
     { const hipError_t eg = launch_sgram64(ctx, S->sub256, y, S->gs64_part, S->gs64, ws.c0); if (eg != hipSuccess) return eg; }
     const ResLog<double> log{ S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
-    if (e4) (void)hipEventRecord(e4, s);
+    if (path.a) (void)hipEventRecord(path.a, s);
     { const hipError_t es = launch_res_solve<double>(ctx, 1, S->gs64, (uint32_t)RC::S, 0, ws.c0, 0, S->sub256, tol, max_iter, ws.dims.kcap, log, ws.x, 0, ws.gam,
                                                      ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
       if (es != hipSuccess) return es; }
-    if (e5) (void)hipEventRecord(e5, s);
+    if (path.b) (void)hipEventRecord(path.b, s);
     uint32_t* fl = (ctx->screen_recheck && !omp) ? S->fl : nullptr;      // (the exact re-check decides Homotopy's predicates: not OMP's)
     (void)launch_res_residuals64(ctx, y, log, tol, S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, first16, omp, 1, nullptr, fl);
-    if (e2) (void)hipEventRecord(e2, s);
+    if (screen.a) (void)hipEventRecord(screen.a, s);
     hipLaunchKernelGGL(k_scr_gemm<4>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 4), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
                        (const float*)S->anorm, (const float*)S->rn2p, kS64Rhs, (const float*)S->tab, (const uint32_t*)S->sub256, (uint32_t)RC::S, (const float*)S->meta,
                        ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 1u, fl, first16 ? (const float*)S->cabs : (const float*)nullptr);
     hipLaunchKernelGGL(k_scr_gemm<5>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 5), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
                        (const float*)S->anorm, (const float*)S->rn2p, kS64Rhs, (const float*)S->tab, (const uint32_t*)S->sub256, (uint32_t)RC::S, (const float*)S->meta,
                        ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 2u, fl, first16 ? (const float*)S->cabs : (const float*)nullptr);
-    if (e3) (void)hipEventRecord(e3, s);
+    if (screen.b) (void)hipEventRecord(screen.b, s);
     if (fl != nullptr) {
         // the columns those passes left undecided, exactly, in fp64 (an empty list: the launches return at once)
         const double* At = static_cast<const double*>(ctx->At);

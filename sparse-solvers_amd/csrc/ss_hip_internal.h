@@ -230,7 +230,7 @@ struct Workspace {
     uint64_t* v_min = nullptr;    // [kSoloLogCap][nvwg] per-workgroup best step-length candidate (bits << 32 | column)
     uint64_t* cand_top = nullptr; // [nvwg][kCandPerBlock] per-workgroup best entrant candidates (ordered key << 32 | column)
     uint32_t nvwg = 0;            // workgroups of k_la_verify = ceil(n / kSoloWidth)
-    uint64_t* la_dbg = nullptr;   // [1024][8] stage timestamps of k_la_iter (option "la_debug"), else null
+    uint64_t* la_dbg = nullptr;   // [1024][8] stage timestamps of k_la_iter (environment variable SS_HIP_LA_DEBUG), else null
     uint32_t la_nparts = 0;       // partial maxima written by the last k_la_cq launch
     uint32_t* tile_skip = nullptr; // [b_pad/128 + 1] compact list of GEMM row tiles with a running signal + count
     TraceEntry* trace = nullptr;  // [trace_cap] when tracing is on
@@ -241,6 +241,39 @@ struct SweepConfig {
     int variant = 0;
 };
 
+// A pair of profiling events around one pass of a solve (both null: the solve is not profiled, nothing is recorded)
+struct EventPair { hipEvent_t a = nullptr, b = nullptr; };
+// ... and what such a pair bracketed (homotopy.hip: ProfSpans hands the pairs out, account_profile books them)
+enum class ProfKind : uint8_t {
+    FirstSweep,     // c0 = A^T y, one right-hand side, in the context's precision
+    Sweep32,        // a lookahead sweep of 32 (fp64: up to 64) Gram columns
+    Sweep64First,   // the 64-column first lookahead sweep
+    EarlyPass,      // the main launch of an early-form pass (its share of the columns)
+    Screen,         // the screening pass over the fp16 copy of A
+    FirstReduced,   // the first pass over the fp16 / fp8 copy
+    PathKernel,     // the screened form's path on the subset (resident.hip / k_sub_solve)
+    FusedSweep      // engine 0: the two-right-hand-side sweep of round `round`
+};
+struct ProfSpan { ProfKind kind; uint32_t round; };
+
+// The step-aside window of a form: of every eight signals the form took, did it hand back more than half?  Then the next 64 solves
+// go the other way at once, and the form is tried again.
+struct StepAside {
+    uint32_t seen = 0, failed = 0, off = 0;
+    void note(bool back)
+    {
+        seen += 1;
+        if (back) failed += 1;
+        if (seen >= 8) {
+            if (2 * failed > seen) off = 64;
+            seen = 0;
+            failed = 0;
+        }
+    }
+    bool take() { if (off == 0) return false; off -= 1; return true; }     // true: this solve falls inside the window — skip the form
+    void reset() { *this = StepAside{}; }
+};
+
 }  // namespace sship
 
 struct ss_hip_ctx {
@@ -248,13 +281,13 @@ struct ss_hip_ctx {
     // the per-signal c0 = A^T y rows of the current chunk
     float* gram_full = nullptr;
     uint32_t gram_pitch = 0;
-    // G's memory reserved ahead of its first use: a context that has received a batch of >= 4 signals will likely receive the large
-    // one that forms G — the allocation (the driver clears fresh VRAM: ~0.5 s for 17 GiB) then runs on a helper thread beside the
-    // batches before it instead of in front of the first large one (option gram_reserve; only where G is a small share of the HBM)
     int screen_rescue = 1;                   // a declined screened solve (positions ran out / an outside column beat a state) is scanned for the columns the
                                              // ranking missed and repeated once with those in the subset (screen.hip: launch_screen_rescue_scan)
     int screen_first8 = 1;                   // the screened form's ranking pass over an fp8 copy of A (screen.hip: k_scr_first8); 0 = over the fp16 copy
     int first_pass_elem_bytes = 2;           // what the last reduced-precision first pass read per entry of A (statistics)
+    // G's memory reserved ahead of its first use: a context that has received a batch of >= 4 signals will likely receive the large
+    // one that forms G — the allocation (the driver clears fresh VRAM: ~0.5 s for 17 GiB) then runs on a helper thread beside the
+    // batches before it instead of in front of the first large one (option gram_reserve; only where G is a small share of the HBM)
     void* gram_reserve_thread = nullptr;     // std::thread*
     float* gram_reserved = nullptr;          // what that thread obtained (read after join)
     int gram_reserve = 1;
@@ -266,8 +299,9 @@ struct ss_hip_ctx {
     int sub_attr_set = -1;
     // the subset form steps aside where it does not pay: after a chunk (or a run of single solves) of which it had to hand
     // back more than a third, the next 8 chunks (64 solves) go the other way at once, then it is tried again
-    uint32_t sub_off_chunks = 0, sub_off_solves = 0, sub_seen = 0, sub_failed = 0;
-    uint32_t res_off_solves = 0, res_seen = 0, res_failed = 0;   // ... the same for the resident tier of the fp64 screened form
+    uint32_t sub_off_chunks = 0;
+    sship::StepAside sub_aside;       // single solves in the subset / screened forms
+    sship::StepAside res_aside;       // ... the same for the resident tier of the fp64 screened form
     int screen_recheck = 1;           // option: 1 = columns the screened form's half-precision certificate cannot vouch for are re-checked exactly in fp32
                                       // (screen.hip: k_scr_recheck) instead of failing the signal
     int screen_resident = 1;          // option: 1 = the screened forms run their path in the resident kernel (resident.hip), 0 = the forms before it
@@ -385,7 +419,7 @@ struct ss_hip_ctx {
     void* hs_mapped = nullptr;        // its device address (k_epilogue writes the state there)
     uint32_t* dev_flags = nullptr;    // device address of host_flags
     std::vector<hipEvent_t> prof_events;   // pairs (start, stop) for sweeps of the current solve
-    std::vector<int> prof_kind;            // 2 = fused sweep, 1 = single-RHS sweep
+    std::vector<sship::ProfSpan> prof_spans;   // what each of those pairs bracketed, in the order they were handed out
     hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;
     int solo_attr_set = -1;                // dynamic-LDS attribute of the solo kernel: -1 not tried, 0 refused, 1 set
     int persist_workers[2] = { -1, -1 };   // worker workgroups of k_la_persist per LDS tier (-1 = not queried, 0 = unusable)
@@ -454,9 +488,8 @@ hipError_t launch_select_top(ss_hip_ctx* ctx, const float* v, uint32_t n, uint32
 // the path then screened against all columns by one pass over a half-precision copy of A with a rigorous error bound
 bool screen_form_usable(ss_hip_ctx* ctx);                 // shape / option test + one-time preparation (fp16 copy of A, column norms)
 bool screen_first16_usable(const ss_hip_ctx* ctx);        // ... with the FIRST pass (A^T y) over the half-precision copy too
-hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, hipEvent_t e0 = nullptr,
-                              hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr, hipEvent_t e3 = nullptr, hipEvent_t e4 = nullptr, hipEvent_t e5 = nullptr,
-                              bool omp = false, bool rescue = false);
+hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first = {},
+                              EventPair screen = {}, EventPair path = {}, bool omp = false, bool rescue = false);      // (pairs: around the reduced-precision first pass, the screening pass, the path kernel)
 // the rescue of a declined solve: the scan of its log for the columns the ranking missed (-> their number), see screen.hip
 hipError_t launch_screen_rescue_scan(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, bool from_recheck, uint32_t* count_out);
 uint32_t screen_rescue_cap();
@@ -478,14 +511,13 @@ void screen_free(ss_hip_ctx* ctx);
 bool screen64_usable(ss_hip_ctx* ctx);
 ss_hip_ctx* screen64_sub(ss_hip_ctx* ctx);
 double* screen64_xsub(ss_hip_ctx* ctx);
-hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);   // (c0 = nullptr: the first pass over the fp16 copy, here; e0, e1 around it)
+hipError_t screen64_gather(ss_hip_ctx* ctx, const double* c0, const double* y, EventPair first = {});   // (c0 = nullptr: the first pass over the fp16 copy, here; `first` around it)
 hipError_t screen64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double* y, uint32_t T, double tol, double c_inf, uint32_t K,
-                            hipEvent_t e2 = nullptr, hipEvent_t e3 = nullptr, bool omp = false, bool first16 = false);
+                            EventPair screen = {}, bool omp = false, bool first16 = false);
 // fp64, resident tier (resident.hip): the path on the 256 best-ranked columns in ONE workgroup, everything queued in one go
 bool screen64_resident_usable(ss_hip_ctx* ctx);
 hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, uint32_t max_iter, bool first16, bool omp,
-                                    hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr, hipEvent_t e3 = nullptr,
-                                    hipEvent_t e4 = nullptr, hipEvent_t e5 = nullptr, bool rescue = false);
+                                    EventPair first = {}, EventPair screen = {}, EventPair path = {}, bool rescue = false);
 hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, bool from_recheck, uint32_t* count_out);
 // fp64 batches in the resident tier: a chunk of nslots <= screen64_batch_cap() signals (in ws.y) — one pass over the fp16 copy ranks every signal's
 // columns, the chunk's paths run side by side, each signal's states are certified by a screening pass of its own; verdicts in the slots' states
@@ -495,7 +527,7 @@ hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_
 void screen_debug_recheck(ss_hip_ctx* ctx);               // developer aid (SS_HIP_SUB_DEBUG)
 double screen_read_headroom(ss_hip_ctx* ctx);             // largest (|c~| + eps) / bound of the last screened solve (synchronises)
 hipError_t launch_sub_form(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0, float tol, uint32_t max_iter,
-                           hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, hipEvent_t e2 = nullptr);      // signals one pass of the engine can carry (1 without the LDS-staged sweep)
+                           EventPair solve = {}, hipEvent_t verified = nullptr);      // (solve: around selection + solves; verified: after the check over all columns)
 // list[0..count) = 128-row tiles that still hold a running signal, list[rows/128] = count
 hipError_t launch_tile_list(const ss_hip_ctx* ctx, const DevState* st, uint32_t nslots, uint32_t rows,
                             uint32_t* list);

@@ -1018,22 +1018,22 @@ hipError_t launch_sub_finish_st(ss_hip_ctx* ctx, DevState* st, uint32_t nslots)
 }
 
 hipError_t launch_sub_form(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0, float tol, uint32_t max_iter,
-                           hipEvent_t e0, hipEvent_t e1, hipEvent_t e2)
+                           EventPair solve, hipEvent_t verified)
 {
     if (!sub_form_usable(ctx) || ctx->sub_buf == nullptr || ctx->gram_full == nullptr) return hipErrorInvalidConfiguration;
     const SubBufs B = sub_bufs(ctx, nslots);
     const uint32_t n = (uint32_t)ctx->n;
     hipStream_t s = ctx->stream;
-    if (e0) (void)hipEventRecord(e0, s);
+    if (solve.a) (void)hipEventRecord(solve.a, s);
     (void)launch_sub_select(ctx, B, nslots, c0);
-    if (e0 && ctx->ev_sub_sel) (void)hipEventRecord(ctx->ev_sub_sel, s);
+    if (solve.a && ctx->ev_sub_sel) (void)hipEventRecord(ctx->ev_sub_sel, s);
     (void)launch_sub_solve(ctx, ws, B, nslots, (const float*)ctx->gram_full, ctx->gram_pitch, 0, c0, tol, max_iter);
-    if (e1) (void)hipEventRecord(e1, s);
+    if (solve.b) (void)hipEventRecord(solve.b, s);
     hipLaunchKernelGGL(k_sub_verify, dim3((n + kVsCols - 1) / kVsCols, nslots), dim3(kVsThreads), sub_verify_lds_bytes(), s,
                        (const float*)ctx->gram_full, ctx->gram_pitch, c0, n, ctx->n_pad, (const uint32_t*)B.sub, (const uint32_t*)B.hdr,
                        (const uint32_t*)B.pcol, (const float*)B.LX, (const float*)B.LD, ctx->tie_guard, tol, ws.st);
     (void)launch_sub_finish(ctx, ws, nslots);
-    if (e2) (void)hipEventRecord(e2, s);
+    if (verified) (void)hipEventRecord(verified, s);
     return hipGetLastError();
 }
 

@@ -371,8 +371,8 @@ def test_homotopy_and_omp_interleaved(sship, dtype):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 def test_step_aside_window(sship, dtype):
     """Noisy signals (their paths remove columns) are handed back by the screened form; after eight attempts with
-    more failures than successes the context steps the form aside for the next 64 solves (fp32: sub_off_solves; fp64 resident
-    tier: res_off_solves).  A certifiable signal inside that window skips the form — a route a fresh context does not take — and
+    more failures than successes the context steps the form aside for the next 64 solves (fp32: sub_aside; fp64 resident
+    tier: res_aside).  A certifiable signal inside that window skips the form — a route a fresh context does not take — and
     is still the oracle's.  Setting screen_single again forgets the counters: the fresh route and the fresh words come back."""
     m, n, k = (1024, 8192, 16) if dtype == np.float32 else (2048, 16384, 16)
     A, _, _, _ = make_gaussian_problem(15000 + np.dtype(dtype).itemsize, m, n, k, dtype)
