@@ -29,7 +29,9 @@ extern "C" {
 #define SS_HIP_ABI_VERSION 7     /* (5: the per-reason counters of round 4; 6: screen_rescued / screen_rescue_tried, the colshard _f64 entry points;
                                     7: the OMP batch entry points and their counters; added under 7 since: the IRLS batch
                                     entry points ss_hip_irls_solve_batch_*, option "irls_batch_max", and the counters
-                                    irls_batch_signals / irls_batch_rounds at the end of ss_hip_stats) */
+                                    irls_batch_signals / irls_batch_rounds at the end of ss_hip_stats; classification from compact records:
+                                    ss_hip_set_classes, ss_hip_reconstruct_records_*, ss_hip_class_residuals_*, ss_hip_homotopy_classify_batch_* —
+                                    no new option key, no new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -191,6 +193,57 @@ int ss_hip_omp_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, size_t 
                                        ptrdiff_t y_stride, ptrdiff_t incy,
                                        double tol, uint32_t max_iter, uint32_t kmax,
                                        void* records, char* err, size_t errlen);
+
+/*
+ * Sparse-representation classification from compact records (added under ABI version 7; csrc/classify.hip; NOT in the
+ * reference).  The dictionary's columns are training samples grouped by class; a signal coded by l1 minimisation is assigned
+ * to the class c whose columns alone reconstruct it best, r_c(y) = ||y - A delta_c(x)||_2, and the sparsity concentration
+ * index of x says whether to reject it (Wright et al.; Yang et al., "Fast l1-minimization algorithms for robust face
+ * recognition").  The input is the record of ss_hip_homotopy_solve_batch_compact_* / ss_hip_omp_solve_batch_compact_* (same
+ * kmax): only the record's columns of A are read — sum K_b * m elements, not m * n per signal.
+ * All data pointers may be host or device pointers.  Validation: SS_HIP_EINVAL for a null ctx, records, Y, Yhat or best, an
+ * IRLS or column-sharded context, kmax outside 1..4096, records not 8-byte aligned, non-positive increments, r_stride <
+ * num_classes, class_residuals / classify before set_classes, a label >= num_classes, a record index >= n (found on the
+ * device, never used as an address; the outputs of such a call are unspecified); SS_HIP_ETYPE on a dtype mismatch; B == 0
+ * returns SS_HIP_OK and touches nothing.
+ * A TRUNCATED record (K > kmax) does not hold its whole solution: best[b] = 0xffffffff, its row of R and sci[b] are NaN, its
+ * reconstruction is that of the stored entries, and the call still returns SS_HIP_OK.
+ * CONTRACT: signal b's row of R, best[b], sci[b] and row of Yhat are a function of its record, its y, the labels and A —
+ * bit for bit the same alone or in any batch, with host or device pointers, whatever the context did before.  Every sum
+ * runs in one documented order (csrc/classify.hip): no floating-point atomics, no dependence on B or on the
+ * internal chunking.  None of these calls changes what any solve returns.
+ */
+/* class of every dictionary column: labels[n] (host or device), values < num_classes, num_classes >= 1.
+   May be called again to replace them.  Never changes what any solve returns. */
+int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_classes, char* err, size_t errlen);
+
+/* Yhat_b = A x_b for B compact records: row b at Yhat[b*yh_stride + i*incyh], i < m.  The entries are added in the record's
+   order (ascending column), in the context's precision.  Needs no classes. */
+int ss_hip_reconstruct_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax,
+                                   float* Yhat, ptrdiff_t yh_stride, ptrdiff_t incyh, char* err, size_t errlen);
+int ss_hip_reconstruct_records_f64(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax,
+                                   double* Yhat, ptrdiff_t yh_stride, ptrdiff_t incyh, char* err, size_t errlen);
+
+/* R[b*r_stride + c] = ||y_b - A delta_c(x_b)||_2 for c < num_classes (R may be NULL; a class without a stored entry gets
+   ||y_b||_2), best[b] = left-most arg-min over c of that row as stored, sci[b] (may be NULL) =
+   (C * max_c ||delta_c x||_1 / ||x||_1 - 1) / (C - 1) in double — 0 when x == 0, else 1 when C == 1.
+   y_i - (A delta_c x)_i is taken in the context's precision, its square and all sums of squares in double. */
+int ss_hip_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                               const void* records, uint32_t kmax,
+                               float* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+int ss_hip_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                               const void* records, uint32_t kmax,
+                               double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+
+/* ss_hip_homotopy_solve_batch_compact_* followed by ss_hip_class_residuals_* without leaving the device: a host Y is uploaded
+   once, and the records stay in the context's staging when `records` is NULL (otherwise they are also written there: the bytes
+   solve_batch_compact returns).  tol / max_iter as for the solve. */
+int ss_hip_homotopy_classify_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       float tol, uint32_t max_iter, uint32_t kmax, void* records,
+                                       float* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+int ss_hip_homotopy_classify_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       double tol, uint32_t max_iter, uint32_t kmax, void* records,
+                                       double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
 
 /*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)

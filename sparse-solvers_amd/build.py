@@ -53,6 +53,8 @@ HIP_UNITS = [
     ("resident.hip", ["-ffp-contract=off"]),
     # OMP batches in the Gram form: the subset Gram matrices gathered from G, the MFMA certificate over all columns (bounds only)
     ("ompbatch.hip", []),
+    # classification from compact records: products and sums rounded separately, in the documented order (the tests' bounds)
+    ("classify.hip", ["-ffp-contract=off"]),
 ]
 
 

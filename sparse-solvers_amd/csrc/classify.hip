@@ -1,0 +1,773 @@
+// classify.hip — sparse-representation classification on the device, from compact records (include/ss_hip.h):
+//   ss_hip_set_classes, ss_hip_reconstruct_records_*, ss_hip_class_residuals_*, ss_hip_homotopy_classify_batch_*.
+//
+// A record (ss_hip_homotopy_solve_batch_compact_*) holds the K non-zero coefficients of a solution as (column, value) pairs.  The
+// class residual r_c(y) = ||y - A delta_c(x)||_2 needs only the record's columns of class c, and A is stored column-contiguous
+// (ctx->At, [n_pad][ldm]): every such column is one contiguous run of ldm elements.  Three kernels per chunk of signals:
+//
+//   k_cls_prepare   one workgroup per signal.  Reads K, idx[], val[] and each column's class, orders the entries by
+//                   (class, position in the record) — a stable counting rank, a function of the record alone — writes the segment
+//                   list (class, first entry, count) and, in double from the record's values, the per-class ||delta_c x||_1,
+//                   ||x||_1 and the sparsity concentration index.  A column index >= n marks the signal invalid; it is never used
+//                   as an address.
+//   k_cls_residual  grid = (row tile, signal).  A workgroup of 256 threads holds a tile of 1024 rows of y in registers (thread t:
+//                   fp32 rows 4t .. 4t+3 of the tile, fp64 rows 2t, 2t+1 and 512+2t, 512+2t+1: 16-byte loads along a column; rows
+//                   m .. ldm-1 of At are zero).  For each segment it forms acc_i = sum_k v_k * A[i][col_k] over the segment's
+//                   entries in the prepared order, eight columns' loads in flight, then sums (y_i - acc_i)^2 over the tile.  With
+//                   STORE it runs one segment over all entries and stores acc: ss_hip_reconstruct_records_*.
+//   k_cls_finish    one workgroup per signal: the tile partials per segment added up, square roots, the row of R, the arg-min.
+//
+// SUMMATION ORDER (the tests' tolerances follow from it; build flag -ffp-contract=off: products and sums are rounded separately):
+//   acc_i      starts at 0 and takes v_k * A[i][col_k] one entry after the other in the prepared order, in the context's precision;
+//   d_i        = y_i - acc_i in the context's precision; its square and every sum of squares in double;
+//   a thread   adds its four squares in ascending row order;
+//   a wave     adds its 64 thread sums by the butterfly lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 (every lane ends with the same word);
+//   a segment  = the wave sums taken one after the other: tiles ascending, inside a tile waves 0, 1, 2, 3;
+//   ||y||_2    the same way from y_i^2;
+//   ||delta_c x||_1 = |v| of the segment's entries one after the other in the prepared order; ||x||_1 = those sums one after the other
+//              in ascending class order.
+// No floating-point atomics; nothing depends on B, on the chunking or on the launch geometry: a signal's words are a function of its
+// record, its y, the labels and A.
+#include "ss_hip_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+namespace sship {
+
+namespace {
+
+constexpr uint32_t kClsThreads = 256;
+constexpr uint32_t kClsTileRows = 1024;                  // rows of y a workgroup holds: four per thread
+constexpr uint32_t kClsInFlight = 8;                     // columns whose loads a thread has in flight
+constexpr uint32_t kClsChunkMax = 1024;                  // most signals per internal chunk ...
+constexpr size_t kClsChunkBytes = (size_t)64 << 20;      // ... and the byte budget of a chunk's workspace (never changes a result)
+constexpr uint32_t kClsTruncated = 1u, kClsInvalid = 2u; // per-signal flags
+constexpr uint32_t kSigWords = 4;                        // per-signal header: K stored, segments, flags, unused
+
+struct ClassifyState {
+    uint32_t* labels = nullptr;        // [n_pad] class of every column (padding columns: 0)
+    uint32_t num_classes = 0;
+    unsigned char* arena = nullptr;    // the workspace of one chunk, carved per call
+    size_t arena_bytes = 0;
+    unsigned char* y_all = nullptr;    // classify: the batch's signals, uploaded once (a host Y)
+    size_t y_all_bytes = 0;
+    unsigned char* rec_all = nullptr;  // classify: the batch's records (the caller's are on the host, or not asked for)
+    size_t rec_all_bytes = 0;
+};
+
+struct HipFail { hipError_t code; const char* what; };
+#define CLS_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw HipFail{ e_, #expr }; } while (0)
+
+template <typename F>
+int guarded(char* err, size_t errlen, const char* prefix, F&& body)
+{
+    try {
+        return body();
+    } catch (const HipFail& f) {
+        (void)hipGetLastError();
+        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
+        return f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
+    } catch (const std::bad_alloc&) {
+        set_err(err, errlen, std::string(prefix) + ": out of host memory");
+        return SS_HIP_ENOMEM;
+    }
+}
+
+bool on_device(const void* p)
+{
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();       // unregistered host memory
+        return false;
+    }
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
+}
+
+ClassifyState* state_of(ss_hip_ctx* ctx)
+{
+    if (!ctx->cls) ctx->cls = new ClassifyState();
+    return static_cast<ClassifyState*>(ctx->cls);
+}
+
+void grow(unsigned char*& p, size_t& have, size_t need, const char* what)
+{
+    if (have >= need) return;
+    if (p) CLS_CHK(hipFree(p));
+    p = nullptr;
+    have = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need);
+    if (e != hipSuccess) { p = nullptr; throw HipFail{ e, what }; }
+    have = need;
+}
+
+inline size_t record_bytes(uint32_t kmax, size_t elem) { return (16 + (size_t)kmax * (4 + elem) + 7) & ~(size_t)7; }
+
+// carves 256-byte aligned pieces out of the arena; with base == nullptr it only adds up
+struct Carver {
+    unsigned char* base;
+    size_t off = 0;
+    explicit Carver(unsigned char* b) : base(b) {}
+    template <typename P> P* take(size_t count)
+    {
+        P* p = base ? reinterpret_cast<P*>(base + off) : nullptr;
+        off += (count * sizeof(P) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// ---- kernels -------------------------------------------------------------------------------------------------------------------
+
+// (the values of a fp64 record sit at 16 + 4 kmax: 4-byte aligned only when kmax is odd)
+__device__ inline float load_val(const unsigned char* p, uint32_t e, float) { return reinterpret_cast<const float*>(p)[e]; }
+__device__ inline double load_val(const unsigned char* p, uint32_t e, double)
+{
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(p) + 2u * e;
+    return __longlong_as_double((long long)(((unsigned long long)w[1] << 32) | w[0]));
+}
+
+__global__ __launch_bounds__(256)
+void k_cls_check_labels(const uint32_t* __restrict__ labels, uint32_t n, uint32_t C, uint32_t* __restrict__ bad)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < n && labels[j] >= C) atomicMin(bad, j);
+}
+
+// labels == nullptr: every column in one class (the record's own order: reconstruct_records)
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_cls_prepare(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax, uint32_t n, const uint32_t* __restrict__ labels,
+                   uint32_t C, uint32_t segcap, uint32_t* __restrict__ ord_idx, T* __restrict__ ord_val, uint32_t* __restrict__ seg,
+                   double* __restrict__ seg_l1, uint32_t* __restrict__ sig, double* __restrict__ sci, uint32_t* __restrict__ bad,
+                   uint32_t b0)
+{
+    extern __shared__ uint32_t s_mem[];
+    uint32_t* s_cls = s_mem;               // [kmax] class of entry e
+    uint32_t* s_sorted = s_mem + kmax;     // [kmax] class at prepared position p
+    __shared__ uint32_t s_bad, s_nseg;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const unsigned char* r = rec + (size_t)b * rb;
+    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
+    const uint32_t K = Krec < kmax ? Krec : kmax;
+    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+    const unsigned char* valp = r + 16 + (size_t)kmax * 4;
+    ord_idx += (size_t)b * kmax;
+    ord_val += (size_t)b * kmax;
+    seg += (size_t)b * segcap * 3;
+    seg_l1 += (size_t)b * segcap;
+    sig += (size_t)b * kSigWords;
+    if (tid == 0) { s_bad = 0u; s_nseg = 0u; }
+    __syncthreads();
+    for (uint32_t e = tid; e < K; e += 256u) {
+        const uint32_t col = idx[e];
+        uint32_t c = 0u;
+        if (col >= n) s_bad = 1u;
+        else if (labels) c = labels[col];
+        s_cls[e] = c;
+    }
+    __syncthreads();
+    if (s_bad != 0u) {
+        if (tid == 0) {
+            sig[0] = 0u; sig[1] = 0u; sig[2] = kClsInvalid; sig[3] = 0u;
+            sci[b] = __longlong_as_double(0x7ff8000000000000ll);
+            atomicMin(bad, b0 + b);
+        }
+        return;
+    }
+    // stable rank: entries of a smaller class first, then earlier entries of the same class
+    for (uint32_t e = tid; e < K; e += 256u) {
+        const uint32_t c = s_cls[e];
+        uint32_t pos = 0;
+        for (uint32_t j = 0; j < K; ++j) {
+            const uint32_t cj = s_cls[j];
+            pos += (cj < c || (cj == c && j < e)) ? 1u : 0u;
+        }
+        s_sorted[pos] = c;
+        ord_idx[pos] = idx[e];
+        ord_val[pos] = load_val(valp, e, T(0));
+    }
+    __threadfence_block();
+    __syncthreads();
+    // segments: the thread of a segment's first position writes it and adds up its |v| in order
+    for (uint32_t p = tid; p < K; p += 256u) {
+        const uint32_t c = s_sorted[p];
+        if (p != 0u && s_sorted[p - 1u] == c) continue;
+        uint32_t si = 0;
+        for (uint32_t j = 1; j <= p; ++j) si += s_sorted[j] != s_sorted[j - 1u] ? 1u : 0u;
+        uint32_t cnt = 1;
+        while (p + cnt < K && s_sorted[p + cnt] == c) ++cnt;
+        double l1 = 0.0;
+        for (uint32_t q = p; q < p + cnt; ++q) l1 += fabs((double)ord_val[q]);
+        seg[3u * si] = c; seg[3u * si + 1u] = p; seg[3u * si + 2u] = cnt;
+        seg_l1[si] = l1;
+        if (p + cnt == K) s_nseg = si + 1u;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t nseg = s_nseg;
+        double total = 0.0, mx = 0.0;
+        for (uint32_t s = 0; s < nseg; ++s) { const double l = seg_l1[s]; total += l; mx = l > mx ? l : mx; }
+        double v;
+        if (Krec > kmax) v = __longlong_as_double(0x7ff8000000000000ll);
+        else if (!(total > 0.0)) v = 0.0;
+        else if (C <= 1u) v = 1.0;
+        else v = ((double)C * mx / total - 1.0) / (double)(C - 1u);
+        sci[b] = v;
+        sig[0] = K; sig[1] = nseg; sig[2] = Krec > kmax ? kClsTruncated : 0u; sig[3] = 0u;
+    }
+}
+
+template <typename T> struct ClsVec;
+template <> struct ClsVec<float> { typedef float4 type; static constexpr uint32_t W = 4, L = 1; };
+template <> struct ClsVec<double> { typedef double2 type; static constexpr uint32_t W = 2, L = 2; };
+__device__ inline float vget(const float4& v, uint32_t e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+__device__ inline double vget(const double2& v, uint32_t e) { return e == 0 ? v.x : v.y; }
+
+__device__ inline double wave_sum(double s)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
+// STORE: acc of ONE segment over all stored entries goes to yhat ([signals][ldm]); otherwise the tile's partial sums of squares
+// of every segment go to part ([signal][tile][segcap][4 waves]) and those of y to party ([signal][tile][4]).
+template <typename T, bool STORE>
+__global__ __launch_bounds__(256)
+void k_cls_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __restrict__ Y, long long y_stride, long long incy,
+                    const uint32_t* __restrict__ ord_idx, const T* __restrict__ ord_val, uint32_t kmax,
+                    const uint32_t* __restrict__ seg, uint32_t segcap, const uint32_t* __restrict__ sig,
+                    double* __restrict__ part, double* __restrict__ party, T* __restrict__ yhat)
+{
+    typedef typename ClsVec<T>::type V;
+    constexpr uint32_t W = ClsVec<T>::W, L = ClsVec<T>::L, U = kClsInFlight;
+    const uint32_t tile = blockIdx.x, b = blockIdx.y, ntiles = gridDim.x;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t K = sig[(size_t)b * kSigWords], nseg = sig[(size_t)b * kSigWords + 1u], flags = sig[(size_t)b * kSigWords + 2u];
+    ord_idx += (size_t)b * kmax;
+    ord_val += (size_t)b * kmax;
+    seg += (size_t)b * segcap * 3;
+    uint32_t row0[L];
+#pragma unroll
+    for (uint32_t j = 0; j < L; ++j) row0[j] = tile * kClsTileRows + j * (256u * W) + tid * W;
+
+    T yv[L][W];
+    if (!STORE) {
+        const T* y = Y + (long long)b * y_stride;
+        double s = 0.0;
+#pragma unroll
+        for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+            for (uint32_t e = 0; e < W; ++e) {
+                const uint32_t row = row0[j] + e;
+                yv[j][e] = row < m ? y[(long long)row * incy] : T(0);
+                s += (double)yv[j][e] * (double)yv[j][e];
+            }
+        s = wave_sum(s);
+        if (lane == 0u) party[((size_t)b * ntiles + tile) * 4u + wave] = s;
+        if (flags != 0u) return;                       // truncated or invalid: k_cls_finish writes NaN
+    }
+    const uint32_t nsegs = STORE ? (flags & kClsInvalid ? 0u : 1u) : nseg;
+    for (uint32_t s = 0; s < nsegs; ++s) {
+        const uint32_t first = STORE ? 0u : seg[3u * s + 1u], cnt = STORE ? K : seg[3u * s + 2u];
+        T acc[L][W];
+#pragma unroll
+        for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+            for (uint32_t e = 0; e < W; ++e) acc[j][e] = T(0);
+        uint32_t k = 0;
+        for (; k + U <= cnt; k += U) {                  // U columns' loads in flight, added in order
+            V a[U][L];
+            T v[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) {
+                const T* colp = At + (size_t)ord_idx[first + k + u] * ldm;
+                v[u] = ord_val[first + k + u];
+#pragma unroll
+                for (uint32_t j = 0; j < L; ++j) a[u][j] = row0[j] < ldm ? *reinterpret_cast<const V*>(colp + row0[j]) : V{};
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u)
+#pragma unroll
+                for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+                    for (uint32_t e = 0; e < W; ++e) acc[j][e] = acc[j][e] + v[u] * vget(a[u][j], e);
+        }
+        for (; k < cnt; ++k) {
+            const T* colp = At + (size_t)ord_idx[first + k] * ldm;
+            const T v = ord_val[first + k];
+#pragma unroll
+            for (uint32_t j = 0; j < L; ++j) {
+                const V a = row0[j] < ldm ? *reinterpret_cast<const V*>(colp + row0[j]) : V{};
+#pragma unroll
+                for (uint32_t e = 0; e < W; ++e) acc[j][e] = acc[j][e] + v * vget(a, e);
+            }
+        }
+        if (STORE) {
+#pragma unroll
+            for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+                for (uint32_t e = 0; e < W; ++e)
+                    if (row0[j] + e < ldm) yhat[(size_t)b * ldm + row0[j] + e] = acc[j][e];
+        } else {
+            double q = 0.0;
+#pragma unroll
+            for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+                for (uint32_t e = 0; e < W; ++e) {
+                    const T d = yv[j][e] - acc[j][e];
+                    q += (double)d * (double)d;
+                }
+            q = wave_sum(q);
+            if (lane == 0u) part[(((size_t)b * ntiles + tile) * segcap + s) * 4u + wave] = q;
+        }
+    }
+    if (STORE && nsegs == 0u) {
+#pragma unroll
+        for (uint32_t j = 0; j < L; ++j)
+#pragma unroll
+            for (uint32_t e = 0; e < W; ++e)
+                if (row0[j] + e < ldm) yhat[(size_t)b * ldm + row0[j] + e] = T(0);
+    }
+}
+
+template <typename T> __device__ inline T cls_nan();
+template <> __device__ inline float cls_nan<float>() { return __uint_as_float(0x7fc00000u); }
+template <> __device__ inline double cls_nan<double>() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_cls_finish(const uint32_t* __restrict__ seg, uint32_t segcap, const uint32_t* __restrict__ sig, const double* __restrict__ part,
+                  const double* __restrict__ party, uint32_t ntiles, uint32_t C, T* __restrict__ Rb, uint32_t* __restrict__ best)
+{
+    __shared__ T s_yn;
+    __shared__ T s_v[4];
+    __shared__ uint32_t s_c[4];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nseg = sig[(size_t)b * kSigWords + 1u], flags = sig[(size_t)b * kSigWords + 2u];
+    T* R = Rb + (size_t)b * C;
+    seg += (size_t)b * segcap * 3;
+    if (flags != 0u) {
+        for (uint32_t c = tid; c < C; c += 256u) R[c] = cls_nan<T>();
+        if (tid == 0) best[b] = 0xffffffffu;
+        return;
+    }
+    if (tid == 0) {
+        double s = 0.0;
+        for (uint32_t t = 0; t < ntiles * 4u; ++t) s += party[(size_t)b * ntiles * 4u + t];
+        s_yn = (T)sqrt(s);
+    }
+    __syncthreads();
+    const T yn = s_yn;
+    for (uint32_t c = tid; c < C; c += 256u) R[c] = yn;
+    __threadfence_block();
+    __syncthreads();
+    for (uint32_t s = tid; s < nseg; s += 256u) {
+        double q = 0.0;
+        for (uint32_t t = 0; t < ntiles; ++t)
+            for (uint32_t w = 0; w < 4u; ++w) q += part[(((size_t)b * ntiles + t) * segcap + s) * 4u + w];
+        R[seg[3u * s]] = (T)sqrt(q);
+    }
+    __threadfence_block();
+    __syncthreads();
+    // left-most arg-min of the row as stored (a NaN is never smaller)
+    T bv = R[0];
+    uint32_t bc = 0u;
+    for (uint32_t c = tid; c < C; c += 256u) {
+        const T v = R[c];
+        if (c != 0u && (v < bv || (v == bv && c < bc) || (bv != bv && v == v))) { bv = v; bc = c; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const T ov = __shfl_xor(bv, o);
+        const uint32_t oc = (uint32_t)__shfl_xor((int)bc, o);
+        if (ov < bv || (ov == bv && oc < bc) || (bv != bv && ov == ov)) { bv = ov; bc = oc; }
+    }
+    if (lane == 0u) { s_v[wave] = bv; s_c[wave] = bc; }
+    __syncthreads();
+    if (tid == 0) {
+        for (uint32_t w = 1; w < 4u; ++w) {
+            const T ov = s_v[w];
+            const uint32_t oc = s_c[w];
+            if (ov < bv || (ov == bv && oc < bc) || (bv != bv && ov == ov)) { bv = ov; bc = oc; }
+        }
+        best[b] = bc;
+    }
+}
+
+// dst[b * d_stride + i * d_inc] = src[b * ld + i] (a device Yhat whose rows a 2-D copy cannot describe)
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_cls_scatter(const T* __restrict__ src, uint32_t ld, uint32_t m, T* __restrict__ dst, long long d_stride, long long d_inc)
+{
+    const uint32_t b = blockIdx.y;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < m; i += gridDim.x * 256u)
+        dst[(long long)b * d_stride + (long long)i * d_inc] = src[(size_t)b * ld + i];
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+
+// the checks the three record entry points share, in the order they are reported
+template <typename T>
+int check_common(const ss_hip_ctx* ctx, const char* who, const void* records, bool need_records, uint32_t kmax, char* err, size_t errlen)
+{
+    const std::string w(who);
+    if (!ctx) { set_err(err, errlen, w + ": null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 0) { set_err(err, errlen, w + ": this context was created for IRLS"); return SS_HIP_EINVAL; }
+    if (ctx->colshard != nullptr) { set_err(err, errlen, w + ": not available on a column-sharded context"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, w + ": element type mismatch"); return SS_HIP_ETYPE; }
+    if (need_records && !records) { set_err(err, errlen, w + ": records must not be null"); return SS_HIP_EINVAL; }
+    if (kmax == 0 || kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(records) & 7u)) {
+        set_err(err, errlen, w + ": kmax must be 1..4096 and records 8-byte aligned");
+        return SS_HIP_EINVAL;
+    }
+    return SS_HIP_OK;
+}
+
+int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errlen)
+{
+    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    if (!cs || !cs->labels) { set_err(err, errlen, std::string(who) + ": no classes set (ss_hip_set_classes)"); return SS_HIP_EINVAL; }
+    return SS_HIP_OK;
+}
+
+int bad_index(uint32_t first_bad, const char* who, char* err, size_t errlen)
+{
+    set_err(err, errlen, std::string(who) + ": record " + std::to_string(first_bad) + " holds a column index >= n");
+    return SS_HIP_EINVAL;
+}
+
+// rows b0 .. b0 + Bc - 1 of a HOST matrix (row stride / increment in elements) into dst [Bc][m], contiguous
+template <typename T>
+void upload_rows(ss_hip_ctx* ctx, T* dst, const T* src, ptrdiff_t stride, ptrdiff_t inc, size_t b0, size_t Bc, std::vector<T>& tmp)
+{
+    const size_t m = ctx->m;
+    if (inc == 1 && stride >= (ptrdiff_t)m) {
+        CLS_CHK(hipMemcpy2DAsync(dst, m * sizeof(T), src + (ptrdiff_t)b0 * stride, (size_t)stride * sizeof(T), m * sizeof(T), Bc,
+                                 hipMemcpyHostToDevice, ctx->stream));
+        return;
+    }
+    tmp.resize(Bc * m);
+    for (size_t b = 0; b < Bc; ++b)
+        for (size_t i = 0; i < m; ++i) tmp[b * m + i] = src[(ptrdiff_t)(b0 + b) * stride + (ptrdiff_t)i * inc];
+    CLS_CHK(hipMemcpyAsync(dst, tmp.data(), Bc * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    CLS_CHK(hipStreamSynchronize(ctx->stream));        // (tmp is filled again for the next chunk)
+}
+
+template <typename T>
+int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                   T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    static const char* who = "class_residuals";
+    CLS_CHK(hipSetDevice(ctx->device));
+    ClassifyState* cs = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, C = cs->num_classes;
+    const uint32_t ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), segcap = std::min(kmax, C);
+    const bool rec_dev = on_device(records), y_dev = on_device(Y);
+
+    auto carve = [&](unsigned char* base, size_t ch, auto&& use) {
+        Carver cv(base);
+        unsigned char* rec = rec_dev ? nullptr : cv.take<unsigned char>(ch * rb);
+        T* ybuf = y_dev ? nullptr : cv.take<T>(ch * m);
+        uint32_t* ord_idx = cv.take<uint32_t>(ch * kmax);
+        T* ord_val = cv.take<T>(ch * kmax);
+        uint32_t* seg = cv.take<uint32_t>(ch * segcap * 3);
+        double* seg_l1 = cv.take<double>(ch * segcap);
+        uint32_t* sig = cv.take<uint32_t>(ch * kSigWords);
+        double* dsci = cv.take<double>(ch);
+        uint32_t* dbest = cv.take<uint32_t>(ch);
+        double* part = cv.take<double>(ch * ntiles * segcap * 4);
+        double* party = cv.take<double>(ch * ntiles * 4);
+        T* Rb = cv.take<T>(ch * C);
+        uint32_t* bad = cv.take<uint32_t>(1);
+        use(rec, ybuf, ord_idx, ord_val, seg, seg_l1, sig, dsci, dbest, part, party, Rb, bad);
+        return cv.off;
+    };
+    const size_t per = carve(nullptr, 1, [](auto...) {});
+    const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kClsChunkMax, kClsChunkBytes / per)));
+    grow(cs->arena, cs->arena_bytes, carve(nullptr, chunk, [](auto...) {}), "hipMalloc(classify workspace)");
+
+    uint32_t first_bad = 0xffffffffu;
+    std::vector<T> tmp;
+    carve(cs->arena, chunk, [&](unsigned char* rec, T* ybuf, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig,
+                                double* dsci, uint32_t* dbest, double* part, double* party, T* Rb, uint32_t* bad) {
+        CLS_CHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        for (size_t b0 = 0; b0 < B; b0 += chunk) {
+            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+            const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
+            if (!rec_dev) { CLS_CHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
+            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
+            long long ys = y_stride, yi = incy;
+            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
+            hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
+                               (const uint32_t*)cs->labels, C, segcap, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
+            hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                               (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
+                               (const uint32_t*)sig, part, party, (T*)nullptr);
+            hipLaunchKernelGGL((k_cls_finish<T>), dim3(Bc), dim3(kClsThreads), 0, st, (const uint32_t*)seg, segcap, (const uint32_t*)sig,
+                               (const double*)part, (const double*)party, ntiles, C, Rb, dbest);
+            CLS_CHK(hipGetLastError());
+            if (R) CLS_CHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), Rb, (size_t)C * sizeof(T),
+                                            (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
+            CLS_CHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
+            if (sci) CLS_CHK(hipMemcpyAsync(sci + b0, dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
+        }
+        CLS_CHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CLS_CHK(hipStreamSynchronize(st));
+    });
+    if (first_bad != 0xffffffffu) return bad_index(first_bad, who, err, errlen);
+    return SS_HIP_OK;
+}
+
+template <typename T>
+int class_residuals_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                          T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    static const char* who = "class_residuals";
+    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !best) { set_err(err, errlen, "class_residuals: Y and best must not be null"); return SS_HIP_EINVAL; }
+    if (const int rq = check_classes(ctx, who, err, errlen)) return rq;
+    if (B == 0) return SS_HIP_OK;
+    if (incy <= 0) { set_err(err, errlen, "class_residuals: increments must be positive"); return SS_HIP_EINVAL; }
+    if (R && r_stride < (ptrdiff_t)static_cast<const ClassifyState*>(ctx->cls)->num_classes) {
+        set_err(err, errlen, "class_residuals: r_stride must be at least num_classes");
+        return SS_HIP_EINVAL;
+    }
+    return guarded(err, errlen, who, [&] { return residuals_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen); });
+}
+
+template <typename T>
+int reconstruct_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, T* Yhat, ptrdiff_t yh_stride, ptrdiff_t incyh,
+                     char* err, size_t errlen)
+{
+    CLS_CHK(hipSetDevice(ctx->device));
+    ClassifyState* cs = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n;
+    const uint32_t ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
+    const bool rec_dev = on_device(records), out_dev = on_device(Yhat);
+    const bool rows2d = incyh == 1 && yh_stride >= (ptrdiff_t)m;
+
+    auto carve = [&](unsigned char* base, size_t ch, auto&& use) {
+        Carver cv(base);
+        unsigned char* rec = rec_dev ? nullptr : cv.take<unsigned char>(ch * rb);
+        uint32_t* ord_idx = cv.take<uint32_t>(ch * kmax);
+        T* ord_val = cv.take<T>(ch * kmax);
+        uint32_t* seg = cv.take<uint32_t>(ch * 3);
+        double* seg_l1 = cv.take<double>(ch);
+        uint32_t* sig = cv.take<uint32_t>(ch * kSigWords);
+        double* dsci = cv.take<double>(ch);
+        T* yh = cv.take<T>(ch * ldm);
+        uint32_t* bad = cv.take<uint32_t>(1);
+        use(rec, ord_idx, ord_val, seg, seg_l1, sig, dsci, yh, bad);
+        return cv.off;
+    };
+    const size_t per = carve(nullptr, 1, [](auto...) {});
+    const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kClsChunkMax, kClsChunkBytes / per)));
+    grow(cs->arena, cs->arena_bytes, carve(nullptr, chunk, [](auto...) {}), "hipMalloc(classify workspace)");
+
+    uint32_t first_bad = 0xffffffffu;
+    std::vector<T> tmp;
+    carve(cs->arena, chunk, [&](unsigned char* rec, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig, double* dsci,
+                                T* yh, uint32_t* bad) {
+        CLS_CHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        for (size_t b0 = 0; b0 < B; b0 += chunk) {
+            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+            const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
+            if (!rec_dev) { CLS_CHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
+            hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
+                               (const uint32_t*)nullptr, 1u, 1u, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
+            hipLaunchKernelGGL((k_cls_residual<T, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                               (uint32_t)m, (const T*)nullptr, 0ll, 1ll, (const uint32_t*)ord_idx, (const T*)ord_val, kmax,
+                               (const uint32_t*)seg, 1u, (const uint32_t*)sig, (double*)nullptr, (double*)nullptr, yh);
+            CLS_CHK(hipGetLastError());
+            T* out = Yhat + (ptrdiff_t)b0 * yh_stride;
+            if (rows2d) {
+                CLS_CHK(hipMemcpy2DAsync(out, (size_t)yh_stride * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
+            } else if (out_dev) {
+                hipLaunchKernelGGL((k_cls_scatter<T>), dim3((uint32_t)std::min<size_t>((m + 255) / 256, 64), Bc), dim3(256), 0, st, (const T*)yh, ldm,
+                                   (uint32_t)m, out, (long long)yh_stride, (long long)incyh);
+                CLS_CHK(hipGetLastError());
+            } else {
+                tmp.resize((size_t)Bc * m);
+                CLS_CHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDeviceToHost, st));
+                CLS_CHK(hipStreamSynchronize(st));
+                for (size_t b = 0; b < Bc; ++b)
+                    for (size_t i = 0; i < m; ++i) out[(ptrdiff_t)b * yh_stride + (ptrdiff_t)i * incyh] = tmp[b * m + i];
+            }
+        }
+        CLS_CHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CLS_CHK(hipStreamSynchronize(st));
+    });
+    if (first_bad != 0xffffffffu) return bad_index(first_bad, "reconstruct_records", err, errlen);
+    return SS_HIP_OK;
+}
+
+template <typename T>
+int reconstruct_entry(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, T* Yhat, ptrdiff_t yh_stride, ptrdiff_t incyh,
+                      char* err, size_t errlen)
+{
+    static const char* who = "reconstruct_records";
+    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Yhat) { set_err(err, errlen, "reconstruct_records: Yhat must not be null"); return SS_HIP_EINVAL; }
+    if (B == 0) return SS_HIP_OK;
+    if (incyh <= 0) { set_err(err, errlen, "reconstruct_records: increments must be positive"); return SS_HIP_EINVAL; }
+    return guarded(err, errlen, who, [&] { return reconstruct_impl<T>(ctx, records, B, kmax, Yhat, yh_stride, incyh, err, errlen); });
+}
+
+inline int solve_compact(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t ys, ptrdiff_t iy, float tol, uint32_t mi, uint32_t kmax, void* rec,
+                         char* err, size_t errlen)
+{
+    return ss_hip_homotopy_solve_batch_compact_f32(ctx, Y, B, ys, iy, tol, mi, kmax, rec, err, errlen);
+}
+inline int solve_compact(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t ys, ptrdiff_t iy, double tol, uint32_t mi, uint32_t kmax, void* rec,
+                         char* err, size_t errlen)
+{
+    return ss_hip_homotopy_solve_batch_compact_f64(ctx, Y, B, ys, iy, tol, mi, kmax, rec, err, errlen);
+}
+
+template <typename T>
+int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, T tol, uint32_t max_iter, uint32_t kmax,
+                   void* records, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    static const char* who = "classify_batch";
+    const int rc = check_common<T>(ctx, who, records, false, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !best) { set_err(err, errlen, "classify_batch: Y and best must not be null"); return SS_HIP_EINVAL; }
+    if (const int rq = check_classes(ctx, who, err, errlen)) return rq;
+    if (B == 0) return SS_HIP_OK;
+    if (incy <= 0) { set_err(err, errlen, "classify_batch: increments must be positive"); return SS_HIP_EINVAL; }
+    if (R && r_stride < (ptrdiff_t)static_cast<const ClassifyState*>(ctx->cls)->num_classes) {
+        set_err(err, errlen, "classify_batch: r_stride must be at least num_classes");
+        return SS_HIP_EINVAL;
+    }
+    return guarded(err, errlen, who, [&]() -> int {
+        CLS_CHK(hipSetDevice(ctx->device));
+        ClassifyState* cs = state_of(ctx);
+        const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
+        // Y once to the device, the records kept there
+        const T* yd = Y;
+        ptrdiff_t ys = y_stride, yi = incy;
+        if (!on_device(Y)) {
+            grow(cs->y_all, cs->y_all_bytes, B * m * sizeof(T), "hipMalloc(classify signals)");
+            std::vector<T> tmp;
+            upload_rows<T>(ctx, reinterpret_cast<T*>(cs->y_all), Y, y_stride, incy, 0, B, tmp);
+            CLS_CHK(hipStreamSynchronize(ctx->stream));
+            yd = reinterpret_cast<const T*>(cs->y_all); ys = (ptrdiff_t)m; yi = 1;
+        }
+        void* rd = records;
+        if (!records || !on_device(records)) {
+            grow(cs->rec_all, cs->rec_all_bytes, B * rb, "hipMalloc(classify records)");
+            rd = cs->rec_all;
+        }
+        const int rs = solve_compact(ctx, yd, B, ys, yi, tol, max_iter, kmax, rd, err, errlen);
+        if (rs != SS_HIP_OK) return rs;
+        const int rr = residuals_impl<T>(ctx, yd, B, ys, yi, rd, kmax, R, r_stride, best, sci, err, errlen);
+        if (rr != SS_HIP_OK) return rr;
+        if (records && rd != records) CLS_CHK(hipMemcpy(records, rd, B * rb, hipMemcpyDeviceToHost));
+        return SS_HIP_OK;
+    });
+}
+
+}  // namespace
+
+void classify_free(ss_hip_ctx* ctx)
+{
+    ClassifyState* cs = static_cast<ClassifyState*>(ctx->cls);
+    if (!cs) return;
+    if (cs->labels) (void)hipFree(cs->labels);
+    if (cs->arena) (void)hipFree(cs->arena);
+    if (cs->y_all) (void)hipFree(cs->y_all);
+    if (cs->rec_all) (void)hipFree(cs->rec_all);
+    delete cs;
+    ctx->cls = nullptr;
+}
+
+}  // namespace sship
+
+using namespace sship;
+
+extern "C" {
+
+int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_classes, char* err, size_t errlen)
+{
+    if (!ctx) { set_err(err, errlen, "set_classes: null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 0) { set_err(err, errlen, "set_classes: this context was created for IRLS"); return SS_HIP_EINVAL; }
+    if (ctx->colshard != nullptr) { set_err(err, errlen, "set_classes: not available on a column-sharded context"); return SS_HIP_EINVAL; }
+    if (!labels || num_classes == 0) { set_err(err, errlen, "set_classes: labels must not be null and num_classes >= 1"); return SS_HIP_EINVAL; }
+    return guarded(err, errlen, "set_classes", [&]() -> int {
+        CLS_CHK(hipSetDevice(ctx->device));
+        ClassifyState* cs = state_of(ctx);
+        const uint32_t n = (uint32_t)ctx->n, np = ctx->n_pad;
+        uint32_t* fresh = nullptr;
+        CLS_CHK(hipMalloc(reinterpret_cast<void**>(&fresh), ((size_t)np + 1) * sizeof(uint32_t)));
+        uint32_t bad = 0xffffffffu;
+        hipError_t e = hipMemsetAsync(fresh, 0, (size_t)np * sizeof(uint32_t), ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(fresh + np, 0xff, sizeof(uint32_t), ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(fresh, labels, (size_t)n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_cls_check_labels, dim3((n + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint32_t*)fresh, n, num_classes, fresh + np);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, fresh + np, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { (void)hipFree(fresh); throw HipFail{ e, "set_classes: upload of the labels" }; }
+        if (bad != 0xffffffffu) {
+            (void)hipFree(fresh);
+            set_err(err, errlen, "set_classes: the label of column " + std::to_string(bad) + " is not below num_classes");
+            return SS_HIP_EINVAL;
+        }
+        if (cs->labels) CLS_CHK(hipFree(cs->labels));
+        cs->labels = fresh;
+        cs->num_classes = num_classes;
+        return SS_HIP_OK;
+    });
+}
+
+int ss_hip_reconstruct_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, float* Yhat, ptrdiff_t yh_stride,
+                                   ptrdiff_t incyh, char* err, size_t errlen)
+{
+    return reconstruct_entry<float>(ctx, records, B, kmax, Yhat, yh_stride, incyh, err, errlen);
+}
+int ss_hip_reconstruct_records_f64(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, double* Yhat, ptrdiff_t yh_stride,
+                                   ptrdiff_t incyh, char* err, size_t errlen)
+{
+    return reconstruct_entry<double>(ctx, records, B, kmax, Yhat, yh_stride, incyh, err, errlen);
+}
+
+int ss_hip_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                               uint32_t kmax, float* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    return class_residuals_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+}
+int ss_hip_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                               uint32_t kmax, double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    return class_residuals_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+}
+
+int ss_hip_homotopy_classify_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol,
+                                       uint32_t max_iter, uint32_t kmax, void* records, float* R, ptrdiff_t r_stride, uint32_t* best,
+                                       double* sci, char* err, size_t errlen)
+{
+    return classify_entry<float>(ctx, Y, B, y_stride, incy, tol, max_iter, kmax, records, R, r_stride, best, sci, err, errlen);
+}
+int ss_hip_homotopy_classify_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, double tol,
+                                       uint32_t max_iter, uint32_t kmax, void* records, double* R, ptrdiff_t r_stride, uint32_t* best,
+                                       double* sci, char* err, size_t errlen)
+{
+    return classify_entry<double>(ctx, Y, B, y_stride, incy, tol, max_iter, kmax, records, R, r_stride, best, sci, err, errlen);
+}
+
+}  // extern "C"

@@ -2912,6 +2912,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     if (ctx->gram_full) (void)hipFree(ctx->gram_full);
     if (ctx->c0_batch) (void)hipFree(ctx->c0_batch);
     sship::omp_gram_free(ctx);
+    sship::classify_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);

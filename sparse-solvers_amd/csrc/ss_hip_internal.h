@@ -365,6 +365,7 @@ struct ss_hip_ctx {
     void* irls = nullptr;    // sship::IrlsState<T>* of an IRLS context
     void* irls_batch = nullptr;   // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
     int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
+    void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
     int device = 0;
     int is_f64 = 0;
     size_t m = 0, n = 0;
@@ -504,6 +505,8 @@ bool omp_gram_usable(ss_hip_ctx* ctx);
 uint32_t omp_gram_cap();
 hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter);
 void omp_gram_free(ss_hip_ctx* ctx);
+// classification from compact records (classify.hip): releases the labels and the workspace of a context
+void classify_free(ss_hip_ctx* ctx);
 
 void screen_free(ss_hip_ctx* ctx);
 // fp64: the path is solved by the fp64 engine on a sub-dictionary (a context of its own: the kS64Sub columns with the largest

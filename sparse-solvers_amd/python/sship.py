@@ -37,6 +37,9 @@ SYMBOLS = [
     "ss_hip_irls_destroy", "ss_hip_irls_solve_batch_f32", "ss_hip_irls_solve_batch_f64",
     "ss_hip_comm_unique_id", "ss_hip_homotopy_colshard_create_f32", "ss_hip_homotopy_colshard_solve_f32",
     "ss_hip_homotopy_colshard_create_f64", "ss_hip_homotopy_colshard_solve_f64",
+    "ss_hip_set_classes", "ss_hip_reconstruct_records_f32", "ss_hip_reconstruct_records_f64",
+    "ss_hip_class_residuals_f32", "ss_hip_class_residuals_f64",
+    "ss_hip_homotopy_classify_batch_f32", "ss_hip_homotopy_classify_batch_f64",
 ]
 
 
@@ -173,6 +176,15 @@ def lib():
         f = getattr(L, "ss_hip_omp_solve_batch_compact_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, cp, sz]
+        f = getattr(L, "ss_hip_reconstruct_records_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, u32, vp, pd, pd, cp, sz]
+        f = getattr(L, "ss_hip_class_residuals_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, pd, vp, vp, cp, sz]
+        f = getattr(L, "ss_hip_homotopy_classify_batch_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, vp, pd, vp, vp, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
@@ -192,6 +204,8 @@ def lib():
         f = getattr(L, "ss_hip_irls_solve_batch_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, vp, cp, sz]
+    L.ss_hip_set_classes.restype = ctypes.c_int
+    L.ss_hip_set_classes.argtypes = [vp, vp, u32, cp, sz]
     L.ss_hip_subset_gram_f32.restype = ctypes.c_int
     L.ss_hip_subset_gram_f32.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
     L.ss_hip_record_bytes.restype = sz
@@ -303,6 +317,7 @@ class Homotopy:
         self.suffix, self.ctype = _suffix(dt)
         self.dtype = dt
         self.m, self.n = int(shape[0]), int(shape[1])
+        self.num_classes = 0               # set_classes
         err = ctypes.create_string_buffer(512)
         fn = getattr(lib(), "ss_hip_homotopy_create_" + self.suffix)
         self._h = fn(ptr, self.m, self.n, strides[0], strides[1], device, err, len(err))
@@ -423,6 +438,123 @@ class Homotopy:
                 rp, err, len(err))
         self._check(rc, err)
         return out
+
+    # ---- classification from compact records (include/ss_hip.h, csrc/classify.hip) ----------------------------------------
+
+    def set_classes(self, labels, num_classes=None):
+        """class of every dictionary column: `labels` (n,) integers below num_classes (default max + 1); a numpy array or an
+        int32 / uint32 torch tensor on either side.  May be called again; never changes what a solve returns."""
+        if hasattr(labels, "data_ptr"):
+            import torch
+            if labels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or labels.dim() != 1 or not labels.is_contiguous():
+                raise ValueError("labels must be a contiguous 1-D int32 / uint32 tensor")
+            count, lp, keep = int(labels.shape[0]), labels.data_ptr(), labels
+            if num_classes is None:
+                num_classes = int(labels.max().item()) + 1 if count else 1
+        else:
+            arr = np.asarray(labels)
+            if arr.ndim != 1 or arr.dtype.kind not in "iu":
+                raise ValueError("labels must be a 1-D integer array")
+            if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
+                raise ValueError("labels must fit in 32 unsigned bits")
+            keep = np.ascontiguousarray(arr, dtype=np.uint32)
+            count, lp = int(keep.shape[0]), keep.ctypes.data
+            if num_classes is None:
+                num_classes = int(keep.max()) + 1 if count else 1
+        if count != self.n:
+            raise ValueError("labels must have one entry per column (n = %d)" % self.n)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(labels)
+        self._check(lib().ss_hip_set_classes(self._h, lp, int(num_classes), err, len(err)), err)
+        self.num_classes = int(num_classes)
+
+    def _records_arg(self, records, kmax):
+        """-> (pointer, B) of a contiguous (B, record_bytes) uint8 numpy array or torch tensor"""
+        rb = self.record_bytes(kmax)
+        if isinstance(records, np.ndarray):
+            ok = records.dtype == np.uint8 and records.ndim == 2 and records.shape[1] == rb and records.flags.c_contiguous
+            rp = records.ctypes.data
+        elif hasattr(records, "data_ptr"):
+            import torch
+            ok = records.dtype == torch.uint8 and records.dim() == 2 and records.shape[1] == rb and records.is_contiguous()
+            rp = records.data_ptr()
+        else:
+            raise TypeError("records must be a uint8 numpy array or torch tensor")
+        if not ok:
+            raise ValueError("records must be a contiguous (B, %d) uint8 array" % rb)
+        return rp, int(records.shape[0])
+
+    def reconstruct_records(self, records, kmax, out=None):
+        """Yhat (B, m) = A x_b for the compact records of solve_batch_compact (same kmax); `out`: a (B, m) array or tensor of the
+        matrix dtype on either side (default a numpy array)"""
+        rp, B = self._records_arg(records, kmax)
+        if out is None:
+            out = np.empty((B, self.m), dtype=self.dtype)
+        op, oshape, ostr, odt, keep = _describe(out)
+        if odt != self.dtype or tuple(oshape) != (B, self.m):
+            raise ValueError("out must be (B, m) of the matrix dtype")
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(records, out)
+        fn = getattr(lib(), "ss_hip_reconstruct_records_" + self.suffix)
+        self._check(fn(self._h, rp, B, int(kmax), op, ostr[0] if B else self.m, ostr[1] if B else 1, err, len(err)), err)
+        return out
+
+    def _class_outputs(self, B, residuals, like):
+        """best, sci and R (or None) where `like` lives: torch tensors on its device, else numpy arrays"""
+        C = self.num_classes or 1          # (without classes the library reports the error)
+        if hasattr(like, "data_ptr") and getattr(like, "is_cuda", False):
+            import torch
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            best = torch.empty(B, dtype=torch.int32, device=like.device)      # (the words are uint32: 0xffffffff reads as -1)
+            sci = torch.empty(B, dtype=torch.float64, device=like.device)
+            R = torch.empty((B, C), dtype=tdt, device=like.device) if residuals else None
+            return best, sci, R, best.data_ptr(), sci.data_ptr(), (R.data_ptr() if residuals else None)
+        best = np.empty(B, dtype=np.uint32)
+        sci = np.empty(B, dtype=np.float64)
+        R = np.empty((B, C), dtype=self.dtype) if residuals else None
+        return best, sci, R, best.ctypes.data, sci.ctypes.data, (R.ctypes.data if residuals else None)
+
+    def class_residuals(self, Y, records, kmax, residuals=True):
+        """-> (best (B,), sci (B,) float64, R (B, num_classes) or None): R[b, c] = ||y_b - A delta_c(x_b)||_2 from the compact
+        records, best = its left-most arg-min (uint32; 0xffffffff for a truncated record), sci the sparsity concentration
+        index.  The outputs live where Y lives (device tensors for a device Y — best then int32 — else numpy arrays)."""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        rp, B = self._records_arg(records, kmax)
+        if B != int(shape[0]):
+            raise ValueError("Y and records must hold the same number of signals")
+        best, sci, R, bp, sp, Rp = self._class_outputs(B, residuals, Y)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(Y, records)
+        fn = getattr(lib(), "ss_hip_class_residuals_" + self.suffix)
+        self._check(fn(self._h, Yp, B, strides[0], strides[1], rp, int(kmax), Rp, self.num_classes or 1, bp, sp, err, len(err)), err)
+        return best, sci, R
+
+    def classify(self, Y, tolerance=None, max_iterations=100, kmax=96, residuals=True, records=None):
+        """solve_batch_compact + class_residuals without leaving the device -> (best, sci, R or None, records).  `records`: a
+        contiguous (B, record_bytes) uint8 array or tensor that receives the records, True for a new numpy array, None to
+        leave them in the context (returned as None)."""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        B = int(shape[0])
+        if tolerance is None:
+            tolerance = float(np.finfo(self.dtype).eps) * 10
+        rp = None
+        if records is True:
+            records = np.empty((B, self.record_bytes(kmax)), dtype=np.uint8)
+        if records is not None:
+            rp, Br = self._records_arg(records, kmax)
+            if Br != B:
+                raise ValueError("Y and records must hold the same number of signals")
+        best, sci, R, bp, sp, Rp = self._class_outputs(B, residuals, Y)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(Y, records)
+        fn = getattr(lib(), "ss_hip_homotopy_classify_batch_" + self.suffix)
+        self._check(fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations), int(kmax), rp,
+                       Rp, self.num_classes or 1, bp, sp, err, len(err)), err)
+        return best, sci, R, records
 
     def gemv_t(self, r, repeats=1, out=None):
         """c = A^T r on the device copy -> (c, mean kernel ms); `out` (host array or device tensor, length n) receives c"""
