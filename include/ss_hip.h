@@ -69,6 +69,35 @@ ss_hip_ctx* ss_hip_homotopy_create_f64(const double* A, size_t m, size_t n,
 void ss_hip_homotopy_destroy(ss_hip_ctx* ctx);
 
 /*
+ * Replaces S columns of a live context's dictionary in place (added under ABI version 7): column cols[s] of the m x n
+ * matrix becomes V(:, s), element (i, s) at V[i*stride_row + s*stride_col] (strides in ELEMENTS, the layouts create
+ * accepts).  cols and V may each be a host or a device pointer (the library asks the runtime which).
+ *
+ * The call returns when the update is complete; every later call on the context sees the new dictionary, and returns
+ * what a context created from the updated matrix with the same options returns — the same words where both take the
+ * same route.  Every copy the context derives from A is kept current, not dropped: the column-contiguous copy (padding
+ * rows stay zero), the screened forms' fp16 / fp8 copies with their column norms and their two global scales (re-derived
+ * from per-column maxima: a new column can raise max |A|, replacing the column that held it can lower it; a whole copy
+ * is converted again only when its scale exponent moved; a copy that has not been made yet is not made here), the OMP
+ * certificate's norms, and G = A^T A (the tiles that meet a replaced column, formed by the kernel and in the order of
+ * the build: bit for bit the G a fresh build forms; not counted in gram_full_builds).  The step-aside windows of the
+ * forms, learned on the old dictionary, start again.  Labels (ss_hip_set_classes), options, statistics, the last trace
+ * and the workspace stay as they are.
+ *
+ * Validation happens before anything is written: a failing call leaves the context exactly as it was.
+ *   SS_HIP_EINVAL  null ctx, cols or V; an IRLS or a column-sharded context; a column >= n; a column named twice
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   S == 0         SS_HIP_OK, nothing touched
+ * m and n do not change; columns cannot be appended.
+ */
+int ss_hip_homotopy_replace_columns_f32(ss_hip_ctx* ctx, const uint32_t* cols, size_t S,
+                                        const float* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                        char* err, size_t errlen);
+int ss_hip_homotopy_replace_columns_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S,
+                                        const double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                        char* err, size_t errlen);
+
+/*
  * Replaces solve_homotopy::op<compute_mode, T> (src/solvers/homotopy.h:27-38,
  * run_solver src/solvers/homotopy-cpu.cpp:186-275):
  *   min ||x||_1  s.t.  A x = y

@@ -55,6 +55,8 @@ HIP_UNITS = [
     ("ompbatch.hip", []),
     # classification from compact records: products and sums rounded separately, in the documented order (the tests' bounds)
     ("classify.hip", ["-ffp-contract=off"]),
+    # columns of a live context replaced in place: the statistics and conversions are screen.hip's statements, built like screen.hip
+    ("dictupdate.hip", []),
 ]
 
 

@@ -40,7 +40,11 @@ constexpr int GLD = GK + GPAD;                 // LDS row pitch in floats (144 B
 // tools/dbg_colform.py) — and that error stays in every c = c0 - sum_j x_j g_j of the path.  With BLK
 // every K-step (32 rows) runs its own chain from zero and the 32-row sums are added up in a second accumulator:
 // chains of 32 + m / 32 instead of m.  Not for SYM: G's entries have to be the mirrored-tile chains.
-template <bool SYM, bool BLK = false>
+// LIST (with SYM; a refresh of G after columns were replaced): only the tiles that meet a listed column tile, named by
+// row_tile_skip = [0 .. mtiles) 1 = listed, then the listed tiles: workgroup b pairs listed tile b / mtiles with tile b % mtiles
+// (a pair of two listed tiles is formed once, by the smaller one's entry).  An entry of G is a chain over its two columns
+// alone, so these tiles hold what the whole build would put there.
+template <bool SYM, bool BLK = false, bool LIST = false>
 __global__ __launch_bounds__(256, 2)
 void k_gemm_tn_f32(const float* __restrict__ R, const float* __restrict__ Q, float* __restrict__ D,
                    uint32_t mtiles, uint32_t K, uint32_t ldr, uint32_t ldq, uint32_t ldd,
@@ -52,7 +56,12 @@ void k_gemm_tn_f32(const float* __restrict__ R, const float* __restrict__ Q, flo
     // row tiles fastest: concurrently resident workgroups share the same panel of At.  With a
     // tile list only its `nact` tiles are computed, by the leading nact*ntiles workgroups.
     uint32_t bm, bn;
-    if (SYM) {
+    if (SYM && LIST) {
+        const uint32_t tl = row_tile_skip[mtiles + blockIdx.x / mtiles], to = blockIdx.x % mtiles;
+        if (row_tile_skip[to] != 0u && to < tl) return;          // (uniform; the pair belongs to the entry of `to`)
+        bm = tl < to ? tl : to;
+        bn = tl < to ? to : tl;
+    } else if (SYM) {
         // blockIdx.x = bn (bn + 1) / 2 + bm with bm <= bn
         const uint32_t b = blockIdx.x;
         uint32_t t = (uint32_t)((__fsqrt_rn(8.f * (float)b + 1.f) - 1.f) * 0.5f);
@@ -1071,6 +1080,18 @@ hipError_t launch_gemm_sym_f32(const ss_hip_ctx* ctx, float* G, uint32_t ldd)
     const float* At = static_cast<const float*>(ctx->At);
     hipLaunchKernelGGL((k_gemm_tn_f32<true, false>), dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, At, At, G, (uint32_t)t,
                        ctx->ldm, ctx->ldm, ctx->ldm, ldd, (const uint32_t*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_gemm_sym_tiles_f32(const ss_hip_ctx* ctx, float* G, uint32_t ldd, const uint32_t* tiles, uint32_t count)
+{
+    static_assert(kGramTile == (uint32_t)GN && GM == GN, "tile of the symmetric build");
+    if (ctx->n_pad % GN != 0 || ctx->ldm % GK != 0 || ldd % 4 != 0) return hipErrorInvalidValue;
+    const uint64_t t = ctx->n_pad / GN;
+    if (count == 0 || count > t || t * count > 0x7fffffffull) return hipErrorInvalidValue;
+    const float* At = static_cast<const float*>(ctx->At);
+    hipLaunchKernelGGL((k_gemm_tn_f32<true, false, true>), dim3((uint32_t)(t * count)), dim3(256), 0, ctx->stream, At, At, G, (uint32_t)t,
+                       ctx->ldm, ctx->ldm, ctx->ldm, ldd, tiles);
     return hipGetLastError();
 }
 

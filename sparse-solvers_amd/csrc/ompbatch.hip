@@ -37,9 +37,13 @@ constexpr uint32_t kOmpGramChunk = 256;                    // slots per chunk of
 
 // column norms ||a_j|| in fp64, rounded up into fp32 (the error bound's scale); padding columns 0.  One wave per column.
 __global__ __launch_bounds__(256)
-void k_omp_colnorm(const float* __restrict__ At, uint32_t ldm, uint32_t n, uint32_t np, float* __restrict__ norm)
+void k_omp_colnorm(const float* __restrict__ At, uint32_t ldm, uint32_t n, uint32_t np, float* __restrict__ norm,
+                   const uint32_t* __restrict__ list, uint32_t nlist)
 {
-    const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    // (list: only those columns — the ones a replacement rewrote)
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (list != nullptr && w >= nlist) return;
+    const uint32_t j = list != nullptr ? list[w] : w;
     if (j >= np) return;
     double s = 0.0;
     if (j < n)
@@ -217,7 +221,8 @@ hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
             (void)hipGetLastError();
             return hipErrorOutOfMemory;
         }
-        hipLaunchKernelGGL(k_omp_colnorm, dim3((np + 3u) / 4u), dim3(256), 0, s, static_cast<const float*>(ctx->At), ldm, n, np, ctx->omp_norm);
+        hipLaunchKernelGGL(k_omp_colnorm, dim3((np + 3u) / 4u), dim3(256), 0, s, static_cast<const float*>(ctx->At), ldm, n, np, ctx->omp_norm,
+                           (const uint32_t*)nullptr, 0u);
     }
     const SubBufs B = sub_bufs(ctx, nslots);
     (void)launch_sub_select(ctx, B, nslots, c0_all);
@@ -230,6 +235,14 @@ hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
                        c0_all, np, (const float*)ctx->omp_norm, (const uint32_t*)B.sub, (const uint32_t*)B.hdr,
                        (const uint32_t*)B.pcol, (const float*)B.LX, tol, ws.st);
     (void)launch_sub_finish_st(ctx, ws.st, nslots);
+    return hipGetLastError();
+}
+
+hipError_t omp_norm_refresh(ss_hip_ctx* ctx, const uint32_t* cols_dev, uint32_t S)
+{
+    if (ctx->omp_norm == nullptr || S == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_omp_colnorm, dim3((S + 3u) / 4u), dim3(256), 0, ctx->stream, static_cast<const float*>(ctx->At), ctx->ldm, (uint32_t)ctx->n, ctx->n_pad,
+                       ctx->omp_norm, cols_dev, S);
     return hipGetLastError();
 }
 

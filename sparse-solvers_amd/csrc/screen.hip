@@ -96,6 +96,7 @@ struct ScreenState {
     uint8_t* a8 = nullptr;       // [n_pad][ldm] fl8(sA8 * A) in OCP e4m3: the RANKING pass only (k_scr_first8; made on first use)
     bool a8_failed = false;      // its allocation did not fit: the half-precision first pass goes on
     float* anorm = nullptr;      // [n_pad] ||a_i||_2, rounded up
+    float* amaxc = nullptr;      // [n_pad] max |a_i| per column: what meta[2] is the maximum of (a column replaced later re-derives it, dictupdate.hip)
     float* meta = nullptr;       // [0] sA  [1] 1 / sA  [2] bits(max |A|)  [3] headroom of the last solve (bits, as uint)
                                  // [4] max ||a_i||  [5] ||y||^2 (k_scr_first)  [6] what the columns left out of the subset stay below (selection)
     __half* r16 = nullptr;       // [kScrRhs][ldm] fl16(s_k * r_k)
@@ -152,7 +153,7 @@ struct Screen64Batch {
 // ---- one-time preparation ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256)
-void k_a16_stats(const T* __restrict__ At, uint32_t ldm, float* __restrict__ anorm, float* __restrict__ meta)
+void k_a16_stats(const T* __restrict__ At, uint32_t ldm, float* __restrict__ anorm, float* __restrict__ amaxc, float* __restrict__ meta)
 {
     __shared__ float sv[16];
     const T* a = At + (size_t)blockIdx.x * ldm;
@@ -171,6 +172,7 @@ void k_a16_stats(const T* __restrict__ At, uint32_t ldm, float* __restrict__ ano
     if (threadIdx.x == 0) {
         mx = fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3]));
         anorm[blockIdx.x] = sqrtf(ss) * 1.0001f;                       // (rounded up: it scales an upper bound; fp64 sources: the cast's 2^-24 is inside)
+        amaxc[blockIdx.x] = mx;
         atomicMax(reinterpret_cast<uint32_t*>(meta) + 2, __float_as_uint(mx));
         atomicMax(reinterpret_cast<uint32_t*>(meta) + 4, __float_as_uint(sqrtf(ss) * 1.0001f));      // (non-negative floats order like their bits)
     }
@@ -179,9 +181,7 @@ void k_a16_stats(const T* __restrict__ At, uint32_t ldm, float* __restrict__ ano
 __global__ void k_a16_scale(float* __restrict__ meta)
 {
     const float amax = __uint_as_float(reinterpret_cast<const uint32_t*>(meta)[2]);
-    int e = 0;
-    if (amax > 0.f && amax < 3.0e38f) e = (int)floorf(log2f(16384.f / amax));
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
+    const int e = pow2_scale_exp(16384.f, amax);
     meta[0] = ldexpf(1.f, e);
     meta[1] = ldexpf(1.f, -e);
 }
@@ -206,9 +206,7 @@ void k_a16_convert(const T* __restrict__ At, size_t total8, const float* __restr
 __global__ void k_a8_scale(float* __restrict__ meta)
 {
     const float amax = __uint_as_float(reinterpret_cast<const uint32_t*>(meta)[2]);
-    int e = 0;
-    if (amax > 0.f && amax < 3.0e38f) e = (int)floorf(log2f(224.f / amax));
-    e = e < -100 ? -100 : (e > 100 ? 100 : e);
+    const int e = pow2_scale_exp(224.f, amax);
     meta[10] = ldexpf(1.f, e);
     meta[11] = ldexpf(1.f, -e);
 }
@@ -1578,7 +1576,7 @@ void screen_free(ss_hip_ctx* ctx)
 {
     ScreenState* S = scr_of(ctx);
     if (!S) return;
-    void* ptrs[] = { S->rank, S->a8, S->a16, S->anorm, S->meta, S->r16, S->rn2p, S->tab, S->gs_part, S->gs, S->wmax, S->cabs, S->sublist, S->xsub, S->xd, S->ctl,
+    void* ptrs[] = { S->rank, S->a8, S->a16, S->anorm, S->amaxc, S->meta, S->r16, S->rn2p, S->tab, S->gs_part, S->gs, S->wmax, S->cabs, S->sublist, S->xsub, S->xd, S->ctl,
                      S->b_r16, S->b_rn2p, S->b_tab, S->b_gs_part, S->b_gs, S->fl, S->sub256, S->gs64, S->gs64_part, S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -1599,6 +1597,33 @@ void screen_free(ss_hip_ctx* ctx)
     }
     delete S;
     ctx->screen = nullptr;
+}
+
+// ---- what a column replacement keeps current (dictupdate.hip) -------------------------------------------------------------------
+ScreenCopies screen_copies(ss_hip_ctx* ctx)
+{
+    ScreenCopies c;
+    if (ScreenState* S = scr_of(ctx)) { c.a16 = S->a16; c.a8 = S->a8; c.anorm = S->anorm; c.amaxc = S->amaxc; c.meta = S->meta; c.sub = S->sub; }
+    return c;
+}
+
+// the whole fp16 / fp8 copy again under the scales meta[0] / meta[10] hold now: the preparation's own conversion passes
+hipError_t screen_reconvert(ss_hip_ctx* ctx, bool a16, bool a8)
+{
+    ScreenState* S = scr_of(ctx);
+    if (S == nullptr) return hipErrorInvalidConfiguration;
+    const size_t total = (size_t)ctx->n_pad * ctx->ldm;
+    hipStream_t s = ctx->stream;
+    auto grid = [](size_t items) { return dim3((unsigned)std::min<size_t>((items + 255) / 256, 65536)); };
+    if (a16 && S->a16 != nullptr) {
+        if (ctx->is_f64) hipLaunchKernelGGL((k_a16_convert<double>), grid(total / 8), dim3(256), 0, s, static_cast<const double*>(ctx->At), total / 8, (const float*)S->meta, S->a16);
+        else hipLaunchKernelGGL((k_a16_convert<float>), grid(total / 8), dim3(256), 0, s, static_cast<const float*>(ctx->At), total / 8, (const float*)S->meta, S->a16);
+    }
+    if (a8 && S->a8 != nullptr) {
+        if (ctx->is_f64) hipLaunchKernelGGL((k_a8_convert<double>), grid(total / 16), dim3(256), 0, s, static_cast<const double*>(ctx->At), total / 16, (const float*)S->meta, S->a8);
+        else hipLaunchKernelGGL((k_a8_convert<float>), grid(total / 16), dim3(256), 0, s, static_cast<const float*>(ctx->At), total / 16, (const float*)S->meta, S->a8);
+    }
+    return hipGetLastError();
 }
 
 // (the main loop's two tiles; the epilogue's tables — 96 x 4 + 448 + 128 x 96 floats — fit inside)
@@ -1633,6 +1658,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
     alloc(reinterpret_cast<void**>(&S->a16), (size_t)np * ldm * sizeof(__half));
     alloc(reinterpret_cast<void**>(&S->anorm), (size_t)np * sizeof(float));
+    alloc(reinterpret_cast<void**>(&S->amaxc), (size_t)np * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->meta), kScrMeta * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->r16), (size_t)kScrRhs * ldm * sizeof(__half));
     alloc(reinterpret_cast<void**>(&S->rn2p), (size_t)(ldm / 64u) * kScrRhs * sizeof(float));
@@ -1652,7 +1678,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
     (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), s);
     (void)hipMemsetAsync(S->r16, 0, (size_t)kScrRhs * ldm * sizeof(__half), s);
-    hipLaunchKernelGGL((k_a16_stats<float>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->meta);
+    hipLaunchKernelGGL((k_a16_stats<float>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
     hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta);
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<float>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
@@ -1954,6 +1980,7 @@ bool screen64_usable(ss_hip_ctx* ctx)
     auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
     alloc(reinterpret_cast<void**>(&S->a16), (size_t)np * ldm * sizeof(__half));
     alloc(reinterpret_cast<void**>(&S->anorm), (size_t)np * sizeof(float));
+    alloc(reinterpret_cast<void**>(&S->amaxc), (size_t)np * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->meta), kScrMeta * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->r16), (size_t)kS64Rhs * ldm * sizeof(__half));
     alloc(reinterpret_cast<void**>(&S->rn2p), (size_t)(ldm / 64u) * kS64Rhs * sizeof(float));
@@ -2007,7 +2034,7 @@ bool screen64_usable(ss_hip_ctx* ctx)
     const double* At = static_cast<const double*>(ctx->At);
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
     (void)hipMemsetAsync(S->r16, 0, (size_t)kS64Rhs * ldm * sizeof(__half), s);
-    hipLaunchKernelGGL((k_a16_stats<double>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->meta);
+    hipLaunchKernelGGL((k_a16_stats<double>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
     hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta);
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<double>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,

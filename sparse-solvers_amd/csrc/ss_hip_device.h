@@ -122,6 +122,15 @@ __device__ __forceinline__ void block_reduce_pair(T& v, uint32_t& i, T* sv, uint
     i = bi;
 }
 
+// Exponent e of the power-of-two scale that puts the largest |a| of a reduced-precision copy into (target / 2, target]:
+// floor(log2(target / amax)), 0 for an all-zero or non-finite dictionary (screen.hip: k_a16_scale, k_a8_scale; dictupdate.hip)
+__device__ __forceinline__ int pow2_scale_exp(float target, float amax)
+{
+    int e = 0;
+    if (amax > 0.f && amax < 3.0e38f) e = (int)floorf(log2f(target / amax));
+    return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+
 // Sum over the wave, the same value in every lane.  Fixed association: butterfly inside each row
 // of 16 lanes (1, 2, 4, 8 apart), then ((row0 + row1) + row2) + row3.
 template <typename T>

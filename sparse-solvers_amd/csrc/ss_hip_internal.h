@@ -509,6 +509,20 @@ void omp_gram_free(ss_hip_ctx* ctx);
 void classify_free(ss_hip_ctx* ctx);
 
 void screen_free(ss_hip_ctx* ctx);
+// what the screened forms derive from A, for a column replacement (dictupdate.hip) to keep current; every pointer null while the
+// preparation has not run (a8: until its first use).  screen_reconvert: the whole fp16 / fp8 copy again under the scales in meta
+struct ScreenCopies {
+    void* a16 = nullptr;         // __half [n_pad][ldm]
+    uint8_t* a8 = nullptr;       // [n_pad][ldm]
+    float* anorm = nullptr;      // [n_pad]
+    float* amaxc = nullptr;      // [n_pad]
+    float* meta = nullptr;
+    ss_hip_ctx* sub = nullptr;   // fp64: the sub-context (gathers its columns per solve)
+};
+ScreenCopies screen_copies(ss_hip_ctx* ctx);
+hipError_t screen_reconvert(ss_hip_ctx* ctx, bool a16, bool a8);
+// ||a_j|| of the listed columns again (ompbatch.hip: the OMP certificate's scale; a no-op before the first Gram-form OMP batch)
+hipError_t omp_norm_refresh(ss_hip_ctx* ctx, const uint32_t* cols_dev, uint32_t S);
 // fp64: the path is solved by the fp64 engine on a sub-dictionary (a context of its own: the kS64Sub columns with the largest
 // |A^T y|), its states are logged (ss_hip_ctx::slog) and certified against all columns by the same fp16 pass
 bool screen64_usable(ss_hip_ctx* ctx);
@@ -637,6 +651,10 @@ hipError_t launch_gemm_tn_f32(const ss_hip_ctx* ctx, const float* R, uint32_t Mg
 
 // G[n_pad][ldd] = At · At^T (the full Gram matrix) from the tiles on and above the diagonal + mirrored stores
 hipError_t launch_gemm_sym_f32(const ss_hip_ctx* ctx, float* G, uint32_t ldd);
+// the same tiles of the same kernel, only those that meet a listed 128-column tile, stored to both sides: G after columns of
+// those tiles changed.  tiles (device): [0 .. n_pad / 128) 1 = listed, then the `count` listed tiles
+hipError_t launch_gemm_sym_tiles_f32(const ss_hip_ctx* ctx, float* G, uint32_t ldd, const uint32_t* tiles, uint32_t count);
+constexpr uint32_t kGramTile = 128;      // columns per tile of those two
 
 // D[drows[s]][:] = At · At[rcols[s]][:] for s < 32: 32 right-hand sides in one HBM-bound pass
 // (rcols / drows live on the device; 0xffffffff entries are skipped; with st != null the launch

@@ -40,6 +40,7 @@ SYMBOLS = [
     "ss_hip_set_classes", "ss_hip_reconstruct_records_f32", "ss_hip_reconstruct_records_f64",
     "ss_hip_class_residuals_f32", "ss_hip_class_residuals_f64",
     "ss_hip_homotopy_classify_batch_f32", "ss_hip_homotopy_classify_batch_f64",
+    "ss_hip_homotopy_replace_columns_f32", "ss_hip_homotopy_replace_columns_f64",
 ]
 
 
@@ -185,6 +186,9 @@ def lib():
         f = getattr(L, "ss_hip_homotopy_classify_batch_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, vp, pd, vp, vp, cp, sz]
+        f = getattr(L, "ss_hip_homotopy_replace_columns_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, vp, pd, pd, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
@@ -344,6 +348,39 @@ class Homotopy:
     def _check(self, rc, err):
         if rc != 0:
             raise SsHipError(rc, err.value.decode())
+
+    def replace_columns(self, cols, V):
+        """Column cols[s] of the dictionary becomes V[:, s], in place (include/ss_hip.h, ss_hip_homotopy_replace_columns_*): every
+        later call returns what a context created from the updated matrix returns.  V: (m, S) — or (m,) for one column — numpy array
+        or torch tensor of the matrix dtype, host or device, any strides the constructor accepts; cols: S distinct column indices,
+        an int sequence, a numpy array or an int32 / uint32 torch tensor on either side."""
+        vp_, vshape, vstr, vdt, keepv = _describe(V)
+        if vdt != self.dtype:
+            raise TypeError("dtype of V (%s) does not match the matrix (%s)" % (vdt, self.dtype))
+        if len(vshape) == 1:
+            vshape, vstr = (vshape[0], 1), (vstr[0], max(int(vshape[0]), 1) * max(abs(int(vstr[0])), 1))
+        if len(vshape) != 2 or vshape[0] != self.m:
+            raise ValueError("V must be (m, S) or (m,) with m = %d" % self.m)
+        if hasattr(cols, "data_ptr"):
+            import torch
+            if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
+                raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
+            count, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
+        else:
+            arr = np.atleast_1d(np.asarray(cols))
+            if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                raise ValueError("cols must be a 1-D integer sequence")
+            if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
+                raise ValueError("cols must fit in 32 unsigned bits")
+            keepc = np.ascontiguousarray(arr, dtype=np.uint32)
+            count, cptr = int(keepc.shape[0]), keepc.ctypes.data
+        if count != int(vshape[1]):
+            raise ValueError("cols names %d columns, V holds %d" % (count, int(vshape[1])))
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(V)
+        _sync_producers(cols)
+        fn = getattr(lib(), "ss_hip_homotopy_replace_columns_" + self.suffix)
+        self._check(fn(self._h, cptr, count, vp_, vstr[0], vstr[1], err, len(err)), err)
 
     def solve_omp(self, y, tolerance=None, max_iterations=100, out=None):
         """orthogonal matching pursuit on the same device copy -> (x, iter, ||A^T r||_inf)"""
