@@ -616,6 +616,8 @@ void k_irls_solve(const T* __restrict__ Qt, const T* __restrict__ R, const T* __
         T mx;
         uint32_t mi;
         block_max_excl(xnext, n, 0xffffffffu, mx, mi, sv, si);
+        const bool has_nan = block_any_nan(xnext, n);             // (an exact-zero pivot of the QR: the reference's order decides)
+        if (has_nan) mx = block_seq_max<T, false>(xnext, n, sv);
         abstol = mx * tol;                                        // :100
         for (uint32_t i = tid; i < n; i += kIrlsThreads) {        // :103-104
             const T v = xnext[i] < abstol ? T(0) : xnext[i];
@@ -633,6 +635,7 @@ void k_irls_solve(const T* __restrict__ Qt, const T* __restrict__ R, const T* __
         } else {
             second = mx;
         }
+        if (has_nan) second = block_seq_max<T, true>(xnext, n, sv);
         {
             const T cand = second / T(n);                         // :110
             if (cand < eps) eps = cand;
@@ -963,6 +966,8 @@ void k_irls_tail(const T* __restrict__ R, uint32_t n, T* __restrict__ vec, T tol
     T mx;
     uint32_t mi;
     block_max_excl(xnext, n, 0xffffffffu, mx, mi, sv, si);
+    const bool has_nan = block_any_nan(xnext, n);                 // (an exact-zero pivot of the QR: the reference's order decides)
+    if (has_nan) mx = block_seq_max<T, false>(xnext, n, sv);
     const T abstol = mx * tol;                                    // :100
     for (uint32_t i = tid; i < n; i += kIrlsThreads) {            // :103-104
         const T v = xnext[i] < abstol ? T(0) : xnext[i];
@@ -980,6 +985,7 @@ void k_irls_tail(const T* __restrict__ R, uint32_t n, T* __restrict__ vec, T tol
     } else {
         second = mx;
     }
+    if (has_nan) second = block_seq_max<T, true>(xnext, n, sv);
     T eps = ctl->eps;
     {
         const T cand = second / T(n);                             // :110

@@ -158,6 +158,8 @@ void k_irlsb_solve(const T* __restrict__ Qt, const T* __restrict__ R, const T* _
         T mx;
         uint32_t mi;
         ib_max_excl(xnext, n, 0xffffffffu, mx, mi, sv, si);
+        const bool has_nan = block_any_nan(xnext, n);             // (an exact-zero pivot of the QR: the reference's order decides)
+        if (has_nan) mx = block_seq_max<T, false>(xnext, n, sv);
         abstol = mx * tol;
         for (uint32_t i = tid; i < n; i += kIbThreads) {
             const T v = xnext[i] < abstol ? T(0) : xnext[i];
@@ -174,6 +176,7 @@ void k_irlsb_solve(const T* __restrict__ Qt, const T* __restrict__ R, const T* _
         } else {
             second = mx;
         }
+        if (has_nan) second = block_seq_max<T, true>(xnext, n, sv);
         {
             const T cand = second / T(n);
             if (cand < eps) eps = cand;
@@ -549,6 +552,8 @@ void k_irlsb_tail(const T* __restrict__ R, uint32_t n, T* __restrict__ vecall, T
     T mx;
     uint32_t mi;
     ib_max_excl(xnext, n, 0xffffffffu, mx, mi, sv, si);
+    const bool has_nan = block_any_nan(xnext, n);                 // (an exact-zero pivot of the QR: the reference's order decides)
+    if (has_nan) mx = block_seq_max<T, false>(xnext, n, sv);
     const T abstol = mx * tol;
     for (uint32_t i = tid; i < n; i += kIbThreads) {
         const T v = xnext[i] < abstol ? T(0) : xnext[i];
@@ -566,6 +571,7 @@ void k_irlsb_tail(const T* __restrict__ R, uint32_t n, T* __restrict__ vecall, T
     } else {
         second = mx;
     }
+    if (has_nan) second = block_seq_max<T, true>(xnext, n, sv);
     T eps = ctl->eps;
     {
         const T cand = second / T(n);

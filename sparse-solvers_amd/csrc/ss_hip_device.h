@@ -122,6 +122,48 @@ __device__ __forceinline__ void block_reduce_pair(T& v, uint32_t& i, T* sv, uint
     i = bi;
 }
 
+// ---- IRLS on a vector that holds a NaN: the reference's maximum and second largest, in its order -------------------------
+// irls-cpu.cpp:100 / :107 read as plain loops in the order of the vector: a running maximum that starts at v[0], a
+// running (largest, second) pair that starts at v[0], v[1].  Every comparison with a NaN is false, so the outcome depends on
+// WHERE the NaN stands — in v[0] it stays the maximum, further back it is passed over — and a tree reduction cannot restate
+// that; one thread walking the vector can.  A NaN appears when the QR met an exact-zero pivot (R x = x divides by it: x[k] is
+// +-inf, the entries above it 0 * inf); without one the reductions' results stand and these are not reached.
+template <typename T>
+__device__ __forceinline__ bool block_any_nan(const T* v, uint32_t n)
+{
+    int f = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) f |= (v[i] != v[i]) ? 1 : 0;
+    return __syncthreads_or(f) != 0;
+}
+template <typename T>
+__device__ __forceinline__ T seq_max(const T* v, uint32_t n)
+{
+    T mx = v[0];
+    for (uint32_t i = 1; i < n; ++i) if (v[i] > mx) mx = v[i];
+    return mx;
+}
+template <typename T>
+__device__ __forceinline__ T seq_second_largest(const T* v, uint32_t n)
+{
+    if (n < 2) return v[0];
+    T a = v[0] > v[1] ? v[0] : v[1], b = v[0] > v[1] ? v[1] : v[0];
+    for (uint32_t i = 2; i < n; ++i) {
+        if (v[i] > a) { b = a; a = v[i]; }
+        else if (v[i] > b) b = v[i];
+    }
+    return b;
+}
+// thread 0 walks, every thread receives the value (s1: one LDS word; the callers' barriers have made v visible)
+template <typename T, bool SECOND>
+__device__ __forceinline__ T block_seq_max(const T* v, uint32_t n, T* s1)
+{
+    if (threadIdx.x == 0) *s1 = SECOND ? seq_second_largest(v, n) : seq_max(v, n);
+    __syncthreads();
+    const T r = *s1;
+    __syncthreads();
+    return r;
+}
+
 // Exponent e of the power-of-two scale that puts the largest |a| of a reduced-precision copy into (target / 2, target]:
 // floor(log2(target / amax)), 0 for an all-zero or non-finite dictionary (screen.hip: k_a16_scale, k_a8_scale; dictupdate.hip)
 __device__ __forceinline__ int pow2_scale_exp(float target, float amax)
