@@ -31,7 +31,9 @@ extern "C" {
                                     entry points ss_hip_irls_solve_batch_*, option "irls_batch_max", and the counters
                                     irls_batch_signals / irls_batch_rounds at the end of ss_hip_stats; classification from compact records:
                                     ss_hip_set_classes, ss_hip_reconstruct_records_*, ss_hip_class_residuals_*, ss_hip_homotopy_classify_batch_* —
-                                    no new option key, no new field of ss_hip_stats) */
+                                    no new option key, no new field of ss_hip_stats; ss_hip_homotopy_replace_columns_*;
+                                    the atom update of dictionary learning, ss_hip_homotopy_atom_update_*, with the test-aid option
+                                    "dl_chunk_max" — no new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -273,6 +275,53 @@ int ss_hip_homotopy_classify_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B
 int ss_hip_homotopy_classify_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
                                        double tol, uint32_t max_iter, uint32_t kmax, void* records,
                                        double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+
+/*
+ * The atom step of dictionary learning (approximate K-SVD: Rubinstein, Zibulevsky, Elad 2008) from compact records (added under
+ * ABI version 7; csrc/dictlearn.hip; NOT in the reference).  Y holds B signals (row b at Y[b*y_stride + i*incy]), `records` their
+ * compact records (ss_hip_homotopy_solve_batch_compact_* / ss_hip_omp_solve_batch_compact_*, same kmax), cols[S] the atoms
+ * (columns) to update; cols == NULL means all n atoms (S is ignored, V is m x n).  For every requested atom j
+ *     r_b = y_b - A x_b                          A x_b accumulated as ss_hip_reconstruct_records_* does, in the context's precision
+ *     U_j = the signals that COUNT (K_b <= kmax: the record is not truncated) and whose record holds column j, in ascending b;
+ *           w_b = that record's value for j
+ *     g_j = sum_{b in U_j} w_b r_b + (sum_{b in U_j} w_b^2) a_j        (= E_j w: the error matrix without atom j's own share)
+ *     v_j = g_j / ||g_j||_2
+ * and the atom is LEFT AS IT IS (v_j = the stored column, bit for bit) when U_j is empty or ||g_j||_2 is zero or not finite.  All
+ * atoms are computed against the same old dictionary and the same residuals (the parallel, Jacobi variant of the sweep: atoms that
+ * share signals do not see each other's update; for S = 1 and a unit-norm old atom the objective cannot rise, for several atoms
+ * that share signals it can — DESIGN.md §3.13d).
+ *   V(i, s)    at V[i*stride_row + s*stride_col]; may be NULL when apply != 0
+ *   usage[s]   (may be NULL) |U_j|; bit 31 is set when the atom had users but was left as it is
+ *   objective  (may be NULL) one double: sum ||r_b||_2^2 over the counting signals, BEFORE the update (a record with K = 0
+ *              counts and adds ||y_b||^2)
+ *   apply != 0 the atoms that changed (usage in 1 .. 2^31 - 1) are written into the context as
+ *              ss_hip_homotopy_replace_columns_* with those columns and those V writes them: the same words in every derived copy
+ *              (fp16 / fp8 copies, norms, scales, OMP norms, G), the routing reset; when no atom changed nothing is touched
+ * All data pointers may be host or device pointers.
+ * CONTRACT: an atom's column of V and its usage are a function of the records, Y, A and the atom alone — bit for bit the same
+ * whatever else was requested, with host or device pointers, whatever the context did before.  Every sum runs in one documented
+ * order (csrc/dictlearn.hip): no floating-point atomics, no dependence on B, on the internal chunking or on the launch geometry.
+ * Validation happens before anything is written: a failing call leaves the context and the outputs untouched.
+ *   SS_HIP_EINVAL  null ctx, Y or records; V null with apply == 0; an IRLS or a column-sharded context; kmax outside 1..4096;
+ *                  records not 8-byte aligned; a non-positive incy, y_stride (for every B, B == 1 included), stride_row or
+ *                  stride_col (the two of V only when V is given); a column >= n or named twice in cols; a record
+ *                  index >= n (found on the device, never used as an address)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   B == 0, or S == 0 with cols given: SS_HIP_OK, nothing touched — after the checks above that need no data (null pointers, context,
+ *                  type, kmax, alignment, increments and strides), which such a call fails like any other
+ */
+int ss_hip_homotopy_atom_update_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const void* records, uint32_t kmax,
+                                    const uint32_t* cols, size_t S,
+                                    float* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                    uint32_t* usage, double* objective, uint32_t apply,
+                                    char* err, size_t errlen);
+int ss_hip_homotopy_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const void* records, uint32_t kmax,
+                                    const uint32_t* cols, size_t S,
+                                    double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                    uint32_t* usage, double* objective, uint32_t apply,
+                                    char* err, size_t errlen);
 
 /*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
@@ -669,6 +718,8 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *   "batch_chunk"    signals processed together by the batched path (default 4096)
  *   "irls_batch_max" IRLS contexts: most signals one chunk of ss_hip_irls_solve_batch_* holds (default 256; 1..65535); chunks are
  *                    also bounded by 1 GiB of per-signal state (n^2 + 5 n + 2 ldm elements each).  Never changes a result
+ *   "dl_chunk_max"   test aid: most signals whose residuals ss_hip_homotopy_atom_update_* holds at once (default 0 = a byte budget
+ *                    alone; at most 32768); chunks are taken in ascending order with g carried between them: never changes a result
  *   "batch_gram_min" (where the screened batch form applies — "batch_screen" — G pays later and is formed for a batch of at
  *                    least max(batch_gram_min, 1536) signals, or once the context has received 3072 signals in batches)
  *                    smallest lock-step batch that forms G = A^T A (n^2 fp32, 2 m n^2 flops once) and then

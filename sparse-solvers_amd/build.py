@@ -57,6 +57,8 @@ HIP_UNITS = [
     ("classify.hip", ["-ffp-contract=off"]),
     # columns of a live context replaced in place: the statistics and conversions are screen.hip's statements, built like screen.hip
     ("dictupdate.hip", []),
+    # the atom update of dictionary learning from compact records: products and sums rounded separately, in the documented order
+    ("dictlearn.hip", ["-ffp-contract=off"]),
 ]
 
 

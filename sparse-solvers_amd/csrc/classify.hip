@@ -29,6 +29,7 @@
 // No floating-point atomics; nothing depends on B, on the chunking or on the launch geometry: a signal's words are a function of its
 // record, its y, the labels and A.
 #include "ss_hip_internal.h"
+#include "record_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -41,9 +42,6 @@ namespace sship {
 
 namespace {
 
-constexpr uint32_t kClsThreads = 256;
-constexpr uint32_t kClsTileRows = 1024;                  // rows of y a workgroup holds: four per thread
-constexpr uint32_t kClsInFlight = 8;                     // columns whose loads a thread has in flight
 constexpr uint32_t kClsChunkMax = 1024;                  // most signals per internal chunk ...
 constexpr size_t kClsChunkBytes = (size_t)64 << 20;      // ... and the byte budget of a chunk's workspace (never changes a result)
 constexpr uint32_t kClsTruncated = 1u, kClsInvalid = 2u; // per-signal flags
@@ -60,76 +58,13 @@ struct ClassifyState {
     size_t rec_all_bytes = 0;
 };
 
-struct HipFail { hipError_t code; const char* what; };
-#define CLS_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw HipFail{ e_, #expr }; } while (0)
-
-template <typename F>
-int guarded(char* err, size_t errlen, const char* prefix, F&& body)
-{
-    try {
-        return body();
-    } catch (const HipFail& f) {
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
-        return f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, std::string(prefix) + ": out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-}
-
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();       // unregistered host memory
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
-}
-
 ClassifyState* state_of(ss_hip_ctx* ctx)
 {
     if (!ctx->cls) ctx->cls = new ClassifyState();
     return static_cast<ClassifyState*>(ctx->cls);
 }
 
-void grow(unsigned char*& p, size_t& have, size_t need, const char* what)
-{
-    if (have >= need) return;
-    if (p) CLS_CHK(hipFree(p));
-    p = nullptr;
-    have = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need);
-    if (e != hipSuccess) { p = nullptr; throw HipFail{ e, what }; }
-    have = need;
-}
-
-inline size_t record_bytes(uint32_t kmax, size_t elem) { return (16 + (size_t)kmax * (4 + elem) + 7) & ~(size_t)7; }
-
-// carves 256-byte aligned pieces out of the arena; with base == nullptr it only adds up
-struct Carver {
-    unsigned char* base;
-    size_t off = 0;
-    explicit Carver(unsigned char* b) : base(b) {}
-    template <typename P> P* take(size_t count)
-    {
-        P* p = base ? reinterpret_cast<P*>(base + off) : nullptr;
-        off += (count * sizeof(P) + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
-
-// (the values of a fp64 record sit at 16 + 4 kmax: 4-byte aligned only when kmax is odd)
-__device__ inline float load_val(const unsigned char* p, uint32_t e, float) { return reinterpret_cast<const float*>(p)[e]; }
-__device__ inline double load_val(const unsigned char* p, uint32_t e, double)
-{
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(p) + 2u * e;
-    return __longlong_as_double((long long)(((unsigned long long)w[1] << 32) | w[0]));
-}
 
 __global__ __launch_bounds__(256)
 void k_cls_check_labels(const uint32_t* __restrict__ labels, uint32_t n, uint32_t C, uint32_t* __restrict__ bad)
@@ -221,19 +156,6 @@ void k_cls_prepare(const unsigned char* __restrict__ rec, size_t rb, uint32_t km
         sci[b] = v;
         sig[0] = K; sig[1] = nseg; sig[2] = Krec > kmax ? kClsTruncated : 0u; sig[3] = 0u;
     }
-}
-
-template <typename T> struct ClsVec;
-template <> struct ClsVec<float> { typedef float4 type; static constexpr uint32_t W = 4, L = 1; };
-template <> struct ClsVec<double> { typedef double2 type; static constexpr uint32_t W = 2, L = 2; };
-__device__ inline float vget(const float4& v, uint32_t e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
-__device__ inline double vget(const double2& v, uint32_t e) { return e == 0 ? v.x : v.y; }
-
-__device__ inline double wave_sum(double s)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    return s;
 }
 
 // STORE: acc of ONE segment over all stored entries goes to yhat ([signals][ldm]); otherwise the tile's partial sums of squares
@@ -413,51 +335,11 @@ void k_cls_scatter(const T* __restrict__ src, uint32_t ld, uint32_t m, T* __rest
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-// the checks the three record entry points share, in the order they are reported
-template <typename T>
-int check_common(const ss_hip_ctx* ctx, const char* who, const void* records, bool need_records, uint32_t kmax, char* err, size_t errlen)
-{
-    const std::string w(who);
-    if (!ctx) { set_err(err, errlen, w + ": null context"); return SS_HIP_EINVAL; }
-    if (ctx->kind != 0) { set_err(err, errlen, w + ": this context was created for IRLS"); return SS_HIP_EINVAL; }
-    if (ctx->colshard != nullptr) { set_err(err, errlen, w + ": not available on a column-sharded context"); return SS_HIP_EINVAL; }
-    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, w + ": element type mismatch"); return SS_HIP_ETYPE; }
-    if (need_records && !records) { set_err(err, errlen, w + ": records must not be null"); return SS_HIP_EINVAL; }
-    if (kmax == 0 || kmax > kKcapLimit || (reinterpret_cast<uintptr_t>(records) & 7u)) {
-        set_err(err, errlen, w + ": kmax must be 1..4096 and records 8-byte aligned");
-        return SS_HIP_EINVAL;
-    }
-    return SS_HIP_OK;
-}
-
 int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errlen)
 {
     const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
     if (!cs || !cs->labels) { set_err(err, errlen, std::string(who) + ": no classes set (ss_hip_set_classes)"); return SS_HIP_EINVAL; }
     return SS_HIP_OK;
-}
-
-int bad_index(uint32_t first_bad, const char* who, char* err, size_t errlen)
-{
-    set_err(err, errlen, std::string(who) + ": record " + std::to_string(first_bad) + " holds a column index >= n");
-    return SS_HIP_EINVAL;
-}
-
-// rows b0 .. b0 + Bc - 1 of a HOST matrix (row stride / increment in elements) into dst [Bc][m], contiguous
-template <typename T>
-void upload_rows(ss_hip_ctx* ctx, T* dst, const T* src, ptrdiff_t stride, ptrdiff_t inc, size_t b0, size_t Bc, std::vector<T>& tmp)
-{
-    const size_t m = ctx->m;
-    if (inc == 1 && stride >= (ptrdiff_t)m) {
-        CLS_CHK(hipMemcpy2DAsync(dst, m * sizeof(T), src + (ptrdiff_t)b0 * stride, (size_t)stride * sizeof(T), m * sizeof(T), Bc,
-                                 hipMemcpyHostToDevice, ctx->stream));
-        return;
-    }
-    tmp.resize(Bc * m);
-    for (size_t b = 0; b < Bc; ++b)
-        for (size_t i = 0; i < m; ++i) tmp[b * m + i] = src[(ptrdiff_t)(b0 + b) * stride + (ptrdiff_t)i * inc];
-    CLS_CHK(hipMemcpyAsync(dst, tmp.data(), Bc * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    CLS_CHK(hipStreamSynchronize(ctx->stream));        // (tmp is filled again for the next chunk)
 }
 
 template <typename T>

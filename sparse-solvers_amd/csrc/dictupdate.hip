@@ -144,33 +144,23 @@ void reset_routing(ss_hip_ctx* ctx)
     ctx->solo_failed = 0;
 }
 
+}  // namespace
+
+// The update itself, for a validated list (distinct columns < n; hc = its host copy) and columns that are on the device already:
+// V(i, s) = V[i * rs + s * cs].  What ss_hip_homotopy_replace_columns_* runs after its validation and staging, and what the
+// atom update of dictionary learning (dictlearn.hip) applies its changed atoms with.  Returns when the update is complete.
 template <typename T>
-int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, ptrdiff_t rs, ptrdiff_t cs, char* err, size_t errlen)
+int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* dcols, const std::vector<uint32_t>& hc, const T* dV, long long drs, long long dcs,
+                           char* err, size_t errlen)
 {
-    if (!ctx) { set_err(err, errlen, "replace_columns: null context"); return SS_HIP_EINVAL; }
-    if (ctx->kind != 0) { set_err(err, errlen, "replace_columns: an IRLS context holds the factorised matrix (not supported)"); return SS_HIP_EINVAL; }
-    if (ctx->colshard != nullptr) { set_err(err, errlen, "replace_columns: column-sharded contexts are not supported"); return SS_HIP_EINVAL; }
-    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "replace_columns: element type of the call does not match the context"); return SS_HIP_ETYPE; }
+    const size_t S = hc.size();
     if (S == 0) return SS_HIP_OK;
-    if (!cols || !V) { set_err(err, errlen, "replace_columns: null argument"); return SS_HIP_EINVAL; }
-    if (S > ctx->n) { set_err(err, errlen, "replace_columns: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
     unsigned char* scratch = nullptr;
     int rc = SS_HIP_OK;
     try {
         DU_CHK(hipSetDevice(ctx->device));
-        const size_t m = ctx->m, n = ctx->n;
+        const size_t m = ctx->m;
         const uint32_t ldm = ctx->ldm, np = ctx->n_pad, ntiles = np / kGramTile;
-        const bool cols_dev = on_device(cols), v_dev = on_device(V);
-        // ---- validation, on a host copy of the list: nothing has been written when it fails ----
-        std::vector<uint32_t> hc(S);
-        if (cols_dev) DU_CHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
-        {
-            std::vector<uint32_t> sorted(hc);
-            std::sort(sorted.begin(), sorted.end());
-            if (sorted.back() >= n) { set_err(err, errlen, "replace_columns: column index out of range"); return SS_HIP_EINVAL; }
-            if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_err(err, errlen, "replace_columns: a column is named twice"); return SS_HIP_EINVAL; }
-        }
         // ---- G: which 128-column tiles hold a replaced column ([0 .. ntiles) flags, then the list) ----
         const bool with_g = ctx->gram_full != nullptr && np % kGramTile == 0;
         std::vector<uint32_t> tiles;
@@ -186,28 +176,13 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
             // only when every tile holds a replaced column — then the build itself runs)
             g_full = ntouched == ntiles;
         }
-        // ---- one scratch allocation: the list, the tile table, the two flags, a host V's staged copy ----
+        // ---- one scratch allocation: the tile table, the two flags ----
         auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t off_tiles = up(S * sizeof(uint32_t)), off_flag = off_tiles + up(tiles.size() * sizeof(uint32_t)), off_v = off_flag + 256;
-        DU_CHK(hipMalloc(&scratch, off_v + (v_dev ? 0 : S * m * sizeof(T))));
+        const size_t off_flag = up(tiles.size() * sizeof(uint32_t));
+        DU_CHK(hipMalloc(&scratch, off_flag + 256));
         hipStream_t st = ctx->stream;
-        const uint32_t* dcols = cols_dev ? cols : reinterpret_cast<const uint32_t*>(scratch);
-        if (!cols_dev) DU_CHK(hipMemcpyAsync(scratch, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (!tiles.empty()) DU_CHK(hipMemcpyAsync(scratch + off_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (!tiles.empty()) DU_CHK(hipMemcpyAsync(scratch, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         uint32_t* dmoved = reinterpret_cast<uint32_t*>(scratch + off_flag);
-        const T* dV = V;
-        long long drs = rs, dcs = cs;
-        std::vector<T> pack;
-        if (!v_dev) {
-            // the S new columns, contiguous, through one upload of S * m elements
-            pack.resize(S * m);
-            for (size_t s = 0; s < S; ++s)
-                for (size_t i = 0; i < m; ++i) pack[s * m + i] = V[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs];
-            DU_CHK(hipMemcpyAsync(scratch + off_v, pack.data(), S * m * sizeof(T), hipMemcpyHostToDevice, st));
-            dV = reinterpret_cast<const T*>(scratch + off_v);
-            drs = 1;
-            dcs = (long long)m;
-        }
         // ---- the columns, their statistics, the reduced-precision columns ----
         const ScreenCopies sc = screen_copies(ctx);
         hipLaunchKernelGGL((k_du_columns<T>), dim3((uint32_t)S), dim3(256), 0, st, dV, drs, dcs, dcols, (uint32_t)m, ldm, static_cast<T*>(ctx->At),
@@ -228,7 +203,7 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
                 DU_CHK(ctx->gram_symmetric ? launch_gemm_sym_f32(ctx, ctx->gram_full, ctx->gram_pitch)
                                            : launch_gemm_tn_f32(ctx, static_cast<const float*>(ctx->At), np, ldm, ctx->gram_full, ctx->gram_pitch, nullptr, false));
             } else {
-                DU_CHK(launch_gemm_sym_tiles_f32(ctx, ctx->gram_full, ctx->gram_pitch, reinterpret_cast<const uint32_t*>(scratch + off_tiles), ntouched));
+                DU_CHK(launch_gemm_sym_tiles_f32(ctx, ctx->gram_full, ctx->gram_pitch, reinterpret_cast<const uint32_t*>(scratch), ntouched));
             }
         }
         // ---- Gram columns cached in the workspace: a solve clears the slot map before it caches anything (k_la_reset), the column
@@ -240,6 +215,73 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
         DU_CHK(hipStreamSynchronize(st));
         reset_routing(ctx);
         if (sc.sub != nullptr) reset_routing(sc.sub);
+    } catch (const HipFail& f) {
+        (void)hipGetLastError();
+        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
+        rc = f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
+    } catch (const std::bad_alloc&) {
+        set_err(err, errlen, "replace_columns: out of host memory");
+        rc = SS_HIP_ENOMEM;
+    }
+    if (scratch) (void)hipFree(scratch);
+    return rc;
+}
+
+template int replace_columns_device<float>(ss_hip_ctx*, const uint32_t*, const std::vector<uint32_t>&, const float*, long long, long long, char*, size_t);
+template int replace_columns_device<double>(ss_hip_ctx*, const uint32_t*, const std::vector<uint32_t>&, const double*, long long, long long, char*, size_t);
+
+namespace {
+
+template <typename T>
+int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, ptrdiff_t rs, ptrdiff_t cs, char* err, size_t errlen)
+{
+    if (!ctx) { set_err(err, errlen, "replace_columns: null context"); return SS_HIP_EINVAL; }
+    if (ctx->kind != 0) { set_err(err, errlen, "replace_columns: an IRLS context holds the factorised matrix (not supported)"); return SS_HIP_EINVAL; }
+    if (ctx->colshard != nullptr) { set_err(err, errlen, "replace_columns: column-sharded contexts are not supported"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "replace_columns: element type of the call does not match the context"); return SS_HIP_ETYPE; }
+    if (S == 0) return SS_HIP_OK;
+    if (!cols || !V) { set_err(err, errlen, "replace_columns: null argument"); return SS_HIP_EINVAL; }
+    if (S > ctx->n) { set_err(err, errlen, "replace_columns: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
+    unsigned char* scratch = nullptr;
+    int rc = SS_HIP_OK;
+    try {
+        DU_CHK(hipSetDevice(ctx->device));
+        const size_t m = ctx->m, n = ctx->n;
+        const bool cols_dev = on_device(cols), v_dev = on_device(V);
+        // ---- validation, on a host copy of the list: nothing has been written when it fails ----
+        std::vector<uint32_t> hc(S);
+        if (cols_dev) DU_CHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
+        {
+            std::vector<uint32_t> sorted(hc);
+            std::sort(sorted.begin(), sorted.end());
+            if (sorted.back() >= n) { set_err(err, errlen, "replace_columns: column index out of range"); return SS_HIP_EINVAL; }
+            if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_err(err, errlen, "replace_columns: a column is named twice"); return SS_HIP_EINVAL; }
+        }
+        // ---- the list and a host V staged on the device (one allocation), then the update itself ----
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t off_v = up(S * sizeof(uint32_t));
+        hipStream_t st = ctx->stream;
+        const uint32_t* dcols = cols;
+        const T* dV = V;
+        long long drs = rs, dcs = cs;
+        std::vector<T> pack;
+        if (!cols_dev || !v_dev) DU_CHK(hipMalloc(&scratch, off_v + (v_dev ? 0 : S * m * sizeof(T))));
+        if (!cols_dev) {
+            DU_CHK(hipMemcpyAsync(scratch, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            dcols = reinterpret_cast<const uint32_t*>(scratch);
+        }
+        if (!v_dev) {
+            // the S new columns, contiguous, through one upload of S * m elements
+            pack.resize(S * m);
+            for (size_t s = 0; s < S; ++s)
+                for (size_t i = 0; i < m; ++i) pack[s * m + i] = V[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs];
+            DU_CHK(hipMemcpyAsync(scratch + off_v, pack.data(), S * m * sizeof(T), hipMemcpyHostToDevice, st));
+            dV = reinterpret_cast<const T*>(scratch + off_v);
+            drs = 1;
+            dcs = (long long)m;
+        }
+        rc = replace_columns_device<T>(ctx, dcols, hc, dV, drs, dcs, err, errlen);
     } catch (const HipFail& f) {
         (void)hipGetLastError();
         set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);

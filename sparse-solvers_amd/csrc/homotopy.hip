@@ -2913,6 +2913,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     if (ctx->c0_batch) (void)hipFree(ctx->c0_batch);
     sship::omp_gram_free(ctx);
     sship::classify_free(ctx);
+    sship::dictlearn_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);
@@ -3163,6 +3164,7 @@ int ss_hip_set_option(ss_hip_ctx* ctx, const char* key, long value)
     if (!std::strcmp(key, "gram_symmetric")) { ctx->gram_symmetric = value ? 1 : 0; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_chunk"))   { ctx->batch_chunk = (int)std::max<long>(4, value); return SS_HIP_OK; }
     if (!std::strcmp(key, "irls_batch_max")) { ctx->irls_batch_max = (int)std::max<long>(1, std::min<long>(65535, value)); return SS_HIP_OK; }
+    if (!std::strcmp(key, "dl_chunk_max")) { ctx->dl_chunk_max = (int)std::max<long>(0, std::min<long>(32768, value)); return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_single")) {
         // (setting the option also forgets what the context has learnt about its signals: the step-aside counters start again)
         ctx->screen_single = (int)std::max<long>(0, std::min<long>(2, value));
@@ -3251,6 +3253,7 @@ int ss_hip_get_option(ss_hip_ctx* ctx, const char* key, long* value)
     if (!std::strcmp(key, "gram_symmetric")) { *value = ctx->gram_symmetric; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_chunk"))   { *value = ctx->batch_chunk; return SS_HIP_OK; }
     if (!std::strcmp(key, "irls_batch_max")) { *value = ctx->irls_batch_max; return SS_HIP_OK; }
+    if (!std::strcmp(key, "dl_chunk_max")) { *value = ctx->dl_chunk_max; return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_single")) { *value = ctx->screen_single; return SS_HIP_OK; }
     if (!std::strcmp(key, "screen_first16")) { *value = ctx->screen_first16; return SS_HIP_OK; }
     if (!std::strcmp(key, "batch_screen"))  { *value = ctx->batch_screen; return SS_HIP_OK; }

@@ -366,6 +366,8 @@ struct ss_hip_ctx {
     void* irls_batch = nullptr;   // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
     int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
     void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
+    void* dl = nullptr;           // sship::DictLearnState* (dictlearn.hip): the workspace of the atom update
+    int dl_chunk_max = 0;         // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
     size_t m = 0, n = 0;
@@ -507,6 +509,13 @@ hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
 void omp_gram_free(ss_hip_ctx* ctx);
 // classification from compact records (classify.hip): releases the labels and the workspace of a context
 void classify_free(ss_hip_ctx* ctx);
+// the atom update of dictionary learning (dictlearn.hip): releases its workspace
+void dictlearn_free(ss_hip_ctx* ctx);
+// a column replacement from the device (dictupdate.hip): the body of ss_hip_homotopy_replace_columns_* behind its validation and
+// staging — cols_dev: the distinct columns (< n), cols_host: the same list on the host, V_dev(i, s) = V_dev[i * rs + s * cs]
+template <typename T>
+int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* cols_dev, const std::vector<uint32_t>& cols_host, const T* V_dev, long long rs,
+                           long long cs, char* err, size_t errlen);
 
 void screen_free(ss_hip_ctx* ctx);
 // what the screened forms derive from A, for a column replacement (dictupdate.hip) to keep current; every pointer null while the

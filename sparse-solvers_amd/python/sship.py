@@ -41,6 +41,7 @@ SYMBOLS = [
     "ss_hip_class_residuals_f32", "ss_hip_class_residuals_f64",
     "ss_hip_homotopy_classify_batch_f32", "ss_hip_homotopy_classify_batch_f64",
     "ss_hip_homotopy_replace_columns_f32", "ss_hip_homotopy_replace_columns_f64",
+    "ss_hip_homotopy_atom_update_f32", "ss_hip_homotopy_atom_update_f64",
 ]
 
 
@@ -189,6 +190,9 @@ def lib():
         f = getattr(L, "ss_hip_homotopy_replace_columns_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, vp, pd, pd, cp, sz]
+        f = getattr(L, "ss_hip_homotopy_atom_update_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, sz, vp, pd, pd, vp, vp, u32, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
@@ -381,6 +385,61 @@ class Homotopy:
         _sync_producers(cols)
         fn = getattr(lib(), "ss_hip_homotopy_replace_columns_" + self.suffix)
         self._check(fn(self._h, cptr, count, vp_, vstr[0], vstr[1], err, len(err)), err)
+
+    def atom_update(self, Y, records, kmax, cols=None, apply=True, out=None):
+        """The atom step of dictionary learning from compact records (include/ss_hip.h, ss_hip_homotopy_atom_update_*): for every
+        atom of `cols` (None = all n) v = g / ||g||_2 with g = sum_b w_b (y_b - A x_b) + (sum_b w_b^2) a_j over the signals whose
+        record holds the atom -> (V (m, S), usage (S,) uint32, objective).  usage[s] = the number of those signals, bit 31 set when
+        the atom had users but was left as it is; an atom without users comes back as the stored column; objective = sum ||y_b - A
+        x_b||^2 before the update.  apply=True writes the changed atoms into the context as replace_columns does.  V and usage
+        live where Y lives (device tensors for a device Y — usage then int32 — else numpy arrays); `out`: an (m, S) array or tensor
+        of the matrix dtype on either side that receives V.  cols: as for replace_columns."""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        rp, B = self._records_arg(records, kmax)
+        if B != int(shape[0]):
+            raise ValueError("Y and records must hold the same number of signals")
+        cptr, keepc, S = None, None, self.n
+        if cols is not None:
+            if hasattr(cols, "data_ptr"):
+                import torch
+                if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
+                    raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
+                S, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
+            else:
+                arr = np.atleast_1d(np.asarray(cols))
+                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                    raise ValueError("cols must be a 1-D integer sequence")
+                if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
+                    raise ValueError("cols must fit in 32 unsigned bits")
+                keepc = np.ascontiguousarray(arr, dtype=np.uint32)
+                S, cptr = int(keepc.shape[0]), keepc.ctypes.data
+        on_dev = hasattr(Y, "data_ptr") and getattr(Y, "is_cuda", False)
+        if on_dev:
+            import torch
+            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
+            V = torch.empty((S, self.m), dtype=tdt, device=Y.device).t() if out is None else out       # (columns contiguous)
+            usage = torch.zeros(S, dtype=torch.int32, device=Y.device)
+            up = usage.data_ptr()
+        else:
+            V = np.empty((S, self.m), dtype=self.dtype).T if out is None else out
+            usage = np.zeros(S, dtype=np.uint32)
+            up = usage.ctypes.data
+        vp_, vshape, vstr, vdt, keepv = _describe(V)
+        if vdt != self.dtype or tuple(vshape) != (self.m, S):
+            raise ValueError("out must be (m, %d) of the matrix dtype" % S)
+        obj = ctypes.c_double(0.0)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(Y, records, V)
+        _sync_producers(cols)
+        fn = getattr(lib(), "ss_hip_homotopy_atom_update_" + self.suffix)
+        # (an empty V has no strides to speak of: S == 0 touches nothing)
+        rs_, cs_ = (vstr[0], vstr[1]) if S and self.m > 1 else (max(int(vstr[0]), 1), max(int(vstr[1]), 1))
+        rc = fn(self._h, Yp, B, strides[0] if B else self.m, strides[1] if B else 1, rp, int(kmax), cptr, S, vp_, rs_, cs_, up,
+                ctypes.addressof(obj), 1 if apply else 0, err, len(err))
+        self._check(rc, err)
+        return V, usage, float(obj.value)
 
     def solve_omp(self, y, tolerance=None, max_iterations=100, out=None):
         """orthogonal matching pursuit on the same device copy -> (x, iter, ||A^T r||_inf)"""
