@@ -660,10 +660,7 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *                    (k_scr_recheck) and a last step an outside column stops early is repaired (k_scr_repair); 0 = such signals go back
  *   "gram_reserve"   1 (default) = the memory of G = A^T A is reserved on a helper thread when the first batch of >= 4 signals arrives, so that
  *                    the batch that forms G does not wait for the allocation; 0 = allocated on first use
- *   "temporal_cols"  leading dictionary columns the sweeps read with cache-allocating loads (the rest: non-temporal); 0 (default) = none
- *   "sweep_f64_variant" tiling of the 32-column fp64 pass: 0 (default) = 256 columns / 512 threads, one workgroup per CU; 1, 2 = 128 / 256, two or three
  *   "solo_full_gram" tests: 1 = the speculative form may run with G = A^T A as its cache too (default 0: it does not — gathers of scattered entries)
- *   "early_probe"    developer aid: 1 = the early form without overlap (the passes first, then the speculative launch)
  *   "pass_dbg_ptr"   developer aid: a device buffer (1 + 4 x 4096 u64) that receives a per-workgroup trace of the early form's passes (tools/probe_pass_trace.py)
  *   "colshard_fail_prepare" test aid: 1 = the next column-sharded solve fails on this rank while it prepares (the ranks must all leave)
  *   "ro_slots"       1..8 (default 8; fp64 contexts use at most 4): signals the reference-order engine runs in lock-step per pass over A (batches in
@@ -706,12 +703,6 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *                    progress when the first pass has finished (columns that have entered its support, then those
  *                    closest to entering); 0 = from the |c0| ranking.  Decides which Gram columns are fetched when,
  *                    never a result
- *   "sweep_cols_f64" 64 (default) / 32: right-hand sides of one fp64 lookahead pass (k_gemm32_tn_f64<RH>): fp64
- *                    passes are MFMA-bound, so 64 columns cost 1.6 x the time of 32 and a solve needs fewer passes
- *                    and fewer round trips through the host; same results as 32
- *   "sweep_cols_f64_late" 32 (default) / 64: the same for the third and later passes of a solve — misses that late on
- *                    the path are sparse (16384 x 131072, k = 128: the third pass serves the last ~8 iterations), a
- *                    narrow pass (3.4 ms against 5.4) covers them; same results
  *   "cache_mib"      memory budget of the lookahead engine's Gram-column cache (default 2048)
  *   "batch_min"      smallest fp32 batch that takes the lock-step MFMA path (default 192: below
  *                    that, one lookahead solve per signal is faster)
@@ -725,24 +716,17 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *                    smallest lock-step batch that forms G = A^T A (n^2 fp32, 2 m n^2 flops once) and then
  *                    takes every signal's correlations from rows of G instead of two GEMMs per round
  *                    (default 512; once G exists every lock-step batch uses it; 0 = never)
- *   "batch_cols_min" / "batch_cols_max"  fp32 batches of at least batch_cols_min signals (default 24; max 0 = no upper
- *                    limit) with no G at hand — below batch_gram_min, or G switched off or too large — run in
- *                    lock-step in the column form: per round ONE pass over A per 64 signals forms the Gram columns
+ *   "batch_cols_min" fp32 batches of at least batch_cols_min signals (default 24) with no G at hand — below
+ *                    batch_gram_min, or G switched off or too large — run in lock-step in the column form: per round ONE pass over A per 64 signals forms the Gram columns
  *                    of the columns that enter (a single solve spends three passes on one signal), and correlations
  *                    come from those cached columns as in the Gram form; chunks of at most 448 signals; smaller
  *                    batches run one solve per signal; batch_cols_min = 0: never (round-1 behaviour: one solve per
  *                    signal below batch_min, two GEMMs per round from there on)
- *   "scan_blocks"    workgroups per signal of the step-length scan in the lock-step Gram forms with 64 signals or more
- *                    (default 8: a launch of 4096 signals x 64 workgroups spends its time on reductions and tickets,
- *                    not on its 9 bytes per column; same results); 0 = one per 1024 columns
  *   "batch_fused_scan" 1 (default) = the lock-step Gram forms scan inside the Gram-form pass (k_la_cqs: c and q of a
  *                    workgroup's columns stay in registers while the signal's workgroups meet for lambda = ||c||_inf);
- *                    0 = two kernels (k_la_cq writes c and q, k_scansel reads them back).  Same results bit for bit
- *   "cq_cols" / "cq_rows"  columns per thread (4, 8, 16 (default), 32) and rows of G in flight per thread (1, 2 (default),
- *                    3, 4, 8) of that pass: a workgroup of 256 threads reads runs of 256 * cq_cols columns of each of its
- *                    signal's K rows of G — 16 KiB runs stream at 82 % of the HBM peak where 4 KiB runs reached 64 %.
- *                    "cq_vec4" 1 = four consecutive columns per thread with 16-byte loads (cq_cols = 4 only; no faster).
- *                    Same results bit for bit
+ *                    0 = two kernels (k_la_cq writes c and q, k_scansel reads them back).  Same results bit for bit.
+ *                    (A workgroup of 256 threads reads runs of 4096 columns of each of its signal's K rows of G, two rows in
+ *                    flight per thread: 16 KiB runs stream at 82 % of the HBM peak where 4 KiB runs reached 64 %.)
  *   "gram_full_gib"  largest G — and largest column cache of the column form — that may be allocated
  *                    (default 64 GiB; 0 = never form G)
  *   "gram_full_after" opt-in (default 0 = never): single-signal solves (fp32) after which the context forms G

@@ -297,6 +297,7 @@ __device__ __forceinline__ bool select_toggle(uint32_t round, T c_inf, uint32_t 
 // ---- k_scansel: find_max_gamma's scan (homotopy-cpu.cpp:122-163) in every workgroup,
 // ---- then loop control, pick, support toggle and x update in the last one to arrive ----
 constexpr int kScanPerThread = 4;
+constexpr uint32_t kScanBlocksMany = 8;   // workgroups per slot of a batched Gram form's scan with 64 slots or more
 
 template <typename T>
 __global__ __launch_bounds__(kSmallThreads)
@@ -567,61 +568,27 @@ void k_la_top(const T* __restrict__ tcand, const T* __restrict__ c, uint32_t n, 
     }
 }
 
-// four consecutive elements with 16-byte loads (rows of the Gram cache, c0): a wave reads 1 KiB (fp32) per instruction
-// where four strided 4-byte loads per lane moved 256 bytes each
-__device__ __forceinline__ void load4(const float* __restrict__ p, float (&v)[4])
-{
-    const v4f t = *reinterpret_cast<const v4f*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-}
-__device__ __forceinline__ void load4(const double* __restrict__ p, double (&v)[4])
-{
-    const v2d a = *reinterpret_cast<const v2d*>(p), b = *reinterpret_cast<const v2d*>(p + 2);
-    v[0] = a[0]; v[1] = a[1]; v[2] = b[0]; v[3] = b[1];
-}
-
-// the four columns of a thread: VEC — consecutive (base + 4 tid .. + 3, one 16-byte load per row); else strided by the
-// workgroup (base + tid + 256 k, four 4-byte loads per row: each wave-instruction reads 256 contiguous bytes)
+// the N columns of a thread, strided by the workgroup (base + tid + 256 k, N 4-byte loads per row: each wave-instruction
+// reads 256 contiguous bytes; 16-byte loads of consecutive columns measured no better)
 // (lim: padded columns left from the workgroup's base — a multiple of 256, so the guards are uniform per workgroup and
-// per k: rows of c0 hold n_pad columns, a multiple of 256 but not of the workgroup's run)
-template <bool VEC, typename T>
-__device__ __forceinline__ void load_cols(const T* __restrict__ p, T (&v)[4], uint32_t lim)
+// per k: rows of c0 hold n_pad columns, a multiple of 256 but not of the workgroup's run — a wide workgroup at the end of
+// a row reads only the 256-column groups that exist)
+template <int N, typename T>
+__device__ __forceinline__ void load_cols(const T* __restrict__ p, T (&v)[N], uint32_t lim)
 {
-    if (VEC) {
-        if (4u * threadIdx.x < lim) load4(p, v);
-        else { v[0] = v[1] = v[2] = v[3] = T(0); }
-    } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = ((uint32_t)k * kSmallThreads < lim) ? p[k * kSmallThreads] : T(0);
-    }
+    for (int k = 0; k < N; ++k) v[k] = ((uint32_t)k * kSmallThreads < lim) ? p[k * kSmallThreads] : T(0);
 }
-// the same with N columns per thread (strided form; VEC only with N == 4)
-// (lim: padded columns left from the workgroup's base, a multiple of 256: a wide workgroup at the end of a row reads
-// only the 256-column groups that exist — uniform per workgroup)
-template <bool VEC, int N, typename T>
-__device__ __forceinline__ void load_colsN(const T* __restrict__ p, T (&v)[N], uint32_t lim)
-{
-    static_assert(!VEC || N == 4, "16-byte form: four columns per thread");
-    if (VEC) {
-        T t[4] = { T(0), T(0), T(0), T(0) };
-        if (4u * threadIdx.x < lim) load4(p, t);
-        for (int k = 0; k < 4 && k < N; ++k) v[k] = t[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = ((uint32_t)k * kSmallThreads < lim) ? p[k * kSmallThreads] : T(0);
-    }
-}
-template <bool VEC>
 __device__ __forceinline__ uint32_t col_of(uint32_t base, uint32_t tid, int k)
 {
-    return VEC ? base + 4u * tid + (uint32_t)k : base + (uint32_t)k * kSmallThreads + tid;
+    return base + (uint32_t)k * kSmallThreads + tid;
 }
 
 // c = c0 - sum_j x_j g_j ; q = sum_j d_j g_j over the touched columns; partial max |c|
 constexpr uint32_t kCqChunk = 1024;
 constexpr uint32_t kCqTile = 256;        // touched columns staged in LDS per pass
 
-template <typename T, bool VEC>
+template <typename T>
 __global__ __launch_bounds__(kSmallThreads)
 void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, const T* __restrict__ c0,
              const T* __restrict__ x, const T* __restrict__ d, const uint32_t* __restrict__ touched2,
@@ -647,7 +614,7 @@ void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, 
     const uint32_t* touched = touched2 + (size_t)st->cur * L.kcap;
     const uint32_t base = blockIdx.x * kCqChunk;
     const uint32_t lim = L.n_pad - base;                       // (padded columns left from here)
-    const T* gbase = gcache + base + (VEC ? 4u : 1u) * threadIdx.x;               // gpitch % 1024 == 0: rows never run out
+    const T* gbase = gcache + base + threadIdx.x;               // gpitch % 1024 == 0: rows never run out
     T ax[4] = { T(0), T(0), T(0), T(0) }, ad[4] = { T(0), T(0), T(0), T(0) };
     for (uint32_t j0 = 0; j0 < nt; j0 += kCqTile) {
         const uint32_t cnt = (nt - j0 < kCqTile) ? (nt - j0) : kCqTile;
@@ -663,7 +630,7 @@ void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, 
         for (; j + 4 <= cnt; j += 4) {
             T gv[4][4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) load_cols<VEC>(gbase + (size_t)s_slot[j + u] * gpitch, gv[u], lim);
+            for (int u = 0; u < 4; ++u) load_cols(gbase + (size_t)s_slot[j + u] * gpitch, gv[u], lim);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const T xj = s_x[j + u], dj = s_d[j + u];
@@ -673,7 +640,7 @@ void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, 
         }
         for (; j < cnt; ++j) {
             T gv1[4];
-            load_cols<VEC>(gbase + (size_t)s_slot[j] * gpitch, gv1, lim);
+            load_cols(gbase + (size_t)s_slot[j] * gpitch, gv1, lim);
             const T xj = s_x[j], dj = s_d[j];
 #pragma unroll
             for (int k = 0; k < 4; ++k) { ax[k] += xj * gv1[k]; ad[k] += dj * gv1[k]; }
@@ -682,10 +649,10 @@ void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, 
     T bv = T(-1);
     uint32_t bi = 0xffffffffu;
     T c0v[4];
-    load_cols<VEC>(c0 + base + (VEC ? 4u : 1u) * threadIdx.x, c0v, lim);
+    load_cols(c0 + base + threadIdx.x, c0v, lim);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const uint32_t i = col_of<VEC>(base, threadIdx.x, k);
+        const uint32_t i = col_of(base, threadIdx.x, k);
         if (i < n) {
             const T cv = c0v[k] - ax[k];
             c[i] = cv;
@@ -714,7 +681,10 @@ void k_la_cq(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, 
 // slot ends with SS_HIP_ERUNTIME instead of hanging the queue.
 constexpr uint32_t kCqsSpinLimit = 1u << 22;
 
-template <typename T, bool VEC, int CPT, int RIF>
+constexpr int kCqsCols = 16;            // columns per thread: a workgroup reads runs of 4096 columns (16 KiB in fp32) of a row of G
+constexpr int kCqsRows = 2;             // rows of G a thread has in flight (the measurements that chose both: DESIGN.md §3.6)
+
+template <typename T>
 __global__ __launch_bounds__(kSmallThreads)
 void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of, const T* __restrict__ c0,
               T* __restrict__ x, const T* __restrict__ d, uint32_t* __restrict__ touched2, uint32_t* __restrict__ gam2,
@@ -723,6 +693,7 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
               DevState* st, uint32_t round, T tol, uint32_t max_iter, uint32_t* hflags, TraceEntry* trace, uint32_t trace_cap,
               int zero_on_removal, int tie_guard, uint32_t* ndone, uint32_t nslots, int tie_exit)
 {
+    constexpr int CPT = kCqsCols, RIF = kCqsRows;
     const uint32_t kcap = L.kcap;
     const int32_t* slot_tab = slot_of;
     {
@@ -747,7 +718,7 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
     const uint32_t* touched = touched2 + (size_t)st->cur * kcap;
     const uint32_t base = blockIdx.x * (uint32_t)(kSmallThreads * CPT);      // CPT columns per thread
     const uint32_t lim = L.n_pad - base;                                      // (n_pad, a multiple of 256, is what rows hold at least)
-    const T* gbase = gcache + base + (VEC ? 4u : 1u) * threadIdx.x;
+    const T* gbase = gcache + base + threadIdx.x;
     T ax[CPT], ad[CPT];
 #pragma unroll
     for (int k = 0; k < CPT; ++k) { ax[k] = T(0); ad[k] = T(0); }
@@ -765,7 +736,7 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
         for (; j + RIF <= cnt; j += RIF) {                       // RIF rows of G in flight per thread
             T gv[RIF][CPT];
 #pragma unroll
-            for (int u = 0; u < RIF; ++u) load_colsN<VEC, CPT>(gbase + (size_t)s_slot[j + u] * gpitch, gv[u], lim);
+            for (int u = 0; u < RIF; ++u) load_cols(gbase + (size_t)s_slot[j + u] * gpitch, gv[u], lim);
 #pragma unroll
             for (int u = 0; u < RIF; ++u) {
                 const T xj = s_x[j + u], dj = s_d[j + u];
@@ -775,7 +746,7 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
         }
         for (; j < cnt; ++j) {
             T gv1[CPT];
-            load_colsN<VEC, CPT>(gbase + (size_t)s_slot[j] * gpitch, gv1, lim);
+            load_cols(gbase + (size_t)s_slot[j] * gpitch, gv1, lim);
             const T xj = s_x[j], dj = s_d[j];
 #pragma unroll
             for (int k = 0; k < CPT; ++k) { ax[k] += xj * gv1[k]; ad[k] += dj * gv1[k]; }
@@ -786,10 +757,10 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
     T bv = T(-1);
     uint32_t bi = 0xffffffffu;
     T c0v[CPT];
-    load_colsN<VEC, CPT>(c0 + base + (VEC ? 4u : 1u) * threadIdx.x, c0v, lim);
+    load_cols(c0 + base + threadIdx.x, c0v, lim);
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
-        const uint32_t i = col_of<VEC>(base, threadIdx.x, k);
+        const uint32_t i = col_of(base, threadIdx.x, k);
         cv[k] = T(0); qv[k] = T(0); act[k] = 0;
         if (i < n) {
             cv[k] = c0v[k] - ax[k];
@@ -847,7 +818,7 @@ void k_la_cqs(const T* __restrict__ gcache, const int32_t* __restrict__ slot_of,
     bool tie = false;
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
-        const uint32_t i = col_of<VEC>(base, threadIdx.x, k);
+        const uint32_t i = col_of(base, threadIdx.x, k);
         if (i < n) {
             T m = Lim<T>::max();
             if (act[k]) {
@@ -1982,7 +1953,7 @@ hipError_t launch_la_cq(const ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t* npart
     const uint32_t nb = (n + kCqChunk - 1) / kCqChunk;
     if (nb > ws.dims.pmax_stride) return hipErrorInvalidValue;
     if (nparts_out) *nparts_out = nb;
-    hipLaunchKernelGGL((k_la_cq<T, false>), dim3(nb), dim3(kSmallThreads), 0, ctx->stream, ws.gcache, ws.slot_of,
+    hipLaunchKernelGGL((k_la_cq<T>), dim3(nb), dim3(kSmallThreads), 0, ctx->stream, ws.gcache, ws.slot_of,
                        ws.c0, ws.x, ws.d, ws.touched, n, ws.gpitch, ws.dims, ws.c, ws.q, ws.pmax_val, ws.pmax_idx, ws.st);
     return hipGetLastError();
 }
@@ -2115,46 +2086,19 @@ hipError_t launch_cq_gram_batched(const ss_hip_ctx* ctx, Workspace<T>& ws, uint3
     if (nparts_out) *nparts_out = nb;
     if (round != 0) {
         if (nb > ws.dims.pmin_stride) return hipErrorInvalidValue;
-#define SS_CQS_LAUNCH(VEC)                                                                                                   \
-        hipLaunchKernelGGL((k_la_cqs<T, VEC, 4, 4>), dim3(nb, nslots), dim3(kSmallThreads), 0, ctx->stream, G, bslot,              \
-                           c0b, ws.x, (const T*)ws.d, ws.touched, ws.gam, n, gpitch, ws.dims, ws.c, ws.q,                           \
-                           ws.pmax_val, ws.pmax_idx, ws.pmin_val, ws.pmin_idx, ws.insup, ws.st, round, tol, max_iter,               \
-                           ctx->dev_flags, ws.trace, ws.trace_cap, ctx->zero_on_removal, ctx->tie_guard, ws.ndone, nslots,          \
-                           (ctx->tie_rerun && !ctx->tie_guard) ? 1 : 0)
-#define SS_CQS_WIDE(CPT, RIF)                                                                                               \
-        {                                                                                                                    \
-            const uint32_t nbw = (n + (uint32_t)(kSmallThreads * CPT) - 1u) / (uint32_t)(kSmallThreads * CPT);                     \
-            hipLaunchKernelGGL((k_la_cqs<T, false, CPT, RIF>), dim3(nbw, nslots), dim3(kSmallThreads), 0, ctx->stream, G, bslot,   \
-                               c0b, ws.x, (const T*)ws.d, ws.touched, ws.gam, n, gpitch, ws.dims, ws.c, ws.q,                      \
-                               ws.pmax_val, ws.pmax_idx, ws.pmin_val, ws.pmin_idx, ws.insup, ws.st, round, tol, max_iter,          \
-                               ctx->dev_flags, ws.trace, ws.trace_cap, ctx->zero_on_removal, ctx->tie_guard, ws.ndone, nslots,     \
-                               (ctx->tie_rerun && !ctx->tie_guard) ? 1 : 0);                                                       \
-            if (nparts_out) *nparts_out = nbw;                                                                               \
-        }
-        // columns per thread x Gram rows in flight (options cq_cols, cq_rows): wider workgroups read longer runs of a row
-        const int cc = ctx->cq_cols, rr = ctx->cq_rows;
-        if (cc == 8 && rr == 2) SS_CQS_WIDE(8, 2)
-        else if (cc == 8 && rr == 4) SS_CQS_WIDE(8, 4)
-        else if (cc == 8 && rr == 8) SS_CQS_WIDE(8, 8)
-        else if (cc == 16 && rr == 2) SS_CQS_WIDE(16, 2)
-        else if (cc == 16 && rr == 4) SS_CQS_WIDE(16, 4)
-        else if (cc == 4 && rr == 8) SS_CQS_WIDE(4, 8)
-        else if (cc == 32 && rr == 2) SS_CQS_WIDE(32, 2)
-        else if (cc == 8 && rr == 1) SS_CQS_WIDE(8, 1)
-        else if (cc == 16 && rr == 1) SS_CQS_WIDE(16, 1)
-        else if (cc == 32 && rr == 1) SS_CQS_WIDE(32, 1)
-        else if (cc == 16 && rr == 3) SS_CQS_WIDE(16, 3)
-        else if (ctx->cq_vec4) SS_CQS_LAUNCH(true); else SS_CQS_LAUNCH(false);
-#undef SS_CQS_WIDE
-#undef SS_CQS_LAUNCH
+        // (a workgroup of 256 threads owns a run of 256 * kCqsCols columns)
+        const uint32_t nbw = (n + (uint32_t)(kSmallThreads * kCqsCols) - 1u) / (uint32_t)(kSmallThreads * kCqsCols);
+        hipLaunchKernelGGL((k_la_cqs<T>), dim3(nbw, nslots), dim3(kSmallThreads), 0, ctx->stream, G, bslot,
+                           c0b, ws.x, (const T*)ws.d, ws.touched, ws.gam, n, gpitch, ws.dims, ws.c, ws.q,
+                           ws.pmax_val, ws.pmax_idx, ws.pmin_val, ws.pmin_idx, ws.insup, ws.st, round, tol, max_iter,
+                           ctx->dev_flags, ws.trace, ws.trace_cap, ctx->zero_on_removal, ctx->tie_guard, ws.ndone, nslots,
+                           (ctx->tie_rerun && !ctx->tie_guard) ? 1 : 0);
+        if (nparts_out) *nparts_out = nbw;
         return hipGetLastError();
     }
-#define SS_CQ_LAUNCH(VEC)                                                                                                    \
-    hipLaunchKernelGGL((k_la_cq<T, VEC>), dim3(nb, nslots), dim3(kSmallThreads), 0, ctx->stream, G, bslot,                         \
-                       c0b, (const T*)ws.x, (const T*)ws.d, (const uint32_t*)ws.touched, n, gpitch, ws.dims, ws.c, ws.q,            \
-                       ws.pmax_val, ws.pmax_idx, (const DevState*)ws.st)
-    if (ctx->cq_vec4) SS_CQ_LAUNCH(true); else SS_CQ_LAUNCH(false);
-#undef SS_CQ_LAUNCH
+    hipLaunchKernelGGL((k_la_cq<T>), dim3(nb, nslots), dim3(kSmallThreads), 0, ctx->stream, G, bslot,
+                       c0b, (const T*)ws.x, (const T*)ws.d, (const uint32_t*)ws.touched, n, gpitch, ws.dims, ws.c, ws.q,
+                       ws.pmax_val, ws.pmax_idx, (const DevState*)ws.st);
     return hipGetLastError();
 }
 
@@ -2170,8 +2114,8 @@ hipError_t launch_tail_gram_batched(const ss_hip_ctx* ctx, Workspace<T>& ws, uin
     uint32_t ns = (n + per_block - 1) / per_block;
     if (ns > ws.dims.pmin_stride) ns = ws.dims.pmin_stride;
     // (many slots: fewer, longer workgroups per slot — the kernel grid-strides; with 64 per slot a launch of 4096 slots is
-    // 262 144 workgroups whose reductions and tickets, not their 9 bytes per column, set its time; option scan_blocks)
-    if (nslots >= 64u && ctx->scan_blocks > 0 && ns > (uint32_t)ctx->scan_blocks) ns = (uint32_t)ctx->scan_blocks;
+    // 262 144 workgroups whose reductions and tickets, not their 9 bytes per column, set its time)
+    if (nslots >= 64u && ns > kScanBlocksMany) ns = kScanBlocksMany;
     if (!scan_done)          // (fused form: k_la_cqs has scanned and picked already)
     hipLaunchKernelGGL((k_scansel<T>), dim3(ns, nslots), dim3(kSmallThreads), 0, ctx->stream, round, tol,
                        max_iter, n, ws.c, ws.q, ws.x, ws.d, ws.insup, ws.pmax_val, ws.pmax_idx,

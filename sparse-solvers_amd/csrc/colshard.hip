@@ -848,7 +848,7 @@ int colshard_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint
                            AS, cs->gam, cs->tch, cs->trow, xt, ds, inv, ws.d, ws.insup, dst, trace);
         CSHIP(hipGetLastError());
         const uint32_t rp_blocks = (ldm + kCsThreads - 1) / kCsThreads;
-        uint32_t scan_blocks = std::max<uint32_t>(1u, std::min<uint32_t>((nl + kCsThreads * 4 - 1) / (kCsThreads * 4), kMaxScanBlocks / 2));
+        uint32_t nscan = std::max<uint32_t>(1u, std::min<uint32_t>((nl + kCsThreads * 4 - 1) / (kCsThreads * 4), kMaxScanBlocks / 2));
         // Rounds are enqueued in blocks of `block` and the replicated `done` flag is read back after each block: every
         // rank sees the same flag at the same round, so all ranks issue the same collectives.
         const uint32_t block = (uint32_t)std::max(1, std::min(ctx->lookahead * 2, 16));
@@ -864,7 +864,7 @@ int colshard_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint
                 hipLaunchKernelGGL((k_cs_lmax<T>), dim3(1), dim3(kCsThreads), 0, st, (const T*)ws.pmax_val, (const uint32_t*)ws.pmax_idx, nb,
                                    cs->col_lo, nl, red_max, rk, W, (const CsStateT<T>*)dst);
                 cs_allreduce(ctx, cs, red_max, rw, kNcclUint64, kNcclMax);
-                hipLaunchKernelGGL((k_cs_scan<T>), dim3(scan_blocks), dim3(kCsThreads), 0, st, (uint32_t)round, tol, max_iter, nl, cs->col_lo,
+                hipLaunchKernelGGL((k_cs_scan<T>), dim3(nscan), dim3(kCsThreads), 0, st, (uint32_t)round, tol, max_iter, nl, cs->col_lo,
                                    (const T*)ws.c, (const T*)ws.q, (const T*)ws.x, (const T*)ws.d, (const uint8_t*)ws.insup,
                                    (const uint64_t*)red_max, red_min, rk, W, pmin, ctx->tie_guard, dst, ctx->dev_flags);
                 cs_allreduce(ctx, cs, red_min, rw, kNcclUint64, op_min);

@@ -696,7 +696,7 @@ constexpr int DLD = DK + 2;                  // LDS row pitch in doubles (144 B,
 // (MFMA-bound: ~3.5 ms at the peak) but not the bytes, so one wide pass costs little more than one narrow pass and
 // replaces two of them.
 // HN / HT / BPC: 256 columns per 512-thread workgroup, one per CU (default), or 128 columns per 256-thread workgroup,
-// two or three per CU — one workgroup's barrier waits are then another's MFMAs (SQ counters, DESIGN.md §3.9: with one
+// three per CU (ss_hip_ctx::pass_tile128) — one workgroup's barrier waits are then another's MFMAs (SQ counters, DESIGN.md §3.9: with one
 // workgroup per CU a third of the wave cycles of the 32-column pass are parked at the barrier).
 template <int RH, int HN = 256, int HT = 512, int BPC = 1>
 __global__ __launch_bounds__(HT, BPC)
@@ -880,17 +880,13 @@ hipError_t launch_gemm32_tn_f64(const ss_hip_ctx* ctx, const uint32_t* rcols, co
 {
     if (ctx->n_pad % 256 != 0 || ctx->ldm % DK != 0) return hipErrorInvalidValue;
     if (ctx->pass_ksplit > 1 && ctx->pass_part != nullptr) return launch_gemm_split_f64<32>(ctx, rcols, drows, D, ldd, st);
-    if (ctx->sweep_f64_variant == 1 || ctx->sweep_f64_variant == 2) {
-        // 128-column tiles, 256 threads, two or three workgroups per CU
+    if (ctx->pass_tile128) {
+        // 128-column tiles, 256 threads, three workgroups per CU
         const uint32_t nt = ctx->n_pad / 128;
-        const uint32_t cap = (ctx->sweep_f64_variant == 1 ? 2u : 3u) * (uint32_t)ctx->num_cus;
+        const uint32_t cap = 3u * (uint32_t)ctx->num_cus;
         const uint32_t g = nt < cap ? nt : cap;
-        if (ctx->sweep_f64_variant == 1)
-            hipLaunchKernelGGL((k_gemm32_tn_f64<32, 128, 256, 2>), dim3(g), dim3(256), 0, ctx->stream, static_cast<const double*>(ctx->At),
-                               rcols, drows, D, ctx->ldm, ctx->ldm, ldd, nt, st);
-        else
-            hipLaunchKernelGGL((k_gemm32_tn_f64<32, 128, 256, 3>), dim3(g), dim3(256), 0, ctx->stream, static_cast<const double*>(ctx->At),
-                               rcols, drows, D, ctx->ldm, ctx->ldm, ldd, nt, st);
+        hipLaunchKernelGGL((k_gemm32_tn_f64<32, 128, 256, 3>), dim3(g), dim3(256), 0, ctx->stream, static_cast<const double*>(ctx->At),
+                           rcols, drows, D, ctx->ldm, ctx->ldm, ldd, nt, st);
         return hipGetLastError();
     }
     const uint32_t ntiles = ctx->n_pad / 256;

@@ -488,14 +488,14 @@ inline hipError_t launch_gemm_first(const ss_hip_ctx* ctx, uint32_t nsel, const 
 { return nsel > 32 ? launch_gemm64_tn_f32(ctx, rcols, drows, D, ldd, st) : launch_gemm32_tn_f32(ctx, rcols, drows, D, ldd, st); }
 inline hipError_t launch_gemm_first(const ss_hip_ctx* ctx, uint32_t nsel, const uint32_t* rcols, const uint32_t* drows, double* D, uint32_t ldd, const DevState* st)
 { return nsel > 32 ? launch_gemm64_tn_f64(ctx, rcols, drows, D, ldd, st) : launch_gemm32_tn_f64(ctx, rcols, drows, D, ldd, st); }
-// columns of a miss sweep: 32 in fp32 (HBM-bound), option sweep_cols_f64 in double precision
+// columns of a miss sweep: 32 in fp32 (HBM-bound); in double precision 64 (the pass is MFMA-bound either way), late ones 32
 // (fetch = how many passes this solve has fetched after its first: in double precision the first two passes are wide;
 // later misses come late on the path — at configs[4] the third pass serves the last ~8 of 128 iterations — and take 32)
 inline uint32_t miss_cols(const ss_hip_ctx*, const Workspace<float>&, uint32_t = 0) { return 32u; }
-inline uint32_t miss_cols(const ss_hip_ctx* ctx, const Workspace<double>& ws, uint32_t fetch = 0)
+inline uint32_t miss_cols(const ss_hip_ctx*, const Workspace<double>& ws, uint32_t fetch = 0)
 {
-    if (!(ctx->sweep_cols_f64 > 32 && ws.gcap >= 192)) return 32u;
-    return (fetch >= 1 && ctx->sweep_cols_f64_late <= 32) ? 32u : 64u;
+    if (ws.gcap < 192) return 32u;
+    return fetch >= 1 ? 32u : 64u;
 }
 
 // early form of the speculative engine (fp32): the first solo launch runs on the subset Gram matrix beside the passes over A
@@ -656,7 +656,6 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
                            EventPair pass1, EventPair pass2)
 {
     hipStream_t st = ctx->stream;
-    const int probe = ctx->early_probe;              // developer aid: 1 = no overlap (the passes first, then the solo launch)
     if (!ctx->stream2) {
         // A stream of another priority class: HIP keeps a pool of hardware queues per class, so this one never
         // shares a queue with the main stream (two streams on ONE hardware queue execute in submission order, and
@@ -693,7 +692,7 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
     // two tiles that are left of 512 are formed by the VALU chain (k_cols_gram) on a fourth stream.  Every CU but one
     // then carries exactly two tiles.
     uint32_t main_tiles = 0, se_last = 0, tail_c0 = 0, tail_cols = 0, se_quota = 2u, range_last = 0;
-    if (ctx->early_se && ctx->early_pass == 2 && !probe && ctx->stream3 && ctx->num_cus == 8 * (int)kSeCount &&
+    if (ctx->early_se && ctx->early_pass == 2 && ctx->stream3 && ctx->num_cus == 8 * (int)kSeCount &&
         ctx->n_pad % 128 == 0 && ctx->ldm % 256 == 0) {
         const uint32_t nt = (uint32_t)(ctx->n_pad / 128);
         if (nt > 14u * kSeCount && nt <= 16u * kSeCount) {
@@ -730,50 +729,46 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
     HIPCHK(launch_subset_gram_f32(ctx, ws.sub_cols, ws.subg, ws.st, ws.gcache, ws.slot_of, ws.gpitch));
     // (the counters of the dealing-out were zeroed by k_subset_pick)
     HIPCHK(hipEventRecord(ctx->ev_fork, st));
-    // second stream: the two 32-column passes, held back until the solo workgroup is resident.  (Enqueued AFTER the
-    // solo launch: should the two streams ever share a hardware queue after all, the gate then follows the launch it
-    // waits for and everything merely runs one after the other.)
-    auto enqueue_passes = [&]() {
-        HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        if (!probe) HIPCHK(launch_wait_started(ctx, ws, ctx->stream2));
-        if (main_tiles) {
-            // third stream: the tiles dealt out by shader engine.  Its workgroups must hold their CUs BEFORE the main launch
-            // of the pass arrives (a workgroup that finds its SE full holds up every workgroup behind it in its grid; the
-            // two that land on the solo workgroup's SE leave at once when they get there first): the main launch waits for
-            // their arrival count
-            HIPCHK(hipEventRecord(ctx->ev_gate, ctx->stream2));                     // (behind the gate: the solo workgroup is resident)
-            HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_gate, 0));
-            HIPCHK(launch_gemm32se_on(ctx, ctx->stream3, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, main_tiles, se_last, ws.st,
-                                      ctx->se_count, se_quota));
-            HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + kSeCount, early_se_wgs(ctx), ws.st));
-        }
-        if (pass1.a) HIPCHK(hipEventRecord(pass1.a, ctx->stream2));
-        HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, main_tiles));
-        if (pass1.b) HIPCHK(hipEventRecord(pass1.b, ctx->stream2));
-        if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, se_last, range_last));
-        // the second pass's 32 columns are chosen now, half a millisecond into the solo launch: what has entered
-        // its support without a Gram row so far, then the columns closest to entering (k_pick_pass_b)
-        HIPCHK(launch_pick_pass_b_f32(ctx, ws, ctx->stream2));
-        if (main_tiles) {
-            HIPCHK(hipEventRecord(ctx->ev_b0, ctx->stream2));                       // (the second list exists, the first pass is complete)
-            HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_b0, 0));
-            HIPCHK(launch_gemm32se_on(ctx, ctx->stream3, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, main_tiles, se_last, ws.st,
-                                      ctx->se_count + (kSeCount + 2), se_quota));
-            HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
-            HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + (kSeCount + 2) + kSeCount, early_se_wgs(ctx), ws.st));
-        }
-        if (pass2.a) HIPCHK(hipEventRecord(pass2.a, ctx->stream2));
-        HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, main_tiles));
-        if (pass2.b) HIPCHK(hipEventRecord(pass2.b, ctx->stream2));
-        if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, se_last, range_last));
-        if (main_tiles) HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_join3, 0));
-        HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
-    };
-    if (probe == 1) { enqueue_passes(); HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0)); }
     // main stream: first inverse + direction (k_gramupd, round 0: reads only the seeded entry), then the solo launch
     HIPCHK(launch_la_update<float>(ctx, ws, 0, tol));
     HIPCHK(launch_la_solo_f32(ctx, ws, tol, max_iter));
-    if (probe != 1) enqueue_passes();
+    // second stream: the two 32-column passes, held back until the solo workgroup is resident.  (Enqueued AFTER the
+    // solo launch: should the two streams ever share a hardware queue after all, the gate then follows the launch it
+    // waits for and everything merely runs one after the other.)
+    HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    HIPCHK(launch_wait_started(ctx, ws, ctx->stream2));
+    if (main_tiles) {
+        // third stream: the tiles dealt out by shader engine.  Its workgroups must hold their CUs BEFORE the main launch
+        // of the pass arrives (a workgroup that finds its SE full holds up every workgroup behind it in its grid; the
+        // two that land on the solo workgroup's SE leave at once when they get there first): the main launch waits for
+        // their arrival count
+        HIPCHK(hipEventRecord(ctx->ev_gate, ctx->stream2));                     // (behind the gate: the solo workgroup is resident)
+        HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_gate, 0));
+        HIPCHK(launch_gemm32se_on(ctx, ctx->stream3, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, main_tiles, se_last, ws.st,
+                                  ctx->se_count, se_quota));
+        HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + kSeCount, early_se_wgs(ctx), ws.st));
+    }
+    if (pass1.a) HIPCHK(hipEventRecord(pass1.a, ctx->stream2));
+    HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, main_tiles));
+    if (pass1.b) HIPCHK(hipEventRecord(pass1.b, ctx->stream2));
+    if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list, ws.sw_list + 64, ws.gcache, ws.gpitch, se_last, range_last));
+    // the second pass's 32 columns are chosen now, half a millisecond into the solo launch: what has entered
+    // its support without a Gram row so far, then the columns closest to entering (k_pick_pass_b)
+    HIPCHK(launch_pick_pass_b_f32(ctx, ws, ctx->stream2));
+    if (main_tiles) {
+        HIPCHK(hipEventRecord(ctx->ev_b0, ctx->stream2));                       // (the second list exists, the first pass is complete)
+        HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_b0, 0));
+        HIPCHK(launch_gemm32se_on(ctx, ctx->stream3, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, main_tiles, se_last, ws.st,
+                                  ctx->se_count + (kSeCount + 2), se_quota));
+        HIPCHK(hipEventRecord(ctx->ev_join3, ctx->stream3));
+        HIPCHK(launch_wait_count(ctx->stream2, ctx->se_count + (kSeCount + 2) + kSeCount, early_se_wgs(ctx), ws.st));
+    }
+    if (pass2.a) HIPCHK(hipEventRecord(pass2.a, ctx->stream2));
+    HIPCHK(launch_gemm32w_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, main_tiles));
+    if (pass2.b) HIPCHK(hipEventRecord(pass2.b, ctx->stream2));
+    if (range_last) HIPCHK(launch_gemm32range_on(ctx, ctx->stream2, ws.sw_list + 32, ws.sw_list + 96, ws.gcache, ws.gpitch, se_last, range_last));
+    if (main_tiles) HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_join3, 0));
+    HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
     if (tail_cols) {
         // the last columns of both passes by the VALU chain (32 small workgroups each, ~70 us): on a fourth stream beside the
         // passes when there is one, else on this stream behind the solo launch
@@ -1228,7 +1223,7 @@ Forms choose_forms(ss_hip_ctx* ctx, const Route& route, const T* y, void* rec_ou
     // (la_fused = 3 with the early form: contexts whose options ask for another engine get that engine).
     // (OMP — ss::omp<float> — takes it too: the resident kernel's OMP statement on the same subset, the same certificate; not with a trace)
     f.scr1 = (f.la || (f.la_omp && ctx->screen_resident && !ctx->tracing)) && sizeof(T) == 4 && !route.no_sub && ctx->la_fused >= 3 && ctx->early_solo &&
-             !ctx->early_probe && ctx->solo_subset == 256 && (!f.sub1 || screen_first16_usable(ctx)) && screen_form_usable(ctx);
+             ctx->solo_subset == 256 && (!f.sub1 || screen_first16_usable(ctx)) && screen_form_usable(ctx);
     if (f.scr1) f.sub1 = false;
     // fp64: the same certificate around the fp64 engine — the path is solved by a context of its own on the 2048 columns with
     // the largest |c0| (passes and iterations on 1.6 % of the dictionary), its logged states are screened against all columns
@@ -1573,7 +1568,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
                 ss_hip_ctx* sub = screen64_sub(ctx);
                 sub->strict_sign = ctx->strict_sign; sub->zero_on_removal = ctx->zero_on_removal; sub->tie_guard = ctx->tie_guard;
                 sub->tie_rerun = ctx->tie_rerun; sub->engine = ctx->engine; sub->lookahead = ctx->lookahead;
-                sub->sweep_f64_variant = 2;               // (128-column tiles: the sub-dictionary has 16 of them)
+                sub->pass_tile128 = 1;                   // (128-column tiles: the sub-dictionary has 16 of them)
                 const uint64_t ties0 = sub->stats.tie_reruns, gf0 = sub->stats.gram_fallbacks, pf0 = sub->stats.persist_fallbacks;
                 uint32_t it_s = 0;
                 double e_s = 0.0;
@@ -2340,12 +2335,12 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
         if (ctx->sub_off_chunks > 0) ctx->sub_off_chunks -= 1;      // (it handed back too much lately)
         else form = 3;
     }
-    // column form for the batches in between (batch_cols_min .. batch_cols_max signals, no G): in lock-step, one pass
+    // column form for the batches in between (batch_cols_min signals or more, no G): in lock-step, one pass
     // over A per round and 64 signals forms the Gram columns of the entering columns (half the flops of the two GEMMs
     // of form 0, and one pass serves 64 signals where a single solve spends three on one).  The cache holds one row
     // per slot and round; a budget (option gram_full_gib) it does not fit sends the batch the old way.
     if (form == 0 && !ctx->gram_full && ctx->engine >= 1 && ctx->batch_cols_min > 0 && B >= (size_t)std::max(2, ctx->batch_cols_min) &&
-        (ctx->batch_cols_max <= 0 || B <= (size_t)ctx->batch_cols_max) && ctx->n_pad % 256 == 0) {
+        ctx->n_pad % 256 == 0) {
         // signals per chunk: at most 448 (7 full passes per round), at most what the cache budget AND the free HBM hold
         // (the cache is (max_iter + 2) rows per signal: a large max_iter with many signals does not fit — such a batch
         // goes the old way instead of failing), whole passes
@@ -3111,74 +3106,114 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx)
     return SS_HIP_OK;
 }
 
+// ---- options: one row per key, walked by ss_hip_set_option and ss_hip_get_option (the defaults are the member
+// ---- initialisers of ss_hip_ctx; the keys are described in include/ss_hip.h) ----------------------------------------
+namespace {
+
+// how a written value is normalised before it is stored
+enum class OptNorm {
+    AsIs,        // stored as given
+    Flag,        // value ? 1 : 0
+    Clamp,       // into [lo, hi]
+    Floor,       // at least lo
+    Snap64,      // value > 32 ? 64 : 32
+    Range,       // outside [lo, hi]: SS_HIP_EINVAL, nothing stored
+    PassDebug,   // an action, not a member: write-only
+};
+
+struct OptRow {
+    const char* key;
+    int ss_hip_ctx::* i;       // the member: an int ...
+    long ss_hip_ctx::* l;      // ... or a long (neither: an action)
+    OptNorm norm;
+    long lo, hi;
+    constexpr OptRow(const char* k, int ss_hip_ctx::* m, OptNorm nm, long lo_ = 0, long hi_ = 0) : key(k), i(m), l(nullptr), norm(nm), lo(lo_), hi(hi_) {}
+    constexpr OptRow(const char* k, long ss_hip_ctx::* m, OptNorm nm, long lo_ = 0, long hi_ = 0) : key(k), i(nullptr), l(m), norm(nm), lo(lo_), hi(hi_) {}
+    constexpr OptRow(const char* k, OptNorm nm) : key(k), i(nullptr), l(nullptr), norm(nm), lo(0), hi(0) {}
+};
+
+const OptRow kOptions[] = {
+    { "sweep_variant",         &ss_hip_ctx::sweep_variant,         OptNorm::AsIs },
+    { "lookahead",             &ss_hip_ctx::lookahead,             OptNorm::AsIs },
+    { "strict_sign",           &ss_hip_ctx::strict_sign,           OptNorm::Flag },
+    { "screen_first8",         &ss_hip_ctx::screen_first8,         OptNorm::Flag },
+    { "screen_rescue",         &ss_hip_ctx::screen_rescue,         OptNorm::Flag },
+    { "trace",                 &ss_hip_ctx::tracing,               OptNorm::Flag },
+    { "zero_on_removal",       &ss_hip_ctx::zero_on_removal,       OptNorm::Flag },
+    { "tie_guard",             &ss_hip_ctx::tie_guard,             OptNorm::Flag },
+    { "profile_every",         &ss_hip_ctx::profile_every,         OptNorm::Floor, 1 },
+    { "profile_solve_every",   &ss_hip_ctx::profile_solve_every,   OptNorm::Floor, 1 },      // (+ the tick starts again)
+    { "engine",                &ss_hip_ctx::engine,                OptNorm::Clamp, 0, 3 },
+    { "tie_rerun",             &ss_hip_ctx::tie_rerun,             OptNorm::Flag },
+    { "ro_force_resweep",      &ss_hip_ctx::ro_force_resweep,      OptNorm::Flag },
+    { "ro_staged",             &ss_hip_ctx::ro_staged,             OptNorm::Flag },
+    { "batch_subset",          &ss_hip_ctx::batch_subset,          OptNorm::Flag },
+    { "ro_slots",              &ss_hip_ctx::ro_slots,              OptNorm::Range, 1, 8 },
+    { "batch_fused_scan",      &ss_hip_ctx::batch_fused_scan,      OptNorm::Flag },
+    { "sweep32_variant",       &ss_hip_ctx::sweep32_variant,       OptNorm::Clamp, 0, 9 },
+    { "first_sweep_cols",      &ss_hip_ctx::first_sweep_cols,      OptNorm::Snap64 },
+    { "early_solo",            &ss_hip_ctx::early_solo,            OptNorm::Flag },
+    { "early_pass",            &ss_hip_ctx::early_pass,            OptNorm::AsIs },
+    { "early_adapt",           &ss_hip_ctx::early_adapt,           OptNorm::Flag },
+    { "early_se",              &ss_hip_ctx::early_se,              OptNorm::Clamp, 0, 3 },
+    { "pass_dbg_ptr",          OptNorm::PassDebug },
+    { "la_fused",              &ss_hip_ctx::la_fused,              OptNorm::Clamp, 0, 3 },
+    { "solo_subset",           &ss_hip_ctx::solo_subset,           OptNorm::Clamp, 0, 256 },
+    { "solo_full_gram",        &ss_hip_ctx::solo_full_gram,        OptNorm::Flag },
+    { "cache_mib",             &ss_hip_ctx::cache_mib,             OptNorm::Floor, 16 },
+    { "batch_min",             &ss_hip_ctx::batch_min,             OptNorm::Floor, 2 },
+    { "batch_gram_min",        &ss_hip_ctx::batch_gram_min,        OptNorm::Floor, 0 },
+    { "batch_cols_min",        &ss_hip_ctx::batch_cols_min,        OptNorm::Floor, 0 },
+    { "gram_full_gib",         &ss_hip_ctx::gram_full_gib,         OptNorm::Floor, 0 },
+    { "gram_full_after",       &ss_hip_ctx::gram_full_after,       OptNorm::Floor, 0 },
+    { "gram_single",           &ss_hip_ctx::gram_single,           OptNorm::Flag },
+    { "gram_symmetric",        &ss_hip_ctx::gram_symmetric,        OptNorm::Flag },
+    { "batch_chunk",           &ss_hip_ctx::batch_chunk,           OptNorm::Floor, 4 },
+    { "irls_batch_max",        &ss_hip_ctx::irls_batch_max,        OptNorm::Clamp, 1, 65535 },
+    { "dl_chunk_max",          &ss_hip_ctx::dl_chunk_max,          OptNorm::Clamp, 0, 32768 },
+    { "screen_single",         &ss_hip_ctx::screen_single,         OptNorm::Clamp, 0, 2 },   // (+ the step-aside counters start again)
+    { "screen_first16",        &ss_hip_ctx::screen_first16,        OptNorm::Flag },
+    { "batch_screen",          &ss_hip_ctx::batch_screen,          OptNorm::Flag },
+    { "screen_resident",       &ss_hip_ctx::screen_resident,       OptNorm::Flag },
+    { "screen_recheck",        &ss_hip_ctx::screen_recheck,        OptNorm::Flag },
+    { "gram_reserve",          &ss_hip_ctx::gram_reserve,          OptNorm::Flag },
+    { "colshard_fail_prepare", &ss_hip_ctx::colshard_fail_prepare, OptNorm::Flag },
+};
+
+const OptRow* find_option(const char* key)
+{
+    for (const OptRow& r : kOptions)
+        if (!std::strcmp(key, r.key)) return &r;
+    return nullptr;
+}
+
+}  // namespace
+
 int ss_hip_set_option(ss_hip_ctx* ctx, const char* key, long value)
 {
     if (!ctx || !key) return SS_HIP_EINVAL;
-    if (!std::strcmp(key, "sweep_variant")) { ctx->sweep_variant = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "lookahead"))     { ctx->lookahead = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "temporal_cols")) { ctx->temporal_cols = std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "strict_sign"))   { ctx->strict_sign = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_first8")) { ctx->screen_first8 = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_rescue")) { ctx->screen_rescue = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "trace"))         { ctx->tracing = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "zero_on_removal")) { ctx->zero_on_removal = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "tie_guard"))     { ctx->tie_guard = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "profile_every")) { ctx->profile_every = (int)std::max<long>(1, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "profile_solve_every")) { ctx->profile_solve_every = (int)std::max<long>(1, value); ctx->prof_solve_tick = 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "engine"))        { ctx->engine = (int)std::max<long>(0, std::min<long>(3, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "tie_rerun"))     { ctx->tie_rerun = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_force_resweep")) { ctx->ro_force_resweep = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_staged"))     { ctx->ro_staged = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_subset"))  { ctx->batch_subset = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_slots"))      { if (value < 1 || value > 8) return SS_HIP_EINVAL; ctx->ro_slots = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_fused_scan")) { ctx->batch_fused_scan = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_vec4"))       { ctx->cq_vec4 = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_cols"))       { ctx->cq_cols = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_rows"))       { ctx->cq_rows = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep32_variant")) { ctx->sweep32_variant = (int)std::max<long>(0, std::min<long>(9, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "first_sweep_cols")) { ctx->first_sweep_cols = value > 32 ? 64 : 32; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_solo"))    { ctx->early_solo = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep_cols_f64")) { ctx->sweep_cols_f64 = value > 32 ? 64 : 32; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep_cols_f64_late")) { ctx->sweep_cols_f64_late = value > 32 ? 64 : 32; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_probe"))   { ctx->early_probe = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_pass"))    { ctx->early_pass = (int)value; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_adapt"))   { ctx->early_adapt = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "scan_blocks"))   { ctx->scan_blocks = (int)std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_se"))      { ctx->early_se = (int)std::max<long>(0, std::min<long>(3, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "pass_dbg_ptr"))  {   // developer aid: device buffer of 1 + 4 * 4096 u64 (0 = off), tools/probe_pass_trace.py
+    const OptRow* r = find_option(key);
+    if (!r) return SS_HIP_EINVAL;
+    switch (r->norm) {
+    case OptNorm::AsIs:   break;
+    case OptNorm::Flag:   value = value ? 1 : 0; break;
+    case OptNorm::Clamp:  value = std::max<long>(r->lo, std::min<long>(r->hi, value)); break;
+    case OptNorm::Floor:  value = std::max<long>(r->lo, value); break;
+    case OptNorm::Snap64: value = value > 32 ? 64 : 32; break;
+    case OptNorm::Range:  if (value < r->lo || value > r->hi) return SS_HIP_EINVAL; break;
+    case OptNorm::PassDebug:   // developer aid: device buffer of 1 + 4 * 4096 u64 (0 = off), tools/probe_pass_trace.py
         (void)hipSetDevice(ctx->device);
         return sship::set_pass_debug(reinterpret_cast<uint64_t*>(static_cast<uintptr_t>(value))) == hipSuccess ? SS_HIP_OK : SS_HIP_ERUNTIME;
     }
-    if (!std::strcmp(key, "sweep_f64_variant")) { ctx->sweep_f64_variant = (int)std::max<long>(0, std::min<long>(2, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "la_fused"))      { ctx->la_fused = (int)std::max<long>(0, std::min<long>(3, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "solo_subset"))   { ctx->solo_subset = (int)std::max<long>(0, std::min<long>(256, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "solo_full_gram")) { ctx->solo_full_gram = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cache_mib"))     { ctx->cache_mib = std::max<long>(16, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_min"))     { ctx->batch_min = (int)std::max<long>(2, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_gram_min")) { ctx->batch_gram_min = (int)std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_cols_min")) { ctx->batch_cols_min = (int)std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_cols_max")) { ctx->batch_cols_max = (int)std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_full_gib")) { ctx->gram_full_gib = std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_full_after")) { ctx->gram_full_after = std::max<long>(0, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_single"))   { ctx->gram_single = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_symmetric")) { ctx->gram_symmetric = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_chunk"))   { ctx->batch_chunk = (int)std::max<long>(4, value); return SS_HIP_OK; }
-    if (!std::strcmp(key, "irls_batch_max")) { ctx->irls_batch_max = (int)std::max<long>(1, std::min<long>(65535, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "dl_chunk_max")) { ctx->dl_chunk_max = (int)std::max<long>(0, std::min<long>(32768, value)); return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_single")) {
+    if (r->i) ctx->*(r->i) = (int)value;
+    else ctx->*(r->l) = value;
+    if (r->i == &ss_hip_ctx::profile_solve_every) ctx->prof_solve_tick = 0;
+    if (r->i == &ss_hip_ctx::screen_single) {
         // (setting the option also forgets what the context has learnt about its signals: the step-aside counters start again)
-        ctx->screen_single = (int)std::max<long>(0, std::min<long>(2, value));
         ctx->sub_aside.reset();
         ctx->res_aside.reset();
-        return SS_HIP_OK;
     }
-    if (!std::strcmp(key, "screen_first16")) { ctx->screen_first16 = value != 0 ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_screen"))  { ctx->batch_screen = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_resident")) { ctx->screen_resident = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_recheck")) { ctx->screen_recheck = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_reserve")) { ctx->gram_reserve = value ? 1 : 0; return SS_HIP_OK; }
-    if (!std::strcmp(key, "colshard_fail_prepare")) { ctx->colshard_fail_prepare = value ? 1 : 0; return SS_HIP_OK; }
-    return SS_HIP_EINVAL;
+    return SS_HIP_OK;
 }
 
 int ss_hip_get_trace(ss_hip_ctx* ctx, uint32_t capacity, uint32_t* idx, uint8_t* added, double* gamma,
@@ -3199,69 +3234,10 @@ int ss_hip_get_trace(ss_hip_ctx* ctx, uint32_t capacity, uint32_t* idx, uint8_t*
 int ss_hip_get_option(ss_hip_ctx* ctx, const char* key, long* value)
 {
     if (!ctx || !key || !value) return SS_HIP_EINVAL;
-    if (!std::strcmp(key, "sweep_variant")) { *value = ctx->sweep_variant; return SS_HIP_OK; }
-    if (!std::strcmp(key, "lookahead"))     { *value = ctx->lookahead; return SS_HIP_OK; }
-    if (!std::strcmp(key, "temporal_cols")) { *value = ctx->temporal_cols; return SS_HIP_OK; }
-    if (!std::strcmp(key, "strict_sign"))   { *value = ctx->strict_sign; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_first8")) { *value = ctx->screen_first8; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_rescue")) { *value = ctx->screen_rescue; return SS_HIP_OK; }
-    if (!std::strcmp(key, "trace"))         { *value = ctx->tracing; return SS_HIP_OK; }
-    if (!std::strcmp(key, "zero_on_removal")) { *value = ctx->zero_on_removal; return SS_HIP_OK; }
-    if (!std::strcmp(key, "tie_guard"))     { *value = ctx->tie_guard; return SS_HIP_OK; }
-    if (!std::strcmp(key, "profile_every")) { *value = ctx->profile_every; return SS_HIP_OK; }
-    if (!std::strcmp(key, "dbg_ndone") || !std::strcmp(key, "dbg_skip_sum")) {
-        // debugging aids: device-side counters of the last batched solve (fp32 contexts)
-        if (ctx->is_f64 || !ctx->ws) return SS_HIP_EINVAL;
-        Workspace<float>* w = static_cast<Workspace<float>*>(ctx->ws);
-        if (hipSetDevice(ctx->device) != hipSuccess) return SS_HIP_ERUNTIME;
-        if (!std::strcmp(key, "dbg_ndone")) {
-            uint32_t v = 0;
-            if (hipMemcpy(&v, w->ndone, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return SS_HIP_ERUNTIME;
-            *value = (long)v;
-        } else {
-            *value = -1;   // (the tile list is rebuilt every round; nothing meaningful to report)
-        }
-        return SS_HIP_OK;
-    }
-    if (!std::strcmp(key, "engine"))        { *value = ctx->engine; return SS_HIP_OK; }
-    if (!std::strcmp(key, "tie_rerun"))     { *value = ctx->tie_rerun; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_force_resweep")) { *value = ctx->ro_force_resweep; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_staged"))     { *value = ctx->ro_staged; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_subset"))  { *value = ctx->batch_subset; return SS_HIP_OK; }
-    if (!std::strcmp(key, "ro_slots"))      { *value = ctx->ro_slots; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_fused_scan")) { *value = ctx->batch_fused_scan; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_vec4"))       { *value = ctx->cq_vec4; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_cols"))       { *value = ctx->cq_cols; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cq_rows"))       { *value = ctx->cq_rows; return SS_HIP_OK; }
-    if (!std::strcmp(key, "la_fused"))      { *value = ctx->la_fused; return SS_HIP_OK; }
-    if (!std::strcmp(key, "solo_subset"))   { *value = ctx->solo_subset; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep32_variant")) { *value = ctx->sweep32_variant; return SS_HIP_OK; }
-    if (!std::strcmp(key, "first_sweep_cols")) { *value = ctx->first_sweep_cols; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_solo"))    { *value = ctx->early_solo; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_pass"))    { *value = ctx->early_pass; return SS_HIP_OK; }
-    if (!std::strcmp(key, "early_adapt"))   { *value = ctx->early_adapt; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep_cols_f64")) { *value = ctx->sweep_cols_f64; return SS_HIP_OK; }
-    if (!std::strcmp(key, "sweep_cols_f64_late")) { *value = ctx->sweep_cols_f64_late; return SS_HIP_OK; }
-    if (!std::strcmp(key, "cache_mib"))     { *value = ctx->cache_mib; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_min"))     { *value = ctx->batch_min; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_gram_min")) { *value = ctx->batch_gram_min; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_cols_min")) { *value = ctx->batch_cols_min; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_cols_max")) { *value = ctx->batch_cols_max; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_full_gib")) { *value = ctx->gram_full_gib; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_full_after")) { *value = ctx->gram_full_after; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_single"))   { *value = ctx->gram_single; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_symmetric")) { *value = ctx->gram_symmetric; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_chunk"))   { *value = ctx->batch_chunk; return SS_HIP_OK; }
-    if (!std::strcmp(key, "irls_batch_max")) { *value = ctx->irls_batch_max; return SS_HIP_OK; }
-    if (!std::strcmp(key, "dl_chunk_max")) { *value = ctx->dl_chunk_max; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_single")) { *value = ctx->screen_single; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_first16")) { *value = ctx->screen_first16; return SS_HIP_OK; }
-    if (!std::strcmp(key, "batch_screen"))  { *value = ctx->batch_screen; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_resident")) { *value = ctx->screen_resident; return SS_HIP_OK; }
-    if (!std::strcmp(key, "screen_recheck")) { *value = ctx->screen_recheck; return SS_HIP_OK; }
-    if (!std::strcmp(key, "gram_reserve")) { *value = ctx->gram_reserve; return SS_HIP_OK; }
-    if (!std::strcmp(key, "colshard_fail_prepare")) { *value = ctx->colshard_fail_prepare; return SS_HIP_OK; }
-    return SS_HIP_EINVAL;
+    const OptRow* r = find_option(key);
+    if (!r || (!r->i && !r->l)) return SS_HIP_EINVAL;      // (a key without a member is an action: write-only)
+    *value = r->i ? (long)(ctx->*(r->i)) : ctx->*(r->l);
+    return SS_HIP_OK;
 }
 
 int ss_hip_ctx_info(const ss_hip_ctx* ctx, size_t* m, size_t* n, int* is_f64, int* device)

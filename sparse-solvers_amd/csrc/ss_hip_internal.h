@@ -323,6 +323,7 @@ struct ss_hip_ctx {
     // narrow fp64 dictionaries (the same sub-context): the passes split their rows over pass_ksplit workgroups per column tile,
     // partial sums in pass_part ([pass_ksplit][64][n_pad] doubles), added up in order (gemm.hip: launch_gemm_split_f64)
     int pass_ksplit = 0;
+    int pass_tile128 = 0;             // (private, the same sub-context) the 32-column fp64 pass in 128-column tiles of 256 threads, three per CU (gemm.hip)
     void* pass_part = nullptr;
     size_t c0_batch_rows = 0;
     // column form of mid-size batches: cache of Gram columns, row tables, pass lists (grown on demand)
@@ -338,18 +339,11 @@ struct ss_hip_ctx {
     hipEvent_t ev_join4 = nullptr;
     hipEvent_t ev_gate = nullptr, ev_b0 = nullptr, ev_join3 = nullptr;
     uint32_t* se_count = nullptr;     // [2][kSeCount + 2] device counters, one set per pass: arrivals per SE, arrivals in all, tiles taken
-    int cq_rows = 2;                  // option: rows of G a thread of the fused batched Gram-form pass has in flight (1, 2, 3, 4, 8)
-    int cq_cols = 16;                 // option: columns per thread of that pass (4, 8, 16, 32): a workgroup reads runs of 256 * cq_cols columns of a
-                                      // row of G — 16 KiB at 16 (measured 9500 signals/s at 8192 x 65536 x 4096 against 7560 with 4: DESIGN.md §3.6)
-    int cq_vec4 = 0;                  // option (A/B): threads of the batched Gram-form pass own four consecutive columns (16-byte loads) instead of four strided ones
     int batch_fused_scan = 1;         // option: the batched Gram forms scan inside the Gram-form pass (k_la_cqs: c, q stay in registers)
-    int scan_blocks = 8;              // option: workgroups per slot of the batched Gram form's scan (0 = one per 1024 columns)
-    int sweep_f64_variant = 0;        // option: tiling of the 32-column fp64 pass (0 = 256 columns / 512 threads / 1 per CU; 1, 2 = 128 / 256 / 2, 3 per CU)
     uint64_t solo_seen = 0, solo_failed = 0;   // speculative solves / failed checks since the form was last switched off (private: not the statistics)
     int early_adapt = 1;              // option: the early form's second pass takes its columns from the solo launch's progress (0 = from |c0|)
-    int batch_cols_min = 24;          // option: smallest fp32 batch that runs in lock-step in the column form (0 = never)
-    int batch_cols_max = 0;           // largest one (0 = no limit: larger batches run in chunks of <= 448 signals); batches of
-                                      // batch_gram_min signals or more form G instead when that is allowed
+    int batch_cols_min = 24;          // option: smallest fp32 batch that runs in lock-step in the column form (0 = never); larger batches run in
+                                      // chunks of <= 448 signals; batches of batch_gram_min signals or more form G instead when that is allowed
     int bcol_chunk = 448;             // signals per chunk of the batch being dispatched (set by the dispatcher)
     unsigned char* rec_stage = nullptr;   // compact output: device staging of the records of one chunk
     size_t rec_stage_bytes = 0;
@@ -382,7 +376,6 @@ struct ss_hip_ctx {
 
     // options
     int sweep_variant = 5;   // 16 waves x 4 columns, 2-stage ring, 1 workgroup per CU: fastest on MI355X (profiles/)
-    long temporal_cols = 0;  // leading dictionary columns swept with cache-allocating loads (rest: nt)
     int lookahead = 4;
     int strict_sign = 0;
     int zero_on_removal = 0; // 0 = the reference's x + gamma*d residue on a leaving column (homotopy-cpu.cpp:252); 1 = exact 0 (opt-in)
@@ -398,9 +391,6 @@ struct ss_hip_ctx {
     long cache_mib = 2048;   // budget of the lookahead engine's Gram-column cache
     int engine = 1;          // fp32 single-signal Homotopy: 1 = lookahead (cached Gram columns) unless the tolerance is too tight for it, 2 = lookahead always, 0 = one fused sweep per iteration
     int early_solo = 1;        // option: 1 = early form of the speculative engine (iterations on the subset Gram matrix beside the passes over A)
-    int sweep_cols_f64 = 64;   // option: columns per lookahead sweep in double precision (64: the pass is MFMA-bound either way; 32)
-    int sweep_cols_f64_late = 32;     // option: ... of the third and later passes of a solve (late misses are sparse)
-    int early_probe = 0;       // developer aid (option): 1 = early form without overlap (passes first, then the solo launch)
     int first_sweep_cols = 32; // option: columns of the first lookahead sweep of a fp32 solve (64: one MFMA-bound pass instead of two HBM-bound ones; 32)
     int sweep32_variant = 0; // lookahead sweep tiling: 0 = 256 columns x 512 threads (1 per CU), 1 / 2 = 128 columns x 256 threads (2 / 3 per CU)
     int la_fused = 3;        // lookahead engine: 3 = speculative form of the resident kernel (one workgroup + verification of every breakpoint, solo.hip), 2 = resident kernel (k_la_persist), 1 = one kernel per iteration (k_la_iter), 0 = scan / update / cq kernels

@@ -102,8 +102,7 @@ template <typename T, int NRHS, int CPW, int WAVES, bool NT, int DEPTH, int BPC>
 __global__ __launch_bounds__(WAVES * 64, (BPC * WAVES) / 4)
 void k_sweep(const T* __restrict__ At, uint32_t ldm, uint32_t n, uint32_t ngroups, uint32_t mc,
              const T* __restrict__ rhs, size_t rhs_stride, T* __restrict__ out0, T* __restrict__ out1,
-             T* __restrict__ pmax_val, uint32_t* __restrict__ pmax_idx, const DevState* st,
-             uint32_t temporal_groups)
+             T* __restrict__ pmax_val, uint32_t* __restrict__ pmax_idx, const DevState* st)
 {
     using V = typename VecOf<T>::type;
     constexpr int VN = VecOf<T>::N;
@@ -153,12 +152,8 @@ void k_sweep(const T* __restrict__ At, uint32_t ldm, uint32_t n, uint32_t ngroup
 
             const uint32_t nsteps = rows / (64 * VN);
             const uint32_t lane_b = lane * 16;
-            // leading `temporal_groups` column groups are read with ordinary (cache-allocating)
-            // loads, the rest with the non-temporal hint (wave-uniform choice)
-            if (NT && g >= temporal_groups)
-                stream_columns<T, NRHS, CPW, DEPTH, true>(cb, lds_b, mc, nsteps, lane_b, acc);
-            else
-                stream_columns<T, NRHS, CPW, DEPTH, false>(cb, lds_b, mc, nsteps, lane_b, acc);
+            // NT: every column is read with the non-temporal hint; else with ordinary (cache-allocating) loads
+            stream_columns<T, NRHS, CPW, DEPTH, NT>(cb, lds_b, mc, nsteps, lane_b, acc);
         }
 
 #pragma unroll
@@ -239,8 +234,7 @@ static hipError_t launch_one(const ss_hip_ctx* ctx, const Variant& v, const T* r
     if (nblocks_out) *nblocks_out = grid;
     hipLaunchKernelGGL((k_sweep<T, NRHS, CPW, WAVES, NT, DEPTH, BPC>), dim3(grid), dim3(WAVES * 64), lds_bytes,
                        ctx->stream, static_cast<const T*>(ctx->At), ldm, (uint32_t)ctx->n, ngroups, mc,
-                       rhs, rhs_stride, out0, out1, pmax_val, pmax_idx, st,
-                       (uint32_t)(ctx->temporal_cols / (WAVES * CPW)));
+                       rhs, rhs_stride, out0, out1, pmax_val, pmax_idx, st);
     return hipGetLastError();
 }
 

@@ -94,7 +94,11 @@ def test_abi_version_and_statistics_did_not_move():
 def test_the_chunk_option_is_documented():
     assert '"dl_chunk_max"' in _header()
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "csrc", "homotopy.hip")).read()
-    assert src.count('strcmp(key, "dl_chunk_max")') == 2      # set and get
+    table = src[src.index("const OptRow kOptions[]"):src.index("int ss_hip_set_option")]
+    assert len(re.findall(r'\{ "dl_chunk_max",\s*&ss_hip_ctx::dl_chunk_max,', table)) == 1
+    for fn in ("int ss_hip_set_option", "int ss_hip_get_option"):      # set and get walk that table
+        body = src[src.index(fn):]
+        assert "find_option(key)" in body[:body.index("\n}\n")]
 
 
 def test_the_kernels_are_built_with_separately_rounded_sums():

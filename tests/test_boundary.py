@@ -117,13 +117,13 @@ def test_no_null_stream_memset_in_the_device_sources():
 
 
 def test_every_option_key_is_documented_in_the_header():
-    """ss_hip_set_option accepts a key iff include/ss_hip.h says what it does: the keys of the dispatcher in csrc/homotopy.hip
-    (strcmp(key, "...")) must all appear, quoted, in the header's option list."""
+    """ss_hip_set_option accepts a key iff include/ss_hip.h says what it does: the keys of the option table in csrc/homotopy.hip
+    (the rows of kOptions, which both entry points walk) must all appear, quoted, in the header's option list."""
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "sparse-solvers_amd", "csrc", "homotopy.hip")).read()
-    body = src[src.index("int ss_hip_set_option"):src.index("int ss_hip_get_option")]
-    keys = sorted(set(re.findall(r'strcmp\(key, "([a-z0-9_]+)"\)', body)))
+    body = src[src.index("const OptRow kOptions[]"):src.index("int ss_hip_set_option")]
+    keys = sorted(set(re.findall(r'^\s*\{ "([a-z0-9_]+)",', body, flags=re.M)))
     hdr = open(os.path.join(root, "include", "ss_hip.h")).read()
     assert len(keys) >= 40
     missing = [k for k in keys if ('"%s"' % k) not in hdr]

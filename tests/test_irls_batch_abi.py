@@ -90,5 +90,6 @@ def test_irls_batch_counters_end_the_statistics():
 def test_irls_batch_max_is_documented():
     assert '"irls_batch_max"' in _header()
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "csrc", "homotopy.hip")).read()
-    body = src[src.index("int ss_hip_set_option"):src.index("int ss_hip_get_option")]
-    assert 'strcmp(key, "irls_batch_max")' in body
+    table = src[src.index("const OptRow kOptions[]"):src.index("int ss_hip_set_option")]       # (the rows both entry points walk)
+    assert re.search(r'\{ "irls_batch_max",\s*&ss_hip_ctx::irls_batch_max,', table)
+    assert "find_option(key)" in src[src.index("int ss_hip_set_option"):src.index("int ss_hip_get_trace")]

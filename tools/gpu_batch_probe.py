@@ -43,7 +43,6 @@ for B in [int(b) for b in args.batches.split(",")]:
         if np.array_equal(np.nonzero(row)[0], sup[b]) and np.abs(row[sup[b]] - coef[b]).max() < 1e-4 * coef[b].max():
             ok += 1
     rounds = st["batch_rounds"]
-    print("   dbg: ndone", h.get_option("dbg_ndone"), "tile skip flags set", h.get_option("dbg_skip_sum"), "of", (B + 127) // 128)
     print("B=%5d: %.3f s  %.1f signals/s  rounds=%d (%.2f ms/round, GEMM flops %.1f TFLOP/s incl. tails)  iters min/mean/max %d/%.1f/%d  recovered %d/%d" % (
         B, dt, B / dt, rounds, dt / max(1, rounds) * 1e3,
         (rounds * 2 + 1) * 2.0 * ((B + 127) // 128 * 128) * n * m / dt / 1e12,

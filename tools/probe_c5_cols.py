@@ -1,4 +1,5 @@
-"""Developer probe: configs[4] (fp64, 16384 x 131072, k = 128) with 32 / 64 columns per lookahead sweep."""
+"""Developer probe: configs[4] (fp64, 16384 x 131072, k = 128) with profiling on: time per lookahead pass, passes per solve
+(the workload of tools/profile_f64_pass.sh)."""
 import sys, time, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "sparse-solvers_amd", "python"))
@@ -15,22 +16,16 @@ h = sship.Homotopy(A5)
 del A5
 torch.cuda.empty_cache()
 x = torch.zeros(n5, device="cuda:0", dtype=torch.float64)
-res = {}
-for cols, variant in ((32, 0), (32, 1), (32, 2), (64, 0)):
-    h.set_option("sweep_cols_f64", cols)
-    h.set_option("sweep_f64_variant", variant)
-    h.set_profiling(True)
-    h.solve(y, 1e-9, 512, out=x)
-    h.reset_stats()
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(3):
-        _, it, e = h.solve(y, 1e-9, 512, out=x)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t) / 3
-    st = h.stats()
-    xs = x.cpu().numpy()
-    res[(cols, variant)] = xs.copy()
-    print("sweep cols", cols, "variant", variant, "pass ms %.3f" % (st["sweep32_ms"] / max(1, st["sweep32_launches"])), "ms/solve %.2f" % (dt * 1e3), "iters", it, "sweeps/solve", st["lookahead_sweeps"] / st["solves"],
-          "support ok", np.array_equal(np.nonzero(xs)[0], sup), "coef err", np.abs(xs[sup] - coef).max() / coef.max())
-print("bitwise equal across tilings:", all(np.array_equal(res[(32, 0)], v) for v in res.values()))
+h.set_profiling(True)
+h.solve(y, 1e-9, 512, out=x)
+h.reset_stats()
+torch.cuda.synchronize()
+t = time.perf_counter()
+for _ in range(3):
+    _, it, e = h.solve(y, 1e-9, 512, out=x)
+torch.cuda.synchronize()
+dt = (time.perf_counter() - t) / 3
+st = h.stats()
+xs = x.cpu().numpy()
+print("pass ms %.3f" % (st["sweep32_ms"] / max(1, st["sweep32_launches"])), "ms/solve %.2f" % (dt * 1e3), "iters", it, "sweeps/solve", st["lookahead_sweeps"] / st["solves"],
+      "support ok", np.array_equal(np.nonzero(xs)[0], sup), "coef err", np.abs(xs[sup] - coef).max() / coef.max())

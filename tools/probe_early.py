@@ -1,5 +1,5 @@
-"""Developer probe: the early form at C2 — solve time and the event-timed pass on the second stream, with and
-without the overlap (option early_probe = 1 runs the passes first, then the solo launch)."""
+"""Developer probe: the early form at C2 — solve time and the event-timed pass on the second stream, for every
+switch of the form against the plain form (the passes first, then the solo launch)."""
 import os, sys, time
 import numpy as np
 import torch
@@ -20,11 +20,10 @@ for s in range(42):
 x = torch.zeros(N, device="cuda:0")
 with sship.Homotopy(Ad) as h:
     for name, opts in (("plain", {"early_solo": 0}),
-                       ("early e-kernel |c0|", {"early_solo": 1, "early_probe": 0, "early_pass": 0, "early_adapt": 0}),
-                       ("early LDSx3 |c0|", {"early_solo": 1, "early_probe": 0, "early_pass": 2, "early_adapt": 0, "early_se": 0}),
-                       ("early LDSx3 adaptive", {"early_solo": 1, "early_probe": 0, "early_pass": 2, "early_adapt": 1, "early_se": 0}),
-                       ("early by SE adaptive", {"early_solo": 1, "early_probe": 0, "early_pass": 2, "early_adapt": 1, "early_se": 1}),
-                       ("early, no overlap", {"early_solo": 1, "early_probe": 1, "early_pass": 2, "early_adapt": 1})):
+                       ("early e-kernel |c0|", {"early_solo": 1, "early_pass": 0, "early_adapt": 0}),
+                       ("early LDSx3 |c0|", {"early_solo": 1, "early_pass": 2, "early_adapt": 0, "early_se": 0}),
+                       ("early LDSx3 adaptive", {"early_solo": 1, "early_pass": 2, "early_adapt": 1, "early_se": 0}),
+                       ("early by SE adaptive", {"early_solo": 1, "early_pass": 2, "early_adapt": 1, "early_se": 1})):
         for k_, v_ in opts.items():
             h.set_option(k_, v_)
         for prof in (0, 1):

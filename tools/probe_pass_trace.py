@@ -1,6 +1,5 @@
 """Developer probe: where and when the workgroups of the early form's two passes run in a real configs[1] solve
-(option pass_dbg_ptr: per-workgroup start / end / XCC_ID / HW_ID), beside the speculative launch and — for comparison —
-with the passes first and the launch afterwards (early_probe = 1)."""
+(option pass_dbg_ptr: per-workgroup start / end / XCC_ID / HW_ID), beside the speculative launch."""
 import os, sys
 import numpy as np
 import torch
@@ -69,15 +68,11 @@ def report(tag):
 
 with sship.Homotopy(Ad) as h:
     del Ad
-    for probe, tag in ((0, "passes beside the speculative launch"), (1, "passes first, launch afterwards")):
-        h.set_option("early_probe", probe)
-        for _ in range(3):
-            h.solve(y, 1e-3, 256, out=x)
-        torch.cuda.synchronize()
-        buf.zero_()
-        torch.cuda.synchronize()
-        h.set_option("pass_dbg_ptr", buf.data_ptr())
+    for _ in range(3):
         h.solve(y, 1e-3, 256, out=x)
-        torch.cuda.synchronize()
-        h.set_option("pass_dbg_ptr", 0)
-        report(tag)
+    torch.cuda.synchronize()
+    h.set_option("pass_dbg_ptr", buf.data_ptr())
+    h.solve(y, 1e-3, 256, out=x)
+    torch.cuda.synchronize()
+    h.set_option("pass_dbg_ptr", 0)
+    report("passes beside the speculative launch")
