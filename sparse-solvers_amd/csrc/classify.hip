@@ -347,7 +347,7 @@ int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
                    T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
 {
     static const char* who = "class_residuals";
-    CLS_CHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     ClassifyState* cs = state_of(ctx);
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
@@ -381,11 +381,11 @@ int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
     std::vector<T> tmp;
     carve(cs->arena, chunk, [&](unsigned char* rec, T* ybuf, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig,
                                 double* dsci, uint32_t* dbest, double* part, double* party, T* Rb, uint32_t* bad) {
-        CLS_CHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
         for (size_t b0 = 0; b0 < B; b0 += chunk) {
             const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
             const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
-            if (!rec_dev) { CLS_CHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
+            if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
             const T* yd = Y + (ptrdiff_t)b0 * y_stride;
             long long ys = y_stride, yi = incy;
             if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
@@ -396,14 +396,14 @@ int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
                                (const uint32_t*)sig, part, party, (T*)nullptr);
             hipLaunchKernelGGL((k_cls_finish<T>), dim3(Bc), dim3(kClsThreads), 0, st, (const uint32_t*)seg, segcap, (const uint32_t*)sig,
                                (const double*)part, (const double*)party, ntiles, C, Rb, dbest);
-            CLS_CHK(hipGetLastError());
-            if (R) CLS_CHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), Rb, (size_t)C * sizeof(T),
-                                            (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
-            CLS_CHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
-            if (sci) CLS_CHK(hipMemcpyAsync(sci + b0, dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
+            HIPCHK(hipGetLastError());
+            if (R) HIPCHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), Rb, (size_t)C * sizeof(T),
+                                           (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
+            HIPCHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
+            if (sci) HIPCHK(hipMemcpyAsync(sci + b0, dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
         }
-        CLS_CHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CLS_CHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     });
     if (first_bad != 0xffffffffu) return bad_index(first_bad, who, err, errlen);
     return SS_HIP_OK;
@@ -431,7 +431,7 @@ template <typename T>
 int reconstruct_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, T* Yhat, ptrdiff_t yh_stride, ptrdiff_t incyh,
                      char* err, size_t errlen)
 {
-    CLS_CHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     ClassifyState* cs = state_of(ctx);
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
@@ -462,34 +462,34 @@ int reconstruct_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t km
     std::vector<T> tmp;
     carve(cs->arena, chunk, [&](unsigned char* rec, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig, double* dsci,
                                 T* yh, uint32_t* bad) {
-        CLS_CHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
         for (size_t b0 = 0; b0 < B; b0 += chunk) {
             const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
             const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
-            if (!rec_dev) { CLS_CHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
+            if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
             hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
                                (const uint32_t*)nullptr, 1u, 1u, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
             hipLaunchKernelGGL((k_cls_residual<T, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
                                (uint32_t)m, (const T*)nullptr, 0ll, 1ll, (const uint32_t*)ord_idx, (const T*)ord_val, kmax,
                                (const uint32_t*)seg, 1u, (const uint32_t*)sig, (double*)nullptr, (double*)nullptr, yh);
-            CLS_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
             T* out = Yhat + (ptrdiff_t)b0 * yh_stride;
             if (rows2d) {
-                CLS_CHK(hipMemcpy2DAsync(out, (size_t)yh_stride * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
+                HIPCHK(hipMemcpy2DAsync(out, (size_t)yh_stride * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
             } else if (out_dev) {
                 hipLaunchKernelGGL((k_cls_scatter<T>), dim3((uint32_t)std::min<size_t>((m + 255) / 256, 64), Bc), dim3(256), 0, st, (const T*)yh, ldm,
                                    (uint32_t)m, out, (long long)yh_stride, (long long)incyh);
-                CLS_CHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
             } else {
                 tmp.resize((size_t)Bc * m);
-                CLS_CHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDeviceToHost, st));
-                CLS_CHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 for (size_t b = 0; b < Bc; ++b)
                     for (size_t i = 0; i < m; ++i) out[(ptrdiff_t)b * yh_stride + (ptrdiff_t)i * incyh] = tmp[b * m + i];
             }
         }
-        CLS_CHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CLS_CHK(hipStreamSynchronize(st));
+        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     });
     if (first_bad != 0xffffffffu) return bad_index(first_bad, "reconstruct_records", err, errlen);
     return SS_HIP_OK;
@@ -535,7 +535,7 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
         return SS_HIP_EINVAL;
     }
     return guarded(err, errlen, who, [&]() -> int {
-        CLS_CHK(hipSetDevice(ctx->device));
+        HIPCHK(hipSetDevice(ctx->device));
         ClassifyState* cs = state_of(ctx);
         const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
         // Y once to the device, the records kept there
@@ -545,7 +545,7 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
             grow(cs->y_all, cs->y_all_bytes, B * m * sizeof(T), "hipMalloc(classify signals)");
             std::vector<T> tmp;
             upload_rows<T>(ctx, reinterpret_cast<T*>(cs->y_all), Y, y_stride, incy, 0, B, tmp);
-            CLS_CHK(hipStreamSynchronize(ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
             yd = reinterpret_cast<const T*>(cs->y_all); ys = (ptrdiff_t)m; yi = 1;
         }
         void* rd = records;
@@ -557,7 +557,7 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
         if (rs != SS_HIP_OK) return rs;
         const int rr = residuals_impl<T>(ctx, yd, B, ys, yi, rd, kmax, R, r_stride, best, sci, err, errlen);
         if (rr != SS_HIP_OK) return rr;
-        if (records && rd != records) CLS_CHK(hipMemcpy(records, rd, B * rb, hipMemcpyDeviceToHost));
+        if (records && rd != records) HIPCHK(hipMemcpy(records, rd, B * rb, hipMemcpyDeviceToHost));
         return SS_HIP_OK;
     });
 }
@@ -589,11 +589,11 @@ int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_cla
     if (ctx->colshard != nullptr) { set_err(err, errlen, "set_classes: not available on a column-sharded context"); return SS_HIP_EINVAL; }
     if (!labels || num_classes == 0) { set_err(err, errlen, "set_classes: labels must not be null and num_classes >= 1"); return SS_HIP_EINVAL; }
     return guarded(err, errlen, "set_classes", [&]() -> int {
-        CLS_CHK(hipSetDevice(ctx->device));
+        HIPCHK(hipSetDevice(ctx->device));
         ClassifyState* cs = state_of(ctx);
         const uint32_t n = (uint32_t)ctx->n, np = ctx->n_pad;
         uint32_t* fresh = nullptr;
-        CLS_CHK(hipMalloc(reinterpret_cast<void**>(&fresh), ((size_t)np + 1) * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&fresh), ((size_t)np + 1) * sizeof(uint32_t)));
         uint32_t bad = 0xffffffffu;
         hipError_t e = hipMemsetAsync(fresh, 0, (size_t)np * sizeof(uint32_t), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(fresh + np, 0xff, sizeof(uint32_t), ctx->stream);
@@ -610,7 +610,7 @@ int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_cla
             set_err(err, errlen, "set_classes: the label of column " + std::to_string(bad) + " is not below num_classes");
             return SS_HIP_EINVAL;
         }
-        if (cs->labels) CLS_CHK(hipFree(cs->labels));
+        if (cs->labels) HIPCHK(hipFree(cs->labels));
         cs->labels = fresh;
         cs->num_classes = num_classes;
         return SS_HIP_OK;

@@ -35,6 +35,7 @@
 // own chain, the reductions are exact max / min, the active set is replicated arithmetic).
 #include "ss_hip_internal.h"
 #include "ss_hip_device.h"
+#include "host_common.h"
 
 #include <dlfcn.h>
 
@@ -582,7 +583,7 @@ using namespace sship;
 namespace {
 
 struct CsFail { std::string msg; };
-#define CSHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw CsFail{ std::string("HIP error: ") + hipGetErrorString(e_) + " in " #expr }; } while (0)
+#define CSHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw CsFail{ hip_msg(HipFail{ e_, #expr }) }; } while (0)
 
 // one all-reduce of `count` elements at `buf` (device), in place
 void cs_allreduce(ss_hip_ctx* ctx, ColShard* cs, void* buf, size_t count, int dtype, int op)

@@ -441,7 +441,7 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
                      char* err, size_t errlen)
 {
     static const char* who = "atom_update";
-    CLS_CHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     DictLearnState* ds = state_of(ctx);
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, n = ctx->n, rb = record_bytes(kmax, sizeof(T));
@@ -452,7 +452,7 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
     std::vector<uint32_t> hc;
     if (cols) {
         hc.resize(S);
-        if (on_device(cols)) CLS_CHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (on_device(cols)) HIPCHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
         else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
         std::vector<uint32_t> sorted(hc);
         std::sort(sorted.begin(), sorted.end());
@@ -489,24 +489,24 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
     carve_index(ds->index, [&](unsigned char* rec, uint32_t* slot_of, uint32_t* dcols, uint32_t* counts, uint32_t* off, uint32_t* bad,
                                double* part, double* sig, double* obj, T* s2, double* partg, uint32_t* dusage, uint32_t* sel) {
         const unsigned char* recs = static_cast<const unsigned char*>(records);
-        if (!rec_dev) { CLS_CHK(hipMemcpyAsync(rec, recs, B * rb, hipMemcpyHostToDevice, st)); recs = rec; }
+        if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, B * rb, hipMemcpyHostToDevice, st)); recs = rec; }
         std::vector<uint32_t> slots;
         if (cols) {
             slots.assign(n, kDlNone);
             for (size_t s = 0; s < S; ++s) slots[hc[s]] = (uint32_t)s;
-            CLS_CHK(hipMemcpyAsync(slot_of, slots.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            CLS_CHK(hipMemcpyAsync(dcols, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(slot_of, slots.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(dcols, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         }
-        CLS_CHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
-        CLS_CHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        HIPCHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
+        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
         hipLaunchKernelGGL((k_dl_count<false>), dim3(Bu), dim3(256), 0, st, recs, rb, kmax, (uint32_t)n, (const uint32_t*)slot_of, counts,
                            (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, bad);
         hipLaunchKernelGGL(k_dl_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, Su, off);
-        CLS_CHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         uint32_t first_bad = kDlNone, tail[2] = { 0u, 0u };
-        CLS_CHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CLS_CHK(hipMemcpyAsync(tail, off + S, sizeof(tail), hipMemcpyDeviceToHost, st));
-        CLS_CHK(hipStreamSynchronize(st));                // (the first host read: is a record invalid; how long are the lists)
+        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(tail, off + S, sizeof(tail), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                // (the first host read: is a record invalid; how long are the lists)
         const uint32_t total = tail[0], longest = tail[1];
         if (first_bad != kDlNone) { rc = bad_index(first_bad, who, err, errlen); return; }
 
@@ -529,7 +529,7 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
         grow(ds->work, ds->work_bytes, carve_work(nullptr, [](auto...) {}), "hipMalloc(atom update workspace)");
         carve_work(ds->work, [&](uint32_t* pair_b, uint32_t* pair_e, uint32_t* sb, T* sw, T* G, T* R, T* ybuf) {
             if (total != 0u) {
-                CLS_CHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
+                HIPCHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
                 hipLaunchKernelGGL((k_dl_count<true>), dim3(Bu), dim3(256), 0, st, recs, rb, kmax, (uint32_t)n, (const uint32_t*)slot_of, counts,
                                    (const uint32_t*)off, pair_b, pair_e, bad);
                 hipLaunchKernelGGL((k_dl_sort<T>), dim3((Su + 3u) / 4u), dim3(256), 0, st, recs, rb, kmax, (const uint32_t*)off, Su,
@@ -537,7 +537,7 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
                 if (longest > kDlRankMax)
                     hipLaunchKernelGGL((k_dl_long<T>), dim3(Su), dim3(256), 0, st, recs, rb, kmax, Bu, (const uint32_t*)dcols, (const uint32_t*)off,
                                        sb, sw, s2);
-                CLS_CHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
             }
             std::vector<T> tmp;
             if (total != 0u || objective) {
@@ -552,35 +552,35 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
                         hipLaunchKernelGGL((k_dl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)dcols,
                                            (const uint32_t*)off, (const uint32_t*)sb, (const T*)sw, (const T*)s2, (const T*)R, (uint32_t)b0,
                                            (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, b0 + Bc >= B ? 1 : 0, G, partg);
-                    CLS_CHK(hipGetLastError());
+                    HIPCHK(hipGetLastError());
                 }
             }
             if (objective) {
                 hipLaunchKernelGGL(k_dl_signal_sums, dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const double*)part, per, Bu, sig);
                 hipLaunchKernelGGL(k_dl_objective, dim3(1), dim3(64), 0, st, (const double*)sig, Bu, obj);
-                CLS_CHK(hipGetLastError());
+                HIPCHK(hipGetLastError());
             }
             // ---- norms, changed / unchanged, V: straight into a device V, else in place over g ([S][ldm]) ----
             T* out = v_dev ? Vout : G;
             const long long ors = v_dev ? (long long)rs : 1ll, ocs = v_dev ? (long long)cs : (long long)ldm;
             hipLaunchKernelGGL((k_dl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)dcols, (const uint32_t*)off,
                                (const T*)G, (const double*)partg, ntiles, out, ors, ocs, dusage);
-            CLS_CHK(hipGetLastError());
-            if (objective) CLS_CHK(hipMemcpyAsync(objective, obj, sizeof(double), hipMemcpyDefault, st));
-            if (usage) CLS_CHK(hipMemcpyAsync(usage, dusage, S * sizeof(uint32_t), hipMemcpyDefault, st));
+            HIPCHK(hipGetLastError());
+            if (objective) HIPCHK(hipMemcpyAsync(objective, obj, sizeof(double), hipMemcpyDefault, st));
+            if (usage) HIPCHK(hipMemcpyAsync(usage, dusage, S * sizeof(uint32_t), hipMemcpyDefault, st));
             std::vector<uint32_t> hus;
             if (apply) {
                 hus.resize(S);
-                CLS_CHK(hipMemcpyAsync(hus.data(), dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(hus.data(), dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             }
             if (Vout && !v_dev) {
                 tmp.resize(S * m);
-                CLS_CHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), G, (size_t)ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
-                CLS_CHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), G, (size_t)ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 for (size_t s = 0; s < S; ++s)
                     for (size_t i = 0; i < m; ++i) Vout[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs] = tmp[s * m + i];
             }
-            CLS_CHK(hipStreamSynchronize(st));
+            HIPCHK(hipStreamSynchronize(st));
             if (!apply) return;
             // ---- apply: the changed atoms as a device column list + a contiguous device V, through the column replacement ----
             std::vector<uint32_t> pos, ccols;
@@ -590,11 +590,11 @@ int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, 
             const size_t nc = pos.size();
             grow(ds->vc, ds->vc_bytes, nc * m * sizeof(T), "hipMalloc(atom update: changed atoms)");
             T* Vc = reinterpret_cast<T*>(ds->vc);
-            CLS_CHK(hipMemcpyAsync(sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            CLS_CHK(hipMemcpyAsync(sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL((k_dl_gather<T>), dim3((uint32_t)nc), dim3(256), 0, st, (const T*)out, ors, ocs, (const uint32_t*)sel, (uint32_t)m, Vc);
-            CLS_CHK(hipGetLastError());
-            CLS_CHK(hipStreamSynchronize(st));
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(st));
             rc = replace_columns_device<T>(ctx, sel + S, ccols, Vc, 1ll, (long long)m, err, errlen);
         });
     });

@@ -17,6 +17,7 @@
 // No floating-point atomics: every sum is a per-thread chain and a fixed tree.
 #include "ss_hip_internal.h"
 #include "ss_hip_device.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cstring>
@@ -122,17 +123,6 @@ void k_du_scales(const float* __restrict__ amaxc, const float* __restrict__ anor
 
 namespace {
 
-struct HipFail { hipError_t code; const char* what; };
-#define DU_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw HipFail{ e_, #expr }; } while (0)
-
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }     // (unregistered host memory)
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
-}
-
 // the step-aside windows and failure counts were learned on another dictionary (the call counters stay: they count calls)
 void reset_routing(ss_hip_ctx* ctx)
 {
@@ -144,21 +134,16 @@ void reset_routing(ss_hip_ctx* ctx)
     ctx->solo_failed = 0;
 }
 
-}  // namespace
-
-// The update itself, for a validated list (distinct columns < n; hc = its host copy) and columns that are on the device already:
-// V(i, s) = V[i * rs + s * cs].  What ss_hip_homotopy_replace_columns_* runs after its validation and staging, and what the
-// atom update of dictionary learning (dictlearn.hip) applies its changed atoms with.  Returns when the update is complete.
+// the body of replace_columns_device (file-local: the lambda it hands to guarded stays out of the library's symbols)
 template <typename T>
-int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* dcols, const std::vector<uint32_t>& hc, const T* dV, long long drs, long long dcs,
-                           char* err, size_t errlen)
+int replace_device_impl(ss_hip_ctx* ctx, const uint32_t* dcols, const std::vector<uint32_t>& hc, const T* dV, long long drs, long long dcs,
+                        char* err, size_t errlen)
 {
     const size_t S = hc.size();
     if (S == 0) return SS_HIP_OK;
-    unsigned char* scratch = nullptr;
-    int rc = SS_HIP_OK;
-    try {
-        DU_CHK(hipSetDevice(ctx->device));
+    DeviceBuf scratch_buf;       // (freed after the last synchronisation, or on the way out with an error)
+    return guarded(err, errlen, "replace_columns", [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m;
         const uint32_t ldm = ctx->ldm, np = ctx->n_pad, ntiles = np / kGramTile;
         // ---- G: which 128-column tiles hold a replaced column ([0 .. ntiles) flags, then the list) ----
@@ -179,52 +164,57 @@ int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* dcols, const std::ve
         // ---- one scratch allocation: the tile table, the two flags ----
         auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t off_flag = up(tiles.size() * sizeof(uint32_t));
-        DU_CHK(hipMalloc(&scratch, off_flag + 256));
+        scratch_buf.alloc(off_flag + 256, "hipMalloc(&scratch, off_flag + 256)");
+        unsigned char* scratch = scratch_buf.get<unsigned char>();
         hipStream_t st = ctx->stream;
-        if (!tiles.empty()) DU_CHK(hipMemcpyAsync(scratch, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (!tiles.empty()) HIPCHK(hipMemcpyAsync(scratch, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         uint32_t* dmoved = reinterpret_cast<uint32_t*>(scratch + off_flag);
         // ---- the columns, their statistics, the reduced-precision columns ----
         const ScreenCopies sc = screen_copies(ctx);
         hipLaunchKernelGGL((k_du_columns<T>), dim3((uint32_t)S), dim3(256), 0, st, dV, drs, dcs, dcols, (uint32_t)m, ldm, static_cast<T*>(ctx->At),
                            static_cast<_Float16*>(sc.a16), sc.a8, sc.anorm, sc.amaxc, (const float*)sc.meta);
-        DU_CHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         if (sc.anorm != nullptr) {
             hipLaunchKernelGGL(k_du_scales, dim3(1), dim3(1024), 0, st, (const float*)sc.amaxc, (const float*)sc.anorm, np, sc.meta, sc.a8 != nullptr ? 1 : 0, dmoved);
-            DU_CHK(hipGetLastError());
+            HIPCHK(hipGetLastError());
             uint32_t moved[2] = { 0u, 0u };
-            DU_CHK(hipMemcpyAsync(moved, dmoved, sizeof(moved), hipMemcpyDeviceToHost, st));
-            DU_CHK(hipStreamSynchronize(st));                       // (the one host read: is a whole copy due again?)
-            if (moved[0] || moved[1]) DU_CHK(screen_reconvert(ctx, moved[0] != 0u, moved[1] != 0u));
+            HIPCHK(hipMemcpyAsync(moved, dmoved, sizeof(moved), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));                       // (the one host read: is a whole copy due again?)
+            if (moved[0] || moved[1]) HIPCHK(screen_reconvert(ctx, moved[0] != 0u, moved[1] != 0u));
         }
-        DU_CHK(omp_norm_refresh(ctx, dcols, (uint32_t)S));
+        HIPCHK(omp_norm_refresh(ctx, dcols, (uint32_t)S));
         // ---- G ----
         if (ctx->gram_full != nullptr) {
             if (g_full) {
-                DU_CHK(ctx->gram_symmetric ? launch_gemm_sym_f32(ctx, ctx->gram_full, ctx->gram_pitch)
+                HIPCHK(ctx->gram_symmetric ? launch_gemm_sym_f32(ctx, ctx->gram_full, ctx->gram_pitch)
                                            : launch_gemm_tn_f32(ctx, static_cast<const float*>(ctx->At), np, ldm, ctx->gram_full, ctx->gram_pitch, nullptr, false));
             } else {
-                DU_CHK(launch_gemm_sym_tiles_f32(ctx, ctx->gram_full, ctx->gram_pitch, reinterpret_cast<const uint32_t*>(scratch), ntouched));
+                HIPCHK(launch_gemm_sym_tiles_f32(ctx, ctx->gram_full, ctx->gram_pitch, reinterpret_cast<const uint32_t*>(scratch), ntouched));
             }
         }
         // ---- Gram columns cached in the workspace: a solve clears the slot map before it caches anything (k_la_reset), the column
         // form's table and the early form's subset are made per call — nothing of them outlives a call; the map is cleared all the same
         if (ctx->ws != nullptr) {
             int32_t* slot_of = ctx->is_f64 ? static_cast<Workspace<double>*>(ctx->ws)->slot_of : static_cast<Workspace<float>*>(ctx->ws)->slot_of;
-            if (slot_of != nullptr) DU_CHK(hipMemsetAsync(slot_of, 0xff, (size_t)np * sizeof(int32_t), st));
+            if (slot_of != nullptr) HIPCHK(hipMemsetAsync(slot_of, 0xff, (size_t)np * sizeof(int32_t), st));
         }
-        DU_CHK(hipStreamSynchronize(st));
+        HIPCHK(hipStreamSynchronize(st));
         reset_routing(ctx);
         if (sc.sub != nullptr) reset_routing(sc.sub);
-    } catch (const HipFail& f) {
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
-        rc = f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "replace_columns: out of host memory");
-        rc = SS_HIP_ENOMEM;
-    }
-    if (scratch) (void)hipFree(scratch);
-    return rc;
+        return SS_HIP_OK;
+    });
+}
+
+}  // namespace
+
+// The update itself, for a validated list (distinct columns < n; hc = its host copy) and columns that are on the device already:
+// V(i, s) = V[i * rs + s * cs].  What ss_hip_homotopy_replace_columns_* runs after its validation and staging, and what the
+// atom update of dictionary learning (dictlearn.hip) applies its changed atoms with.  Returns when the update is complete.
+template <typename T>
+int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* dcols, const std::vector<uint32_t>& hc, const T* dV, long long drs, long long dcs,
+                           char* err, size_t errlen)
+{
+    return replace_device_impl<T>(ctx, dcols, hc, dV, drs, dcs, err, errlen);
 }
 
 template int replace_columns_device<float>(ss_hip_ctx*, const uint32_t*, const std::vector<uint32_t>&, const float*, long long, long long, char*, size_t);
@@ -242,15 +232,14 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
     if (S == 0) return SS_HIP_OK;
     if (!cols || !V) { set_err(err, errlen, "replace_columns: null argument"); return SS_HIP_EINVAL; }
     if (S > ctx->n) { set_err(err, errlen, "replace_columns: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
-    unsigned char* scratch = nullptr;
-    int rc = SS_HIP_OK;
-    try {
-        DU_CHK(hipSetDevice(ctx->device));
+    DeviceBuf scratch_buf;
+    return guarded(err, errlen, "replace_columns", [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n;
         const bool cols_dev = on_device(cols), v_dev = on_device(V);
         // ---- validation, on a host copy of the list: nothing has been written when it fails ----
         std::vector<uint32_t> hc(S);
-        if (cols_dev) DU_CHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (cols_dev) HIPCHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
         else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
         {
             std::vector<uint32_t> sorted(hc);
@@ -266,9 +255,10 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
         const T* dV = V;
         long long drs = rs, dcs = cs;
         std::vector<T> pack;
-        if (!cols_dev || !v_dev) DU_CHK(hipMalloc(&scratch, off_v + (v_dev ? 0 : S * m * sizeof(T))));
+        if (!cols_dev || !v_dev) scratch_buf.alloc(off_v + (v_dev ? 0 : S * m * sizeof(T)), "hipMalloc(&scratch, off_v + (v_dev ? 0 : S * m * sizeof(T)))");
+        unsigned char* scratch = scratch_buf.get<unsigned char>();
         if (!cols_dev) {
-            DU_CHK(hipMemcpyAsync(scratch, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(scratch, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             dcols = reinterpret_cast<const uint32_t*>(scratch);
         }
         if (!v_dev) {
@@ -276,22 +266,13 @@ int replace_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, const T* V, pt
             pack.resize(S * m);
             for (size_t s = 0; s < S; ++s)
                 for (size_t i = 0; i < m; ++i) pack[s * m + i] = V[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs];
-            DU_CHK(hipMemcpyAsync(scratch + off_v, pack.data(), S * m * sizeof(T), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(scratch + off_v, pack.data(), S * m * sizeof(T), hipMemcpyHostToDevice, st));
             dV = reinterpret_cast<const T*>(scratch + off_v);
             drs = 1;
             dcs = (long long)m;
         }
-        rc = replace_columns_device<T>(ctx, dcols, hc, dV, drs, dcs, err, errlen);
-    } catch (const HipFail& f) {
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
-        rc = f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "replace_columns: out of host memory");
-        rc = SS_HIP_ENOMEM;
-    }
-    if (scratch) (void)hipFree(scratch);
-    return rc;
+        return replace_columns_device<T>(ctx, dcols, hc, dV, drs, dcs, err, errlen);
+    });
 }
 
 }  // namespace

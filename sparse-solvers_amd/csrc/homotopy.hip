@@ -13,6 +13,7 @@
 // no-op), the host only polls a copy of that flag `lookahead` rounds behind the queue
 // head, so the GPU never waits for the host between iterations.
 #include "ss_hip_internal.h"
+#include "host_common.h"
 #include "resident.h"
 
 #include <algorithm>
@@ -41,53 +42,13 @@ void set_err(char* err, size_t errlen, const std::string& msg)
 
 namespace {
 
-struct HipFail {
-    hipError_t code;
-    const char* what;
-};
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) throw HipFail{ e_, #expr };                                     \
-    } while (0)
-
-std::string hip_msg(const HipFail& f)
-{
-    return std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what;
-}
-
-// Runs `body` (which returns a status) and turns what it throws into the C-ABI's codes: a failed HIP call (HIPCHK) into
-// SS_HIP_ERUNTIME with the call's text, std::bad_alloc into SS_HIP_ENOMEM with "<prefix>: out of host memory".
+// The entry points of this file report every failed HIP call as SS_HIP_ERUNTIME, a failed allocation included ("The host
+// boundary"): guarded() with that mapping.
 template <typename F>
-int guarded(char* err, size_t errlen, const char* prefix, F&& body)
-{
-    try {
-        return body();
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        return SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, std::string(prefix) + ": out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-}
+int guarded_rt(char* err, size_t errlen, const char* prefix, F&& body) { return guarded(err, errlen, prefix, body, SS_HIP_ERUNTIME); }
 
 template <typename T>
 Workspace<T>* ws_of(ss_hip_ctx* ctx) { return static_cast<Workspace<T>*>(ctx->ws); }
-
-bool is_device_pointer(const void* p)
-{
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof(attr));
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // unregistered host memory: clear the sticky error
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged ||
-           attr.type == hipMemoryTypeUnified;
-}
 
 // ---- re-layout: At[j][i] = src[i*rs + j*cs] for rows [r0, r0+R) --------------------
 template <typename T>
@@ -118,9 +79,7 @@ void upload_matrix(ss_hip_ctx* ctx, const T* A, ptrdiff_t rs, ptrdiff_t cs)
     const size_t m = ctx->m, n = ctx->n, s = sizeof(T);
     T* At = static_cast<T*>(ctx->At);
     const uint32_t ldm = ctx->ldm;
-    const bool on_device = is_device_pointer(A);
-
-    if (on_device) {
+    if (on_device(A)) {
         // one generic strided transpose straight from the caller's device buffer
         const dim3 grid((unsigned)((n + 31) / 32), (unsigned)std::min<size_t>((m + 31) / 32, 32768));
         hipLaunchKernelGGL((k_relayout<T>), grid, dim3(1024), 0, ctx->stream, A, (long long)rs,
@@ -141,36 +100,30 @@ void upload_matrix(ss_hip_ctx* ctx, const T* A, ptrdiff_t rs, ptrdiff_t cs)
     // row panels through a staging buffer, transposed on the device
     const size_t panel_bytes = (size_t)256 << 20;
     size_t R = std::max<size_t>(1, std::min(m, panel_bytes / std::max<size_t>(1, n * s)));
-    T* stage = nullptr;
-    HIPCHK(hipMalloc(&stage, R * n * s));
+    DeviceBuf stage_buf;
+    stage_buf.alloc(R * n * s, "hipMalloc(&stage, R * n * s)");
+    T* stage = stage_buf.get<T>();
     std::vector<T> gather;
     const bool rowmajor = (cs == 1 || n == 1) && (rs >= (ptrdiff_t)n || m == 1) && rs > 0;
-    try {
-        for (size_t r0 = 0; r0 < m; r0 += R) {
-            const size_t rows = std::min(R, m - r0);
-            if (rowmajor) {
-                const size_t spitch = (m == 1) ? n * s : (size_t)rs * s;
-                HIPCHK(hipMemcpy2D(stage, n * s, A + (ptrdiff_t)r0 * rs, spitch, n * s, rows,
-                                   hipMemcpyHostToDevice));
-            } else {
-                // arbitrary (e.g. negative or doubly strided) host view: gather on the host
-                gather.resize(rows * n);
-                for (size_t i = 0; i < rows; ++i)
-                    for (size_t j = 0; j < n; ++j)
-                        gather[i * n + j] = A[(ptrdiff_t)(r0 + i) * rs + (ptrdiff_t)j * cs];
-                HIPCHK(hipMemcpy(stage, gather.data(), rows * n * s, hipMemcpyHostToDevice));
-            }
-            const dim3 grid((unsigned)((n + 31) / 32), (unsigned)std::min<size_t>((rows + 31) / 32, 32768));
-            hipLaunchKernelGGL((k_relayout<T>), grid, dim3(1024), 0, ctx->stream, stage, (long long)n,
-                               1LL, (uint32_t)rows, (uint32_t)n, (uint32_t)r0, At, ldm);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (size_t r0 = 0; r0 < m; r0 += R) {
+        const size_t rows = std::min(R, m - r0);
+        if (rowmajor) {
+            const size_t spitch = (m == 1) ? n * s : (size_t)rs * s;
+            HIPCHK(hipMemcpy2D(stage, n * s, A + (ptrdiff_t)r0 * rs, spitch, n * s, rows, hipMemcpyHostToDevice));
+        } else {
+            // arbitrary (e.g. negative or doubly strided) host view: gather on the host
+            gather.resize(rows * n);
+            for (size_t i = 0; i < rows; ++i)
+                for (size_t j = 0; j < n; ++j)
+                    gather[i * n + j] = A[(ptrdiff_t)(r0 + i) * rs + (ptrdiff_t)j * cs];
+            HIPCHK(hipMemcpy(stage, gather.data(), rows * n * s, hipMemcpyHostToDevice));
         }
-    } catch (...) {
-        (void)hipFree(stage);
-        throw;
+        const dim3 grid((unsigned)((n + 31) / 32), (unsigned)std::min<size_t>((rows + 31) / 32, 32768));
+        hipLaunchKernelGGL((k_relayout<T>), grid, dim3(1024), 0, ctx->stream, stage, (long long)n,
+                           1LL, (uint32_t)rows, (uint32_t)n, (uint32_t)r0, At, ldm);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(ctx->stream));
     }
-    HIPCHK(hipFree(stage));
 }
 
 // ---- compact output: one fixed-size record per signal, packed from the solver's own lists ----------
@@ -179,7 +132,6 @@ void upload_matrix(ss_hip_ctx* ctx, const T* A, ptrdiff_t rs, ptrdiff_t cs)
 // ever in the support: reference mode, where a leaving column may keep a rounding residue) or on its
 // support list (zero_on_removal = 1: leaving columns carry exact zeros) — both sorted by column, so a
 // stable compaction of the entries with x != 0 gives the record without scanning the n coefficients.
-inline size_t record_bytes(uint32_t kmax, size_t elem) { return (16 + (size_t)kmax * (4 + elem) + 7) & ~(size_t)7; }
 
 template <typename T>
 __global__ __launch_bounds__(256)
@@ -1207,7 +1159,7 @@ Forms choose_forms(ss_hip_ctx* ctx, const Route& route, const T* y, void* rec_ou
     Forms f;
     const bool omp = route.omp;
     f.y_direct = !omp && !route.force_ro && ctx->engine != 3 && Lookahead<T>::supported && ctx->engine >= 1 && !route.force_residual &&
-                 is_device_pointer(y);
+                 on_device(y);
     f.ro = !omp && (route.force_ro || ctx->engine == 3);
     f.la = !omp && Lookahead<T>::supported && ctx->engine >= 1 && !route.force_residual && !f.ro;
     f.la_omp = omp && Lookahead<T>::supported && ctx->engine >= 1 && !route.force_residual && ctx->la_fused >= 1;
@@ -1435,7 +1387,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
 {
     const bool omp = route.omp, no_solo = route.no_solo;
     auto retry = [&](const Route& r) { *next = r; *again = true; return SS_HIP_OK; };
-    return guarded(err, errlen, "solve", [&]() -> int {
+    return guarded_rt(err, errlen, "solve", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(
@@ -1481,7 +1433,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         PumpState ps;
         // end of a solve: the device state to pinned memory, x (and the compact record) to the caller
         bool spec_epilogue = false;
-        const bool x_on_device = x != nullptr && is_device_pointer(x);
+        const bool x_on_device = x != nullptr && on_device(x);
         auto enqueue_epilogue = [&]() {
             if (ctx->hs_mapped != nullptr) {
                 // one launch: state -> pinned memory, x -> the caller's device buffer (a host x still takes a copy command)
@@ -1970,7 +1922,7 @@ int solve_batch_ro(ss_hip_ctx* ctx, const BatchCall<T>& c, const size_t* sig, si
 {
     const T tol = c.tol;
     const uint32_t max_iter = c.max_iter;
-    return guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
+    return guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
@@ -2046,7 +1998,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
     const size_t B = c.B;
     const T tol = c.tol;
     const uint32_t max_iter = c.max_iter;
-    return guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
+    return guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
@@ -2320,13 +2272,12 @@ int solve_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
     const bool gram_pays = B >= gram_min || (scr_batches && ctx->batch_signals_seen + B >= 3072 && B >= (size_t)ctx->batch_gram_min);
     ctx->batch_signals_seen += B;
     if (lockstep && ctx->engine >= 1 && ctx->batch_gram_min > 0 && (ctx->gram_full || gram_pays)) {
-        try {
+        const int rc = guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
             HIPCHK(hipSetDevice(ctx->device));
             if (ensure_full_gram(ctx)) form = 1;
-        } catch (const HipFail& f) {
-            set_err(c.err, c.errlen, hip_msg(f));
-            return SS_HIP_ERUNTIME;
-        }
+            return SS_HIP_OK;
+        });
+        if (rc != SS_HIP_OK) return rc;
     }
     // screened form for the batches in between (4 .. batch_gram_min - 1 signals, no G; option batch_screen): c0 of a chunk by the
     // batch GEMM, every signal solved by one workgroup on its subset's own Gram matrix, one screening launch per chunk of 64
@@ -2367,7 +2318,7 @@ int solve_batch_res64(ss_hip_ctx* ctx, const BatchCall<double>& c, bool omp = fa
     const size_t B = c.B, rb = record_bytes(c.kmax, sizeof(double));
     const uint32_t cap = screen64_batch_cap();
     std::vector<size_t> redo;
-    const int rc = guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
+    const int rc = guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t m = ctx->m, n = ctx->n;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)c.max_iter + 1), kKcapLimit);
@@ -2467,7 +2418,7 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, bool gram)
     const T tol = c.tol;
     const uint32_t max_iter = c.max_iter;
     std::vector<size_t> redo;
-    const int rc = guarded(c.err, c.errlen, "solve_batch", [&]() -> int {
+    const int rc = guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t n = ctx->n, ldm = ctx->ldm, np = ctx->n_pad;
         const uint32_t kcap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(n, (uint64_t)max_iter + 1), kKcapLimit);
@@ -2533,19 +2484,20 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, bool gram)
 int omp_batch_dispatch(ss_hip_ctx* ctx, const BatchCall<float>& c)
 {
     if (c.B >= 4 && !ctx->tracing && ctx->engine >= 1 && ctx->engine != 3 && ctx->screen_resident) {
-        try {
+        int form = 0;       // 1: (a) the Gram form, 2: (b) the screened form
+        const int rc = guarded_rt(c.err, c.errlen, "solve_batch", [&]() -> int {
             HIPCHK(hipSetDevice(ctx->device));
             if (ctx->batch_gram_min > 0 && res_solve_usable<float>()) {
                 const bool scr_batches = !ctx->gram_full && ctx->batch_screen && screen_form_usable(ctx);
                 const size_t gram_min = scr_batches ? std::max<size_t>((size_t)ctx->batch_gram_min, 1536) : (size_t)ctx->batch_gram_min;
-                if ((ctx->gram_full || c.B >= gram_min) && ensure_full_gram(ctx) && omp_gram_usable(ctx)) return solve_omp_batch_f32(ctx, c, true);
+                if ((ctx->gram_full || c.B >= gram_min) && ensure_full_gram(ctx) && omp_gram_usable(ctx)) { form = 1; return SS_HIP_OK; }
             }
             if (ctx->batch_screen && ctx->la_fused >= 3 && ctx->early_solo && ctx->solo_subset == 256 && res_solve_usable<float>() && screen_form_usable(ctx))
-                return solve_omp_batch_f32(ctx, c, false);
-        } catch (const HipFail& f) {
-            set_err(c.err, c.errlen, hip_msg(f));
-            return SS_HIP_ERUNTIME;
-        }
+                form = 2;
+            return SS_HIP_OK;
+        });
+        if (rc != SS_HIP_OK) return rc;
+        if (form != 0) return solve_omp_batch_f32(ctx, c, form == 1);
     }
     return solve_omp_seq<float>(ctx, c, nullptr, c.B);
 }
@@ -2571,6 +2523,21 @@ int omp_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
     return omp_batch_dispatch(ctx, c);
 }
 
+// The timed loop of the measurement hooks, on the context's stream: ev_solve0, `repeats` launches, ev_solve1, the entry point's
+// copy-out, ONE synchronisation; *ms_out = the time of one launch.  (`launch` and `copy_out` check their own HIP calls.)
+template <typename Launch, typename CopyOut>
+void timed_repeats(ss_hip_ctx* ctx, int repeats, float* ms_out, Launch&& launch, CopyOut&& copy_out)
+{
+    HIPCHK(hipEventRecord(ctx->ev_solve0, ctx->stream));
+    for (int i = 0; i < repeats; ++i) launch();
+    HIPCHK(hipEventRecord(ctx->ev_solve1, ctx->stream));
+    copy_out();
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
+    if (ms_out) *ms_out = ms / (float)repeats;
+}
+
 template <typename T>
 int gemv_t_impl(ss_hip_ctx* ctx, const T* r, T* c, int repeats, float* ms_out, char* err, size_t errlen)
 {
@@ -2578,7 +2545,7 @@ int gemv_t_impl(ss_hip_ctx* ctx, const T* r, T* c, int repeats, float* ms_out, c
     if (!ctx || !r || !c) { set_err(err, errlen, "gemv_t: null argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "gemv_t: type mismatch"); return SS_HIP_ETYPE; }
     if (repeats < 1) repeats = 1;
-    return guarded(err, errlen, "gemv_t", [&]() -> int {
+    return guarded_rt(err, errlen, "gemv_t", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         Workspace<T>& ws = *ws_of<T>(ctx);
         hipStream_t st = ctx->stream;
@@ -2586,18 +2553,11 @@ int gemv_t_impl(ss_hip_ctx* ctx, const T* r, T* c, int repeats, float* ms_out, c
         if (ctx->ldm > ctx->m)
             HIPCHK(hipMemsetAsync(ws.rhs + ctx->m, 0, (ctx->ldm - ctx->m) * sizeof(T), st));
         uint32_t nb = 0;
-        HIPCHK(hipEventRecord(ctx->ev_solve0, st));
-        for (int i = 0; i < repeats; ++i) {
+        timed_repeats(ctx, repeats, ms_out, [&] {
             // (option engine = 3: the reference-order sweep, reforder.hip)
             if (ctx->engine == 3) HIPCHK(launch_ro_sweep<T>(ctx, ws.rhs, 0, ws.c, 0, ws.dims.n_pad, 1, 1u, ws.pmax_val, ws.pmax_idx, ws.dims.pmax_stride, &nb, nullptr, false));
             else HIPCHK(launch_sweep<T>(ctx, ws.rhs, 0, 1, ws.c, nullptr, ws.pmax_val, ws.pmax_idx, &nb, nullptr));
-        }
-        HIPCHK(hipEventRecord(ctx->ev_solve1, st));
-        copy_out<T>(ctx, c, 1, ws.c, ctx->n);
-        HIPCHK(hipStreamSynchronize(st));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
-        if (ms_out) *ms_out = ms / (float)repeats;
+        }, [&] { copy_out<T>(ctx, c, 1, ws.c, ctx->n); });
         return SS_HIP_OK;
     });
 }
@@ -2610,35 +2570,23 @@ int gemm_t_impl(ss_hip_ctx* ctx, const float* R, size_t B, ptrdiff_t ldR, float*
     if (!ctx || !R || !C || B == 0) { set_err(err, errlen, "gemm_t: null/empty argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64) { set_err(err, errlen, "gemm_t: fp32 contexts only"); return SS_HIP_ETYPE; }
     if (repeats < 1) repeats = 1;
-    float* Rd = nullptr;
-    float* Dd = nullptr;
-    int rc = SS_HIP_OK;
-    try {
+    DeviceBuf Dd_buf, Rd_buf;      // (scratch of the call: freed after its synchronisation, Rd first)
+    return guarded_rt(err, errlen, "gemm_t", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         const size_t Bp = (B + 127) / 128 * 128;
         const size_t ldm = ctx->ldm, np = ctx->n_pad;
-        HIPCHK(hipMalloc(&Rd, Bp * ldm * sizeof(float)));
-        HIPCHK(hipMalloc(&Dd, Bp * np * sizeof(float)));
+        Rd_buf.alloc(Bp * ldm * sizeof(float), "hipMalloc(&Rd, Bp * ldm * sizeof(float))");
+        Dd_buf.alloc(Bp * np * sizeof(float), "hipMalloc(&Dd, Bp * np * sizeof(float))");
+        float *Rd = Rd_buf.get<float>(), *Dd = Dd_buf.get<float>();
         HIPCHK(hipMemsetAsync(Rd, 0, Bp * ldm * sizeof(float), ctx->stream));
         HIPCHK(hipMemcpy2DAsync(Rd, ldm * sizeof(float), R, (size_t)ldR * sizeof(float),
                                 ctx->m * sizeof(float), B, hipMemcpyDefault, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev_solve0, ctx->stream));
-        for (int i = 0; i < repeats; ++i)
-            HIPCHK(launch_gemm_tn_f32(ctx, Rd, (uint32_t)Bp, (uint32_t)ldm, Dd, (uint32_t)np, nullptr));
-        HIPCHK(hipEventRecord(ctx->ev_solve1, ctx->stream));
-        HIPCHK(hipMemcpy2DAsync(C, (size_t)ldC * sizeof(float), Dd, np * sizeof(float),
-                                ctx->n * sizeof(float), B, hipMemcpyDefault, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
-        if (ms_out) *ms_out = ms / (float)repeats;
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        rc = SS_HIP_ERUNTIME;
-    }
-    if (Rd) (void)hipFree(Rd);
-    if (Dd) (void)hipFree(Dd);
-    return rc;
+        timed_repeats(ctx, repeats, ms_out, [&] { HIPCHK(launch_gemm_tn_f32(ctx, Rd, (uint32_t)Bp, (uint32_t)ldm, Dd, (uint32_t)np, nullptr)); }, [&] {
+            HIPCHK(hipMemcpy2DAsync(C, (size_t)ldC * sizeof(float), Dd, np * sizeof(float),
+                                    ctx->n * sizeof(float), B, hipMemcpyDefault, ctx->stream));
+        });
+        return SS_HIP_OK;
+    });
 }
 
 // G[s][:] = A^T a_{cols[s]} for up to 32 columns in one HBM-bound pass (lookahead sweep kernel)
@@ -2652,10 +2600,8 @@ int gram_cols_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, T* G, ptrdif
     for (size_t s = 0; s < S; ++s)
         if (cols[s] >= ctx->n) { set_err(err, errlen, "gram_cols: column index out of range"); return SS_HIP_EINVAL; }
     if (repeats < 1) repeats = 1;
-    uint32_t* dlist = nullptr;
-    T* Dd = nullptr;
-    int rc = SS_HIP_OK;
-    try {
+    DeviceBuf Dd_buf, dlist_buf;
+    return guarded_rt(err, errlen, "gram_cols", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         uint32_t h[64];
         for (int s = 0; s < 32; ++s) {
@@ -2663,26 +2609,17 @@ int gram_cols_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, T* G, ptrdif
             h[32 + s] = (size_t)s < S ? (uint32_t)s : 0xffffffffu;
         }
         const size_t np = ctx->n_pad;
-        HIPCHK(hipMalloc(&dlist, sizeof(h)));
-        HIPCHK(hipMalloc(&Dd, 32 * np * sizeof(T)));
+        dlist_buf.alloc(sizeof(h), "hipMalloc(&dlist, sizeof(h))");
+        Dd_buf.alloc(32 * np * sizeof(T), "hipMalloc(&Dd, 32 * np * sizeof(T))");
+        uint32_t* dlist = dlist_buf.get<uint32_t>();
+        T* Dd = Dd_buf.get<T>();
         HIPCHK(hipMemcpyAsync(dlist, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev_solve0, ctx->stream));
-        for (int i = 0; i < repeats; ++i)
-            HIPCHK(launch_gemm32(ctx, dlist, dlist + 32, Dd, (uint32_t)np, nullptr));
-        HIPCHK(hipEventRecord(ctx->ev_solve1, ctx->stream));
-        HIPCHK(hipMemcpy2DAsync(G, (size_t)ldG * sizeof(T), Dd, np * sizeof(T), ctx->n * sizeof(T), S,
-                                hipMemcpyDefault, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
-        if (ms_out) *ms_out = ms / (float)repeats;
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        rc = SS_HIP_ERUNTIME;
-    }
-    if (dlist) (void)hipFree(dlist);
-    if (Dd) (void)hipFree(Dd);
-    return rc;
+        timed_repeats(ctx, repeats, ms_out, [&] { HIPCHK(launch_gemm32(ctx, dlist, dlist + 32, Dd, (uint32_t)np, nullptr)); }, [&] {
+            HIPCHK(hipMemcpy2DAsync(G, (size_t)ldG * sizeof(T), Dd, np * sizeof(T), ctx->n * sizeof(T), S,
+                                    hipMemcpyDefault, ctx->stream));
+        });
+        return SS_HIP_OK;
+    });
 }
 
 int subset_gram_impl(ss_hip_ctx* ctx, const uint32_t* cols, float* Gs, int repeats, float* ms_out, char* err, size_t errlen)
@@ -2691,30 +2628,18 @@ int subset_gram_impl(ss_hip_ctx* ctx, const uint32_t* cols, float* Gs, int repea
     if (!ctx || !cols || !Gs) { set_err(err, errlen, "subset_gram: null argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64) { set_err(err, errlen, "subset_gram: fp32 contexts only"); return SS_HIP_ETYPE; }
     if (repeats < 1) repeats = 1;
-    uint32_t* dcols = nullptr;
-    float* dG = nullptr;
-    int rc = SS_HIP_OK;
-    try {
+    DeviceBuf dG_buf, dcols_buf;
+    return guarded_rt(err, errlen, "subset_gram", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
-        HIPCHK(hipMalloc(&dcols, kSoloWidth * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&dG, (size_t)kSoloWidth * kSoloWidth * sizeof(float)));
+        dcols_buf.alloc(kSoloWidth * sizeof(uint32_t), "hipMalloc(&dcols, kSoloWidth * sizeof(uint32_t))");
+        dG_buf.alloc((size_t)kSoloWidth * kSoloWidth * sizeof(float), "hipMalloc(&dG, (size_t)kSoloWidth * kSoloWidth * sizeof(float))");
+        uint32_t* dcols = dcols_buf.get<uint32_t>();
+        float* dG = dG_buf.get<float>();
         HIPCHK(hipMemcpyAsync(dcols, cols, kSoloWidth * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipEventRecord(ctx->ev_solve0, ctx->stream));
-        for (int i = 0; i < repeats; ++i)
-            HIPCHK(launch_subset_gram_f32(ctx, dcols, dG, nullptr, nullptr, nullptr, 0));
-        HIPCHK(hipEventRecord(ctx->ev_solve1, ctx->stream));
-        HIPCHK(hipMemcpyAsync(Gs, dG, (size_t)kSoloWidth * kSoloWidth * sizeof(float), hipMemcpyDefault, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, ctx->ev_solve0, ctx->ev_solve1));
-        if (ms_out) *ms_out = ms / (float)repeats;
-    } catch (const HipFail& f) {
-        set_err(err, errlen, hip_msg(f));
-        rc = SS_HIP_ERUNTIME;
-    }
-    if (dcols) (void)hipFree(dcols);
-    if (dG) (void)hipFree(dG);
-    return rc;
+        timed_repeats(ctx, repeats, ms_out, [&] { HIPCHK(launch_subset_gram_f32(ctx, dcols, dG, nullptr, nullptr, nullptr, 0)); },
+                      [&] { HIPCHK(hipMemcpyAsync(Gs, dG, (size_t)kSoloWidth * kSoloWidth * sizeof(float), hipMemcpyDefault, ctx->stream)); });
+        return SS_HIP_OK;
+    });
 }
 
 template <typename T>
@@ -2723,7 +2648,7 @@ int reconstruct_impl(ss_hip_ctx* ctx, const T* x, T* y, char* err, size_t errlen
     if (ctx && ctx->kind != 0) { set_err(err, errlen, "this entry point needs a Homotopy context (an IRLS context holds the factorised matrix)"); return SS_HIP_EINVAL; }
     if (!ctx || !x || !y) { set_err(err, errlen, "reconstruct: null argument"); return SS_HIP_EINVAL; }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "reconstruct: type mismatch"); return SS_HIP_ETYPE; }
-    return guarded(err, errlen, "reconstruct", [&]() -> int {
+    return guarded_rt(err, errlen, "reconstruct", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         Workspace<T>& ws = *ws_of<T>(ctx);
         copy_in<T>(ctx, ws.q, x, 1, ctx->n);
@@ -2749,7 +2674,7 @@ int irls_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t
     }
     if (!y || !x) { set_err(err, errlen, "irls_solve: y and x must not be null"); return SS_HIP_EINVAL; }
     if (const int rc = check_solve_args<T>("irls_solve", max_iter, tol, false, incy, incx, err, errlen)) return rc;
-    return guarded(err, errlen, "irls_solve", [&]() -> int {
+    return guarded_rt(err, errlen, "irls_solve", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         copy_in<T>(ctx, irls_y_buffer<T>(ctx), y, incy, ctx->m);
         IrlsResult res{};
@@ -2781,7 +2706,7 @@ int irls_batch_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, p
     if (!Y || !X) { set_err(err, errlen, "irls_solve_batch: Y and X must not be null"); return SS_HIP_EINVAL; }
     if (const int rc = check_solve_args<T>("irls_solve_batch", max_iter, tol, false, incy, incx, err, errlen)) return rc;
     if (B == 0) return SS_HIP_OK;
-    return guarded(err, errlen, "irls_solve_batch", [&]() -> int {
+    return guarded_rt(err, errlen, "irls_solve_batch", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         uint32_t chunk = 0;
         HIPCHK(irls_batch_reserve<T>(ctx, B, &chunk));

@@ -1,12 +1,11 @@
-// What the translation units that read compact records share (classify.hip, dictlearn.hip): the record's layout, the 1024-row
-// register tile of the streaming kernels and its fixed reduction order, and the host helpers around a chunked workspace.
+// What the translation units that read compact records share (classify.hip, dictlearn.hip): the 1024-row register tile of the
+// streaming kernels and its fixed reduction order, the entry points' common checks, and the host helpers around a chunked workspace
+// (grow, Carver, upload_rows).  Errors, pointers and the record's size come from host_common.h.
 // Everything sits in an unnamed namespace: each unit gets its own copy, nothing here is part of the library's link surface.
 #pragma once
 
-#include "ss_hip_internal.h"
+#include "host_common.h"
 
-#include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -18,47 +17,16 @@ constexpr uint32_t kClsThreads = 256;
 constexpr uint32_t kClsTileRows = 1024;                  // rows of y a workgroup holds: four per thread
 constexpr uint32_t kClsInFlight = 8;                     // columns whose loads a thread has in flight
 
-struct HipFail { hipError_t code; const char* what; };
-#define CLS_CHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw HipFail{ e_, #expr }; } while (0)
-
-template <typename F>
-int guarded(char* err, size_t errlen, const char* prefix, F&& body)
-{
-    try {
-        return body();
-    } catch (const HipFail& f) {
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
-        return f.code == hipErrorOutOfMemory ? SS_HIP_ENOMEM : SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, std::string(prefix) + ": out of host memory");
-        return SS_HIP_ENOMEM;
-    }
-}
-
-inline bool on_device(const void* p)
-{
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();       // unregistered host memory
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
-}
-
 inline void grow(unsigned char*& p, size_t& have, size_t need, const char* what)
 {
     if (have >= need) return;
-    if (p) CLS_CHK(hipFree(p));
+    if (p) HIPCHK(hipFree(p));
     p = nullptr;
     have = 0;
     const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need);
     if (e != hipSuccess) { p = nullptr; throw HipFail{ e, what }; }
     have = need;
 }
-
-inline size_t record_bytes(uint32_t kmax, size_t elem) { return (16 + (size_t)kmax * (4 + elem) + 7) & ~(size_t)7; }
 
 // carves 256-byte aligned pieces out of the arena; with base == nullptr it only adds up
 struct Carver {
@@ -123,15 +91,15 @@ void upload_rows(ss_hip_ctx* ctx, T* dst, const T* src, ptrdiff_t stride, ptrdif
 {
     const size_t m = ctx->m;
     if (inc == 1 && stride >= (ptrdiff_t)m) {
-        CLS_CHK(hipMemcpy2DAsync(dst, m * sizeof(T), src + (ptrdiff_t)b0 * stride, (size_t)stride * sizeof(T), m * sizeof(T), Bc,
-                                 hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpy2DAsync(dst, m * sizeof(T), src + (ptrdiff_t)b0 * stride, (size_t)stride * sizeof(T), m * sizeof(T), Bc,
+                                hipMemcpyHostToDevice, ctx->stream));
         return;
     }
     tmp.resize(Bc * m);
     for (size_t b = 0; b < Bc; ++b)
         for (size_t i = 0; i < m; ++i) tmp[b * m + i] = src[(ptrdiff_t)(b0 + b) * stride + (ptrdiff_t)i * inc];
-    CLS_CHK(hipMemcpyAsync(dst, tmp.data(), Bc * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    CLS_CHK(hipStreamSynchronize(ctx->stream));        // (tmp is filled again for the next chunk)
+    HIPCHK(hipMemcpyAsync(dst, tmp.data(), Bc * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));        // (tmp is filled again for the next chunk)
 }
 
 }  // namespace

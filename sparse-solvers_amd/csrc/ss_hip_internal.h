@@ -703,6 +703,8 @@ hipError_t launch_gemm64_tn_f64(const ss_hip_ctx* ctx, const uint32_t* rcols, co
                                 double* D, uint32_t ldd, const DevState* st);
 
 // ---- helpers implemented in homotopy.hip ---------------------------------------
+// (the rest of the host side the entry points share — HipFail / HIPCHK, guarded, on_device, record_bytes, DeviceBuf — is host_common.h)
+// msg into the caller's buffer, cut to errlen - 1 characters and always terminated; a null or empty buffer is left alone
 void set_err(char* err, size_t errlen, const std::string& msg);
 // the one-slot fp32 workspace of a context with an active-set capacity of at least kcap (0 / ss_hip_status)
 int colshard_workspace(ss_hip_ctx* ctx, uint32_t kcap);

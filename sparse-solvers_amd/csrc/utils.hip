@@ -11,6 +11,7 @@
 // result does not depend on the launch geometry.
 #include "ss_hip_internal.h"
 #include "ss_hip_device.h"
+#include "host_common.h"
 
 #include <algorithm>
 #include <cstring>
@@ -81,17 +82,6 @@ void k_l1_scale(T* __restrict__ A, long long rs, long long cs, uint32_t rows, ui
     }
 }
 
-struct HipFail2 { hipError_t code; const char* what; };
-#define HIPCHK2(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw HipFail2{ e_, #expr }; } while (0)
-
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof(attr));
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || attr.type == hipMemoryTypeUnified;
-}
-
 // column sums of a device-resident strided block of `rows` rows into sums (accumulate: add to what is there)
 template <typename T>
 void device_col_sums(const T* A, long long rs, long long cs, uint32_t rows, uint32_t n, T* partial, T* sums, int accumulate,
@@ -101,9 +91,9 @@ void device_col_sums(const T* A, long long rs, long long cs, uint32_t rows, uint
     const bool col_contig = (rs == 1 && cs != 1);
     if (col_contig) hipLaunchKernelGGL((k_l1_partial_col<T>), dim3(n, chunks), dim3(256), 0, st, A, rs, cs, rows, n, partial);
     else hipLaunchKernelGGL((k_l1_partial<T>), dim3((n + 255u) / 256u, chunks), dim3(256), 0, st, A, rs, cs, rows, n, partial);
-    HIPCHK2(hipGetLastError());
+    HIPCHK(hipGetLastError());
     hipLaunchKernelGGL((k_l1_reduce<T>), dim3((n + 255u) / 256u), dim3(256), 0, st, (const T*)partial, chunks, n, sums, accumulate);
-    HIPCHK2(hipGetLastError());
+    HIPCHK(hipGetLastError());
 }
 
 template <typename T>
@@ -113,7 +103,7 @@ void device_scale(T* A, long long rs, long long cs, uint32_t rows, uint32_t n, c
     const size_t total = (size_t)rows * n;
     const uint32_t grid = (uint32_t)std::min<size_t>((total + 255) / 256, (size_t)1 << 20);
     hipLaunchKernelGGL((k_l1_scale<T>), dim3(grid), dim3(256), 0, st, A, rs, cs, rows, n, sums, col_contig ? 0 : 1);
-    HIPCHK2(hipGetLastError());
+    HIPCHK(hipGetLastError());
 }
 
 template <typename T>
@@ -124,45 +114,51 @@ int norm_l1_impl(T* A, size_t m, size_t n, ptrdiff_t rs, ptrdiff_t cs, int devic
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(err, errlen, "norm_l1: no HIP device available"); return SS_HIP_ENODEVICE; }
     if (device < 0 || device >= ndev) { set_err(err, errlen, "norm_l1: device index out of range"); return SS_HIP_EINVAL; }
-    T* partial = nullptr; T* sums = nullptr; T* stage = nullptr;
-    hipStream_t st = nullptr;
-    int rc = SS_HIP_OK;
-    try {
-        HIPCHK2(hipSetDevice(device));
-        HIPCHK2(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        HIPCHK2(hipMalloc(&sums, n * sizeof(T)));
+    // the call's own stream and scratch, released in this order on every way out: partial, sums, stage, the stream
+    struct OwnStream { hipStream_t st = nullptr; ~OwnStream() { if (st) (void)hipStreamDestroy(st); } } own;
+    DeviceBuf stage_buf, sums_buf, partial_buf;
+    // (like the solver's entry points, every failed HIP call reports SS_HIP_ERUNTIME, an allocation included)
+    return guarded(err, errlen, "norm_l1", [&]() -> int {
+        hipStream_t& st = own.st;
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        sums_buf.alloc(n * sizeof(T), "hipMalloc(&sums, n * sizeof(T))");
+        T* sums = sums_buf.get<T>();
         if (on_device(A)) {
             const uint32_t chunks = (uint32_t)((m + kL1Chunk - 1) / kL1Chunk);
-            HIPCHK2(hipMalloc(&partial, (size_t)chunks * n * sizeof(T)));
+            partial_buf.alloc((size_t)chunks * n * sizeof(T), "hipMalloc(&partial, (size_t)chunks * n * sizeof(T))");
+            T* partial = partial_buf.get<T>();
             device_col_sums<T>(A, rs, cs, (uint32_t)m, (uint32_t)n, partial, sums, 0, st);
             device_scale<T>(A, rs, cs, (uint32_t)m, (uint32_t)n, sums, st);
-            HIPCHK2(hipStreamSynchronize(st));
+            HIPCHK(hipStreamSynchronize(st));
         } else {
             // host matrix: row panels through a staging buffer (row-major there), two passes
             const size_t panel_bytes = (size_t)256 << 20;
             const size_t R = std::max<size_t>(1, std::min(m, panel_bytes / std::max<size_t>(1, n * sizeof(T))));
             const uint32_t chunks = (uint32_t)((R + kL1Chunk - 1) / kL1Chunk);
-            HIPCHK2(hipMalloc(&stage, R * n * sizeof(T)));
-            HIPCHK2(hipMalloc(&partial, (size_t)chunks * n * sizeof(T)));
+            stage_buf.alloc(R * n * sizeof(T), "hipMalloc(&stage, R * n * sizeof(T))");
+            partial_buf.alloc((size_t)chunks * n * sizeof(T), "hipMalloc(&partial, (size_t)chunks * n * sizeof(T))");
+            T* stage = stage_buf.get<T>();
+            T* partial = partial_buf.get<T>();
             const bool rowmajor = (cs == 1 || n == 1) && (rs >= (ptrdiff_t)n || m == 1) && rs > 0;
             std::vector<T> gather;
             auto upload = [&](size_t r0, size_t rows) {
                 if (rowmajor) {
                     const size_t spitch = (m == 1) ? n * sizeof(T) : (size_t)rs * sizeof(T);
-                    HIPCHK2(hipMemcpy2DAsync(stage, n * sizeof(T), A + (ptrdiff_t)r0 * rs, spitch, n * sizeof(T), rows, hipMemcpyHostToDevice, st));
+                    HIPCHK(hipMemcpy2DAsync(stage, n * sizeof(T), A + (ptrdiff_t)r0 * rs, spitch, n * sizeof(T), rows, hipMemcpyHostToDevice, st));
                 } else {
                     gather.resize(rows * n);
                     for (size_t i = 0; i < rows; ++i)
                         for (size_t j = 0; j < n; ++j) gather[i * n + j] = A[(ptrdiff_t)(r0 + i) * rs + (ptrdiff_t)j * cs];
-                    HIPCHK2(hipMemcpyAsync(stage, gather.data(), rows * n * sizeof(T), hipMemcpyHostToDevice, st));
-                    HIPCHK2(hipStreamSynchronize(st));           // `gather` is reused by the next panel
+                    HIPCHK(hipMemcpyAsync(stage, gather.data(), rows * n * sizeof(T), hipMemcpyHostToDevice, st));
+                    HIPCHK(hipStreamSynchronize(st));           // `gather` is reused by the next panel
                 }
             };
             for (size_t r0 = 0; r0 < m; r0 += R) {
                 const size_t rows = std::min(R, m - r0);
                 upload(r0, rows);
                 device_col_sums<T>(stage, (long long)n, 1, (uint32_t)rows, (uint32_t)n, partial, sums, r0 != 0, st);
-                HIPCHK2(hipStreamSynchronize(st));
+                HIPCHK(hipStreamSynchronize(st));
             }
             for (size_t r0 = 0; r0 < m; r0 += R) {
                 const size_t rows = std::min(R, m - r0);
@@ -170,29 +166,19 @@ int norm_l1_impl(T* A, size_t m, size_t n, ptrdiff_t rs, ptrdiff_t cs, int devic
                 device_scale<T>(stage, (long long)n, 1, (uint32_t)rows, (uint32_t)n, sums, st);
                 if (rowmajor) {
                     const size_t dpitch = (m == 1) ? n * sizeof(T) : (size_t)rs * sizeof(T);
-                    HIPCHK2(hipMemcpy2DAsync(A + (ptrdiff_t)r0 * rs, dpitch, stage, n * sizeof(T), n * sizeof(T), rows, hipMemcpyDeviceToHost, st));
-                    HIPCHK2(hipStreamSynchronize(st));
+                    HIPCHK(hipMemcpy2DAsync(A + (ptrdiff_t)r0 * rs, dpitch, stage, n * sizeof(T), n * sizeof(T), rows, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
                 } else {
                     gather.resize(rows * n);
-                    HIPCHK2(hipMemcpyAsync(gather.data(), stage, rows * n * sizeof(T), hipMemcpyDeviceToHost, st));
-                    HIPCHK2(hipStreamSynchronize(st));
+                    HIPCHK(hipMemcpyAsync(gather.data(), stage, rows * n * sizeof(T), hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipStreamSynchronize(st));
                     for (size_t i = 0; i < rows; ++i)
                         for (size_t j = 0; j < n; ++j) A[(ptrdiff_t)(r0 + i) * rs + (ptrdiff_t)j * cs] = gather[i * n + j];
                 }
             }
         }
-    } catch (const HipFail2& f) {
-        set_err(err, errlen, std::string("HIP error: ") + hipGetErrorString(f.code) + " in " + f.what);
-        rc = SS_HIP_ERUNTIME;
-    } catch (const std::bad_alloc&) {
-        set_err(err, errlen, "norm_l1: out of host memory");
-        rc = SS_HIP_ENOMEM;
-    }
-    if (partial) (void)hipFree(partial);
-    if (sums) (void)hipFree(sums);
-    if (stage) (void)hipFree(stage);
-    if (st) (void)hipStreamDestroy(st);
-    return rc;
+        return SS_HIP_OK;
+    }, SS_HIP_ERUNTIME);
 }
 
 }  // namespace

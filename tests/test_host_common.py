@@ -1,0 +1,104 @@
+"""The host-side toolkit of the C-ABI entry points (sparse-solvers_amd/csrc/host_common.h): a failed HIP call as a status and a
+message, where a pointer lives, the size of a compact record, the owner of a call's scratch allocation.
+
+tests/cpp/test_host_common.cpp includes the header and checks it as a host program (built with the compiler and the target
+build.py uses, linked against the built libss_hip.so for set_err); it launches no kernel, and without a device it skips its
+DeviceBuf part and says so.  The source-level tests keep the toolkit single: one pointer query, one exception struct, one
+throwing macro, one record_bytes.
+"""
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "sparse-solvers_amd")
+CSRC = os.path.join(PKG, "csrc")
+sys.path.insert(0, ROOT)
+
+KMAX = (1, 2, 3, 96, 4096)
+
+
+def record_bytes(kmax, elem):
+    return (16 + kmax * (4 + elem) + 7) & ~7
+
+
+@pytest.fixture(scope="module")
+def program_output(tmp_path_factory):
+    """Builds the library, then the host program, and runs it once as a child process: -> its output"""
+    import __graft_entry__ as ge
+    ge.build()
+    spec = importlib.util.spec_from_file_location("ss_amd_build", os.path.join(PKG, "build.py"))
+    build = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(build)
+    exe = str(tmp_path_factory.mktemp("host_common") / "test_host_common")
+    cmd = [build.HIPCC, "--offload-arch=" + build.ARCH, "-x", "hip", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-comment",
+           "-I", build.INCLUDE, "-I", build.CSRC, os.path.join(ROOT, "tests", "cpp", "test_host_common.cpp"), "-o", exe,
+           "-L", build.LIB, "-lss_hip", "-Wl,-rpath," + build.LIB]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout
+    return r.stdout
+
+
+def test_host_program_passes(program_output):
+    assert "all checks passed" in program_output, program_output
+    assert "FAILED" not in program_output, program_output
+
+
+def test_device_buf_part_runs_exactly_where_a_device_is(program_output):
+    import sship
+    if sship.device_count() > 0:
+        assert "DeviceBuf: checked" in program_output, program_output
+    else:
+        assert "DeviceBuf: skipped (no HIP device)" in program_output, program_output
+
+
+def test_record_bytes_is_the_same_everywhere(program_output):
+    """the header's record_bytes (printed by the program), the C-ABI's ss_hip_record_bytes and the layout's formula"""
+    import sship
+    printed = {(int(k), int(e)): int(v) for k, e, v in re.findall(r"^record_bytes (\d+) (\d+) (\d+)$", program_output, flags=re.M)}
+    assert sorted(printed) == sorted((k, e) for k in KMAX for e in (4, 8))
+    for kmax in KMAX:
+        for elem in (4, 8):
+            want = record_bytes(kmax, elem)
+            assert printed[(kmax, elem)] == want
+            assert int(sship.lib().ss_hip_record_bytes(kmax, 1 if elem == 8 else 0)) == want
+
+
+# ---- the toolkit stays single ------------------------------------------------------------------------------------
+
+def _sources():
+    return {name: open(os.path.join(CSRC, name)).read() for name in sorted(os.listdir(CSRC)) if name.endswith((".hip", ".h"))}
+
+
+def _where(pattern, flags=0):
+    """'file:line' of every match of `pattern` in csrc/"""
+    return ["%s:%d" % (name, text.count("\n", 0, m.start()) + 1)
+            for name, text in _sources().items() for m in re.finditer(pattern, text, flags)]
+
+
+def test_only_host_common_asks_where_a_pointer_lives():
+    hits = _where(r"\bhipPointerGetAttributes\b")
+    assert hits and all(h.startswith("host_common.h:") for h in hits), hits
+    assert len(_where(r"\bhipPointerGetAttributes\s*\(")) == 1
+
+
+def test_hipfail_is_defined_once():
+    assert [h.split(":")[0] for h in _where(r"\bstruct\s+HipFail\w*\s*\{")] == ["host_common.h"]
+
+
+def test_one_macro_throws_hipfail():
+    # (a macro's body, continuation lines included)
+    hits = _where(r"^[ \t]*#[ \t]*define\b(?:[^\n\\]|\\\n|\\.)*\bthrow\s+(?:sship::)?HipFail\w*", re.M)
+    assert [h.split(":")[0] for h in hits] == ["host_common.h"], hits
+
+
+def test_record_bytes_is_defined_once():
+    # a definition: a return type in front of the name, a body behind the parameter list (ss_hip_record_bytes is the C-ABI's name)
+    hits = _where(r"\b(?:size_t|auto)\s+record_bytes\s*\([^)]*\)\s*(?:noexcept\s*)?\{")
+    assert [h.split(":")[0] for h in hits] == ["host_common.h"], hits
