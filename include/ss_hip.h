@@ -357,6 +357,33 @@ int ss_hip_gram_cols_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double
                          int repeats, float* ms_out, char* err, size_t errlen);
 
 /*
+ * The same Gram columns for 1..64 dictionary columns, in every form a solve runs the pass in: S <= 32 runs the
+ * 32-column pass, S > 32 the 64-column pass (the first lookahead sweep of a solve) — the choice a solve makes.
+ * Measurement / test entry; G: S rows of n elements (ldG).  For S <= 32 and tier = 0 the words are
+ * ss_hip_gram_cols_*'s.
+ *   tier = 0    the context's own configuration (fp32: option sweep32_variant names the tiling of the 32-column pass)
+ *   tier = 1    fp64 only: the 32-column pass in 128-column tiles, three workgroups per CU (the 64-column pass has one tiling)
+ *   tier = k>=2 fp64 only: the rows split over k workgroups per column tile, the partial sums added up in order (the form
+ *               narrow sub-dictionaries of the fp64 screened solve run).  The padded row count (m rounded up to 256) must be
+ *               a multiple of 16 k: SS_HIP_EINVAL otherwise.  The partial sums (k * 64 * n_pad doubles) live for the call.
+ * The tier is an argument of this call only; the context is left as it was found, whatever the call returns.
+ */
+int ss_hip_gram_cols_wide_f32(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, int tier, float* G, ptrdiff_t ldG,
+                              int repeats, float* ms_out, char* err, size_t errlen);
+int ss_hip_gram_cols_wide_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, int tier, double* G, ptrdiff_t ldG,
+                              int repeats, float* ms_out, char* err, size_t errlen);
+
+/*
+ * Rows of the context's G = A^T A: out[i][0 .. n) = G[rows[i]][0 .. n) for `count` row indices < n (host list; out: host or
+ * device memory, row stride ldout >= n).  A context that has not formed G yet forms it here, exactly as its first large batch
+ * would: within the budget of option gram_full_gib, by the build option gram_symmetric names, counted in gram_full_builds.
+ * SS_HIP_ENOMEM with a message when G does not fit the budget or the free device memory.  fp32 Homotopy contexts only.
+ * Measurement / test entry: the entries of G are what the batched Gram forms and the full-G single solve decide on.
+ */
+int ss_hip_gram_full_rows_f32(ss_hip_ctx* ctx, const uint32_t* rows, size_t count, float* out, ptrdiff_t ldout,
+                              char* err, size_t errlen);
+
+/*
  * Gs[i][j] = a_{cols[i]} . a_{cols[j]} for a subset of exactly 256 dictionary columns (host index list; entries
  * >= n give zero rows / columns): the 256 x 256 Gram matrix the early speculative iterations of the single-signal
  * engine run on while the full Gram columns are still being swept (csrc/subgram.hip).  Every entry is, bit for

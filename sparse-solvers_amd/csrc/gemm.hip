@@ -21,6 +21,7 @@
 // the 64 MFMAs of step t), one barrier per K-step, 2 workgroups per CU (72 KiB LDS each).
 // Roofline: MFMA fp32, 157.3 TFLOP/s dense peak (MI355X_MICROARCH.md).
 #include "ss_hip_internal.h"
+#include "tri_decode.h"
 
 namespace sship {
 
@@ -63,12 +64,7 @@ void k_gemm_tn_f32(const float* __restrict__ R, const float* __restrict__ Q, flo
         bn = tl < to ? to : tl;
     } else if (SYM) {
         // blockIdx.x = bn (bn + 1) / 2 + bm with bm <= bn
-        const uint32_t b = blockIdx.x;
-        uint32_t t = (uint32_t)((__fsqrt_rn(8.f * (float)b + 1.f) - 1.f) * 0.5f);
-        while ((uint64_t)t * (t + 1u) / 2u > b) --t;
-        while ((uint64_t)(t + 1u) * (t + 2u) / 2u <= b) ++t;
-        bn = t;
-        bm = b - (uint32_t)((uint64_t)t * (t + 1u) / 2u);
+        tri_tile_decode(blockIdx.x, bm, bn);
     } else if (row_tile_skip != nullptr) {
         const uint32_t nact = row_tile_skip[mtiles];
         if (nact == 0 || blockIdx.x / nact >= gridDim.x / mtiles) return;

@@ -2589,35 +2589,92 @@ int gemm_t_impl(ss_hip_ctx* ctx, const float* R, size_t B, ptrdiff_t ldR, float*
     });
 }
 
-// G[s][:] = A^T a_{cols[s]} for up to 32 columns in one HBM-bound pass (lookahead sweep kernel)
+// The private pass fields of a context (the tiling and the row split of the fp64 passes: gemm.hip) as a measurement call found them,
+// put back when the call leaves — by a return or by a thrown HipFail
+struct PassTierGuard {
+    ss_hip_ctx* ctx;
+    int ksplit, tile128;
+    void* part;
+    explicit PassTierGuard(ss_hip_ctx* c) : ctx(c), ksplit(c->pass_ksplit), tile128(c->pass_tile128), part(c->pass_part) {}
+    PassTierGuard(const PassTierGuard&) = delete;
+    PassTierGuard& operator=(const PassTierGuard&) = delete;
+    ~PassTierGuard() { ctx->pass_ksplit = ksplit; ctx->pass_tile128 = tile128; ctx->pass_part = part; }
+};
+
+// G[s][:] = A^T a_{cols[s]} for up to `max_cols` (32 or 64) columns in one pass: S <= 32 the 32-column pass, more the 64-column
+// pass (launch_gemm_first's choice).  tier 0: the context's configuration; fp64 only: 1 = the 128-column tiling of the 32-column
+// pass, k >= 2 = the rows split k ways (what the sub-context of the fp64 screened form runs: gemm.hip)
 template <typename T>
-int gram_cols_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, T* G, ptrdiff_t ldG, int repeats,
-                   float* ms_out, char* err, size_t errlen)
+int gram_cols_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, int tier, T* G, ptrdiff_t ldG, int repeats,
+                   float* ms_out, char* err, size_t errlen, size_t max_cols)
 {
     if (ctx && ctx->kind != 0) { set_err(err, errlen, "this entry point needs a Homotopy context (an IRLS context holds the factorised matrix)"); return SS_HIP_EINVAL; }
-    if (!ctx || !cols || !G || S == 0 || S > 32) { set_err(err, errlen, "gram_cols: need 1..32 columns"); return SS_HIP_EINVAL; }
+    if (!ctx || !cols || !G || S == 0 || S > max_cols) {
+        set_err(err, errlen, max_cols > 32 ? "gram_cols_wide: need 1..64 columns" : "gram_cols: need 1..32 columns");
+        return SS_HIP_EINVAL;
+    }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "gram_cols: element type of the call does not match the context"); return SS_HIP_ETYPE; }
     for (size_t s = 0; s < S; ++s)
         if (cols[s] >= ctx->n) { set_err(err, errlen, "gram_cols: column index out of range"); return SS_HIP_EINVAL; }
+    if (tier < 0 || (tier != 0 && sizeof(T) != 8)) { set_err(err, errlen, "gram_cols_wide: tier must be 0 (fp64 contexts: 0, 1, or the number of row chunks)"); return SS_HIP_EINVAL; }
+    if (tier >= 2 && (ctx->ldm / 16u < (uint32_t)tier || ctx->ldm % (16u * (uint32_t)tier) != 0u)) {
+        set_err(err, errlen, "gram_cols_wide: the padded row count " + std::to_string(ctx->ldm) + " does not split into " + std::to_string(tier) +
+                             " chunks of whole 16-row steps");
+        return SS_HIP_EINVAL;
+    }
     if (repeats < 1) repeats = 1;
-    DeviceBuf Dd_buf, dlist_buf;
+    DeviceBuf Dd_buf, dlist_buf, part_buf;
+    PassTierGuard restore(ctx);
     return guarded_rt(err, errlen, "gram_cols", [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
-        uint32_t h[64];
-        for (int s = 0; s < 32; ++s) {
+        uint32_t h[128];
+        for (int s = 0; s < 64; ++s) {
             h[s] = (size_t)s < S ? cols[s] : 0xffffffffu;
-            h[32 + s] = (size_t)s < S ? (uint32_t)s : 0xffffffffu;
+            h[64 + s] = (size_t)s < S ? (uint32_t)s : 0xffffffffu;
         }
         const size_t np = ctx->n_pad;
+        const size_t rows = S > 32 ? 64 : 32;
         dlist_buf.alloc(sizeof(h), "hipMalloc(&dlist, sizeof(h))");
-        Dd_buf.alloc(32 * np * sizeof(T), "hipMalloc(&Dd, 32 * np * sizeof(T))");
+        Dd_buf.alloc(rows * np * sizeof(T), "hipMalloc(&Dd, rows * np * sizeof(T))");
+        if (tier >= 2) {
+            part_buf.alloc((size_t)tier * 64 * np * sizeof(double), "hipMalloc(&part, tier * 64 * np * sizeof(double))");
+            ctx->pass_part = part_buf.get<void>();
+            ctx->pass_ksplit = tier;
+        } else if (tier == 1) {
+            ctx->pass_ksplit = 0;
+            ctx->pass_tile128 = 1;
+        }
         uint32_t* dlist = dlist_buf.get<uint32_t>();
         T* Dd = Dd_buf.get<T>();
         HIPCHK(hipMemcpyAsync(dlist, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-        timed_repeats(ctx, repeats, ms_out, [&] { HIPCHK(launch_gemm32(ctx, dlist, dlist + 32, Dd, (uint32_t)np, nullptr)); }, [&] {
+        timed_repeats(ctx, repeats, ms_out, [&] { HIPCHK(launch_gemm_first(ctx, (uint32_t)S, dlist, dlist + 64, Dd, (uint32_t)np, nullptr)); }, [&] {
             HIPCHK(hipMemcpy2DAsync(G, (size_t)ldG * sizeof(T), Dd, np * sizeof(T), ctx->n * sizeof(T), S,
                                     hipMemcpyDefault, ctx->stream));
         });
+        return SS_HIP_OK;
+    });
+}
+
+// rows of the context's G = A^T A (formed here if the context has not formed it yet), columns [0, n)
+int gram_full_rows_impl(ss_hip_ctx* ctx, const uint32_t* rows, size_t count, float* out, ptrdiff_t ldout, char* err, size_t errlen)
+{
+    if (ctx && ctx->kind != 0) { set_err(err, errlen, "this entry point needs a Homotopy context (an IRLS context holds the factorised matrix)"); return SS_HIP_EINVAL; }
+    if (!ctx || !rows || !out || count == 0) { set_err(err, errlen, "gram_full_rows: null/empty argument"); return SS_HIP_EINVAL; }
+    if (ctx->is_f64) { set_err(err, errlen, "gram_full_rows: fp32 contexts only"); return SS_HIP_ETYPE; }
+    if (ldout < 0 || (size_t)ldout < ctx->n) { set_err(err, errlen, "gram_full_rows: ldout must be at least n"); return SS_HIP_EINVAL; }
+    for (size_t i = 0; i < count; ++i)
+        if (rows[i] >= ctx->n) { set_err(err, errlen, "gram_full_rows: row index out of range"); return SS_HIP_EINVAL; }
+    return guarded_rt(err, errlen, "gram_full_rows", [&]() -> int {
+        HIPCHK(hipSetDevice(ctx->device));
+        if (!ensure_full_gram(ctx)) {
+            set_err(err, errlen, "gram_full_rows: G = A^T A (" + std::to_string(((size_t)ctx->n_pad * ctx->n_pad * sizeof(float)) >> 20) +
+                                 " MiB) does not fit the budget (option gram_full_gib) or the free device memory");
+            return SS_HIP_ENOMEM;
+        }
+        for (size_t i = 0; i < count; ++i)
+            HIPCHK(hipMemcpyAsync(out + (ptrdiff_t)i * ldout, ctx->gram_full + (size_t)rows[i] * ctx->gram_pitch, ctx->n * sizeof(float),
+                                  hipMemcpyDefault, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
         return SS_HIP_OK;
     });
 }
@@ -2973,13 +3030,30 @@ int ss_hip_gemm_t_f32(ss_hip_ctx* ctx, const float* R, size_t B, ptrdiff_t ldR, 
 int ss_hip_gram_cols_f32(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, float* G, ptrdiff_t ldG, int repeats,
                          float* ms_out, char* err, size_t errlen)
 {
-    return gram_cols_impl<float>(ctx, cols, S, G, ldG, repeats, ms_out, err, errlen);
+    return gram_cols_impl<float>(ctx, cols, S, 0, G, ldG, repeats, ms_out, err, errlen, 32);
 }
 
 int ss_hip_gram_cols_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* G, ptrdiff_t ldG, int repeats,
                          float* ms_out, char* err, size_t errlen)
 {
-    return gram_cols_impl<double>(ctx, cols, S, G, ldG, repeats, ms_out, err, errlen);
+    return gram_cols_impl<double>(ctx, cols, S, 0, G, ldG, repeats, ms_out, err, errlen, 32);
+}
+
+int ss_hip_gram_cols_wide_f32(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, int tier, float* G, ptrdiff_t ldG, int repeats,
+                              float* ms_out, char* err, size_t errlen)
+{
+    return gram_cols_impl<float>(ctx, cols, S, tier, G, ldG, repeats, ms_out, err, errlen, 64);
+}
+
+int ss_hip_gram_cols_wide_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, int tier, double* G, ptrdiff_t ldG, int repeats,
+                              float* ms_out, char* err, size_t errlen)
+{
+    return gram_cols_impl<double>(ctx, cols, S, tier, G, ldG, repeats, ms_out, err, errlen, 64);
+}
+
+int ss_hip_gram_full_rows_f32(ss_hip_ctx* ctx, const uint32_t* rows, size_t count, float* out, ptrdiff_t ldout, char* err, size_t errlen)
+{
+    return gram_full_rows_impl(ctx, rows, count, out, ldout, err, errlen);
 }
 
 int ss_hip_subset_gram_f32(ss_hip_ctx* ctx, const uint32_t* cols, float* Gs, int repeats, float* ms_out, char* err, size_t errlen)

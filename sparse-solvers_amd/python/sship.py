@@ -29,7 +29,7 @@ SYMBOLS = [
     "ss_hip_omp_solve_batch_f32", "ss_hip_omp_solve_batch_f64",
     "ss_hip_omp_solve_batch_compact_f32", "ss_hip_omp_solve_batch_compact_f64",
     "ss_hip_gemv_t_f32", "ss_hip_gemv_t_f64", "ss_hip_gemm_t_f32", "ss_hip_gram_cols_f32", "ss_hip_gram_cols_f64",
-    "ss_hip_subset_gram_f32",
+    "ss_hip_subset_gram_f32", "ss_hip_gram_cols_wide_f32", "ss_hip_gram_cols_wide_f64", "ss_hip_gram_full_rows_f32",
     "ss_hip_reconstruct_f32", "ss_hip_reconstruct_f64", "ss_hip_norm_l1_f32", "ss_hip_norm_l1_f64",
     "ss_hip_set_profiling", "ss_hip_get_stats", "ss_hip_reset_stats",
     "ss_hip_set_option", "ss_hip_get_option", "ss_hip_get_trace", "ss_hip_ctx_info",
@@ -223,6 +223,11 @@ def lib():
     for nme in ("ss_hip_gram_cols_f32", "ss_hip_gram_cols_f64"):
         getattr(L, nme).restype = ctypes.c_int
         getattr(L, nme).argtypes = [vp, vp, sz, vp, pd, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
+    for nme in ("ss_hip_gram_cols_wide_f32", "ss_hip_gram_cols_wide_f64"):
+        getattr(L, nme).restype = ctypes.c_int
+        getattr(L, nme).argtypes = [vp, vp, sz, ctypes.c_int, vp, pd, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
+    L.ss_hip_gram_full_rows_f32.restype = ctypes.c_int
+    L.ss_hip_gram_full_rows_f32.argtypes = [vp, vp, sz, vp, pd, cp, sz]
     L.ss_hip_homotopy_destroy.restype = None
     L.ss_hip_homotopy_destroy.argtypes = [vp]
     L.ss_hip_irls_destroy.restype = None
@@ -685,15 +690,31 @@ class Homotopy:
                                             ctypes.byref(ms), err, len(err)), err)
         return out, float(ms.value)
 
-    def gram_cols(self, cols, repeats=1):
-        """G[s] = A^T a_{cols[s]} for up to 32 columns in one pass -> (G (S, n), mean ms)"""
+    def gram_cols(self, cols, repeats=1, tier=0, wide=None):
+        """G[s] = A^T a_{cols[s]} for up to 64 columns in one pass -> (G (S, n), mean ms).  Up to 32 columns at tier 0 go through
+        ss_hip_gram_cols_*; more columns, a tier (include/ss_hip.h: fp64 tilings and row splits) or wide=True through
+        ss_hip_gram_cols_wide_*."""
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
         G = np.empty((len(cols), self.n), dtype=self.dtype)
         ms = ctypes.c_float(0.0)
         err = ctypes.create_string_buffer(512)
-        self._check(getattr(lib(), "ss_hip_gram_cols_" + self.suffix)(self._h, cols.ctypes.data, len(cols), G.ctypes.data, self.n,
-                                               int(repeats), ctypes.byref(ms), err, len(err)), err)
+        if wide is None:
+            wide = len(cols) > 32 or int(tier) != 0
+        if wide:
+            self._check(getattr(lib(), "ss_hip_gram_cols_wide_" + self.suffix)(self._h, cols.ctypes.data, len(cols), int(tier), G.ctypes.data,
+                                                                             self.n, int(repeats), ctypes.byref(ms), err, len(err)), err)
+        else:
+            self._check(getattr(lib(), "ss_hip_gram_cols_" + self.suffix)(self._h, cols.ctypes.data, len(cols), G.ctypes.data, self.n,
+                                                                        int(repeats), ctypes.byref(ms), err, len(err)), err)
         return G, float(ms.value)
+
+    def gram_rows(self, rows):
+        """rows of the context's G = A^T A (formed on first use: options gram_full_gib, gram_symmetric) -> (len(rows), n) float32"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        out = np.empty((len(rows), self.n), dtype=np.float32)
+        err = ctypes.create_string_buffer(512)
+        self._check(lib().ss_hip_gram_full_rows_f32(self._h, rows.ctypes.data, len(rows), out.ctypes.data, self.n, err, len(err)), err)
+        return out
 
     def subset_gram(self, cols, repeats=1):
         """Gs = A_S^T A_S for exactly 256 columns (csrc/subgram.hip) -> (Gs (256, 256) float32, mean kernel ms)"""

@@ -490,6 +490,9 @@ def test_gemm_t_vs_numpy(sship):
         C, ms = h.gemm_t(R)
         want = R.astype(np.float64) @ A.astype(np.float64)
         assert np.abs(C - want).max() <= 2e-5 * np.abs(want).max()
+        # ... and every entry within the a-priori bound of an m-term fp32 dot product in any order: gamma_m (|R| |A|)
+        mu = A.shape[0] * 2.0 ** -24
+        assert np.all(np.abs(C - want) <= mu / (1 - mu) * (np.abs(R).astype(np.float64) @ np.abs(A).astype(np.float64)))
         c0, _ = h.gemv_t(R[3])
         assert np.abs(C[3] - c0).max() <= 2e-5 * np.abs(c0).max()
 
@@ -1404,6 +1407,13 @@ def test_gram_cols_vs_numpy(sship, dtype):
             ref = (A.astype(np.float64).T @ A.astype(np.float64)[:, cols[:S]]).T
             assert G.shape == (S, n) and G.dtype == dtype
             assert np.abs(G - ref).max() <= (2e-6 if dtype == np.float32 else 1e-14)
+            # ... and every entry within the a-priori bound of an m-term dot product in any order, gamma_m (|A|^T |A|), against a
+            # reference one precision up (float64 for fp32, long double for fp64)
+            up = np.float64 if dtype == np.float32 else np.longdouble
+            Aup = A.astype(up)
+            mu = m * (2.0 ** -24 if dtype == np.float32 else 2.0 ** -53)
+            bound = mu / (1 - mu) * (np.abs(Aup[:, cols[:S]]).T @ np.abs(Aup))
+            assert np.all(np.abs(G.astype(up) - Aup[:, cols[:S]].T @ Aup) <= bound)
 
 
 @pytest.mark.gpu
