@@ -33,7 +33,8 @@ extern "C" {
                                     ss_hip_set_classes, ss_hip_reconstruct_records_*, ss_hip_class_residuals_*, ss_hip_homotopy_classify_batch_* —
                                     no new option key, no new field of ss_hip_stats; ss_hip_homotopy_replace_columns_*;
                                     the atom update of dictionary learning, ss_hip_homotopy_atom_update_*, with the test-aid option
-                                    "dl_chunk_max" — no new field of ss_hip_stats) */
+                                    "dl_chunk_max" — no new field of ss_hip_stats; the least-squares refit of compact records,
+                                    ss_hip_refit_records_* — no new option key, no new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -322,6 +323,51 @@ int ss_hip_homotopy_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
                                     double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
                                     uint32_t* usage, double* objective, uint32_t apply,
                                     char* err, size_t errlen);
+
+/*
+ * The least-squares refit of compact records on their supports — debiasing (added under ABI version 7; csrc/refit.hip; NOT in the
+ * reference).  A Homotopy record holds the LASSO solution at lambda ~ tol: the support is right, every coefficient is shrunk by the
+ * l1 penalty (|A_S^T (y - A_S x)| = lambda on the support).  For signal b, with S the record's stored columns in record order and K
+ * their number,
+ *     records_out[b] = the input record with val[0 .. K) replaced by z = argmin || y_b - A_S z ||_2, rounded once to T;
+ *                      K, iter, err, idx and the unused tail are copied word for word; a coefficient that comes out as 0 stays in
+ *                      the record; for every status other than SS_HIP_REFIT_DONE the record is copied unchanged
+ *     resnorm[b]     (may be NULL) || y_b - A x ||_2 of the record as written to records_out: the words ss_hip_class_residuals_*
+ *                      returns in R[b][0] for that record with every column in class 0 (widened to double; NaN for a TRUNCATED
+ *                      record, || y_b ||_2 for K = 0)
+ *     status[b]      (may be NULL) one of SS_HIP_REFIT_*
+ * records_out may be `records` itself (in place) or disjoint from it; any other overlap is undefined.  Y holds the B signals (row b
+ * at Y[b*y_stride + i*incy]); all data pointers may be host or device pointers.
+ * ARITHMETIC (one documented order: csrc/refit.hip): G = A_S^T A_S and h = A_S^T y are formed together, y as
+ * column K of the panel, lower triangle only, products and sums in the context's precision on the matrix cores; the rows are split
+ * into chunks of 1024 (a function of m alone), the chunk partials added in double in ascending chunk order; the normal equations
+ * are solved in double for both element types by a Cholesky factorisation.  A signal is SS_HIP_REFIT_SINGULAR when for some j
+ * !(d_j > 8 K eps(T) G_jj), d_j the j-th pivot before its square root: a column listed twice and an all-zero column always are.
+ * The columns are always read from A, never from a resident A^T A.
+ * CONTRACT: signal b's output record, resnorm[b] and status[b] are a function of its input record, its y and A alone — bit for bit
+ * the same alone or in any batch, in any batch order, with host or device pointers, in place or out of place, across the internal
+ * chunking, whatever the context did before.  No floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  null ctx, Y, records or records_out; an IRLS or a column-sharded context; kmax outside 1..4096; records or
+ *                  records_out not 8-byte aligned; a non-positive incy or y_stride; a record index >= n (found on the device,
+ *                  never used as an address)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_REFIT_KMAX 160
+/* status[b] */
+#define SS_HIP_REFIT_DONE 0       /* values replaced by the least-squares fit            */
+#define SS_HIP_REFIT_EMPTY 1      /* K == 0: nothing to fit                              */
+#define SS_HIP_REFIT_TRUNCATED 2  /* K > kmax: the record does not hold its support      */
+#define SS_HIP_REFIT_TOO_LARGE 3  /* kmax >= K > SS_HIP_REFIT_KMAX                       */
+#define SS_HIP_REFIT_SINGULAR 4   /* the support's Gram matrix failed the pivot test     */
+
+int ss_hip_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                             const void* records, uint32_t kmax, void* records_out,
+                             double* resnorm, uint32_t* status, char* err, size_t errlen);
+int ss_hip_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                             const void* records, uint32_t kmax, void* records_out,
+                             double* resnorm, uint32_t* status, char* err, size_t errlen);
 
 /*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)

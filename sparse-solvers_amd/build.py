@@ -59,6 +59,8 @@ HIP_UNITS = [
     ("dictupdate.hip", []),
     # the atom update of dictionary learning from compact records: products and sums rounded separately, in the documented order
     ("dictlearn.hip", ["-ffp-contract=off"]),
+    # the least-squares refit of compact records: products and sums rounded separately, in the documented order (the tests' bounds)
+    ("refit.hip", ["-ffp-contract=off"]),
 ]
 
 

@@ -342,16 +342,18 @@ int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errl
     return SS_HIP_OK;
 }
 
+// labels / C: the classes the residuals are taken by — the context's (class_residuals, classify), or nullptr / 1: every column in
+// one class (record_residual_norms).  best may be null then.
 template <typename T>
-int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                   T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+int residuals_impl(ss_hip_ctx* ctx, const char* who, const uint32_t* labels, uint32_t C, const T* Y, size_t B, ptrdiff_t y_stride,
+                   ptrdiff_t incy, const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err,
+                   size_t errlen)
 {
-    static const char* who = "class_residuals";
     HIPCHK(hipSetDevice(ctx->device));
     ClassifyState* cs = state_of(ctx);
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, C = cs->num_classes;
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n;
     const uint32_t ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), segcap = std::min(kmax, C);
     const bool rec_dev = on_device(records), y_dev = on_device(Y);
 
@@ -390,7 +392,7 @@ int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
             long long ys = y_stride, yi = incy;
             if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
             hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
-                               (const uint32_t*)cs->labels, C, segcap, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
+                               labels, C, segcap, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
             hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
                                (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
                                (const uint32_t*)sig, part, party, (T*)nullptr);
@@ -399,7 +401,7 @@ int residuals_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
             HIPCHK(hipGetLastError());
             if (R) HIPCHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), Rb, (size_t)C * sizeof(T),
                                            (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
-            HIPCHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
+            if (best) HIPCHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
             if (sci) HIPCHK(hipMemcpyAsync(sci + b0, dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
         }
         HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -424,7 +426,10 @@ int class_residuals_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_str
         set_err(err, errlen, "class_residuals: r_stride must be at least num_classes");
         return SS_HIP_EINVAL;
     }
-    return guarded(err, errlen, who, [&] { return residuals_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen); });
+    return guarded(err, errlen, who, [&] {
+        const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+        return residuals_impl<T>(ctx, who, cs->labels, cs->num_classes, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+    });
 }
 
 template <typename T>
@@ -555,7 +560,7 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
         }
         const int rs = solve_compact(ctx, yd, B, ys, yi, tol, max_iter, kmax, rd, err, errlen);
         if (rs != SS_HIP_OK) return rs;
-        const int rr = residuals_impl<T>(ctx, yd, B, ys, yi, rd, kmax, R, r_stride, best, sci, err, errlen);
+        const int rr = residuals_impl<T>(ctx, "class_residuals", cs->labels, cs->num_classes, yd, B, ys, yi, rd, kmax, R, r_stride, best, sci, err, errlen);
         if (rr != SS_HIP_OK) return rr;
         if (records && rd != records) HIPCHK(hipMemcpy(records, rd, B * rb, hipMemcpyDeviceToHost));
         return SS_HIP_OK;
@@ -563,6 +568,19 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
 }
 
 }  // namespace
+
+// Rn[b] = ||y_b - A x_b||_2 of B compact records: the words ss_hip_class_residuals_* gives in R[b][0] with every column in class 0
+// (its kernels, its order; NaN for a truncated record, ||y_b||_2 for K = 0).  The residual path behind the entry point's validation,
+// for the refit (refit.hip); needs no classes.  Y, records and Rn on either side.  Throws what HIPCHK throws: call it under guarded.
+template <typename T>
+int record_residual_norms(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                          uint32_t kmax, T* Rn, char* err, size_t errlen)
+{
+    return residuals_impl<T>(ctx, who, nullptr, 1u, Y, B, y_stride, incy, records, kmax, Rn, 1, nullptr, nullptr, err, errlen);
+}
+
+template int record_residual_norms<float>(ss_hip_ctx*, const char*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, float*, char*, size_t);
+template int record_residual_norms<double>(ss_hip_ctx*, const char*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, double*, char*, size_t);
 
 void classify_free(ss_hip_ctx* ctx)
 {

@@ -2891,6 +2891,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     sship::omp_gram_free(ctx);
     sship::classify_free(ctx);
     sship::dictlearn_free(ctx);
+    sship::refit_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);

@@ -1,0 +1,454 @@
+// refit.hip — the least-squares refit of compact records on their supports (debiasing), on the device (include/ss_hip.h):
+//   ss_hip_refit_records_*.
+//
+// A Homotopy record holds the LASSO solution at lambda ~ tol: the right support, every coefficient shrunk by the l1 penalty.  For
+// signal b with the record's stored columns S (record order, K of them) the refit replaces val[0 .. K) by
+//   z = argmin || y_b - A_S z ||_2,      the solution of the normal equations (A_S^T A_S) z = A_S^T y_b,
+// and copies everything else of the record word for word.  Only the record's columns of A are read, one contiguous run of ldm
+// elements each (ctx->At, [n_pad][ldm]): sum K_b * ldm elements, never a resident G = A^T A (whose words depend on what the context
+// did before).  Three kernels:
+//
+//   k_rf_check   one workgroup per signal, the whole batch before anything is written: the status from K (EMPTY, TRUNCATED,
+//                TOO_LARGE, else DONE), and the first record with a column index >= n — never used as an address.
+//   k_rf_gram    grid = (row chunk, signal).  The panel P = [A_S | y] (K + 1 columns, padded with zero columns to a multiple of 16)
+//                is staged through LDS 32 rows at a time, the next stage's loads in flight under the MFMAs; the lower triangle of
+//                P^T P (G = A_S^T A_S, and h = A_S^T y as its row K) is formed in 16 x 16 tiles on v_mfma_f32_16x16x4_f32 /
+//                v_mfma_f64_16x16x4_f64, the tiles dealt round-robin to the four waves.  One partial per (signal, chunk, tile).
+//   k_rf_solve   one workgroup per signal: the chunk partials added up in double, the packed lower triangle of [G h; h^T .] in LDS
+//                ((K + 1)(K + 2) / 2 doubles, 104 KB at K = 160), its Cholesky factorisation column by column — row K takes the
+//                forward substitution along — the pivot test, the back substitution, z rounded once to T into the output record.
+// The residual norms are the words of ss_hip_class_residuals_* with every column in class 0 on the records as written: its kernels,
+// reached through record_residual_norms (classify.hip).
+//
+// SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately outside
+// the MFMA, whose four products per instruction are a chain of fused multiply-adds):
+//   row chunks   of kRfRows = 1024 rows: chunk c holds rows 1024 c .. min(1024 c + 1023, ldm - 1) — a function of m alone (rows
+//                m .. ldm - 1 of At and of y are zero);
+//   a partial    G_c[i][j] = sum over the chunk's rows r, ascending, of P[r][i] * P[r][j]: one accumulator per element, started at 0,
+//                fma after fma in the context's precision (the longest chain: 1024 terms) — whichever wave or tile holds it;
+//   G, h         = the chunk partials added one after the other in ascending chunk order, in double, starting from 0;
+//   Cholesky     in double, right-looking: for j ascending  d_j = G_jj as updated so far (the pivot),  l_jj = sqrt(d_j),
+//                l_ij = G_ij / l_jj for i > j (row K: w_j = h_j / l_jj),  then G_ik = G_ik - l_ij * l_kj for j < k <= i: every
+//                element takes its updates one after the other in ascending j;
+//   pivot test   the signal is SINGULAR when for some j  !(d_j > 8 K eps(T) G_jj)  with G_jj the diagonal before any update (a NaN
+//                fails it; a column named twice gives a second pivot of rounding size, an all-zero column G_jj = 0);
+//   back subst.  for j descending  z_j = w_j / l_jj,  then w_i = w_i - l_ji * z_j for i < j, in double;
+//   val[e]       = z_e rounded once to T.
+// No floating-point atomics; nothing depends on B, on the chunking of the batch, on the launch geometry, on where the pointers live or
+// on what the context did before: a signal's record, residual norm and status are a function of its input record, its y and A.
+#include "ss_hip_internal.h"
+#include "record_common.h"
+#include "tri_decode.h"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace sship {
+
+namespace {
+
+constexpr uint32_t kRfRows = 1024;                       // rows of a row chunk (a function of nothing: the split depends on m alone)
+constexpr uint32_t kRfStep = 32;                         // rows staged through LDS at a time
+constexpr uint32_t kRfChunkMax = 1024;                   // most signals per internal chunk ...
+constexpr size_t kRfChunkBytes = (size_t)256 << 20;      // ... and the byte budget of a chunk's partials (never changes a result)
+
+typedef float rf_v4f __attribute__((ext_vector_type(4)));
+typedef double rf_v4d __attribute__((ext_vector_type(4)));
+typedef double rf_v2d __attribute__((ext_vector_type(2)));
+
+// the 16 x 16 x 4 MFMA of T: operands one element a lane (row / column lane & 15, k = lane >> 4), four results a lane at column
+// lane & 15 and row `row(e, lane)`; slot(ri, cj) = where element (ri, cj) of a tile sits among a wave's 4 x 64 results
+template <typename T> struct RfMma;
+template <> struct RfMma<float> {
+    typedef rf_v4f Acc;
+    typedef rf_v4f V;
+    static constexpr uint32_t W = 4;
+    __device__ static Acc mma(float a, float b, Acc c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+    __device__ static uint32_t slot(uint32_t ri, uint32_t cj) { return (ri & 3u) * 64u + (ri >> 2) * 16u + cj; }
+};
+template <> struct RfMma<double> {
+    typedef rf_v4d Acc;
+    typedef rf_v2d V;
+    static constexpr uint32_t W = 2;
+    __device__ static Acc mma(double a, double b, Acc c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+    __device__ static uint32_t slot(uint32_t ri, uint32_t cj) { return (ri >> 2) * 64u + (ri & 3u) * 16u + cj; }
+};
+
+__device__ inline void store_val(unsigned char* p, uint32_t e, float v) { reinterpret_cast<float*>(p)[e] = v; }
+__device__ inline void store_val(unsigned char* p, uint32_t e, double v)
+{
+    uint32_t* w = reinterpret_cast<uint32_t*>(p) + 2u * e;       // (4-byte aligned only when kmax is odd: record_common.h, load_val)
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    w[0] = (uint32_t)u;
+    w[1] = (uint32_t)(u >> 32);
+}
+
+struct RefitState {
+    unsigned char* batch = nullptr;    // per call: staged records (a host caller's), status, residual norms, the bad-index word
+    size_t batch_bytes = 0;
+    unsigned char* arena = nullptr;    // per chunk of signals: the Gram partials, a host caller's signals
+    size_t arena_bytes = 0;
+};
+
+RefitState* state_of(ss_hip_ctx* ctx)
+{
+    if (!ctx->rf) ctx->rf = new RefitState();
+    return static_cast<RefitState*>(ctx->rf);
+}
+
+// tile rows of the panel of a record with K stored columns (+ the column of y)
+__host__ __device__ inline uint32_t rf_tile_rows(uint32_t K) { return (K + 16u) / 16u; }
+
+// ---- kernels -------------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(64)
+void k_rf_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax, uint32_t n, uint32_t* __restrict__ stat,
+                uint32_t* __restrict__ bad)
+{
+    const uint32_t b = blockIdx.x;
+    const unsigned char* r = rec + (size_t)b * rb;
+    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
+    const uint32_t K = Krec < kmax ? Krec : kmax;
+    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+    for (uint32_t e = threadIdx.x; e < K; e += 64u)
+        if (idx[e] >= n) atomicMin(bad, b);
+    if (threadIdx.x == 0)
+        stat[b] = Krec == 0u ? (uint32_t)SS_HIP_REFIT_EMPTY : Krec > kmax ? (uint32_t)SS_HIP_REFIT_TRUNCATED
+                  : Krec > (uint32_t)SS_HIP_REFIT_KMAX ? (uint32_t)SS_HIP_REFIT_TOO_LARGE : (uint32_t)SS_HIP_REFIT_DONE;
+}
+
+// NT: the most tile rows a panel of this call can have (from min(kmax, SS_HIP_REFIT_KMAX)); a wave holds up to NTW tiles.
+// part: [signal][chunk][tile_cap tiles][4 results][64 lanes], tile t = ti (ti + 1) / 2 + tj with tj <= ti
+template <typename T, int NT>
+__global__ __launch_bounds__(256)
+void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __restrict__ Y, long long y_stride, long long incy,
+               const unsigned char* __restrict__ rec, size_t rb, const uint32_t* __restrict__ stat, T* __restrict__ part, uint32_t tile_cap)
+{
+    typedef RfMma<T> M;
+    typedef typename M::V V;
+    typedef typename M::Acc Acc;
+    constexpr uint32_t W = M::W, VPC = kRfStep / W, PITCH = kRfStep + W;
+    constexpr int NTW = (NT * (NT + 1) / 2 + 3) / 4;
+    constexpr int NV = (NT * 16 * (int)VPC + 255) / 256;
+    extern __shared__ __align__(16) unsigned char s_rf_raw[];
+    T* sP = reinterpret_cast<T*>(s_rf_raw);                  // [ncol][PITCH]: column c of the panel, the stage's 32 rows
+    const uint32_t chunk = blockIdx.x, b = blockIdx.y, nchunks = gridDim.x;
+    if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) return;
+    const unsigned char* r = rec + (size_t)b * rb;
+    const uint32_t K = *reinterpret_cast<const uint32_t*>(r);
+    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+    const uint32_t nt = rf_tile_rows(K), ntile = nt * (nt + 1u) / 2u, ncol = nt * 16u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, l15 = lane & 15u, kq = lane >> 4;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t row_lo = chunk * kRfRows, row_hi = row_lo + kRfRows < ldm ? row_lo + kRfRows : ldm;
+    const T* y = Y + (long long)b * y_stride;
+
+    for (uint32_t i = tid; i < ncol * PITCH; i += 256u) sP[i] = T(0);       // (the padding columns stay zero)
+
+    // staging slots: vector v = tid + 256 s is rows q W .. q W + W - 1 of the stage, column c = v / VPC
+    const T* cp[NV];
+    uint32_t kind[NV], soff[NV], srow[NV];                   // kind: 0 nothing, 1 a column of A, 2 the signal
+#pragma unroll
+    for (int s = 0; s < NV; ++s) {
+        const uint32_t v = tid + 256u * (uint32_t)s, c = v / VPC, q = (v % VPC) * W;
+        kind[s] = c < K ? 1u : c == K ? 2u : 0u;
+        cp[s] = At + (size_t)(c < K ? idx[c] : 0u) * ldm + q;
+        soff[s] = c * PITCH + q;
+        srow[s] = q;
+    }
+    V vr[NV];
+#define RF_LOAD(R0)                                                                                    \
+    _Pragma("unroll") for (int s = 0; s < NV; ++s) {                                                   \
+        if (kind[s] == 1u) vr[s] = *reinterpret_cast<const V*>(cp[s] + (R0));                          \
+        else if (kind[s] == 2u) {                                                                      \
+            _Pragma("unroll") for (uint32_t e = 0; e < W; ++e) {                                       \
+                const uint32_t row = (R0) + srow[s] + e;                                               \
+                vr[s][e] = row < m ? y[(long long)row * incy] : T(0);                                  \
+            }                                                                                          \
+        }                                                                                              \
+    }
+    RF_LOAD(row_lo)
+
+    // this wave's tiles t = wave, wave + 4, ...: where a lane reads its two operands
+    bool mine[NTW];
+    uint32_t offa[NTW], offb[NTW];
+    Acc acc[NTW];
+#pragma unroll
+    for (int s = 0; s < NTW; ++s) {
+        const uint32_t t = wave + 4u * (uint32_t)s;
+        mine[s] = t < ntile;
+        uint32_t tj = 0, ti = 0;
+        tri_tile_decode(mine[s] ? t : 0u, tj, ti);
+        offa[s] = (ti * 16u + l15) * PITCH + kq;
+        offb[s] = (tj * 16u + l15) * PITCH + kq;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[s][e] = T(0);
+    }
+
+    for (uint32_t r0 = row_lo; r0 < row_hi; r0 += kRfStep) {
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < NV; ++s)
+            if (kind[s] != 0u) *reinterpret_cast<V*>(&sP[soff[s]]) = vr[s];
+        __syncthreads();
+        if (r0 + kRfStep < row_hi) { RF_LOAD(r0 + kRfStep) }
+#pragma unroll
+        for (int s = 0; s < NTW; ++s) {
+            if (!mine[s]) continue;
+#pragma unroll
+            for (uint32_t k4 = 0; k4 < kRfStep; k4 += 4u) acc[s] = M::mma(sP[offa[s] + k4], sP[offb[s] + k4], acc[s]);
+        }
+    }
+#undef RF_LOAD
+    T* pp = part + ((size_t)b * nchunks + chunk) * tile_cap * 256u;
+#pragma unroll
+    for (int s = 0; s < NTW; ++s) {
+        if (!mine[s]) continue;
+        const uint32_t t = wave + 4u * (uint32_t)s;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pp[(size_t)t * 256u + (uint32_t)e * 64u + lane] = acc[s][e];
+    }
+}
+
+// rec_in and rec_out: the same records (in place) or disjoint ones
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_rf_solve(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out,
+                size_t rb, uint32_t kmax, uint32_t* __restrict__ stat)
+{
+    typedef RfMma<T> M;
+    extern __shared__ __align__(16) unsigned char s_rf_raw[];
+    double* L = reinterpret_cast<double*>(s_rf_raw);         // packed rows 0 .. K of [G h; h^T .]: (i, j) at i (i + 1) / 2 + j
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const unsigned char* ri = rec_in + (size_t)b * rb;
+    unsigned char* ro = rec_out + (size_t)b * rb;
+    const uint32_t* wi = reinterpret_cast<const uint32_t*>(ri);
+    uint32_t* wo = reinterpret_cast<uint32_t*>(ro);
+    const uint32_t words = (uint32_t)(rb / 4);
+    if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) {
+        if (ri != ro)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+        return;
+    }
+    const uint32_t K = wi[0], np = (K + 1u) * (K + 2u) / 2u, KB = K * (K + 1u) / 2u;
+    double* g0 = L + np;                                     // [K] the diagonal before any update
+    const size_t cstride = (size_t)tile_cap * 256u;
+    for (uint32_t p = tid; p < np; p += 256u) {
+        uint32_t j = 0, i = 0;
+        tri_tile_decode(p, j, i);
+        const uint32_t ti = i >> 4, tj = j >> 4, t = ti * (ti + 1u) / 2u + tj;
+        const T* pp = part + (size_t)b * nchunks * cstride + (size_t)t * 256u + M::slot(i & 15u, j & 15u);
+        double s = 0.0;
+        for (uint32_t c = 0; c < nchunks; ++c) s += (double)pp[(size_t)c * cstride];
+        L[p] = s;
+    }
+    __syncthreads();
+    for (uint32_t j = tid; j < K; j += 256u) g0[j] = L[j * (j + 1u) / 2u + j];
+    __syncthreads();
+    const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon();
+    bool singular = false;
+    for (uint32_t j = 0; j < K; ++j) {
+        const uint32_t jj = j * (j + 1u) / 2u + j;
+        const double d = L[jj];                              // (every thread reads the same word: the branch is uniform)
+        if (!(d > thr * g0[j])) { singular = true; break; }
+        const double ljj = sqrt(d);
+        __syncthreads();
+        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) { const uint32_t ij = i * (i + 1u) / 2u + j; L[ij] = L[ij] / ljj; }
+        if (tid == 0) L[jj] = ljj;
+        __syncthreads();
+        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) {
+            const uint32_t ib = i * (i + 1u) / 2u, kend = i < K ? i : K - 1u;
+            const double lij = L[ib + j];
+            for (uint32_t k = j + 1u; k <= kend; ++k) L[ib + k] = L[ib + k] - lij * L[k * (k + 1u) / 2u + j];
+        }
+        __syncthreads();
+    }
+    if (singular) {
+        if (tid == 0) stat[b] = (uint32_t)SS_HIP_REFIT_SINGULAR;
+        if (ri != ro)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+        return;
+    }
+    for (uint32_t j = K; j-- > 0u;) {
+        const uint32_t jb = j * (j + 1u) / 2u;
+        __syncthreads();
+        const double zj = L[KB + j] / L[jb + j];
+        __syncthreads();
+        if (tid == 0) L[KB + j] = zj;
+        for (uint32_t i = tid; i < j; i += 256u) L[KB + i] = L[KB + i] - L[jb + i] * zj;
+    }
+    __syncthreads();
+    // everything but val[0 .. K) word for word, then the fit
+    const uint32_t v0 = 4u + kmax, v1 = v0 + K * (uint32_t)(sizeof(T) / 4);
+    if (ri != ro)
+        for (uint32_t w = tid; w < words; w += 256u)
+            if (w < v0 || w >= v1) wo[w] = wi[w];
+    unsigned char* valp = ro + 16 + (size_t)kmax * 4;
+    for (uint32_t e = tid; e < K; e += 256u) store_val(valp, e, (T)L[KB + e]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_rf_widen(const T* __restrict__ in, double* __restrict__ out, uint32_t B)
+{
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b < B) out[b] = (double)in[b];
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+
+template <typename T> size_t rf_solve_lds(uint32_t kcap) { return ((size_t)(kcap + 1) * (kcap + 2) / 2 + kcap) * sizeof(double); }
+
+template <typename T>
+bool rf_solve_attr()
+{
+    static const bool ok = [] {
+        const bool a = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rf_solve<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)rf_solve_lds<T>(SS_HIP_REFIT_KMAX)) == hipSuccess;
+        if (!a) (void)hipGetLastError();
+        return a;
+    }();
+    return ok;
+}
+
+template <typename T, int NT>
+void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, const T* At, uint32_t ldm, uint32_t m, const T* yd, long long ys,
+                 long long yi, const unsigned char* recs, size_t rb, const uint32_t* stat, T* part, uint32_t tile_cap)
+{
+    constexpr uint32_t PITCH = kRfStep + RfMma<T>::W;
+    hipLaunchKernelGGL((k_rf_gram<T, NT>), dim3(nchunks, Bc), dim3(256), (size_t)ntc * 16u * PITCH * sizeof(T), st, At, ldm, m, yd, ys, yi, recs,
+                       rb, stat, part, tile_cap);
+}
+
+template <typename T>
+int refit_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+               void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+{
+    static const char* who = "refit_records";
+    HIPCHK(hipSetDevice(ctx->device));
+    RefitState* rs = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, Bu = (uint32_t)B;
+    const uint32_t nchunks = (uint32_t)((m + kRfRows - 1) / kRfRows);
+    const uint32_t kcap = std::min<uint32_t>(kmax, SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
+    const bool in_dev = on_device(records), out_dev = on_device(records_out), y_dev = on_device(Y);
+    if (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>()) {
+        set_err(err, errlen, "refit_records: the device does not give a workgroup the LDS of a support this large");
+        return SS_HIP_ERUNTIME;
+    }
+
+    // ---- the batch's records where the kernels read and write them, the per-signal outputs ----
+    auto carve_batch = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        unsigned char* stage = (in_dev && out_dev) ? nullptr : cv.take<unsigned char>(B * rb);
+        uint32_t* stat = cv.take<uint32_t>(B);
+        T* rn = cv.take<T>(B);
+        double* rnd = cv.take<double>(B);
+        uint32_t* bad = cv.take<uint32_t>(1);
+        use(stage, stat, rn, rnd, bad);
+        return cv.off;
+    };
+    grow(rs->batch, rs->batch_bytes, carve_batch(nullptr, [](auto...) {}), "hipMalloc(refit batch)");
+    const size_t per = (size_t)nchunks * tile_cap * 256u * sizeof(T) + (y_dev ? 0 : m * sizeof(T)) + 512;
+    const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kRfChunkMax, kRfChunkBytes / per)));
+    auto carve_arena = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        T* part = cv.take<T>(chunk * nchunks * tile_cap * 256u);
+        T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
+        use(part, ybuf);
+        return cv.off;
+    };
+    grow(rs->arena, rs->arena_bytes, carve_arena(nullptr, [](auto...) {}), "hipMalloc(refit workspace)");
+
+    int rc = SS_HIP_OK;
+    carve_batch(rs->batch, [&](unsigned char* stage, uint32_t* stat, T* rn, double* rnd, uint32_t* bad) {
+        // din: the input records on the device; dout: where the output records are written there (a host caller's: the staging,
+        // in place when the input is staged too)
+        const unsigned char* din = static_cast<const unsigned char*>(records);
+        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
+        unsigned char* dout = out_dev ? static_cast<unsigned char*>(records_out) : stage;
+        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(k_rf_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, stat, bad);
+        HIPCHK(hipGetLastError());
+        uint32_t first_bad = 0xffffffffu;
+        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record is invalid)
+        if (first_bad != 0xffffffffu) { rc = bad_index(first_bad, who, err, errlen); return; }
+
+        std::vector<T> tmp;
+        carve_arena(rs->arena, [&](T* part, T* ybuf) {
+            for (size_t b0 = 0; b0 < B; b0 += chunk) {
+                const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+                const T* yd = Y + (ptrdiff_t)b0 * y_stride;
+                long long ys = y_stride, yi = incy;
+                if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
+                const T* At = static_cast<const T*>(ctx->At);
+                if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
+                else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
+                else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
+                hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
+                                   dout + b0 * rb, rb, kmax, stat + b0);
+                HIPCHK(hipGetLastError());
+            }
+        });
+        if (resnorm) {
+            const int rr = record_residual_norms<T>(ctx, who, Y, B, y_stride, incy, dout, kmax, rn, err, errlen);
+            if (rr != SS_HIP_OK) { rc = rr; return; }
+            hipLaunchKernelGGL((k_rf_widen<T>), dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const T*)rn, rnd, Bu);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(resnorm, rnd, B * sizeof(double), hipMemcpyDefault, st));
+        }
+        if (status) HIPCHK(hipMemcpyAsync(status, stat, B * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return rc;
+}
+
+template <typename T>
+int refit_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+{
+    static const char* who = "refit_records";
+    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !records_out) { set_err(err, errlen, "refit_records: Y and records_out must not be null"); return SS_HIP_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "refit_records: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
+    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "refit_records: increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
+    if (B >= 0x80000000ull) { set_err(err, errlen, "refit_records: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    return guarded(err, errlen, who, [&] { return refit_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen); });
+}
+
+}  // namespace
+
+void refit_free(ss_hip_ctx* ctx)
+{
+    RefitState* rs = static_cast<RefitState*>(ctx->rf);
+    if (!rs) return;
+    if (rs->batch) (void)hipFree(rs->batch);
+    if (rs->arena) (void)hipFree(rs->arena);
+    delete rs;
+    ctx->rf = nullptr;
+}
+
+}  // namespace sship
+
+using namespace sship;
+
+extern "C" {
+
+int ss_hip_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                             uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+{
+    return refit_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen);
+}
+int ss_hip_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                             uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+{
+    return refit_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen);
+}
+
+}  // extern "C"

@@ -361,6 +361,7 @@ struct ss_hip_ctx {
     int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
     void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
     void* dl = nullptr;           // sship::DictLearnState* (dictlearn.hip): the workspace of the atom update
+    void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
     int dl_chunk_max = 0;         // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
@@ -501,6 +502,13 @@ void omp_gram_free(ss_hip_ctx* ctx);
 void classify_free(ss_hip_ctx* ctx);
 // the atom update of dictionary learning (dictlearn.hip): releases its workspace
 void dictlearn_free(ss_hip_ctx* ctx);
+// the least-squares refit of compact records (refit.hip): releases its workspace
+void refit_free(ss_hip_ctx* ctx);
+// the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word
+// R[b][0] of that call (NaN for a truncated record).  Y, records, Rn on either side; `who` names the caller in an error's text
+template <typename T>
+int record_residual_norms(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                          uint32_t kmax, T* Rn, char* err, size_t errlen);
 // a column replacement from the device (dictupdate.hip): the body of ss_hip_homotopy_replace_columns_* behind its validation and
 // staging — cols_dev: the distinct columns (< n), cols_host: the same list on the host, V_dev(i, s) = V_dev[i * rs + s * cs]
 template <typename T>

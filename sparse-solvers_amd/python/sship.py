@@ -42,6 +42,7 @@ SYMBOLS = [
     "ss_hip_homotopy_classify_batch_f32", "ss_hip_homotopy_classify_batch_f64",
     "ss_hip_homotopy_replace_columns_f32", "ss_hip_homotopy_replace_columns_f64",
     "ss_hip_homotopy_atom_update_f32", "ss_hip_homotopy_atom_update_f64",
+    "ss_hip_refit_records_f32", "ss_hip_refit_records_f64",
 ]
 
 
@@ -193,6 +194,9 @@ def lib():
         f = getattr(L, "ss_hip_homotopy_atom_update_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, sz, vp, pd, pd, vp, vp, u32, cp, sz]
+        f = getattr(L, "ss_hip_refit_records_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, vp, vp, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
@@ -445,6 +449,48 @@ class Homotopy:
                 ctypes.addressof(obj), 1 if apply else 0, err, len(err))
         self._check(rc, err)
         return V, usage, float(obj.value)
+
+    # status words of refit_records (include/ss_hip.h, SS_HIP_REFIT_*)
+    REFIT_DONE, REFIT_EMPTY, REFIT_TRUNCATED, REFIT_TOO_LARGE, REFIT_SINGULAR = range(5)
+    REFIT_KMAX = 160
+
+    def refit_records(self, Y, records, kmax, out=None, residuals=True):
+        """The least-squares refit of compact records on their supports, debiasing (include/ss_hip.h, ss_hip_refit_records_*):
+        every record's values replaced by argmin ||y_b - A_S z||_2 over its stored columns, everything else of the record copied
+        word for word -> (records_out, resnorm (B,) float64 or None, status (B,)).  status[b] is one of REFIT_*; a record that is
+        not REFIT_DONE comes back unchanged.  resnorm[b] = ||y_b - A x_b||_2 of the record as returned (the words class_residuals
+        gives with every column in class 0; NaN for a truncated record).  `out`: a contiguous (B, record_bytes) uint8 array or
+        tensor on either side that receives the records — `records` itself refits in place; default: a new one where `records`
+        lives.  resnorm and status live where Y lives (device tensors for a device Y — status then int32 — else numpy arrays)."""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        rp, B = self._records_arg(records, kmax)
+        if B != int(shape[0]):
+            raise ValueError("Y and records must hold the same number of signals")
+        if out is None:
+            if isinstance(records, np.ndarray):
+                out = np.empty_like(records)
+            else:
+                import torch
+                out = torch.empty_like(records)
+        op, Bo = self._records_arg(out, kmax)
+        if Bo != B:
+            raise ValueError("out and records must hold the same number of signals")
+        if hasattr(Y, "data_ptr") and getattr(Y, "is_cuda", False):
+            import torch
+            status = torch.empty(B, dtype=torch.int32, device=Y.device)
+            resnorm = torch.empty(B, dtype=torch.float64, device=Y.device) if residuals else None
+            sp, np_ = status.data_ptr(), (resnorm.data_ptr() if residuals else None)
+        else:
+            status = np.empty(B, dtype=np.uint32)
+            resnorm = np.empty(B, dtype=np.float64) if residuals else None
+            sp, np_ = status.ctypes.data, (resnorm.ctypes.data if residuals else None)
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(Y, records, out)
+        fn = getattr(lib(), "ss_hip_refit_records_" + self.suffix)
+        self._check(fn(self._h, Yp, B, strides[0] if B else self.m, strides[1] if B else 1, rp, int(kmax), op, np_, sp, err, len(err)), err)
+        return out, resnorm, status
 
     def solve_omp(self, y, tolerance=None, max_iterations=100, out=None):
         """orthogonal matching pursuit on the same device copy -> (x, iter, ||A^T r||_inf)"""
