@@ -370,6 +370,40 @@ int ss_hip_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff
                              double* resnorm, uint32_t* status, char* err, size_t errlen);
 
 /*
+ * The coherence of atoms: for every query atom its largest normalised correlation with any OTHER atom, and which atom that is (added
+ * under ABI version 7; csrc/coherence.hip; NOT in the reference).  cols[S] names the query atoms; cols == NULL means all n (S is
+ * ignored, the outputs have n entries).  A column may be named more than once: the call reads the context and changes nothing.  For
+ * query j = cols[s], with i over the n columns of A,
+ *     dot(i, j) = sum_k a_ki a_kj     products and sums in the context's precision on the matrix cores, one accumulator
+ *     d_i       = sum_k a_ki^2        in double, formed per call from A (nothing is cached on the context: a column replacement needs
+ *                                     no refresh and no stale norm can exist)
+ *     s(i, j)   = |dot(i, j)| * (r_i * r_j),  r_i = 1 / sqrt(d_i), in double
+ *     mu[s]     = max of s(i, j) over i != j, i not excluded (may be NULL); not clipped: it may exceed 1 by rounding
+ *     partner[s] = the smallest i that attains it (may be NULL; mu and partner not both)
+ * Column i is EXCLUDED when d_i is 0 or not finite: it is never a partner, and as a query it returns mu = 0, partner =
+ * SS_HIP_COHERENCE_NONE — as does every query when no other column is left (n == 1).  Exclusion is by index mask.
+ * The queries run in chunks of SS_HIP_COHERENCE_CHUNK against all column tiles (128 x 128 tiles; the workspace holds one (score,
+ * index) partial per query of a chunk and column tile, grown on demand, freed with the context).  cols == NULL forms every (i, j) and
+ * (j, i): twice the flops of the triangular build of G, for one code path.  G is neither read nor written, resident or not.
+ * cols, mu and partner may each be host or device pointers.
+ * ARITHMETIC (one documented order: csrc/coherence.hip): |s - s_float64| <= gamma_m + 1e-12 with
+ * gamma_m = m u / (1 - m u), u = 2^-24 (fp32) or 2^-53 (fp64).
+ * CONTRACT: mu[s] and partner[s] are a function of A and cols[s] alone — bit for bit the same whatever else is in cols, in any
+ * order of cols, for cols == NULL, with host or device pointers, across the query chunking, whatever the context did before.  No
+ * floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  null ctx; mu and partner both null; an IRLS or a column-sharded context; a column >= n in cols
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   S == 0 with cols given: SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_COHERENCE_NONE  0xffffffffu
+#define SS_HIP_COHERENCE_CHUNK 4096      /* queries per internal pass */
+int ss_hip_atom_coherence_f32(ss_hip_ctx* ctx, const uint32_t* cols, size_t S,
+                              double* mu, uint32_t* partner, char* err, size_t errlen);
+int ss_hip_atom_coherence_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S,
+                              double* mu, uint32_t* partner, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the

@@ -61,6 +61,8 @@ HIP_UNITS = [
     ("dictlearn.hip", ["-ffp-contract=off"]),
     # the least-squares refit of compact records: products and sums rounded separately, in the documented order (the tests' bounds)
     ("refit.hip", ["-ffp-contract=off"]),
+    # the coherence of atoms: the norms and the normalisation round products and sums separately, in the documented order (the tests' bound)
+    ("coherence.hip", ["-ffp-contract=off"]),
 ]
 
 

@@ -362,7 +362,8 @@ struct ss_hip_ctx {
     void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
     void* dl = nullptr;           // sship::DictLearnState* (dictlearn.hip): the workspace of the atom update
     void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
-    int dl_chunk_max = 0;         // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
+    void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
+    int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
     size_t m = 0, n = 0;
@@ -504,6 +505,8 @@ void classify_free(ss_hip_ctx* ctx);
 void dictlearn_free(ss_hip_ctx* ctx);
 // the least-squares refit of compact records (refit.hip): releases its workspace
 void refit_free(ss_hip_ctx* ctx);
+// the coherence of atoms (coherence.hip): releases its workspace
+void coherence_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word
 // R[b][0] of that call (NaN for a truncated record).  Y, records, Rn on either side; `who` names the caller in an error's text
 template <typename T>

@@ -43,6 +43,7 @@ SYMBOLS = [
     "ss_hip_homotopy_replace_columns_f32", "ss_hip_homotopy_replace_columns_f64",
     "ss_hip_homotopy_atom_update_f32", "ss_hip_homotopy_atom_update_f64",
     "ss_hip_refit_records_f32", "ss_hip_refit_records_f64",
+    "ss_hip_atom_coherence_f32", "ss_hip_atom_coherence_f64",
 ]
 
 
@@ -197,6 +198,9 @@ def lib():
         f = getattr(L, "ss_hip_refit_records_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, vp, vp, cp, sz]
+        f = getattr(L, "ss_hip_atom_coherence_" + suf)
+        f.restype = ctypes.c_int
+        f.argtypes = [vp, vp, sz, vp, vp, cp, sz]
         f = getattr(L, "ss_hip_gemv_t_" + suf)
         f.restype = ctypes.c_int
         f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
@@ -491,6 +495,124 @@ class Homotopy:
         fn = getattr(lib(), "ss_hip_refit_records_" + self.suffix)
         self._check(fn(self._h, Yp, B, strides[0] if B else self.m, strides[1] if B else 1, rp, int(kmax), op, np_, sp, err, len(err)), err)
         return out, resnorm, status
+
+    # atom_coherence (include/ss_hip.h, SS_HIP_COHERENCE_*): the partner of an atom that has none, the queries per internal pass
+    COHERENCE_NONE = 0xffffffff
+    COHERENCE_CHUNK = 4096
+
+    def atom_coherence(self, cols=None):
+        """The coherence of atoms (include/ss_hip.h, ss_hip_atom_coherence_*): for every atom of `cols` (None = all n) its largest
+        |a_i . a_j| / (||a_i|| ||a_j||) over the OTHER atoms i and the smallest i that attains it -> (mu (S,) float64, partner (S,)).
+        An all-zero (or non-finite) atom is never a partner and returns mu = 0, partner = COHERENCE_NONE.  cols: as for
+        replace_columns, except that an atom may be named more than once.  The outputs live where cols lives: device tensors for
+        a device tensor (partner then int32: COHERENCE_NONE reads as -1), else numpy arrays (partner uint32); numpy for cols=None."""
+        cptr, keepc, S, dev = None, None, self.n, None
+        if cols is not None:
+            if hasattr(cols, "data_ptr"):
+                import torch
+                if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
+                    raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
+                S, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
+                dev = cols.device if getattr(cols, "is_cuda", False) else None
+            else:
+                arr = np.atleast_1d(np.asarray(cols))
+                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                    raise ValueError("cols must be a 1-D integer sequence")
+                if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
+                    raise ValueError("cols must fit in 32 unsigned bits")
+                keepc = np.ascontiguousarray(arr, dtype=np.uint32)
+                S, cptr = int(keepc.shape[0]), keepc.ctypes.data
+        if dev is not None:
+            import torch
+            mu = torch.zeros(S, dtype=torch.float64, device=dev)
+            partner = torch.full((S,), -1, dtype=torch.int32, device=dev)
+            mp, pp = mu.data_ptr(), partner.data_ptr()
+        else:
+            mu = np.zeros(S, dtype=np.float64)
+            partner = np.full(S, self.COHERENCE_NONE, dtype=np.uint32)
+            mp, pp = mu.ctypes.data, partner.ctypes.data
+        err = ctypes.create_string_buffer(512)
+        _sync_producers(cols, mu)
+        fn = getattr(lib(), "ss_hip_atom_coherence_" + self.suffix)
+        self._check(fn(self._h, cptr, S, mp, pp, err, len(err)), err)
+        return mu, partner
+
+    def _record_usage(self, records, kmax):
+        """-> (usage (n,) uint32, K (B,) int64), numpy: the number of counting records (K <= kmax) that hold each column, and every
+        record's K, read from the records' own words (include/ss_hip.h: u32 K, u32 iter, f64 err, u32 idx[kmax], T val[kmax])
+        where the records live"""
+        kmax = int(kmax)
+        if isinstance(records, np.ndarray):
+            w = records.view(np.uint32)
+            K = w[:, 0].astype(np.int64)
+            held = (np.arange(kmax)[None, :] < K[:, None]) & (K <= kmax)[:, None]
+            counts = np.bincount(w[:, 4:4 + kmax][held].astype(np.int64), minlength=self.n)
+        else:
+            import torch
+            w = records.view(torch.int32)
+            K = w[:, 0].long() & 0xffffffff
+            held = (torch.arange(kmax, device=records.device)[None, :] < K[:, None]) & (K <= kmax)[:, None]
+            counts = torch.bincount(w[:, 4:4 + kmax][held].long() & 0xffffffff, minlength=self.n).cpu().numpy()
+            K = K.cpu().numpy()
+        if counts.shape[0] != self.n:
+            raise ValueError("a record holds a column index >= n")
+        return counts.astype(np.uint32), K
+
+    def prune_atoms(self, Y, records, kmax, mu_max=0.99, min_users=1, apply=True):
+        """The clearing step of a dictionary-learning loop: atoms nobody uses and the lesser atom of a near-duplicate pair are
+        replaced by the signals the dictionary represents worst -> (cols, donors, mu, partner, usage), all numpy: the condemned
+        atoms in ascending order (uint32), the signal each one took (int64), and for all n atoms the coherence (atom_coherence)
+        and the usage.  A composition of device calls; Y (B, m) and `records` (solve_batch_compact, same kmax) on either side.
+          usage[j]   the number of counting signals (K_b <= kmax) whose record holds j: atom_update's usage & 0x7fffffff
+          condemned  usage[j] < min_users, or mu[j] > mu_max and j is the lesser of j and p = partner[j]: usage[j] < usage[p], or
+                     equal usage and j > p.  Each atom looks only at its OWN partner, so a chain j -> p -> q can condemn both j
+                     and p: the rule over-prunes rather than loops
+          donors     the counting signals with ||y_b||_2 > 0 by descending ||y_b - A x_b||_2 (reconstruct_records, the difference
+                     and its norm in float64), ties by ascending b; the t-th condemned atom takes the t-th donor, and the atoms
+                     left over when the donors run out are dropped from `cols` and left alone
+          new atom   y_b / ||y_b||_2 in float64, rounded once to the matrix dtype
+        apply=True writes them into the context with replace_columns."""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        rp, B = self._records_arg(records, kmax)
+        if B != int(shape[0]):
+            raise ValueError("Y and records must hold the same number of signals")
+        usage, K = self._record_usage(records, kmax)
+        mu, partner = self.atom_coherence(None)
+        j = np.arange(self.n, dtype=np.int64)
+        p = np.where(partner == self.COHERENCE_NONE, j, partner.astype(np.int64))      # (no partner: mu = 0 never exceeds mu_max >= 0)
+        u = usage.astype(np.int64)
+        lesser = (partner != self.COHERENCE_NONE) & ((u < u[p]) | ((u == u[p]) & (j > p)))
+        cols = np.nonzero((u < int(min_users)) | ((mu > float(mu_max)) & lesser))[0]
+        # the donors: the norms where Y lives, the B of them ranked on the host
+        on_dev = hasattr(Y, "data_ptr")
+        if on_dev:
+            import torch
+            Yhat = self.reconstruct_records(records, kmax, out=torch.empty((B, self.m), dtype=Y.dtype, device=Y.device))
+            Y64 = Y.double()
+            rn = torch.sqrt(((Y64 - Yhat.double()) ** 2).sum(dim=1)).cpu().numpy()
+            yn = torch.sqrt((Y64 ** 2).sum(dim=1))
+            yn_h = yn.cpu().numpy()
+        else:
+            Yhat = self.reconstruct_records(records, kmax)
+            Y64 = np.asarray(Y, dtype=np.float64)
+            rn = np.sqrt(((Y64 - Yhat.astype(np.float64)) ** 2).sum(axis=1))
+            yn_h = yn = np.sqrt((Y64 ** 2).sum(axis=1))
+        ok = np.nonzero((K <= int(kmax)) & (yn_h > 0.0))[0]
+        ranked = ok[np.argsort(-rn[ok], kind="stable")]
+        take = min(len(cols), len(ranked))
+        cols = cols[:take].astype(np.uint32)
+        donors = ranked[:take].astype(np.int64)
+        if apply and take:
+            if on_dev:
+                import torch
+                d = torch.as_tensor(donors, device=Y.device)
+                V = (Y64[d] / yn[d][:, None]).to(Y.dtype).t()                            # (m, S), columns contiguous
+            else:
+                V = (Y64[donors] / yn[donors][:, None]).astype(self.dtype).T
+            self.replace_columns(cols, V)
+        return cols, donors, mu, partner, usage
 
     def solve_omp(self, y, tolerance=None, max_iterations=100, out=None):
         """orthogonal matching pursuit on the same device copy -> (x, iter, ||A^T r||_inf)"""
