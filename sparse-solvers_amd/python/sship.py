@@ -18,35 +18,6 @@ import _hip_runtime
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libss_hip.so")
 
-# every symbol include/ss_hip.h declares
-SYMBOLS = [
-    "ss_hip_device_count", "ss_hip_version",
-    "ss_hip_homotopy_create_f32", "ss_hip_homotopy_create_f64", "ss_hip_homotopy_destroy",
-    "ss_hip_homotopy_solve_f32", "ss_hip_homotopy_solve_f64",
-    "ss_hip_omp_solve_f32", "ss_hip_omp_solve_f64",
-    "ss_hip_homotopy_solve_batch_f32", "ss_hip_homotopy_solve_batch_f64",
-    "ss_hip_record_bytes", "ss_hip_homotopy_solve_batch_compact_f32", "ss_hip_homotopy_solve_batch_compact_f64",
-    "ss_hip_omp_solve_batch_f32", "ss_hip_omp_solve_batch_f64",
-    "ss_hip_omp_solve_batch_compact_f32", "ss_hip_omp_solve_batch_compact_f64",
-    "ss_hip_gemv_t_f32", "ss_hip_gemv_t_f64", "ss_hip_gemm_t_f32", "ss_hip_gram_cols_f32", "ss_hip_gram_cols_f64",
-    "ss_hip_subset_gram_f32", "ss_hip_gram_cols_wide_f32", "ss_hip_gram_cols_wide_f64", "ss_hip_gram_full_rows_f32",
-    "ss_hip_reconstruct_f32", "ss_hip_reconstruct_f64", "ss_hip_norm_l1_f32", "ss_hip_norm_l1_f64",
-    "ss_hip_set_profiling", "ss_hip_get_stats", "ss_hip_reset_stats",
-    "ss_hip_set_option", "ss_hip_get_option", "ss_hip_get_trace", "ss_hip_ctx_info",
-    "ss_hip_irls_create_f32", "ss_hip_irls_create_f64", "ss_hip_irls_solve_f32", "ss_hip_irls_solve_f64",
-    "ss_hip_irls_destroy", "ss_hip_irls_solve_batch_f32", "ss_hip_irls_solve_batch_f64",
-    "ss_hip_comm_unique_id", "ss_hip_homotopy_colshard_create_f32", "ss_hip_homotopy_colshard_solve_f32",
-    "ss_hip_homotopy_colshard_create_f64", "ss_hip_homotopy_colshard_solve_f64",
-    "ss_hip_set_classes", "ss_hip_reconstruct_records_f32", "ss_hip_reconstruct_records_f64",
-    "ss_hip_class_residuals_f32", "ss_hip_class_residuals_f64",
-    "ss_hip_homotopy_classify_batch_f32", "ss_hip_homotopy_classify_batch_f64",
-    "ss_hip_homotopy_replace_columns_f32", "ss_hip_homotopy_replace_columns_f64",
-    "ss_hip_homotopy_atom_update_f32", "ss_hip_homotopy_atom_update_f64",
-    "ss_hip_refit_records_f32", "ss_hip_refit_records_f64",
-    "ss_hip_atom_coherence_f32", "ss_hip_atom_coherence_f64",
-]
-
-
 COMM_ID_BYTES = 128
 _CB_U64 = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t)
 _CB_F32 = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t)
@@ -139,6 +110,84 @@ class Stats(ctypes.Structure):
     ]
 
 
+# ---- the prototypes of include/ss_hip.h, each stated once ----------------------------------------------------------------------
+
+_vp, _sz, _pd, _u32, _cp, _int = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_ssize_t, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int
+_P = ctypes.POINTER
+_T = "T"                            # the element type of a _f32 / _f64 pair
+_ERR = [_cp, _sz]                   # (char* err, size_t errlen) ends every call that reports errors
+_CREATE = [_vp, _sz, _sz, _pd, _pd, _int] + _ERR
+_SOLVE = [_vp, _vp, _pd, _T, _u32, _vp, _pd, _P(_u32), _P(ctypes.c_double)]
+_BATCH = [_vp, _vp, _sz, _pd, _pd, _T, _u32, _vp, _pd, _pd, _vp, _vp]
+_COMPACT = [_vp, _vp, _sz, _pd, _pd, _T, _u32, _u32, _vp] + _ERR
+_MS = [_int, _P(ctypes.c_float)] + _ERR                                    # (int repeats, float* ms_out, err, errlen)
+
+
+def _colshard_create(collectives):
+    return [_vp, _sz, _sz, _pd, _pd, _sz, _sz, _int, _vp, _int, _int, _P(collectives)] + _ERR
+
+
+# (name, restype, argtypes): a name that ends in "_" stands for its _f32 and _f64 entry points, _T in its types for float and double;
+# argtypes None sets none (the two functions without parameters).  A scalar out-parameter the methods pass by ctypes.byref is a
+# POINTER(...), an array whose address they pass is a void pointer.
+_PROTOTYPES = [
+    ("ss_hip_device_count", _int, None),
+    ("ss_hip_version", _cp, None),
+    ("ss_hip_homotopy_create_", _vp, _CREATE),
+    ("ss_hip_homotopy_destroy", None, [_vp]),
+    ("ss_hip_homotopy_solve_", _int, _SOLVE + _ERR),
+    ("ss_hip_omp_solve_", _int, _SOLVE + _ERR),
+    ("ss_hip_homotopy_solve_batch_", _int, _BATCH + _ERR),
+    ("ss_hip_omp_solve_batch_", _int, _BATCH + _ERR),
+    ("ss_hip_record_bytes", _sz, [_u32, _int]),
+    ("ss_hip_homotopy_solve_batch_compact_", _int, _COMPACT),
+    ("ss_hip_omp_solve_batch_compact_", _int, _COMPACT),
+    ("ss_hip_set_classes", _int, [_vp, _vp, _u32] + _ERR),
+    ("ss_hip_reconstruct_records_", _int, [_vp, _vp, _sz, _u32, _vp, _pd, _pd] + _ERR),
+    ("ss_hip_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _pd, _vp, _vp] + _ERR),
+    ("ss_hip_homotopy_classify_batch_", _int, [_vp, _vp, _sz, _pd, _pd, _T, _u32, _u32, _vp, _vp, _pd, _vp, _vp] + _ERR),
+    ("ss_hip_homotopy_replace_columns_", _int, [_vp, _vp, _sz, _vp, _pd, _pd] + _ERR),
+    ("ss_hip_homotopy_atom_update_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _vp, _pd, _pd, _vp, _vp, _u32] + _ERR),
+    ("ss_hip_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_atom_coherence_", _int, [_vp, _vp, _sz, _vp, _vp] + _ERR),
+    ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
+    ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
+    ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
+    ("ss_hip_gram_cols_wide_", _int, [_vp, _vp, _sz, _int, _vp, _pd] + _MS),
+    ("ss_hip_gram_full_rows_f32", _int, [_vp, _vp, _sz, _vp, _pd] + _ERR),
+    ("ss_hip_subset_gram_f32", _int, [_vp, _vp, _vp] + _MS),
+    ("ss_hip_reconstruct_", _int, [_vp, _vp, _vp] + _ERR),
+    ("ss_hip_norm_l1_", _int, [_vp, _sz, _sz, _pd, _pd, _int] + _ERR),
+    ("ss_hip_set_profiling", _int, [_vp, _int]),
+    ("ss_hip_get_stats", _int, [_vp, _P(Stats)]),
+    ("ss_hip_reset_stats", _int, [_vp]),
+    ("ss_hip_set_option", _int, [_vp, _cp, ctypes.c_long]),
+    ("ss_hip_get_option", _int, [_vp, _cp, _P(ctypes.c_long)]),
+    ("ss_hip_get_trace", _int, [_vp, _u32, _vp, _vp, _vp, _vp, _P(_u32)]),
+    ("ss_hip_ctx_info", _int, [_vp, _P(_sz), _P(_sz), _P(_int), _P(_int)]),
+    ("ss_hip_irls_create_", _vp, _CREATE),
+    ("ss_hip_irls_solve_", _int, _SOLVE + [_P(_int)] + _ERR),
+    ("ss_hip_irls_destroy", None, [_vp]),
+    ("ss_hip_irls_solve_batch_", _int, _BATCH + [_vp] + _ERR),
+    ("ss_hip_comm_unique_id", _int, [_vp] + _ERR),
+    ("ss_hip_homotopy_colshard_create_f32", _vp, _colshard_create(Collectives)),
+    ("ss_hip_homotopy_colshard_create_f64", _vp, _colshard_create(Collectives64)),
+    ("ss_hip_homotopy_colshard_solve_", _int, _SOLVE + _ERR),
+]
+
+
+def _expanded():
+    for name, restype, argtypes in _PROTOTYPES:
+        if name.endswith("_"):
+            for suf, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
+                yield name + suf, restype, [ct if a is _T else a for a in argtypes]
+        else:
+            yield name, restype, argtypes
+
+
+_TABLE = list(_expanded())
+SYMBOLS = [name for name, _, _ in _TABLE]           # every symbol include/ss_hip.h declares
+
 _lib = None
 
 
@@ -152,118 +201,36 @@ def lib():
                       "(expected at %s)" % LIB_PATH)
     _hip_runtime.preload()
     L = ctypes.CDLL(LIB_PATH)
-    vp, sz, pd, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_ssize_t, ctypes.c_uint32
-    cp = ctypes.c_char_p
-    L.ss_hip_device_count.restype = ctypes.c_int
-    L.ss_hip_version.restype = ctypes.c_char_p
-    for suf, ct in (("f32", ctypes.c_float), ("f64", ctypes.c_double)):
-        f = getattr(L, "ss_hip_homotopy_create_" + suf)
-        f.restype = vp
-        f.argtypes = [vp, sz, sz, pd, pd, ctypes.c_int, cp, sz]
-        f = getattr(L, "ss_hip_homotopy_solve_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, pd, ct, u32, vp, pd, ctypes.POINTER(u32),
-                      ctypes.POINTER(ctypes.c_double), cp, sz]
-        f = getattr(L, "ss_hip_omp_solve_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, pd, ct, u32, vp, pd, ctypes.POINTER(u32),
-                      ctypes.POINTER(ctypes.c_double), cp, sz]
-        f = getattr(L, "ss_hip_homotopy_solve_batch_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_homotopy_solve_batch_compact_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, cp, sz]
-        f = getattr(L, "ss_hip_omp_solve_batch_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_omp_solve_batch_compact_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, cp, sz]
-        f = getattr(L, "ss_hip_reconstruct_records_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, u32, vp, pd, pd, cp, sz]
-        f = getattr(L, "ss_hip_class_residuals_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, pd, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_homotopy_classify_batch_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, u32, vp, vp, pd, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_homotopy_replace_columns_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, vp, pd, pd, cp, sz]
-        f = getattr(L, "ss_hip_homotopy_atom_update_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, sz, vp, pd, pd, vp, vp, u32, cp, sz]
-        f = getattr(L, "ss_hip_refit_records_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, vp, u32, vp, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_atom_coherence_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_gemv_t_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
-        f = getattr(L, "ss_hip_reconstruct_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, vp, cp, sz]
-        f = getattr(L, "ss_hip_norm_l1_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, sz, sz, pd, pd, ctypes.c_int, cp, sz]
-        f = getattr(L, "ss_hip_irls_create_" + suf)
-        f.restype = vp
-        f.argtypes = [vp, sz, sz, pd, pd, ctypes.c_int, cp, sz]
-        f = getattr(L, "ss_hip_irls_solve_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, pd, ct, u32, vp, pd, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_double),
-                      ctypes.POINTER(ctypes.c_int), cp, sz]
-        f = getattr(L, "ss_hip_irls_solve_batch_" + suf)
-        f.restype = ctypes.c_int
-        f.argtypes = [vp, vp, sz, pd, pd, ct, u32, vp, pd, pd, vp, vp, vp, cp, sz]
-    L.ss_hip_set_classes.restype = ctypes.c_int
-    L.ss_hip_set_classes.argtypes = [vp, vp, u32, cp, sz]
-    L.ss_hip_subset_gram_f32.restype = ctypes.c_int
-    L.ss_hip_subset_gram_f32.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
-    L.ss_hip_record_bytes.restype = sz
-    L.ss_hip_record_bytes.argtypes = [u32, ctypes.c_int]
-    L.ss_hip_gemm_t_f32.restype = ctypes.c_int
-    L.ss_hip_gemm_t_f32.argtypes = [vp, vp, sz, pd, vp, pd, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
-    for nme in ("ss_hip_gram_cols_f32", "ss_hip_gram_cols_f64"):
-        getattr(L, nme).restype = ctypes.c_int
-        getattr(L, nme).argtypes = [vp, vp, sz, vp, pd, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
-    for nme in ("ss_hip_gram_cols_wide_f32", "ss_hip_gram_cols_wide_f64"):
-        getattr(L, nme).restype = ctypes.c_int
-        getattr(L, nme).argtypes = [vp, vp, sz, ctypes.c_int, vp, pd, ctypes.c_int, ctypes.POINTER(ctypes.c_float), cp, sz]
-    L.ss_hip_gram_full_rows_f32.restype = ctypes.c_int
-    L.ss_hip_gram_full_rows_f32.argtypes = [vp, vp, sz, vp, pd, cp, sz]
-    L.ss_hip_homotopy_destroy.restype = None
-    L.ss_hip_homotopy_destroy.argtypes = [vp]
-    L.ss_hip_irls_destroy.restype = None
-    L.ss_hip_irls_destroy.argtypes = [vp]
-    L.ss_hip_set_profiling.argtypes = [vp, ctypes.c_int]
-    L.ss_hip_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
-    L.ss_hip_reset_stats.argtypes = [vp]
-    L.ss_hip_set_option.argtypes = [vp, cp, ctypes.c_long]
-    L.ss_hip_get_option.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_long)]
-    L.ss_hip_get_trace.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.POINTER(u32)]
-    L.ss_hip_ctx_info.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(sz),
-                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    L.ss_hip_comm_unique_id.restype = ctypes.c_int
-    L.ss_hip_comm_unique_id.argtypes = [vp, cp, sz]
-    L.ss_hip_homotopy_colshard_create_f32.restype = vp
-    L.ss_hip_homotopy_colshard_create_f32.argtypes = [vp, sz, sz, pd, pd, sz, sz, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.POINTER(Collectives), cp, sz]
-    L.ss_hip_homotopy_colshard_solve_f32.restype = ctypes.c_int
-    L.ss_hip_homotopy_colshard_solve_f32.argtypes = [vp, vp, pd, ctypes.c_float, u32, vp, pd, ctypes.POINTER(u32),
-                                                     ctypes.POINTER(ctypes.c_double), cp, sz]
-    L.ss_hip_homotopy_colshard_create_f64.restype = vp
-    L.ss_hip_homotopy_colshard_create_f64.argtypes = [vp, sz, sz, pd, pd, sz, sz, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.POINTER(Collectives64), cp, sz]
-    L.ss_hip_homotopy_colshard_solve_f64.restype = ctypes.c_int
-    L.ss_hip_homotopy_colshard_solve_f64.argtypes = [vp, vp, pd, ctypes.c_double, u32, vp, pd, ctypes.POINTER(u32),
-                                                     ctypes.POINTER(ctypes.c_double), cp, sz]
+    for name, restype, argtypes in _TABLE:
+        f = getattr(L, name)
+        f.restype = restype
+        if argtypes is not None:
+            f.argtypes = argtypes
     _lib = L
     return L
+
+
+class SsHipError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__("ss_hip error %d: %s" % (code, msg))
+        self.code = code
+
+
+def _call(fn, *args):
+    """fn(*args, err, errlen): the library call with its message buffer; a status other than 0 raises with the message"""
+    err = ctypes.create_string_buffer(512)
+    rc = fn(*args, err, 512)
+    if rc != 0:
+        raise SsHipError(rc, err.value.decode())
+
+
+def _create(fn, *args):
+    """the same for a function that returns a context: a null handle raises"""
+    err = ctypes.create_string_buffer(512)
+    h = fn(*args, err, len(err))
+    if not h:
+        raise SsHipError(-1, err.value.decode())
+    return h
 
 
 def device_count():
@@ -282,18 +249,8 @@ def norm_l1(A, device=0):
         raise ValueError("A must be 2-D")
     suffix, _ = _suffix(dt)
     _sync_producers(A)
-    err = ctypes.create_string_buffer(512)
-    rc = getattr(lib(), "ss_hip_norm_l1_" + suffix)(ptr, int(shape[0]), int(shape[1]), strides[0], strides[1], device,
-                                                     err, len(err))
-    if rc != 0:
-        raise SsHipError(rc, err.value.decode())
+    _call(getattr(lib(), "ss_hip_norm_l1_" + suffix), ptr, int(shape[0]), int(shape[1]), strides[0], strides[1], device)
     return A
-
-
-class SsHipError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__("ss_hip error %d: %s" % (code, msg))
-        self.code = code
 
 
 def _describe(a):
@@ -327,27 +284,84 @@ def _suffix(dt):
     raise TypeError("only float32 / float64 are supported, got %s" % dt)
 
 
-class Homotopy:
-    """A device-resident copy of the sensing matrix + the solver loop (one HIP stream)."""
+# ---- argument helpers: each thing the methods do to an argument, stated once ---------------------------------------------------
 
-    def __init__(self, A, device=0):
-        ptr, shape, strides, dt, keep = _describe(A)
-        if len(shape) != 2:
-            raise ValueError("A must be 2-D")
-        _sync_producers(A)
-        self.suffix, self.ctype = _suffix(dt)
-        self.dtype = dt
-        self.m, self.n = int(shape[0]), int(shape[1])
-        self.num_classes = 0               # set_classes
-        err = ctypes.create_string_buffer(512)
-        fn = getattr(lib(), "ss_hip_homotopy_create_" + self.suffix)
-        self._h = fn(ptr, self.m, self.n, strides[0], strides[1], device, err, len(err))
-        if not self._h:
-            raise SsHipError(-1, err.value.decode())
+def _device_of(a):
+    """the torch device of a device tensor, None for a host tensor or a numpy array"""
+    return a.device if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) else None
+
+
+def _default_tolerance(dtype):
+    """mirrors the reference binding (tolerance = eps(T)*10: binding.cpp:94-95)"""
+    return float(np.finfo(dtype).eps) * 10
+
+
+def _index_list(x, noun, scalar=True):
+    """-> (pointer, count, keepalive, device or None) of a list of 32-bit indices: an int32 / uint32 torch tensor on either side as
+    it is, or integers made a contiguous uint32 array.  scalar=True takes a sequence — a scalar names one index and an empty list
+    of any type is a list of none; scalar=False takes an integer array only."""
+    if hasattr(x, "data_ptr"):
+        import torch
+        if x.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or x.dim() != 1 or not x.is_contiguous():
+            raise ValueError("%s must be a contiguous 1-D int32 / uint32 tensor" % noun)
+        return x.data_ptr(), int(x.shape[0]), x, _device_of(x)
+    arr = np.atleast_1d(np.asarray(x)) if scalar else np.asarray(x)
+    if arr.ndim != 1 or ((arr.size or not scalar) and arr.dtype.kind not in "iu"):
+        raise ValueError("%s must be a 1-D integer %s" % (noun, "sequence" if scalar else "array"))
+    if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
+        raise ValueError("%s must fit in 32 unsigned bits" % noun)
+    keep = np.ascontiguousarray(arr, dtype=np.uint32)
+    return keep.ctypes.data, int(keep.shape[0]), keep, None
+
+
+def _records(a, rb, noun="records", B=None, other=None):
+    """-> (pointer, B) of a contiguous (B, rb) uint8 numpy array or torch tensor.  With `B` given it must hold B records: another
+    count is a wrong shape, or, when `other` names the argument that B came from, a disagreement with that argument."""
+    if isinstance(a, np.ndarray):
+        ok = a.dtype == np.uint8 and a.ndim == 2 and a.shape[1] == rb and a.flags.c_contiguous
+        ptr = a.ctypes.data
+    elif hasattr(a, "data_ptr"):
+        import torch
+        ok = a.dtype == torch.uint8 and a.dim() == 2 and a.shape[1] == rb and a.is_contiguous()
+        ptr = a.data_ptr()
+    else:
+        raise TypeError("%s must be a uint8 numpy array or torch tensor" % noun)
+    if ok and B is not None and a.shape[0] != B:
+        if other is not None:
+            raise ValueError("%s and records must hold the same number of signals" % other)
+        ok = False
+    if not ok:
+        raise ValueError("%s must be a contiguous (B, %d) uint8 array" % (noun, rb))
+    return ptr, int(a.shape[0])
+
+
+_TORCH_NAME = {"float32": "float32", "float64": "float64", "uint32": "int32"}
+
+
+def _alloc(dev, shape, dtype, fill=None):
+    """-> (array, pointer): a new array where the caller's data lives — a torch tensor on the device `dev`, a numpy array for None.
+    uint32 words are int32 on a device (0xffffffff reads as -1).  fill=None leaves it uninitialised; shape=None: (None, None)."""
+    if shape is None:
+        return None, None
+    if dev is None:
+        a = np.empty(shape, dtype=dtype) if fill is None else np.full(shape, fill, dtype=dtype)
+        return a, a.ctypes.data
+    import torch
+    tdt = getattr(torch, _TORCH_NAME[np.dtype(dtype).name])
+    if fill is None:
+        a = torch.empty(shape, dtype=tdt, device=dev)
+    else:
+        a = torch.full(shape, np.array(fill, dtype=dtype).view(np.int32).item() if dtype == np.uint32 else fill, dtype=tdt, device=dev)
+    return a, a.data_ptr()
+
+
+class _Context:
+    """what the two kinds of context share: the handle's lifetime, the statistics and options, and the bodies of solve / solve_batch"""
+    _DESTROY = None
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().ss_hip_homotopy_destroy(self._h)
+            getattr(lib(), self._DESTROY)(self._h)
             self._h = None
 
     def __del__(self):
@@ -362,9 +376,128 @@ class Homotopy:
     def __exit__(self, *exc):
         self.close()
 
-    def _check(self, rc, err):
+    def reset_stats(self):
+        lib().ss_hip_reset_stats(self._h)
+
+    def stats(self):
+        s = Stats()
+        lib().ss_hip_get_stats(self._h, ctypes.byref(s))
+        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+
+    def set_option(self, key, value):
+        rc = lib().ss_hip_set_option(self._h, key.encode(), int(value))
         if rc != 0:
-            raise SsHipError(rc, err.value.decode())
+            raise SsHipError(rc, "unknown option %r" % key)
+
+    def get_option(self, key):
+        v = ctypes.c_long(0)
+        rc = lib().ss_hip_get_option(self._h, key.encode(), ctypes.byref(v))
+        if rc != 0:
+            raise SsHipError(rc, "unknown option %r" % key)
+        return int(v.value)
+
+    def _open(self, A, entry, device, sync=True):
+        """the matrix a constructor was given -> the attributes every method reads, and the context.  sync=False: the caller's
+        stream is not waited for (Irls, whose constructor and single solve never did)"""
+        ptr, shape, strides, dt, keep = _describe(A)
+        if len(shape) != 2:
+            raise ValueError("A must be 2-D")
+        if sync:
+            _sync_producers(A)
+        self.suffix, self.ctype = _suffix(dt)
+        self.dtype = dt
+        self.m, self.n = int(shape[0]), int(shape[1])
+        self._h = _create(getattr(lib(), entry + self.suffix), ptr, self.m, self.n, strides[0], strides[1], device)
+
+    def _bad_y(self, ydt):
+        if ydt != self.dtype:
+            raise TypeError("dtype of y (%s) does not match the matrix (%s)" % (ydt, self.dtype))
+        raise ValueError("y must have length m = %d" % self.m)
+
+    def _bad_out(self):
+        raise ValueError("out must be a length-n vector of the matrix dtype")
+
+    def _solve(self, entry, y, tolerance, max_iterations, out, spd=False, shard=False, sync=True):
+        """one signal through `entry` -> (x, iter, solution_error), and the IRLS failure flag with spd=True.  shard=True: a shard
+        without columns passes no pointer (ColumnSharded).  sync: as for _open."""
+        yp, yshape, ystr, ydt, keep = _describe(y)
+        if ydt != self.dtype or len(yshape) != 1 or yshape[0] != self.m:
+            self._bad_y(ydt)
+        if tolerance is None:
+            tolerance = _default_tolerance(self.dtype)
+        if out is None:
+            out = np.empty(self.n, dtype=self.dtype)
+        xp, xshape, xstr, xdt, keepx = _describe(out)
+        if xdt != self.dtype or len(xshape) != 1 or xshape[0] != self.n:
+            self._bad_out()
+        incx = xstr[0]
+        if shard and not self.n:
+            xp, incx = None, 1
+        it = ctypes.c_uint32(0)
+        e = ctypes.c_double(0.0)
+        fn = getattr(lib(), entry + self.suffix)
+        if sync:
+            _sync_producers(y, out)
+        if not spd:
+            _call(fn, self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations), xp, incx, ctypes.byref(it), ctypes.byref(e))
+            return out, int(it.value), float(e.value)
+        flag = ctypes.c_int(0)
+        _call(fn, self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations), xp, incx, ctypes.byref(it), ctypes.byref(e),
+              ctypes.byref(flag))
+        return out, int(it.value), float(e.value), bool(flag.value)
+
+    def _signals(self, Y):
+        """-> (pointer, B, row stride, element stride) of a (B, m) batch of the matrix dtype"""
+        Yp, shape, strides, dt, keep = _describe(Y)
+        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
+            raise ValueError("Y must be (B, m) of the matrix dtype")
+        return Yp, int(shape[0]), strides[0], strides[1]
+
+    def _solve_batch(self, entry, Y, tolerance, max_iterations, out, spd=False):
+        """every row of Y through `entry` -> X (B, n), iters (B,), errors (B,), and the IRLS failure flags with spd=True"""
+        Yp, B, ys, incy = self._signals(Y)
+        if tolerance is None:
+            tolerance = _default_tolerance(self.dtype)
+        X = np.empty((B, self.n), dtype=self.dtype) if out is None else out
+        Xp, xshape, xstr, xdt, keepx = _describe(X)
+        if xdt != self.dtype or tuple(xshape) != (B, self.n):
+            raise ValueError("out must be (B, n) of the matrix dtype")
+        iters = np.zeros(B, dtype=np.uint32)
+        errs = np.zeros(B, dtype=np.float64)
+        outs = (iters.ctypes.data, errs.ctypes.data)
+        if spd:
+            flags = np.zeros(B, dtype=np.intc)
+            outs += (flags.ctypes.data,)
+        _sync_producers(Y, X)
+        _call(getattr(lib(), entry + self.suffix), self._h, Yp, B, ys, incy, self.ctype(tolerance), int(max_iterations),
+              Xp, xstr[0], xstr[1], *outs)
+        return (X, iters, errs, flags.astype(bool)) if spd else (X, iters, errs)
+
+
+class Homotopy(_Context):
+    """A device-resident copy of the sensing matrix + the solver loop (one HIP stream)."""
+    _DESTROY = "ss_hip_homotopy_destroy"
+
+    def __init__(self, A, device=0):
+        self.num_classes = 0               # set_classes
+        self._open(A, "ss_hip_homotopy_create_", device)
+
+    def _fn(self, stem):
+        return getattr(lib(), stem + self.suffix)
+
+    def _signals_with_records(self, Y, records, kmax, contiguous_if_empty=False):
+        """_signals, and the pointer of the batch's compact records, which must hold B signals -> (..., records pointer).
+        contiguous_if_empty: an empty batch passes the strides of a contiguous one (numpy gives an array without elements
+        strides of 0)."""
+        Yp, B, ys, incy = self._signals(Y)
+        rp, _ = _records(records, self.record_bytes(kmax), B=B, other="Y")
+        if contiguous_if_empty and not B:
+            ys, incy = self.m, 1
+        return Yp, B, ys, incy, rp
+
+    def _cols(self, cols):
+        """`cols` of the dictionary tools -> (pointer, S, keepalive, device or None); None = all n columns, no list"""
+        return (None, self.n, None, None) if cols is None else _index_list(cols, "cols")
 
     def replace_columns(self, cols, V):
         """Column cols[s] of the dictionary becomes V[:, s], in place (include/ss_hip.h, ss_hip_homotopy_replace_columns_*): every
@@ -378,26 +511,12 @@ class Homotopy:
             vshape, vstr = (vshape[0], 1), (vstr[0], max(int(vshape[0]), 1) * max(abs(int(vstr[0])), 1))
         if len(vshape) != 2 or vshape[0] != self.m:
             raise ValueError("V must be (m, S) or (m,) with m = %d" % self.m)
-        if hasattr(cols, "data_ptr"):
-            import torch
-            if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
-                raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
-            count, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
-        else:
-            arr = np.atleast_1d(np.asarray(cols))
-            if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-                raise ValueError("cols must be a 1-D integer sequence")
-            if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
-                raise ValueError("cols must fit in 32 unsigned bits")
-            keepc = np.ascontiguousarray(arr, dtype=np.uint32)
-            count, cptr = int(keepc.shape[0]), keepc.ctypes.data
+        cptr, count, keepc, _ = _index_list(cols, "cols")
         if count != int(vshape[1]):
             raise ValueError("cols names %d columns, V holds %d" % (count, int(vshape[1])))
-        err = ctypes.create_string_buffer(512)
         _sync_producers(V)
         _sync_producers(cols)
-        fn = getattr(lib(), "ss_hip_homotopy_replace_columns_" + self.suffix)
-        self._check(fn(self._h, cptr, count, vp_, vstr[0], vstr[1], err, len(err)), err)
+        _call(self._fn("ss_hip_homotopy_replace_columns_"), self._h, cptr, count, vp_, vstr[0], vstr[1])
 
     def atom_update(self, Y, records, kmax, cols=None, apply=True, out=None):
         """The atom step of dictionary learning from compact records (include/ss_hip.h, ss_hip_homotopy_atom_update_*): for every
@@ -407,51 +526,21 @@ class Homotopy:
         x_b||^2 before the update.  apply=True writes the changed atoms into the context as replace_columns does.  V and usage
         live where Y lives (device tensors for a device Y — usage then int32 — else numpy arrays); `out`: an (m, S) array or tensor
         of the matrix dtype on either side that receives V.  cols: as for replace_columns."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        rp, B = self._records_arg(records, kmax)
-        if B != int(shape[0]):
-            raise ValueError("Y and records must hold the same number of signals")
-        cptr, keepc, S = None, None, self.n
-        if cols is not None:
-            if hasattr(cols, "data_ptr"):
-                import torch
-                if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
-                    raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
-                S, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
-            else:
-                arr = np.atleast_1d(np.asarray(cols))
-                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-                    raise ValueError("cols must be a 1-D integer sequence")
-                if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
-                    raise ValueError("cols must fit in 32 unsigned bits")
-                keepc = np.ascontiguousarray(arr, dtype=np.uint32)
-                S, cptr = int(keepc.shape[0]), keepc.ctypes.data
-        on_dev = hasattr(Y, "data_ptr") and getattr(Y, "is_cuda", False)
-        if on_dev:
-            import torch
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            V = torch.empty((S, self.m), dtype=tdt, device=Y.device).t() if out is None else out       # (columns contiguous)
-            usage = torch.zeros(S, dtype=torch.int32, device=Y.device)
-            up = usage.data_ptr()
-        else:
-            V = np.empty((S, self.m), dtype=self.dtype).T if out is None else out
-            usage = np.zeros(S, dtype=np.uint32)
-            up = usage.ctypes.data
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        cptr, S, keepc, _ = self._cols(cols)
+        dev = _device_of(Y)
+        V = _alloc(dev, (S, self.m), self.dtype)[0].T if out is None else out           # (columns contiguous)
+        usage, up = _alloc(dev, (S,), np.uint32, 0)
         vp_, vshape, vstr, vdt, keepv = _describe(V)
         if vdt != self.dtype or tuple(vshape) != (self.m, S):
             raise ValueError("out must be (m, %d) of the matrix dtype" % S)
         obj = ctypes.c_double(0.0)
-        err = ctypes.create_string_buffer(512)
         _sync_producers(Y, records, V)
         _sync_producers(cols)
-        fn = getattr(lib(), "ss_hip_homotopy_atom_update_" + self.suffix)
         # (an empty V has no strides to speak of: S == 0 touches nothing)
         rs_, cs_ = (vstr[0], vstr[1]) if S and self.m > 1 else (max(int(vstr[0]), 1), max(int(vstr[1]), 1))
-        rc = fn(self._h, Yp, B, strides[0] if B else self.m, strides[1] if B else 1, rp, int(kmax), cptr, S, vp_, rs_, cs_, up,
-                ctypes.addressof(obj), 1 if apply else 0, err, len(err))
-        self._check(rc, err)
+        _call(self._fn("ss_hip_homotopy_atom_update_"), self._h, Yp, B, ys, incy, rp, int(kmax), cptr, S, vp_, rs_, cs_, up,
+              ctypes.addressof(obj), 1 if apply else 0)
         return V, usage, float(obj.value)
 
     # status words of refit_records (include/ss_hip.h, SS_HIP_REFIT_*)
@@ -466,34 +555,19 @@ class Homotopy:
         gives with every column in class 0; NaN for a truncated record).  `out`: a contiguous (B, record_bytes) uint8 array or
         tensor on either side that receives the records — `records` itself refits in place; default: a new one where `records`
         lives.  resnorm and status live where Y lives (device tensors for a device Y — status then int32 — else numpy arrays)."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        rp, B = self._records_arg(records, kmax)
-        if B != int(shape[0]):
-            raise ValueError("Y and records must hold the same number of signals")
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
         if out is None:
             if isinstance(records, np.ndarray):
                 out = np.empty_like(records)
             else:
                 import torch
                 out = torch.empty_like(records)
-        op, Bo = self._records_arg(out, kmax)
-        if Bo != B:
-            raise ValueError("out and records must hold the same number of signals")
-        if hasattr(Y, "data_ptr") and getattr(Y, "is_cuda", False):
-            import torch
-            status = torch.empty(B, dtype=torch.int32, device=Y.device)
-            resnorm = torch.empty(B, dtype=torch.float64, device=Y.device) if residuals else None
-            sp, np_ = status.data_ptr(), (resnorm.data_ptr() if residuals else None)
-        else:
-            status = np.empty(B, dtype=np.uint32)
-            resnorm = np.empty(B, dtype=np.float64) if residuals else None
-            sp, np_ = status.ctypes.data, (resnorm.ctypes.data if residuals else None)
-        err = ctypes.create_string_buffer(512)
+        op, _ = _records(out, self.record_bytes(kmax), B=B, other="out")
+        dev = _device_of(Y)
+        status, sp = _alloc(dev, (B,), np.uint32)
+        resnorm, np_ = _alloc(dev, (B,) if residuals else None, np.float64)
         _sync_producers(Y, records, out)
-        fn = getattr(lib(), "ss_hip_refit_records_" + self.suffix)
-        self._check(fn(self._h, Yp, B, strides[0] if B else self.m, strides[1] if B else 1, rp, int(kmax), op, np_, sp, err, len(err)), err)
+        _call(self._fn("ss_hip_refit_records_"), self._h, Yp, B, ys, incy, rp, int(kmax), op, np_, sp)
         return out, resnorm, status
 
     # atom_coherence (include/ss_hip.h, SS_HIP_COHERENCE_*): the partner of an atom that has none, the queries per internal pass
@@ -506,35 +580,11 @@ class Homotopy:
         An all-zero (or non-finite) atom is never a partner and returns mu = 0, partner = COHERENCE_NONE.  cols: as for
         replace_columns, except that an atom may be named more than once.  The outputs live where cols lives: device tensors for
         a device tensor (partner then int32: COHERENCE_NONE reads as -1), else numpy arrays (partner uint32); numpy for cols=None."""
-        cptr, keepc, S, dev = None, None, self.n, None
-        if cols is not None:
-            if hasattr(cols, "data_ptr"):
-                import torch
-                if cols.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or cols.dim() != 1 or not cols.is_contiguous():
-                    raise ValueError("cols must be a contiguous 1-D int32 / uint32 tensor")
-                S, cptr, keepc = int(cols.shape[0]), cols.data_ptr(), cols
-                dev = cols.device if getattr(cols, "is_cuda", False) else None
-            else:
-                arr = np.atleast_1d(np.asarray(cols))
-                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-                    raise ValueError("cols must be a 1-D integer sequence")
-                if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
-                    raise ValueError("cols must fit in 32 unsigned bits")
-                keepc = np.ascontiguousarray(arr, dtype=np.uint32)
-                S, cptr = int(keepc.shape[0]), keepc.ctypes.data
-        if dev is not None:
-            import torch
-            mu = torch.zeros(S, dtype=torch.float64, device=dev)
-            partner = torch.full((S,), -1, dtype=torch.int32, device=dev)
-            mp, pp = mu.data_ptr(), partner.data_ptr()
-        else:
-            mu = np.zeros(S, dtype=np.float64)
-            partner = np.full(S, self.COHERENCE_NONE, dtype=np.uint32)
-            mp, pp = mu.ctypes.data, partner.ctypes.data
-        err = ctypes.create_string_buffer(512)
+        cptr, S, keepc, dev = self._cols(cols)
+        mu, mp = _alloc(dev, (S,), np.float64, 0.0)
+        partner, pp = _alloc(dev, (S,), np.uint32, self.COHERENCE_NONE)
         _sync_producers(cols, mu)
-        fn = getattr(lib(), "ss_hip_atom_coherence_" + self.suffix)
-        self._check(fn(self._h, cptr, S, mp, pp, err, len(err)), err)
+        _call(self._fn("ss_hip_atom_coherence_"), self._h, cptr, S, mp, pp)
         return mu, partner
 
     def _record_usage(self, records, kmax):
@@ -572,12 +622,7 @@ class Homotopy:
                      left over when the donors run out are dropped from `cols` and left alone
           new atom   y_b / ||y_b||_2 in float64, rounded once to the matrix dtype
         apply=True writes them into the context with replace_columns."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        rp, B = self._records_arg(records, kmax)
-        if B != int(shape[0]):
-            raise ValueError("Y and records must hold the same number of signals")
+        B = self._signals_with_records(Y, records, kmax)[1]
         usage, K = self._record_usage(records, kmax)
         mu, partner = self.atom_coherence(None)
         j = np.arange(self.n, dtype=np.int64)
@@ -621,27 +666,7 @@ class Homotopy:
     def solve(self, y, tolerance=None, max_iterations=100, out=None, _entry="ss_hip_homotopy_solve_"):
         """-> (x, iter, solution_error); defaults mirror the reference binding
         (tolerance = eps(T)*10, max_iterations = 100: binding.cpp:94-95)."""
-        yp, yshape, ystr, ydt, keep = _describe(y)
-        if ydt != self.dtype:
-            raise TypeError("dtype of y (%s) does not match the matrix (%s)" % (ydt, self.dtype))
-        if len(yshape) != 1 or yshape[0] != self.m:
-            raise ValueError("y must have length m = %d" % self.m)
-        if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        if out is None:
-            out = np.empty(self.n, dtype=self.dtype)
-        xp, xshape, xstr, xdt, keepx = _describe(out)
-        if xdt != self.dtype or len(xshape) != 1 or xshape[0] != self.n:
-            raise ValueError("out must be a length-n vector of the matrix dtype")
-        it = ctypes.c_uint32(0)
-        e = ctypes.c_double(0.0)
-        err = ctypes.create_string_buffer(512)
-        _sync_producers(y, out)
-        fn = getattr(lib(), _entry + self.suffix)
-        rc = fn(self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations), xp, xstr[0],
-                ctypes.byref(it), ctypes.byref(e), err, len(err))
-        self._check(rc, err)
-        return out, int(it.value), float(e.value)
+        return self._solve(_entry, y, tolerance, max_iterations, out)
 
     def solve_omp_batch(self, Y, tolerance=None, max_iterations=100, out=None):
         """OMP for every row of Y: (B, m) -> X (B, n), iters (B,), errors (B,); each row's result is solve_omp's for it
@@ -654,25 +679,7 @@ class Homotopy:
 
     def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None, _entry="ss_hip_homotopy_solve_batch_"):
         """Y: (B, m) -> X (B, n), iters (B,), errors (B,); Y / out may live on the device"""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        B = int(shape[0])
-        if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        X = np.empty((B, self.n), dtype=self.dtype) if out is None else out
-        Xp, xshape, xstr, xdt, keepx = _describe(X)
-        if xdt != self.dtype or tuple(xshape) != (B, self.n):
-            raise ValueError("out must be (B, n) of the matrix dtype")
-        iters = np.zeros(B, dtype=np.uint32)
-        errs = np.zeros(B, dtype=np.float64)
-        err = ctypes.create_string_buffer(512)
-        _sync_producers(Y, X)
-        fn = getattr(lib(), _entry + self.suffix)
-        rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations),
-                Xp, xstr[0], xstr[1], iters.ctypes.data, errs.ctypes.data, err, len(err))
-        self._check(rc, err)
-        return X, iters, errs
+        return self._solve_batch(_entry, Y, tolerance, max_iterations, out)
 
     def record_bytes(self, kmax):
         return int(lib().ss_hip_record_bytes(int(kmax), 1 if self.dtype == np.float64 else 0))
@@ -682,30 +689,15 @@ class Homotopy:
         """Y: (B, m) -> records (B, record_bytes) uint8: {u32 K, u32 iter, f64 err, u32 idx[kmax], T val[kmax]}
         per signal (include/ss_hip.h), packed on the device.  `out`: a uint8 numpy array or torch tensor
         (host or device) of that shape; default a numpy array.  Decode with sharding.unpack_records."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        B = int(shape[0])
+        Yp, B, ys, incy = self._signals(Y)
         if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
+            tolerance = _default_tolerance(self.dtype)
         rb = self.record_bytes(kmax)
         if out is None:
             out = np.empty((B, rb), dtype=np.uint8)
-        if isinstance(out, np.ndarray):
-            ok = out.dtype == np.uint8 and out.shape == (B, rb) and out.flags.c_contiguous
-            rp = out.ctypes.data
-        else:
-            import torch
-            ok = out.dtype == torch.uint8 and tuple(out.shape) == (B, rb) and out.is_contiguous()
-            rp = out.data_ptr()
-        if not ok:
-            raise ValueError("out must be a contiguous (B, %d) uint8 array" % rb)
-        err = ctypes.create_string_buffer(512)
+        rp, _ = _records(out, rb, "out", B=B)
         _sync_producers(Y, out)
-        fn = getattr(lib(), _entry + self.suffix)
-        rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations), int(kmax),
-                rp, err, len(err))
-        self._check(rc, err)
+        _call(self._fn(_entry), self._h, Yp, B, ys, incy, self.ctype(tolerance), int(max_iterations), int(kmax), rp)
         return out
 
     # ---- classification from compact records (include/ss_hip.h, csrc/classify.hip) ----------------------------------------
@@ -713,117 +705,65 @@ class Homotopy:
     def set_classes(self, labels, num_classes=None):
         """class of every dictionary column: `labels` (n,) integers below num_classes (default max + 1); a numpy array or an
         int32 / uint32 torch tensor on either side.  May be called again; never changes what a solve returns."""
-        if hasattr(labels, "data_ptr"):
-            import torch
-            if labels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or labels.dim() != 1 or not labels.is_contiguous():
-                raise ValueError("labels must be a contiguous 1-D int32 / uint32 tensor")
-            count, lp, keep = int(labels.shape[0]), labels.data_ptr(), labels
-            if num_classes is None:
-                num_classes = int(labels.max().item()) + 1 if count else 1
-        else:
-            arr = np.asarray(labels)
-            if arr.ndim != 1 or arr.dtype.kind not in "iu":
-                raise ValueError("labels must be a 1-D integer array")
-            if arr.size and (arr.min() < 0 or arr.max() > 0xffffffff):
-                raise ValueError("labels must fit in 32 unsigned bits")
-            keep = np.ascontiguousarray(arr, dtype=np.uint32)
-            count, lp = int(keep.shape[0]), keep.ctypes.data
-            if num_classes is None:
-                num_classes = int(keep.max()) + 1 if count else 1
+        lp, count, keep, _ = _index_list(labels, "labels", scalar=False)
+        if num_classes is None:
+            num_classes = int(keep.max()) + 1 if count else 1
         if count != self.n:
             raise ValueError("labels must have one entry per column (n = %d)" % self.n)
-        err = ctypes.create_string_buffer(512)
         _sync_producers(labels)
-        self._check(lib().ss_hip_set_classes(self._h, lp, int(num_classes), err, len(err)), err)
+        _call(lib().ss_hip_set_classes, self._h, lp, int(num_classes))
         self.num_classes = int(num_classes)
-
-    def _records_arg(self, records, kmax):
-        """-> (pointer, B) of a contiguous (B, record_bytes) uint8 numpy array or torch tensor"""
-        rb = self.record_bytes(kmax)
-        if isinstance(records, np.ndarray):
-            ok = records.dtype == np.uint8 and records.ndim == 2 and records.shape[1] == rb and records.flags.c_contiguous
-            rp = records.ctypes.data
-        elif hasattr(records, "data_ptr"):
-            import torch
-            ok = records.dtype == torch.uint8 and records.dim() == 2 and records.shape[1] == rb and records.is_contiguous()
-            rp = records.data_ptr()
-        else:
-            raise TypeError("records must be a uint8 numpy array or torch tensor")
-        if not ok:
-            raise ValueError("records must be a contiguous (B, %d) uint8 array" % rb)
-        return rp, int(records.shape[0])
 
     def reconstruct_records(self, records, kmax, out=None):
         """Yhat (B, m) = A x_b for the compact records of solve_batch_compact (same kmax); `out`: a (B, m) array or tensor of the
         matrix dtype on either side (default a numpy array)"""
-        rp, B = self._records_arg(records, kmax)
+        rp, B = _records(records, self.record_bytes(kmax))
         if out is None:
             out = np.empty((B, self.m), dtype=self.dtype)
         op, oshape, ostr, odt, keep = _describe(out)
         if odt != self.dtype or tuple(oshape) != (B, self.m):
             raise ValueError("out must be (B, m) of the matrix dtype")
-        err = ctypes.create_string_buffer(512)
         _sync_producers(records, out)
-        fn = getattr(lib(), "ss_hip_reconstruct_records_" + self.suffix)
-        self._check(fn(self._h, rp, B, int(kmax), op, ostr[0] if B else self.m, ostr[1] if B else 1, err, len(err)), err)
+        _call(self._fn("ss_hip_reconstruct_records_"), self._h, rp, B, int(kmax), op, ostr[0] if B else self.m, ostr[1] if B else 1)
         return out
 
     def _class_outputs(self, B, residuals, like):
-        """best, sci and R (or None) where `like` lives: torch tensors on its device, else numpy arrays"""
+        """-> ((best, sci, R or None), (R pointer, num_classes, best pointer, sci pointer)): the outputs where `like` lives, and
+        the words the library takes for them"""
         C = self.num_classes or 1          # (without classes the library reports the error)
-        if hasattr(like, "data_ptr") and getattr(like, "is_cuda", False):
-            import torch
-            tdt = torch.float32 if self.dtype == np.float32 else torch.float64
-            best = torch.empty(B, dtype=torch.int32, device=like.device)      # (the words are uint32: 0xffffffff reads as -1)
-            sci = torch.empty(B, dtype=torch.float64, device=like.device)
-            R = torch.empty((B, C), dtype=tdt, device=like.device) if residuals else None
-            return best, sci, R, best.data_ptr(), sci.data_ptr(), (R.data_ptr() if residuals else None)
-        best = np.empty(B, dtype=np.uint32)
-        sci = np.empty(B, dtype=np.float64)
-        R = np.empty((B, C), dtype=self.dtype) if residuals else None
-        return best, sci, R, best.ctypes.data, sci.ctypes.data, (R.ctypes.data if residuals else None)
+        dev = _device_of(like)
+        best, bp = _alloc(dev, (B,), np.uint32)
+        sci, sp = _alloc(dev, (B,), np.float64)
+        R, Rp = _alloc(dev, (B, C) if residuals else None, self.dtype)
+        return (best, sci, R), (Rp, C, bp, sp)
 
     def class_residuals(self, Y, records, kmax, residuals=True):
         """-> (best (B,), sci (B,) float64, R (B, num_classes) or None): R[b, c] = ||y_b - A delta_c(x_b)||_2 from the compact
         records, best = its left-most arg-min (uint32; 0xffffffff for a truncated record), sci the sparsity concentration
         index.  The outputs live where Y lives (device tensors for a device Y — best then int32 — else numpy arrays)."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        rp, B = self._records_arg(records, kmax)
-        if B != int(shape[0]):
-            raise ValueError("Y and records must hold the same number of signals")
-        best, sci, R, bp, sp, Rp = self._class_outputs(B, residuals, Y)
-        err = ctypes.create_string_buffer(512)
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax)
+        outs, words = self._class_outputs(B, residuals, Y)
         _sync_producers(Y, records)
-        fn = getattr(lib(), "ss_hip_class_residuals_" + self.suffix)
-        self._check(fn(self._h, Yp, B, strides[0], strides[1], rp, int(kmax), Rp, self.num_classes or 1, bp, sp, err, len(err)), err)
-        return best, sci, R
+        _call(self._fn("ss_hip_class_residuals_"), self._h, Yp, B, ys, incy, rp, int(kmax), *words)
+        return outs
 
     def classify(self, Y, tolerance=None, max_iterations=100, kmax=96, residuals=True, records=None):
         """solve_batch_compact + class_residuals without leaving the device -> (best, sci, R or None, records).  `records`: a
         contiguous (B, record_bytes) uint8 array or tensor that receives the records, True for a new numpy array, None to
         leave them in the context (returned as None)."""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        B = int(shape[0])
+        Yp, B, ys, incy = self._signals(Y)
         if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        rp = None
+            tolerance = _default_tolerance(self.dtype)
         if records is True:
             records = np.empty((B, self.record_bytes(kmax)), dtype=np.uint8)
+        rp = None
         if records is not None:
-            rp, Br = self._records_arg(records, kmax)
-            if Br != B:
-                raise ValueError("Y and records must hold the same number of signals")
-        best, sci, R, bp, sp, Rp = self._class_outputs(B, residuals, Y)
-        err = ctypes.create_string_buffer(512)
+            rp, _ = _records(records, self.record_bytes(kmax), B=B, other="Y")
+        outs, words = self._class_outputs(B, residuals, Y)
         _sync_producers(Y, records)
-        fn = getattr(lib(), "ss_hip_homotopy_classify_batch_" + self.suffix)
-        self._check(fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations), int(kmax), rp,
-                       Rp, self.num_classes or 1, bp, sp, err, len(err)), err)
-        return best, sci, R, records
+        _call(self._fn("ss_hip_homotopy_classify_batch_"), self._h, Yp, B, ys, incy, self.ctype(tolerance), int(max_iterations),
+              int(kmax), rp, *words)
+        return outs + (records,)
 
     def gemv_t(self, r, repeats=1, out=None):
         """c = A^T r on the device copy -> (c, mean kernel ms); `out` (host array or device tensor, length n) receives c"""
@@ -835,10 +775,8 @@ class Homotopy:
         if cdt != self.dtype or len(cshape) != 1 or cshape[0] != self.n or cstrides[0] != 1:
             raise ValueError("out must be a contiguous length-n vector of the matrix dtype")
         ms = ctypes.c_float(0.0)
-        err = ctypes.create_string_buffer(512)
         _sync_producers(r, c)
-        fn = getattr(lib(), "ss_hip_gemv_t_" + self.suffix)
-        self._check(fn(self._h, rp, cp, int(repeats), ctypes.byref(ms), err, len(err)), err)
+        _call(self._fn("ss_hip_gemv_t_"), self._h, rp, cp, int(repeats), ctypes.byref(ms))
         return c, float(ms.value)
 
     def gemm_t(self, R, repeats=1, out=None):
@@ -853,9 +791,7 @@ class Homotopy:
         if cdt != np.float32 or tuple(cshape) != (B, self.n) or cstr[1] != 1:
             raise ValueError("out must be (B, n) float32 with contiguous rows")
         ms = ctypes.c_float(0.0)
-        err = ctypes.create_string_buffer(512)
-        self._check(lib().ss_hip_gemm_t_f32(self._h, Rp, B, strides[0], Cp, cstr[0], int(repeats),
-                                            ctypes.byref(ms), err, len(err)), err)
+        _call(lib().ss_hip_gemm_t_f32, self._h, Rp, B, strides[0], Cp, cstr[0], int(repeats), ctypes.byref(ms))
         return out, float(ms.value)
 
     def gram_cols(self, cols, repeats=1, tier=0, wide=None):
@@ -865,23 +801,21 @@ class Homotopy:
         cols = np.ascontiguousarray(cols, dtype=np.uint32)
         G = np.empty((len(cols), self.n), dtype=self.dtype)
         ms = ctypes.c_float(0.0)
-        err = ctypes.create_string_buffer(512)
         if wide is None:
             wide = len(cols) > 32 or int(tier) != 0
         if wide:
-            self._check(getattr(lib(), "ss_hip_gram_cols_wide_" + self.suffix)(self._h, cols.ctypes.data, len(cols), int(tier), G.ctypes.data,
-                                                                             self.n, int(repeats), ctypes.byref(ms), err, len(err)), err)
+            _call(self._fn("ss_hip_gram_cols_wide_"), self._h, cols.ctypes.data, len(cols), int(tier), G.ctypes.data, self.n,
+                  int(repeats), ctypes.byref(ms))
         else:
-            self._check(getattr(lib(), "ss_hip_gram_cols_" + self.suffix)(self._h, cols.ctypes.data, len(cols), G.ctypes.data, self.n,
-                                                                        int(repeats), ctypes.byref(ms), err, len(err)), err)
+            _call(self._fn("ss_hip_gram_cols_"), self._h, cols.ctypes.data, len(cols), G.ctypes.data, self.n, int(repeats),
+                  ctypes.byref(ms))
         return G, float(ms.value)
 
     def gram_rows(self, rows):
         """rows of the context's G = A^T A (formed on first use: options gram_full_gib, gram_symmetric) -> (len(rows), n) float32"""
         rows = np.ascontiguousarray(rows, dtype=np.uint32)
         out = np.empty((len(rows), self.n), dtype=np.float32)
-        err = ctypes.create_string_buffer(512)
-        self._check(lib().ss_hip_gram_full_rows_f32(self._h, rows.ctypes.data, len(rows), out.ctypes.data, self.n, err, len(err)), err)
+        _call(lib().ss_hip_gram_full_rows_f32, self._h, rows.ctypes.data, len(rows), out.ctypes.data, self.n)
         return out
 
     def subset_gram(self, cols, repeats=1):
@@ -891,8 +825,7 @@ class Homotopy:
             raise ValueError("cols must hold 256 column indices")
         G = np.empty((256, 256), dtype=np.float32)
         ms = ctypes.c_float(0.0)
-        err = ctypes.create_string_buffer(512)
-        self._check(lib().ss_hip_subset_gram_f32(self._h, cols.ctypes.data, G.ctypes.data, int(repeats), ctypes.byref(ms), err, len(err)), err)
+        _call(lib().ss_hip_subset_gram_f32, self._h, cols.ctypes.data, G.ctypes.data, int(repeats), ctypes.byref(ms))
         return G, float(ms.value)
 
     def reconstruct(self, x):
@@ -901,21 +834,11 @@ class Homotopy:
         if dt != self.dtype or len(shape) != 1 or shape[0] != self.n or strides[0] != 1:
             raise ValueError("x must be a contiguous length-n vector of the matrix dtype")
         y = np.empty(self.m, dtype=self.dtype)
-        err = ctypes.create_string_buffer(512)
-        fn = getattr(lib(), "ss_hip_reconstruct_" + self.suffix)
-        self._check(fn(self._h, xp, y.ctypes.data, err, len(err)), err)
+        _call(self._fn("ss_hip_reconstruct_"), self._h, xp, y.ctypes.data)
         return y
 
     def set_profiling(self, on):
         lib().ss_hip_set_profiling(self._h, 1 if on else 0)
-
-    def reset_stats(self):
-        lib().ss_hip_reset_stats(self._h)
-
-    def stats(self):
-        s = Stats()
-        lib().ss_hip_get_stats(self._h, ctypes.byref(s))
-        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
 
     def trace(self):
         """path of the last solve (option "trace" must be on): dict of arrays"""
@@ -931,26 +854,11 @@ class Homotopy:
                                    c_inf.ctypes.data, ctypes.byref(cnt))
         return {"idx": idx, "added": added, "gamma": gamma, "c_inf": c_inf}
 
-    def set_option(self, key, value):
-        rc = lib().ss_hip_set_option(self._h, key.encode(), int(value))
-        if rc != 0:
-            raise SsHipError(rc, "unknown option %r" % key)
-
-    def get_option(self, key):
-        v = ctypes.c_long(0)
-        rc = lib().ss_hip_get_option(self._h, key.encode(), ctypes.byref(v))
-        if rc != 0:
-            raise SsHipError(rc, "unknown option %r" % key)
-        return int(v.value)
-
 
 def comm_unique_id():
     """ncclGetUniqueId through the library (rank 0 calls it and distributes the 128 bytes) -> bytes"""
     buf = ctypes.create_string_buffer(COMM_ID_BYTES)
-    err = ctypes.create_string_buffer(512)
-    rc = lib().ss_hip_comm_unique_id(ctypes.cast(buf, ctypes.c_void_p), err, len(err))
-    if rc != 0:
-        raise SsHipError(rc, err.value.decode())
+    _call(lib().ss_hip_comm_unique_id, ctypes.cast(buf, ctypes.c_void_p))
     return buf.raw
 
 
@@ -995,137 +903,35 @@ class ColumnSharded(Homotopy):
             if len(comm_id) != COMM_ID_BYTES:
                 raise ValueError("comm_id must be %d bytes" % COMM_ID_BYTES)
             idbuf = ctypes.create_string_buffer(bytes(comm_id), COMM_ID_BYTES)
-        err = ctypes.create_string_buffer(512)
         # (an empty shard has no data pointer worth passing)
-        self._h = getattr(lib(), "ss_hip_homotopy_colshard_create_" + self.suffix)(
-            ptr if self.n else None, self.m, self.n, strides[0], strides[1], self.col_lo, self.n_total, device,
-            ctypes.cast(idbuf, ctypes.c_void_p) if idbuf is not None else None, int(rank), int(world), coll_p, err, len(err))
-        if not self._h:
-            raise SsHipError(-1, err.value.decode())
+        self._h = _create(getattr(lib(), "ss_hip_homotopy_colshard_create_" + self.suffix),
+                          ptr if self.n else None, self.m, self.n, strides[0], strides[1], self.col_lo, self.n_total, device,
+                          ctypes.cast(idbuf, ctypes.c_void_p) if idbuf is not None else None, int(rank), int(world), coll_p)
+
+    def _bad_y(self, ydt):
+        raise ValueError("y must be a %s vector of length m = %d" % (np.dtype(self.dtype).name, self.m))
+
+    def _bad_out(self):
+        raise ValueError("out must be a %s vector of the shard's width" % np.dtype(self.dtype).name)
 
     def solve(self, y, tolerance=None, max_iterations=100, out=None):
         """-> (x_local, iter, solution_error): the shard's coefficients"""
-        yp, yshape, ystr, ydt, keep = _describe(y)
-        if ydt != self.dtype or len(yshape) != 1 or yshape[0] != self.m:
-            raise ValueError("y must be a %s vector of length m = %d" % (np.dtype(self.dtype).name, self.m))
-        if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        if out is None:
-            out = np.empty(self.n, dtype=self.dtype)
-        xp, xshape, xstr, xdt, keepx = _describe(out)
-        if xdt != self.dtype or len(xshape) != 1 or xshape[0] != self.n:
-            raise ValueError("out must be a %s vector of the shard's width" % np.dtype(self.dtype).name)
-        it = ctypes.c_uint32(0)
-        e = ctypes.c_double(0.0)
-        err = ctypes.create_string_buffer(512)
-        _sync_producers(y, out)
-        rc = getattr(lib(), "ss_hip_homotopy_colshard_solve_" + self.suffix)(self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations),
-                                                      xp if self.n else None, xstr[0] if self.n else 1, ctypes.byref(it), ctypes.byref(e),
-                                                      err, len(err))
-        self._check(rc, err)
-        return out, int(it.value), float(e.value)
+        return self._solve("ss_hip_homotopy_colshard_solve_", y, tolerance, max_iterations, out, shard=True)
 
 
-class Irls:
+class Irls(_Context):
     """IRLS on the device (the reference's ss::irls<T>): Householder QR of A at construction
     (rows >= columns), the reweighting loop in one launch per solve."""
+    _DESTROY = "ss_hip_irls_destroy"
 
     def __init__(self, A, device=0):
-        ptr, shape, strides, dt, keep = _describe(A)
-        if len(shape) != 2:
-            raise ValueError("A must be 2-D")
-        self.suffix, self.ctype = _suffix(dt)
-        self.dtype = dt
-        self.m, self.n = int(shape[0]), int(shape[1])
-        err = ctypes.create_string_buffer(512)
-        fn = getattr(lib(), "ss_hip_irls_create_" + self.suffix)
-        self._h = fn(ptr, self.m, self.n, strides[0], strides[1], device, err, len(err))
-        if not self._h:
-            raise SsHipError(-1, err.value.decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().ss_hip_irls_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._open(A, "ss_hip_irls_create_", device, sync=False)
 
     def solve(self, y, tolerance=None, max_iterations=100, out=None):
         """-> (x, iter, solution_error, spd_failure); defaults mirror the reference binding (binding.cpp:94-95)"""
-        yp, yshape, ystr, ydt, keep = _describe(y)
-        if ydt != self.dtype:
-            raise TypeError("dtype of y (%s) does not match the matrix (%s)" % (ydt, self.dtype))
-        if len(yshape) != 1 or yshape[0] != self.m:
-            raise ValueError("y must have length m = %d" % self.m)
-        if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        if out is None:
-            out = np.empty(self.n, dtype=self.dtype)
-        xp, xshape, xstr, xdt, keepx = _describe(out)
-        if xdt != self.dtype or len(xshape) != 1 or xshape[0] != self.n:
-            raise ValueError("out must be a length-n vector of the matrix dtype")
-        it = ctypes.c_uint32(0)
-        e = ctypes.c_double(0.0)
-        spd = ctypes.c_int(0)
-        err = ctypes.create_string_buffer(512)
-        fn = getattr(lib(), "ss_hip_irls_solve_" + self.suffix)
-        rc = fn(self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations), xp, xstr[0],
-                ctypes.byref(it), ctypes.byref(e), ctypes.byref(spd), err, len(err))
-        if rc != 0:
-            raise SsHipError(rc, err.value.decode())
-        return out, int(it.value), float(e.value), bool(spd.value)
+        return self._solve("ss_hip_irls_solve_", y, tolerance, max_iterations, out, spd=True, sync=False)
 
     def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None):
         """Y: (B, m) -> X (B, n), iters (B,) uint32, errors (B,) float64, spd (B,) bool; each row's result is solve's for it
         bit for bit (include/ss_hip.h, ss_hip_irls_solve_batch_*); Y / out may live on the device or be strided"""
-        Yp, shape, strides, dt, keep = _describe(Y)
-        if dt != self.dtype or len(shape) != 2 or shape[1] != self.m:
-            raise ValueError("Y must be (B, m) of the matrix dtype")
-        B = int(shape[0])
-        if tolerance is None:
-            tolerance = float(np.finfo(self.dtype).eps) * 10
-        X = np.empty((B, self.n), dtype=self.dtype) if out is None else out
-        Xp, xshape, xstr, xdt, keepx = _describe(X)
-        if xdt != self.dtype or tuple(xshape) != (B, self.n):
-            raise ValueError("out must be (B, n) of the matrix dtype")
-        iters = np.zeros(B, dtype=np.uint32)
-        errs = np.zeros(B, dtype=np.float64)
-        spd = np.zeros(B, dtype=np.intc)
-        err = ctypes.create_string_buffer(512)
-        _sync_producers(Y, X)
-        fn = getattr(lib(), "ss_hip_irls_solve_batch_" + self.suffix)
-        rc = fn(self._h, Yp, B, strides[0], strides[1], self.ctype(tolerance), int(max_iterations),
-                Xp, xstr[0], xstr[1], iters.ctypes.data, errs.ctypes.data, spd.ctypes.data, err, len(err))
-        if rc != 0:
-            raise SsHipError(rc, err.value.decode())
-        return X, iters, errs, spd.astype(bool)
-
-    def reset_stats(self):
-        lib().ss_hip_reset_stats(self._h)
-
-    def stats(self):
-        s = Stats()
-        lib().ss_hip_get_stats(self._h, ctypes.byref(s))
-        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
-
-    def set_option(self, key, value):
-        rc = lib().ss_hip_set_option(self._h, key.encode(), int(value))
-        if rc != 0:
-            raise SsHipError(rc, "unknown option %r" % key)
-
-    def get_option(self, key):
-        v = ctypes.c_long(0)
-        rc = lib().ss_hip_get_option(self._h, key.encode(), ctypes.byref(v))
-        if rc != 0:
-            raise SsHipError(rc, "unknown option %r" % key)
-        return int(v.value)
+        return self._solve_batch("ss_hip_irls_solve_batch_", Y, tolerance, max_iterations, out, spd=True)

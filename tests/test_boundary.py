@@ -12,20 +12,19 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_common
+from abi_common import ROOT
+
 PKG = os.path.join(ROOT, "sparse-solvers_amd")
-sys.path.insert(0, ROOT)
 
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()
-    return True
+    return abi_common.build()
 
 
 def test_c_abi_exports_every_declared_symbol(built):
-    hdr = open(os.path.join(ROOT, "include", "ss_hip.h")).read()
+    hdr = abi_common.header()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(ss_hip_[a-z0-9_]+)\s*\(", hdr))
     assert len(declared) >= 19
@@ -147,3 +146,97 @@ def test_python_mirror_of_the_statistics_struct_matches_the_header():
     mirror = [(n, t) for n, t in sship.Stats._fields_]
     assert [n for _, n in fields] == [n for n, _ in mirror]
     assert [ctype[t] for t, _ in fields] == [t for _, t in mirror]
+
+
+def test_abi_version_and_statistics_did_not_move():
+    hdr = abi_common.header()
+    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", hdr)
+    body = hdr[hdr.index("typedef struct ss_hip_stats"):hdr.index("} ss_hip_stats;")]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    fields = re.findall(r"\b(uint64_t|double|uint32_t|float)\s+([a-z0-9_]+)\s*;", body)
+    assert fields[-2:] == [("uint64_t", "irls_batch_signals"), ("uint64_t", "irls_batch_rounds")]
+    import sship
+    assert [f[0] for f in sship.Stats._fields_[-2:]] == ["irls_batch_signals", "irls_batch_rounds"]
+
+
+# the pointee of a POINTER(...) the binding may set for a C pointer; a struct's is a ctypes.Structure subclass
+POINTEE = dict(abi_common.VALUE, **{"uint8_t": ctypes.c_uint8, "unsigned char": ctypes.c_ubyte})
+# entry points the binding sets no argtypes for, each with its reason
+NO_ARGTYPES = {"ss_hip_device_count": "declared (void): there is nothing to convert",
+               "ss_hip_version": "declared (void): there is nothing to convert"}
+
+
+def _binding_type_matches(c_type, got):
+    """does the ctypes type `got` carry a parameter or return value the header declares as `c_type`"""
+    c_type = re.sub(r"\bconst\s+", "", c_type)
+    if c_type == "void":
+        return got is None
+    if c_type == "char*":
+        return got is ctypes.c_char_p
+    if not c_type.endswith("*"):
+        return got is abi_common.VALUE[c_type]
+    if got is ctypes.c_void_p:
+        return True
+    if not (isinstance(got, type) and issubclass(got, ctypes._Pointer)):
+        return False
+    pointee = c_type[:-1].strip()
+    if pointee in POINTEE:
+        return got._type_ is POINTEE[pointee]
+    return pointee.startswith("ss_hip_") and issubclass(got._type_, ctypes.Structure)
+
+
+def test_binding_types_match_the_header_for_every_entry_point(built):
+    """every function include/ss_hip.h declares against what sship.lib() sets on it: the number of parameters, by-value types and
+    the return type exactly, char* as c_char_p, any other pointer as c_void_p or POINTER of the pointee's ctypes type"""
+    import sship
+    L = sship.lib()
+    declared = abi_common.declarations()
+    assert set(declared) == set(sship.SYMBOLS) and len(declared) >= 65
+    wrong = []
+    for name, (ret, params) in sorted(declared.items()):
+        fn = getattr(L, name)
+        if ret.endswith("*") and ret != "const char*":
+            ret_ok = fn.restype is ctypes.c_void_p
+        else:
+            ret_ok = _binding_type_matches(ret, fn.restype)
+        if not ret_ok:
+            wrong.append((name, "returns", ret, fn.restype))
+        if fn.argtypes is None:
+            if name not in NO_ARGTYPES or params:
+                wrong.append((name, "no argtypes", params))
+            continue
+        assert name not in NO_ARGTYPES, name
+        types = [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in params]
+        if len(fn.argtypes) != len(types):
+            wrong.append((name, "parameter count", len(types), len(fn.argtypes)))
+            continue
+        wrong += [(name, i, t, g) for i, (t, g) in enumerate(zip(types, fn.argtypes)) if not _binding_type_matches(t, g)]
+    assert not wrong, wrong
+
+
+# the out-parameters the methods pass with ctypes.byref, and the structs: {entry point (a trailing _ = both suffixes): {position: pointee}}.
+# Everywhere else a pointer is a c_void_p (an address is passed) or a c_char_p.
+_SOLVE_OUT = {7: ctypes.c_uint32, 8: ctypes.c_double}
+TYPED_POINTERS = {
+    "ss_hip_homotopy_solve_": _SOLVE_OUT, "ss_hip_omp_solve_": _SOLVE_OUT, "ss_hip_homotopy_colshard_solve_": _SOLVE_OUT,
+    "ss_hip_irls_solve_": {7: ctypes.c_uint32, 8: ctypes.c_double, 9: ctypes.c_int},
+    "ss_hip_gemv_t_": {4: ctypes.c_float}, "ss_hip_gemm_t_f32": {7: ctypes.c_float}, "ss_hip_gram_cols_": {6: ctypes.c_float},
+    "ss_hip_gram_cols_wide_": {7: ctypes.c_float}, "ss_hip_subset_gram_f32": {4: ctypes.c_float},
+    "ss_hip_get_stats": {1: "Stats"}, "ss_hip_get_option": {2: ctypes.c_long}, "ss_hip_get_trace": {6: ctypes.c_uint32},
+    "ss_hip_ctx_info": {1: ctypes.c_size_t, 2: ctypes.c_size_t, 3: ctypes.c_int, 4: ctypes.c_int},
+    "ss_hip_homotopy_colshard_create_f32": {11: "Collectives"}, "ss_hip_homotopy_colshard_create_f64": {11: "Collectives64"},
+}
+
+
+def test_which_pointers_are_typed_is_pinned(built):
+    """the whole-header check takes c_void_p for any pointer; which parameters are POINTER(...) instead, and of what, is this literal"""
+    import sship
+    L = sship.lib()
+    want = {}
+    for name, typed in TYPED_POINTERS.items():
+        for full in ([name + "f32", name + "f64"] if name.endswith("_") else [name]):
+            want[full] = {i: getattr(sship, t) if isinstance(t, str) else t for i, t in typed.items()}
+    assert set(want) <= set(sship.SYMBOLS)
+    for name in sship.SYMBOLS:
+        got = {i: t._type_ for i, t in enumerate(getattr(L, name).argtypes or ()) if issubclass(t, ctypes._Pointer)}
+        assert got == want.get(name, {}), (name, got)

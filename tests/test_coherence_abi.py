@@ -1,17 +1,15 @@
 """CPU-only checks of the atom coherence (include/ss_hip.h, ss_hip_atom_coherence_*, added under ABI version 7): the header declares
 both entry points with the agreed prototypes and the two defines, the library exports them, the ctypes binding gives them the header's
-argument types, sship.Homotopy has the two methods and the two constants, neither the ABI version nor the statistics struct moved, no
+argument types, sship.Homotopy has the two methods and the two constants, no
 option key was added, and the kernels are built with separately rounded products and sums.  No compute calls (no GPU here)."""
 import ctypes
 import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "sparse-solvers_amd", "python"))
+import abi_common
+from abi_common import ROOT
 
 _PARAMS = ["ss_hip_ctx*", "const uint32_t*", "size_t", "double*", "uint32_t*", "char*", "size_t"]
 PROTOTYPES = {"ss_hip_atom_coherence_f32": _PARAMS, "ss_hip_atom_coherence_f64": _PARAMS}
@@ -19,37 +17,16 @@ PROTOTYPES = {"ss_hip_atom_coherence_f32": _PARAMS, "ss_hip_atom_coherence_f64":
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()
-    return True
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ss_hip.h")).read()
-
-
-def _prototype(name):
-    """the parameter types of `name` as the header declares them, in order"""
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "%s is not declared" % name
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    return [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in params]
-
-
-_CTYPE = {
-    "ss_hip_ctx*": ctypes.c_void_p, "double*": ctypes.c_void_p, "uint32_t*": ctypes.c_void_p, "const uint32_t*": ctypes.c_void_p,
-    "char*": ctypes.c_char_p, "size_t": ctypes.c_size_t,
-}
+    return abi_common.build()
 
 
 def test_header_declares_both_entry_points():
     for name, want in PROTOTYPES.items():
-        assert _prototype(name) == want, (name, _prototype(name))
+        assert abi_common.prototype(name) == want, (name, abi_common.prototype(name))
 
 
 def test_header_defines_none_and_chunk():
-    hdr = _header()
+    hdr = abi_common.header()
     assert re.search(r"#define\s+SS_HIP_COHERENCE_NONE\s+0xffffffffu\b", hdr)
     assert re.search(r"#define\s+SS_HIP_COHERENCE_CHUNK\s+4096\b", hdr)
 
@@ -66,7 +43,7 @@ def test_binding_argtypes_match_the_header(built):
     import sship
     L = sship.lib()
     for name in PROTOTYPES:
-        want = [_CTYPE[p] for p in _prototype(name)]
+        want = [abi_common.CTYPE[p] for p in abi_common.prototype(name)]
         got = list(getattr(L, name).argtypes)
         assert got == want, (name, got, want)
         assert getattr(L, name).restype == ctypes.c_int
@@ -79,17 +56,6 @@ def test_python_surface_has_the_methods_and_constants():
     assert list(inspect.signature(H.atom_coherence).parameters) == ["self", "cols"]
     assert list(inspect.signature(H.prune_atoms).parameters) == ["self", "Y", "records", "kmax", "mu_max", "min_users", "apply"]
     assert H.COHERENCE_NONE == 0xffffffff and H.COHERENCE_CHUNK == 4096
-
-
-def test_abi_version_and_statistics_did_not_move():
-    hdr = _header()
-    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", hdr)
-    body = hdr[hdr.index("typedef struct ss_hip_stats"):hdr.index("} ss_hip_stats;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"\b(uint64_t|double|uint32_t|float)\s+([a-z0-9_]+)\s*;", body)
-    assert fields[-2:] == [("uint64_t", "irls_batch_signals"), ("uint64_t", "irls_batch_rounds")]
-    import sship
-    assert [f[0] for f in sship.Stats._fields_[-2:]] == ["irls_batch_signals", "irls_batch_rounds"]
 
 
 def test_no_option_key_was_added():

@@ -1,19 +1,17 @@
 """CPU-only checks of the GEMM measurement entry points ss_hip_gram_cols_wide_{f32,f64} and ss_hip_gram_full_rows_f32
 (include/ss_hip.h, added under ABI version 7): the header declares them with the agreed prototypes, the library exports them, the
 ctypes binding gives them the header's argument types, sship.Homotopy has the methods, a call without a context is refused with a
-message before anything touches a device, and neither the ABI version nor the statistics struct moved.  The refusals that need a
+message before anything touches a device, and no context option was added.  The refusals that need a
 live context (column count, index range, tier, element type) are in tests/test_gpu_gemm_kernels.py."""
 import ctypes
 import inspect
 import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "sparse-solvers_amd", "python"))
+import abi_common
+from abi_common import ROOT
 
 PROTOTYPES = {
     "ss_hip_gram_cols_wide_f32": ["ss_hip_ctx*", "const uint32_t*", "size_t", "int", "float*", "ptrdiff_t", "int", "float*", "char*", "size_t"],
@@ -30,37 +28,19 @@ SS_HIP_EINVAL = 1
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()
-    return True
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ss_hip.h")).read()
-
-
-def _params(name):
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "%s is not declared" % name
-    return [" ".join(p.split()) for p in m.group(1).split(",")]
-
-
-def _prototype(name):
-    """the parameter types of `name` as the header declares them, in order"""
-    return [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in _params(name)]
+    return abi_common.build()
 
 
 def test_header_declares_the_three_prototypes_exactly():
     assert len(PROTOTYPES) == 3
     for name, want in PROTOTYPES.items():
-        assert _prototype(name) == want, (name, _prototype(name))
-        assert [re.search(r"([A-Za-z_0-9]+)$", p).group(1) for p in _params(name)] == NAMES[name], name
+        assert abi_common.prototype(name) == want, (name, abi_common.prototype(name))
+        assert [re.search(r"([A-Za-z_0-9]+)$", p).group(1) for p in abi_common.params(name)] == NAMES[name], name
 
 
 def test_the_narrow_entry_points_kept_their_prototypes():
     for suf, t in (("f32", "float"), ("f64", "double")):
-        assert _prototype("ss_hip_gram_cols_" + suf) == ["ss_hip_ctx*", "const uint32_t*", "size_t", t + "*", "ptrdiff_t", "int", "float*",
+        assert abi_common.prototype("ss_hip_gram_cols_" + suf) == ["ss_hip_ctx*", "const uint32_t*", "size_t", t + "*", "ptrdiff_t", "int", "float*",
                                                          "char*", "size_t"]
 
 
@@ -75,10 +55,8 @@ def test_library_exports_them(built):
 def test_binding_argtypes_match_the_header(built):
     import sship
     L = sship.lib()
-    ctype = {"ss_hip_ctx*": ctypes.c_void_p, "const uint32_t*": ctypes.c_void_p, "float*": ctypes.c_void_p, "double*": ctypes.c_void_p,
-             "char*": ctypes.c_char_p, "size_t": ctypes.c_size_t, "ptrdiff_t": ctypes.c_ssize_t, "int": ctypes.c_int}
     for name in PROTOTYPES:
-        want = [ctype[p] for p in _prototype(name)]
+        want = [abi_common.CTYPE[p] for p in abi_common.prototype(name)]
         if "ms_out" in NAMES[name]:
             want[NAMES[name].index("ms_out")] = ctypes.POINTER(ctypes.c_float)
         got = list(getattr(L, name).argtypes)
@@ -113,17 +91,6 @@ def test_a_call_without_a_context_is_refused_with_a_message(built):
     assert L.ss_hip_gram_full_rows_f32(None, ctypes.addressof(cols), 4, ctypes.addressof(out), 4, err, len(err)) == SS_HIP_EINVAL
     assert b"gram_full_rows" in err.value
     assert L.ss_hip_gram_full_rows_f32(None, None, 0, None, 0, None, 0) == SS_HIP_EINVAL
-
-
-def test_abi_version_and_statistics_did_not_move():
-    hdr = _header()
-    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", hdr)
-    body = hdr[hdr.index("typedef struct ss_hip_stats"):hdr.index("} ss_hip_stats;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"\b(uint64_t|double|uint32_t|float)\s+([a-z0-9_]+)\s*;", body)
-    assert fields[-2:] == [("uint64_t", "irls_batch_signals"), ("uint64_t", "irls_batch_rounds")]
-    import sship
-    assert [f[0] for f in sship.Stats._fields_[-2:]] == ["irls_batch_signals", "irls_batch_rounds"]
 
 
 def test_no_new_context_option():

@@ -4,48 +4,23 @@ counters at the end, and the chunk option is documented.  No compute calls (no G
 import ctypes
 import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "sparse-solvers_amd", "python"))
+import abi_common
+from abi_common import ROOT
 
 IRLS_BATCH = ["ss_hip_irls_solve_batch_f32", "ss_hip_irls_solve_batch_f64"]
 
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()
-    return True
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ss_hip.h")).read()
-
-
-def _prototype(name):
-    """the parameter types of `name` as the header declares them, in order"""
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "%s is not declared" % name
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    return [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in params]
-
-
-_CTYPE = {
-    "ss_hip_ctx*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "const double*": ctypes.c_void_p, "float*": ctypes.c_void_p,
-    "double*": ctypes.c_void_p, "uint32_t*": ctypes.c_void_p, "int*": ctypes.c_void_p,
-    "char*": ctypes.c_char_p, "size_t": ctypes.c_size_t, "ptrdiff_t": ctypes.c_ssize_t, "float": ctypes.c_float, "double": ctypes.c_double,
-    "uint32_t": ctypes.c_uint32,
-}
+    return abi_common.build()
 
 
 def test_header_declares_the_irls_batch():
     for name, t in zip(IRLS_BATCH, ("float", "double")):
-        p = _prototype(name)
+        p = abi_common.prototype(name)
         assert p == ["ss_hip_ctx*", "const %s*" % t, "size_t", "ptrdiff_t", "ptrdiff_t", t, "uint32_t", "%s*" % t, "ptrdiff_t",
                      "ptrdiff_t", "uint32_t*", "double*", "int*", "char*", "size_t"], (name, p)
 
@@ -62,7 +37,7 @@ def test_binding_argtypes_match_the_header(built):
     import sship
     L = sship.lib()
     for name in IRLS_BATCH:
-        want = [_CTYPE[p] for p in _prototype(name)]
+        want = [abi_common.CTYPE[p] for p in abi_common.prototype(name)]
         got = list(getattr(L, name).argtypes)
         # (pointers to the uint32 / double / int outputs are bound as void pointers: numpy addresses are passed)
         assert len(got) == len(want), name
@@ -78,7 +53,7 @@ def test_python_surface_has_the_irls_batch():
 
 
 def test_irls_batch_counters_end_the_statistics():
-    hdr = _header()
+    hdr = abi_common.header()
     body = hdr[hdr.index("typedef struct ss_hip_stats"):hdr.index("} ss_hip_stats;")]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = re.findall(r"\b(uint64_t|double|uint32_t|float)\s+([a-z0-9_]+)\s*;", body)
@@ -88,7 +63,7 @@ def test_irls_batch_counters_end_the_statistics():
 
 
 def test_irls_batch_max_is_documented():
-    assert '"irls_batch_max"' in _header()
+    assert '"irls_batch_max"' in abi_common.header()
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "csrc", "homotopy.hip")).read()
     table = src[src.index("const OptRow kOptions[]"):src.index("int ss_hip_set_option")]       # (the rows both entry points walk)
     assert re.search(r'\{ "irls_batch_max",\s*&ss_hip_ctx::irls_batch_max,', table)

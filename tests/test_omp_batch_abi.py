@@ -1,14 +1,11 @@
 """CPU-only checks of the OMP batch entry points (include/ss_hip.h, ABI version 7): the library exports them, the header
 declares them, and the ctypes binding gives them the header's argument types.  No compute calls (no GPU here)."""
 import ctypes
-import os
 import re
-import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import abi_common
 
 OMP_BATCH = ["ss_hip_omp_solve_batch_f32", "ss_hip_omp_solve_batch_f64",
              "ss_hip_omp_solve_batch_compact_f32", "ss_hip_omp_solve_batch_compact_f64"]
@@ -16,39 +13,16 @@ OMP_BATCH = ["ss_hip_omp_solve_batch_f32", "ss_hip_omp_solve_batch_f64",
 
 @pytest.fixture(scope="module")
 def built():
-    import __graft_entry__ as ge
-    ge.build()
-    return True
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "ss_hip.h")).read()
-
-
-def _prototype(name):
-    """the parameter types of `name` as the header declares them, in order"""
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "%s is not declared" % name
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
-    return [re.sub(r"\s*\b[A-Za-z_0-9]+$", "", p) for p in params]
-
-
-_CTYPE = {
-    "ss_hip_ctx*": ctypes.c_void_p, "const float*": ctypes.c_void_p, "const double*": ctypes.c_void_p, "float*": ctypes.c_void_p,
-    "double*": ctypes.c_void_p, "void*": ctypes.c_void_p, "uint32_t*": ctypes.c_void_p,
-    "char*": ctypes.c_char_p, "size_t": ctypes.c_size_t, "ptrdiff_t": ctypes.c_ssize_t, "float": ctypes.c_float, "double": ctypes.c_double,
-    "uint32_t": ctypes.c_uint32,
-}
+    return abi_common.build()
 
 
 def test_abi_version_is_7():
-    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", _header())
+    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", abi_common.header())
 
 
 def test_header_declares_the_omp_batch():
     for name in OMP_BATCH:
-        _prototype(name)
+        abi_common.prototype(name)
 
 
 def test_library_exports_the_omp_batch(built):
@@ -63,7 +37,7 @@ def test_binding_argtypes_match_the_header(built):
     import sship
     L = sship.lib()
     for name in OMP_BATCH:
-        want = [_CTYPE[p] for p in _prototype(name)]
+        want = [abi_common.CTYPE[p] for p in abi_common.prototype(name)]
         got = list(getattr(L, name).argtypes)
         # (pointers to uint32 / double outputs are bound as void pointers: numpy addresses are passed)
         assert len(got) == len(want), name
