@@ -34,7 +34,9 @@ extern "C" {
                                     no new option key, no new field of ss_hip_stats; ss_hip_homotopy_replace_columns_*;
                                     the atom update of dictionary learning, ss_hip_homotopy_atom_update_*, with the test-aid option
                                     "dl_chunk_max" — no new field of ss_hip_stats; the least-squares refit of compact records,
-                                    ss_hip_refit_records_* — no new option key, no new field of ss_hip_stats) */
+                                    ss_hip_refit_records_* — no new option key, no new field of ss_hip_stats; the sequential atom and
+                                    coefficient sweep of K-SVD, ss_hip_homotopy_ksvd_sweep_* — no new option key, no new field of
+                                    ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -290,7 +292,8 @@ int ss_hip_homotopy_classify_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t 
  * and the atom is LEFT AS IT IS (v_j = the stored column, bit for bit) when U_j is empty or ||g_j||_2 is zero or not finite.  All
  * atoms are computed against the same old dictionary and the same residuals (the parallel, Jacobi variant of the sweep: atoms that
  * share signals do not see each other's update; for S = 1 and a unit-norm old atom the objective cannot rise, for several atoms
- * that share signals it can — DESIGN.md §3.13d).
+ * that share signals it can — DESIGN.md §3.13d).  The sequential sweep that re-fits each atom's coefficients, carries the residuals
+ * along and cannot raise the objective is ss_hip_homotopy_ksvd_sweep_* below.
  *   V(i, s)    at V[i*stride_row + s*stride_col]; may be NULL when apply != 0
  *   usage[s]   (may be NULL) |U_j|; bit 31 is set when the atom had users but was left as it is
  *   objective  (may be NULL) one double: sum ||r_b||_2^2 over the counting signals, BEFORE the update (a record with K = 0
@@ -323,6 +326,70 @@ int ss_hip_homotopy_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
                                     double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
                                     uint32_t* usage, double* objective, uint32_t apply,
                                     char* err, size_t errlen);
+
+/*
+ * The K-SVD sweep: the atoms of cols one after the other, each atom's coefficients re-fitted and the residuals carried along (the
+ * sequential atom step of approximate K-SVD; added under ABI version 7; csrc/ksvd.hip; NOT in the reference).  Y, records, kmax,
+ * V, usage as for ss_hip_homotopy_atom_update_*; cols[S] names distinct atoms in PROCESSING ORDER (cols == NULL: all n atoms in
+ * ascending order, S is ignored, V is m x n); records_out receives the records with the re-fitted values and may be `records`
+ * itself (in place) or disjoint from it.  A signal counts when K_b <= kmax.  The working residual starts as r_b = y_b - A x_b (the
+ * words of ss_hip_homotopy_atom_update_*) and objective[0] = sum ||r_b||^2 (that call's objective, word for word).  Then for
+ * s = 0 .. S - 1, j = cols[s], U_j = the counting signals whose record holds j in ascending b, w_b = the INPUT record's value for j:
+ *     sigma = sum w_b^2 (double, ascending b, rounded once to T);  g_i starts at sigma * a_ij and takes w_b * r_b,i in ascending b
+ *     (T, one chain per element);  ||g||^2 in double — ss_hip_homotopy_atom_update_*'s order with the CURRENT residuals.
+ *     U_j empty, or ||g||_2 zero or not finite: the atom is LEFT AS IT IS — v_j = the stored column bit for bit, no record value and
+ *     no residual is touched, usage[s] as in ss_hip_homotopy_atom_update_* (bit 31: had users, left as it is).  Otherwise
+ *     v_j,i  = g_i / (T)||g||_2
+ *     rho    = sum_i (double)a_ij (double)v_j,i,     t_b = sum_i (double)r_b,i (double)v_j,i for every user (one summation order,
+ *              a function of m alone: csrc/ksvd.hip)
+ *     w'_b   = (T)(t_b + (double)w_b rho)                                     (row b of E_j^T v_j,  E_j = R_U + a_j w^T)
+ *     r_b,i <- (r_b,i + w_b a_ij) - w'_b v_j,i      each product and sum rounded in T, a_ij the STORED column
+ *     the output record's value for j becomes w'_b (a value that comes out 0 stays in the record).
+ * objective[1] = sum ||r_b||^2 of the final working residuals, in the order of objective[0].  In the output records K, iter, err,
+ * idx, the unused tail and every value of an atom not in cols are copied word for word; a truncated record is copied unchanged and
+ * adds +0 to both objectives; a record with K = 0 counts.
+ * MONOTONE BY CONSTRUCTION: with E = R_U + a w^T the minimiser over the atom for fixed w is E w / ||w||^2, which has the direction
+ * of v; w' = E^T v is the minimiser over the coefficients for the unit v.  Hence ||E - v w'^T||_F <= ||E - a w^T||_F whatever the
+ * norm of a: no atom step, and therefore no sweep, raises the objective in exact arithmetic; and the output records are the
+ * coefficients of the new atoms.
+ *   flags      SS_HIP_KSVD_APPLY: after the sweep the atoms that changed (usage in 1 .. 2^31 - 1) are written into the context as
+ *              ss_hip_homotopy_replace_columns_* writes them (nothing is touched when no atom changed);
+ *              SS_HIP_KSVD_SERIAL: a test aid, an argument of this call only — one atom per level (the plain sequential order)
+ *   V          may be NULL;  usage (S words) may be NULL;  objective may be NULL, else it receives TWO doubles: before, after
+ * All data pointers may be host or device pointers.
+ * SCHEDULE: an atom's step touches only its own users' residuals and record values, so atoms that share no signal commute exactly.
+ * The atoms run level by level of that dependency order (level[s] = 1 + the largest level of an earlier atom of cols that shares a
+ * signal with s; csrc/ks_levels.h), every level in parallel.  The residual block B * ldm * sizeof(T) of ALL signals is resident.
+ * CONTRACT: the outputs are a function of (records, Y, A, cols as an ordered list) alone — bit for bit the same with or without
+ * SS_HIP_KSVD_SERIAL, with host or device pointers, in place or out of place, whatever the context did before, whatever the launch
+ * geometry.  The columns of V, the usage and the record values of the first S' atoms of cols are those of a call with
+ * cols[0 .. S').  For an atom that no earlier atom of cols shares a signal with, the column of V and usage are
+ * ss_hip_homotopy_atom_update_*'s words.  No floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the context and every output untouched.
+ *   SS_HIP_EINVAL  null ctx, Y, records or records_out; V null without SS_HIP_KSVD_APPLY and usage and objective both null (nothing
+ *                  asked for); an IRLS or a column-sharded context; kmax outside 1..4096; records or records_out not 8-byte
+ *                  aligned; a partial overlap of records and records_out; a non-positive incy or y_stride, or stride_row /
+ *                  stride_col when V is given; an unknown flag bit; a column >= n or named twice in cols; a record index >= n
+ *                  (found on the device, never used as an address); a requested atom listed twice in one counting record
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace cannot be had (the message names the bytes): the residual block cannot be chunked over the
+ *                  signals, because an atom needs all its users at once
+ *   B == 0, or S == 0 with cols given: SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_KSVD_APPLY  1u   /* write the changed atoms into the context (as ss_hip_homotopy_replace_columns_* does) */
+#define SS_HIP_KSVD_SERIAL 2u   /* test aid, an argument of this call only: one atom per level (the plain sequential order) */
+int ss_hip_homotopy_ksvd_sweep_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                   const void* records, uint32_t kmax, void* records_out,
+                                   const uint32_t* cols, size_t S,
+                                   float* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                   uint32_t* usage, double* objective, uint32_t flags,
+                                   char* err, size_t errlen);
+int ss_hip_homotopy_ksvd_sweep_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                   const void* records, uint32_t kmax, void* records_out,
+                                   const uint32_t* cols, size_t S,
+                                   double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                   uint32_t* usage, double* objective, uint32_t flags,
+                                   char* err, size_t errlen);
 
 /*
  * The least-squares refit of compact records on their supports — debiasing (added under ABI version 7; csrc/refit.hip; NOT in the

@@ -622,6 +622,64 @@ int atom_update_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride,
 
 }  // namespace
 
+// ---- the index and the residuals for the K-SVD sweep (ksvd.hip): the launches above on the context's stream, nothing else ----
+
+hipError_t dl_launch_count(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, const uint32_t* slot_of, uint32_t S,
+                           uint32_t* counts, uint32_t* off, uint32_t* bad)
+{
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)S * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_dl_count<false>), dim3(B), dim3(256), 0, st, recs, rb, kmax, (uint32_t)ctx->n, slot_of, counts, (const uint32_t*)nullptr,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, bad);
+    hipLaunchKernelGGL(k_dl_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, S, off);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dl_launch_lists(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, const uint32_t* slot_of,
+                           const uint32_t* dcols, uint32_t S, uint32_t* counts, const uint32_t* off, uint32_t longest, uint32_t* pair_b,
+                           uint32_t* pair_e, uint32_t* sb, T* sw, T* s2, uint32_t* bad)
+{
+    hipStream_t st = ctx->stream;
+    const hipError_t e = hipMemsetAsync(counts, 0, (size_t)S * sizeof(uint32_t), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_dl_count<true>), dim3(B), dim3(256), 0, st, recs, rb, kmax, (uint32_t)ctx->n, slot_of, counts, off, pair_b, pair_e, bad);
+    hipLaunchKernelGGL((k_dl_sort<T>), dim3((S + 3u) / 4u), dim3(256), 0, st, recs, rb, kmax, off, S, (const uint32_t*)pair_b,
+                       (const uint32_t*)pair_e, sb, sw, s2);
+    if (longest > kDlRankMax)
+        hipLaunchKernelGGL((k_dl_long<T>), dim3(S), dim3(256), 0, st, recs, rb, kmax, B, dcols, off, sb, sw, s2);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dl_launch_residuals(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
+                               uint32_t Bc, T* R, double* part)
+{
+    const uint32_t ntiles = (uint32_t)((ctx->m + kClsTileRows - 1) / kClsTileRows);
+    hipLaunchKernelGGL((k_dl_residual<T>), dim3(ntiles, Bc), dim3(kClsThreads), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm,
+                       (uint32_t)ctx->m, yd, ys, yi, recs, rb, kmax, R, part);
+    return hipGetLastError();
+}
+
+hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per, uint32_t B, double* sig, double* obj)
+{
+    hipLaunchKernelGGL(k_dl_signal_sums, dim3((B + 255u) / 256u), dim3(256), 0, ctx->stream, part, per, B, sig);
+    hipLaunchKernelGGL(k_dl_objective, dim3(1), dim3(64), 0, ctx->stream, (const double*)sig, B, obj);
+    return hipGetLastError();
+}
+
+template hipError_t dl_launch_lists<float>(ss_hip_ctx*, const unsigned char*, size_t, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t,
+                                           uint32_t*, const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*, float*, float*, uint32_t*);
+template hipError_t dl_launch_lists<double>(ss_hip_ctx*, const unsigned char*, size_t, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t,
+                                            uint32_t*, const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*, double*, double*, uint32_t*);
+template hipError_t dl_launch_residuals<float>(ss_hip_ctx*, const float*, long long, long long, const unsigned char*, size_t, uint32_t, uint32_t,
+                                               float*, double*);
+template hipError_t dl_launch_residuals<double>(ss_hip_ctx*, const double*, long long, long long, const unsigned char*, size_t, uint32_t, uint32_t,
+                                                double*, double*);
+
 void dictlearn_free(ss_hip_ctx* ctx)
 {
     DictLearnState* ds = static_cast<DictLearnState*>(ctx->dl);

@@ -363,6 +363,7 @@ struct ss_hip_ctx {
     void* dl = nullptr;           // sship::DictLearnState* (dictlearn.hip): the workspace of the atom update
     void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
     void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
+    void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
@@ -503,8 +504,26 @@ void omp_gram_free(ss_hip_ctx* ctx);
 void classify_free(ss_hip_ctx* ctx);
 // the atom update of dictionary learning (dictlearn.hip): releases its workspace
 void dictlearn_free(ss_hip_ctx* ctx);
+// ... and the launches of its kernels the K-SVD sweep (ksvd.hip) shares with it, on the context's stream (every pointer on the device):
+// dl_launch_count: counts[S] and off[0 .. S + 1] (the offsets, the total, the longest list) of the atom -> user lists, and bad = the
+// first record with a column index >= n (else 0xffffffff); slot_of [n]: column -> position in the request, null = every column its own.
+// dl_launch_lists: the lists sb / sw (signal, value) in ascending (signal, position in the record) order and s2[s] = sum w^2;
+// pair_b / pair_e: scratch of `total` words each.  dl_launch_residuals: R[b][0 .. ldm) = y_b - A x_b and the partial sums of squares
+// part[b][tile][wave] for Bc <= 32768 signals from recs on.  dl_launch_objective: sig[b] from `per` partials each, obj[0] = their sum
+hipError_t dl_launch_count(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, const uint32_t* slot_of, uint32_t S,
+                           uint32_t* counts, uint32_t* off, uint32_t* bad);
+template <typename T>
+hipError_t dl_launch_lists(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, const uint32_t* slot_of,
+                           const uint32_t* dcols, uint32_t S, uint32_t* counts, const uint32_t* off, uint32_t longest, uint32_t* pair_b,
+                           uint32_t* pair_e, uint32_t* sb, T* sw, T* s2, uint32_t* bad);
+template <typename T>
+hipError_t dl_launch_residuals(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
+                               uint32_t Bc, T* R, double* part);
+hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per, uint32_t B, double* sig, double* obj);
 // the least-squares refit of compact records (refit.hip): releases its workspace
 void refit_free(ss_hip_ctx* ctx);
+// the K-SVD sweep (ksvd.hip): releases its workspace
+void ksvd_free(ss_hip_ctx* ctx);
 // the coherence of atoms (coherence.hip): releases its workspace
 void coherence_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word

@@ -148,6 +148,7 @@ _PROTOTYPES = [
     ("ss_hip_homotopy_classify_batch_", _int, [_vp, _vp, _sz, _pd, _pd, _T, _u32, _u32, _vp, _vp, _pd, _vp, _vp] + _ERR),
     ("ss_hip_homotopy_replace_columns_", _int, [_vp, _vp, _sz, _vp, _pd, _pd] + _ERR),
     ("ss_hip_homotopy_atom_update_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _vp, _pd, _pd, _vp, _vp, _u32] + _ERR),
+    ("ss_hip_homotopy_ksvd_sweep_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _sz, _vp, _pd, _pd, _vp, _vp, _u32] + _ERR),
     ("ss_hip_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_atom_coherence_", _int, [_vp, _vp, _sz, _vp, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
@@ -542,6 +543,42 @@ class Homotopy(_Context):
         _call(self._fn("ss_hip_homotopy_atom_update_"), self._h, Yp, B, ys, incy, rp, int(kmax), cptr, S, vp_, rs_, cs_, up,
               ctypes.addressof(obj), 1 if apply else 0)
         return V, usage, float(obj.value)
+
+    # flags of ksvd_sweep (include/ss_hip.h, SS_HIP_KSVD_*)
+    KSVD_APPLY, KSVD_SERIAL = 1, 2
+
+    def ksvd_sweep(self, Y, records, kmax, cols=None, apply=True, out=None, records_out=None, serial=False):
+        """The K-SVD sweep from compact records (include/ss_hip.h, ss_hip_homotopy_ksvd_sweep_*): the atoms of `cols` (None = all n,
+        ascending) ONE AFTER THE OTHER in the order given — v = g / ||g||_2 as in atom_update but from the residuals as the earlier
+        atoms left them, then the atom's coefficients re-fitted (w' = E^T v) and the residuals updated
+        -> (V (m, S), usage (S,), records_out, objective_before, objective_after).  The sweep cannot raise the objective in exact
+        arithmetic, and records_out holds the coefficients of the new atoms; everything else of a record is copied word for word.
+        usage, V, `out`, cols and apply: as for atom_update.  records_out: a contiguous (B, record_bytes) uint8 array or tensor on
+        either side — `records` itself sweeps in place; default: a new one where `records` lives.  serial=True (a test aid) runs
+        one atom per level instead of the level schedule: the same words."""
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        if records_out is None:
+            if isinstance(records, np.ndarray):
+                records_out = np.empty_like(records)
+            else:
+                import torch
+                records_out = torch.empty_like(records)
+        op, _ = _records(records_out, self.record_bytes(kmax), noun="records_out", B=B, other="records_out")
+        cptr, S, keepc, _ = self._cols(cols)
+        dev = _device_of(Y)
+        V = _alloc(dev, (S, self.m), self.dtype)[0].T if out is None else out           # (columns contiguous)
+        usage, up = _alloc(dev, (S,), np.uint32, 0)
+        vp_, vshape, vstr, vdt, keepv = _describe(V)
+        if vdt != self.dtype or tuple(vshape) != (self.m, S):
+            raise ValueError("out must be (m, %d) of the matrix dtype" % S)
+        obj = (ctypes.c_double * 2)(0.0, 0.0)
+        _sync_producers(Y, records, V, records_out)
+        _sync_producers(cols)
+        rs_, cs_ = (vstr[0], vstr[1]) if S and self.m > 1 else (max(int(vstr[0]), 1), max(int(vstr[1]), 1))
+        flags = (self.KSVD_APPLY if apply else 0) | (self.KSVD_SERIAL if serial else 0)
+        _call(self._fn("ss_hip_homotopy_ksvd_sweep_"), self._h, Yp, B, ys, incy, rp, int(kmax), op, cptr, S, vp_, rs_, cs_, up,
+              ctypes.addressof(obj), flags)
+        return V, usage, records_out, float(obj[0]), float(obj[1])
 
     # status words of refit_records (include/ss_hip.h, SS_HIP_REFIT_*)
     REFIT_DONE, REFIT_EMPTY, REFIT_TRUNCATED, REFIT_TOO_LARGE, REFIT_SINGULAR = range(5)
