@@ -36,7 +36,9 @@ extern "C" {
                                     "dl_chunk_max" — no new field of ss_hip_stats; the least-squares refit of compact records,
                                     ss_hip_refit_records_* — no new option key, no new field of ss_hip_stats; the sequential atom and
                                     coefficient sweep of K-SVD, ss_hip_homotopy_ksvd_sweep_* — no new option key, no new field of
-                                    ss_hip_stats) */
+                                    ss_hip_stats; the top correlations of residuals and the record extension of the stagewise coders,
+                                    ss_hip_top_correlations_* and ss_hip_extend_records_*, with the test-aid option "tc_chunk_max" — no
+                                    new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -471,6 +473,81 @@ int ss_hip_atom_coherence_f64(ss_hip_ctx* ctx, const uint32_t* cols, size_t S,
                               double* mu, uint32_t* partner, char* err, size_t errlen);
 
 /*
+ * The top correlations of residuals: for every signal the k atoms that best explain what its record leaves over (added under ABI
+ * version 7; csrc/topcorr.hip; NOT in the reference).  The primitive of the thresholding coder and of stagewise OMP (one stage =
+ * this call, ss_hip_extend_records_*, ss_hip_refit_records_*), of nearest-atom retrieval and of residual diagnostics.  Y holds the
+ * B signals (row b at Y[b*y_stride + i*incy]); records: B compact records of capacity kmax, or NULL.  For signal b, with i over
+ * the n columns of A,
+ *     r_b       = y_b - A x_b          the residual of record b: the words of the atom update and of the K-SVD sweep (the chain
+ *                                      of ss_hip_reconstruct_records_*, then one subtraction in T); with records == NULL the
+ *                                      words of y_b (kmax is ignored)
+ *     dot(i, b) = sum_k a_ki r_kb      products and sums in the context's precision on the matrix cores, one accumulator, one
+ *                                      chain from 0 over the rows in ascending K-steps: a function of column i, r_b and m alone
+ *     d_i       = sum_k a_ki^2         in double, formed per call from A (ss_hip_atom_coherence_*'s words; nothing is cached on the
+ *                                      context: a column replacement needs no refresh), rn_i = 1 / sqrt(d_i)
+ *     s(i, b)   = |dot(i, b)| * rn_i   in double
+ * The CANDIDATES of signal b are the columns i < n with d_i finite and non-zero that record b does not store (exclusion is by
+ * index mask, never by arithmetic); a candidate whose score is NaN is never selected.
+ *     idx[b][t]   the candidates by descending score, ties by ascending index, t = 0 .. k - 1
+ *     score[b][t] (may be NULL) the candidate's score
+ *     coef[b][t]  (may be NULL) (T)((double)dot * rn_i^2): the least-squares coefficient of r_b on that atom alone, with its sign
+ * Entries beyond the number of candidates are SS_HIP_TOPCORR_NONE in idx and 0 in coef and score; a truncated record (K > kmax)
+ * yields such entries throughout.  1 <= k <= SS_HIP_TOPCORR_KMAX.  All data pointers may be host or device pointers.
+ * The signals run in chunks under a byte budget, in ascending order (the workspace holds a chunk's residuals, [.][ldm], and dots,
+ * [.][n_pad], grown on demand, freed with the context; option "tc_chunk_max").  G = A^T A is neither read nor written, resident or not.
+ * ARITHMETIC (one documented order: csrc/topcorr.hip): |s - s_float64| <= (gamma_m + 1e-12) ||r_b||_2 with
+ * gamma_m = m u / (1 - m u), u = 2^-24 (fp32) or 2^-53 (fp64), s_float64 formed from the same words of A and r_b.
+ * CONTRACT: row b of the outputs is a function of A, y_b, record b and k alone — bit for bit the same alone or in any batch, in any
+ * batch order, with host or device pointers, across the chunking, whatever the context did before, with G resident or not; after
+ * a column replacement it is a fresh context's result.  PREFIX PROPERTY: the result for k is the first k entries of the result for
+ * any larger k.  No floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  null ctx, Y or idx; an IRLS or a column-sharded context; k outside 1..SS_HIP_TOPCORR_KMAX; with records given:
+ *                  kmax outside 1..4096, records not 8-byte aligned; a non-positive incy or y_stride; a record index >= n (found
+ *                  on the device, never used as an address)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_TOPCORR_NONE 0xffffffffu
+#define SS_HIP_TOPCORR_KMAX 256
+int ss_hip_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                const void* records, uint32_t kmax, uint32_t k,
+                                uint32_t* idx, float* coef, double* score, char* err, size_t errlen);
+int ss_hip_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                const void* records, uint32_t kmax, uint32_t k,
+                                uint32_t* idx, double* coef, double* score, char* err, size_t errlen);
+
+/*
+ * The record extension: columns named per signal enter its compact record (added under ABI version 7; csrc/topcorr.hip; NOT in the
+ * reference).  Integer and copy work only: every word of the output is exactly predictable.  idx [B][k] (the layout
+ * ss_hip_top_correlations_* writes), coef [B][k] or NULL.  For signal b, with K the record's count:
+ *     the entries idx[b][0 .. k) are taken in order; an entry is skipped when it is SS_HIP_TOPCORR_NONE, when the record already
+ *     stores that column, or when an earlier entry of the row was taken for it; taking stops when K reaches kmax;
+ *     a taken column c is inserted in front of the first stored entry whose index is larger than c (at the end when there is
+ *     none: an ascending idx[] stays ascending), the entries behind it move up by one; its value is coef[b][t], or 0 when coef
+ *     is NULL;
+ *     records_out[b] = the record so extended: K grown by added[b] (may be NULL), iter, err, the existing indices and values and
+ *     the tail behind the last entry word for word;
+ *     a truncated record (K > kmax) is copied unchanged, added[b] = 0.
+ * records_out may be `records` itself (in place) or disjoint from it.  All data pointers may be host or device pointers.
+ * CONTRACT: record b of the output and added[b] are a function of record b and row b of idx and coef alone; no floating-point
+ * arithmetic at all.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  null ctx, records, idx or records_out; an IRLS or a column-sharded context; kmax outside 1..4096; records or
+ *                  records_out not 8-byte aligned, or overlapping in part; k outside 1..SS_HIP_TOPCORR_KMAX; a record index >= n,
+ *                  or an entry of idx >= n that is not SS_HIP_TOPCORR_NONE (found on the device, never used as an address)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+int ss_hip_extend_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax,
+                              const uint32_t* idx, const float* coef, uint32_t k,
+                              void* records_out, uint32_t* added, char* err, size_t errlen);
+int ss_hip_extend_records_f64(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax,
+                              const uint32_t* idx, const double* coef, uint32_t k,
+                              void* records_out, uint32_t* added, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the
@@ -885,6 +962,8 @@ int ss_hip_reset_stats(ss_hip_ctx* ctx);
  *                    also bounded by 1 GiB of per-signal state (n^2 + 5 n + 2 ldm elements each).  Never changes a result
  *   "dl_chunk_max"   test aid: most signals whose residuals ss_hip_homotopy_atom_update_* holds at once (default 0 = a byte budget
  *                    alone; at most 32768); chunks are taken in ascending order with g carried between them: never changes a result
+ *   "tc_chunk_max"   test aid: most signals whose residuals and dots ss_hip_top_correlations_* holds at once (default 0 = a byte budget
+ *                    alone; at most 32768); every signal's row is formed on its own: never changes a result
  *   "batch_gram_min" (where the screened batch form applies — "batch_screen" — G pays later and is formed for a batch of at
  *                    least max(batch_gram_min, 1536) signals, or once the context has received 3072 signals in batches)
  *                    smallest lock-step batch that forms G = A^T A (n^2 fp32, 2 m n^2 flops once) and then

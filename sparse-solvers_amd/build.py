@@ -65,6 +65,8 @@ HIP_UNITS = [
     ("coherence.hip", ["-ffp-contract=off"]),
     # the K-SVD sweep from compact records: dictlearn.hip's atom on the carried residuals, so the same flags (the words are pinned to it)
     ("ksvd.hip", ["-ffp-contract=off"]),
+    # the top correlations of residuals and the record extension: coherence.hip's tile and normalisation, so the same flags (the tests' bound)
+    ("topcorr.hip", ["-ffp-contract=off"]),
 ]
 
 

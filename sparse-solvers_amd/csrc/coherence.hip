@@ -350,6 +350,16 @@ int coherence_entry(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* mu,
 
 }  // namespace
 
+template <typename T>
+hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* rinv)
+{
+    hipLaunchKernelGGL((k_coh_norms<T>), dim3(ctx->n_pad / 4u), dim3(256), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm,
+                       (uint32_t)ctx->m, (uint32_t)ctx->n, ctx->n_pad, rinv);
+    return hipGetLastError();
+}
+template hipError_t coh_launch_norms<float>(ss_hip_ctx*, double*);
+template hipError_t coh_launch_norms<double>(ss_hip_ctx*, double*);
+
 void coherence_free(ss_hip_ctx* ctx)
 {
     CoherenceState* cs = static_cast<CoherenceState*>(ctx->coh);

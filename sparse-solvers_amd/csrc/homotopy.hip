@@ -2894,6 +2894,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     sship::refit_free(ctx);
     sship::coherence_free(ctx);
     sship::ksvd_free(ctx);
+    sship::topcorr_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);
@@ -3134,6 +3135,12 @@ struct OptRow {
     constexpr OptRow(const char* k, OptNorm nm) : key(k), i(nullptr), l(nullptr), norm(nm), lo(0), hi(0) {}
 };
 
+// keys added after the rows of the table below were pinned, key for key, by tests/test_gpu_options.py: the same row type, walked by the
+// same two entry points, each key covered by the tests of its feature (tc_chunk_max: tests/test_gpu_topcorr.py)
+const OptRow kLaterKeys[] = {
+    { "tc_chunk_max",          &ss_hip_ctx::tc_chunk_max,          OptNorm::Clamp, 0, 32768 },
+};
+
 const OptRow kOptions[] = {
     { "sweep_variant",         &ss_hip_ctx::sweep_variant,         OptNorm::AsIs },
     { "lookahead",             &ss_hip_ctx::lookahead,             OptNorm::AsIs },
@@ -3185,6 +3192,8 @@ const OptRow kOptions[] = {
 const OptRow* find_option(const char* key)
 {
     for (const OptRow& r : kOptions)
+        if (!std::strcmp(key, r.key)) return &r;
+    for (const OptRow& r : kLaterKeys)
         if (!std::strcmp(key, r.key)) return &r;
     return nullptr;
 }

@@ -364,7 +364,9 @@ struct ss_hip_ctx {
     void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
     void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
     void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
+    void* tc = nullptr;           // sship::TopCorrState* (topcorr.hip): the workspace of the top correlations and the record extension
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
+    int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
     size_t m = 0, n = 0;
@@ -526,6 +528,11 @@ void refit_free(ss_hip_ctx* ctx);
 void ksvd_free(ss_hip_ctx* ctx);
 // the coherence of atoms (coherence.hip): releases its workspace
 void coherence_free(ss_hip_ctx* ctx);
+// ... and the launch of its norms kernel the top correlations (topcorr.hip) share with it, on the context's stream: rinv[i] = 1 / sqrt(d_i),
+// d_i = sum_k a_ki^2 in double, for i < n_pad (0 for an excluded column: d_i zero or not finite, or i >= n) — k_coh_norms' words
+template <typename T> hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* rinv);
+// the top correlations and the record extension (topcorr.hip): releases their workspace
+void topcorr_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word
 // R[b][0] of that call (NaN for a truncated record).  Y, records, Rn on either side; `who` names the caller in an error's text
 template <typename T>

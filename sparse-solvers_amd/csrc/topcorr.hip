@@ -1,0 +1,694 @@
+// topcorr.hip — the top correlations of residuals on the matrix cores and the record extension (include/ss_hip.h):
+//   ss_hip_top_correlations_*, ss_hip_extend_records_*.
+//
+// For signal b the first call returns the k atoms that best explain what its record leaves over: the columns i, not stored in the
+// record, with the largest s(i, b) = |a_i . r_b| / ||a_i||, r_b = y_b - A x_b.  The second call enters named columns into compact
+// records.  Together with the refit (refit.hip) they are one stage of stagewise OMP; one stage alone is the thresholding coder.
+// G = A^T A is never read: the product A^T R of a chunk of signals runs on the MFMA units from A.  Kernels:
+//
+//   k_tc_signals  grid = (row tile, signal): the residual block of a call WITHOUT records — the words of y_b, zero padded to ldm.
+//                 With records the block is dictlearn.hip's (dl_launch_residuals: the atom update's and the K-SVD sweep's words).
+//   k_tc_check    one workgroup per signal, the whole batch before anything is written: the first record with a column index >= n
+//                 (never used as an address).
+//   k_tc_tile     grid = (signal tile, column tile), 128 x 128 x 128 bytes of K per step, 256 threads, two workgroups a CU.  The
+//                 queries are the rows of the residual block [Bc][ldm], the other operand is At.  Tiling, staging, MFMA instructions
+//                 and chain order are coherence.hip's k_coh_tile (its main loop is stated here a second time: the two epilogues share
+//                 nothing, and coherence.hip stays the unit its tests pin).  Epilogue: dot in T to the block D [Bc][n_pad].
+//   k_tc_select   one workgroup per signal.  The record's columns are struck out of the signal's row of D by index (a NaN word: a NaN
+//                 score is never selected); the scores are formed in double from the stored dots and rn; the k best by the total order
+//                 (score descending, index ascending) are found by a radix selection on the score's bits — eight bits a pass, LDS
+//                 histogram of integer counts — until the columns that can still be among the k best fit an LDS list of 1024, which is
+//                 sorted by the total order (bitonic).  All columns tied on the k-th score (a zero residual): the smallest indices
+//                 are taken in ascending blocks.
+//   k_tc_extend_check / k_tc_extend   the record extension: one workgroup per signal, the record in LDS, the entries of the row one
+//                 after the other (membership and insertion point across the threads, the move block by block from the top).
+//
+// ORDER (stated once; build flag -ffp-contract=off: outside the MFMA products and sums are rounded separately):
+//   r_b          k_dl_residual's words (dictlearn.hip: the record's columns added in record order, one subtraction in T); rows
+//                m .. ldm - 1 are zero.
+//   dot(i, b)    one accumulator, started at 0, in the context's precision; the K-steps ascending over the padded rows.  fp32: a
+//                K-step holds 32 rows; MFMA (g, t), g = 0 .. 3 outer, t = 0 .. 3 inner, adds the rows 8 g + t and 8 g + 4 + t of the
+//                step, in the instruction's order.  fp64: a K-step holds 16 rows; MFMA g = 0 .. 3 adds the rows 4 g .. 4 g + 3.  The
+//                chain does not depend on where in a tile the pair sits: dot(i, b) is a function of column i, r_b and m alone.
+//   d_i, rn_i    k_coh_norms' words (coherence.hip), per call: rn_i = 1 / sqrt(d_i) in double, 0 for an excluded column.
+//   s(i, b)      = |dot(i, b)| * rn_i, dot widened to double: one multiplication.
+//   coef         = (T)((double)dot * (rn_i * rn_i)): the square first, one rounding to T at the end.
+//   selection    a maximum under a total order: whichever way the comparisons run, the result is the same.  The integer atomics (the
+//                histogram's counts, the slots of the unsorted list) cannot change it: counts commute, and the list is sorted by a
+//                total order afterwards.  No floating-point atomics.
+// Nothing depends on B, on the chunking, on the launch geometry, on where the pointers live or on what the context did before.
+#include "ss_hip_internal.h"
+#include "record_common.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace sship {
+
+namespace {
+
+constexpr uint32_t kTcTile = 128;                        // signals and columns per tile
+constexpr uint32_t kTcVecs = 8;                          // 16-byte vectors of K per row and step (32 floats / 16 doubles)
+constexpr uint32_t kTcPitch = kTcVecs + 1;               // LDS row pitch in vectors (144 B, as in coherence.hip)
+constexpr uint32_t kTcNone = SS_HIP_TOPCORR_NONE;
+constexpr uint32_t kTcList = 1024;                       // entries of the selection's LDS list (>= 2 SS_HIP_TOPCORR_KMAX)
+constexpr uint32_t kTcChunkMax = 32768;                  // most signals per chunk (grid.y of the residual kernels)
+constexpr size_t kTcChunkBytes = (size_t)1536 << 20;     // the byte budget of a chunk's residuals and dots (never changes a result)
+static_assert(kTcList >= 2 * SS_HIP_TOPCORR_KMAX, "the list holds the k best and a boundary bin");
+
+typedef float tc_v4f __attribute__((ext_vector_type(4)));
+typedef float tc_v16f __attribute__((ext_vector_type(16)));
+typedef double tc_v2d __attribute__((ext_vector_type(2)));
+typedef double tc_v4d __attribute__((ext_vector_type(4)));
+
+// the wave's 64 x 64 share of a tile as NI x NI accumulators of WT x WT (coherence.hip: CohMma)
+template <typename T> struct TcMma;
+template <> struct TcMma<float> {
+    typedef tc_v4f Vec;
+    typedef tc_v16f Acc;
+    static constexpr uint32_t NI = 2, NE = 16, WT = 32, KS = 32;
+    // C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    __device__ static uint32_t row(uint32_t e, uint32_t hq) { return (e & 3u) + 8u * (e >> 2) + 4u * hq; }
+};
+template <> struct TcMma<double> {
+    typedef tc_v2d Vec;
+    typedef tc_v4d Acc;
+    static constexpr uint32_t NI = 4, NE = 4, WT = 16, KS = 16;
+    // C/D layout of the fp64 16 x 16 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg
+    __device__ static uint32_t row(uint32_t e, uint32_t hq) { return 4u * e + hq; }
+};
+
+struct TopCorrState {
+    unsigned char* buf = nullptr;      // per call: inverse norms, staged records and outputs; per chunk: residuals, dots, a host caller's signals
+    size_t bytes = 0;
+};
+
+TopCorrState* state_of(ss_hip_ctx* ctx)
+{
+    if (!ctx->tc) ctx->tc = new TopCorrState();
+    return static_cast<TopCorrState*>(ctx->tc);
+}
+
+__device__ inline float tc_nan(float) { return __int_as_float(0x7fc00000); }
+__device__ inline double tc_nan(double) { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// ---- kernels -------------------------------------------------------------------------------------------------------------------
+
+// R[b][0 .. ldm) = the words of y_b, rows m .. ldm - 1 zero
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_tc_signals(const T* __restrict__ Y, long long y_stride, long long incy, uint32_t m, uint32_t ldm, T* __restrict__ R)
+{
+    const uint32_t row = blockIdx.x * 256u + threadIdx.x, b = blockIdx.y;
+    if (row >= ldm) return;
+    R[(size_t)b * ldm + row] = row < m ? Y[(long long)b * y_stride + (long long)row * incy] : T(0);
+}
+
+__global__ __launch_bounds__(64)
+void k_tc_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax, uint32_t n, uint32_t* __restrict__ bad)
+{
+    const uint32_t b = blockIdx.x;
+    const unsigned char* r = rec + (size_t)b * rb;
+    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
+    const uint32_t K = Krec < kmax ? Krec : kmax;
+    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+    for (uint32_t e = threadIdx.x; e < K; e += 64u)
+        if (idx[e] >= n) atomicMin(bad, b);
+}
+
+// R: [signal tiles x 128][ldm]; D: [signal tiles x 128][n_pad]
+template <typename T>
+__global__ __launch_bounds__(256, 2)
+void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, uint32_t n_pad, T* __restrict__ D)
+{
+    typedef TcMma<T> M;
+    typedef typename M::Vec Vec;
+    typedef typename M::Acc Acc;
+    constexpr uint32_t NI = M::NI, NE = M::NE, WT = M::WT;
+    __shared__ __attribute__((aligned(16))) Vec sA[2][kTcTile][kTcPitch];      // the residuals
+    __shared__ __attribute__((aligned(16))) Vec sB[2][kTcTile][kTcPitch];      // the columns
+
+    // signal tiles fastest: concurrently resident workgroups share the same panel of At
+    const uint32_t bt = blockIdx.x, bn = blockIdx.y;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t wm = wave & 1u, wn = wave >> 1;
+    const uint32_t lc = lane & (WT - 1u), hq = lane / WT;
+
+    // staging map: thread -> (rows srow + 32 j, vector svec of the step)
+    const uint32_t srow = tid >> 3, svec = tid & 7u;
+    const Vec* gA[4];
+    const Vec* gB[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        gA[j] = reinterpret_cast<const Vec*>(R + (size_t)(bt * kTcTile + srow + 32u * (uint32_t)j) * ldm) + svec;
+        gB[j] = reinterpret_cast<const Vec*>(At + (size_t)(bn * kTcTile + srow + 32u * (uint32_t)j) * ldm) + svec;
+    }
+
+    Acc acc[NI][NI];
+#pragma unroll
+    for (uint32_t i = 0; i < NI; ++i)
+#pragma unroll
+        for (uint32_t j = 0; j < NI; ++j)
+#pragma unroll
+            for (uint32_t e = 0; e < NE; ++e) acc[i][j][e] = T(0);
+
+    Vec stA[4], stB[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { stA[j] = gA[j][0]; stB[j] = gB[j][0]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { sA[0][srow + 32 * j][svec] = stA[j]; sB[0][srow + 32 * j][svec] = stB[j]; }
+    __syncthreads();
+
+    const uint32_t nk = ldm / M::KS;
+    uint32_t cur = 0;
+    for (uint32_t kt = 0; kt < nk; ++kt) {
+        const bool more = (kt + 1u) < nk;
+        if (more) {
+            const uint32_t voff = (kt + 1u) * kTcVecs;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { stA[j] = gA[j][voff]; stB[j] = gB[j][voff]; }
+        }
+        if constexpr (sizeof(T) == 4) {
+#pragma unroll
+            for (uint32_t g = 0; g < 4; ++g) {
+                Vec a[NI], b[NI];
+#pragma unroll
+                for (uint32_t i = 0; i < NI; ++i) {
+                    a[i] = sA[cur][wm * 64u + i * WT + lc][2u * g + hq];
+                    b[i] = sB[cur][wn * 64u + i * WT + lc][2u * g + hq];
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (uint32_t i = 0; i < NI; ++i)
+#pragma unroll
+                        for (uint32_t j = 0; j < NI; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][t], b[j][t], acc[i][j], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t g = 0; g < 4; ++g) {
+                const uint32_t k = 4u * g + hq;
+                double a[NI], b[NI];
+#pragma unroll
+                for (uint32_t i = 0; i < NI; ++i) {
+                    a[i] = reinterpret_cast<const double*>(&sA[cur][wm * 64u + i * WT + lc][0])[k];
+                    b[i] = reinterpret_cast<const double*>(&sB[cur][wn * 64u + i * WT + lc][0])[k];
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < NI; ++i)
+#pragma unroll
+                    for (uint32_t j = 0; j < NI; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sA[cur ^ 1u][srow + 32 * j][svec] = stA[j]; sB[cur ^ 1u][srow + 32 * j][svec] = stB[j]; }
+        }
+        __syncthreads();
+        cur ^= 1u;
+    }
+
+    // ---- epilogue: the dots as they are; a lane holds column lc of each accumulator, WT lanes write one run of a row ----
+    T* d0 = D + (size_t)(bt * kTcTile + wm * 64u) * n_pad + bn * kTcTile + wn * 64u + lc;
+#pragma unroll
+    for (uint32_t i = 0; i < NI; ++i)
+#pragma unroll
+        for (uint32_t e = 0; e < NE; ++e) {
+            T* dr = d0 + (size_t)(i * WT + M::row(e, hq)) * n_pad;
+#pragma unroll
+            for (uint32_t j = 0; j < NI; ++j) dr[j * WT] = acc[i][j][e];
+        }
+}
+
+// (key, index): a comes before b when its score is larger, or equal with the smaller index; the keys are the bits of non-negative
+// doubles, which order as the doubles do
+__device__ inline bool tc_before(unsigned long long ka, uint32_t ia, unsigned long long kb, uint32_t ib) { return ka > kb || (ka == kb && ia < ib); }
+
+// D: the chunk's dots, row b of it is this workgroup's to strike columns out of; rec == nullptr: no records
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_tc_select(T* __restrict__ D, uint32_t n, uint32_t n_pad, const double* __restrict__ rinv, const unsigned char* __restrict__ rec,
+                 size_t rb, uint32_t kmax, uint32_t k, uint32_t* __restrict__ oidx, T* __restrict__ ocoef, double* __restrict__ oscore)
+{
+    __shared__ unsigned long long lkey[kTcList];
+    __shared__ uint32_t lidx[kTcList];
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sh[4], wcnt[4];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    T* d = D + (size_t)b * n_pad;
+    oidx += (size_t)b * k;
+    ocoef += (size_t)b * k;
+    oscore += (size_t)b * k;
+    if (rec) {
+        const unsigned char* r = rec + (size_t)b * rb;
+        const uint32_t K = *reinterpret_cast<const uint32_t*>(r);
+        if (K > kmax) {                                          // a truncated record does not hold its support: no candidates
+            for (uint32_t t = tid; t < k; t += 256u) { oidx[t] = kTcNone; ocoef[t] = T(0); oscore[t] = 0.0; }
+            return;
+        }
+        const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+        for (uint32_t e = tid; e < K; e += 256u) d[idx[e]] = tc_nan(T(0));        // (idx < n: k_tc_check)
+        __threadfence_block();
+        __syncthreads();
+    }
+    // the key of column i, false for a column that is no candidate
+    auto keyof = [&](uint32_t i, unsigned long long& key) -> bool {
+        const double r = rinv[i];
+        if (r == 0.0) return false;
+        const double s = fabs((double)d[i]) * r;
+        if (!(s == s)) return false;
+        key = (unsigned long long)__double_as_longlong(s);
+        return true;
+    };
+
+    // ---- radix selection: P = the bits above `shift` of the k-th best key so far as they are known, `above` columns lie in higher
+    // bins (all of them among the k best), `need` more come from the bin of P, which holds c columns ----
+    unsigned long long P = 0;
+    uint32_t need = k, above = 0, c = 0;
+    int shift = 56;
+    bool ties = false;
+    for (;;) {
+        hist[tid] = 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += 256u) {
+            unsigned long long key;
+            if (keyof(i, key) && (shift == 56 || (key >> (shift + 8)) == P)) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t cum = 0, bin = 0;
+            bool found = false;
+            for (int bb = 255; bb >= 0; --bb) {
+                if (cum + hist[bb] >= need) { bin = (uint32_t)bb; found = true; break; }
+                cum += hist[bb];
+            }
+            if (!found) cum -= hist[0];                          // fewer candidates than k (first pass only): all of them, bin 0 last
+            sh[0] = bin;
+            sh[1] = cum;
+            sh[2] = hist[bin];
+        }
+        __syncthreads();
+        const uint32_t bin = sh[0], cum = sh[1];
+        c = sh[2];
+        above += cum;
+        need -= cum < need ? cum : need;
+        P = (P << 8) | bin;
+        if (above + c <= kTcList) break;
+        if (shift == 0) { ties = true; break; }
+        shift -= 8;
+    }
+
+    // ---- the list: every column above the bin, and the bin itself unless it is one exact score that more than the list share ----
+    if (tid == 0) sh[3] = 0u;
+    __syncthreads();
+    for (uint32_t i = tid; i < n; i += 256u) {
+        unsigned long long key;
+        if (!keyof(i, key)) continue;
+        const unsigned long long top = key >> shift;
+        if (top > P || (top == P && !ties)) {
+            const uint32_t slot = atomicAdd(&sh[3], 1u);
+            lkey[slot] = key;
+            lidx[slot] = i;
+        }
+    }
+    __syncthreads();
+    uint32_t L = sh[3];
+    if (ties) {
+        // every column of the bin has the key P: the `need` smallest indices, in ascending blocks of 256
+        for (uint32_t base = 0; base < n && need != 0u; base += 256u) {
+            const uint32_t i = base + tid;
+            unsigned long long key = 0;
+            const bool mine = i < n && keyof(i, key) && key == P;
+            const unsigned long long mask = __ballot(mine);
+            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mask);
+            __syncthreads();
+            uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)), total = 0;
+            for (uint32_t w = 0; w < 4u; ++w) { if (w < wave) before += wcnt[w]; total += wcnt[w]; }
+            if (mine && before < need) { lkey[L + before] = key; lidx[L + before] = i; }
+            const uint32_t taken = total < need ? total : need;
+            L += taken;
+            need -= taken;
+            __syncthreads();
+        }
+    }
+    uint32_t S = 1;
+    while (S < L) S <<= 1;
+    for (uint32_t t = L + tid; t < S; t += 256u) { lkey[t] = 0ull; lidx[t] = kTcNone; }      // (behind every column: the largest index)
+    for (uint32_t size = 2; size <= S; size <<= 1)
+        for (uint32_t stride = size >> 1; stride > 0u; stride >>= 1) {
+            __syncthreads();
+            for (uint32_t t = tid; t < S / 2u; t += 256u) {
+                const uint32_t lo = 2u * t - (t & (stride - 1u)), hi = lo + stride;
+                const unsigned long long ka = lkey[lo], kb = lkey[hi];
+                const uint32_t ia = lidx[lo], ib = lidx[hi];
+                const bool fwd = (lo & size) == 0u;
+                if (fwd ? tc_before(kb, ib, ka, ia) : tc_before(ka, ia, kb, ib)) { lkey[lo] = kb; lidx[lo] = ib; lkey[hi] = ka; lidx[hi] = ia; }
+            }
+        }
+    __syncthreads();
+    for (uint32_t t = tid; t < k; t += 256u) {
+        if (t < L) {
+            const uint32_t i = lidx[t];
+            const double r = rinv[i];
+            oidx[t] = i;
+            ocoef[t] = (T)((double)d[i] * (r * r));
+            oscore[t] = __longlong_as_double((long long)lkey[t]);
+        } else {
+            oidx[t] = kTcNone;
+            ocoef[t] = T(0);
+            oscore[t] = 0.0;
+        }
+    }
+}
+
+// bad[0]: the first record with a column index >= n; bad[1]: the first row of idx with an entry >= n that is not NONE
+__global__ __launch_bounds__(64)
+void k_tc_extend_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax, uint32_t n, const uint32_t* __restrict__ idx,
+                       uint32_t k, uint32_t* __restrict__ bad)
+{
+    const uint32_t b = blockIdx.x;
+    const unsigned char* r = rec + (size_t)b * rb;
+    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
+    const uint32_t K = Krec < kmax ? Krec : kmax;
+    const uint32_t* ri = reinterpret_cast<const uint32_t*>(r + 16);
+    for (uint32_t e = threadIdx.x; e < K; e += 64u)
+        if (ri[e] >= n) atomicMin(&bad[0], b);
+    for (uint32_t t = threadIdx.x; t < k; t += 64u) {
+        const uint32_t cidx = idx[(size_t)b * k + t];
+        if (cidx != kTcNone && cidx >= n) atomicMin(&bad[1], b);
+    }
+}
+
+// VW: 32-bit words of a value.  rec_in and rec_out: the same records (in place) or disjoint ones.  coef: words, or null
+template <uint32_t VW>
+__global__ __launch_bounds__(256)
+void k_tc_extend(const unsigned char* rec_in, unsigned char* rec_out, size_t rb, uint32_t kmax, const uint32_t* __restrict__ idx,
+                 const uint32_t* __restrict__ coef, uint32_t k, uint32_t* __restrict__ added)
+{
+    extern __shared__ __align__(16) unsigned char s_tc_raw[];
+    uint32_t* sidx = reinterpret_cast<uint32_t*>(s_tc_raw);      // [kmax]
+    uint32_t* sval = sidx + kmax;                                // [kmax][VW]
+    __shared__ uint32_t s_found, s_pos;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const uint32_t* wi = reinterpret_cast<const uint32_t*>(rec_in + (size_t)b * rb);
+    uint32_t* wo = reinterpret_cast<uint32_t*>(rec_out + (size_t)b * rb);
+    const uint32_t words = (uint32_t)(rb / 4), Krec = wi[0];
+    if (Krec > kmax) {                                           // a truncated record: unchanged
+        if (wi != wo)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+        if (tid == 0) added[b] = 0u;
+        return;
+    }
+    for (uint32_t e = tid; e < kmax; e += 256u) sidx[e] = wi[4u + e];
+    for (uint32_t w = tid; w < kmax * VW; w += 256u) sval[w] = wi[4u + kmax + w];
+    uint32_t K = Krec;
+    for (uint32_t t = 0; t < k && K < kmax; ++t) {               // (every condition below is uniform across the workgroup)
+        const uint32_t cidx = idx[(size_t)b * k + t];
+        if (cidx == kTcNone) continue;
+        __syncthreads();
+        if (tid == 0) { s_found = 0u; s_pos = K; }
+        __syncthreads();
+        for (uint32_t e = tid; e < K; e += 256u) {
+            const uint32_t v = sidx[e];
+            if (v == cidx) atomicOr(&s_found, 1u);
+            if (v > cidx) atomicMin(&s_pos, e);
+        }
+        __syncthreads();
+        const uint32_t found = s_found, pos = s_pos;
+        if (found) continue;
+        // the entries pos .. K - 1 move up by one: blocks of 256 from the top, each read whole before it is written
+        for (uint32_t hi = K; hi > pos;) {
+            const uint32_t lo = hi - pos > 256u ? hi - 256u : pos, e = lo + tid;
+            uint32_t vi = 0, vv[VW];
+            if (e < hi) {
+                vi = sidx[e];
+#pragma unroll
+                for (uint32_t w = 0; w < VW; ++w) vv[w] = sval[e * VW + w];
+            }
+            __syncthreads();
+            if (e < hi) {
+                sidx[e + 1u] = vi;
+#pragma unroll
+                for (uint32_t w = 0; w < VW; ++w) sval[(e + 1u) * VW + w] = vv[w];
+            }
+            __syncthreads();
+            hi = lo;
+        }
+        if (tid == 0) {
+            sidx[pos] = cidx;
+#pragma unroll
+            for (uint32_t w = 0; w < VW; ++w) sval[pos * VW + w] = coef ? coef[((size_t)b * k + t) * VW + w] : 0u;
+        }
+        K += 1u;
+    }
+    __syncthreads();
+    // K, then iter and err word for word, the lists from LDS, the padding behind them
+    for (uint32_t w = tid; w < words; w += 256u) {
+        const uint32_t v = w == 0u ? K : w < 4u ? wi[w] : w < 4u + kmax ? sidx[w - 4u] : w < 4u + kmax + kmax * VW ? sval[w - 4u - kmax] : wi[w];
+        wo[w] = v;
+    }
+    if (tid == 0) added[b] = K - Krec;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+
+// grow() with an out-of-memory failure turned into the call's SS_HIP_ENOMEM and a message that names the bytes
+bool tc_grow(TopCorrState* ts, size_t need, const char* who, char* err, size_t errlen)
+{
+    try {
+        grow(ts->buf, ts->bytes, need, "hipMalloc(top correlations workspace)");
+    } catch (const HipFail& f) {
+        if (f.code != hipErrorOutOfMemory) throw;
+        (void)hipGetLastError();
+        set_err(err, errlen, std::string(who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes");
+        return false;
+    }
+    return true;
+}
+
+template <typename T>
+int topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, uint32_t k,
+                 uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
+{
+    static const char* who = "top_correlations";
+    HIPCHK(hipSetDevice(ctx->device));
+    TopCorrState* ts = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t m = ctx->m, rb = records ? record_bytes(kmax, sizeof(T)) : 0;
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, n_pad = ctx->n_pad, Bu = (uint32_t)B;
+    const uint32_t ctiles = (n + kTcTile - 1u) / kTcTile, rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
+    const bool rec_dev = records && on_device(records), y_dev = on_device(Y);
+
+    // the chunk: whole signal tiles under the byte budget
+    const size_t per = (size_t)ldm * sizeof(T) + (size_t)n_pad * sizeof(T) + (size_t)rtiles * 4u * sizeof(double) + (y_dev ? 0 : m * sizeof(T));
+    size_t chunk = std::max<size_t>(kTcTile, std::min<size_t>(kTcChunkMax, kTcChunkBytes / per) / kTcTile * kTcTile);
+    if (ctx->tc_chunk_max > 0) chunk = std::min<size_t>(chunk, (size_t)ctx->tc_chunk_max);
+    chunk = std::min(chunk, B);
+    const size_t chunk_pad = (chunk + kTcTile - 1) / kTcTile * kTcTile;
+
+    auto carve = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        double* rinv = cv.take<double>(n_pad);
+        uint32_t* bad = cv.take<uint32_t>(1);
+        unsigned char* stage = (records && !rec_dev) ? cv.take<unsigned char>(B * rb) : nullptr;
+        uint32_t* oi = cv.take<uint32_t>(B * k);
+        T* oc = cv.take<T>(B * k);
+        double* os = cv.take<double>(B * k);
+        T* R = cv.take<T>(chunk_pad * ldm);
+        T* D = cv.take<T>(chunk_pad * n_pad);
+        double* part = cv.take<double>(chunk * rtiles * 4u);
+        T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
+        use(rinv, bad, stage, oi, oc, os, R, D, part, ybuf);
+        return cv.off;
+    };
+    if (!tc_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+
+    int rc = SS_HIP_OK;
+    carve(ts->buf, [&](double* rinv, uint32_t* bad, unsigned char* stage, uint32_t* oi, T* oc, double* os, T* R, T* D, double* part, T* ybuf) {
+        const unsigned char* din = static_cast<const unsigned char*>(records);
+        if (records) {
+            if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
+            HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+            hipLaunchKernelGGL(k_tc_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, bad);
+            HIPCHK(hipGetLastError());
+            uint32_t first_bad = kTcNone;
+            HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));            // (nothing has been written when a record is invalid)
+            if (first_bad != kTcNone) { rc = bad_index(first_bad, who, err, errlen); return; }
+        }
+        HIPCHK(coh_launch_norms<T>(ctx, rinv));
+        const T* At = static_cast<const T*>(ctx->At);
+        std::vector<T> tmp;
+        for (size_t b0 = 0; b0 < B; b0 += chunk) {
+            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0), btiles = (Bc + kTcTile - 1u) / kTcTile;
+            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
+            long long ys = y_stride, yi = incy;
+            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
+            // the rows behind the chunk's last signal, up to a whole tile: zero (their dots are never read).  The row of a truncated record
+            // is not written by the residual kernel either and holds what the workspace held: a tile's rows are independent of each
+            // other, and k_tc_select leaves such a signal before it reads a dot
+            if (btiles * kTcTile != Bc) HIPCHK(hipMemsetAsync(R + (size_t)Bc * ldm, 0, (size_t)(btiles * kTcTile - Bc) * ldm * sizeof(T), st));
+            if (records) HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, din + b0 * rb, rb, kmax, Bc, R, part));
+            else {
+                hipLaunchKernelGGL((k_tc_signals<T>), dim3((ldm + 255u) / 256u, Bc), dim3(256), 0, st, yd, ys, yi, (uint32_t)m, ldm, R);
+                HIPCHK(hipGetLastError());
+            }
+            hipLaunchKernelGGL((k_tc_tile<T>), dim3(btiles, ctiles), dim3(256), 0, st, At, ldm, (const T*)R, n_pad, D);
+            HIPCHK(hipGetLastError());
+            hipLaunchKernelGGL((k_tc_select<T>), dim3(Bc), dim3(256), 0, st, D, n, n_pad, (const double*)rinv, records ? din + b0 * rb : nullptr, rb,
+                               kmax, k, oi + b0 * k, oc + b0 * k, os + b0 * k);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(idx, oi, B * k * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (coef) HIPCHK(hipMemcpyAsync(coef, oc, B * k * sizeof(T), hipMemcpyDefault, st));
+        if (score) HIPCHK(hipMemcpyAsync(score, os, B * k * sizeof(double), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return rc;
+}
+
+// the checks the two entry points share beyond check_common's, in the order they are reported
+int tc_check_k(const char* who, uint32_t k, char* err, size_t errlen)
+{
+    if (k == 0 || k > (uint32_t)SS_HIP_TOPCORR_KMAX) {
+        set_err(err, errlen, std::string(who) + ": k must be 1.." + std::to_string(SS_HIP_TOPCORR_KMAX));
+        return SS_HIP_EINVAL;
+    }
+    return SS_HIP_OK;
+}
+
+template <typename T>
+int topcorr_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, uint32_t k,
+                  uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
+{
+    static const char* who = "top_correlations";
+    // (without records kmax is ignored: the checks see a capacity that passes)
+    int rc = check_common<T>(ctx, who, records, false, records ? kmax : 1u, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !idx) { set_err(err, errlen, "top_correlations: Y and idx must not be null"); return SS_HIP_EINVAL; }
+    if ((rc = tc_check_k(who, k, err, errlen)) != SS_HIP_OK) return rc;
+    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "top_correlations: increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
+    if (B >= 0x80000000ull) { set_err(err, errlen, "top_correlations: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    return guarded(err, errlen, who, [&] { return topcorr_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen); });
+}
+
+template <typename T>
+int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const T* coef, uint32_t k, void* records_out,
+                uint32_t* added, char* err, size_t errlen)
+{
+    static const char* who = "extend_records";
+    constexpr uint32_t VW = sizeof(T) / 4;
+    HIPCHK(hipSetDevice(ctx->device));
+    TopCorrState* ts = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t rb = record_bytes(kmax, sizeof(T));
+    const uint32_t n = (uint32_t)ctx->n, Bu = (uint32_t)B;
+    const bool in_dev = on_device(records), out_dev = on_device(records_out), idx_dev = on_device(idx), coef_dev = !coef || on_device(coef);
+
+    auto carve = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        unsigned char* stage = (in_dev && out_dev) ? nullptr : cv.take<unsigned char>(B * rb);
+        uint32_t* di = idx_dev ? nullptr : cv.take<uint32_t>(B * k);
+        T* dc = coef_dev ? nullptr : cv.take<T>(B * k);
+        uint32_t* dadd = cv.take<uint32_t>(B);
+        uint32_t* bad = cv.take<uint32_t>(2);
+        use(stage, di, dc, dadd, bad);
+        return cv.off;
+    };
+    if (!tc_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+
+    int rc = SS_HIP_OK;
+    carve(ts->buf, [&](unsigned char* stage, uint32_t* di, T* dc, uint32_t* dadd, uint32_t* bad) {
+        // din / dout: as in refit.hip (a host caller's records are staged, in place when the input is staged too)
+        const unsigned char* din = static_cast<const unsigned char*>(records);
+        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
+        unsigned char* dout = out_dev ? static_cast<unsigned char*>(records_out) : stage;
+        const uint32_t* didx = idx;
+        if (!idx_dev) { HIPCHK(hipMemcpyAsync(di, idx, B * k * sizeof(uint32_t), hipMemcpyHostToDevice, st)); didx = di; }
+        const T* dcoef = coef;
+        if (!coef_dev) { HIPCHK(hipMemcpyAsync(dc, coef, B * k * sizeof(T), hipMemcpyHostToDevice, st)); dcoef = dc; }
+        HIPCHK(hipMemsetAsync(bad, 0xff, 2 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(k_tc_extend_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, didx, k, bad);
+        HIPCHK(hipGetLastError());
+        uint32_t first_bad[2] = { kTcNone, kTcNone };
+        HIPCHK(hipMemcpyAsync(first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record or a row is invalid)
+        if (first_bad[0] != kTcNone) { rc = bad_index(first_bad[0], who, err, errlen); return; }
+        if (first_bad[1] != kTcNone) {
+            set_err(err, errlen, std::string(who) + ": row " + std::to_string(first_bad[1]) + " of idx holds a column index >= n");
+            rc = SS_HIP_EINVAL;
+            return;
+        }
+        hipLaunchKernelGGL((k_tc_extend<VW>), dim3(Bu), dim3(256), (size_t)kmax * (1u + VW) * sizeof(uint32_t), st, din, dout, rb, kmax, didx,
+                           reinterpret_cast<const uint32_t*>(dcoef), k, dadd);
+        HIPCHK(hipGetLastError());
+        if (added) HIPCHK(hipMemcpyAsync(added, dadd, B * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return rc;
+}
+
+template <typename T>
+int extend_entry(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const T* coef, uint32_t k, void* records_out,
+                 uint32_t* added, char* err, size_t errlen)
+{
+    static const char* who = "extend_records";
+    int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!idx || !records_out) { set_err(err, errlen, "extend_records: idx and records_out must not be null"); return SS_HIP_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "extend_records: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
+    if ((rc = tc_check_k(who, k, err, errlen)) != SS_HIP_OK) return rc;
+    if (B >= 0x80000000ull) { set_err(err, errlen, "extend_records: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if (records_out != records) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(records), b = reinterpret_cast<uintptr_t>(records_out);
+        const size_t bytes = B * record_bytes(kmax, sizeof(T));
+        if (a < b + bytes && b < a + bytes) { set_err(err, errlen, "extend_records: records and records_out overlap in part"); return SS_HIP_EINVAL; }
+    }
+    if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
+    return guarded(err, errlen, who, [&] { return extend_impl<T>(ctx, records, B, kmax, idx, coef, k, records_out, added, err, errlen); });
+}
+
+}  // namespace
+
+void topcorr_free(ss_hip_ctx* ctx)
+{
+    TopCorrState* ts = static_cast<TopCorrState*>(ctx->tc);
+    if (!ts) return;
+    if (ts->buf) (void)hipFree(ts->buf);
+    delete ts;
+    ctx->tc = nullptr;
+}
+
+}  // namespace sship
+
+using namespace sship;
+
+extern "C" {
+
+int ss_hip_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                uint32_t kmax, uint32_t k, uint32_t* idx, float* coef, double* score, char* err, size_t errlen)
+{
+    return topcorr_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen);
+}
+int ss_hip_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                uint32_t kmax, uint32_t k, uint32_t* idx, double* coef, double* score, char* err, size_t errlen)
+{
+    return topcorr_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen);
+}
+
+int ss_hip_extend_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const float* coef, uint32_t k,
+                              void* records_out, uint32_t* added, char* err, size_t errlen)
+{
+    return extend_entry<float>(ctx, records, B, kmax, idx, coef, k, records_out, added, err, errlen);
+}
+int ss_hip_extend_records_f64(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const double* coef, uint32_t k,
+                              void* records_out, uint32_t* added, char* err, size_t errlen)
+{
+    return extend_entry<double>(ctx, records, B, kmax, idx, coef, k, records_out, added, err, errlen);
+}
+
+}  // extern "C"

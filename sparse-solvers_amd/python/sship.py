@@ -151,6 +151,8 @@ _PROTOTYPES = [
     ("ss_hip_homotopy_ksvd_sweep_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _sz, _vp, _pd, _pd, _vp, _vp, _u32] + _ERR),
     ("ss_hip_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_atom_coherence_", _int, [_vp, _vp, _sz, _vp, _vp] + _ERR),
+    ("ss_hip_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_extend_records_", _int, [_vp, _vp, _sz, _u32, _vp, _vp, _u32, _vp, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
     ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
     ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
@@ -264,6 +266,12 @@ def _describe(a):
         dt = {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64)}[a.dtype]
         return a.data_ptr(), tuple(a.shape), tuple(a.stride()), dt, a
     raise TypeError("expected a numpy array or a torch tensor")
+
+
+def _torch_to_numpy_dtype(a):
+    """the numpy dtype of a float32, float64 or int32 torch tensor — the three extend_records takes — None for any other"""
+    import torch
+    return {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64), torch.int32: np.dtype(np.int32)}.get(a.dtype)
 
 
 def _sync_producers(*arrays):
@@ -623,6 +631,141 @@ class Homotopy(_Context):
         _sync_producers(cols, mu)
         _call(self._fn("ss_hip_atom_coherence_"), self._h, cptr, S, mp, pp)
         return mu, partner
+
+    # top_correlations / extend_records (include/ss_hip.h, SS_HIP_TOPCORR_*): the entry behind the last candidate, the largest k
+    TOPCORR_NONE = 0xffffffff
+    TOPCORR_KMAX = 256
+
+    def top_correlations(self, Y, k, records=None, kmax=None, coef=True, score=True):
+        """The top correlations of residuals (include/ss_hip.h, ss_hip_top_correlations_*): for every signal the k columns, not
+        stored in its record, with the largest |a_i . r_b| / ||a_i||, r_b = y_b - A x_b (records=None: r_b = y_b, kmax is not
+        needed) -> (idx (B, k), coef (B, k) or None, score (B, k) float64 or None), by descending score, ties by ascending index.
+        coef = a_i . r_b / ||a_i||^2, the least-squares coefficient of r_b on that atom alone.  Entries behind the last candidate
+        are TOPCORR_NONE in idx and 0 in coef and score.  The outputs live where Y lives: device tensors for a device Y (idx then
+        int32: TOPCORR_NONE reads as -1), else numpy arrays (idx uint32)."""
+        if records is None:
+            Yp, B, ys, incy = self._signals(Y)
+            rp, kmax = None, 0
+            if not B:
+                ys, incy = self.m, 1
+        else:
+            if kmax is None:
+                raise ValueError("kmax must be given with records")
+            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        k = int(k)
+        dev = _device_of(Y)
+        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
+        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
+        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
+        _sync_producers(Y, records, idx)
+        _call(self._fn("ss_hip_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), k, ip, cp, sp)
+        return idx, cf, sc
+
+    def extend_records(self, records, kmax, idx, coef=None, out=None):
+        """The record extension (include/ss_hip.h, ss_hip_extend_records_*): per signal the columns idx[b, :] enter the record in
+        order — an entry that is TOPCORR_NONE, already stored or already taken is skipped, taking stops at kmax — each in front of
+        the first stored index that is larger, with the value coef[b, t] (0 for coef=None) -> (records_out, added (B,)).  idx:
+        a contiguous (B, k) int32 / uint32 array or tensor (what top_correlations returns), coef: (B, k) of the matrix dtype,
+        each on either side.  `out`: a contiguous (B, record_bytes) uint8 array or tensor on either side — `records` itself
+        extends in place; default: a new one where `records` lives, where `added` lives too (int32 on a device)."""
+        rp, B = _records(records, self.record_bytes(kmax))
+        if out is None:
+            if isinstance(records, np.ndarray):
+                out = np.empty_like(records)
+            else:
+                import torch
+                out = torch.empty_like(records)
+        op, _ = _records(out, self.record_bytes(kmax), noun="out", B=B, other="out")
+
+        def table(a, noun, dtypes):
+            if isinstance(a, np.ndarray):
+                ok = a.dtype in dtypes and a.ndim == 2 and a.flags.c_contiguous
+                ptr = a.ctypes.data
+            elif hasattr(a, "data_ptr"):
+                ok = _torch_to_numpy_dtype(a) in dtypes and a.dim() == 2 and a.is_contiguous()
+                ptr = a.data_ptr()
+            else:
+                raise TypeError("%s must be a numpy array or a torch tensor" % noun)
+            if not ok or a.shape[0] != B:
+                raise ValueError("%s must be a contiguous (B, k) array of %s" % (noun, " / ".join(np.dtype(d).name for d in dtypes)))
+            return ptr, int(a.shape[1])
+
+        ip, k = table(idx, "idx", (np.dtype(np.uint32), np.dtype(np.int32)))
+        cp = None
+        if coef is not None:
+            cp, kc = table(coef, "coef", (np.dtype(self.dtype),))
+            if kc != k:
+                raise ValueError("idx and coef must have the same shape")
+        added, ap = _alloc(_device_of(records), (B,), np.uint32, 0)
+        _sync_producers(records, out)
+        _sync_producers(idx)
+        _sync_producers(coef)
+        _call(self._fn("ss_hip_extend_records_"), self._h, rp, B, int(kmax), ip, cp, k, op, ap)
+        return out, added
+
+    def stagewise_code(self, Y, stages, per_stage, kmax=96, tolerance=None, records=None):
+        """Stagewise OMP from the three record calls, and nothing more -> (records, resnorm (B,) float64, status (B,)).  From empty
+        records (K = 0) or a copy of `records`, every stage runs top_correlations(per_stage) -> extend_records -> refit_records.
+        A signal whose refit status is not REFIT_DONE takes back its record from before the stage and is frozen; with a
+        `tolerance`, a signal whose resnorm is at or below it after a stage is frozen; a frozen signal enters no more columns.
+        resnorm and status are those of the last refit that set the signal's record (status: of the refit that froze it);
+        while no refit has set it they read NaN and REFIT_EMPTY — no fit is claimed.  Frozen signals still ride along in every
+        call of a stage (their rows are independent of the others' and are discarded); the loop ends once all are frozen.
+        stages >= 1; stages=1 is the thresholding coder.  The records live where `records`
+        lives, or where Y lives without; resnorm and status where Y lives (status int32 on a device)."""
+        kmax = int(kmax)
+        if int(stages) < 1:
+            raise ValueError("stages must be at least 1")
+        if kmax > self.REFIT_KMAX:
+            raise ValueError("kmax must not exceed REFIT_KMAX = %d" % self.REFIT_KMAX)
+        B = self._signals(Y)[1]
+        dev = _device_of(Y)
+        if records is None:
+            if dev is None:
+                cur = np.zeros((B, self.record_bytes(kmax)), dtype=np.uint8)
+            else:
+                import torch
+                cur = torch.zeros((B, self.record_bytes(kmax)), dtype=torch.uint8, device=dev)
+        else:
+            _records(records, self.record_bytes(kmax), B=B, other="Y")
+            cur = records.copy() if isinstance(records, np.ndarray) else records.clone()
+        on_dev = dev is not None
+        if on_dev:
+            import torch
+            rdev = cur.device
+            frozen = torch.zeros(B, dtype=torch.bool, device=dev)
+        else:
+            frozen = np.zeros(B, dtype=bool)
+        rec_on_dev = hasattr(cur, "data_ptr") and cur.is_cuda
+        resnorm = _alloc(dev, (B,), np.float64, float("nan"))[0]
+        status = _alloc(dev, (B,), np.uint32, self.REFIT_EMPTY)[0]
+
+        def where_records_live(mask):
+            """a mask over the signals, computed where Y lives, as an index of the records"""
+            if on_dev:
+                return mask.to(rdev) if rec_on_dev else mask.cpu().numpy()
+            if rec_on_dev:
+                import torch
+                return torch.as_tensor(mask, device=cur.device)
+            return mask
+
+        for _ in range(int(stages)):
+            if bool(frozen.all()):
+                break
+            idx, coef, _ = self.top_correlations(Y, per_stage, records=cur, kmax=kmax, score=False)
+            idx[frozen] = -1 if on_dev else self.TOPCORR_NONE
+            ext, _ = self.extend_records(cur, kmax, idx, coef)
+            new, rn, st = self.refit_records(Y, ext, kmax)
+            live = ~frozen
+            good = live & (st == self.REFIT_DONE)
+            g = where_records_live(good)
+            cur[g] = new[g]
+            resnorm[good] = rn[good]
+            status[live] = st[live]
+            frozen = frozen | (live & ~good)
+            if tolerance is not None:
+                frozen = frozen | (good & (resnorm <= float(tolerance)))
+        return cur, resnorm, status
 
     def _record_usage(self, records, kmax):
         """-> (usage (n,) uint32, K (B,) int64), numpy: the number of counting records (K <= kmax) that hold each column, and every
