@@ -193,8 +193,12 @@ int ss_hip_homotopy_solve_batch_compact_f64(ss_hip_ctx* ctx, const double* Y, si
  * OMP batch (ABI version 7): B signals sharing the context's sensing matrix, solved by orthogonal matching pursuit
  * (ss_hip_omp_solve_*).  Arguments, record layout and validation are those of the Homotopy batch above
  * (SS_HIP_ETYPE on a dtype mismatch; SS_HIP_EINVAL on an IRLS context, max_iter == 0, a tolerance outside
- * [eps, 1), non-positive increments, null pointers; B == 0 returns SS_HIP_OK).  The report is {iterations,
- * ||A^T r||_inf at exit}.
+ * [eps, 1), non-positive increments, null pointers; B == 0 returns SS_HIP_OK).  The report is {iterations, error
+ * at exit}.  For a signal a chunk certified, the error is the maximum of |A^T r| over the signal's SUBSET columns at
+ * exit (its 448 best-ranked columns in fp32, 256 in fp64), every other column being certified below 15/16 tol (below
+ * 7/8 of that maximum where the budget ended the path above tol): it is at most ||A^T r||_inf and can be well below it
+ * (a column outside the subset at tol / 2: 1.5e-3 reported against 5e-3).  It is ||A^T r||_inf itself when the signal
+ * was solved alone by an engine; the single-signal screened form reports its subset's maximum in the same way.
  * CONTRACT: signal b's result is what ss_hip_omp_solve_* returns for it alone — the same picks, support and
  * iteration count, coefficients equal to rounding; a signal no chunk form certifies is solved alone by the
  * single-signal ladder, and then its result is that solve's bit for bit.
