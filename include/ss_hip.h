@@ -38,7 +38,8 @@ extern "C" {
                                     coefficient sweep of K-SVD, ss_hip_homotopy_ksvd_sweep_* — no new option key, no new field of
                                     ss_hip_stats; the top correlations of residuals and the record extension of the stagewise coders,
                                     ss_hip_top_correlations_* and ss_hip_extend_records_*, with the test-aid option "tc_chunk_max" — no
-                                    new field of ss_hip_stats) */
+                                    new field of ss_hip_stats; joint sparse coding of signal groups, ss_hip_group_top_correlations_* and
+                                    ss_hip_group_class_residuals_* — no new option key, no new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -550,6 +551,77 @@ int ss_hip_extend_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, ui
 int ss_hip_extend_records_f64(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax,
                               const uint32_t* idx, const double* coef, uint32_t k,
                               void* records_out, uint32_t* added, char* err, size_t errlen);
+
+/*
+ * Joint sparse coding of signal groups — the group top correlations: for every GROUP of signals the k atoms that best explain what
+ * the members' records leave over together (added under ABI version 7; csrc/joint.hip; NOT in the reference).  The selection step of
+ * simultaneous OMP (the multiple-measurement-vector model): several observations of one subject share one support.  One stage of
+ * the joint coder = this call, ss_hip_extend_records_* with a group's idx row for each of its members, ss_hip_refit_records_*.
+ * GROUPS are consecutive runs of signals: group g holds the signals group_off[g] .. group_off[g + 1] - 1; group_off [Gn + 1] starts
+ * at 0, ascends strictly, ends at B, and no group holds more than SS_HIP_GROUP_MAX signals.  Y, records, kmax, k: as for
+ * ss_hip_top_correlations_*, whose r_b, dot(i, b), d_i and rn_i these are (the same kernels on the same rows).  For group g:
+ *     q(i, g)   = sum_b (double)dot(i, b) * (double)dot(i, b)    one accumulator from 0, the members in ascending b, every product and
+ *                                                               every sum rounded on its own
+ *     s(i, g)   = sqrt(q(i, g)) * rn_i                          in double
+ * The CANDIDATES of group g are the columns i < n with d_i finite and non-zero that NO member's record stores (exclusion is by
+ * index); a candidate whose score is NaN is never selected; a group with a truncated member (K > kmax) has no candidates.
+ *     idx[g][t]   the candidates by descending score, ties by ascending index, t = 0 .. k - 1                      [Gn][k]
+ *     score[g][t] (may be NULL) the candidate's score                                                             [Gn][k]
+ *     coef[b][t]  (may be NULL) (T)((double)dot(idx[g][t], b) * rn^2) for every member b of g: the member's own single-atom
+ *                 coefficient, the value ss_hip_extend_records_* takes                                            [B][k]
+ * Entries beyond the number of candidates are SS_HIP_TOPCORR_NONE in idx and 0 in coef and score.  All data pointers, group_off
+ * among them, may be host or device pointers.  The signals run in chunks of whole groups under ss_hip_top_correlations_*' byte
+ * budget (option "tc_chunk_max"; a cap below the largest group is raised to that group's size); the workspace (a chunk's residuals,
+ * dots and score rows [.][n_pad] in double) is the context's, grown on demand, freed with it.  G = A^T A is neither read nor written.
+ * ARITHMETIC (one documented order: csrc/joint.hip): |s - s_float64| <= (gamma_m + 1e-12) ||R_g||_F, R_g the
+ * residuals of the group, gamma_m as for ss_hip_top_correlations_*.
+ * CONTRACT: row g of idx and score and the members' rows of coef are a function of A, the group's signals and records in order, and
+ * k alone — bit for bit the same alone or in any batch, under any other grouping of the other signals, with host or device pointers,
+ * across the chunking, whatever the context did before, with G resident or not; after a column replacement they are a fresh
+ * context's result.  PREFIX PROPERTY in k.  No floating-point atomics.  No call changes what any solve returns.
+ * A GROUP OF ONE returns ss_hip_top_correlations_*' idx, score and coef words: in fp32 the square of a dot is exact in double, and in
+ * either precision sqrt(fl(x * x)) = |x| in binary round-to-nearest — provided x * x neither underflows nor overflows (fp64 only).
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  ss_hip_top_correlations_*' list, and: a null group_off or Gn == 0 with B > 0; Gn != 0 with B == 0; offsets that do
+ *                  not start at 0, do not ascend strictly or do not end at B; a group of more than SS_HIP_GROUP_MAX signals (found on
+ *                  the device — k_js_check — never used as an address)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         (then Gn == 0) SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_GROUP_MAX 256          /* most signals in one group */
+int ss_hip_group_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const void* records, uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k,
+                                      uint32_t* idx, float* coef, double* score, char* err, size_t errlen);
+int ss_hip_group_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const void* records, uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k,
+                                      uint32_t* idx, double* coef, double* score, char* err, size_t errlen);
+
+/*
+ * The group class residuals: the class residuals of compact records added up over the members of every group, and the class each
+ * group falls to (added under ABI version 7; csrc/joint.hip; NOT in the reference).  Needs ss_hip_set_classes.  Groups: as above.
+ * With R[b][c] the words ss_hip_class_residuals_* returns for signal b,
+ *     Rg[g][c] = (T)sqrt(sum_b (double)R[b][c] * (double)R[b][c])    one accumulator from 0, the members in ascending b   [Gn] rows of
+ *                                                                    rg_stride >= num_classes elements; may be NULL
+ *     best[g]  = the left-most arg-min of row g as stored (a NaN is never smaller)                                        [Gn]
+ * A group with a truncated member (K > kmax) gets best = 0xffffffff and a NaN row.  A group of one returns
+ * ss_hip_class_residuals_*' R row and best word (the proviso above).  The per-signal rows go through ss_hip_class_residuals_*' own
+ * path into a workspace of the context, in chunks of whole groups under a fixed byte budget; they are never written to the caller.
+ * Row g is a function of A, the labels and the group's signals and records in order.  No floating-point atomics.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  ss_hip_class_residuals_*' list (null ctx, Y, records or best; an IRLS or a column-sharded context; kmax outside
+ *                  1..4096; records not 8-byte aligned; no classes set; a non-positive incy or y_stride; rg_stride < num_classes with
+ *                  Rg given; a record index >= n), and the offset errors of ss_hip_group_top_correlations_*
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         (then Gn == 0) SS_HIP_OK, nothing touched
+ */
+int ss_hip_group_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                     const void* records, uint32_t kmax, const uint32_t* group_off, size_t Gn,
+                                     float* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen);
+int ss_hip_group_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                     const void* records, uint32_t kmax, const uint32_t* group_off, size_t Gn,
+                                     double* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen);
 
 /*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)

@@ -67,6 +67,8 @@ HIP_UNITS = [
     ("ksvd.hip", ["-ffp-contract=off"]),
     # the top correlations of residuals and the record extension: coherence.hip's tile and normalisation, so the same flags (the tests' bound)
     ("topcorr.hip", ["-ffp-contract=off"]),
+    # the group top correlations and group class residuals: sums of squares in double in the documented order, so the same flags
+    ("joint.hip", ["-ffp-contract=off"]),
 ]
 
 

@@ -582,6 +582,27 @@ int record_residual_norms(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B
 template int record_residual_norms<float>(ss_hip_ctx*, const char*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, float*, char*, size_t);
 template int record_residual_norms<double>(ss_hip_ctx*, const char*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, double*, char*, size_t);
 
+// the rows of ss_hip_class_residuals_* under the context's classes, behind the entry point's validation: for the group class residuals
+// (joint.hip).  Call it under guarded, with classes set (classify_num_classes != 0)
+template <typename T>
+int class_residual_rows(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                        uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, char* err, size_t errlen)
+{
+    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    return residuals_impl<T>(ctx, who, cs->labels, cs->num_classes, Y, B, y_stride, incy, records, kmax, R, r_stride, best, nullptr, err, errlen);
+}
+
+template int class_residual_rows<float>(ss_hip_ctx*, const char*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, float*, ptrdiff_t,
+                                        uint32_t*, char*, size_t);
+template int class_residual_rows<double>(ss_hip_ctx*, const char*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, double*,
+                                         ptrdiff_t, uint32_t*, char*, size_t);
+
+uint32_t classify_num_classes(const ss_hip_ctx* ctx)
+{
+    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    return cs && cs->labels ? cs->num_classes : 0u;
+}
+
 void classify_free(ss_hip_ctx* ctx)
 {
     ClassifyState* cs = static_cast<ClassifyState*>(ctx->cls);

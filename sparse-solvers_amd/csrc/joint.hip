@@ -1,0 +1,543 @@
+// joint.hip — joint sparse coding of signal groups: the group top correlations and the group class residuals (include/ss_hip.h):
+//   ss_hip_group_top_correlations_*, ss_hip_group_class_residuals_*.
+//
+// A group is a run of consecutive signals that share one support (simultaneous OMP, the multiple-measurement-vector model).  The
+// first call scores an atom by the l2 norm of its correlations with all residuals of the group and returns the k best atoms no
+// member's record stores; the second adds the class residuals up over the members.  The product A^T R stays topcorr.hip's: its
+// record check, residual block and MFMA tile run unchanged through tc_launch_* (ss_hip_internal.h).  Kernels of this file:
+//
+//   k_js_check    the offsets, before anything is written: the first group whose offsets do not start at 0, ascend strictly, end at B
+//                 or span more than SS_HIP_GROUP_MAX signals.  An offset is compared, never used as an address.
+//   k_js_scores   grid = (block of 256 columns, group).  First a pass over the members' records marks the block's stored columns in
+//                 LDS (and a truncated member); then a thread owns a column and walks the members' rows of D in ascending order —
+//                 the reads are coalesced along i, 4 L n bytes a group in fp32 — and writes the group's score row [n_pad] in double,
+//                 a NaN word at a stored or excluded column.  D itself is not struck into: k_js_coef reads it afterwards.
+//   k_js_select   one workgroup per group: tc_select.h's selection (k_tc_select's total order, list, tie branch and prefix property)
+//                 with the stored score as the key.
+//   k_js_coef     one workgroup per group: the members' coef rows from D and rn at the group's columns.
+//   k_gc_reduce   one workgroup per group, threads over the classes: the class reduction and the arg-min.
+//
+// ORDER (stated once; build flag -ffp-contract=off: products and sums are rounded separately):
+//   r_b, dot(i, b), d_i, rn_i   topcorr.hip's words (its ORDER block): the same kernels on the same rows.
+//   q(i, g)      = sum_b (double)dot(i, b) * (double)dot(i, b): one accumulator, started at 0, the members in ascending b; each
+//                product and each sum rounded on its own.
+//   s(i, g)      = sqrt(q(i, g)) * rn_i in double: one square root, one multiplication.
+//   candidates   the columns with d_i finite and non-zero that no member's record stores (by index); a NaN score is never selected;
+//                a group with a truncated member (K > kmax) has none.
+//   coef[b][t]   = (T)((double)dot(idx[g][t], b) * (rn * rn)), member by member: topcorr.hip's coef of that column and signal.
+//   selection    a maximum under a total order (score descending, index ascending): tc_select.h.  No floating-point atomics.
+//   Rg[g][c]     = (T)sqrt(sum_b (double)R[b][c] * (double)R[b][c]), R the words of ss_hip_class_residuals_*: one accumulator from 0,
+//                the members ascending; best[g] = the left-most arg-min of the row as stored (a NaN is never smaller).
+//   A GROUP OF ONE returns top_correlations' idx, score and coef words, and class_residuals' R row and best word: in fp32 the
+//   square of a dot is exact in double, and in either precision sqrt(fl(x * x)) = |x| in binary round-to-nearest as long as x * x
+//   neither underflows nor overflows (fp64 only: |x| between 2^-511 and 2^511 is safe).
+// A group's rows depend on A, its own signals and records in order, and k: not on B, on the other groups, on the chunking (a chunk
+// holds whole groups; a row of D is a function of its own signal), on where the pointers live or on what the context did before.
+#include "ss_hip_internal.h"
+#include "record_common.h"
+#include "tc_select.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace sship {
+
+namespace {
+
+constexpr uint32_t kJsGroupMax = SS_HIP_GROUP_MAX;
+constexpr size_t kGcChunkBytes = (size_t)64 << 20;       // the byte budget of a chunk's per-signal class rows (never changes a result)
+
+struct JointState {
+    unsigned char* buf = nullptr;      // per call: inverse norms, staged offsets, records and outputs; per chunk: residuals, dots, score rows
+    size_t bytes = 0;
+};
+
+JointState* state_of(ss_hip_ctx* ctx)
+{
+    if (!ctx->js) ctx->js = new JointState();
+    return static_cast<JointState*>(ctx->js);
+}
+
+__device__ inline double js_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+__device__ inline float js_nan_of(float) { return __int_as_float(0x7fc00000); }
+__device__ inline double js_nan_of(double) { return js_nan(); }
+
+// ---- kernels -------------------------------------------------------------------------------------------------------------------
+
+// off [Gn + 1]; bad: the first group whose offsets are wrong (the last group when the end is)
+__global__ __launch_bounds__(256)
+void k_js_check(const uint32_t* __restrict__ off, uint32_t Gn, uint32_t B, uint32_t* __restrict__ bad)
+{
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g > Gn) return;
+    const uint32_t v = off[g];
+    if (g == 0u && v != 0u) atomicMin(bad, 0u);
+    if (g == Gn) {
+        if (v != B) atomicMin(bad, Gn - 1u);
+        return;
+    }
+    const uint32_t w = off[g + 1u];
+    if (w <= v || w - v > kJsGroupMax) atomicMin(bad, g);
+}
+
+// D: the chunk's dots; rec: the chunk's first record, nullptr: no records; off: the offsets from the chunk's first group on; b0: the
+// chunk's first signal; S: the chunk's score rows [groups][n_pad]
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_js_scores(const T* __restrict__ D, uint32_t n, uint32_t n_pad, const double* __restrict__ rinv, const unsigned char* __restrict__ rec,
+                 size_t rb, uint32_t kmax, const uint32_t* __restrict__ off, uint32_t b0, double* __restrict__ S)
+{
+    __shared__ uint32_t s_mark[256];
+    __shared__ uint32_t s_trunc;
+    const uint32_t g = blockIdx.y, tid = threadIdx.x, base = blockIdx.x * 256u, i = base + tid;
+    const uint32_t lo = off[g] - b0, hi = off[g + 1u] - b0;      // (validated: k_js_check)
+    s_mark[tid] = 0u;
+    if (tid == 0) s_trunc = 0u;
+    __syncthreads();
+    if (rec) {
+        for (uint32_t b = lo; b < hi; ++b) {
+            const unsigned char* r = rec + (size_t)b * rb;
+            const uint32_t K = *reinterpret_cast<const uint32_t*>(r);
+            if (K > kmax) {                                      // a truncated record does not hold its support: the group has no candidates
+                if (tid == 0) s_trunc = 1u;
+                continue;
+            }
+            const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+            for (uint32_t e = tid; e < K; e += 256u) {
+                const uint32_t c = idx[e] - base;                // (every thread that marks writes the same word)
+                if (c < 256u) s_mark[c] = 1u;
+            }
+        }
+        __syncthreads();
+    }
+    double s = js_nan();
+    const double r = rinv[i];
+    if (s_trunc == 0u && i < n && r != 0.0 && s_mark[tid] == 0u) {
+        const T* d = D + (size_t)lo * n_pad + i;
+        double q = 0.0;
+        uint32_t b = lo;
+        for (; b + 4u <= hi; b += 4u, d += 4u * (size_t)n_pad) {  // four loads in flight, added in ascending member order
+            const double x0 = (double)d[0], x1 = (double)d[n_pad], x2 = (double)d[2u * (size_t)n_pad], x3 = (double)d[3u * (size_t)n_pad];
+            q += x0 * x0;
+            q += x1 * x1;
+            q += x2 * x2;
+            q += x3 * x3;
+        }
+        for (; b < hi; ++b, d += n_pad) {
+            const double x = (double)d[0];
+            q += x * x;
+        }
+        s = sqrt(q) * r;
+    }
+    S[(size_t)g * n_pad + i] = s;
+}
+
+__global__ __launch_bounds__(256)
+void k_js_select(const double* __restrict__ S, uint32_t n, uint32_t n_pad, uint32_t k, uint32_t* __restrict__ oidx, double* __restrict__ oscore)
+{
+    __shared__ TcSelectLds lds;
+    const uint32_t g = blockIdx.x, tid = threadIdx.x;
+    const double* s = S + (size_t)g * n_pad;
+    oidx += (size_t)g * k;
+    oscore += (size_t)g * k;
+    // the key of column i, false for a column that is no candidate (its stored score is a NaN)
+    auto keyof = [&](uint32_t i, unsigned long long& key) -> bool {
+        const double v = s[i];
+        if (!(v == v)) return false;
+        key = (unsigned long long)__double_as_longlong(v);
+        return true;
+    };
+    const uint32_t L = tc_select_sorted(lds, n, k, keyof);
+    for (uint32_t t = tid; t < k; t += 256u) {
+        if (t < L) {
+            oidx[t] = lds.lidx[t];
+            oscore[t] = __longlong_as_double((long long)lds.lkey[t]);
+        } else {
+            oidx[t] = kTcNone;
+            oscore[t] = 0.0;
+        }
+    }
+}
+
+// oidx: the chunk's group rows [groups][k]; ocoef: the chunk's signal rows [signals][k]
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_js_coef(const T* __restrict__ D, uint32_t n_pad, const double* __restrict__ rinv, const uint32_t* __restrict__ off, uint32_t b0, uint32_t k,
+               const uint32_t* __restrict__ oidx, T* __restrict__ ocoef)
+{
+    const uint32_t g = blockIdx.x;
+    const uint32_t lo = off[g] - b0, hi = off[g + 1u] - b0;
+    for (uint32_t e = threadIdx.x; e < (hi - lo) * k; e += 256u) {
+        const uint32_t b = lo + e / k, t = e % k, i = oidx[(size_t)g * k + t];
+        T v = T(0);
+        if (i != kTcNone) {
+            const double r = rinv[i];
+            v = (T)((double)D[(size_t)b * n_pad + i] * (r * r));
+        }
+        ocoef[(size_t)b * k + t] = v;
+    }
+}
+
+// R [signals][C] and bestb [signals]: the chunk's rows of class_residuals; Rg [groups][C], bestg [groups]
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_gc_reduce(const T* __restrict__ R, const uint32_t* __restrict__ bestb, uint32_t C, const uint32_t* __restrict__ off, uint32_t b0,
+                 T* __restrict__ Rg, uint32_t* __restrict__ bestg)
+{
+    __shared__ uint32_t s_trunc;
+    __shared__ T s_v[4];
+    __shared__ uint32_t s_c[4];
+    const uint32_t g = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t lo = off[g] - b0, hi = off[g + 1u] - b0;
+    T* row = Rg + (size_t)g * C;
+    if (tid == 0) s_trunc = 0u;
+    __syncthreads();
+    if (lo + tid < hi && bestb[lo + tid] == 0xffffffffu) s_trunc = 1u;       // (a group holds at most 256 members: one a thread)
+    __syncthreads();
+    if (s_trunc != 0u) {                                         // a truncated member: no class is claimed
+        for (uint32_t c = tid; c < C; c += 256u) row[c] = js_nan_of(T(0));
+        if (tid == 0) bestg[g] = 0xffffffffu;
+        return;
+    }
+    for (uint32_t c = tid; c < C; c += 256u) {
+        double q = 0.0;
+        for (uint32_t b = lo; b < hi; ++b) {
+            const double x = (double)R[(size_t)b * C + c];
+            q += x * x;
+        }
+        row[c] = (T)sqrt(q);
+    }
+    __threadfence_block();
+    __syncthreads();
+    // left-most arg-min of the row as stored (a NaN is never smaller): k_cls_finish's rule
+    T bv = row[0];
+    uint32_t bc = 0u;
+    for (uint32_t c = tid; c < C; c += 256u) {
+        const T v = row[c];
+        if (c != 0u && (v < bv || (v == bv && c < bc) || (bv != bv && v == v))) { bv = v; bc = c; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const T ov = __shfl_xor(bv, o);
+        const uint32_t oc = (uint32_t)__shfl_xor((int)bc, o);
+        if (ov < bv || (ov == bv && oc < bc) || (bv != bv && ov == ov)) { bv = ov; bc = oc; }
+    }
+    if (lane == 0u) { s_v[wave] = bv; s_c[wave] = bc; }
+    __syncthreads();
+    if (tid == 0) {
+        for (uint32_t w = 1; w < 4u; ++w) {
+            const T ov = s_v[w];
+            const uint32_t oc = s_c[w];
+            if (ov < bv || (ov == bv && oc < bc) || (bv != bv && ov == ov)) { bv = ov; bc = oc; }
+        }
+        bestg[g] = bc;
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+
+// grow() with an out-of-memory failure turned into the call's SS_HIP_ENOMEM and a message that names the bytes
+bool js_grow(JointState* js, size_t need, const char* who, char* err, size_t errlen)
+{
+    try {
+        grow(js->buf, js->bytes, need, "hipMalloc(joint coding workspace)");
+    } catch (const HipFail& f) {
+        if (f.code != hipErrorOutOfMemory) throw;
+        (void)hipGetLastError();
+        set_err(err, errlen, std::string(who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes");
+        return false;
+    }
+    return true;
+}
+
+// the checks of the offsets the host can make without reading them, in the order they are reported (B > 0)
+int js_check_groups(const char* who, const uint32_t* group_off, size_t Gn, size_t B, char* err, size_t errlen)
+{
+    if (!group_off || Gn == 0 || Gn > B) {
+        set_err(err, errlen, std::string(who) + ": group_off must not be null and must hold 1..B groups");
+        return SS_HIP_EINVAL;
+    }
+    return SS_HIP_OK;
+}
+
+// The offsets checked on the device (k_js_check) and fetched: hoff [Gn + 1].  Nothing of the caller's has been written when they are
+// wrong.  The workspace is grown for the staging alone: the caller carves it anew afterwards.
+int js_fetch_offsets(ss_hip_ctx* ctx, JointState* js, const char* who, const uint32_t* group_off, size_t Gn, size_t B, std::vector<uint32_t>& hoff,
+                     char* err, size_t errlen)
+{
+    hipStream_t st = ctx->stream;
+    Carver cv(nullptr);
+    cv.take<uint32_t>(1);
+    cv.take<uint32_t>(Gn + 1);
+    if (!js_grow(js, cv.off, who, err, errlen)) return SS_HIP_ENOMEM;
+    Carver cw(js->buf);
+    uint32_t* bad = cw.take<uint32_t>(1);
+    uint32_t* stage = cw.take<uint32_t>(Gn + 1);
+    const uint32_t* doff = group_off;
+    if (!on_device(group_off)) { HIPCHK(hipMemcpyAsync(stage, group_off, (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = stage; }
+    HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_js_check, dim3((uint32_t)((Gn + 256) / 256)), dim3(256), 0, st, doff, (uint32_t)Gn, (uint32_t)B, bad);
+    HIPCHK(hipGetLastError());
+    uint32_t first_bad = kTcNone;
+    hoff.resize(Gn + 1);
+    HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hoff.data(), doff, (Gn + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (first_bad != kTcNone) {
+        set_err(err, errlen, std::string(who) + ": group_off must start at 0, ascend strictly, end at B and hold no group of more than " +
+                                 std::to_string(kJsGroupMax) + " signals (first bad group: " + std::to_string(first_bad) + ")");
+        return SS_HIP_EINVAL;
+    }
+    return SS_HIP_OK;
+}
+
+// The chunks of a call: runs of whole groups [g0, g1) of at most `cap` signals and `budget` bytes (per_sig a signal, per_grp a group);
+// a group that exceeds either on its own is a chunk of its own.  -> the most signals and the most groups a chunk holds
+struct JsChunk { size_t g0, g1; };
+void js_chunks(const std::vector<uint32_t>& hoff, size_t cap, size_t budget, size_t per_sig, size_t per_grp, std::vector<JsChunk>& out,
+               size_t& max_sig, size_t& max_grp)
+{
+    const size_t Gn = hoff.size() - 1;
+    max_sig = max_grp = 0;
+    for (size_t g0 = 0; g0 < Gn;) {
+        size_t g1 = g0, sig = 0;
+        while (g1 < Gn) {
+            const size_t L = hoff[g1 + 1] - hoff[g1];
+            if (g1 > g0 && (sig + L > cap || (sig + L) * per_sig + (g1 - g0 + 1) * per_grp > budget)) break;
+            sig += L;
+            g1 += 1;
+        }
+        out.push_back({ g0, g1 });
+        max_sig = std::max(max_sig, sig);
+        max_grp = std::max(max_grp, g1 - g0);
+        g0 = g1;
+    }
+}
+
+template <typename T>
+int group_topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                       const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
+{
+    static const char* who = "group_top_correlations";
+    HIPCHK(hipSetDevice(ctx->device));
+    JointState* js = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t m = ctx->m, rb = records ? record_bytes(kmax, sizeof(T)) : 0;
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, n_pad = ctx->n_pad, Bu = (uint32_t)B;
+    const uint32_t rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
+    const bool rec_dev = records && on_device(records), y_dev = on_device(Y), off_dev = on_device(group_off);
+
+    std::vector<uint32_t> hoff;
+    int rc = js_fetch_offsets(ctx, js, who, group_off, Gn, B, hoff, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+
+    // the chunks: whole groups under topcorr.hip's byte budget and signal cap, plus a score row a group
+    const size_t per_sig = (size_t)ldm * sizeof(T) + (size_t)n_pad * sizeof(T) + (size_t)rtiles * 4u * sizeof(double) + (y_dev ? 0 : m * sizeof(T));
+    const size_t cap = ctx->tc_chunk_max > 0 ? std::min<size_t>(kTcChunkMax, (size_t)ctx->tc_chunk_max) : kTcChunkMax;
+    std::vector<JsChunk> chunks;
+    size_t max_sig = 0, max_grp = 0;
+    js_chunks(hoff, cap, kTcChunkBytes, per_sig, (size_t)n_pad * sizeof(double), chunks, max_sig, max_grp);
+    const size_t sig_pad = (max_sig + kTcTile - 1) / kTcTile * kTcTile;
+
+    auto carve = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        double* rinv = cv.take<double>(n_pad);
+        uint32_t* bad = cv.take<uint32_t>(1);
+        uint32_t* offs = off_dev ? nullptr : cv.take<uint32_t>(Gn + 1);
+        unsigned char* stage = (records && !rec_dev) ? cv.take<unsigned char>(B * rb) : nullptr;
+        uint32_t* oi = cv.take<uint32_t>(Gn * k);
+        double* os = cv.take<double>(Gn * k);
+        T* oc = cv.take<T>(B * k);
+        T* R = cv.take<T>(sig_pad * ldm);
+        T* D = cv.take<T>(sig_pad * n_pad);
+        double* part = cv.take<double>(max_sig * rtiles * 4u);
+        double* S = cv.take<double>(max_grp * n_pad);
+        T* ybuf = y_dev ? nullptr : cv.take<T>(max_sig * m);
+        use(rinv, bad, offs, stage, oi, os, oc, R, D, part, S, ybuf);
+        return cv.off;
+    };
+    if (!js_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+
+    carve(js->buf, [&](double* rinv, uint32_t* bad, uint32_t* offs, unsigned char* stage, uint32_t* oi, double* os, T* oc, T* R, T* D, double* part,
+                       double* S, T* ybuf) {
+        const uint32_t* doff = group_off;
+        if (!off_dev) { HIPCHK(hipMemcpyAsync(offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = offs; }
+        const unsigned char* din = static_cast<const unsigned char*>(records);
+        if (records) {
+            if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
+            HIPCHK(tc_launch_record_check(ctx, din, rb, kmax, Bu, bad));
+            uint32_t first_bad = kTcNone;
+            HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));            // (nothing has been written when a record is invalid)
+            if (first_bad != kTcNone) { rc = bad_index(first_bad, who, err, errlen); return; }
+        }
+        HIPCHK(coh_launch_norms<T>(ctx, rinv));
+        std::vector<T> tmp;
+        for (const JsChunk& ch : chunks) {
+            const size_t b0 = hoff[ch.g0];
+            const uint32_t Bc = hoff[ch.g1] - hoff[ch.g0], Gc = (uint32_t)(ch.g1 - ch.g0);
+            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
+            long long ys = y_stride, yi = incy;
+            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
+            const unsigned char* recs = records ? din + b0 * rb : nullptr;
+            HIPCHK(tc_launch_residual_block<T>(ctx, yd, ys, yi, recs, rb, kmax, Bc, R, part));
+            HIPCHK(tc_launch_dots<T>(ctx, R, Bc, D));
+            hipLaunchKernelGGL((k_js_scores<T>), dim3(n_pad / 256u, Gc), dim3(256), 0, st, (const T*)D, n, n_pad, (const double*)rinv, recs, rb, kmax,
+                               doff + ch.g0, (uint32_t)b0, S);
+            hipLaunchKernelGGL(k_js_select, dim3(Gc), dim3(256), 0, st, (const double*)S, n, n_pad, k, oi + ch.g0 * k, os + ch.g0 * k);
+            hipLaunchKernelGGL((k_js_coef<T>), dim3(Gc), dim3(256), 0, st, (const T*)D, n_pad, (const double*)rinv, doff + ch.g0, (uint32_t)b0, k,
+                               (const uint32_t*)(oi + ch.g0 * k), oc + b0 * k);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(idx, oi, Gn * k * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (coef) HIPCHK(hipMemcpyAsync(coef, oc, B * k * sizeof(T), hipMemcpyDefault, st));
+        if (score) HIPCHK(hipMemcpyAsync(score, os, Gn * k * sizeof(double), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return rc;
+}
+
+template <typename T>
+int group_topcorr_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                        const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
+{
+    static const char* who = "group_top_correlations";
+    // (without records kmax is ignored: the checks see a capacity that passes)
+    int rc = check_common<T>(ctx, who, records, false, records ? kmax : 1u, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !idx) { set_err(err, errlen, "group_top_correlations: Y and idx must not be null"); return SS_HIP_EINVAL; }
+    if (k == 0 || k > (uint32_t)SS_HIP_TOPCORR_KMAX) {
+        set_err(err, errlen, std::string(who) + ": k must be 1.." + std::to_string(SS_HIP_TOPCORR_KMAX));
+        return SS_HIP_EINVAL;
+    }
+    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "group_top_correlations: increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (B == 0) {
+        if (Gn != 0) { set_err(err, errlen, "group_top_correlations: no signals, but groups"); return SS_HIP_EINVAL; }
+        return SS_HIP_OK;                                     // (every argument above was checked all the same)
+    }
+    if (B >= 0x80000000ull) { set_err(err, errlen, "group_top_correlations: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if ((rc = js_check_groups(who, group_off, Gn, B, err, errlen)) != SS_HIP_OK) return rc;
+    return guarded(err, errlen, who, [&] {
+        return group_topcorr_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+    });
+}
+
+template <typename T>
+int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                       const uint32_t* group_off, size_t Gn, T* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen)
+{
+    static const char* who = "group_class_residuals";
+    HIPCHK(hipSetDevice(ctx->device));
+    JointState* js = state_of(ctx);
+    hipStream_t st = ctx->stream;
+    const size_t rb = record_bytes(kmax, sizeof(T));
+    const uint32_t C = classify_num_classes(ctx);
+    const bool off_dev = on_device(group_off);
+
+    std::vector<uint32_t> hoff;
+    int rc = js_fetch_offsets(ctx, js, who, group_off, Gn, B, hoff, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+
+    // the per-signal rows never leave the context: chunks of whole groups under a fixed byte budget
+    std::vector<JsChunk> chunks;
+    size_t max_sig = 0, max_grp = 0;
+    js_chunks(hoff, kTcChunkMax, kGcChunkBytes, (size_t)C * sizeof(T) + sizeof(uint32_t), 0, chunks, max_sig, max_grp);
+
+    auto carve = [&](unsigned char* base, auto&& use) {
+        Carver cv(base);
+        uint32_t* offs = off_dev ? nullptr : cv.take<uint32_t>(Gn + 1);
+        T* og = cv.take<T>(Gn * C);
+        uint32_t* ob = cv.take<uint32_t>(Gn);
+        T* Rb = cv.take<T>(max_sig * C);
+        uint32_t* bb = cv.take<uint32_t>(max_sig);
+        use(offs, og, ob, Rb, bb);
+        return cv.off;
+    };
+    if (!js_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+
+    carve(js->buf, [&](uint32_t* offs, T* og, uint32_t* ob, T* Rb, uint32_t* bb) {
+        const uint32_t* doff = group_off;
+        if (!off_dev) { HIPCHK(hipMemcpyAsync(offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = offs; }
+        for (const JsChunk& ch : chunks) {
+            const size_t b0 = hoff[ch.g0], Bc = hoff[ch.g1] - hoff[ch.g0];
+            rc = class_residual_rows<T>(ctx, who, Y + (ptrdiff_t)b0 * y_stride, Bc, y_stride, incy, static_cast<const unsigned char*>(records) + b0 * rb,
+                                        kmax, Rb, (ptrdiff_t)C, bb, err, errlen);
+            if (rc != SS_HIP_OK) return;                  // (a record index >= n: nothing of the caller's has been written)
+            hipLaunchKernelGGL((k_gc_reduce<T>), dim3((uint32_t)(ch.g1 - ch.g0)), dim3(256), 0, st, (const T*)Rb, (const uint32_t*)bb, C, doff + ch.g0,
+                               (uint32_t)b0, og + ch.g0 * C, ob + ch.g0);
+            HIPCHK(hipGetLastError());
+        }
+        if (Rg) HIPCHK(hipMemcpy2DAsync(Rg, (size_t)rg_stride * sizeof(T), og, (size_t)C * sizeof(T), (size_t)C * sizeof(T), Gn, hipMemcpyDefault, st));
+        HIPCHK(hipMemcpyAsync(best, ob, Gn * sizeof(uint32_t), hipMemcpyDefault, st));
+        HIPCHK(hipStreamSynchronize(st));
+    });
+    return rc;
+}
+
+template <typename T>
+int group_classes_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                        const uint32_t* group_off, size_t Gn, T* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen)
+{
+    static const char* who = "group_class_residuals";
+    int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    if (rc != SS_HIP_OK) return rc;
+    if (!Y || !best) { set_err(err, errlen, "group_class_residuals: Y and best must not be null"); return SS_HIP_EINVAL; }
+    const uint32_t C = classify_num_classes(ctx);
+    if (C == 0) { set_err(err, errlen, "group_class_residuals: no classes set (ss_hip_set_classes)"); return SS_HIP_EINVAL; }
+    if (B == 0) {
+        if (Gn != 0) { set_err(err, errlen, "group_class_residuals: no signals, but groups"); return SS_HIP_EINVAL; }
+        return SS_HIP_OK;
+    }
+    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "group_class_residuals: increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (Rg && rg_stride < (ptrdiff_t)C) { set_err(err, errlen, "group_class_residuals: rg_stride must be at least num_classes"); return SS_HIP_EINVAL; }
+    if (B >= 0x80000000ull) { set_err(err, errlen, "group_class_residuals: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if ((rc = js_check_groups(who, group_off, Gn, B, err, errlen)) != SS_HIP_OK) return rc;
+    return guarded(err, errlen, who, [&] {
+        return group_classes_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, Rg, rg_stride, best, err, errlen);
+    });
+}
+
+}  // namespace
+
+void joint_free(ss_hip_ctx* ctx)
+{
+    JointState* js = static_cast<JointState*>(ctx->js);
+    if (!js) return;
+    if (js->buf) (void)hipFree(js->buf);
+    delete js;
+    ctx->js = nullptr;
+}
+
+}  // namespace sship
+
+using namespace sship;
+
+extern "C" {
+
+int ss_hip_group_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                      uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, float* coef, double* score,
+                                      char* err, size_t errlen)
+{
+    return group_topcorr_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+}
+int ss_hip_group_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                      uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, double* coef, double* score,
+                                      char* err, size_t errlen)
+{
+    return group_topcorr_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+}
+
+int ss_hip_group_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                     uint32_t kmax, const uint32_t* group_off, size_t Gn, float* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err,
+                                     size_t errlen)
+{
+    return group_classes_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, Rg, rg_stride, best, err, errlen);
+}
+int ss_hip_group_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                                     uint32_t kmax, const uint32_t* group_off, size_t Gn, double* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err,
+                                     size_t errlen)
+{
+    return group_classes_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, Rg, rg_stride, best, err, errlen);
+}
+
+}  // extern "C"

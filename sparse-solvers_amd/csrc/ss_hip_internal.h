@@ -365,6 +365,7 @@ struct ss_hip_ctx {
     void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
     void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
     void* tc = nullptr;           // sship::TopCorrState* (topcorr.hip): the workspace of the top correlations and the record extension
+    void* js = nullptr;           // sship::JointState* (joint.hip): the workspace of the group top correlations and the group class residuals
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -533,6 +534,25 @@ void coherence_free(ss_hip_ctx* ctx);
 template <typename T> hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* rinv);
 // the top correlations and the record extension (topcorr.hip): releases their workspace
 void topcorr_free(ss_hip_ctx* ctx);
+// ... and the launches of a chunk's kernels the group top correlations (joint.hip) share with them, on the context's stream, every pointer on
+// the device.  tc_launch_record_check: bad[0] = the first of B records with a column index >= n (else 0xffffffff).
+// tc_launch_residual_block: R[b][0 .. ldm) for Bc <= 32768 signals — y_b - A x_b from recs on (dl_launch_residuals, with its partials in
+// part) or the words of y_b (recs == nullptr) — and zero rows behind them up to a whole tile of 128.  tc_launch_dots: D [tiles x 128][n_pad]
+// = the dots of those rows with every column (k_tc_tile)
+hipError_t tc_launch_record_check(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, uint32_t* bad);
+template <typename T>
+hipError_t tc_launch_residual_block(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
+                                    uint32_t Bc, T* R, double* part);
+template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uint32_t Bc, T* D);
+// the group top correlations and the group class residuals (joint.hip): releases their workspace
+void joint_free(ss_hip_ctx* ctx);
+// the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of
+// `r_stride` >= num_classes elements and best [B], the words of that call.  Y, records, R and best on either side; `who` names the
+// caller in an error's text.  classify_num_classes: the classes set on the context, 0 for none.  Throws what HIPCHK throws
+template <typename T>
+int class_residual_rows(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                        uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, char* err, size_t errlen);
+uint32_t classify_num_classes(const ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word
 // R[b][0] of that call (NaN for a truncated record).  Y, records, Rn on either side; `who` names the caller in an error's text
 template <typename T>

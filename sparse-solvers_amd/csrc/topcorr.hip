@@ -19,7 +19,8 @@
 //                 (score descending, index ascending) are found by a radix selection on the score's bits — eight bits a pass, LDS
 //                 histogram of integer counts — until the columns that can still be among the k best fit an LDS list of 1024, which is
 //                 sorted by the total order (bitonic).  All columns tied on the k-th score (a zero residual): the smallest indices
-//                 are taken in ascending blocks.
+//                 are taken in ascending blocks.  The selection behind the key is tc_select.h's tc_select_sorted, which joint.hip's
+//                 k_js_select calls with a group's stored score.
 //   k_tc_extend_check / k_tc_extend   the record extension: one workgroup per signal, the record in LDS, the entries of the row one
 //                 after the other (membership and insertion point across the threads, the move block by block from the top).
 //
@@ -37,8 +38,11 @@
 //                histogram's counts, the slots of the unsorted list) cannot change it: counts commute, and the list is sorted by a
 //                total order afterwards.  No floating-point atomics.
 // Nothing depends on B, on the chunking, on the launch geometry, on where the pointers live or on what the context did before.
+// tc_launch_record_check / tc_launch_residual_block / tc_launch_dots (ss_hip_internal.h) are the launches of a chunk's record check,
+// residual block and dot block: joint.hip runs the same kernels through them.
 #include "ss_hip_internal.h"
 #include "record_common.h"
+#include "tc_select.h"
 
 #include <algorithm>
 #include <cmath>
@@ -47,14 +51,9 @@ namespace sship {
 
 namespace {
 
-constexpr uint32_t kTcTile = 128;                        // signals and columns per tile
 constexpr uint32_t kTcVecs = 8;                          // 16-byte vectors of K per row and step (32 floats / 16 doubles)
 constexpr uint32_t kTcPitch = kTcVecs + 1;               // LDS row pitch in vectors (144 B, as in coherence.hip)
-constexpr uint32_t kTcNone = SS_HIP_TOPCORR_NONE;
-constexpr uint32_t kTcList = 1024;                       // entries of the selection's LDS list (>= 2 SS_HIP_TOPCORR_KMAX)
-constexpr uint32_t kTcChunkMax = 32768;                  // most signals per chunk (grid.y of the residual kernels)
-constexpr size_t kTcChunkBytes = (size_t)1536 << 20;     // the byte budget of a chunk's residuals and dots (never changes a result)
-static_assert(kTcList >= 2 * SS_HIP_TOPCORR_KMAX, "the list holds the k best and a boundary bin");
+// (kTcTile, kTcNone, kTcList, kTcChunkMax, kTcChunkBytes: tc_select.h, shared with joint.hip)
 
 typedef float tc_v4f __attribute__((ext_vector_type(4)));
 typedef float tc_v16f __attribute__((ext_vector_type(16)));
@@ -222,21 +221,15 @@ void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, 
         }
 }
 
-// (key, index): a comes before b when its score is larger, or equal with the smaller index; the keys are the bits of non-negative
-// doubles, which order as the doubles do
-__device__ inline bool tc_before(unsigned long long ka, uint32_t ia, unsigned long long kb, uint32_t ib) { return ka > kb || (ka == kb && ia < ib); }
-
-// D: the chunk's dots, row b of it is this workgroup's to strike columns out of; rec == nullptr: no records
+// D: the chunk's dots, row b of it is this workgroup's to strike columns out of; rec == nullptr: no records.  The selection itself
+// is tc_select.h's, with the key formed on the fly from the row of D and rn
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_tc_select(T* __restrict__ D, uint32_t n, uint32_t n_pad, const double* __restrict__ rinv, const unsigned char* __restrict__ rec,
                  size_t rb, uint32_t kmax, uint32_t k, uint32_t* __restrict__ oidx, T* __restrict__ ocoef, double* __restrict__ oscore)
 {
-    __shared__ unsigned long long lkey[kTcList];
-    __shared__ uint32_t lidx[kTcList];
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t sh[4], wcnt[4];
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ TcSelectLds lds;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
     T* d = D + (size_t)b * n_pad;
     oidx += (size_t)b * k;
     ocoef += (size_t)b * k;
@@ -262,99 +255,14 @@ void k_tc_select(T* __restrict__ D, uint32_t n, uint32_t n_pad, const double* __
         key = (unsigned long long)__double_as_longlong(s);
         return true;
     };
-
-    // ---- radix selection: P = the bits above `shift` of the k-th best key so far as they are known, `above` columns lie in higher
-    // bins (all of them among the k best), `need` more come from the bin of P, which holds c columns ----
-    unsigned long long P = 0;
-    uint32_t need = k, above = 0, c = 0;
-    int shift = 56;
-    bool ties = false;
-    for (;;) {
-        hist[tid] = 0u;
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += 256u) {
-            unsigned long long key;
-            if (keyof(i, key) && (shift == 56 || (key >> (shift + 8)) == P)) atomicAdd(&hist[(uint32_t)(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t cum = 0, bin = 0;
-            bool found = false;
-            for (int bb = 255; bb >= 0; --bb) {
-                if (cum + hist[bb] >= need) { bin = (uint32_t)bb; found = true; break; }
-                cum += hist[bb];
-            }
-            if (!found) cum -= hist[0];                          // fewer candidates than k (first pass only): all of them, bin 0 last
-            sh[0] = bin;
-            sh[1] = cum;
-            sh[2] = hist[bin];
-        }
-        __syncthreads();
-        const uint32_t bin = sh[0], cum = sh[1];
-        c = sh[2];
-        above += cum;
-        need -= cum < need ? cum : need;
-        P = (P << 8) | bin;
-        if (above + c <= kTcList) break;
-        if (shift == 0) { ties = true; break; }
-        shift -= 8;
-    }
-
-    // ---- the list: every column above the bin, and the bin itself unless it is one exact score that more than the list share ----
-    if (tid == 0) sh[3] = 0u;
-    __syncthreads();
-    for (uint32_t i = tid; i < n; i += 256u) {
-        unsigned long long key;
-        if (!keyof(i, key)) continue;
-        const unsigned long long top = key >> shift;
-        if (top > P || (top == P && !ties)) {
-            const uint32_t slot = atomicAdd(&sh[3], 1u);
-            lkey[slot] = key;
-            lidx[slot] = i;
-        }
-    }
-    __syncthreads();
-    uint32_t L = sh[3];
-    if (ties) {
-        // every column of the bin has the key P: the `need` smallest indices, in ascending blocks of 256
-        for (uint32_t base = 0; base < n && need != 0u; base += 256u) {
-            const uint32_t i = base + tid;
-            unsigned long long key = 0;
-            const bool mine = i < n && keyof(i, key) && key == P;
-            const unsigned long long mask = __ballot(mine);
-            if (lane == 0) wcnt[wave] = (uint32_t)__popcll(mask);
-            __syncthreads();
-            uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-            for (uint32_t w = 0; w < 4u; ++w) { if (w < wave) before += wcnt[w]; total += wcnt[w]; }
-            if (mine && before < need) { lkey[L + before] = key; lidx[L + before] = i; }
-            const uint32_t taken = total < need ? total : need;
-            L += taken;
-            need -= taken;
-            __syncthreads();
-        }
-    }
-    uint32_t S = 1;
-    while (S < L) S <<= 1;
-    for (uint32_t t = L + tid; t < S; t += 256u) { lkey[t] = 0ull; lidx[t] = kTcNone; }      // (behind every column: the largest index)
-    for (uint32_t size = 2; size <= S; size <<= 1)
-        for (uint32_t stride = size >> 1; stride > 0u; stride >>= 1) {
-            __syncthreads();
-            for (uint32_t t = tid; t < S / 2u; t += 256u) {
-                const uint32_t lo = 2u * t - (t & (stride - 1u)), hi = lo + stride;
-                const unsigned long long ka = lkey[lo], kb = lkey[hi];
-                const uint32_t ia = lidx[lo], ib = lidx[hi];
-                const bool fwd = (lo & size) == 0u;
-                if (fwd ? tc_before(kb, ib, ka, ia) : tc_before(ka, ia, kb, ib)) { lkey[lo] = kb; lidx[lo] = ib; lkey[hi] = ka; lidx[hi] = ia; }
-            }
-        }
-    __syncthreads();
+    const uint32_t L = tc_select_sorted(lds, n, k, keyof);
     for (uint32_t t = tid; t < k; t += 256u) {
         if (t < L) {
-            const uint32_t i = lidx[t];
+            const uint32_t i = lds.lidx[t];
             const double r = rinv[i];
             oidx[t] = i;
             ocoef[t] = (T)((double)d[i] * (r * r));
-            oscore[t] = __longlong_as_double((long long)lkey[t]);
+            oscore[t] = __longlong_as_double((long long)lds.lkey[t]);
         } else {
             oidx[t] = kTcNone;
             ocoef[t] = T(0);
@@ -478,7 +386,7 @@ int topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrd
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, rb = records ? record_bytes(kmax, sizeof(T)) : 0;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, n_pad = ctx->n_pad, Bu = (uint32_t)B;
-    const uint32_t ctiles = (n + kTcTile - 1u) / kTcTile, rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
+    const uint32_t rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
     const bool rec_dev = records && on_device(records), y_dev = on_device(Y);
 
     // the chunk: whole signal tiles under the byte budget
@@ -510,33 +418,21 @@ int topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrd
         const unsigned char* din = static_cast<const unsigned char*>(records);
         if (records) {
             if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-            HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(k_tc_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, bad);
-            HIPCHK(hipGetLastError());
+            HIPCHK(tc_launch_record_check(ctx, din, rb, kmax, Bu, bad));
             uint32_t first_bad = kTcNone;
             HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));            // (nothing has been written when a record is invalid)
             if (first_bad != kTcNone) { rc = bad_index(first_bad, who, err, errlen); return; }
         }
         HIPCHK(coh_launch_norms<T>(ctx, rinv));
-        const T* At = static_cast<const T*>(ctx->At);
         std::vector<T> tmp;
         for (size_t b0 = 0; b0 < B; b0 += chunk) {
-            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0), btiles = (Bc + kTcTile - 1u) / kTcTile;
+            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
             const T* yd = Y + (ptrdiff_t)b0 * y_stride;
             long long ys = y_stride, yi = incy;
             if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-            // the rows behind the chunk's last signal, up to a whole tile: zero (their dots are never read).  The row of a truncated record
-            // is not written by the residual kernel either and holds what the workspace held: a tile's rows are independent of each
-            // other, and k_tc_select leaves such a signal before it reads a dot
-            if (btiles * kTcTile != Bc) HIPCHK(hipMemsetAsync(R + (size_t)Bc * ldm, 0, (size_t)(btiles * kTcTile - Bc) * ldm * sizeof(T), st));
-            if (records) HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, din + b0 * rb, rb, kmax, Bc, R, part));
-            else {
-                hipLaunchKernelGGL((k_tc_signals<T>), dim3((ldm + 255u) / 256u, Bc), dim3(256), 0, st, yd, ys, yi, (uint32_t)m, ldm, R);
-                HIPCHK(hipGetLastError());
-            }
-            hipLaunchKernelGGL((k_tc_tile<T>), dim3(btiles, ctiles), dim3(256), 0, st, At, ldm, (const T*)R, n_pad, D);
-            HIPCHK(hipGetLastError());
+            HIPCHK(tc_launch_residual_block<T>(ctx, yd, ys, yi, records ? din + b0 * rb : nullptr, rb, kmax, Bc, R, part));
+            HIPCHK(tc_launch_dots<T>(ctx, R, Bc, D));
             hipLaunchKernelGGL((k_tc_select<T>), dim3(Bc), dim3(256), 0, st, D, n, n_pad, (const double*)rinv, records ? din + b0 * rb : nullptr, rb,
                                kmax, k, oi + b0 * k, oc + b0 * k, os + b0 * k);
             HIPCHK(hipGetLastError());
@@ -653,6 +549,48 @@ int extend_entry(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, 
 }
 
 }  // namespace
+
+// ---- the launches joint.hip shares (ss_hip_internal.h), on the context's stream, every pointer on the device -----------------------
+
+hipError_t tc_launch_record_check(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, uint32_t* bad)
+{
+    hipError_t e = hipMemsetAsync(bad, 0xff, sizeof(uint32_t), ctx->stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_tc_check, dim3(B), dim3(64), 0, ctx->stream, recs, rb, kmax, (uint32_t)ctx->n, bad);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t tc_launch_residual_block(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
+                                    uint32_t Bc, T* R, double* part)
+{
+    const uint32_t ldm = ctx->ldm, btiles = (Bc + kTcTile - 1u) / kTcTile;
+    // the rows behind the chunk's last signal, up to a whole tile: zero (their dots are never read).  The row of a truncated record
+    // is not written by the residual kernel either and holds what the workspace held: a tile's rows are independent of each
+    // other, and the selection leaves such a signal (or its group) before it reads a dot
+    if (btiles * kTcTile != Bc) {
+        const hipError_t e = hipMemsetAsync(R + (size_t)Bc * ldm, 0, (size_t)(btiles * kTcTile - Bc) * ldm * sizeof(T), ctx->stream);
+        if (e != hipSuccess) return e;
+    }
+    if (recs) return dl_launch_residuals<T>(ctx, yd, ys, yi, recs, rb, kmax, Bc, R, part);
+    hipLaunchKernelGGL((k_tc_signals<T>), dim3((ldm + 255u) / 256u, Bc), dim3(256), 0, ctx->stream, yd, ys, yi, (uint32_t)ctx->m, ldm, R);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uint32_t Bc, T* D)
+{
+    const uint32_t btiles = (Bc + kTcTile - 1u) / kTcTile, ctiles = ((uint32_t)ctx->n + kTcTile - 1u) / kTcTile;
+    hipLaunchKernelGGL((k_tc_tile<T>), dim3(btiles, ctiles), dim3(256), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm, R, ctx->n_pad, D);
+    return hipGetLastError();
+}
+
+template hipError_t tc_launch_residual_block<float>(ss_hip_ctx*, const float*, long long, long long, const unsigned char*, size_t, uint32_t, uint32_t,
+                                                    float*, double*);
+template hipError_t tc_launch_residual_block<double>(ss_hip_ctx*, const double*, long long, long long, const unsigned char*, size_t, uint32_t,
+                                                     uint32_t, double*, double*);
+template hipError_t tc_launch_dots<float>(ss_hip_ctx*, const float*, uint32_t, float*);
+template hipError_t tc_launch_dots<double>(ss_hip_ctx*, const double*, uint32_t, double*);
 
 void topcorr_free(ss_hip_ctx* ctx)
 {

@@ -153,6 +153,8 @@ _PROTOTYPES = [
     ("ss_hip_atom_coherence_", _int, [_vp, _vp, _sz, _vp, _vp] + _ERR),
     ("ss_hip_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_extend_records_", _int, [_vp, _vp, _sz, _u32, _vp, _vp, _u32, _vp, _vp] + _ERR),
+    ("ss_hip_group_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_group_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _vp, _pd, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
     ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
     ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
@@ -766,6 +768,161 @@ class Homotopy(_Context):
             if tolerance is not None:
                 frozen = frozen | (good & (resnorm <= float(tolerance)))
         return cur, resnorm, status
+
+    # ---- joint sparse coding of signal groups (include/ss_hip.h, csrc/joint.hip) ------------------------------------------------
+
+    GROUP_MAX = 256
+
+    def _groups(self, groups, B):
+        """`groups` of the joint calls -> (pointer, Gn, keepalive, offsets (Gn + 1,) int64 numpy).  An integer L means equal groups
+        of L consecutive signals (B must be a multiple of L); anything else is the (Gn + 1,) offsets themselves — integers, a numpy
+        array or an int32 / uint32 torch tensor on either side — which the library validates."""
+        if isinstance(groups, (int, np.integer)):
+            L = int(groups)
+            if L < 1:
+                raise ValueError("a group holds at least one signal")
+            if B % L:
+                raise ValueError("B = %d is not a multiple of the group size %d" % (B, L))
+            groups = np.arange(0, B + 1, L, dtype=np.uint32)
+        ptr, count, keep, dev = _index_list(groups, "groups", scalar=False)
+        if count < 1:
+            raise ValueError("groups must hold Gn + 1 offsets")
+        host = keep.cpu().numpy() if hasattr(keep, "data_ptr") else keep
+        return ptr, count - 1, keep, host.astype(np.int64) & 0xffffffff
+
+    def group_top_correlations(self, Y, groups, k, records=None, kmax=None, coef=True, score=True):
+        """The group top correlations (include/ss_hip.h, ss_hip_group_top_correlations_*): for every group of consecutive signals
+        the k columns, stored in no member's record, with the largest sqrt(sum_b (a_i . r_b)^2) / ||a_i|| over the members' residuals
+        -> (idx (Gn, k), coef (B, k) or None, score (Gn, k) float64 or None), by descending score, ties by ascending index.
+        coef[b] holds member b's own single-atom coefficients at its group's columns (what extend_records takes).  groups: an
+        integer L for equal groups (B a multiple of L), else the (Gn + 1,) offsets; a group holds at most GROUP_MAX signals.
+        records, kmax, the entries behind the last candidate, the dtypes and where the outputs live: as for top_correlations.
+        A group of one returns top_correlations' words."""
+        if records is None:
+            Yp, B, ys, incy = self._signals(Y)
+            rp, kmax = None, 0
+            if not B:
+                ys, incy = self.m, 1
+        else:
+            if kmax is None:
+                raise ValueError("kmax must be given with records")
+            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        gp, Gn, keepg, _ = self._groups(groups, B)
+        k = int(k)
+        dev = _device_of(Y)
+        idx, ip = _alloc(dev, (Gn, k), np.uint32, self.TOPCORR_NONE)
+        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
+        sc, sp = _alloc(dev, (Gn, k) if score else None, np.float64, 0.0)
+        _sync_producers(Y, records, idx)
+        _sync_producers(groups)
+        _call(self._fn("ss_hip_group_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), gp, Gn, k, ip, cp, sp)
+        return idx, cf, sc
+
+    def group_class_residuals(self, Y, records, kmax, groups, residuals=True):
+        """The group class residuals (include/ss_hip.h, ss_hip_group_class_residuals_*) -> (best (Gn,), Rg (Gn, num_classes) or
+        None): Rg[g, c] = sqrt(sum_b R[b, c]^2) over the members' rows of class_residuals, best = its left-most arg-min (uint32;
+        0xffffffff and a NaN row for a group with a truncated member).  groups: as for group_top_correlations.  The outputs live
+        where Y lives (device tensors for a device Y — best then int32 — else numpy arrays)."""
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        gp, Gn, keepg, _ = self._groups(groups, B)
+        C = self.num_classes or 1          # (without classes the library reports the error)
+        dev = _device_of(Y)
+        best, bp = _alloc(dev, (Gn,), np.uint32)
+        Rg, Rp = _alloc(dev, (Gn, C) if residuals else None, self.dtype)
+        _sync_producers(Y, records)
+        _sync_producers(groups)
+        _call(self._fn("ss_hip_group_class_residuals_"), self._h, Yp, B, ys, incy, rp, int(kmax), gp, Gn, Rp, C, bp)
+        return best, Rg
+
+    @staticmethod
+    def _group_norms(resnorm, off):
+        """sqrt(sum_b resnorm_b^2) per group in double: one accumulator from 0, the members ascending (numpy, host)"""
+        size = np.diff(off)
+        acc = np.zeros(len(size))
+        for j in range(int(size.max()) if len(size) else 0):
+            has = size > j
+            v = resnorm[off[:-1][has] + j]
+            acc[has] = acc[has] + v * v
+        return np.sqrt(acc)
+
+    def joint_stagewise_code(self, Y, groups, stages, per_stage, kmax=96, tolerance=None, records=None):
+        """Simultaneous stagewise OMP from the record calls, and nothing more -> (records, resnorm (B,) float64, status (B,),
+        group_resnorm (Gn,) float64).  From empty records (K = 0) or a copy of `records`, every stage runs
+        group_top_correlations(per_stage) -> the group's idx row for each of its members -> extend_records with the members' own
+        coef -> refit_records: the members of a group share one support, each is fitted on it alone.  A group is frozen AS A WHOLE
+        when any member's refit is not REFIT_DONE — all its members then take back their records from before the stage — or, with a
+        `tolerance`, when group_resnorm = sqrt(sum_b resnorm_b^2) is at or below it after a stage; a frozen group enters no more
+        columns and rides along with TOPCORR_NONE rows.  resnorm and status are those of the last refit that set the signal's
+        record (status: of the stage that froze its group, member by member); before any they read NaN and REFIT_EMPTY.
+        groups: as for group_top_correlations.  stages >= 1.  The records live where `records` lives, or where Y lives without;
+        resnorm, status and group_resnorm where Y lives (status int32 on a device)."""
+        kmax = int(kmax)
+        if int(stages) < 1:
+            raise ValueError("stages must be at least 1")
+        if kmax > self.REFIT_KMAX:
+            raise ValueError("kmax must not exceed REFIT_KMAX = %d" % self.REFIT_KMAX)
+        B = self._signals(Y)[1]
+        _, Gn, keepg, off = self._groups(groups, B)
+        dev = _device_of(Y)
+        if records is None:
+            if dev is None:
+                cur = np.zeros((B, self.record_bytes(kmax)), dtype=np.uint8)
+            else:
+                import torch
+                cur = torch.zeros((B, self.record_bytes(kmax)), dtype=torch.uint8, device=dev)
+        else:
+            _records(records, self.record_bytes(kmax), B=B, other="Y")
+            cur = records.copy() if isinstance(records, np.ndarray) else records.clone()
+
+        def host(a):
+            return a.cpu().numpy() if hasattr(a, "data_ptr") else a
+
+        def beside(mask, like):
+            """a host mask or index as an index of `like`"""
+            if hasattr(like, "data_ptr"):
+                import torch
+                return torch.as_tensor(mask, device=like.device)
+            return mask
+
+        gid = np.repeat(np.arange(Gn), np.diff(off)) if Gn else np.zeros(0, dtype=np.int64)
+        frozen_g = np.zeros(Gn, dtype=bool)
+        resnorm = np.full(B, np.nan)
+        status = np.full(B, self.REFIT_EMPTY, dtype=np.uint32)
+        for _ in range(int(stages)):
+            if bool(frozen_g.all()):
+                break
+            idx_g, coef, _ = self.group_top_correlations(Y, keepg, per_stage, records=cur, kmax=kmax, score=False)
+            idx = idx_g[beside(gid, idx_g)]
+            frozen = frozen_g[gid]
+            idx[beside(frozen, idx)] = -1 if dev is not None else self.TOPCORR_NONE
+            ext, _ = self.extend_records(cur, kmax, idx, coef)
+            new, rn, st = self.refit_records(Y, ext, kmax)
+            rn, st = host(rn), host(st).astype(np.int64) & 0xffffffff
+            live = ~frozen
+            failed = np.zeros(Gn, dtype=bool)
+            failed[gid[live & (st != self.REFIT_DONE)]] = True
+            good = live & ~failed[gid]
+            g = beside(good, cur)
+            cur[g] = new[g]
+            resnorm[good] = rn[good]
+            status[live] = st[live]
+            frozen_g = frozen_g | failed
+            if tolerance is not None:
+                frozen_g = frozen_g | (~failed & (self._group_norms(resnorm, off) <= float(tolerance)))
+        gnorm = self._group_norms(resnorm, off)
+        if dev is not None:
+            import torch
+            resnorm, gnorm = torch.as_tensor(resnorm, device=dev), torch.as_tensor(gnorm, device=dev)
+            status = torch.as_tensor(status.view(np.int32), device=dev)
+        return cur, resnorm, status, gnorm
+
+    def classify_groups(self, Y, groups, stages, per_stage, kmax=96, tolerance=None, residuals=True):
+        """joint_stagewise_code followed by group_class_residuals -> (best (Gn,), Rg (Gn, num_classes) or None, records,
+        group_resnorm (Gn,)): every group coded on one shared support and given the class with the smallest residual summed over
+        its members.  Needs set_classes."""
+        records, _, _, gnorm = self.joint_stagewise_code(Y, groups, stages, per_stage, kmax=kmax, tolerance=tolerance)
+        best, Rg = self.group_class_residuals(Y, records, kmax, groups, residuals=residuals)
+        return best, Rg, records, gnorm
 
     def _record_usage(self, records, kmax):
         """-> (usage (n,) uint32, K (B,) int64), numpy: the number of counting records (K <= kmax) that hold each column, and every

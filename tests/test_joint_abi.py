@@ -1,0 +1,219 @@
+"""CPU-only checks of joint sparse coding of signal groups (include/ss_hip.h, ss_hip_group_top_correlations_*,
+ss_hip_group_class_residuals_*, added under ABI version 7): the header declares both pairs with the agreed prototypes and
+SS_HIP_GROUP_MAX, the library exports them, the ctypes binding gives them the header's argument types, sship.Homotopy has the four
+methods, and a stub library shows the words each method passes — an integer `groups` turned into offsets, a B that is no multiple
+of it refused before any call.  No compute calls (no GPU here)."""
+import ctypes
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import abi_common
+from abi_common import ROOT
+
+
+def _top(T):
+    return ["ss_hip_ctx*", "const %s*" % T, "size_t", "ptrdiff_t", "ptrdiff_t", "const void*", "uint32_t", "const uint32_t*", "size_t",
+            "uint32_t", "uint32_t*", "%s*" % T, "double*", "char*", "size_t"]
+
+
+def _cls(T):
+    return ["ss_hip_ctx*", "const %s*" % T, "size_t", "ptrdiff_t", "ptrdiff_t", "const void*", "uint32_t", "const uint32_t*", "size_t",
+            "%s*" % T, "ptrdiff_t", "uint32_t*", "char*", "size_t"]
+
+
+PROTOTYPES = {"ss_hip_group_top_correlations_f32": _top("float"), "ss_hip_group_top_correlations_f64": _top("double"),
+              "ss_hip_group_class_residuals_f32": _cls("float"), "ss_hip_group_class_residuals_f64": _cls("double")}
+
+
+@pytest.fixture(scope="module")
+def built():
+    return abi_common.build()
+
+
+def test_header_declares_both_pairs():
+    for name, want in PROTOTYPES.items():
+        assert abi_common.prototype(name) == want, (name, abi_common.prototype(name))
+
+
+def test_header_defines_group_max_and_keeps_the_abi_version():
+    hdr = abi_common.header()
+    assert re.search(r"#define\s+SS_HIP_GROUP_MAX\s+256\b", hdr)
+    assert re.search(r"#define\s+SS_HIP_ABI_VERSION\s+7\b", hdr)
+    for stem in ("ss_hip_group_top_correlations_", "ss_hip_group_class_residuals_"):
+        comment = hdr[:hdr.index("int %sf32" % stem)]
+        comment = comment[comment.rindex("/*\n"):]                    # (the block comment, not the remark on the define)
+        assert re.search(r"added under ABI\s+\*?\s*version 7", comment), stem
+    # the proviso of the group-of-one pin is stated where the pin is
+    comment = hdr[:hdr.index("int ss_hip_group_top_correlations_f32")]
+    comment = comment[comment.rindex("/*\n"):]
+    assert "GROUP OF ONE" in comment and "underflows nor overflows" in comment
+
+
+def test_library_exports_them(built):
+    import sship
+    L = ctypes.CDLL(sship.LIB_PATH)
+    for name in PROTOTYPES:
+        assert hasattr(L, name), name
+        assert name in sship.SYMBOLS
+
+
+def test_binding_argtypes_match_the_header(built):
+    import sship
+    L = sship.lib()
+    for name in PROTOTYPES:
+        want = [abi_common.CTYPE[p] for p in abi_common.prototype(name)]
+        got = list(getattr(L, name).argtypes)
+        assert got == want, (name, got, want)
+        assert getattr(L, name).restype == ctypes.c_int
+
+
+def test_python_surface_has_the_four_methods():
+    import sship
+    H = sship.Homotopy
+    sig = inspect.signature
+    assert list(sig(H.group_top_correlations).parameters) == ["self", "Y", "groups", "k", "records", "kmax", "coef", "score"]
+    assert list(sig(H.group_class_residuals).parameters) == ["self", "Y", "records", "kmax", "groups", "residuals"]
+    assert list(sig(H.joint_stagewise_code).parameters) == ["self", "Y", "groups", "stages", "per_stage", "kmax", "tolerance", "records"]
+    assert sig(H.joint_stagewise_code).parameters["kmax"].default == 96
+    assert list(sig(H.classify_groups).parameters)[:5] == ["self", "Y", "groups", "stages", "per_stage"]
+    assert H.GROUP_MAX == 256
+
+
+def test_the_unit_is_registered_with_separately_rounded_sums_and_shares_the_selection():
+    src = open(os.path.join(ROOT, "sparse-solvers_amd", "build.py")).read()
+    assert re.search(r'\("joint\.hip",\s*\[[^\]]*"-ffp-contract=off"', src)
+    csrc = os.path.join(ROOT, "sparse-solvers_amd", "csrc")
+    joint, top = open(os.path.join(csrc, "joint.hip")).read(), open(os.path.join(csrc, "topcorr.hip")).read()
+    # one selection, stated in the shared header and called by both kernels; the MFMA main loop is not stated a third time
+    assert "tc_select_sorted(" in joint and "tc_select_sorted(" in top
+    assert "__builtin_amdgcn_mfma" not in joint
+    for launcher in ("tc_launch_record_check", "tc_launch_residual_block", "tc_launch_dots"):
+        assert launcher in joint and launcher in top
+
+
+# ---- the words each method passes: sship._lib is a stub that records every call and returns 0 ---------------------------------------
+
+H_, M, N, KMAX = 0xABC0, 5, 7, 3
+RB = {np.float32: 40, np.float64: 56}                                   # record_bytes(kmax = 3)
+
+
+class Stub:
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("ss_hip_"):
+            raise AttributeError(name)
+
+        def fn(*args):
+            if name == "ss_hip_record_bytes":
+                return (16 + args[0] * (4 + (8 if args[1] else 4)) + 7) & ~7
+            words = list(args)
+            if name.startswith("ss_hip_group_"):
+                # the offsets as the library would read them, while the method's temporaries are alive
+                words[7] = list((ctypes.c_uint32 * (args[8] + 1)).from_address(args[7]))
+            if name.startswith("ss_hip_refit_records_"):             # every refit succeeds: status REFIT_DONE, resnorm 0
+                ctypes.memset(args[9], 0, 4 * args[2])
+                ctypes.memset(args[8], 0, 8 * args[2])
+            self.calls.append((name, tuple(words[:-2])))
+            return 0
+        return fn
+
+
+@pytest.fixture
+def stub(monkeypatch):
+    import sship
+    s = Stub()
+    monkeypatch.setattr(sship, "_lib", s)
+    made = []
+    s.made = made
+    yield s
+    for o in made:
+        o._h = None
+
+
+def make(stub, dt, num_classes=0):
+    import sship
+    o = object.__new__(sship.Homotopy)
+    o.m, o.n, o.dtype, o.suffix, o.ctype, o.num_classes, o._h = M, N, np.dtype(dt), "f32" if dt == np.float32 else "f64", None, num_classes, H_
+    stub.made.append(o)
+    return o
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_group_top_correlations_words(stub, dt):
+    h = make(stub, dt)
+    B, k = 6, 4
+    Y = np.zeros((B, M), dtype=dt)
+    idx, coef, score = h.group_top_correlations(Y, 3, k)
+    assert idx.shape == (2, k) and idx.dtype == np.uint32 and np.all(idx == 0xffffffff)
+    assert coef.shape == (B, k) and coef.dtype == dt and score.shape == (2, k) and score.dtype == np.float64
+    name, w = stub.calls[-1]
+    assert name == "ss_hip_group_top_correlations_" + h.suffix
+    assert w == (H_, Y.ctypes.data, B, M, 1, None, 0, [0, 3, 6], 2, k, idx.ctypes.data, coef.ctypes.data, score.ctypes.data)
+    # offsets as given, records, one output alone
+    rec = np.zeros((B, RB[dt]), dtype=np.uint8)
+    idx, coef, score = h.group_top_correlations(Y, [0, 1, 6], k, records=rec, kmax=KMAX, coef=False, score=False)
+    assert coef is None and score is None and idx.shape == (2, k)
+    name, w = stub.calls[-1]
+    assert w == (H_, Y.ctypes.data, B, M, 1, rec.ctypes.data, KMAX, [0, 1, 6], 2, k, idx.ctypes.data, None, None)
+    # groups = 1: every signal its own group
+    h.group_top_correlations(Y, 1, k)
+    assert stub.calls[-1][1][7:9] == (list(range(B + 1)), B)
+    # no signals: no groups, the strides of a contiguous batch
+    idx, coef, score = h.group_top_correlations(np.zeros((0, M), dtype=dt), 2, k)
+    assert idx.shape == (0, k) and coef.shape == (0, k)
+    assert stub.calls[-1][1][2:10] == (0, M, 1, None, 0, [0], 0, k)
+
+
+def test_bad_groups_raise_before_any_call(stub):
+    h = make(stub, np.float32)
+    Y = np.zeros((6, M), dtype=np.float32)
+    rec = np.zeros((6, RB[np.float32]), dtype=np.uint8)
+    for call in (lambda g: h.group_top_correlations(Y, g, 2), lambda g: h.group_class_residuals(Y, rec, KMAX, g),
+                 lambda g: h.joint_stagewise_code(Y, g, 1, 2, kmax=KMAX)):
+        for bad in (4, 0, -1, [], np.zeros(3)):
+            with pytest.raises(ValueError):
+                call(bad)
+    with pytest.raises(ValueError):
+        h.group_top_correlations(Y, 3, 2, records=rec)                  # kmax must be given with records
+    with pytest.raises(ValueError):
+        h.joint_stagewise_code(Y, 3, 0, 2, kmax=KMAX)
+    with pytest.raises(ValueError):
+        h.joint_stagewise_code(Y, 3, 1, 2, kmax=h.REFIT_KMAX + 1)
+    assert stub.calls == []
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+def test_group_class_residuals_words(stub, dt):
+    h = make(stub, dt, num_classes=4)
+    B = 6
+    Y = np.zeros((B, M), dtype=dt)
+    rec = np.zeros((B, RB[dt]), dtype=np.uint8)
+    best, Rg = h.group_class_residuals(Y, rec, KMAX, 2)
+    assert best.shape == (3,) and best.dtype == np.uint32 and Rg.shape == (3, 4) and Rg.dtype == dt
+    name, w = stub.calls[-1]
+    assert name == "ss_hip_group_class_residuals_" + h.suffix
+    assert w == (H_, Y.ctypes.data, B, M, 1, rec.ctypes.data, KMAX, [0, 2, 4, 6], 3, Rg.ctypes.data, 4, best.ctypes.data)
+    best, Rg = h.group_class_residuals(Y, rec, KMAX, np.array([0, 5, 6]), residuals=False)
+    assert Rg is None and stub.calls[-1][1][7:12] == ([0, 5, 6], 2, None, 4, best.ctypes.data)
+
+
+def test_joint_stagewise_code_is_the_four_calls(stub):
+    """with a stub every refit reads status 0 = REFIT_DONE: two stages are two rounds of the three calls, the group's offsets passed on"""
+    h = make(stub, np.float32, num_classes=2)
+    Y = np.zeros((5, M), dtype=np.float32)
+    rec, resnorm, status, gnorm = h.joint_stagewise_code(Y, [0, 2, 5], 2, 2, kmax=KMAX)
+    names = [c[0] for c in stub.calls]
+    assert names == ["ss_hip_group_top_correlations_f32", "ss_hip_extend_records_f32", "ss_hip_refit_records_f32"] * 2
+    assert all(c[1][7:10] == ([0, 2, 5], 2, 2) for c in stub.calls if c[0].startswith("ss_hip_group_"))
+    assert rec.shape == (5, RB[np.float32]) and resnorm.shape == (5,) and status.shape == (5,) and gnorm.shape == (2,)
+    stub.calls.clear()
+    best, Rg, rec, gnorm = h.classify_groups(Y, [0, 2, 5], 1, 2, kmax=KMAX)
+    assert [c[0] for c in stub.calls] == ["ss_hip_group_top_correlations_f32", "ss_hip_extend_records_f32", "ss_hip_refit_records_f32",
+                                          "ss_hip_group_class_residuals_f32"]
+    assert best.shape == (2,) and Rg.shape == (2, 2)
