@@ -624,6 +624,102 @@ int ss_hip_group_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B,
                                      double* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen);
 
 /*
+ * Weighted coding — the weighted top correlations: the selection under a non-negative weight per row and signal, the primitive of
+ * coding under occlusion, masks of observed rows and robust (IRLS-style) weights: min sum_k w_kb (y_b - A x)_k^2 (added under ABI
+ * version 7; csrc/weighted.hip; NOT in the reference).  One stage of the weighted coder = this call, ss_hip_extend_records_*,
+ * ss_hip_weighted_refit_records_*.
+ * WEIGHTS, common to the three weighted calls: W holds a weight for every row of every signal in the context's element type, row b
+ * at W[b*w_stride + k], k < m (unit increment); w_stride == 0 is ONE weight vector shared by all signals (a common mask), else
+ * w_stride >= m.  W may be a host or a device pointer.  Every weight must be finite and >= 0: the first offender (the smallest
+ * signal, then row) is found on the device before anything is written, and the call returns SS_HIP_EINVAL with both in the message.
+ * The padding rows m .. ldm - 1 weigh zero.  A 0/1 mask is the special case.
+ * Y, records, kmax, k, idx, coef, score: as for ss_hip_top_correlations_*.  For signal b, with i over the n columns of A,
+ *     r_b       = the residual of ss_hip_top_correlations_* (its words);  rw_b = w_b o r_b, one multiplication in T
+ *     dot(i, b) = sum_k a_ki rw_kb          ss_hip_top_correlations_*' product on the matrix cores: one accumulator, one chain from 0
+ *                                           over the rows in ascending K-steps
+ *     d(i, b)   = sum_k w_kb (a_ki a_ki)    the same tile and chain with the operands (w_b, a_i o a_i), a_ki squared once in T: the
+ *                                           weighted norm of atom i as signal b sees it
+ *     d_i       = sum_k a_ki^2              in double (ss_hip_atom_coherence_*'s words), wmax_b = max_k w_kb
+ *     v(i, b)   = d(i, b) / (wmax_b d_i)    in double: the VISIBLE SHARE of atom i for signal b
+ *     s(i, b)   = |dot(i, b)| / sqrt(d(i, b))                                               in double
+ * The CANDIDATES of signal b are the columns i < n that record b does not store, with d_i finite and non-zero, d(i, b) > 0 and
+ * v(i, b) > min_visible (0 <= min_visible < 1); exclusion is by index mask and comparison, never by arithmetic; a candidate whose
+ * score is NaN is never selected.  A signal whose weights are all zero has no candidates.
+ *     idx[b][t]   the candidates by descending score, ties by ascending index, t = 0 .. k - 1
+ *     score[b][t] (may be NULL) the candidate's score
+ *     coef[b][t]  (may be NULL) (T)((double)dot / (double)d(i, b)): the weighted least-squares coefficient of r_b on that atom alone
+ * Entries beyond the number of candidates are SS_HIP_TOPCORR_NONE in idx and 0 in coef and score; a truncated record (K > kmax)
+ * yields such entries throughout.  1 <= k <= SS_HIP_TOPCORR_KMAX.  The signals run in chunks under ss_hip_top_correlations_*' byte
+ * budget (option "tc_chunk_max"); the workspace — per chunk the residuals and the weights, [.][ldm] each, and the two dot blocks,
+ * [.][n_pad] each; per call a host caller's weights — is the context's, grown on demand, freed with it.
+ * ARITHMETIC (one documented order: csrc/weighted.hip): |s - s_float64| <= (2 gamma_{m+1} + 1e-12) ||r_b||_w with
+ * ||r||_w = sqrt(sum_k w_k r_k^2), gamma_j = j u / (1 - j u), u = 2^-24 (fp32) or 2^-53 (fp64), s_float64 formed from the same words
+ * of A, w_b and r_b.
+ * CONTRACT: row b of the outputs is a function of A, y_b, w_b, record b, k and min_visible alone — bit for bit the same alone or in
+ * any batch, in any batch order, with host or device pointers, across the chunking, with w_stride == 0 or a W whose rows repeat the
+ * vector, whatever the context did before; after a column replacement it is a fresh context's result.  PREFIX PROPERTY in k.  No
+ * floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  ss_hip_top_correlations_*' list, and: a null W; a negative w_stride or one in 1 .. m - 1; min_visible outside
+ *                  [0, 1); a weight that is negative or not finite (found on the device)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+int ss_hip_weighted_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                         const float* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                         double min_visible, uint32_t k,
+                                         uint32_t* idx, float* coef, double* score, char* err, size_t errlen);
+int ss_hip_weighted_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                         const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                         double min_visible, uint32_t k,
+                                         uint32_t* idx, double* coef, double* score, char* err, size_t errlen);
+
+/*
+ * The weighted refit: ss_hip_refit_records_* under the weights above (added under ABI version 7; csrc/weighted.hip, the kernels
+ * of csrc/refit.hip with a weight flag; NOT in the reference).  For signal b with the record's stored columns S,
+ *     z = argmin sum_k w_kb (y_b - A_S z)_k^2,      the solution of (A_S^T W_b A_S) z = A_S^T W_b y_b, W_b = diag(w_b).
+ * The panel, the row chunks of 1024, the tiles, the MFMA instructions and the summation order are ss_hip_refit_records_*'; the weight
+ * is applied while the panel is staged: ONE operand of every product is multiplied by w_k in T (not both by sqrt(w_k)), so an
+ * element of a chunk partial is the chain of fma(P[r][i] w_r, P[r][j], .).  Then the same solve: Cholesky in double, the same pivot
+ * test against the weighted diagonal, the same SS_HIP_REFIT_* status codes (no new ones; a signal whose weights are all zero is
+ * SS_HIP_REFIT_SINGULAR, or SS_HIP_REFIT_EMPTY when K == 0).
+ *     resnorm[b] (may be NULL) = sqrt(sum_k w_kb (y_b - A x_b)_k^2) of the record as written: the words
+ *                ss_hip_weighted_class_residuals_* gives with every column in class 0
+ * PINNED: with every weight exactly 1 the output records, status and resnorm are bit for bit those of ss_hip_refit_records_*; with a
+ * 0/1 mask they are those of ss_hip_refit_records_* on a context created from diag(w) A with the signals w o y.
+ * CONTRACT and validation: as for ss_hip_refit_records_*, with w_b among what a signal's words are a function of (w_stride == 0 or
+ * repeated rows: the same words), and
+ *   SS_HIP_EINVAL  a null W; a negative w_stride or one in 1 .. m - 1; a weight that is negative or not finite
+ */
+int ss_hip_weighted_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const float* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                      void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen);
+int ss_hip_weighted_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                      void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen);
+
+/*
+ * The weighted class residuals: ss_hip_class_residuals_* under the weights above (added under ABI version 7; csrc/weighted.hip, the
+ * kernels of csrc/classify.hip with a weight flag; NOT in the reference).  Needs ss_hip_set_classes.
+ *     R[b*r_stride + c] = sqrt(sum_k w_kb (y_b - A delta_c(x_b))_k^2)    (a class without a stored entry gets ||y_b||_w)
+ * d_k = y_k - (A delta_c x)_k in the context's precision as in the unweighted call, its square in double, multiplied by (double)w_kb
+ * before it enters the unweighted call's sums, in their order.  best[b] and sci[b] are formed as in the unweighted call; sci
+ * depends on the record alone.  A class none of whose rows is visible reads 0 like any other (and may win the arg-min: the caller
+ * who masks everything has asked for it).
+ * PINNED: with every weight exactly 1 every output word equals ss_hip_class_residuals_*'s; with a 0/1 mask, that call's words on a
+ * context created from diag(w) A with the signals w o y.
+ * CONTRACT and validation: as for ss_hip_class_residuals_*, with w_b among what a signal's words are a function of, and
+ *   SS_HIP_EINVAL  a null W; a negative w_stride or one in 1 .. m - 1; a weight that is negative or not finite
+ */
+int ss_hip_weighted_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                        const float* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                        float* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+int ss_hip_weighted_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                        const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                                        double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the

@@ -69,6 +69,8 @@ HIP_UNITS = [
     ("topcorr.hip", ["-ffp-contract=off"]),
     # the group top correlations and group class residuals: sums of squares in double in the documented order, so the same flags
     ("joint.hip", ["-ffp-contract=off"]),
+    # weighted coding: the weighted top correlations beside topcorr.hip's tile (the weighted norms are its second product), so the same flags
+    ("weighted.hip", ["-ffp-contract=off"]),
 ]
 
 

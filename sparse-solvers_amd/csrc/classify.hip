@@ -28,6 +28,9 @@
 //              in ascending class order.
 // No floating-point atomics; nothing depends on B, on the chunking or on the launch geometry: a signal's words are a function of its
 // record, its y, the labels and A.
+// The weighted class residuals (ss_hip_weighted_class_residuals_*, weighted.hip) are this unit with a flag: class_residuals_weighted is
+// class_residuals_entry with the weights checked and brought to the device, k_cls_residual<T, false, true> multiplies every square
+// by (double)w_i before the sums above.  The unflagged instantiations are the code they were.
 #include "ss_hip_internal.h"
 #include "record_common.h"
 
@@ -160,12 +163,17 @@ void k_cls_prepare(const unsigned char* __restrict__ rec, size_t rb, uint32_t km
 
 // STORE: acc of ONE segment over all stored entries goes to yhat ([signals][ldm]); otherwise the tile's partial sums of squares
 // of every segment go to part ([signal][tile][segcap][4 waves]) and those of y to party ([signal][tile][4]).
-template <typename T, bool STORE>
+// WGT (the weighted class residuals, weighted.hip): every square, formed in double as before, is multiplied by (double)w_i — row i of
+// the signal's weights Wt[b * w_stride + i], 0 for the rows from m on — before it enters the same sums: sqrt(sum_i w_i d_i^2), and
+// ||y||_w for a class without entries.  With w_i == 1 the product is the square itself: the unweighted words.  A class none of
+// whose rows is visible reads 0 like any other.  Without WGT nothing is added and Wt is not read.
+template <typename T, bool STORE, bool WGT = false>
 __global__ __launch_bounds__(256)
 void k_cls_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __restrict__ Y, long long y_stride, long long incy,
                     const uint32_t* __restrict__ ord_idx, const T* __restrict__ ord_val, uint32_t kmax,
                     const uint32_t* __restrict__ seg, uint32_t segcap, const uint32_t* __restrict__ sig,
-                    double* __restrict__ part, double* __restrict__ party, T* __restrict__ yhat)
+                    double* __restrict__ part, double* __restrict__ party, T* __restrict__ yhat, const T* __restrict__ Wt = nullptr,
+                    long long w_stride = 0)
 {
     typedef typename ClsVec<T>::type V;
     constexpr uint32_t W = ClsVec<T>::W, L = ClsVec<T>::L, U = kClsInFlight;
@@ -180,6 +188,7 @@ void k_cls_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T*
     for (uint32_t j = 0; j < L; ++j) row0[j] = tile * kClsTileRows + j * (256u * W) + tid * W;
 
     T yv[L][W];
+    double wv[WGT ? L : 1u][W];
     if (!STORE) {
         const T* y = Y + (long long)b * y_stride;
         double s = 0.0;
@@ -189,7 +198,12 @@ void k_cls_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T*
             for (uint32_t e = 0; e < W; ++e) {
                 const uint32_t row = row0[j] + e;
                 yv[j][e] = row < m ? y[(long long)row * incy] : T(0);
-                s += (double)yv[j][e] * (double)yv[j][e];
+                if constexpr (WGT) {
+                    wv[j][e] = row < m ? (double)Wt[(long long)b * w_stride + row] : 0.0;
+                    s += ((double)yv[j][e] * (double)yv[j][e]) * wv[j][e];
+                } else {
+                    s += (double)yv[j][e] * (double)yv[j][e];
+                }
             }
         s = wave_sum(s);
         if (lane == 0u) party[((size_t)b * ntiles + tile) * 4u + wave] = s;
@@ -244,7 +258,8 @@ void k_cls_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T*
 #pragma unroll
                 for (uint32_t e = 0; e < W; ++e) {
                     const T d = yv[j][e] - acc[j][e];
-                    q += (double)d * (double)d;
+                    if constexpr (WGT) q += ((double)d * (double)d) * wv[j][e];
+                    else q += (double)d * (double)d;
                 }
             q = wave_sum(q);
             if (lane == 0u) part[(((size_t)b * ntiles + tile) * segcap + s) * 4u + wave] = q;
@@ -347,7 +362,7 @@ int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errl
 template <typename T>
 int residuals_impl(ss_hip_ctx* ctx, const char* who, const uint32_t* labels, uint32_t C, const T* Y, size_t B, ptrdiff_t y_stride,
                    ptrdiff_t incy, const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err,
-                   size_t errlen)
+                   size_t errlen, const T* Wd = nullptr, long long ws = 0)
 {
     HIPCHK(hipSetDevice(ctx->device));
     ClassifyState* cs = state_of(ctx);
@@ -393,9 +408,14 @@ int residuals_impl(ss_hip_ctx* ctx, const char* who, const uint32_t* labels, uin
             if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
             hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
                                labels, C, segcap, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
-            hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
-                               (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
-                               (const uint32_t*)sig, part, party, (T*)nullptr);
+            if (Wd)                                      // (the batch's weights on the device, validated: weights_on_device)
+                hipLaunchKernelGGL((k_cls_residual<T, false, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                                   (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
+                                   (const uint32_t*)sig, part, party, (T*)nullptr, Wd + (ptrdiff_t)b0 * ws, ws);
+            else
+                hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                                   (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
+                                   (const uint32_t*)sig, part, party, (T*)nullptr, (const T*)nullptr, 0ll);
             hipLaunchKernelGGL((k_cls_finish<T>), dim3(Bc), dim3(kClsThreads), 0, st, (const uint32_t*)seg, segcap, (const uint32_t*)sig,
                                (const double*)part, (const double*)party, ntiles, C, Rb, dbest);
             HIPCHK(hipGetLastError());
@@ -411,24 +431,35 @@ int residuals_impl(ss_hip_ctx* ctx, const char* who, const uint32_t* labels, uin
     return SS_HIP_OK;
 }
 
+// weighted: the call carries W / w_stride (ss_hip_weighted_class_residuals_*), checked and brought to the device behind the other checks
 template <typename T>
-int class_residuals_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                          T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+int class_residuals_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
+                          uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, bool weighted, const T* W, ptrdiff_t w_stride,
+                          char* err, size_t errlen)
 {
-    static const char* who = "class_residuals";
+    const std::string w(who);
     const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
     if (rc != SS_HIP_OK) return rc;
-    if (!Y || !best) { set_err(err, errlen, "class_residuals: Y and best must not be null"); return SS_HIP_EINVAL; }
+    if (!Y || !best) { set_err(err, errlen, w + ": Y and best must not be null"); return SS_HIP_EINVAL; }
     if (const int rq = check_classes(ctx, who, err, errlen)) return rq;
+    if (weighted)
+        if (const int rw = weights_check_args(ctx, who, W, w_stride, err, errlen)) return rw;
     if (B == 0) return SS_HIP_OK;
-    if (incy <= 0) { set_err(err, errlen, "class_residuals: increments must be positive"); return SS_HIP_EINVAL; }
+    if (incy <= 0) { set_err(err, errlen, w + ": increments must be positive"); return SS_HIP_EINVAL; }
     if (R && r_stride < (ptrdiff_t)static_cast<const ClassifyState*>(ctx->cls)->num_classes) {
-        set_err(err, errlen, "class_residuals: r_stride must be at least num_classes");
+        set_err(err, errlen, w + ": r_stride must be at least num_classes");
         return SS_HIP_EINVAL;
     }
-    return guarded(err, errlen, who, [&] {
+    return guarded(err, errlen, who, [&]() -> int {
         const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
-        return residuals_impl<T>(ctx, who, cs->labels, cs->num_classes, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+        const T* Wd = nullptr;
+        long long ws = 0;
+        if (weighted) {
+            const int rw = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &ws, err, errlen);
+            if (rw != SS_HIP_OK) return rw;
+        }
+        return residuals_impl<T>(ctx, who, cs->labels, cs->num_classes, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen,
+                                 Wd, ws);
     });
 }
 
@@ -476,7 +507,7 @@ int reconstruct_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t km
                                (const uint32_t*)nullptr, 1u, 1u, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
             hipLaunchKernelGGL((k_cls_residual<T, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
                                (uint32_t)m, (const T*)nullptr, 0ll, 1ll, (const uint32_t*)ord_idx, (const T*)ord_val, kmax,
-                               (const uint32_t*)seg, 1u, (const uint32_t*)sig, (double*)nullptr, (double*)nullptr, yh);
+                               (const uint32_t*)seg, 1u, (const uint32_t*)sig, (double*)nullptr, (double*)nullptr, yh, (const T*)nullptr, 0ll);
             HIPCHK(hipGetLastError());
             T* out = Yhat + (ptrdiff_t)b0 * yh_stride;
             if (rows2d) {
@@ -597,6 +628,35 @@ template int class_residual_rows<float>(ss_hip_ctx*, const char*, const float*, 
 template int class_residual_rows<double>(ss_hip_ctx*, const char*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, double*,
                                          ptrdiff_t, uint32_t*, char*, size_t);
 
+// the weighted forms (weighted.hip).  weighted_residual_rows: the residual path under weights already on the device and validated —
+// by_class: under the context's classes (set), else every column in class 0 (the weighted refit's residual norms).
+// class_residuals_weighted: ss_hip_weighted_class_residuals_* whole, the unweighted entry's checks in its order
+template <typename T>
+int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                           const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, const T* Wd, long long ws,
+                           char* err, size_t errlen)
+{
+    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    return residuals_impl<T>(ctx, who, by_class ? cs->labels : nullptr, by_class ? cs->num_classes : 1u, Y, B, y_stride, incy, records, kmax, R,
+                             r_stride, best, sci, err, errlen, Wd, ws);
+}
+template int weighted_residual_rows<float>(ss_hip_ctx*, const char*, bool, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, float*,
+                                           ptrdiff_t, uint32_t*, double*, const float*, long long, char*, size_t);
+template int weighted_residual_rows<double>(ss_hip_ctx*, const char*, bool, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t,
+                                            double*, ptrdiff_t, uint32_t*, double*, const double*, long long, char*, size_t);
+
+template <typename T>
+int class_residuals_weighted(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const T* W, ptrdiff_t w_stride,
+                             const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
+{
+    return class_residuals_entry<T>(ctx, "weighted_class_residuals", Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, true, W, w_stride,
+                                    err, errlen);
+}
+template int class_residuals_weighted<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, ptrdiff_t, const float*, ptrdiff_t, const void*, uint32_t,
+                                             float*, ptrdiff_t, uint32_t*, double*, char*, size_t);
+template int class_residuals_weighted<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const double*, ptrdiff_t, const void*,
+                                              uint32_t, double*, ptrdiff_t, uint32_t*, double*, char*, size_t);
+
 uint32_t classify_num_classes(const ss_hip_ctx* ctx)
 {
     const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
@@ -670,12 +730,12 @@ int ss_hip_reconstruct_records_f64(ss_hip_ctx* ctx, const void* records, size_t 
 int ss_hip_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                                uint32_t kmax, float* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
 {
-    return class_residuals_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+    return class_residuals_entry<float>(ctx, "class_residuals", Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, false, nullptr, 0, err, errlen);
 }
 int ss_hip_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                                uint32_t kmax, double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen)
 {
-    return class_residuals_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, err, errlen);
+    return class_residuals_entry<double>(ctx, "class_residuals", Y, B, y_stride, incy, records, kmax, R, r_stride, best, sci, false, nullptr, 0, err, errlen);
 }
 
 int ss_hip_homotopy_classify_batch_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, float tol,

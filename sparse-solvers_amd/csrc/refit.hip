@@ -19,6 +19,9 @@
 //                forward substitution along — the pivot test, the back substitution, z rounded once to T into the output record.
 // The residual norms are the words of ss_hip_class_residuals_* with every column in class 0 on the records as written: its kernels,
 // reached through record_residual_norms (classify.hip).
+// The weighted refit (ss_hip_weighted_refit_records_*, weighted.hip) is this unit with a flag: refit_weighted is refit_entry with the
+// weights checked and brought to the device, k_rf_gram<T, NT, true> forms P^T W_b P (one operand scaled by w_k), k_rf_solve is the
+// same kernel, the residual norms are the weighted ones (weighted_residual_rows).  The unflagged instantiations are the code they were.
 //
 // SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately outside
 // the MFMA, whose four products per instruction are a chain of fused multiply-adds):
@@ -120,10 +123,15 @@ void k_rf_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax,
 
 // NT: the most tile rows a panel of this call can have (from min(kmax, SS_HIP_REFIT_KMAX)); a wave holds up to NTW tiles.
 // part: [signal][chunk][tile_cap tiles][4 results][64 lanes], tile t = ti (ti + 1) / 2 + tj with tj <= ti
-template <typename T, int NT>
+// WGT (the weighted refit, weighted.hip): P^T W_b P.  The stage's 32 weights (row b of W; 0 for the rows m .. ldm - 1) sit in LDS in
+// front of the panel, and ONE operand — the tile-row operand, the one that holds h's row — is multiplied by w_k in T as a lane
+// reads it: element (i, j) is the chain of fma(P[r][i] * w_r, P[r][j], .), the panel, tiles and order unchanged.  With w_r == 1
+// the product is P[r][i] itself: the unweighted kernel's words.  Without WGT nothing is added and W is not read.
+template <typename T, int NT, bool WGT = false>
 __global__ __launch_bounds__(256)
 void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __restrict__ Y, long long y_stride, long long incy,
-               const unsigned char* __restrict__ rec, size_t rb, const uint32_t* __restrict__ stat, T* __restrict__ part, uint32_t tile_cap)
+               const unsigned char* __restrict__ rec, size_t rb, const uint32_t* __restrict__ stat, T* __restrict__ part, uint32_t tile_cap,
+               const T* __restrict__ Wt = nullptr, long long w_stride = 0)
 {
     typedef RfMma<T> M;
     typedef typename M::V V;
@@ -132,7 +140,8 @@ void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __re
     constexpr int NTW = (NT * (NT + 1) / 2 + 3) / 4;
     constexpr int NV = (NT * 16 * (int)VPC + 255) / 256;
     extern __shared__ __align__(16) unsigned char s_rf_raw[];
-    T* sP = reinterpret_cast<T*>(s_rf_raw);                  // [ncol][PITCH]: column c of the panel, the stage's 32 rows
+    T* sW = reinterpret_cast<T*>(s_rf_raw);                  // WGT: [kRfStep] the stage's weights
+    T* sP = sW + (WGT ? kRfStep : 0u);                       // [ncol][PITCH]: column c of the panel, the stage's 32 rows
     const uint32_t chunk = blockIdx.x, b = blockIdx.y, nchunks = gridDim.x;
     if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) return;
     const unsigned char* r = rec + (size_t)b * rb;
@@ -158,6 +167,8 @@ void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __re
         srow[s] = q;
     }
     V vr[NV];
+    T wr = T(0);                                             // WGT: thread t < 32 stages the weight of row t of the stage
+    const T* wrow = Wt + (long long)b * w_stride;
 #define RF_LOAD(R0)                                                                                    \
     _Pragma("unroll") for (int s = 0; s < NV; ++s) {                                                   \
         if (kind[s] == 1u) vr[s] = *reinterpret_cast<const V*>(cp[s] + (R0));                          \
@@ -167,7 +178,8 @@ void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __re
                 vr[s][e] = row < m ? y[(long long)row * incy] : T(0);                                  \
             }                                                                                          \
         }                                                                                              \
-    }
+    }                                                                                                  \
+    if (WGT && tid < kRfStep) wr = (R0) + tid < m ? wrow[(R0) + tid] : T(0);
     RF_LOAD(row_lo)
 
     // this wave's tiles t = wave, wave + 4, ...: where a lane reads its two operands
@@ -191,13 +203,17 @@ void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __re
 #pragma unroll
         for (int s = 0; s < NV; ++s)
             if (kind[s] != 0u) *reinterpret_cast<V*>(&sP[soff[s]]) = vr[s];
+        if (WGT && tid < kRfStep) sW[tid] = wr;
         __syncthreads();
         if (r0 + kRfStep < row_hi) { RF_LOAD(r0 + kRfStep) }
 #pragma unroll
         for (int s = 0; s < NTW; ++s) {
             if (!mine[s]) continue;
 #pragma unroll
-            for (uint32_t k4 = 0; k4 < kRfStep; k4 += 4u) acc[s] = M::mma(sP[offa[s] + k4], sP[offb[s] + k4], acc[s]);
+            for (uint32_t k4 = 0; k4 < kRfStep; k4 += 4u) {
+                if constexpr (WGT) acc[s] = M::mma(sP[offa[s] + k4] * sW[kq + k4], sP[offb[s] + k4], acc[s]);
+                else acc[s] = M::mma(sP[offa[s] + k4], sP[offb[s] + k4], acc[s]);
+            }
         }
     }
 #undef RF_LOAD
@@ -312,20 +328,26 @@ bool rf_solve_attr()
     return ok;
 }
 
+// Wd: the chunk's weights on the device (row b at Wd[b * ws]), null for the unweighted refit
 template <typename T, int NT>
 void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, const T* At, uint32_t ldm, uint32_t m, const T* yd, long long ys,
-                 long long yi, const unsigned char* recs, size_t rb, const uint32_t* stat, T* part, uint32_t tile_cap)
+                 long long yi, const unsigned char* recs, size_t rb, const uint32_t* stat, T* part, uint32_t tile_cap, const T* Wd, long long ws)
 {
     constexpr uint32_t PITCH = kRfStep + RfMma<T>::W;
-    hipLaunchKernelGGL((k_rf_gram<T, NT>), dim3(nchunks, Bc), dim3(256), (size_t)ntc * 16u * PITCH * sizeof(T), st, At, ldm, m, yd, ys, yi, recs,
-                       rb, stat, part, tile_cap);
+    const size_t lds = (size_t)ntc * 16u * PITCH * sizeof(T);
+    if (Wd)
+        hipLaunchKernelGGL((k_rf_gram<T, NT, true>), dim3(nchunks, Bc), dim3(256), lds + kRfStep * sizeof(T), st, At, ldm, m, yd, ys, yi, recs, rb,
+                           stat, part, tile_cap, Wd, ws);
+    else
+        hipLaunchKernelGGL((k_rf_gram<T, NT>), dim3(nchunks, Bc), dim3(256), lds, st, At, ldm, m, yd, ys, yi, recs, rb, stat, part, tile_cap,
+                           (const T*)nullptr, 0ll);
 }
 
+// Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit
 template <typename T>
-int refit_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-               void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+               void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, char* err, size_t errlen)
 {
-    static const char* who = "refit_records";
     HIPCHK(hipSetDevice(ctx->device));
     RefitState* rs = state_of(ctx);
     hipStream_t st = ctx->stream;
@@ -335,7 +357,7 @@ int refit_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdif
     const uint32_t kcap = std::min<uint32_t>(kmax, SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
     const bool in_dev = on_device(records), out_dev = on_device(records_out), y_dev = on_device(Y);
     if (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>()) {
-        set_err(err, errlen, "refit_records: the device does not give a workgroup the LDS of a support this large");
+        set_err(err, errlen, std::string(who) + ": the device does not give a workgroup the LDS of a support this large");
         return SS_HIP_ERUNTIME;
     }
 
@@ -385,16 +407,18 @@ int refit_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdif
                 long long ys = y_stride, yi = incy;
                 if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
                 const T* At = static_cast<const T*>(ctx->At);
-                if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
-                else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
-                else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap);
+                const T* wd = Wd ? Wd + (ptrdiff_t)b0 * ws : nullptr;
+                if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
+                else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
+                else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
                 hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
                                    dout + b0 * rb, rb, kmax, stat + b0);
                 HIPCHK(hipGetLastError());
             }
         });
         if (resnorm) {
-            const int rr = record_residual_norms<T>(ctx, who, Y, B, y_stride, incy, dout, kmax, rn, err, errlen);
+            const int rr = Wd ? weighted_residual_rows<T>(ctx, who, false, Y, B, y_stride, incy, dout, kmax, rn, 1, nullptr, nullptr, Wd, ws, err, errlen)
+                              : record_residual_norms<T>(ctx, who, Y, B, y_stride, incy, dout, kmax, rn, err, errlen);
             if (rr != SS_HIP_OK) { rc = rr; return; }
             hipLaunchKernelGGL((k_rf_widen<T>), dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const T*)rn, rnd, Bu);
             HIPCHK(hipGetLastError());
@@ -407,22 +431,44 @@ int refit_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdif
     return rc;
 }
 
+// weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks
 template <typename T>
-int refit_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
+                void* records_out, double* resnorm, uint32_t* status, bool weighted, const T* W, ptrdiff_t w_stride, char* err, size_t errlen)
 {
-    static const char* who = "refit_records";
-    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
+    const std::string w(who);
+    int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
     if (rc != SS_HIP_OK) return rc;
-    if (!Y || !records_out) { set_err(err, errlen, "refit_records: Y and records_out must not be null"); return SS_HIP_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "refit_records: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
-    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "refit_records: increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (!Y || !records_out) { set_err(err, errlen, w + ": Y and records_out must not be null"); return SS_HIP_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, w + ": records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
+    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, w + ": increments and strides must be positive"); return SS_HIP_EINVAL; }
+    if (weighted && (rc = weights_check_args(ctx, who, W, w_stride, err, errlen)) != SS_HIP_OK) return rc;
     if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
-    if (B >= 0x80000000ull) { set_err(err, errlen, "refit_records: B must stay below 2^31"); return SS_HIP_EINVAL; }
-    return guarded(err, errlen, who, [&] { return refit_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen); });
+    if (B >= 0x80000000ull) { set_err(err, errlen, w + ": B must stay below 2^31"); return SS_HIP_EINVAL; }
+    return guarded(err, errlen, who, [&]() -> int {
+        const T* Wd = nullptr;
+        long long ws = 0;
+        if (weighted) {
+            const int rw = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &ws, err, errlen);
+            if (rw != SS_HIP_OK) return rw;
+        }
+        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, err, errlen);
+    });
 }
 
 }  // namespace
+
+template <typename T>
+int refit_weighted(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const T* W, ptrdiff_t w_stride, const void* records,
+                   uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
+{
+    return refit_entry<T>(ctx, "weighted_refit_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, true, W, w_stride, err,
+                          errlen);
+}
+template int refit_weighted<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, ptrdiff_t, const float*, ptrdiff_t, const void*, uint32_t, void*,
+                                   double*, uint32_t*, char*, size_t);
+template int refit_weighted<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const double*, ptrdiff_t, const void*, uint32_t, void*,
+                                    double*, uint32_t*, char*, size_t);
 
 void refit_free(ss_hip_ctx* ctx)
 {
@@ -443,12 +489,12 @@ extern "C" {
 int ss_hip_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                              uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
 {
-    return refit_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen);
+    return refit_entry<float>(ctx, "refit_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, false, nullptr, 0, err, errlen);
 }
 int ss_hip_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                              uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen)
 {
-    return refit_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, err, errlen);
+    return refit_entry<double>(ctx, "refit_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, false, nullptr, 0, err, errlen);
 }
 
 }  // extern "C"

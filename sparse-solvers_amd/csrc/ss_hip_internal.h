@@ -366,6 +366,7 @@ struct ss_hip_ctx {
     void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
     void* tc = nullptr;           // sship::TopCorrState* (topcorr.hip): the workspace of the top correlations and the record extension
     void* js = nullptr;           // sship::JointState* (joint.hip): the workspace of the group top correlations and the group class residuals
+    void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights and the workspace of the weighted top correlations
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -544,6 +545,31 @@ template <typename T>
 hipError_t tc_launch_residual_block(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
                                     uint32_t Bc, T* R, double* part);
 template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uint32_t Bc, T* D);
+// ... and k_tc_tile with its squaring flag: D2 [tiles x 128][n_pad] = sum_k Wb[b][k] * (a_ki * a_ki), the square formed once in T where
+// At is staged — the second product of the weighted top correlations (weighted.hip); Wb [tiles x 128][ldm] as R above
+template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
+// weighted coding (weighted.hip): releases its workspace
+void weighted_free(ss_hip_ctx* ctx);
+// ... and what the three weighted calls share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
+// weights_on_device: the batch's weights where the kernels read them — W itself, or a staged copy of a host caller's (row pitch m, or
+// 0 for the shared vector) — after a device scan for the first weight that is negative or not finite (SS_HIP_EINVAL, the signal and
+// the row in the message; nothing has been written).  Throws what HIPCHK throws: call it under guarded
+int weights_check_args(const ss_hip_ctx* ctx, const char* who, const void* W, ptrdiff_t w_stride, char* err, size_t errlen);
+template <typename T>
+int weights_on_device(ss_hip_ctx* ctx, const char* who, const T* W, size_t B, ptrdiff_t w_stride, const T** Wd, long long* ws, char* err,
+                      size_t errlen);
+// ... the weighted refit whole (refit.hip: refit_records' checks in its order, k_rf_gram with its weight flag, k_rf_solve) and the weighted
+// class residuals (classify.hip: k_cls_residual with its weight flag), which weighted.hip's entry points forward to
+template <typename T>
+int refit_weighted(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const T* W, ptrdiff_t w_stride, const void* records,
+                   uint32_t kmax, void* records_out, double* resnorm, uint32_t* status, char* err, size_t errlen);
+template <typename T>
+int class_residuals_weighted(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const T* W, ptrdiff_t w_stride,
+                             const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+template <typename T>
+int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                           const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, const T* Wd, long long ws,
+                           char* err, size_t errlen);
 // the group top correlations and the group class residuals (joint.hip): releases their workspace
 void joint_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of

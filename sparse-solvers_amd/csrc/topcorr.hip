@@ -39,7 +39,8 @@
 //                total order afterwards.  No floating-point atomics.
 // Nothing depends on B, on the chunking, on the launch geometry, on where the pointers live or on what the context did before.
 // tc_launch_record_check / tc_launch_residual_block / tc_launch_dots (ss_hip_internal.h) are the launches of a chunk's record check,
-// residual block and dot block: joint.hip runs the same kernels through them.
+// residual block and dot block: joint.hip and weighted.hip run the same kernels through them; tc_launch_weight_dots is k_tc_tile with
+// the squaring flag, weighted.hip's second product.
 #include "ss_hip_internal.h"
 #include "record_common.h"
 #include "tc_select.h"
@@ -115,8 +116,10 @@ void k_tc_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax,
         if (idx[e] >= n) atomicMin(bad, b);
 }
 
-// R: [signal tiles x 128][ldm]; D: [signal tiles x 128][n_pad]
-template <typename T>
+// R: [signal tiles x 128][ldm]; D: [signal tiles x 128][n_pad].  SQ: every element of At is squared once in T where it is staged
+// (one multiplication between the global load and the LDS store): with a block of weights for R the tile is d(i, b) = sum_k
+// w_kb a_ki^2 of the weighted top correlations (weighted.hip) — the same tile, the same chain.  Without SQ nothing is added.
+template <typename T, bool SQ = false>
 __global__ __launch_bounds__(256, 2)
 void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, uint32_t n_pad, T* __restrict__ D)
 {
@@ -153,7 +156,7 @@ void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, 
 
     Vec stA[4], stB[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { stA[j] = gA[j][0]; stB[j] = gB[j][0]; }
+    for (int j = 0; j < 4; ++j) { stA[j] = gA[j][0]; stB[j] = gB[j][0]; if constexpr (SQ) stB[j] = stB[j] * stB[j]; }
 #pragma unroll
     for (int j = 0; j < 4; ++j) { sA[0][srow + 32 * j][svec] = stA[j]; sB[0][srow + 32 * j][svec] = stB[j]; }
     __syncthreads();
@@ -165,7 +168,7 @@ void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, 
         if (more) {
             const uint32_t voff = (kt + 1u) * kTcVecs;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { stA[j] = gA[j][voff]; stB[j] = gB[j][voff]; }
+            for (int j = 0; j < 4; ++j) { stA[j] = gA[j][voff]; stB[j] = gB[j][voff]; if constexpr (SQ) stB[j] = stB[j] * stB[j]; }
         }
         if constexpr (sizeof(T) == 4) {
 #pragma unroll
@@ -585,12 +588,23 @@ hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uint32_t Bc, T* D)
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2)
+{
+    const uint32_t btiles = (Bc + kTcTile - 1u) / kTcTile, ctiles = ((uint32_t)ctx->n + kTcTile - 1u) / kTcTile;
+    hipLaunchKernelGGL((k_tc_tile<T, true>), dim3(btiles, ctiles), dim3(256), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm, Wb, ctx->n_pad,
+                       D2);
+    return hipGetLastError();
+}
+
 template hipError_t tc_launch_residual_block<float>(ss_hip_ctx*, const float*, long long, long long, const unsigned char*, size_t, uint32_t, uint32_t,
                                                     float*, double*);
 template hipError_t tc_launch_residual_block<double>(ss_hip_ctx*, const double*, long long, long long, const unsigned char*, size_t, uint32_t,
                                                      uint32_t, double*, double*);
 template hipError_t tc_launch_dots<float>(ss_hip_ctx*, const float*, uint32_t, float*);
 template hipError_t tc_launch_dots<double>(ss_hip_ctx*, const double*, uint32_t, double*);
+template hipError_t tc_launch_weight_dots<float>(ss_hip_ctx*, const float*, uint32_t, float*);
+template hipError_t tc_launch_weight_dots<double>(ss_hip_ctx*, const double*, uint32_t, double*);
 
 void topcorr_free(ss_hip_ctx* ctx)
 {

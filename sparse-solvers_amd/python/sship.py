@@ -155,6 +155,9 @@ _PROTOTYPES = [
     ("ss_hip_extend_records_", _int, [_vp, _vp, _sz, _u32, _vp, _vp, _u32, _vp, _vp] + _ERR),
     ("ss_hip_group_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_group_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _vp, _pd, _vp] + _ERR),
+    ("ss_hip_weighted_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, ctypes.c_double, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_weighted_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_weighted_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _pd, _vp, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
     ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
     ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
@@ -716,6 +719,14 @@ class Homotopy(_Context):
         stages >= 1; stages=1 is the thresholding coder.  The records live where `records`
         lives, or where Y lives without; resnorm and status where Y lives (status int32 on a device)."""
         kmax = int(kmax)
+        return self._stagewise(Y, stages, kmax, tolerance, records,
+                               lambda cur: self.top_correlations(Y, per_stage, records=cur, kmax=kmax, score=False),
+                               lambda ext: self.refit_records(Y, ext, kmax))
+
+    def _stagewise(self, Y, stages, kmax, tolerance, records, top, refit):
+        """the loop of stagewise_code and weighted_stagewise_code, stated once: top(records) -> (idx, coef, _) selects a stage's
+        columns, refit(records) -> (records, resnorm, status) fits them; everything else — the freezing rules, what rides along,
+        where the results live — is the loop's"""
         if int(stages) < 1:
             raise ValueError("stages must be at least 1")
         if kmax > self.REFIT_KMAX:
@@ -754,10 +765,10 @@ class Homotopy(_Context):
         for _ in range(int(stages)):
             if bool(frozen.all()):
                 break
-            idx, coef, _ = self.top_correlations(Y, per_stage, records=cur, kmax=kmax, score=False)
+            idx, coef, _ = top(cur)
             idx[frozen] = -1 if on_dev else self.TOPCORR_NONE
             ext, _ = self.extend_records(cur, kmax, idx, coef)
-            new, rn, st = self.refit_records(Y, ext, kmax)
+            new, rn, st = refit(ext)
             live = ~frozen
             good = live & (st == self.REFIT_DONE)
             g = where_records_live(good)
@@ -768,6 +779,105 @@ class Homotopy(_Context):
             if tolerance is not None:
                 frozen = frozen | (good & (resnorm <= float(tolerance)))
         return cur, resnorm, status
+
+    # ---- weighted coding: a non-negative weight per row and signal (include/ss_hip.h, csrc/weighted.hip) ------------------------
+
+    def _weights(self, W, B):
+        """`W` of the weighted calls -> (pointer, w_stride): a (B, m) array or tensor of the matrix dtype on either side, rows of
+        unit increment — or an (m,) vector, the weights every signal shares (w_stride 0).  The library checks the values."""
+        Wp, shape, strides, dt, keep = _describe(W)
+        if dt != self.dtype:
+            raise TypeError("dtype of W (%s) does not match the matrix (%s)" % (dt, self.dtype))
+        if len(shape) == 1 and shape[0] == self.m and (strides[0] == 1 or self.m <= 1):
+            return Wp, 0
+        if len(shape) == 2 and tuple(shape) == (B, self.m) and (strides[1] == 1 or self.m <= 1) and (B <= 1 or strides[0] >= self.m):
+            return Wp, (strides[0] if B > 1 else self.m)
+        raise ValueError("W must be (B, m) with rows of unit increment, or (m,), of the matrix dtype")
+
+    def weighted_top_correlations(self, Y, W, k, records=None, kmax=None, min_visible=0.0, coef=True, score=True):
+        """The weighted top correlations (include/ss_hip.h, ss_hip_weighted_top_correlations_*): top_correlations under the
+        weights W — for every signal the k columns, not stored in its record, with the largest |a_i . (w_b o r_b)| / sqrt(d(i, b)),
+        d(i, b) = sum_k w_kb a_ki^2 -> (idx (B, k), coef (B, k) or None, score (B, k) float64 or None).  coef = a_i . (w_b o r_b) /
+        d(i, b), the weighted least-squares coefficient of r_b on that atom alone.  A column whose visible share d(i, b) /
+        (max_k w_kb * ||a_i||^2) is not above min_visible (0 <= min_visible < 1) is no candidate; a signal whose weights are all
+        zero has none.  W: (B, m) or the shared (m,), finite and >= 0.  Everything else as for top_correlations."""
+        if records is None:
+            Yp, B, ys, incy = self._signals(Y)
+            rp, kmax = None, 0
+            if not B:
+                ys, incy = self.m, 1
+        else:
+            if kmax is None:
+                raise ValueError("kmax must be given with records")
+            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        Wp, wst = self._weights(W, B)
+        min_visible = float(min_visible)
+        if not 0.0 <= min_visible < 1.0:
+            raise ValueError("min_visible must lie in [0, 1)")
+        k = int(k)
+        dev = _device_of(Y)
+        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
+        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
+        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
+        _sync_producers(Y, records, idx)
+        _sync_producers(W)
+        _call(self._fn("ss_hip_weighted_top_correlations_"), self._h, Yp, B, ys, incy, Wp, wst, rp, int(kmax), min_visible, k, ip, cp, sp)
+        return idx, cf, sc
+
+    def weighted_refit_records(self, Y, W, records, kmax, out=None, residuals=True):
+        """The weighted refit (include/ss_hip.h, ss_hip_weighted_refit_records_*): refit_records under the weights W — every
+        record's values replaced by argmin sum_k w_kb (y_b - A_S z)_k^2 -> (records_out, resnorm (B,) float64 or None, status
+        (B,)), resnorm[b] = sqrt(sum_k w_kb (y_b - A x_b)_k^2).  With W == 1 the words of refit_records.  W as for
+        weighted_top_correlations, everything else as for refit_records."""
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        Wp, wst = self._weights(W, B)
+        if out is None:
+            if isinstance(records, np.ndarray):
+                out = np.empty_like(records)
+            else:
+                import torch
+                out = torch.empty_like(records)
+        op, _ = _records(out, self.record_bytes(kmax), B=B, other="out")
+        dev = _device_of(Y)
+        status, sp = _alloc(dev, (B,), np.uint32)
+        resnorm, np_ = _alloc(dev, (B,) if residuals else None, np.float64)
+        _sync_producers(Y, records, out)
+        _sync_producers(W)
+        _call(self._fn("ss_hip_weighted_refit_records_"), self._h, Yp, B, ys, incy, Wp, wst, rp, int(kmax), op, np_, sp)
+        return out, resnorm, status
+
+    def weighted_class_residuals(self, Y, W, records, kmax, residuals=True):
+        """The weighted class residuals (include/ss_hip.h, ss_hip_weighted_class_residuals_*) -> (best (B,), sci (B,) float64,
+        R (B, num_classes) or None): R[b, c] = sqrt(sum_k w_kb (y_b - A delta_c(x_b))_k^2), best its left-most arg-min, sci as
+        for class_residuals (the record's alone).  W as for weighted_top_correlations, everything else as for class_residuals."""
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax)
+        Wp, wst = self._weights(W, B)
+        outs, words = self._class_outputs(B, residuals, Y)
+        _sync_producers(Y, records)
+        _sync_producers(W)
+        _call(self._fn("ss_hip_weighted_class_residuals_"), self._h, Yp, B, ys, incy, Wp, wst, rp, int(kmax), *words)
+        return outs
+
+    def weighted_stagewise_code(self, Y, W, stages, per_stage, kmax=96, tolerance=None, records=None, min_visible=0.0):
+        """stagewise_code under the weights W -> (records, resnorm (B,) float64, status (B,)): its loop, freezing rules and
+        return values with weighted_top_correlations(per_stage, min_visible) -> extend_records -> weighted_refit_records per
+        stage.  resnorm and `tolerance` are the weighted residual norm sqrt(sum_k w_kb (y_b - A x_b)_k^2)."""
+        kmax = int(kmax)
+        self._weights(W, self._signals(Y)[1])
+        if not 0.0 <= float(min_visible) < 1.0:
+            raise ValueError("min_visible must lie in [0, 1)")
+        return self._stagewise(Y, stages, kmax, tolerance, records,
+                               lambda cur: self.weighted_top_correlations(Y, W, per_stage, records=cur, kmax=kmax, min_visible=min_visible,
+                                                                          score=False),
+                               lambda ext: self.weighted_refit_records(Y, W, ext, kmax))
+
+    def weighted_classify(self, Y, W, stages, per_stage, kmax=96, tolerance=None, min_visible=0.0, residuals=True):
+        """weighted_stagewise_code followed by weighted_class_residuals -> (best (B,), sci (B,), R (B, num_classes) or None,
+        records, resnorm (B,)): sparse-representation classification that ignores (or discounts) the rows W marks.  Needs
+        set_classes."""
+        records, resnorm, _ = self.weighted_stagewise_code(Y, W, stages, per_stage, kmax=kmax, tolerance=tolerance, min_visible=min_visible)
+        best, sci, R = self.weighted_class_residuals(Y, W, records, kmax, residuals=residuals)
+        return best, sci, R, records, resnorm
 
     # ---- joint sparse coding of signal groups (include/ss_hip.h, csrc/joint.hip) ------------------------------------------------
 
