@@ -720,6 +720,62 @@ int ss_hip_weighted_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t
                                         double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
 
 /*
+ * Non-negative coding — the positive top correlations: ss_hip_top_correlations_* restricted to the atoms that a fit may ADD (added
+ * under ABI version 7; csrc/nonneg.hip; NOT in the reference).  Dictionaries whose atoms are parts — training faces or spectra as
+ * columns, abundances in unmixing, SRC variants that forbid subtracting one subject from another — want a code with x >= 0.  One
+ * stage of the non-negative coder = this call, ss_hip_extend_records_*, ss_hip_nonneg_refit_records_*.  The parameter list, r_b,
+ * dot(i, b), d_i and rn_i are ss_hip_top_correlations_*' (the same kernels through the same launches), and
+ *     CANDIDATES  that call's candidates with dot(i, b) > 0: a comparison on the stored word, never arithmetic — a zero, a
+ *                 negative and a NaN dot are no candidates
+ *     s(i, b)     = dot(i, b) * rn_i in double (positive: its bits order as it does); ties by ascending index
+ *     coef[b][t]  (may be NULL) (T)((double)dot * rn_i^2)
+ * Entries beyond the number of candidates are SS_HIP_TOPCORR_NONE in idx and 0 in coef and score.
+ * CONTRACT: row b of the outputs is a function of A, y_b, record b and k alone, as for ss_hip_top_correlations_*; the PREFIX PROPERTY
+ * in k holds.  PINNED: at n <= SS_HIP_TOPCORR_KMAX the result is the subsequence of ss_hip_top_correlations_*(k = n)'s entries with
+ * coef > 0, word for word in idx, coef and score, padded behind with SS_HIP_TOPCORR_NONE / 0.
+ * Validation, workspace and error codes: as for ss_hip_top_correlations_*.
+ */
+int ss_hip_nonneg_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       const void* records, uint32_t kmax, uint32_t k,
+                                       uint32_t* idx, float* coef, double* score, char* err, size_t errlen);
+int ss_hip_nonneg_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                       const void* records, uint32_t kmax, uint32_t k,
+                                       uint32_t* idx, double* coef, double* score, char* err, size_t errlen);
+
+/*
+ * The non-negative refit: ss_hip_refit_records_* under z >= 0 (added under ABI version 7; csrc/nonneg.hip, the kernels of
+ * csrc/refit.hip with the solve replaced; NOT in the reference).  For signal b with the record's stored columns S, K of them,
+ *     z = argmin || y_b - A_S z ||_2  subject to  z >= 0.
+ * G = A_S^T A_S, h = A_S^T y_b and y^T y are ss_hip_refit_records_*' words (the same panel, row chunks, tiles and summation
+ * order).  On them one workgroup per signal runs the Lawson-Hanson active-set method in double, in LDS, in one documented order
+ * (csrc/refit.hip, NNLS ORDER): from P empty and z = 0, the column outside P with the largest w_j = (h - G z)_j
+ * among those with w_j > tau_j = 8 K eps(T) sqrt(G_jj y^T y) enters (ties to the smallest record position; none: done); G_PP s = h_P
+ * is solved by a Cholesky factor that gains a row on entry and is formed again after a removal; while some s_i <= 0, z moves towards
+ * s as far as it stays non-negative and what reaches zero leaves P.  At most 3 K solves a signal.
+ *     records_out[b]  for SS_HIP_REFIT_DONE: the entries with (T) z_e > 0, in record order, compacted — K' of them, K' in word 0,
+ *                     idx[0 .. K') and val[0 .. K') theirs, idx[K' .. K) and val[K' .. K) zero words; iter, err, the slots behind
+ *                     K and the padding copied word for word.  K' = 0 is a valid result.  For every other status the record is
+ *                     copied unchanged
+ *     resnorm[b]      (may be NULL) as for ss_hip_refit_records_*, of the record as written
+ *     status[b]       (may be NULL) SS_HIP_REFIT_*: EMPTY and TRUNCATED as there; SS_HIP_REFIT_TOO_LARGE for kmax >= K >
+ *                     SS_HIP_NNLS_KMAX; SS_HIP_REFIT_SINGULAR when a column that passed the entry test fails the pivot test
+ *                     !(d > 8 K eps(T) G_jj), or when y^T y, an h_j or a G_jj is not finite; SS_HIP_REFIT_STALLED past the cap
+ *     dropped[b]      (may be NULL) K - K' for SS_HIP_REFIT_DONE, else 0
+ * A column named twice and an all-zero column never pass the entry test: they are dropped, not SINGULAR.
+ * SS_HIP_NNLS_KMAX is 128: G and the factor, two packed triangles in double, share one CU's 160 KiB of LDS; the request is sized
+ * from min(kmax, SS_HIP_NNLS_KMAX) (kmax = 96: two workgroups a CU).
+ * CONTRACT and validation: as for ss_hip_refit_records_*, dropped[b] among a signal's words.
+ */
+#define SS_HIP_NNLS_KMAX 128
+#define SS_HIP_REFIT_STALLED 5    /* the non-negative refit needed more than 3 K solves    */
+int ss_hip_nonneg_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const void* records, uint32_t kmax, void* records_out,
+                                    double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
+int ss_hip_nonneg_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const void* records, uint32_t kmax, void* records_out,
+                                    double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the

@@ -22,6 +22,9 @@
 // The weighted refit (ss_hip_weighted_refit_records_*, weighted.hip) is this unit with a flag: refit_weighted is refit_entry with the
 // weights checked and brought to the device, k_rf_gram<T, NT, true> forms P^T W_b P (one operand scaled by w_k), k_rf_solve is the
 // same kernel, the residual norms are the weighted ones (weighted_residual_rows).  The unflagged instantiations are the code they were.
+// The non-negative refit (ss_hip_nonneg_refit_records_*, nonneg.hip) is this unit with another flag: refit_nonneg is refit_entry with
+// k_rf_cap behind k_rf_check (a DONE record of more than SS_HIP_NNLS_KMAX columns becomes TOO_LARGE), k_rf_gram as it is, and
+//   k_rf_nnls    in k_rf_solve's place, one workgroup per signal: Lawson-Hanson on the same [G h; h^T y^T y] in double, in LDS.
 //
 // SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately outside
 // the MFMA, whose four products per instruction are a chain of fused multiply-adds):
@@ -37,6 +40,24 @@
 //                fails it; a column named twice gives a second pivot of rounding size, an all-zero column G_jj = 0);
 //   back subst.  for j descending  z_j = w_j / l_jj,  then w_i = w_i - l_ji * z_j for i < j, in double;
 //   val[e]       = z_e rounded once to T.
+// NNLS ORDER (k_rf_nnls; G, h and y^T y are the words above, everything below in double, products and sums rounded separately):
+//   state        P, the passive set, a list of record positions in the order they entered; z by record position, 0 outside P;
+//                start P empty, z = 0.  L, the Cholesky factor of G_PP in P's order, row p packed at p (p + 1) / 2; u = L^-1 h_P.
+//   entry test   for every position e not in P, ascending i over P's members BY RECORD POSITION:  w_e = h_e, then w_e = w_e - G_ei * z_i.
+//                tau_e = 8 K eps(T) sqrt(G_ee * y^T y) (one product, one root, one product).  Among the e with w_e > tau_e the
+//                largest w_e enters, ties to the smallest position; none: the signal is done.  (A comparison, so a NaN never enters.)
+//   row p        the factor's row for column j = P[p]:  v_i = G_{j, P[i]} for i < p;  for k ascending  l_k = v_k / L_kk,  then
+//                v_i = v_i - L_ik * l_k for k < i < p;  the pivot d = G_jj, then d = d - l_k * l_k in ascending k;  c = h_j, then
+//                c = c - l_k * u_k in ascending k;  the signal is SINGULAR when !(d > 8 K eps(T) G_jj);  L_pp = sqrt(d), u_p = c / L_pp.
+//                A column that enters appends its row; after a removal the rows 0, 1, ... of the shortened list are formed again
+//                by the same statements — the factor is a function of the list, never of how the list came about.
+//   a solve      L^T s = u:  t = u, for k descending  s_k = t_k / L_kk,  then t_i = t_i - L_ki * s_k for i < k.  At most 3 K solves
+//                a signal; one more needed: SS_HIP_REFIT_STALLED.
+//   inner loop   every s_p > 0: z_P = s, back to the entry test.  Else over the p with !(s_p > 0) in P's order  a_p = z_p / (z_p - s_p)
+//                (0 where z_p is 0: a column that has just entered), alpha = their minimum, attained first at p*;  z_p = z_p +
+//                alpha * (s_p - z_p) for every p;  p* and every p with !(z_p > 0) leave P with z = 0 exactly; the factor again; solve.
+//   the record   the entries with (T) z_e > 0, in record order, compacted to the front of idx and val (z_e rounded once to T), zero
+//                words from there to K, K' in word 0; every other word as it was.
 // No floating-point atomics; nothing depends on B, on the chunking of the batch, on the launch geometry, on where the pointers live or
 // on what the context did before: a signal's record, residual norm and status are a function of its input record, its y and A.
 #include "ss_hip_internal.h"
@@ -304,6 +325,201 @@ void k_rf_solve(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap,
     for (uint32_t e = tid; e < K; e += 256u) store_val(valp, e, (T)L[KB + e]);
 }
 
+// the non-negative refit (nonneg.hip): a DONE record of more than `cap` columns does not fit k_rf_nnls' LDS
+__global__ __launch_bounds__(256)
+void k_rf_cap(const unsigned char* __restrict__ rec, size_t rb, uint32_t cap, uint32_t* __restrict__ stat, uint32_t B)
+{
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= B) return;
+    if (stat[b] == (uint32_t)SS_HIP_REFIT_DONE && *reinterpret_cast<const uint32_t*>(rec + (size_t)b * rb) > cap)
+        stat[b] = (uint32_t)SS_HIP_REFIT_TOO_LARGE;
+}
+
+// element (a, b) of the packed lower triangle of a symmetric matrix, whichever way round
+__device__ inline uint32_t rf_tri(uint32_t a, uint32_t b) { return a >= b ? a * (a + 1u) / 2u + b : b * (b + 1u) / 2u + a; }
+
+// One row of the Cholesky factor of G_PP (P in entry order, plist[0 .. p]): row p from column j = plist[p], with the forward
+// substitution of h along (u[p]).  Every thread of the workgroup calls it and gets the same verdict: false = the pivot failed.
+// (NNLS ORDER in the header: `row p`.)
+__device__ inline bool rf_nn_row(const double* G, double* Lf, double* v, double* u, const uint32_t* plist, uint32_t p, uint32_t KB, double thr)
+{
+    const uint32_t tid = threadIdx.x, j = plist[p], pb = p * (p + 1u) / 2u;
+    const double gjj = G[j * (j + 1u) / 2u + j];
+    __syncthreads();
+    for (uint32_t i = tid; i < p; i += 256u) v[i] = G[rf_tri(j, plist[i])];
+    double d = gjj, c = G[KB + j];
+    for (uint32_t k = 0; k < p; ++k) {
+        __syncthreads();
+        const double lk = v[k] / Lf[k * (k + 1u) / 2u + k];      // (every thread forms the same word)
+        for (uint32_t i = k + 1u + tid; i < p; i += 256u) v[i] = v[i] - Lf[i * (i + 1u) / 2u + k] * lk;
+        if (tid == 0) Lf[pb + k] = lk;
+        d = d - lk * lk;
+        c = c - lk * u[k];
+    }
+    if (!(d > thr * gjj)) return false;
+    const double lpp = sqrt(d);
+    if (tid == 0) { Lf[pb + p] = lpp; u[p] = c / lpp; }
+    __syncthreads();
+    return true;
+}
+
+// The non-negative refit of one signal (ss_hip_nonneg_refit_records_*, nonneg.hip): Lawson-Hanson on the normal equations that
+// k_rf_gram formed, in double, in LDS — the packed [G h; h^T y^T y], the packed Cholesky factor of G_PP beside it, a few vectors of
+// K.  One workgroup per signal; every decision is taken by every thread from the same LDS words, so every branch is uniform.
+// rec_in and rec_out: the same records (in place) or disjoint ones.  (NNLS ORDER in the header.)
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
+               uint32_t kmax, uint32_t* __restrict__ stat, uint32_t* __restrict__ dropped)
+{
+    typedef RfMma<T> M;
+    extern __shared__ __align__(16) unsigned char s_rf_raw[];
+    __shared__ uint32_t s_bad, s_np;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const unsigned char* ri = rec_in + (size_t)b * rb;
+    unsigned char* ro = rec_out + (size_t)b * rb;
+    const uint32_t* wi = reinterpret_cast<const uint32_t*>(ri);
+    uint32_t* wo = reinterpret_cast<uint32_t*>(ro);
+    const uint32_t words = (uint32_t)(rb / 4);
+    // every status but DONE: the record unchanged, nothing dropped
+    auto unchanged = [&](uint32_t status) {
+        if (tid == 0) { stat[b] = status; dropped[b] = 0u; }
+        if (ri != ro)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+    };
+    if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) { unchanged(stat[b]); return; }
+    const uint32_t K = wi[0], np = (K + 1u) * (K + 2u) / 2u, KB = K * (K + 1u) / 2u;
+    double* G = reinterpret_cast<double*>(s_rf_raw);         // packed rows 0 .. K of [G h; h^T y^T y]: (i, j) at i (i + 1) / 2 + j
+    double* Lf = G + np;                                     // packed rows of the factor of G_PP, row p at p (p + 1) / 2
+    double* z = Lf + KB;                                     // [K] by record position, 0 outside P
+    double* s = z + K;                                       // [K] by position in P: the solution of a solve
+    double* v = s + K;                                       // [K] workspace: w of the entry test, a substitution's right-hand side
+    double* u = v + K;                                       // [K] by position in P: h_P taken through the forward substitution
+    uint32_t* plist = reinterpret_cast<uint32_t*>(u + K);    // [K] P in entry order (record positions)
+    uint32_t* inP = plist + K;                               // [K] by record position
+    uint32_t* sidx = inP + K;                                // [K] the record's columns; then the output slot of a kept entry
+    const size_t cstride = (size_t)tile_cap * 256u;
+    for (uint32_t p = tid; p < np; p += 256u) {              // (k_rf_solve's statements: the chunk partials in ascending order, in double)
+        uint32_t j = 0, i = 0;
+        tri_tile_decode(p, j, i);
+        const uint32_t ti = i >> 4, tj = j >> 4, t = ti * (ti + 1u) / 2u + tj;
+        const T* pp = part + (size_t)b * nchunks * cstride + (size_t)t * 256u + M::slot(i & 15u, j & 15u);
+        double a = 0.0;
+        for (uint32_t c = 0; c < nchunks; ++c) a += (double)pp[(size_t)c * cstride];
+        G[p] = a;
+    }
+    if (tid == 0) s_bad = 0u;
+    for (uint32_t e = tid; e < K; e += 256u) { z[e] = 0.0; inP[e] = 0u; sidx[e] = wi[4u + e]; }
+    __syncthreads();
+    const double kDblMax = 1.7976931348623157e308;
+    for (uint32_t e = tid; e <= K; e += 256u)                // (e == K: y^T y)
+        if (!(fabs(G[e * (e + 1u) / 2u + e]) <= kDblMax) || !(fabs(G[KB + e]) <= kDblMax)) atomicOr(&s_bad, 1u);
+    __syncthreads();
+    if (s_bad != 0u) { unchanged((uint32_t)SS_HIP_REFIT_SINGULAR); return; }
+    const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon(), yy = G[KB + K];
+    uint32_t nP = 0, solves = 0, verdict = (uint32_t)SS_HIP_REFIT_DONE;
+    for (;;) {
+        // ---- the entry test: w over the columns not in P, the largest w_j above its threshold ----
+        __syncthreads();
+        for (uint32_t e = tid; e < K; e += 256u) {
+            if (inP[e]) continue;
+            double a = G[KB + e];
+            for (uint32_t i = 0; i < K; ++i)
+                if (inP[i]) a = a - G[rf_tri(e, i)] * z[i];
+            v[e] = a;
+        }
+        __syncthreads();
+        uint32_t best = K;
+        double bw = 0.0;
+        for (uint32_t e = 0; e < K; ++e) {
+            if (inP[e]) continue;
+            const double w = v[e], tau = thr * sqrt(G[e * (e + 1u) / 2u + e] * yy);
+            if (w > tau && (best == K || w > bw)) { best = e; bw = w; }
+        }
+        if (best == K) break;
+        __syncthreads();
+        if (tid == 0) { plist[nP] = best; inP[best] = 1u; }
+        __syncthreads();
+        if (!rf_nn_row(G, Lf, v, u, plist, nP, KB, thr)) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
+        nP += 1u;
+        // ---- the inner loop: solve on P, step towards the solution as far as z stays non-negative, drop what reaches zero ----
+        while (nP != 0u) {
+            if (solves == 3u * K) { verdict = (uint32_t)SS_HIP_REFIT_STALLED; break; }
+            solves += 1u;
+            for (uint32_t i = tid; i < nP; i += 256u) v[i] = u[i];
+            for (uint32_t k = nP; k-- > 0u;) {
+                const uint32_t kb = k * (k + 1u) / 2u;
+                __syncthreads();
+                const double sk = v[k] / Lf[kb + k];
+                for (uint32_t i = tid; i < k; i += 256u) v[i] = v[i] - Lf[kb + i] * sk;
+                if (tid == 0) s[k] = sk;
+            }
+            __syncthreads();
+            bool all_pos = true;
+            double alpha = 0.0;
+            uint32_t pmin = K;
+            for (uint32_t p = 0; p < nP; ++p) {
+                const double sp = s[p];
+                if (sp > 0.0) continue;
+                all_pos = false;
+                const double zp = z[plist[p]], a = zp > 0.0 ? zp / (zp - sp) : 0.0;
+                if (pmin == K || a < alpha) { alpha = a; pmin = p; }
+            }
+            if (all_pos) {
+                for (uint32_t p = tid; p < nP; p += 256u) z[plist[p]] = s[p];
+                break;
+            }
+            __syncthreads();
+            for (uint32_t p = tid; p < nP; p += 256u) {
+                const uint32_t e = plist[p];
+                const double zn = z[e] + alpha * (s[p] - z[e]);
+                if (p == pmin || !(zn > 0.0)) { z[e] = 0.0; inP[e] = 0u; }
+                else z[e] = zn;
+            }
+            __syncthreads();
+            // P without what left, in its order; the factor built again row by row
+            if (tid == 0) {
+                uint32_t kept = 0;
+                for (uint32_t p = 0; p < nP; ++p) {
+                    const uint32_t e = plist[p];
+                    if (inP[e]) plist[kept++] = e;
+                }
+                s_np = kept;
+            }
+            __syncthreads();
+            nP = s_np;
+            bool ok = true;
+            for (uint32_t p = 0; p < nP && ok; ++p) ok = rf_nn_row(G, Lf, v, u, plist, p, KB, thr);
+            if (!ok) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
+        }
+        if (verdict != (uint32_t)SS_HIP_REFIT_DONE) break;
+    }
+    __syncthreads();
+    if (verdict != (uint32_t)SS_HIP_REFIT_DONE) { unchanged(verdict); return; }
+    // ---- the record: the entries with (T) z_e > 0 in record order, zero words up to K, everything else word for word ----
+    if (tid == 0) {
+        uint32_t kept = 0;
+        for (uint32_t e = 0; e < K; ++e) {
+            const bool keep = (T)z[e] > T(0);
+            inP[e] = keep ? kept : K;                        // the output slot, K = dropped
+            kept += keep ? 1u : 0u;
+        }
+        s_bad = kept;
+    }
+    __syncthreads();
+    const uint32_t Kp = s_bad;
+    const uint32_t v0 = 4u + kmax, v1 = v0 + K * (uint32_t)(sizeof(T) / 4);
+    if (ri != ro)
+        for (uint32_t w = tid; w < words; w += 256u)
+            if (w != 0u && (w < 4u || (w >= 4u + K && w < v0) || w >= v1)) wo[w] = wi[w];
+    unsigned char* valp = ro + 16 + (size_t)kmax * 4;
+    for (uint32_t e = tid; e < K; e += 256u) {
+        if (inP[e] != K) { wo[4u + inP[e]] = sidx[e]; store_val(valp, inP[e], (T)z[e]); }
+        if (e >= Kp) { wo[4u + e] = 0u; store_val(valp, e, T(0)); }
+    }
+    if (tid == 0) { wo[0] = Kp; dropped[b] = K - Kp; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_rf_widen(const T* __restrict__ in, double* __restrict__ out, uint32_t B)
@@ -328,6 +544,24 @@ bool rf_solve_attr()
     return ok;
 }
 
+// the non-negative refit's LDS: [G h; h^T .] and the factor of G_PP packed, four vectors of doubles and three of words
+template <typename T> size_t rf_nnls_lds(uint32_t kcap)
+{
+    return ((size_t)(kcap + 1) * (kcap + 2) / 2 + (size_t)kcap * (kcap + 1) / 2 + 4 * (size_t)kcap) * sizeof(double) + 3 * (size_t)kcap * sizeof(uint32_t);
+}
+
+template <typename T>
+bool rf_nnls_attr()
+{
+    static const bool ok = [] {
+        const bool a = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rf_nnls<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)rf_nnls_lds<T>(SS_HIP_NNLS_KMAX)) == hipSuccess;
+        if (!a) (void)hipGetLastError();
+        return a;
+    }();
+    return ok;
+}
+
 // Wd: the chunk's weights on the device (row b at Wd[b * ws]), null for the unweighted refit
 template <typename T, int NT>
 void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, const T* At, uint32_t ldm, uint32_t m, const T* yd, long long ys,
@@ -343,10 +577,12 @@ void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, co
                            (const T*)nullptr, 0ll);
 }
 
-// Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit
+// Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit.  nonneg: k_rf_nnls in
+// k_rf_solve's place, its capacity, `dropped` (may be null) behind status
 template <typename T>
 int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-               void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, char* err, size_t errlen)
+               void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, bool nonneg, uint32_t* dropped, char* err,
+               size_t errlen)
 {
     HIPCHK(hipSetDevice(ctx->device));
     RefitState* rs = state_of(ctx);
@@ -354,9 +590,9 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, Bu = (uint32_t)B;
     const uint32_t nchunks = (uint32_t)((m + kRfRows - 1) / kRfRows);
-    const uint32_t kcap = std::min<uint32_t>(kmax, SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
+    const uint32_t kcap = std::min<uint32_t>(kmax, nonneg ? SS_HIP_NNLS_KMAX : SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
     const bool in_dev = on_device(records), out_dev = on_device(records_out), y_dev = on_device(Y);
-    if (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>()) {
+    if (nonneg ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>()) : (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>())) {
         set_err(err, errlen, std::string(who) + ": the device does not give a workgroup the LDS of a support this large");
         return SS_HIP_ERUNTIME;
     }
@@ -369,7 +605,8 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
         T* rn = cv.take<T>(B);
         double* rnd = cv.take<double>(B);
         uint32_t* bad = cv.take<uint32_t>(1);
-        use(stage, stat, rn, rnd, bad);
+        uint32_t* drop = nonneg ? cv.take<uint32_t>(B) : nullptr;
+        use(stage, stat, rn, rnd, bad, drop);
         return cv.off;
     };
     grow(rs->batch, rs->batch_bytes, carve_batch(nullptr, [](auto...) {}), "hipMalloc(refit batch)");
@@ -385,7 +622,7 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     grow(rs->arena, rs->arena_bytes, carve_arena(nullptr, [](auto...) {}), "hipMalloc(refit workspace)");
 
     int rc = SS_HIP_OK;
-    carve_batch(rs->batch, [&](unsigned char* stage, uint32_t* stat, T* rn, double* rnd, uint32_t* bad) {
+    carve_batch(rs->batch, [&](unsigned char* stage, uint32_t* stat, T* rn, double* rnd, uint32_t* bad, uint32_t* drop) {
         // din: the input records on the device; dout: where the output records are written there (a host caller's: the staging,
         // in place when the input is staged too)
         const unsigned char* din = static_cast<const unsigned char*>(records);
@@ -398,6 +635,10 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
         HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record is invalid)
         if (first_bad != 0xffffffffu) { rc = bad_index(first_bad, who, err, errlen); return; }
+        if (nonneg) {
+            hipLaunchKernelGGL(k_rf_cap, dim3((Bu + 255u) / 256u), dim3(256), 0, st, din, rb, (uint32_t)SS_HIP_NNLS_KMAX, stat, Bu);
+            HIPCHK(hipGetLastError());
+        }
 
         std::vector<T> tmp;
         carve_arena(rs->arena, [&](T* part, T* ybuf) {
@@ -411,8 +652,12 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
                 if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
                 else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
                 else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
-                hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
-                                   dout + b0 * rb, rb, kmax, stat + b0);
+                if (nonneg)
+                    hipLaunchKernelGGL((k_rf_nnls<T>), dim3(Bc), dim3(256), rf_nnls_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
+                                       dout + b0 * rb, rb, kmax, stat + b0, drop + b0);
+                else
+                    hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
+                                       dout + b0 * rb, rb, kmax, stat + b0);
                 HIPCHK(hipGetLastError());
             }
         });
@@ -425,16 +670,19 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
             HIPCHK(hipMemcpyAsync(resnorm, rnd, B * sizeof(double), hipMemcpyDefault, st));
         }
         if (status) HIPCHK(hipMemcpyAsync(status, stat, B * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (nonneg && dropped) HIPCHK(hipMemcpyAsync(dropped, drop, B * sizeof(uint32_t), hipMemcpyDefault, st));
         if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     });
     return rc;
 }
 
-// weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks
+// weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks;
+// nonneg: the non-negative fit (ss_hip_nonneg_refit_records_*), with `dropped`
 template <typename T>
 int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                void* records_out, double* resnorm, uint32_t* status, bool weighted, const T* W, ptrdiff_t w_stride, char* err, size_t errlen)
+                void* records_out, double* resnorm, uint32_t* status, bool weighted, const T* W, ptrdiff_t w_stride, char* err, size_t errlen,
+                bool nonneg = false, uint32_t* dropped = nullptr)
 {
     const std::string w(who);
     int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
@@ -452,7 +700,7 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
             const int rw = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &ws, err, errlen);
             if (rw != SS_HIP_OK) return rw;
         }
-        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, err, errlen);
+        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, nonneg, dropped, err, errlen);
     });
 }
 
@@ -469,6 +717,18 @@ template int refit_weighted<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t,
                                    double*, uint32_t*, char*, size_t);
 template int refit_weighted<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const double*, ptrdiff_t, const void*, uint32_t, void*,
                                     double*, uint32_t*, char*, size_t);
+
+template <typename T>
+int refit_nonneg(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
+                 double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen)
+{
+    return refit_entry<T>(ctx, "nonneg_refit_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, false, nullptr, 0, err,
+                          errlen, true, dropped);
+}
+template int refit_nonneg<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, double*, uint32_t*, uint32_t*,
+                                 char*, size_t);
+template int refit_nonneg<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, double*, uint32_t*, uint32_t*,
+                                  char*, size_t);
 
 void refit_free(ss_hip_ctx* ctx)
 {

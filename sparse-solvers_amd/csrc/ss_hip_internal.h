@@ -367,6 +367,7 @@ struct ss_hip_ctx {
     void* tc = nullptr;           // sship::TopCorrState* (topcorr.hip): the workspace of the top correlations and the record extension
     void* js = nullptr;           // sship::JointState* (joint.hip): the workspace of the group top correlations and the group class residuals
     void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights and the workspace of the weighted top correlations
+    void* nn = nullptr;           // sship::NonnegState* (nonneg.hip): the workspace of the positive top correlations
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -570,6 +571,13 @@ template <typename T>
 int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
                            const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, const T* Wd, long long ws,
                            char* err, size_t errlen);
+// ... and the non-negative refit whole (refit.hip: refit_records' checks in its order, k_rf_gram as it is, k_rf_nnls in k_rf_solve's
+// place), which nonneg.hip's entry points forward to
+template <typename T>
+int refit_nonneg(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
+                 double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
+// non-negative coding (nonneg.hip): releases the workspace of the positive top correlations
+void nonneg_free(ss_hip_ctx* ctx);
 // the group top correlations and the group class residuals (joint.hip): releases their workspace
 void joint_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of

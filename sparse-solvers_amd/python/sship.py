@@ -158,6 +158,8 @@ _PROTOTYPES = [
     ("ss_hip_weighted_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, ctypes.c_double, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_weighted_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_weighted_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _pd, _vp, _vp] + _ERR),
+    ("ss_hip_nonneg_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _u32, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_nonneg_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _vp, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
     ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
     ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
@@ -877,6 +879,77 @@ class Homotopy(_Context):
         set_classes."""
         records, resnorm, _ = self.weighted_stagewise_code(Y, W, stages, per_stage, kmax=kmax, tolerance=tolerance, min_visible=min_visible)
         best, sci, R = self.weighted_class_residuals(Y, W, records, kmax, residuals=residuals)
+        return best, sci, R, records, resnorm
+
+    # ---- non-negative coding: a fit that only adds atoms, x >= 0 (include/ss_hip.h, csrc/nonneg.hip) ----------------------------
+
+    # the status the non-negative refit adds to REFIT_* (the other five keep their values), the largest support it fits
+    REFIT_STALLED = 5
+    NNLS_KMAX = 128
+
+    def nonneg_top_correlations(self, Y, k, records=None, kmax=None, coef=True, score=True):
+        """The positive top correlations (include/ss_hip.h, ss_hip_nonneg_top_correlations_*): top_correlations over the columns
+        with a_i . r_b > 0 alone, ranked by a_i . r_b / ||a_i|| -> (idx (B, k), coef (B, k) or None, score (B, k) float64 or
+        None).  Every coef is positive; a signal with fewer than k such columns is padded with TOPCORR_NONE / 0.  Everything
+        else as for top_correlations, whose entries with coef > 0 these are, word for word."""
+        if records is None:
+            Yp, B, ys, incy = self._signals(Y)
+            rp, kmax = None, 0
+            if not B:
+                ys, incy = self.m, 1
+        else:
+            if kmax is None:
+                raise ValueError("kmax must be given with records")
+            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        k = int(k)
+        dev = _device_of(Y)
+        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
+        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
+        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
+        _sync_producers(Y, records, idx)
+        _call(self._fn("ss_hip_nonneg_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), k, ip, cp, sp)
+        return idx, cf, sc
+
+    def nonneg_refit_records(self, Y, records, kmax, out=None, residuals=True):
+        """The non-negative refit (include/ss_hip.h, ss_hip_nonneg_refit_records_*): every record's values replaced by
+        argmin ||y_b - A_S z||_2 subject to z >= 0 over its stored columns (Lawson-Hanson on the device) -> (records_out,
+        resnorm (B,) float64 or None, status (B,), dropped (B,)).  A REFIT_DONE record keeps the entries with a positive value,
+        in record order, compacted: K shrinks by dropped[b], the freed slots are zero.  status[b] is one of REFIT_* or
+        REFIT_STALLED; REFIT_TOO_LARGE from NNLS_KMAX + 1 columns on; a record that is not REFIT_DONE comes back unchanged
+        with dropped 0.  Everything else as for refit_records; dropped lives where status lives (int32 on a device)."""
+        Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        if out is None:
+            if isinstance(records, np.ndarray):
+                out = np.empty_like(records)
+            else:
+                import torch
+                out = torch.empty_like(records)
+        op, _ = _records(out, self.record_bytes(kmax), B=B, other="out")
+        dev = _device_of(Y)
+        status, sp = _alloc(dev, (B,), np.uint32)
+        dropped, dp = _alloc(dev, (B,), np.uint32, 0)
+        resnorm, np_ = _alloc(dev, (B,) if residuals else None, np.float64)
+        _sync_producers(Y, records, out)
+        _call(self._fn("ss_hip_nonneg_refit_records_"), self._h, Yp, B, ys, incy, rp, int(kmax), op, np_, sp, dp)
+        return out, resnorm, status, dropped
+
+    def nonneg_stagewise_code(self, Y, stages, per_stage, kmax=96, tolerance=None, records=None):
+        """stagewise_code under x >= 0 -> (records, resnorm (B,) float64, status (B,)): its loop, freezing rules and return
+        values with nonneg_top_correlations(per_stage) -> extend_records -> nonneg_refit_records per stage.  Every stored value
+        is positive; a stage's refit may drop columns an earlier stage entered.  kmax <= NNLS_KMAX."""
+        kmax = int(kmax)
+        if kmax > self.NNLS_KMAX:
+            raise ValueError("kmax must not exceed NNLS_KMAX = %d" % self.NNLS_KMAX)
+        return self._stagewise(Y, stages, kmax, tolerance, records,
+                               lambda cur: self.nonneg_top_correlations(Y, per_stage, records=cur, kmax=kmax, score=False),
+                               lambda ext: self.nonneg_refit_records(Y, ext, kmax)[:3])
+
+    def nonneg_classify(self, Y, stages, per_stage, kmax=96, tolerance=None, residuals=True):
+        """nonneg_stagewise_code followed by class_residuals -> (best (B,), sci (B,), R (B, num_classes) or None, records,
+        resnorm (B,)): sparse-representation classification that never subtracts one class's atoms from another's.  Needs
+        set_classes."""
+        records, resnorm, _ = self.nonneg_stagewise_code(Y, stages, per_stage, kmax=kmax, tolerance=tolerance)
+        best, sci, R = self.class_residuals(Y, records, kmax, residuals=residuals)
         return best, sci, R, records, resnorm
 
     # ---- joint sparse coding of signal groups (include/ss_hip.h, csrc/joint.hip) ------------------------------------------------
