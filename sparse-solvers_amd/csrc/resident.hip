@@ -139,6 +139,14 @@ __device__ __forceinline__ T wave_max_val(T v)
     return b;
 }
 
+// What a wave hands the block-wide pick: its extreme value and, from the lane that holds it, who that is — one 16-byte LDS slot per
+// wave, so that after the barrier ONE burst of reads gives every lane the winner's value, subset index, column and support position.
+// who: bits 0..15 the subset index (kPickNone: the lane owns no column), bits 16..30 the column's support position + 1 (0: not in
+// the support), bit 31 the wave's tie flag (Homotopy's scan).
+constexpr uint32_t kPickNone = 0xffffu;
+template <typename T> struct alignas(16) ResPick { T v; uint32_t who; uint32_t col; };
+static_assert(sizeof(ResPick<float>) == 16 && sizeof(ResPick<double>) == 16, "one 16-byte read per wave");
+
 // ---- k_res_solve ------------------------------------------------------------------------------------------------------
 // One workgroup per slot.  Gs: the subset's Gram matrix [S][gpitch] (rows and columns by subset index); c0: dense over the
 // dictionary's columns, exact at the subset's (c0[sub[j]]); sub: the subset, ascending.  Logs every state (header, x by position),
@@ -158,7 +166,7 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
                  DevState* __restrict__ st_all, TraceEntry* trace, uint32_t trace_cap, unsigned long long* dbg = nullptr)
 {
     // dbg (developer aid, SS_HIP_RES_STAMPS; Homotopy only): cycles of slot 0 by phase, summed over the rounds — [0] scan + arg-min,
-    // [1] log, the entering row, x and c updates, [2] the pass over the inverse, [3] dots, direction, bordered inverse, [4] chain, [5] rounds
+    // [1] the entering row, the deferred bordered inverse, x and c updates, [2] the log and the pass over the inverse, [3] dots, direction, [4] chain, [5] rounds
     unsigned long long tph[6] = { 0, 0, 0, 0, 0, 0 };
     unsigned long long tlast = 0;
 #define RES_STAMP(PH) if constexpr (STAMPS) { const unsigned long long now_ = __builtin_readcyclecounter(); tph[PH] += now_ - tlast; tlast = now_; }
@@ -172,10 +180,8 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
     static_assert(PCAP % 8 == 0 && (CT == 4 || CT == 8), "positions dealt out over the eight lanes of a group");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ T s_max[16];
-    __shared__ T s_minv[16];
-    __shared__ uint32_t s_mini[16];
+    __shared__ ResPick<T> s_pick[NW];
     __shared__ T s_f[4];            // [0] Gram value of the entering column with itself  [1] its sign (OMP: its c0)
-    __shared__ uint32_t s_tie;
     ResLds<T> L;
     {
         T* p = reinterpret_cast<T*>(smem);
@@ -209,6 +215,7 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
     const bool myvalid = owner && mycol < n;
     const T my_c0 = mycol < n ? c0[mycol] : T(0);
     T my_c = my_c0, my_q = T(0);
+    int32_t mypos = -1;                                 // my owned column's position in the support
     T gr[CT][PT];
 #pragma unroll
     for (int c = 0; c < CT; ++c)
@@ -220,7 +227,6 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
         L.u1sg[2 * p] = T(0); L.u1sg[2 * p + 1] = T(0); L.u2w[2 * p] = T(0); L.u2w[2 * p + 1] = T(0);
     }
     for (uint32_t e = t; e < PCAP * IP; e += THREADS) L.I[e] = T(0);     // (entries beyond the support are read as zeros by the pass)
-    if (t == 0) s_tie = 0u;
     // The subset's Gram matrix was written by other compute units' launches: a first touch of every 128-byte line brings it into THIS
     // XCD's L2, so that the entering column's row — the round's only trip to memory — is an L2 hit.  (The loads complete under the
     // prologue; their sum is consumed at the very end.)
@@ -234,42 +240,52 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
 
     // block-wide (value, index) reductions.  Within a wave the owning lanes hold ascending subset indices, and so do the waves: the
     // left-most minimum (maximum) is the first lane of the first wave that holds the extreme VALUE — a value-only reduction on the DPP
-    // path, a ballot, one readlane; the waves' results meet in LDS.
-    auto wave_first = [&](T v, T ext, uint32_t idx) __attribute__((always_inline)) -> uint32_t {
+    // path and a ballot; that lane writes the wave's slot itself (it knows its column and its support position), the waves' slots
+    // meet in LDS and are read in one burst: no dependent look-ups of posof / subc behind the barrier.
+    auto publish_pick = [&](T v, T ext, bool tiew) __attribute__((always_inline)) {
         const unsigned long long bal = __builtin_amdgcn_ballot_w64(v == ext);
-        const int src = bal != 0ull ? (int)__builtin_ctzll(bal) : 0;
-        return (uint32_t)__builtin_amdgcn_readlane((int)idx, src);
+        const uint32_t src = bal != 0ull ? (uint32_t)__builtin_ctzll(bal) : 0u;
+        if (lane == src) {
+            ResPick<T> sl;
+            sl.v = ext;
+            sl.who = (myvalid ? myj : kPickNone) | ((uint32_t)(mypos + 1) << 16) | (tiew ? 0x80000000u : 0u);
+            sl.col = mycol;
+            s_pick[wave] = sl;
+        }
     };
-    auto block_min = [&](T& v, uint32_t& i) __attribute__((always_inline)) {     // one barrier; s_minv / s_mini are rewritten a whole round later
-        const T wv = -wave_max_val<T>(-v);
-        const uint32_t wi = wave_first(v, wv, i);
-        if (lane == 0) { s_minv[wave] = wv; s_mini[wave] = wi; }
-        lds_barrier();
-        T bv = s_minv[0];
-        uint32_t bi = s_mini[0];
+    // -> the extreme value, its subset index (0xffffffff: none), its column, its support position (-1: not in it), any wave's tie flag
+    auto gather_pick = [&](bool want_min, T& v, uint32_t& i, uint32_t& col, int32_t& pos, bool& tie) __attribute__((always_inline)) {
+        ResPick<T> sl[NW];
+#pragma unroll
+        for (uint32_t w = 0; w < NW; ++w) sl[w] = s_pick[w];
+        T bv = sl[0].v;
+        uint32_t bw = sl[0].who, bc = sl[0].col, ties = sl[0].who;
 #pragma unroll
         for (uint32_t w = 1; w < NW; ++w) {
-            const T ov = s_minv[w];
-            const uint32_t oi = s_mini[w];
-            if (ov < bv) { bv = ov; bi = oi; }
+            const bool take = want_min ? sl[w].v < bv : sl[w].v > bv;     // (strict: among equal values the first wave, the smaller indices)
+            bv = take ? sl[w].v : bv; bw = take ? sl[w].who : bw; bc = take ? sl[w].col : bc;
+            ties |= sl[w].who;
         }
-        v = uni(bv); i = uni(bi);
+        v = uni(bv);
+        const uint32_t who = uni((bw & 0x7fffffffu) | (ties & 0x80000000u));
+        col = uni(bc);
+        i = (who & 0xffffu) == kPickNone ? 0xffffffffu : (who & 0xffffu);
+        pos = (int32_t)((who >> 16) & 0x7fffu) - 1;
+        tie = (who >> 31) != 0u;
     };
-    auto block_argmax = [&](T& v, uint32_t& i) __attribute__((always_inline)) {  // (prologue and OMP picks: its own barriers)
-        const T wv = wave_max_val<T>(v);
-        const uint32_t wi = wave_first(v, wv, i);
+    auto block_min = [&](T m, bool tie, T& v, uint32_t& i, uint32_t& col, int32_t& pos, bool& anytie) __attribute__((always_inline)) {
+        // one barrier; the slots are rewritten a whole round later
+        publish_pick(m, -wave_max_val<T>(-m), __builtin_amdgcn_ballot_w64(tie) != 0ull);
         lds_barrier();
-        if (lane == 0) { s_minv[wave] = wv; s_mini[wave] = wi; }
+        gather_pick(true, v, i, col, pos, anytie);
+    };
+    auto block_argmax = [&](T m, T& v, uint32_t& i, uint32_t& col, int32_t& pos) __attribute__((always_inline)) {  // (prologue and OMP picks: its own barriers)
+        const T wv = wave_max_val<T>(m);
         lds_barrier();
-        T bv = s_minv[0];
-        uint32_t bi = s_mini[0];
-#pragma unroll
-        for (uint32_t w = 1; w < NW; ++w) {
-            const T ov = s_minv[w];
-            const uint32_t oi = s_mini[w];
-            if (ov > bv) { bv = ov; bi = oi; }
-        }
-        v = uni(bv); i = uni(bi);
+        publish_pick(m, wv, false);
+        lds_barrier();
+        bool none;
+        gather_pick(false, v, i, col, pos, none);
         lds_barrier();
     };
     // the bordered inverse in place (online_inverse.h:232-248): every element on or above the diagonal is computed once and stored on
@@ -285,51 +301,88 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
             const uint32_t n0 = Pn - a0;                            // elements (a0, a0 .. Pn - 1)
             const uint32_t ntot = a0 == a1 ? n0 : n0 + (Pn - a1);   // ... then (a1, a1 .. Pn - 1)
             const T u0 = a0 < P ? L.u2w[2 * a0] : T(0), u1v = a1 < P ? L.u2w[2 * a1] : T(0);
-#pragma nounroll
-            for (uint32_t k = vg; k < ntot; k += NG) {
+            // (every element is read and written by ONE thread, once: the elements of a thread are independent.  BU of them are
+            // requested together — one LDS round trip per BU elements instead of one each — and an element is a select between the
+            // border's value and the update, not a branch: the operands of the side not taken are zeros of the table, in bounds)
+            constexpr uint32_t BU = sizeof(T) == 8 ? 2u : 3u;
+            auto where = [&](uint32_t k, uint32_t& a, uint32_t& b, T& ua) __attribute__((always_inline)) {
                 const bool first = k < n0;
-                const uint32_t a = first ? a0 : a1;
-                const uint32_t b = first ? a0 + k : a1 + (k - n0);
-                const T ua = first ? u0 : u1v;
-                T val;
-                if (b == P) val = a == P ? dvv : -dvv * ua;
-                else val = L.I[a * IP + b] + (dvv * ua) * L.u2w[2 * b];
-                L.I[a * IP + b] = val;
-                L.I[b * IP + a] = val;
+                a = first ? a0 : a1;
+                b = first ? a0 + k : a1 + (k - n0);
+                ua = first ? u0 : u1v;
+            };
+            auto value = [&](uint32_t a, uint32_t b, T ua, T iv, T ub) __attribute__((always_inline)) -> T {
+                const T edge = a == P ? dvv : -dvv * ua;
+                const T inner = iv + (dvv * ua) * ub;
+                return b == P ? edge : inner;
+            };
+            uint32_t k = vg;
+#pragma nounroll
+            for (; k + (BU - 1u) * NG < ntot; k += BU * NG) {
+                uint32_t ea[BU], eb[BU];
+                T ua[BU], iv[BU], ub[BU];
+#pragma unroll
+                for (uint32_t u = 0; u < BU; ++u) {
+                    where(k + u * NG, ea[u], eb[u], ua[u]);
+                    iv[u] = L.I[ea[u] * IP + eb[u]];
+                    ub[u] = L.u2w[2 * eb[u]];
+                }
+#pragma unroll
+                for (uint32_t u = 0; u < BU; ++u) {
+                    const T val = value(ea[u], eb[u], ua[u], iv[u], ub[u]);
+                    L.I[ea[u] * IP + eb[u]] = val;
+                    L.I[eb[u] * IP + ea[u]] = val;
+                }
+            }
+#pragma nounroll
+            for (; k < ntot; k += NG) {
+                uint32_t ea, eb;
+                T ua;
+                where(k, ea, eb, ua);
+                const T val = value(ea, eb, ua, L.I[ea * IP + eb], L.u2w[2 * eb]);
+                L.I[ea * IP + eb] = val;
+                L.I[eb * IP + ea] = val;
             }
         }
     };
 
-    // The entering column (subset index spi) at position Pn: its Gram values with my group's CT columns into my registers (the
-    // lanes with g == Pn % 8 keep them); returns its Gram value with my OWNED column.
-    // pendP / pend_dv: the bordered-inverse update the PREVIOUS round left undone runs here, between the row's loads and their first
-    // use — under the round's only trip to memory (nobody reads the inverse before the next pass, two barriers on)
-    auto enter_row = [&](uint32_t spi, uint32_t Pn, uint32_t pendP, T pend_dv) __attribute__((always_inline)) -> T {
+    // The entering column (subset index spi): its Gram values with my group's CT columns and with my OWNED column.  row_fetch only
+    // ISSUES the loads — the round's only trip to memory — as soon as the pick is known; everything that does not need the values
+    // (the round's verdict, the bordered-inverse update the PREVIOUS round left undone, the x and c updates, the wave maxima) runs
+    // under that trip.  (The empty asm keeps the compiler from sinking the loads towards their first use.)
+    struct RowVals { T mine; T gv[CT]; };
+    auto row_fetch = [&](uint32_t spi, RowVals& rv) __attribute__((always_inline)) {
         const T* row = Gs + (size_t)spi * gpitch;
-        const T mine_g = row[myj];
-        T gv[CT];
+        rv.mine = row[myj];
         if constexpr (sizeof(T) == 8) {
             const v2d a = *reinterpret_cast<const v2d*>(row + jc0), b = *reinterpret_cast<const v2d*>(row + jc0 + 2);
-            gv[0] = a[0]; gv[1] = a[1]; gv[2] = b[0]; gv[3] = b[1];
+            rv.gv[0] = a[0]; rv.gv[1] = a[1]; rv.gv[2] = b[0]; rv.gv[3] = b[1];
         } else {
             const v4f a = *reinterpret_cast<const v4f*>(row + jc0), b = *reinterpret_cast<const v4f*>(row + jc0 + 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { gv[e] = a[e]; gv[4 + e] = b[e]; }
+            for (int e = 0; e < 4; ++e) { rv.gv[e] = a[e]; rv.gv[4 + e] = b[e]; }
         }
-        border_inverse(pendP, pend_dv);
+        asm volatile("" ::: "memory");
+    };
+    // ... and at position Pn the lanes with g == Pn % 8 keep them (the first use of the loaded values; Pn = 0xffffffff: nobody)
+    auto row_place = [&](uint32_t Pn, const RowVals& rv) __attribute__((always_inline)) {
         // (Pn is the same in every lane: the register block e = Pn / 8 is reached by scalar branches, and within it the lanes with
         // g == Pn % 8 take the values by a conditional move IN PLACE — as plain selects over all CT x PT registers this was 72 / 288
         // vector instructions per round, and the register allocator kept old and new values side by side)
         const uint32_t e_new = uni(Pn >> 3);
         const unsigned long long msk = __builtin_amdgcn_ballot_w64(g == (Pn & 7u));
+        // (the values are awaited HERE on every path: behind this point the compiler knows of no load in flight — a declined round
+        // takes none of the branches below, and every later reuse of these registers would wait for the round's log stores too)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) asm volatile("" :: "v"(rv.gv[c]));
+        asm volatile("" :: "v"(rv.mine));
 #pragma unroll
         for (int e = 0; e < PT; ++e) {
             if (e_new == (uint32_t)e) {
 #pragma unroll
-                for (int c = 0; c < CT; ++c) cmov_inplace(gr[c][e], gv[c], msk);
+                for (int c = 0; c < CT; ++c) cmov_inplace(gr[c][e], rv.gv[c], msk);
             }
         }
-        return mine_g;
     };
     // sum_p vec[p] G[p][my column] over the positions < P (vec is zero beyond P): CT partial sums per lane, then the reduce-scatter
     // over the group's eight lanes — mirror (g <-> 7 - g), xor 2, xor 1; a lane keeps the half its own index bit names
@@ -407,24 +460,27 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
         }
         d1 = wave_sum<T>(a1); d2 = wave_sum<T>(a2);
     };
+    // (a kernel argument the rounds read: fetched once here — left to the compiler it is loaded again from the argument segment,
+    // with a wait of its own, in every round)
+    asm volatile("" : "+s"(trace_cap));
     uint32_t P = 0, status = 0, iter = 0, nlog = 0, reason = 0;
     T c_inf = T(0), lambda_prev = T(0), gamma_prev = T(0), lambda0 = T(0);
-    int32_t mypos = -1;
     bool tie_any = false;
     lds_barrier();
 
     // ---- first pick (homotopy-cpu.cpp:217-229): the left-most largest |c0| of the subset; inv = [1 / ||a||^2] through the norm
     uint32_t sp0;
     {
-        T bv = myvalid ? res_abs<T>(my_c) : T(-1);
-        uint32_t bi = myvalid ? myj : 0xffffffffu;
-        block_argmax(bv, bi);
-        sp0 = bi;
-        lambda0 = bv;
+        uint32_t col0;
+        int32_t pos0;
+        block_argmax(myvalid ? res_abs<T>(my_c) : T(-1), lambda0, sp0, col0, pos0);
     }
     if (sp0 >= S) { status = kStatusSubsetDecline; reason |= kReasonNoCand; }
     else {
-        const T g00 = enter_row(sp0, 0u, 0xffffffffu, T(0));
+        RowVals rv0;
+        row_fetch(sp0, rv0);
+        row_place(0u, rv0);
+        const T g00 = rv0.mine;
         if (owner && myj == sp0) {
             const T nrm = res_sqrt<T>(g00);
             const T inv00 = T(1) / (nrm * nrm);
@@ -467,22 +523,34 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
         }
         for (uint32_t round = 2; status == 0u; ++round) {
             my_c = my_c0 - chain(L.xvec, P);                        // c of this state
-            T bv = T(-1);
-            uint32_t bi = 0xffffffffu;
-            if (myvalid) { bv = res_abs<T>(my_c); bi = myj; }
-            block_argmax(bv, bi);                                   // ||c||_inf over the subset and its left-most column
-            c_inf = bv;
+            uint32_t bi, idx;
+            int32_t wpos;
+            block_argmax(myvalid ? res_abs<T>(my_c) : T(-1), c_inf, bi, idx, wpos);   // ||c||_inf over the subset and its left-most column
+            const uint32_t spi = bi < S ? bi : 0u;
+            RowVals rv;
+            row_fetch(spi, rv);                                     // (the round's trip to memory first: the verdict and the log run under it)
             const bool stop = !(c_inf > tol) || round > max_iter;
             const bool logfull = nlog >= LOGCAP;
-            const uint32_t spi = bi < S ? bi : 0u;
-            const bool stall = !stop && (bi >= S || uni(L.posof[spi]) >= 0);      // (the largest |c| sits ON the support: a numerical stall)
-            const bool full = !stop && (P >= PCAP || P + 1u > kcap);
-            const bool ok = !stop && !logfull && !stall && !full;
-            if (logfull) { status = kStatusSubsetDecline; reason |= kReasonLog; }
-            else if (stall) { status = kStatusSubsetDecline; reason |= kReasonNoCand; }
-            else if (full) { status = kStatusSubsetDecline; reason |= kReasonPositions; }
-            else if (stop) { status = 0xffffffffu; iter = round - 1; }          // (the regular end: status set back to 0 below the loop)
-            const uint32_t idx = uni(L.subc[spi]);
+            // the round's verdict by priority: log full, the regular end, a stall (the largest |c| sits ON the support), positions spent
+            const bool stall_c = bi >= S || wpos >= 0;
+            const bool full_c = P >= PCAP || P + 1u > kcap;
+            uint32_t verdict = full_c ? kReasonPositions : 0u;
+            verdict = stall_c ? (uint32_t)kReasonNoCand : verdict;
+            verdict = stop ? 0u : verdict;
+            verdict = logfull ? (uint32_t)kReasonLog : verdict;
+            const bool ok = !stop && verdict == 0u;
+            const bool ends = stop && !logfull;                     // (the regular end: status set back to 0 below the loop)
+            status = verdict != 0u ? (uint32_t)kStatusSubsetDecline : ends ? 0xffffffffu : status;
+            reason |= verdict;
+            iter = ends ? round - 1 : iter;
+            row_place(ok ? P : 0xffffffffu, rv);
+            const T my_g = rv.mine;
+            // u1 = G[idx][support], b_S = c0_S beside it (the pass forms u2 = I u1 and I b = x of the old support at once)
+            if (owner && mypos >= 0) { L.u1sg[2 * mypos] = my_g; L.u1sg[2 * mypos + 1] = my_c0; }
+            if (ok && owner && myj == spi) { s_f[0] = my_g; s_f[1] = my_c0; L.posof[spi] = (int32_t)P; L.pcol[P] = idx; L.psub[P] = spi; mypos = (int32_t)P; }
+            lds_barrier();
+            // the log of this state (x is rewritten two barriers on): behind the row's first use, so that the wait for the row does
+            // not wait for these stores
             if (!logfull) {
                 if (t == 0) {
                     uint32_t* h = hdr + nlog * 8;
@@ -494,11 +562,6 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
                 if (t < PCAP) LX[(size_t)nlog * PCAP + t] = t < P ? L.xvec[t] : T(0);
                 ++nlog;
             }
-            const T my_g = enter_row(spi, ok ? P : 0xffffffffu, 0xffffffffu, T(0));
-            // u1 = G[idx][support], b_S = c0_S beside it (the pass forms u2 = I u1 and I b = x of the old support at once)
-            if (owner && mypos >= 0) { L.u1sg[2 * mypos] = my_g; L.u1sg[2 * mypos + 1] = my_c0; }
-            if (ok && owner && myj == spi) { s_f[0] = my_g; s_f[1] = my_c0; L.posof[spi] = (int32_t)P; L.pcol[P] = idx; L.psub[P] = spi; mypos = (int32_t)P; }
-            lds_barrier();
             inverse_pass(P);
             lds_barrier();
             T d1, d2;
@@ -517,6 +580,9 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
         if (status == 0u) my_q = chain(L.dvec, P);
         uint32_t pendP = 0xffffffffu;
         T pend_dv = T(0);
+        // the threads that keep the log and x: the LAST ones — the waves the pass over the inverse gives rows last (tl >= PCAP: none)
+        constexpr uint32_t TL0 = THREADS - ((PCAP + 63u) / 64u) * 64u;
+        const uint32_t tl = t - TL0;
         for (uint32_t round = 1; status == 0u; ++round) {
             if constexpr (STAMPS) tlast = __builtin_readcyclecounter();
             // ---- loop control (homotopy-cpu.cpp:236, 272) and the log of this state
@@ -546,51 +612,51 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
                     }
                 }
             }
-            if (tie) s_tie = 1u;                                   // (read behind the reduction's barrier; cleared behind the next one)
-            T gmm = m;
-            uint32_t bi = myvalid ? myj : 0xffffffffu;             // (ascending subset: the left-most column is the smaller index)
-            block_min(gmm, bi);                                    // ---- barrier 1
+            T gmm;
+            uint32_t bi, idx;                                      // (ascending subset: the left-most column is the smaller index)
+            int32_t wpos;
+            bool anytie;
+            block_min(m, tie, gmm, bi, idx, wpos, anytie);         // ---- barrier 1
             RES_STAMP(0)
-            if (!stop) tie_any = uni(s_tie) != 0u || tie_any;      // (the last state takes no step: its scan does not count)
+            // (the entering column's Gram values of my columns: the round's only trip to memory, issued before anything else — a
+            // declined round fetches row 0 and places it nowhere)
             const uint32_t spi = bi < S ? bi : 0u;
-            const bool tied = !stop && tie_any && tie_exit != 0;
-            const bool nocand = !stop && !tied && (bi >= S || !(gmm < Lim<T>::max()));       // (no positive candidate: the reference toggles column 0)
-            const bool leaves = !stop && !tied && !nocand && uni(L.posof[spi]) >= 0;           // (a column leaves: not this form's path)
-            const bool full = !stop && !tied && !nocand && !leaves && (P >= PCAP || P + 1u > kcap);
-            const bool ok = !stop && !logfull && !tied && !nocand && !leaves && !full;
-            if (logfull) { status = kStatusSubsetDecline; reason |= kReasonLog; }
-            else if (stop) { status = 0xffffffffu; iter = round - 1; }          // (the regular end: status set back to 0 below the loop)
-            else if (tied) { status = kStatusTieRerun; reason |= kReasonTie; iter = round - 1; }
-            else if (nocand) { status = kStatusSubsetDecline; reason |= kReasonNoCand; }
-            else if (leaves) { status = kStatusSubsetDecline; reason |= kReasonRemoval; }
-            else if (full) { status = kStatusSubsetDecline; reason |= kReasonPositions; }
-            const uint32_t idx = uni(L.subc[spi]);
-            if (!logfull) {
-                if (t == 0) {
-                    uint32_t* h = hdr + nlog * 8;
-                    h[0] = P; h[1] = stop ? 0u : 1u; h[2] = ok ? idx : 0xffffffffu; h[3] = ok ? 1u : 0u; h[4] = __float_as_uint((float)c_inf);
-                    h[5] = ok ? __float_as_uint((float)gmm) : 0u; h[6] = 0xffffffffu; h[7] = in_band ? 1u : 0u;
-                    if (LH != nullptr) { LH[nlog * 2] = c_inf; LH[nlog * 2 + 1] = ok ? gmm : T(0); }
-                    if (ok && trace != nullptr && round < trace_cap) { trace[round].idx = idx; trace[round].added = 1u; trace[round].gamma = (double)gmm; trace[round].c_inf = (double)c_inf; }
-                }
-                if (t < PCAP) {
-                    LX[(size_t)nlog * PCAP + t] = t < P ? L.xvec[t] : T(0);
-                    if (LD != nullptr) LD[(size_t)nlog * PCAP + t] = t < P ? L.dvec[t] : T(0);
-                }
-                if (stop || tied || ok) ++nlog;                    // (a declined round's state is not part of the path)
-            }
-            // (the entering column's Gram values of my columns: the round's only trip to memory, under the x and c updates)
-            const T my_g = enter_row(spi, ok ? P : 0xffffffffu, pendP, pend_dv);
+            RowVals rv;
+            row_fetch(spi, rv);
+            // ---- the round's verdict by priority: log full, the regular end, a tie, no positive candidate (the reference toggles
+            // column 0), a column leaves (not this form's path), positions spent — selects on uniform values, no branch chain
+            tie_any = tie_any || (!stop && anytie);                // (the last state takes no step: its scan does not count)
+            const bool tied_c = tie_any && tie_exit != 0;
+            const bool nocand_c = bi >= S || !(gmm < Lim<T>::max());
+            const bool full_c = P >= PCAP || P + 1u > kcap;
+            uint32_t verdict = full_c ? kReasonPositions : 0u;
+            verdict = wpos >= 0 ? (uint32_t)kReasonRemoval : verdict;
+            verdict = nocand_c ? (uint32_t)kReasonNoCand : verdict;
+            verdict = tied_c ? (uint32_t)kReasonTie : verdict;
+            verdict = stop ? 0u : verdict;
+            verdict = logfull ? (uint32_t)kReasonLog : verdict;
+            const bool ok = !stop && verdict == 0u;
+            const bool ends = stop && !logfull;                    // (the regular end: status set back to 0 below the loop)
+            const bool tied = verdict == kReasonTie;
+            status = ends ? 0xffffffffu : tied ? (uint32_t)kStatusTieRerun : verdict != 0u ? (uint32_t)kStatusSubsetDecline : status;
+            reason |= verdict;
+            iter = ends || tied ? round - 1 : iter;
+            // ---- x of this state for the log, then x += gamma d over the old support (homotopy-cpu.cpp:252) — by the log's threads
+            T xv = T(0), dv = T(0);
+            if (tl < P) { xv = L.xvec[tl]; dv = L.dvec[tl]; }
+            border_inverse(pendP, pend_dv);                        // (the bordered inverse the previous round left undone)
             pendP = 0xffffffffu;
-            // ---- x += gamma d over the old support (homotopy-cpu.cpp:252); c of the next state and its largest magnitude
-            if (ok && t < P) L.xvec[t] = L.xvec[t] + gmm * L.dvec[t];
+            if (ok && tl < P) L.xvec[tl] = xv + gmm * dv;
+            // ---- c of the next state and its largest magnitude
             if (ok) my_c = res_fma<T>(-gmm, my_q, my_c);
             {
                 const T mx = wave_max_val<T>(myvalid ? res_abs<T>(my_c) : T(-1));
                 if (lane == 0) s_max[wave] = mx;
             }
-            // ---- the column enters at position P: u1 = G[idx][support] and sign(c_S) of the correlations after the step, dead zone tol
-            // (homotopy-cpu.cpp:257-267), side by side for the pass over the inverse
+            // ---- the column enters at position P (the first use of the fetched row): u1 = G[idx][support] and sign(c_S) of the
+            // correlations after the step, dead zone tol (homotopy-cpu.cpp:257-267), side by side for the pass over the inverse
+            row_place(ok ? P : 0xffffffffu, rv);
+            const T my_g = rv.mine;
             if (owner && mypos >= 0) { L.u1sg[2 * mypos] = my_g; L.u1sg[2 * mypos + 1] = sign_tol<T>(my_c, tol); }
             if (ok && owner && myj == spi) {
                 s_f[0] = my_g; s_f[1] = sign_tol<T>(my_c, tol);
@@ -598,11 +664,25 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
             }
             lds_barrier();                                      // ---- barrier 2
             RES_STAMP(1)
+            // ---- the log of this state, from registers: behind the barrier, on the waves the pass over the inverse reaches last
+            if (!logfull) {
+                if (tl == 0u) {
+                    uint32_t* h = hdr + nlog * 8;
+                    h[0] = P; h[1] = stop ? 0u : 1u; h[2] = ok ? idx : 0xffffffffu; h[3] = ok ? 1u : 0u; h[4] = __float_as_uint((float)c_inf);
+                    h[5] = ok ? __float_as_uint((float)gmm) : 0u; h[6] = 0xffffffffu; h[7] = in_band ? 1u : 0u;
+                    if (LH != nullptr) { LH[nlog * 2] = c_inf; LH[nlog * 2 + 1] = ok ? gmm : T(0); }
+                    if (ok && trace != nullptr && round < trace_cap) { trace[round].idx = idx; trace[round].added = 1u; trace[round].gamma = (double)gmm; trace[round].c_inf = (double)c_inf; }
+                }
+                if (tl < PCAP) {
+                    LX[(size_t)nlog * PCAP + tl] = xv;
+                    if (LD != nullptr) LD[(size_t)nlog * PCAP + tl] = dv;
+                }
+                if (stop || tied || ok) ++nlog;                    // (a declined round's state is not part of the path)
+            }
             T c_next = s_max[0];
 #pragma unroll
             for (uint32_t w = 1; w < NW; ++w) { const T o = s_max[w]; c_next = o > c_next ? o : c_next; }
             c_next = uni(c_next);
-            if (t == 0) s_tie = 0u;
             inverse_pass(P);                                      // u2 = I u1 (online_inverse.h:218-225), w = I s
             lds_barrier();                                      // ---- barrier 3
             RES_STAMP(2)
@@ -613,7 +693,7 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
             // the new direction: [w - beta u2; beta]
             if (ok && t < P) L.dvec[t] = L.u2w[2 * t + 1] - beta * L.u2w[2 * t];
             if (ok && t == P) L.dvec[P] = beta;
-            pendP = ok ? P : 0xffffffffu;                          // (the bordered inverse: under the next round's memory trip — enter_row)
+            pendP = ok ? P : 0xffffffffu;                          // (the bordered inverse: under the next round's memory trip — row_fetch)
             pend_dv = dvv;
             lds_barrier();                                      // ---- barrier 4
             RES_STAMP(3)
@@ -1014,7 +1094,7 @@ hipError_t launch_res_solve(ss_hip_ctx* ctx, uint32_t nslots, const T* Gs, uint3
             unsigned long long tp[6];
             if (hipMemcpyAsync(tp, dbg, sizeof(tp), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess) {
                 const double r = tp[5] ? (double)tp[5] : 1.0;
-                std::fprintf(stderr, "[k_res_solve<%s>, cycles per round over %llu rounds] scan+argmin %.0f  row+x+c %.0f  inverse pass %.0f  dots+dir+border %.0f  chain %.0f\n",
+                std::fprintf(stderr, "[k_res_solve<%s>, cycles per round over %llu rounds] scan+argmin %.0f  row+border+x+c %.0f  log+inverse pass %.0f  dots+dir %.0f  chain %.0f\n",
                              sizeof(T) == 8 ? "double" : "float", tp[5], tp[0] / r, tp[1] / r, tp[2] / r, tp[3] / r, tp[4] / r);
             }
             return hipGetLastError();
