@@ -89,7 +89,8 @@ CoherenceState* state_of(ss_hip_ctx* ctx)
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
-template <typename T>
+// SUM: d_i itself is stored instead of its inverse root (coh_launch_norms' flag: the weighted top correlations)
+template <typename T, bool SUM = false>
 __global__ __launch_bounds__(256)
 void k_coh_norms(const T* __restrict__ At, uint32_t ldm, uint32_t m, uint32_t n, uint32_t n_pad, double* __restrict__ rinv)
 {
@@ -101,7 +102,7 @@ void k_coh_norms(const T* __restrict__ At, uint32_t ldm, uint32_t m, uint32_t n,
         for (uint32_t k = lane; k < m; k += 64u) { const double v = (double)a[k]; s = s + v * v; }
     }
     s = wave_sum(s);
-    if (lane == 0) rinv[i] = (i < n && s > 0.0 && s <= 1.7976931348623157e308) ? 1.0 / sqrt(s) : 0.0;
+    if (lane == 0) rinv[i] = (i < n && s > 0.0 && s <= 1.7976931348623157e308) ? (SUM ? s : 1.0 / sqrt(s)) : 0.0;
 }
 
 // qlist: the chunk's queries, padded to whole tiles with SS_HIP_COHERENCE_NONE; pscore / pidx: [query of the chunk][ntiles]
@@ -350,15 +351,17 @@ int coherence_entry(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* mu,
 
 }  // namespace
 
-template <typename T>
+template <typename T, bool SUM>
 hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* rinv)
 {
-    hipLaunchKernelGGL((k_coh_norms<T>), dim3(ctx->n_pad / 4u), dim3(256), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm,
+    hipLaunchKernelGGL((k_coh_norms<T, SUM>), dim3(ctx->n_pad / 4u), dim3(256), 0, ctx->stream, static_cast<const T*>(ctx->At), ctx->ldm,
                        (uint32_t)ctx->m, (uint32_t)ctx->n, ctx->n_pad, rinv);
     return hipGetLastError();
 }
 template hipError_t coh_launch_norms<float>(ss_hip_ctx*, double*);
 template hipError_t coh_launch_norms<double>(ss_hip_ctx*, double*);
+template hipError_t coh_launch_norms<float, true>(ss_hip_ctx*, double*);
+template hipError_t coh_launch_norms<double, true>(ss_hip_ctx*, double*);
 
 void coherence_free(ss_hip_ctx* ctx)
 {

@@ -3,8 +3,10 @@
 //
 // A group is a run of consecutive signals that share one support (simultaneous OMP, the multiple-measurement-vector model).  The
 // first call scores an atom by the l2 norm of its correlations with all residuals of the group and returns the k best atoms no
-// member's record stores; the second adds the class residuals up over the members.  The product A^T R stays topcorr.hip's: its
-// record check, residual block and MFMA tile run unchanged through tc_launch_* (ss_hip_internal.h).  Kernels of this file:
+// member's record stores; the second adds the class residuals up over the members.  The first call's host side is the driver of the
+// top correlations (tc_driver.h: its record check, residual block, norms and copies; the MFMA tile through tc_launch_dots).  This
+// unit supplies the variant: chunks of whole groups (js_chunks) whose output rows are groups, the staged offsets and a score row a
+// group to carve, and what runs on a chunk behind the dots.  Kernels of this file:
 //
 //   k_js_check    the offsets, before anything is written: the first group whose offsets do not start at 0, ascend strictly, end at B
 //                 or span more than SS_HIP_GROUP_MAX signals.  An offset is compared, never used as an address.
@@ -12,8 +14,8 @@
 //                 LDS (and a truncated member); then a thread owns a column and walks the members' rows of D in ascending order —
 //                 the reads are coalesced along i, 4 L n bytes a group in fp32 — and writes the group's score row [n_pad] in double,
 //                 a NaN word at a stored or excluded column.  D itself is not struck into: k_js_coef reads it afterwards.
-//   k_js_select   one workgroup per group: tc_select.h's selection (k_tc_select's total order, list, tie branch and prefix property)
-//                 with the stored score as the key.
+//   k_js_select   one workgroup per group: tc_select.h's selection (tc_select_sorted: k_tc_select's total order, list, tie branch and
+//                 prefix property) with the stored score as the key; it strikes nothing out and writes no coef.
 //   k_js_coef     one workgroup per group: the members' coef rows from D and rn at the group's columns.
 //   k_gc_reduce   one workgroup per group, threads over the classes: the class reduction and the arg-min.
 //
@@ -34,8 +36,7 @@
 // A group's rows depend on A, its own signals and records in order, and k: not on B, on the other groups, on the chunking (a chunk
 // holds whole groups; a row of D is a function of its own signal), on where the pointers live or on what the context did before.
 #include "ss_hip_internal.h"
-#include "record_common.h"
-#include "tc_select.h"
+#include "tc_driver.h"
 
 #include <algorithm>
 #include <cmath>
@@ -47,20 +48,12 @@ namespace {
 constexpr uint32_t kJsGroupMax = SS_HIP_GROUP_MAX;
 constexpr size_t kGcChunkBytes = (size_t)64 << 20;       // the byte budget of a chunk's per-signal class rows (never changes a result)
 
-struct JointState {
-    unsigned char* buf = nullptr;      // per call: inverse norms, staged offsets, records and outputs; per chunk: residuals, dots, score rows
-    size_t bytes = 0;
-};
-
-JointState* state_of(ss_hip_ctx* ctx)
+// the workspace of the group class residuals (ss_hip_ctx::js); the group top correlations carve the top correlations' arena
+WorkArena& state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->js) ctx->js = new JointState();
-    return static_cast<JointState*>(ctx->js);
+    if (!ctx->js) ctx->js = new WorkArena();
+    return *static_cast<WorkArena*>(ctx->js);
 }
-
-__device__ inline double js_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline float js_nan_of(float) { return __int_as_float(0x7fc00000); }
-__device__ inline double js_nan_of(double) { return js_nan(); }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
@@ -110,7 +103,7 @@ void k_js_scores(const T* __restrict__ D, uint32_t n, uint32_t n_pad, const doub
         }
         __syncthreads();
     }
-    double s = js_nan();
+    double s = tc_nan(0.0);
     const double r = rinv[i];
     if (s_trunc == 0u && i < n && r != 0.0 && s_mark[tid] == 0u) {
         const T* d = D + (size_t)lo * n_pad + i;
@@ -195,7 +188,7 @@ void k_gc_reduce(const T* __restrict__ R, const uint32_t* __restrict__ bestb, ui
     if (lo + tid < hi && bestb[lo + tid] == 0xffffffffu) s_trunc = 1u;       // (a group holds at most 256 members: one a thread)
     __syncthreads();
     if (s_trunc != 0u) {                                         // a truncated member: no class is claimed
-        for (uint32_t c = tid; c < C; c += 256u) row[c] = js_nan_of(T(0));
+        for (uint32_t c = tid; c < C; c += 256u) row[c] = tc_nan(T(0));
         if (tid == 0) bestg[g] = 0xffffffffu;
         return;
     }
@@ -236,20 +229,6 @@ void k_gc_reduce(const T* __restrict__ R, const uint32_t* __restrict__ bestb, ui
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-// grow() with an out-of-memory failure turned into the call's SS_HIP_ENOMEM and a message that names the bytes
-bool js_grow(JointState* js, size_t need, const char* who, char* err, size_t errlen)
-{
-    try {
-        grow(js->buf, js->bytes, need, "hipMalloc(joint coding workspace)");
-    } catch (const HipFail& f) {
-        if (f.code != hipErrorOutOfMemory) throw;
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string(who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes");
-        return false;
-    }
-    return true;
-}
-
 // the checks of the offsets the host can make without reading them, in the order they are reported (B > 0)
 int js_check_groups(const char* who, const uint32_t* group_off, size_t Gn, size_t B, char* err, size_t errlen)
 {
@@ -262,15 +241,15 @@ int js_check_groups(const char* who, const uint32_t* group_off, size_t Gn, size_
 
 // The offsets checked on the device (k_js_check) and fetched: hoff [Gn + 1].  Nothing of the caller's has been written when they are
 // wrong.  The workspace is grown for the staging alone: the caller carves it anew afterwards.
-int js_fetch_offsets(ss_hip_ctx* ctx, JointState* js, const char* who, const uint32_t* group_off, size_t Gn, size_t B, std::vector<uint32_t>& hoff,
+int js_fetch_offsets(ss_hip_ctx* ctx, WorkArena& js, const char* who, const uint32_t* group_off, size_t Gn, size_t B, std::vector<uint32_t>& hoff,
                      char* err, size_t errlen)
 {
     hipStream_t st = ctx->stream;
     Carver cv(nullptr);
     cv.take<uint32_t>(1);
     cv.take<uint32_t>(Gn + 1);
-    if (!js_grow(js, cv.off, who, err, errlen)) return SS_HIP_ENOMEM;
-    Carver cw(js->buf);
+    if (!arena_grow(js, cv.off, who, err, errlen)) return SS_HIP_ENOMEM;
+    Carver cw(js.buf);
     uint32_t* bad = cw.take<uint32_t>(1);
     uint32_t* stage = cw.take<uint32_t>(Gn + 1);
     const uint32_t* doff = group_off;
@@ -291,14 +270,12 @@ int js_fetch_offsets(ss_hip_ctx* ctx, JointState* js, const char* who, const uin
     return SS_HIP_OK;
 }
 
-// The chunks of a call: runs of whole groups [g0, g1) of at most `cap` signals and `budget` bytes (per_sig a signal, per_grp a group);
-// a group that exceeds either on its own is a chunk of its own.  -> the most signals and the most groups a chunk holds
-struct JsChunk { size_t g0, g1; };
-void js_chunks(const std::vector<uint32_t>& hoff, size_t cap, size_t budget, size_t per_sig, size_t per_grp, std::vector<JsChunk>& out,
-               size_t& max_sig, size_t& max_grp)
+// The chunks of a call: runs of whole groups — a chunk's rows — of at most `cap` signals and `budget` bytes (per_sig a signal,
+// per_grp a group); a group that exceeds either on its own is a chunk of its own
+std::vector<TcChunk> js_chunks(const std::vector<uint32_t>& hoff, size_t cap, size_t budget, size_t per_sig, size_t per_grp)
 {
     const size_t Gn = hoff.size() - 1;
-    max_sig = max_grp = 0;
+    std::vector<TcChunk> out;
     for (size_t g0 = 0; g0 < Gn;) {
         size_t g1 = g0, sig = 0;
         while (g1 < Gn) {
@@ -307,118 +284,67 @@ void js_chunks(const std::vector<uint32_t>& hoff, size_t cap, size_t budget, siz
             sig += L;
             g1 += 1;
         }
-        out.push_back({ g0, g1 });
-        max_sig = std::max(max_sig, sig);
-        max_grp = std::max(max_grp, g1 - g0);
+        out.push_back({ hoff[g0], g0, (uint32_t)sig, (uint32_t)(g1 - g0) });
         g0 = g1;
     }
+    return out;
 }
 
-template <typename T>
-int group_topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                       const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
-{
-    static const char* who = "group_top_correlations";
-    HIPCHK(hipSetDevice(ctx->device));
-    JointState* js = state_of(ctx);
-    hipStream_t st = ctx->stream;
-    const size_t m = ctx->m, rb = records ? record_bytes(kmax, sizeof(T)) : 0;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, n_pad = ctx->n_pad, Bu = (uint32_t)B;
-    const uint32_t rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
-    const bool rec_dev = records && on_device(records), y_dev = on_device(Y), off_dev = on_device(group_off);
+// the variant of the driver (tc_driver.h): a chunk's rows are its groups; the staged offsets and a score row a group; rn_i; per
+// chunk the dots, the groups' scores, their selection and the members' coef rows
+template <typename T> struct GroupVariant {
+    const uint32_t* group_off;         // the caller's offsets, or nullptr: hoff is staged
+    const std::vector<uint32_t>& hoff;
+    uint32_t* offs = nullptr;
+    double* S = nullptr;
+    const uint32_t* doff = nullptr;
 
-    std::vector<uint32_t> hoff;
-    int rc = js_fetch_offsets(ctx, js, who, group_off, Gn, B, hoff, err, errlen);
-    if (rc != SS_HIP_OK) return rc;
-
-    // the chunks: whole groups under topcorr.hip's byte budget and signal cap, plus a score row a group
-    const size_t per_sig = (size_t)ldm * sizeof(T) + (size_t)n_pad * sizeof(T) + (size_t)rtiles * 4u * sizeof(double) + (y_dev ? 0 : m * sizeof(T));
-    const size_t cap = ctx->tc_chunk_max > 0 ? std::min<size_t>(kTcChunkMax, (size_t)ctx->tc_chunk_max) : kTcChunkMax;
-    std::vector<JsChunk> chunks;
-    size_t max_sig = 0, max_grp = 0;
-    js_chunks(hoff, cap, kTcChunkBytes, per_sig, (size_t)n_pad * sizeof(double), chunks, max_sig, max_grp);
-    const size_t sig_pad = (max_sig + kTcTile - 1) / kTcTile * kTcTile;
-
-    auto carve = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        double* rinv = cv.take<double>(n_pad);
-        uint32_t* bad = cv.take<uint32_t>(1);
-        uint32_t* offs = off_dev ? nullptr : cv.take<uint32_t>(Gn + 1);
-        unsigned char* stage = (records && !rec_dev) ? cv.take<unsigned char>(B * rb) : nullptr;
-        uint32_t* oi = cv.take<uint32_t>(Gn * k);
-        double* os = cv.take<double>(Gn * k);
-        T* oc = cv.take<T>(B * k);
-        T* R = cv.take<T>(sig_pad * ldm);
-        T* D = cv.take<T>(sig_pad * n_pad);
-        double* part = cv.take<double>(max_sig * rtiles * 4u);
-        double* S = cv.take<double>(max_grp * n_pad);
-        T* ybuf = y_dev ? nullptr : cv.take<T>(max_sig * m);
-        use(rinv, bad, offs, stage, oi, os, oc, R, D, part, S, ybuf);
-        return cv.off;
-    };
-    if (!js_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
-
-    carve(js->buf, [&](double* rinv, uint32_t* bad, uint32_t* offs, unsigned char* stage, uint32_t* oi, double* os, T* oc, T* R, T* D, double* part,
-                       double* S, T* ybuf) {
-        const uint32_t* doff = group_off;
-        if (!off_dev) { HIPCHK(hipMemcpyAsync(offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = offs; }
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (records) {
-            if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-            HIPCHK(tc_launch_record_check(ctx, din, rb, kmax, Bu, bad));
-            uint32_t first_bad = kTcNone;
-            HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));            // (nothing has been written when a record is invalid)
-            if (first_bad != kTcNone) { rc = bad_index(first_bad, who, err, errlen); return; }
+    void carve(const ss_hip_ctx* ctx, Carver& cv, size_t, size_t, size_t max_grp)
+    {
+        offs = group_off ? nullptr : cv.take<uint32_t>(hoff.size());
+        S = cv.take<double>(max_grp * ctx->n_pad);
+    }
+    hipError_t prepare(ss_hip_ctx* ctx, double* rinv)
+    {
+        doff = group_off;
+        if (!group_off) {
+            const hipError_t e = hipMemcpyAsync(offs, hoff.data(), hoff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return e;
+            doff = offs;
         }
-        HIPCHK(coh_launch_norms<T>(ctx, rinv));
-        std::vector<T> tmp;
-        for (const JsChunk& ch : chunks) {
-            const size_t b0 = hoff[ch.g0];
-            const uint32_t Bc = hoff[ch.g1] - hoff[ch.g0], Gc = (uint32_t)(ch.g1 - ch.g0);
-            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-            long long ys = y_stride, yi = incy;
-            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-            const unsigned char* recs = records ? din + b0 * rb : nullptr;
-            HIPCHK(tc_launch_residual_block<T>(ctx, yd, ys, yi, recs, rb, kmax, Bc, R, part));
-            HIPCHK(tc_launch_dots<T>(ctx, R, Bc, D));
-            hipLaunchKernelGGL((k_js_scores<T>), dim3(n_pad / 256u, Gc), dim3(256), 0, st, (const T*)D, n, n_pad, (const double*)rinv, recs, rb, kmax,
-                               doff + ch.g0, (uint32_t)b0, S);
-            hipLaunchKernelGGL(k_js_select, dim3(Gc), dim3(256), 0, st, (const double*)S, n, n_pad, k, oi + ch.g0 * k, os + ch.g0 * k);
-            hipLaunchKernelGGL((k_js_coef<T>), dim3(Gc), dim3(256), 0, st, (const T*)D, n_pad, (const double*)rinv, doff + ch.g0, (uint32_t)b0, k,
-                               (const uint32_t*)(oi + ch.g0 * k), oc + b0 * k);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(idx, oi, Gn * k * sizeof(uint32_t), hipMemcpyDefault, st));
-        if (coef) HIPCHK(hipMemcpyAsync(coef, oc, B * k * sizeof(T), hipMemcpyDefault, st));
-        if (score) HIPCHK(hipMemcpyAsync(score, os, Gn * k * sizeof(double), hipMemcpyDefault, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    return rc;
-}
+        return coh_launch_norms<T>(ctx, rinv);
+    }
+    void chunk(ss_hip_ctx* ctx, const TcCall<T>& c, const TcChunk& ch, const TcWork<T>& w)
+    {
+        hipStream_t st = ctx->stream;
+        const uint32_t n = (uint32_t)ctx->n, n_pad = ctx->n_pad, k = c.k;
+        HIPCHK(tc_launch_dots<T>(ctx, w.R, ch.Bc, w.D));
+        hipLaunchKernelGGL((k_js_scores<T>), dim3(n_pad / 256u, ch.Rc), dim3(256), 0, st, (const T*)w.D, n, n_pad, w.norms, w.recs, w.rb, c.kmax,
+                           doff + ch.r0, (uint32_t)ch.b0, S);
+        hipLaunchKernelGGL(k_js_select, dim3(ch.Rc), dim3(256), 0, st, (const double*)S, n, n_pad, k, w.oi + ch.r0 * k, w.os + ch.r0 * k);
+        hipLaunchKernelGGL((k_js_coef<T>), dim3(ch.Rc), dim3(256), 0, st, (const T*)w.D, n_pad, w.norms, doff + ch.r0, (uint32_t)ch.b0, k,
+                           (const uint32_t*)(w.oi + ch.r0 * k), w.oc + ch.b0 * k);
+        HIPCHK(hipGetLastError());
+    }
+};
 
 template <typename T>
-int group_topcorr_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                        const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
+int group_topcorr_entry(ss_hip_ctx* ctx, const TcCall<T>& c, const uint32_t* group_off, size_t Gn)
 {
-    static const char* who = "group_top_correlations";
-    // (without records kmax is ignored: the checks see a capacity that passes)
-    int rc = check_common<T>(ctx, who, records, false, records ? kmax : 1u, err, errlen);
+    int rc = tc_check_call<T>(ctx, c);
     if (rc != SS_HIP_OK) return rc;
-    if (!Y || !idx) { set_err(err, errlen, "group_top_correlations: Y and idx must not be null"); return SS_HIP_EINVAL; }
-    if (k == 0 || k > (uint32_t)SS_HIP_TOPCORR_KMAX) {
-        set_err(err, errlen, std::string(who) + ": k must be 1.." + std::to_string(SS_HIP_TOPCORR_KMAX));
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "group_top_correlations: increments and strides must be positive"); return SS_HIP_EINVAL; }
-    if (B == 0) {
-        if (Gn != 0) { set_err(err, errlen, "group_top_correlations: no signals, but groups"); return SS_HIP_EINVAL; }
-        return SS_HIP_OK;                                     // (every argument above was checked all the same)
-    }
-    if (B >= 0x80000000ull) { set_err(err, errlen, "group_top_correlations: B must stay below 2^31"); return SS_HIP_EINVAL; }
-    if ((rc = js_check_groups(who, group_off, Gn, B, err, errlen)) != SS_HIP_OK) return rc;
-    return guarded(err, errlen, who, [&] {
-        return group_topcorr_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+    if (c.B == 0 && Gn != 0) { set_err(c.err, c.errlen, "group_top_correlations: no signals, but groups"); return SS_HIP_EINVAL; }
+    return tc_run(c, [&] {
+        int rg = js_check_groups(c.who, group_off, Gn, c.B, c.err, c.errlen);
+        if (rg != SS_HIP_OK) return rg;
+        HIPCHK(hipSetDevice(ctx->device));
+        std::vector<uint32_t> hoff;
+        if ((rg = js_fetch_offsets(ctx, topcorr_arena(ctx), c.who, group_off, Gn, c.B, hoff, c.err, c.errlen)) != SS_HIP_OK) return rg;
+        // whole groups under topcorr.hip's byte budget and signal cap, plus a score row a group
+        const bool y_dev = on_device(c.Y);
+        const size_t cap = ctx->tc_chunk_max > 0 ? std::min<size_t>(kTcChunkMax, (size_t)ctx->tc_chunk_max) : kTcChunkMax;
+        GroupVariant<T> v{ on_device(group_off) ? group_off : nullptr, hoff };
+        return tc_drive<T>(ctx, c, y_dev, Gn, js_chunks(hoff, cap, kTcChunkBytes, tc_signal_bytes<T>(ctx, y_dev, 1), (size_t)ctx->n_pad * sizeof(double)), v);
     });
 }
 
@@ -428,7 +354,7 @@ int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride
 {
     static const char* who = "group_class_residuals";
     HIPCHK(hipSetDevice(ctx->device));
-    JointState* js = state_of(ctx);
+    WorkArena& js = state_of(ctx);
     hipStream_t st = ctx->stream;
     const size_t rb = record_bytes(kmax, sizeof(T));
     const uint32_t C = classify_num_classes(ctx);
@@ -439,9 +365,9 @@ int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride
     if (rc != SS_HIP_OK) return rc;
 
     // the per-signal rows never leave the context: chunks of whole groups under a fixed byte budget
-    std::vector<JsChunk> chunks;
+    const std::vector<TcChunk> chunks = js_chunks(hoff, kTcChunkMax, kGcChunkBytes, (size_t)C * sizeof(T) + sizeof(uint32_t), 0);
     size_t max_sig = 0, max_grp = 0;
-    js_chunks(hoff, kTcChunkMax, kGcChunkBytes, (size_t)C * sizeof(T) + sizeof(uint32_t), 0, chunks, max_sig, max_grp);
+    tc_chunk_extent(chunks, max_sig, max_grp);
 
     auto carve = [&](unsigned char* base, auto&& use) {
         Carver cv(base);
@@ -453,18 +379,18 @@ int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride
         use(offs, og, ob, Rb, bb);
         return cv.off;
     };
-    if (!js_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+    if (!arena_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
 
-    carve(js->buf, [&](uint32_t* offs, T* og, uint32_t* ob, T* Rb, uint32_t* bb) {
+    carve(js.buf, [&](uint32_t* offs, T* og, uint32_t* ob, T* Rb, uint32_t* bb) {
         const uint32_t* doff = group_off;
         if (!off_dev) { HIPCHK(hipMemcpyAsync(offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = offs; }
-        for (const JsChunk& ch : chunks) {
-            const size_t b0 = hoff[ch.g0], Bc = hoff[ch.g1] - hoff[ch.g0];
+        for (const TcChunk& ch : chunks) {
+            const size_t b0 = ch.b0, Bc = ch.Bc;
             rc = class_residual_rows<T>(ctx, who, Y + (ptrdiff_t)b0 * y_stride, Bc, y_stride, incy, static_cast<const unsigned char*>(records) + b0 * rb,
                                         kmax, Rb, (ptrdiff_t)C, bb, err, errlen);
             if (rc != SS_HIP_OK) return;                  // (a record index >= n: nothing of the caller's has been written)
-            hipLaunchKernelGGL((k_gc_reduce<T>), dim3((uint32_t)(ch.g1 - ch.g0)), dim3(256), 0, st, (const T*)Rb, (const uint32_t*)bb, C, doff + ch.g0,
-                               (uint32_t)b0, og + ch.g0 * C, ob + ch.g0);
+            hipLaunchKernelGGL((k_gc_reduce<T>), dim3(ch.Rc), dim3(256), 0, st, (const T*)Rb, (const uint32_t*)bb, C, doff + ch.r0, (uint32_t)b0,
+                               og + ch.r0 * C, ob + ch.r0);
             HIPCHK(hipGetLastError());
         }
         if (Rg) HIPCHK(hipMemcpy2DAsync(Rg, (size_t)rg_stride * sizeof(T), og, (size_t)C * sizeof(T), (size_t)C * sizeof(T), Gn, hipMemcpyDefault, st));
@@ -501,7 +427,7 @@ int group_classes_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_strid
 
 void joint_free(ss_hip_ctx* ctx)
 {
-    JointState* js = static_cast<JointState*>(ctx->js);
+    WorkArena* js = static_cast<WorkArena*>(ctx->js);
     if (!js) return;
     if (js->buf) (void)hipFree(js->buf);
     delete js;
@@ -518,13 +444,15 @@ int ss_hip_group_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B,
                                       uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, float* coef, double* score,
                                       char* err, size_t errlen)
 {
-    return group_topcorr_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+    return group_topcorr_entry<float>(ctx, { "group_top_correlations", Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen }, group_off,
+                                      Gn);
 }
 int ss_hip_group_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                                       uint32_t kmax, const uint32_t* group_off, size_t Gn, uint32_t k, uint32_t* idx, double* coef, double* score,
                                       char* err, size_t errlen)
 {
-    return group_topcorr_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, k, idx, coef, score, err, errlen);
+    return group_topcorr_entry<double>(ctx, { "group_top_correlations", Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen }, group_off,
+                                       Gn);
 }
 
 int ss_hip_group_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,

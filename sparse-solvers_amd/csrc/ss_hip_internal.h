@@ -364,10 +364,9 @@ struct ss_hip_ctx {
     void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
     void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
     void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
-    void* tc = nullptr;           // sship::TopCorrState* (topcorr.hip): the workspace of the top correlations and the record extension
-    void* js = nullptr;           // sship::JointState* (joint.hip): the workspace of the group top correlations and the group class residuals
-    void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights and the workspace of the weighted top correlations
-    void* nn = nullptr;           // sship::NonnegState* (nonneg.hip): the workspace of the positive top correlations
+    void* tc = nullptr;           // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
+    void* js = nullptr;           // sship::WorkArena* (joint.hip): the workspace of the group class residuals
+    void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -531,12 +530,20 @@ void refit_free(ss_hip_ctx* ctx);
 void ksvd_free(ss_hip_ctx* ctx);
 // the coherence of atoms (coherence.hip): releases its workspace
 void coherence_free(ss_hip_ctx* ctx);
-// ... and the launch of its norms kernel the top correlations (topcorr.hip) share with it, on the context's stream: rinv[i] = 1 / sqrt(d_i),
-// d_i = sum_k a_ki^2 in double, for i < n_pad (0 for an excluded column: d_i zero or not finite, or i >= n) — k_coh_norms' words
-template <typename T> hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* rinv);
-// the top correlations and the record extension (topcorr.hip): releases their workspace
+// ... and the launch of its norms kernel the top correlations share with it, on the context's stream: out[i] = 1 / sqrt(d_i), d_i =
+// sum_k a_ki^2 in double, for i < n_pad (0 for an excluded column: d_i zero or not finite, or i >= n) — k_coh_norms' words.  SUM: d_i
+// itself is stored instead (the weighted top correlations' visible share needs d_i, not its inverse root)
+template <typename T, bool SUM = false> hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* out);
+// A workspace on the device that a call carves anew every time (arena_grow, tc_driver.h) — calls on a context are serial
+struct WorkArena {
+    unsigned char* buf = nullptr;
+    size_t bytes = 0;
+};
+// ... and the one of the top correlations (topcorr.hip), which the four selection calls (tc_driver.h) and the record extension carve.
+// topcorr_free releases it
+WorkArena& topcorr_arena(ss_hip_ctx* ctx);
 void topcorr_free(ss_hip_ctx* ctx);
-// ... and the launches of a chunk's kernels the group top correlations (joint.hip) share with them, on the context's stream, every pointer on
+// ... and the launches of a chunk's kernels behind the driver (tc_driver.h), on the context's stream, every pointer on
 // the device.  tc_launch_record_check: bad[0] = the first of B records with a column index >= n (else 0xffffffff).
 // tc_launch_residual_block: R[b][0 .. ldm) for Bc <= 32768 signals — y_b - A x_b from recs on (dl_launch_residuals, with its partials in
 // part) or the words of y_b (recs == nullptr) — and zero rows behind them up to a whole tile of 128.  tc_launch_dots: D [tiles x 128][n_pad]
@@ -549,7 +556,7 @@ template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uin
 // ... and k_tc_tile with its squaring flag: D2 [tiles x 128][n_pad] = sum_k Wb[b][k] * (a_ki * a_ki), the square formed once in T where
 // At is staged — the second product of the weighted top correlations (weighted.hip); Wb [tiles x 128][ldm] as R above
 template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
-// weighted coding (weighted.hip): releases its workspace
+// weighted coding (weighted.hip): releases the staged weights
 void weighted_free(ss_hip_ctx* ctx);
 // ... and what the three weighted calls share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
 // weights_on_device: the batch's weights where the kernels read them — W itself, or a staged copy of a host caller's (row pitch m, or
@@ -576,9 +583,7 @@ int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, cons
 template <typename T>
 int refit_nonneg(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
                  double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
-// non-negative coding (nonneg.hip): releases the workspace of the positive top correlations
-void nonneg_free(ss_hip_ctx* ctx);
-// the group top correlations and the group class residuals (joint.hip): releases their workspace
+// the group class residuals (joint.hip): releases their workspace
 void joint_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of
 // `r_stride` >= num_classes elements and best [B], the words of that call.  Y, records, R and best on either side; `who` names the

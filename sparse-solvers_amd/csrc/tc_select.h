@@ -1,7 +1,9 @@
-// What topcorr.hip and joint.hip share: the chunk's constants and the selection of the k best columns of one row under the total
-// order (score descending, index ascending), stated once and parameterised by where a column's key comes from.  k_tc_select forms
-// the key on the fly from a signal's dots and rn, k_js_select reads a group's stored score.  Integer and comparison logic only: the
-// result is a function of the keys, whichever kernel asks.
+// The selection of the top correlations, stated once (topcorr.hip, nonneg.hip, weighted.hip, joint.hip): the chunk's constants, the
+// choice of the k best columns of one row under the total order (score descending, index ascending) — tc_select_sorted, parameterised
+// by where a column's key comes from — and k_tc_select, the kernel of the calls whose row is a signal: it strikes the record's
+// columns out of the row of D, selects, and writes idx / coef / score; what a candidate is, its key and its coef come from a small
+// device-side SCORER the call passes by value.  joint.hip's k_js_select calls tc_select_sorted with a group's stored score.
+// Integer and comparison logic only outside the scorers: the result is a function of the keys, whichever kernel asks.
 // Everything sits in an unnamed namespace: each unit gets its own copy, nothing here is part of the library's link surface.
 #pragma once
 
@@ -17,6 +19,10 @@ constexpr uint32_t kTcList = 1024;                       // entries of the selec
 constexpr uint32_t kTcChunkMax = 32768;                  // most signals per chunk (grid.y of the residual kernels)
 constexpr size_t kTcChunkBytes = (size_t)1536 << 20;     // the byte budget of a chunk's residuals and dots (never changes a result)
 static_assert(kTcList >= 2 * SS_HIP_TOPCORR_KMAX, "the list holds the k best and a boundary bin");
+
+// the quiet NaN that strikes a column out: a NaN score is never selected
+__device__ inline float tc_nan(float) { return __int_as_float(0x7fc00000); }
+__device__ inline double tc_nan(double) { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // (key, index): a comes before b when its score is larger, or equal with the smaller index; the keys are the bits of non-negative
 // doubles, which order as the doubles do
@@ -126,6 +132,49 @@ __device__ inline uint32_t tc_select_sorted(TcSelectLds& s, uint32_t n, uint32_t
         }
     __syncthreads();
     return L;
+}
+
+// One workgroup per signal.  D: the chunk's dots, row b of it is this workgroup's to strike columns out of; rec == nullptr: no
+// records.  Scorer: sc.row(b, n_pad) -> the scorer of signal b, with key(d, i, key) — the key of column i from the row d, false for
+// a column that is no candidate — and coef(d, i), the coefficient of a selected column
+template <typename T, typename Scorer>
+__global__ __launch_bounds__(256)
+void k_tc_select(T* __restrict__ D, uint32_t n, uint32_t n_pad, const Scorer sc, const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax,
+                 uint32_t k, uint32_t* __restrict__ oidx, T* __restrict__ ocoef, double* __restrict__ oscore)
+{
+    __shared__ TcSelectLds lds;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    T* d = D + (size_t)b * n_pad;
+    oidx += (size_t)b * k;
+    ocoef += (size_t)b * k;
+    oscore += (size_t)b * k;
+    if (rec) {
+        const unsigned char* r = rec + (size_t)b * rb;
+        const uint32_t K = *reinterpret_cast<const uint32_t*>(r);
+        if (K > kmax) {                                          // a truncated record does not hold its support: no candidates
+            for (uint32_t t = tid; t < k; t += 256u) { oidx[t] = kTcNone; ocoef[t] = T(0); oscore[t] = 0.0; }
+            return;
+        }
+        const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+        for (uint32_t e = tid; e < K; e += 256u) d[idx[e]] = tc_nan(T(0));        // (idx < n: tc_launch_record_check)
+        __threadfence_block();
+        __syncthreads();
+    }
+    const auto row = sc.row(b, n_pad);
+    auto keyof = [&](uint32_t i, unsigned long long& key) -> bool { return row.key(d, i, key); };
+    const uint32_t L = tc_select_sorted(lds, n, k, keyof);
+    for (uint32_t t = tid; t < k; t += 256u) {
+        if (t < L) {
+            const uint32_t i = lds.lidx[t];
+            oidx[t] = i;
+            ocoef[t] = row.coef(d, i);
+            oscore[t] = __longlong_as_double((long long)lds.lkey[t]);
+        } else {
+            oidx[t] = kTcNone;
+            ocoef[t] = T(0);
+            oscore[t] = 0.0;
+        }
+    }
 }
 
 }  // namespace

@@ -14,13 +14,14 @@
 //                 queries are the rows of the residual block [Bc][ldm], the other operand is At.  Tiling, staging, MFMA instructions
 //                 and chain order are coherence.hip's k_coh_tile (its main loop is stated here a second time: the two epilogues share
 //                 nothing, and coherence.hip stays the unit its tests pin).  Epilogue: dot in T to the block D [Bc][n_pad].
-//   k_tc_select   one workgroup per signal.  The record's columns are struck out of the signal's row of D by index (a NaN word: a NaN
-//                 score is never selected); the scores are formed in double from the stored dots and rn; the k best by the total order
-//                 (score descending, index ascending) are found by a radix selection on the score's bits — eight bits a pass, LDS
-//                 histogram of integer counts — until the columns that can still be among the k best fit an LDS list of 1024, which is
-//                 sorted by the total order (bitonic).  All columns tied on the k-th score (a zero residual): the smallest indices
-//                 are taken in ascending blocks.  The selection behind the key is tc_select.h's tc_select_sorted, which joint.hip's
-//                 k_js_select calls with a group's stored score.
+//   k_tc_select   (tc_select.h) one workgroup per signal.  The record's columns are struck out of the signal's row of D by index (a
+//                 NaN word: a NaN score is never selected); the scores are formed in double from the stored dots and rn by this unit's
+//                 scorer, TcAbsScorer; the k best by the total order (score descending, index ascending) are found by a radix
+//                 selection on the score's bits — eight bits a pass, LDS histogram of integer counts — until the columns that can
+//                 still be among the k best fit an LDS list of 1024, which is sorted by the total order (bitonic).  All columns tied
+//                 on the k-th score (a zero residual): the smallest indices are taken in ascending blocks.  nonneg.hip and
+//                 weighted.hip run the same kernel with their scorers; joint.hip's k_js_select calls the selection behind the key
+//                 (tc_select_sorted) with a group's stored score.
 //   k_tc_extend_check / k_tc_extend   the record extension: one workgroup per signal, the record in LDS, the entries of the row one
 //                 after the other (membership and insertion point across the threads, the move block by block from the top).
 //
@@ -38,12 +39,12 @@
 //                histogram's counts, the slots of the unsorted list) cannot change it: counts commute, and the list is sorted by a
 //                total order afterwards.  No floating-point atomics.
 // Nothing depends on B, on the chunking, on the launch geometry, on where the pointers live or on what the context did before.
-// tc_launch_record_check / tc_launch_residual_block / tc_launch_dots (ss_hip_internal.h) are the launches of a chunk's record check,
-// residual block and dot block: joint.hip and weighted.hip run the same kernels through them; tc_launch_weight_dots is k_tc_tile with
-// the squaring flag, weighted.hip's second product.
+// The host side of ss_hip_top_correlations_* is the driver tc_driver.h states once for the four selection calls; this unit owns
+// the arena they and the record extension carve (topcorr_arena) and the launches behind the driver (ss_hip_internal.h):
+// tc_launch_record_check / tc_launch_residual_block / tc_launch_dots, a chunk's record check, residual block and dot block, and
+// tc_launch_weight_dots, k_tc_tile with the squaring flag, weighted.hip's second product.
 #include "ss_hip_internal.h"
-#include "record_common.h"
-#include "tc_select.h"
+#include "tc_driver.h"
 
 #include <algorithm>
 #include <cmath>
@@ -77,20 +78,6 @@ template <> struct TcMma<double> {
     // C/D layout of the fp64 16 x 16 MFMA: col = lane & 15, row = (lane >> 4) + 4 reg
     __device__ static uint32_t row(uint32_t e, uint32_t hq) { return 4u * e + hq; }
 };
-
-struct TopCorrState {
-    unsigned char* buf = nullptr;      // per call: inverse norms, staged records and outputs; per chunk: residuals, dots, a host caller's signals
-    size_t bytes = 0;
-};
-
-TopCorrState* state_of(ss_hip_ctx* ctx)
-{
-    if (!ctx->tc) ctx->tc = new TopCorrState();
-    return static_cast<TopCorrState*>(ctx->tc);
-}
-
-__device__ inline float tc_nan(float) { return __int_as_float(0x7fc00000); }
-__device__ inline double tc_nan(double) { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
@@ -224,55 +211,25 @@ void k_tc_tile(const T* __restrict__ At, uint32_t ldm, const T* __restrict__ R, 
         }
 }
 
-// D: the chunk's dots, row b of it is this workgroup's to strike columns out of; rec == nullptr: no records.  The selection itself
-// is tc_select.h's, with the key formed on the fly from the row of D and rn
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_tc_select(T* __restrict__ D, uint32_t n, uint32_t n_pad, const double* __restrict__ rinv, const unsigned char* __restrict__ rec,
-                 size_t rb, uint32_t kmax, uint32_t k, uint32_t* __restrict__ oidx, T* __restrict__ ocoef, double* __restrict__ oscore)
-{
-    __shared__ TcSelectLds lds;
-    const uint32_t b = blockIdx.x, tid = threadIdx.x;
-    T* d = D + (size_t)b * n_pad;
-    oidx += (size_t)b * k;
-    ocoef += (size_t)b * k;
-    oscore += (size_t)b * k;
-    if (rec) {
-        const unsigned char* r = rec + (size_t)b * rb;
-        const uint32_t K = *reinterpret_cast<const uint32_t*>(r);
-        if (K > kmax) {                                          // a truncated record does not hold its support: no candidates
-            for (uint32_t t = tid; t < k; t += 256u) { oidx[t] = kTcNone; ocoef[t] = T(0); oscore[t] = 0.0; }
-            return;
-        }
-        const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
-        for (uint32_t e = tid; e < K; e += 256u) d[idx[e]] = tc_nan(T(0));        // (idx < n: k_tc_check)
-        __threadfence_block();
-        __syncthreads();
-    }
-    // the key of column i, false for a column that is no candidate
-    auto keyof = [&](uint32_t i, unsigned long long& key) -> bool {
+// top_correlations' scorer for k_tc_select (tc_select.h): every column with a norm is a candidate, s = |dot| * rn_i
+template <typename T> struct TcAbsScorer {
+    const double* __restrict__ rinv;
+    __device__ const TcAbsScorer& row(uint32_t, uint32_t) const { return *this; }
+    __device__ bool key(const T* d, uint32_t i, unsigned long long& key) const
+    {
         const double r = rinv[i];
         if (r == 0.0) return false;
         const double s = fabs((double)d[i]) * r;
         if (!(s == s)) return false;
         key = (unsigned long long)__double_as_longlong(s);
         return true;
-    };
-    const uint32_t L = tc_select_sorted(lds, n, k, keyof);
-    for (uint32_t t = tid; t < k; t += 256u) {
-        if (t < L) {
-            const uint32_t i = lds.lidx[t];
-            const double r = rinv[i];
-            oidx[t] = i;
-            ocoef[t] = (T)((double)d[i] * (r * r));
-            oscore[t] = __longlong_as_double((long long)lds.lkey[t]);
-        } else {
-            oidx[t] = kTcNone;
-            ocoef[t] = T(0);
-            oscore[t] = 0.0;
-        }
     }
-}
+    __device__ T coef(const T* d, uint32_t i) const
+    {
+        const double r = rinv[i];
+        return (T)((double)d[i] * (r * r));
+    }
+};
 
 // bad[0]: the first record with a column index >= n; bad[1]: the first row of idx with an entry >= n that is not NONE
 __global__ __launch_bounds__(64)
@@ -365,115 +322,6 @@ void k_tc_extend(const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-// grow() with an out-of-memory failure turned into the call's SS_HIP_ENOMEM and a message that names the bytes
-bool tc_grow(TopCorrState* ts, size_t need, const char* who, char* err, size_t errlen)
-{
-    try {
-        grow(ts->buf, ts->bytes, need, "hipMalloc(top correlations workspace)");
-    } catch (const HipFail& f) {
-        if (f.code != hipErrorOutOfMemory) throw;
-        (void)hipGetLastError();
-        set_err(err, errlen, std::string(who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes");
-        return false;
-    }
-    return true;
-}
-
-template <typename T>
-int topcorr_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, uint32_t k,
-                 uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
-{
-    static const char* who = "top_correlations";
-    HIPCHK(hipSetDevice(ctx->device));
-    TopCorrState* ts = state_of(ctx);
-    hipStream_t st = ctx->stream;
-    const size_t m = ctx->m, rb = records ? record_bytes(kmax, sizeof(T)) : 0;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, n_pad = ctx->n_pad, Bu = (uint32_t)B;
-    const uint32_t rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
-    const bool rec_dev = records && on_device(records), y_dev = on_device(Y);
-
-    // the chunk: whole signal tiles under the byte budget
-    const size_t per = (size_t)ldm * sizeof(T) + (size_t)n_pad * sizeof(T) + (size_t)rtiles * 4u * sizeof(double) + (y_dev ? 0 : m * sizeof(T));
-    size_t chunk = std::max<size_t>(kTcTile, std::min<size_t>(kTcChunkMax, kTcChunkBytes / per) / kTcTile * kTcTile);
-    if (ctx->tc_chunk_max > 0) chunk = std::min<size_t>(chunk, (size_t)ctx->tc_chunk_max);
-    chunk = std::min(chunk, B);
-    const size_t chunk_pad = (chunk + kTcTile - 1) / kTcTile * kTcTile;
-
-    auto carve = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        double* rinv = cv.take<double>(n_pad);
-        uint32_t* bad = cv.take<uint32_t>(1);
-        unsigned char* stage = (records && !rec_dev) ? cv.take<unsigned char>(B * rb) : nullptr;
-        uint32_t* oi = cv.take<uint32_t>(B * k);
-        T* oc = cv.take<T>(B * k);
-        double* os = cv.take<double>(B * k);
-        T* R = cv.take<T>(chunk_pad * ldm);
-        T* D = cv.take<T>(chunk_pad * n_pad);
-        double* part = cv.take<double>(chunk * rtiles * 4u);
-        T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
-        use(rinv, bad, stage, oi, oc, os, R, D, part, ybuf);
-        return cv.off;
-    };
-    if (!tc_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
-
-    int rc = SS_HIP_OK;
-    carve(ts->buf, [&](double* rinv, uint32_t* bad, unsigned char* stage, uint32_t* oi, T* oc, double* os, T* R, T* D, double* part, T* ybuf) {
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (records) {
-            if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-            HIPCHK(tc_launch_record_check(ctx, din, rb, kmax, Bu, bad));
-            uint32_t first_bad = kTcNone;
-            HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));            // (nothing has been written when a record is invalid)
-            if (first_bad != kTcNone) { rc = bad_index(first_bad, who, err, errlen); return; }
-        }
-        HIPCHK(coh_launch_norms<T>(ctx, rinv));
-        std::vector<T> tmp;
-        for (size_t b0 = 0; b0 < B; b0 += chunk) {
-            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-            long long ys = y_stride, yi = incy;
-            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-            HIPCHK(tc_launch_residual_block<T>(ctx, yd, ys, yi, records ? din + b0 * rb : nullptr, rb, kmax, Bc, R, part));
-            HIPCHK(tc_launch_dots<T>(ctx, R, Bc, D));
-            hipLaunchKernelGGL((k_tc_select<T>), dim3(Bc), dim3(256), 0, st, D, n, n_pad, (const double*)rinv, records ? din + b0 * rb : nullptr, rb,
-                               kmax, k, oi + b0 * k, oc + b0 * k, os + b0 * k);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(idx, oi, B * k * sizeof(uint32_t), hipMemcpyDefault, st));
-        if (coef) HIPCHK(hipMemcpyAsync(coef, oc, B * k * sizeof(T), hipMemcpyDefault, st));
-        if (score) HIPCHK(hipMemcpyAsync(score, os, B * k * sizeof(double), hipMemcpyDefault, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    return rc;
-}
-
-// the checks the two entry points share beyond check_common's, in the order they are reported
-int tc_check_k(const char* who, uint32_t k, char* err, size_t errlen)
-{
-    if (k == 0 || k > (uint32_t)SS_HIP_TOPCORR_KMAX) {
-        set_err(err, errlen, std::string(who) + ": k must be 1.." + std::to_string(SS_HIP_TOPCORR_KMAX));
-        return SS_HIP_EINVAL;
-    }
-    return SS_HIP_OK;
-}
-
-template <typename T>
-int topcorr_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, uint32_t k,
-                  uint32_t* idx, T* coef, double* score, char* err, size_t errlen)
-{
-    static const char* who = "top_correlations";
-    // (without records kmax is ignored: the checks see a capacity that passes)
-    int rc = check_common<T>(ctx, who, records, false, records ? kmax : 1u, err, errlen);
-    if (rc != SS_HIP_OK) return rc;
-    if (!Y || !idx) { set_err(err, errlen, "top_correlations: Y and idx must not be null"); return SS_HIP_EINVAL; }
-    if ((rc = tc_check_k(who, k, err, errlen)) != SS_HIP_OK) return rc;
-    if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "top_correlations: increments and strides must be positive"); return SS_HIP_EINVAL; }
-    if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
-    if (B >= 0x80000000ull) { set_err(err, errlen, "top_correlations: B must stay below 2^31"); return SS_HIP_EINVAL; }
-    return guarded(err, errlen, who, [&] { return topcorr_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen); });
-}
-
 template <typename T>
 int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const T* coef, uint32_t k, void* records_out,
                 uint32_t* added, char* err, size_t errlen)
@@ -481,7 +329,7 @@ int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, c
     static const char* who = "extend_records";
     constexpr uint32_t VW = sizeof(T) / 4;
     HIPCHK(hipSetDevice(ctx->device));
-    TopCorrState* ts = state_of(ctx);
+    WorkArena& ts = topcorr_arena(ctx);
     hipStream_t st = ctx->stream;
     const size_t rb = record_bytes(kmax, sizeof(T));
     const uint32_t n = (uint32_t)ctx->n, Bu = (uint32_t)B;
@@ -497,10 +345,10 @@ int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, c
         use(stage, di, dc, dadd, bad);
         return cv.off;
     };
-    if (!tc_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+    if (!arena_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
 
     int rc = SS_HIP_OK;
-    carve(ts->buf, [&](unsigned char* stage, uint32_t* di, T* dc, uint32_t* dadd, uint32_t* bad) {
+    carve(ts.buf, [&](unsigned char* stage, uint32_t* di, T* dc, uint32_t* dadd, uint32_t* bad) {
         // din / dout: as in refit.hip (a host caller's records are staged, in place when the input is staged too)
         const unsigned char* din = static_cast<const unsigned char*>(records);
         if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
@@ -553,7 +401,7 @@ int extend_entry(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, 
 
 }  // namespace
 
-// ---- the launches joint.hip shares (ss_hip_internal.h), on the context's stream, every pointer on the device -----------------------
+// ---- the launches behind the driver (ss_hip_internal.h), on the context's stream, every pointer on the device -----------------------
 
 hipError_t tc_launch_record_check(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, uint32_t* bad)
 {
@@ -606,9 +454,15 @@ template hipError_t tc_launch_dots<double>(ss_hip_ctx*, const double*, uint32_t,
 template hipError_t tc_launch_weight_dots<float>(ss_hip_ctx*, const float*, uint32_t, float*);
 template hipError_t tc_launch_weight_dots<double>(ss_hip_ctx*, const double*, uint32_t, double*);
 
+WorkArena& topcorr_arena(ss_hip_ctx* ctx)
+{
+    if (!ctx->tc) ctx->tc = new WorkArena();
+    return *static_cast<WorkArena*>(ctx->tc);
+}
+
 void topcorr_free(ss_hip_ctx* ctx)
 {
-    TopCorrState* ts = static_cast<TopCorrState*>(ctx->tc);
+    WorkArena* ts = static_cast<WorkArena*>(ctx->tc);
     if (!ts) return;
     if (ts->buf) (void)hipFree(ts->buf);
     delete ts;
@@ -624,12 +478,12 @@ extern "C" {
 int ss_hip_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                                 uint32_t kmax, uint32_t k, uint32_t* idx, float* coef, double* score, char* err, size_t errlen)
 {
-    return topcorr_entry<float>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen);
+    return tc_dots_entry<float, TcAbsScorer<float>>(ctx, { "top_correlations", Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen });
 }
 int ss_hip_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                                 uint32_t kmax, uint32_t k, uint32_t* idx, double* coef, double* score, char* err, size_t errlen)
 {
-    return topcorr_entry<double>(ctx, Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen);
+    return tc_dots_entry<double, TcAbsScorer<double>>(ctx, { "top_correlations", Y, B, y_stride, incy, records, kmax, k, idx, coef, score, err, errlen });
 }
 
 int ss_hip_extend_records_f32(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const float* coef, uint32_t k,

@@ -650,23 +650,33 @@ class Homotopy(_Context):
         coef = a_i . r_b / ||a_i||^2, the least-squares coefficient of r_b on that atom alone.  Entries behind the last candidate
         are TOPCORR_NONE in idx and 0 in coef and score.  The outputs live where Y lives: device tensors for a device Y (idx then
         int32: TOPCORR_NONE reads as -1), else numpy arrays (idx uint32)."""
+        Yp, B, ys, incy, rp, kmax = self._topcorr_signals(Y, records, kmax)
+        k = int(k)
+        outs, ptrs = self._topcorr_outputs(Y, records, B, B, k, coef, score)
+        _call(self._fn("ss_hip_top_correlations_"), self._h, Yp, B, ys, incy, rp, kmax, k, *ptrs)
+        return outs
+
+    def _topcorr_signals(self, Y, records, kmax):
+        """The signals of the four top-correlation methods, with or without records -> (Y pointer, B, y_stride, incy, records
+        pointer or None, kmax).  records=None: kmax is passed as 0, and an empty batch passes contiguous strides."""
         if records is None:
             Yp, B, ys, incy = self._signals(Y)
-            rp, kmax = None, 0
             if not B:
                 ys, incy = self.m, 1
-        else:
-            if kmax is None:
-                raise ValueError("kmax must be given with records")
-            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
-        k = int(k)
+            return Yp, B, ys, incy, None, 0
+        if kmax is None:
+            raise ValueError("kmax must be given with records")
+        return (*self._signals_with_records(Y, records, kmax, contiguous_if_empty=True), int(kmax))
+
+    def _topcorr_outputs(self, Y, records, B, rows, k, coef, score):
+        """... and their outputs, where Y lives -> ((idx (rows, k), coef (B, k) or None, score (rows, k) or None), their pointers),
+        ordered behind the producers of Y and records."""
         dev = _device_of(Y)
-        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
+        idx, ip = _alloc(dev, (rows, k), np.uint32, self.TOPCORR_NONE)
         cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
-        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
+        sc, sp = _alloc(dev, (rows, k) if score else None, np.float64, 0.0)
         _sync_producers(Y, records, idx)
-        _call(self._fn("ss_hip_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), k, ip, cp, sp)
-        return idx, cf, sc
+        return (idx, cf, sc), (ip, cp, sp)
 
     def extend_records(self, records, kmax, idx, coef=None, out=None):
         """The record extension (include/ss_hip.h, ss_hip_extend_records_*): per signal the columns idx[b, :] enter the record in
@@ -803,28 +813,16 @@ class Homotopy(_Context):
         d(i, b), the weighted least-squares coefficient of r_b on that atom alone.  A column whose visible share d(i, b) /
         (max_k w_kb * ||a_i||^2) is not above min_visible (0 <= min_visible < 1) is no candidate; a signal whose weights are all
         zero has none.  W: (B, m) or the shared (m,), finite and >= 0.  Everything else as for top_correlations."""
-        if records is None:
-            Yp, B, ys, incy = self._signals(Y)
-            rp, kmax = None, 0
-            if not B:
-                ys, incy = self.m, 1
-        else:
-            if kmax is None:
-                raise ValueError("kmax must be given with records")
-            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        Yp, B, ys, incy, rp, kmax = self._topcorr_signals(Y, records, kmax)
         Wp, wst = self._weights(W, B)
         min_visible = float(min_visible)
         if not 0.0 <= min_visible < 1.0:
             raise ValueError("min_visible must lie in [0, 1)")
         k = int(k)
-        dev = _device_of(Y)
-        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
-        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
-        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
-        _sync_producers(Y, records, idx)
+        outs, ptrs = self._topcorr_outputs(Y, records, B, B, k, coef, score)
         _sync_producers(W)
-        _call(self._fn("ss_hip_weighted_top_correlations_"), self._h, Yp, B, ys, incy, Wp, wst, rp, int(kmax), min_visible, k, ip, cp, sp)
-        return idx, cf, sc
+        _call(self._fn("ss_hip_weighted_top_correlations_"), self._h, Yp, B, ys, incy, Wp, wst, rp, kmax, min_visible, k, *ptrs)
+        return outs
 
     def weighted_refit_records(self, Y, W, records, kmax, out=None, residuals=True):
         """The weighted refit (include/ss_hip.h, ss_hip_weighted_refit_records_*): refit_records under the weights W — every
@@ -892,23 +890,11 @@ class Homotopy(_Context):
         with a_i . r_b > 0 alone, ranked by a_i . r_b / ||a_i|| -> (idx (B, k), coef (B, k) or None, score (B, k) float64 or
         None).  Every coef is positive; a signal with fewer than k such columns is padded with TOPCORR_NONE / 0.  Everything
         else as for top_correlations, whose entries with coef > 0 these are, word for word."""
-        if records is None:
-            Yp, B, ys, incy = self._signals(Y)
-            rp, kmax = None, 0
-            if not B:
-                ys, incy = self.m, 1
-        else:
-            if kmax is None:
-                raise ValueError("kmax must be given with records")
-            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        Yp, B, ys, incy, rp, kmax = self._topcorr_signals(Y, records, kmax)
         k = int(k)
-        dev = _device_of(Y)
-        idx, ip = _alloc(dev, (B, k), np.uint32, self.TOPCORR_NONE)
-        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
-        sc, sp = _alloc(dev, (B, k) if score else None, np.float64, 0.0)
-        _sync_producers(Y, records, idx)
-        _call(self._fn("ss_hip_nonneg_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), k, ip, cp, sp)
-        return idx, cf, sc
+        outs, ptrs = self._topcorr_outputs(Y, records, B, B, k, coef, score)
+        _call(self._fn("ss_hip_nonneg_top_correlations_"), self._h, Yp, B, ys, incy, rp, kmax, k, *ptrs)
+        return outs
 
     def nonneg_refit_records(self, Y, records, kmax, out=None, residuals=True):
         """The non-negative refit (include/ss_hip.h, ss_hip_nonneg_refit_records_*): every record's values replaced by
@@ -981,25 +967,13 @@ class Homotopy(_Context):
         integer L for equal groups (B a multiple of L), else the (Gn + 1,) offsets; a group holds at most GROUP_MAX signals.
         records, kmax, the entries behind the last candidate, the dtypes and where the outputs live: as for top_correlations.
         A group of one returns top_correlations' words."""
-        if records is None:
-            Yp, B, ys, incy = self._signals(Y)
-            rp, kmax = None, 0
-            if not B:
-                ys, incy = self.m, 1
-        else:
-            if kmax is None:
-                raise ValueError("kmax must be given with records")
-            Yp, B, ys, incy, rp = self._signals_with_records(Y, records, kmax, contiguous_if_empty=True)
+        Yp, B, ys, incy, rp, kmax = self._topcorr_signals(Y, records, kmax)
         gp, Gn, keepg, _ = self._groups(groups, B)
         k = int(k)
-        dev = _device_of(Y)
-        idx, ip = _alloc(dev, (Gn, k), np.uint32, self.TOPCORR_NONE)
-        cf, cp = _alloc(dev, (B, k) if coef else None, self.dtype, 0.0)
-        sc, sp = _alloc(dev, (Gn, k) if score else None, np.float64, 0.0)
-        _sync_producers(Y, records, idx)
+        outs, ptrs = self._topcorr_outputs(Y, records, B, Gn, k, coef, score)
         _sync_producers(groups)
-        _call(self._fn("ss_hip_group_top_correlations_"), self._h, Yp, B, ys, incy, rp, int(kmax), gp, Gn, k, ip, cp, sp)
-        return idx, cf, sc
+        _call(self._fn("ss_hip_group_top_correlations_"), self._h, Yp, B, ys, incy, rp, kmax, gp, Gn, k, *ptrs)
+        return outs
 
     def group_class_residuals(self, Y, records, kmax, groups, residuals=True):
         """The group class residuals (include/ss_hip.h, ss_hip_group_class_residuals_*) -> (best (Gn,), Rg (Gn, num_classes) or

@@ -87,12 +87,16 @@ def test_the_unit_is_registered_with_separately_rounded_sums_and_shares_the_sele
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "build.py")).read()
     assert re.search(r'\("joint\.hip",\s*\[[^\]]*"-ffp-contract=off"', src)
     csrc = os.path.join(ROOT, "sparse-solvers_amd", "csrc")
-    joint, top = open(os.path.join(csrc, "joint.hip")).read(), open(os.path.join(csrc, "topcorr.hip")).read()
-    # one selection, stated in the shared header and called by both kernels; the MFMA main loop is not stated a third time
-    assert "tc_select_sorted(" in joint and "tc_select_sorted(" in top
+    code = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())       # (comments may name what the code must not)
+    joint, top, drv, sel = (code(f) for f in ("joint.hip", "topcorr.hip", "tc_driver.h", "tc_select.h"))
+    # one selection, stated in the shared header and called by the group kernel and the per-signal kernel alone; the MFMA main loop
+    # is not stated a third time; the driver and its launches are the shared ones
+    assert joint.count("tc_select_sorted(") == 1 and sel.count("tc_select_sorted(") == 2 and "tc_select_sorted(" not in top
     assert "__builtin_amdgcn_mfma" not in joint
-    for launcher in ("tc_launch_record_check", "tc_launch_residual_block", "tc_launch_dots"):
-        assert launcher in joint and launcher in top
+    assert '#include "tc_driver.h"' in joint and "tc_drive<" in joint
+    for launcher in ("tc_launch_record_check", "tc_launch_residual_block"):
+        assert launcher not in joint and launcher in drv and launcher in top
+    assert "tc_launch_dots" in joint and "tc_launch_dots" in top
 
 
 # ---- the words each method passes: sship._lib is a stub that records every call and returns 0 ---------------------------------------

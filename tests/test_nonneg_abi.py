@@ -105,12 +105,16 @@ def test_the_unit_is_registered_with_separately_rounded_sums_and_shares_the_kern
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "build.py")).read()
     assert re.search(r'\("nonneg\.hip",\s*\[[^\]]*"-ffp-contract=off"', src)
     csrc = os.path.join(ROOT, "sparse-solvers_amd", "csrc")
-    nn, top, rf = (open(os.path.join(csrc, f)).read() for f in ("nonneg.hip", "topcorr.hip", "refit.hip"))
-    # one selection and one tile kernel: no product kernel and no second main loop in the new unit
-    assert "tc_select_sorted(" in nn and "__builtin_amdgcn_mfma" not in nn
+    code = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())       # (comments may name what the code must not)
+    nn, top, rf, drv, sel = (code(f) for f in ("nonneg.hip", "topcorr.hip", "refit.hip", "tc_driver.h", "tc_select.h"))
+    # the unit supplies a scorer and nothing else of the selection: no kernel, no launch, no product and no main loop of its own;
+    # the selection kernel, the driver and its launches are the shared ones, stated in the headers and in topcorr.hip
+    assert "__global__" not in nn and "hipLaunchKernelGGL" not in nn and "__builtin_amdgcn_mfma" not in nn
+    assert "tc_select_sorted(" not in nn and "tc_select_sorted(" in sel and "void k_tc_select(" in sel
+    assert '#include "tc_driver.h"' in nn and "tc_dots_entry<" in nn and "NnScorer" in nn
     for launcher in ("tc_launch_record_check", "tc_launch_residual_block", "tc_launch_dots"):
-        assert launcher in nn and launcher in top
-    assert "coh_launch_norms" in nn and "tc_launch_weight_dots" not in nn
+        assert launcher not in nn and launcher in drv and launcher in top
+    assert "coh_launch_norms" in drv and "coh_launch_norms" not in nn and "tc_launch_weight_dots" not in nn
     # the refit is refit.hip's unit with a flag: its Gram kernel, a new solve kernel
     assert "refit_nonneg<" in nn and "k_rf_nnls" in rf and "k_rf_gram" not in nn.split("#include")[-1]
     # the coder's loop is stated once

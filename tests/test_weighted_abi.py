@@ -101,11 +101,18 @@ def test_the_unit_is_registered_with_separately_rounded_sums_and_shares_the_kern
     src = open(os.path.join(ROOT, "sparse-solvers_amd", "build.py")).read()
     assert re.search(r'\("weighted\.hip",\s*\[[^\]]*"-ffp-contract=off"', src)
     csrc = os.path.join(ROOT, "sparse-solvers_amd", "csrc")
-    wt, top = open(os.path.join(csrc, "weighted.hip")).read(), open(os.path.join(csrc, "topcorr.hip")).read()
-    # one selection and one tile kernel: the second product is topcorr.hip's tile with its squaring flag, not a third main loop
-    assert "tc_select_sorted(" in wt and "__builtin_amdgcn_mfma" not in wt
-    for launcher in ("tc_launch_residual_block", "tc_launch_dots", "tc_launch_weight_dots"):
+    code = lambda f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read())       # (comments may name what the code must not)
+    wt, top, drv, sel, coh = (code(f) for f in ("weighted.hip", "topcorr.hip", "tc_driver.h", "tc_select.h", "coherence.hip"))
+    # one selection and one tile kernel: the second product is topcorr.hip's tile with its squaring flag, not a third main loop;
+    # the selection kernel and the driver are the shared ones, the unit supplies a scorer and what runs on a chunk
+    assert "tc_select_sorted(" not in wt and "tc_select_sorted(" in sel and "void k_tc_select(" in sel
+    assert "__builtin_amdgcn_mfma" not in wt
+    assert '#include "tc_driver.h"' in wt and "tc_drive<" in wt and "tc_launch_select(" in wt and "WtScorer" in wt
+    for launcher in ("tc_launch_dots", "tc_launch_weight_dots"):
         assert launcher in wt and launcher in top
+    assert "tc_launch_residual_block" not in wt and "tc_launch_residual_block" in drv and "tc_launch_residual_block" in top
+    # the norms are coherence.hip's kernel with its flag, not a copy
+    assert "coh_launch_norms<T, true>" in wt and "coh_launch_norms<float, true>" in coh and wt.count("wave_sum(") == 0
     # the coder's loop is stated once
     py = open(os.path.join(ROOT, "sparse-solvers_amd", "python", "sship.py")).read()
     assert py.count("frozen = frozen | (live & ~good)") == 1
