@@ -312,6 +312,11 @@ int ss_hip_homotopy_classify_batch_f64(ss_hip_ctx* ctx, const double* Y, size_t 
  * CONTRACT: an atom's column of V and its usage are a function of the records, Y, A and the atom alone — bit for bit the same
  * whatever else was requested, with host or device pointers, whatever the context did before.  Every sum runs in one documented
  * order (csrc/dictlearn.hip): no floating-point atomics, no dependence on B, on the internal chunking or on the launch geometry.
+ * RANGE: the call has no absolute constant, so a change of units by powers of two (A 2^a, Y 2^b, record values 2^(b-a)) returns the
+ * same atoms and usage and the objective times 2^2b, word for word — as long as its intermediates stay normal numbers: sum w_b^2
+ * (size 2^(2b-2a)), (sum w_b^2) a_ij and w_b r_b,i (2^(2b-a)) in T, ||g_j||^2 (2^(4b-2a)) and ||r_b||^2 (2^2b) in double.  Outside
+ * that range a sum rounds as a subnormal (the atom differs in its last bits) or ||g_j||^2 is 0 or infinite (the atom is left as it
+ * is, bit 31 of usage); nothing else goes wrong.  tests/test_gpu_scaling.py holds the call to this.
  * Validation happens before anything is written: a failing call leaves the context and the outputs untouched.
  *   SS_HIP_EINVAL  null ctx, Y or records; V null with apply == 0; an IRLS or a column-sharded context; kmax outside 1..4096;
  *                  records not 8-byte aligned; a non-positive incy, y_stride (for every B, B == 1 included), stride_row or
@@ -372,6 +377,9 @@ int ss_hip_homotopy_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
  * geometry.  The columns of V, the usage and the record values of the first S' atoms of cols are those of a call with
  * cols[0 .. S').  For an atom that no earlier atom of cols shares a signal with, the column of V and usage are
  * ss_hip_homotopy_atom_update_*'s words.  No floating-point atomics.  No call changes what any solve returns.
+ * RANGE: as for ss_hip_homotopy_atom_update_* — under A 2^a, Y 2^b, record values 2^(b-a) the atoms and usage are the same words, the
+ * output values (coefficients of unit atoms) the unscaled ones times 2^b and both objectives times 2^2b, as long as sigma (2^(2b-2a)),
+ * sigma a_ij and w_b r_b,i (2^(2b-a)) stay normal numbers of T and ||g||^2 (2^(4b-2a)) of double.
  * Validation happens before anything is written: a failing call leaves the context and every output untouched.
  *   SS_HIP_EINVAL  null ctx, Y, records or records_out; V null without SS_HIP_KSVD_APPLY and usage and objective both null (nothing
  *                  asked for); an IRLS or a column-sharded context; kmax outside 1..4096; records or records_out not 8-byte

@@ -41,6 +41,11 @@
 //   objective  = those ||r_b||^2 one after the other in ascending b (a truncated record adds +0);
 //   v_j,i      = g_j,i / (T) sqrt(||g_j||^2); the atom is left as it is when that divisor is zero or not finite.
 // No floating-point atomics; nothing depends on B, on the chunking, on the launch geometry or on which other atoms were requested.
+// RANGE: no step has an absolute constant, so the words are an exact function of the units (A 2^a, Y 2^b, record values 2^(b-a): the
+// same v_j and usage, the objective times 2^2b) as long as every intermediate is a normal number of its type: sum w^2 (of size
+// 2^(2b-2a)) after its rounding to the context's precision, (sum w^2) a_ij and w_b r_b,i (2^(2b-a)) in the context's precision,
+// ||g_j||^2 (2^(4b-2a)) and ||r_b||^2 (2^2b) in double.  Below it a sum rounds as a subnormal, above it ||g_j||^2 is infinite and the
+// atom is left as it is (include/ss_hip.h states the same range; tests/test_gpu_scaling.py holds the kernels to it).
 #include "ss_hip_internal.h"
 #include "record_common.h"
 

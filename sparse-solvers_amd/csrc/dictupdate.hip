@@ -105,6 +105,11 @@ void k_du_scales(const float* __restrict__ amaxc, const float* __restrict__ anor
     uint32_t* mw = reinterpret_cast<uint32_t*>(meta);
     mw[2] = ma;
     mw[4] = mn;
+    if (meta[14] != 0.f) {                  // (k_a16_scale: the units of an fp64 dictionary's columns follow max ||a_i||)
+        const int u = dict_unit_exp(__uint_as_float(mn));
+        meta[12] = ldexpf(1.f, -u);
+        meta[13] = ldexpf(1.f, u);
+    }
     const float amax = __uint_as_float(ma);
     const int e16 = pow2_scale_exp(16384.f, amax);
     const float s16 = ldexpf(1.f, e16);

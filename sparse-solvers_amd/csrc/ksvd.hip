@@ -40,6 +40,9 @@
 //   objective[0], objective[1] = the ||r_b||^2 of the initial / final residuals one after the other in ascending b (truncated: +0).
 // No floating-point atomics.  The outputs are a function of (records, Y, A, cols as an ordered list) alone: the same words with or
 // without SS_HIP_KSVD_SERIAL, with host or device pointers, in place or out of place, whatever the context did before.
+// RANGE: dictlearn.hip's — under A 2^a, Y 2^b, record values 2^(b-a) the atoms and usage are the same words, the output values those
+// of the unscaled call times 2^b (the coefficients of unit atoms), the objectives times 2^2b, as long as sum w^2 (2^(2b-2a)),
+// (sum w^2) a_ij and w_b r_b,i (2^(2b-a)) are normal numbers of the context's precision and ||g||^2 (2^(4b-2a)) of double.
 #include "ss_hip_internal.h"
 #include "record_common.h"
 #include "ks_levels.h"

@@ -991,6 +991,8 @@ void k_res_residuals64(const double* __restrict__ At, uint32_t ldm, uint32_t n, 
             }
         }
     }
+    // (the residuals in the units of the dictionary's columns, meta[13] = 2^u: screen.hip, k_s64_residuals)
+    const double units = (double)meta[13];
     bool ovf = false;
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) {
@@ -1002,7 +1004,7 @@ void k_res_residuals64(const double* __restrict__ At, uint32_t ldm, uint32_t n, 
             __half hv[4];
 #pragma unroll
             for (int ri = 0; ri < 4; ++ri) {
-                const float r = (float)acc[rd][si][ri];
+                const float r = (float)(acc[rd][si][ri] * units);          // (2^u r: exact)
                 ss = __builtin_fmaf(r, r, ss);
                 const float v = r * sc;
                 if (kk < nst && !(fabsf(v) < 60000.f)) ovf = true;
@@ -1048,7 +1050,7 @@ void k_res_residuals64(const double* __restrict__ At, uint32_t ldm, uint32_t n, 
                 if (scan && (irregular || final_state)) bound = 3.0e38f;
             }
             const float inv_sk = 1.f / sS[tid];
-            tab[tid * 4u + 0] = meta[1] * inv_sk;
+            tab[tid * 4u + 0] = (meta[1] * meta[12]) * inv_sk;          // (r16 = fl16(s_k 2^u r_k))
             tab[tid * 4u + 1] = bound;
             tab[tid * 4u + 2] = inv_sk;
             tab[tid * 4u + 3] = lam;

@@ -99,6 +99,8 @@ struct ScreenState {
     float* amaxc = nullptr;      // [n_pad] max |a_i| per column: what meta[2] is the maximum of (a column replaced later re-derives it, dictupdate.hip)
     float* meta = nullptr;       // [0] sA  [1] 1 / sA  [2] bits(max |A|)  [3] headroom of the last solve (bits, as uint)
                                  // [4] max ||a_i||  [5] ||y||^2 (k_scr_first)  [6] what the columns left out of the subset stay below (selection)
+                                 // [12] 2^-u  [13] 2^u, u = dict_unit_exp([4]): the units of an fp64 dictionary's columns (1, 1 in an fp32
+                                 // context)  [14] 1 where [12], [13] follow [4] (fp64), 0 where they stay 1
     __half* r16 = nullptr;       // [kScrRhs][ldm] fl16(s_k * r_k)
     float* rn2p = nullptr;       // [ldm / 64][kScrRhs] partial sums of ||r_k||^2, one per workgroup of k_scr_residuals
     float* tab = nullptr;        // [kScrRhs][kScrTab]
@@ -178,12 +180,17 @@ void k_a16_stats(const T* __restrict__ At, uint32_t ldm, float* __restrict__ ano
     }
 }
 
-__global__ void k_a16_scale(float* __restrict__ meta)
+__global__ void k_a16_scale(float* __restrict__ meta, int units)
 {
     const float amax = __uint_as_float(reinterpret_cast<const uint32_t*>(meta)[2]);
     const int e = pow2_scale_exp(16384.f, amax);
     meta[0] = ldexpf(1.f, e);
     meta[1] = ldexpf(1.f, -e);
+    // units (the fp64 forms): residuals and column norms of the certificate in the units of the dictionary's largest column norm
+    const int u = units ? dict_unit_exp(meta[4]) : 0;
+    meta[12] = ldexpf(1.f, -u);
+    meta[13] = ldexpf(1.f, u);
+    meta[14] = units ? 1.f : 0.f;
 }
 
 template <typename T>
@@ -861,7 +868,8 @@ void k_scr_gemm(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, const 
     float* sT = reinterpret_cast<float*>(smem);                 // [32 NT][4]: 1/(sA s_k), bound, eps factor 1 (x ||a||), eps term 2
     uint32_t* sSub = reinterpret_cast<uint32_t*>(smem) + (uint32_t)RH * 4u;   // [nsub] the subset's columns, ascending (0xffffffff: none)
     float* sPart = reinterpret_cast<float*>(smem) + (uint32_t)RH * 4u + nsub; // [PB][32 NT] partial sums of ||r_k||^2
-    const float inv_sA = meta[1];
+    // (meta[12] = 2^-u, 1 in an fp32 context: rn2p and the table are in the units of 2^-u A — k_s64_residuals, k_res_residuals64)
+    const float inv_sA = meta[1] * meta[12];
     const float sq_ldm = sqrtf((float)ldm);
     const uint32_t nblk = ldm / 64u;
     // (128 workgroups' partials in flight at once, summed per state in the order of the workgroups that wrote them: deterministic)
@@ -893,7 +901,7 @@ void k_scr_gemm(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, const 
     uint32_t lo = 0, hi = nsub;
     while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (sSub[mid] < col) lo = mid + 1u; else hi = mid; }
     const bool mine = col < n && !(lo < nsub && sSub[lo] == col);
-    const float an = anorm[col < n ? col : 0u];
+    const float an = anorm[col < n ? col : 0u] * meta[12];
     bool flag = false;
     float worst = 0.f, big = 0.f;
 #pragma unroll
@@ -1491,6 +1499,9 @@ void k_s64_residuals(const double* __restrict__ Asub, uint32_t ldm, const double
             }
         }
     }
+    // the residuals in the units of the dictionary's columns (meta[13] = 2^u: r_k of the dictionary 2^-u A, whose columns are of
+    // ordinary size, is 2^u r_k): s_k is chosen from lambda_k for such columns, and ||r_k||^2 stays inside float
+    const double units = (double)meta[13];
     bool ovf = false;
 #pragma unroll
     for (int rd = 0; rd < 3; ++rd) {
@@ -1502,7 +1513,7 @@ void k_s64_residuals(const double* __restrict__ Asub, uint32_t ldm, const double
             __half hv[4];
 #pragma unroll
             for (int ri = 0; ri < 4; ++ri) {
-                const float r = (float)acc[rd][si][ri];
+                const float r = (float)(acc[rd][si][ri] * units);          // (2^u r: exact)
                 ss = __builtin_fmaf(r, r, ss);
                 const float v = r * sc;
                 if (kk < nst && !(fabsf(v) < 60000.f)) ovf = true;
@@ -1542,7 +1553,7 @@ void k_s64_residuals(const double* __restrict__ Asub, uint32_t ldm, const double
             if (ls_jump) bound = (float)tol * 0.9375f - slack;
             else bound = fminf(lam, (float)l_exp[tid + 1u]) * 0.875f - slack;
             const float inv_sk = 1.f / sS[tid];
-            tab[tid * kScrTab + 0] = meta[1] * inv_sk;
+            tab[tid * kScrTab + 0] = (meta[1] * meta[12]) * inv_sk;     // (r16 = fl16(s_k 2^u r_k))
             tab[tid * kScrTab + 1] = bound;
             tab[tid * kScrTab + 2] = inv_sk;
             tab[tid * kScrTab + 3] = lam;
@@ -1679,7 +1690,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), s);
     (void)hipMemsetAsync(S->r16, 0, (size_t)kScrRhs * ldm * sizeof(__half), s);
     hipLaunchKernelGGL((k_a16_stats<float>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
-    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta);
+    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta, 0);
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<float>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
                        (const float*)S->meta, S->a16);
@@ -2035,7 +2046,7 @@ bool screen64_usable(ss_hip_ctx* ctx)
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
     (void)hipMemsetAsync(S->r16, 0, (size_t)kS64Rhs * ldm * sizeof(__half), s);
     hipLaunchKernelGGL((k_a16_stats<double>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
-    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta);
+    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta, 1);
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<double>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
                        (const float*)S->meta, S->a16);

@@ -173,6 +173,20 @@ __device__ __forceinline__ int pow2_scale_exp(float target, float amax)
     return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
 
+// Exponent u of the units of a dictionary whose largest column norm is max_norm (a float): 0 while that norm lies in [2^-8, 2^8) —
+// every dictionary of unit-norm or randn / sqrt(m) columns — and for an all-zero or non-finite one; otherwise floor(log2(max_norm)),
+// within +-100.  The fp64 screened forms form their half-precision residuals and ||r_k||^2 from 2^u r_k and take the column norms as
+// 2^-u ||a_i||: the certificate's products are those of the dictionary 2^-u A, whose columns are of ordinary size (screen.hip: meta[12 .. 14])
+__device__ __forceinline__ int dict_unit_exp(float max_norm)
+{
+    if (!(max_norm > 0.f && max_norm < 3.0e38f)) return 0;
+    int e;
+    (void)frexpf(max_norm, &e);                                 // max_norm in [2^(e-1), 2^e)
+    e -= 1;
+    if (e >= -8 && e < 8) return 0;
+    return e < -100 ? -100 : (e > 100 ? 100 : e);
+}
+
 // Sum over the wave, the same value in every lane.  Fixed association: butterfly inside each row
 // of 16 lanes (1, 2, 4, 8 apart), then ((row0 + row1) + row2) + row3.
 template <typename T>
