@@ -1904,9 +1904,13 @@ __global__ __launch_bounds__(kSmallThreads)
 void k_la_reset(T* __restrict__ x, T* __restrict__ d, uint8_t* __restrict__ insup, int32_t* __restrict__ slot_of,
                 uint32_t n_pad, uint32_t* __restrict__ la_sync, uint32_t sync_head_words, uint32_t sync_words,
                 uint32_t* __restrict__ st_words, uint32_t st_nwords, uint32_t* __restrict__ ndone,
-                T* __restrict__ y, T* __restrict__ rhs, uint32_t ldm, const T* __restrict__ y_user, long long incy, uint32_t m)
+                T* __restrict__ y, T* __restrict__ rhs, uint32_t ldm, const T* __restrict__ y_user, long long incy, uint32_t m,
+                uint32_t* __restrict__ handoff, uint32_t handoff_words)
 {
+    // (handoff: the tickets and the shared histogram of the screened form's in-launch hand-offs, if the context has them — cleared for
+    // every attempt, whatever the last one left)
     const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
+    for (uint32_t i = gtid; i < handoff_words; i += gsz) handoff[i] = 0u;
     for (uint32_t i = gtid; i < n_pad; i += gsz) {
         x[i] = T(0); d[i] = T(0); insup[i] = 0;
         if (slot_of != nullptr) slot_of[i] = -1;
@@ -1929,7 +1933,8 @@ hipError_t launch_la_reset(const ss_hip_ctx* ctx, Workspace<T>& ws, bool clear_s
     hipLaunchKernelGGL((k_la_reset<T>), dim3(grid), dim3(kSmallThreads), 0, ctx->stream, ws.x, ws.d, ws.insup,
                        clear_slots ? ws.slot_of : (int32_t*)nullptr, ctx->n_pad, reinterpret_cast<uint32_t*>(ws.la_sync),
                        (uint32_t)(sizeof(LaSync) / 4), (uint32_t)(kLaSyncBytes / 4), reinterpret_cast<uint32_t*>(ws.st),
-                       (uint32_t)(sizeof(DevState) / 4), ws.ndone, ws.y, ws.rhs, ctx->ldm, y_user, (long long)incy, (uint32_t)ctx->m);
+                       (uint32_t)(sizeof(DevState) / 4), ws.ndone, ws.y, ws.rhs, ctx->ldm, y_user, (long long)incy, (uint32_t)ctx->m,
+                       static_cast<uint32_t*>(ctx->handoff), ctx->handoff != nullptr ? kHoZeroWords : 0u);
     return hipGetLastError();
 }
 template hipError_t launch_la_reset<float>(const ss_hip_ctx*, Workspace<float>&, bool, const float*, ptrdiff_t);

@@ -886,15 +886,18 @@ void first_sweep(ss_hip_ctx* ctx, Workspace<T>& ws, T* out, ProfSpans& spans, ui
 
 // one signal in the screened form (screen.hip): no G — the subset's own Gram matrix from A, then one pass over the fp16 copy of A
 inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, EventPair first, EventPair screen, EventPair path,
-                             bool omp, bool rescue)
+                             bool omp, bool rescue, ScrHandoff* ho)
 {
     grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
+    // (developer switch, read per solve: which hand-offs inside launches the form may use — 1 = the one-launch tail, 2 = the selection by
+    // many workgroups; unset = all, 0 = the launches before them)
+    if (const char* e = std::getenv("SS_HIP_SCR_HANDOFF")) ho->mask = (uint32_t)std::strtoul(e, nullptr, 0);
     if (ctx->sub_dbg == nullptr && std::getenv("SS_HIP_SUB_STAMPS")) {
         HIPCHK(hipMalloc(&ctx->sub_dbg, 16 * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(ctx->sub_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
     }
     // (with the state mirrored to mapped host memory the epilogue launch applies the certificate's verdict: no k_sub_finish)
-    return launch_screen_form(ctx, ws, tol, max_iter, first16, ctx->hs_mapped == nullptr, first, screen, path, omp, rescue);
+    return launch_screen_form(ctx, ws, tol, max_iter, first16, ctx->hs_mapped == nullptr, first, screen, path, omp, rescue, ho);
 }
 
 // why a subset / screened solve was not reported: DevState::sub_reason's bits into the statistics
@@ -1278,6 +1281,9 @@ int attempt_verdict(ss_hip_ctx* ctx, const Route& route, const Forms& f, const D
     if ((scr1 || scr64) && hs.status == 0) ctx->stats.screen_signals += 1;
     if (scr1 && hs.status == 0 && ctx->screen_resident && res_solve_usable<float>()) ctx->stats.screen_resident += 1;
     if ((scr1 || scr64r) && hs.status == 0 && (hs.sub_reason & kReasonRechecked)) ctx->stats.screen_recheck += 1;
+    if ((scr1 || scr64r) && hs.status == 0 && (hs.sub_reason & kReasonRechecked) && std::getenv("SS_HIP_SUB_DEBUG"))
+        std::fprintf(stderr, "[screened form] certified by the exact re-check%s (reason 0x%x)\n",
+                     (hs.sub_reason & kReasonRepaired) ? ", last step repaired" : "", hs.sub_reason);
     if (scr1 && ctx->sub_dbg != nullptr) {
         unsigned long long tp[9];
         HIPCHK(hipMemcpy(tp, ctx->sub_dbg, sizeof(tp), hipMemcpyDeviceToHost));
@@ -1434,8 +1440,12 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
         // end of a solve: the device state to pinned memory, x (and the compact record) to the caller
         bool spec_epilogue = false;
         const bool x_on_device = x != nullptr && on_device(x);
+        // (the screened fp32 form's last launch may do k_epilogue's work: scr_single hears where x goes and says whether it did)
+        ScrHandoff scr_ho;
         auto enqueue_epilogue = [&]() {
-            if (ctx->hs_mapped != nullptr) {
+            if (ctx->hs_mapped != nullptr && scr_ho.tail_fused) {
+                if (x && !x_on_device) copy_out<T>(ctx, x, incx, ws.x, n);
+            } else if (ctx->hs_mapped != nullptr) {
                 // one launch: state -> pinned memory, x -> the caller's device buffer (a host x still takes a copy command)
                 const uint32_t grid = x_on_device ? std::min<uint32_t>(((uint32_t)n + 1023u) / 1024u, 256u) : 1u;
                 hipLaunchKernelGGL((k_epilogue<T>), dim3(std::max(1u, grid)), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(ws.st),
@@ -1502,7 +1512,10 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
                 const EventPair first = (first16 && !rescue) ? spans.span(ProfKind::FirstReduced) : EventPair{};
                 const EventPair screen = spans.span(ProfKind::Screen), path = spans.span(ProfKind::PathKernel);
                 if constexpr (sizeof(T) == 8) HIPCHK(launch_screen64_resident(ctx, ws, tol, max_iter, first16, omp, first, screen, path, rescue));
-                else HIPCHK(scr_single(ctx, ws, tol, max_iter, first16, first, screen, path, omp, rescue));
+                else {
+                    if (x_on_device) { scr_ho.x_dst = reinterpret_cast<float*>(x); scr_ho.incx = (long long)incx; }
+                    HIPCHK(scr_single(ctx, ws, tol, max_iter, first16, first, screen, path, omp, rescue, &scr_ho));
+                }
             }
         } else if (f.scr64) {
             if constexpr (sizeof(T) == 8) {

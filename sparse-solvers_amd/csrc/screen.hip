@@ -992,11 +992,13 @@ void k_scr_rescue_rank(const float* __restrict__ c0h, const uint32_t* __restrict
 // smallest one.
 template <typename T> struct ScrOrd;
 template <> struct ScrOrd<float>  { static __device__ __forceinline__ unsigned long long pack(float m, uint32_t col) { return ((unsigned long long)__float_as_uint(m) << 32) | col; } };
+// (the body of a workgroup, behind the launch's "is the signal still clean" test: k_scr_recheck, and k_scr_tail's first part.  fl and st
+// are written by other workgroups of the same launch — no __restrict__ on them: nothing of theirs may travel the scalar path)
 template <typename T>
-__global__ __launch_bounds__(256)
-void k_scr_recheck(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
-                   const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, uint32_t* __restrict__ fl,
-                   T tol, int tie_guard, DevState* __restrict__ st)
+__device__ __forceinline__
+void scr_recheck_wg(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
+                    const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, uint32_t* fl,
+                    T tol, int tie_guard, DevState* st)
 {
     constexpr uint32_t PCAP = ResCfg<T>::PCAP, LOGCAP = ResCfg<T>::LOGCAP;
     constexpr uint32_t VE = 16u / sizeof(T);                          // elements per 16-byte load
@@ -1004,7 +1006,6 @@ void k_scr_recheck(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* 
     __shared__ uint32_t sH[LOGCAP * 8];
     __shared__ T sL[LOGCAP * 2];                                   // lambda, step of every state
     __shared__ T sG[PCAP + 1];                                     // g_p of the column in hand; [PCAP] = its c0
-    if (st->status != 0u || st->need_sweep != 0u) return;
     const uint32_t nfl = fl[0];
     if (nfl == 0u) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -1118,24 +1119,35 @@ void k_scr_recheck(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* 
     }
     if (tie) __hip_atomic_store(&st->tie_stall, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_scr_recheck(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
+                   const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, uint32_t* __restrict__ fl,
+                   T tol, int tie_guard, DevState* __restrict__ st)
+{
+    if (st->status != 0u || st->need_sweep != 0u) return;
+    scr_recheck_wg<T>(At, ldm, n, y, hdr, LH, pcol, LX, LD, fl, tol, tie_guard, st);
+}
 
 // ---- the last step again, with the smallest candidate the re-check found (see k_scr_recheck) -----------------------------------
 // x = x_{K-1} + m d_{K-1} over the positions of the last scan state (homotopy-cpu.cpp:252), lambda = lambda_{K-1} - m, the column that
 // stops the step in the lists and the trace instead of the subset's pick (either enters with x = 0: the coefficients do not see it).
 // The winner's step is formed again here from its exact c and q (one workgroup: its Gram values with the positions, the chain).
+// (scr_repair_wg: the workgroup's body behind the "still clean" test — k_scr_repair, and the last arriver of k_scr_tail, where the
+// candidates were posted by other workgroups of the same launch: they are read with agent-scope atomic loads, never on the scalar path)
 template <typename T>
-__global__ __launch_bounds__(256)
-void k_scr_repair(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
-                  const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, const uint32_t* __restrict__ fl, T* __restrict__ x,
-                  uint32_t* __restrict__ gam, uint32_t* __restrict__ tch, DevState* __restrict__ st, TraceEntry* trace, uint32_t trace_cap)
+__device__ __forceinline__
+void scr_repair_wg(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
+                   const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, const uint32_t* fl, T* x,
+                   uint32_t* gam, uint32_t* tch, DevState* st, TraceEntry* trace, uint32_t trace_cap)
 {
     constexpr uint32_t PCAP = ResCfg<T>::PCAP;
     constexpr uint32_t VE = 16u / sizeof(T);
     typedef T vec_t __attribute__((ext_vector_type(16 / sizeof(T))));
     __shared__ T sG[PCAP + 1];
     __shared__ T s_m;
-    if (st->status != 0u || st->need_sweep != 0u) return;
-    const uint32_t ncand = fl[kScrFlCap + 12u];
+    auto ld = [](const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    const uint32_t ncand = ld(&fl[kScrFlCap + 12u]);
     if (ncand == 0u) return;
     const uint32_t nlog = st->solo_nlog;
     if (nlog < 2u || ncand > kScrRepCap) return;                     // (an overflowing list failed the signal in k_scr_recheck)
@@ -1145,8 +1157,9 @@ void k_scr_repair(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* _
         double bm = 1.0e300;
         for (uint32_t i = 0; i < ncand; ++i) {                        // (uniform: every thread walks the short list)
             const uint32_t* ent = fl + kScrFlCap + 16u + 4u * i;
-            const double mi = *reinterpret_cast<const double*>(ent + 2);
-            if (mi < bm || (mi == bm && ent[0] < col)) { bm = mi; col = ent[0]; }
+            const uint32_t ecol = ld(ent);
+            const double mi = __longlong_as_double((long long)(((unsigned long long)ld(ent + 3) << 32) | ld(ent + 2)));
+            if (mi < bm || (mi == bm && ecol < col)) { bm = mi; col = ecol; }
         }
     }
     const uint32_t Pk = hdr[ks * 8u], old_pick = hdr[ks * 8u + 2u];
@@ -1199,6 +1212,72 @@ void k_scr_repair(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* _
             L[pos] = col;
         }
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_scr_repair(const T* __restrict__ At, uint32_t ldm, uint32_t n, const T* __restrict__ y, const uint32_t* __restrict__ hdr, const T* __restrict__ LH,
+                  const uint32_t* __restrict__ pcol, const T* __restrict__ LX, const T* __restrict__ LD, const uint32_t* __restrict__ fl, T* __restrict__ x,
+                  uint32_t* __restrict__ gam, uint32_t* __restrict__ tch, DevState* __restrict__ st, TraceEntry* trace, uint32_t trace_cap)
+{
+    if (st->status != 0u || st->need_sweep != 0u) return;
+    scr_repair_wg<T>(At, ldm, n, y, hdr, LH, pcol, LX, LD, fl, x, gam, tch, st, trace, trace_cap);
+}
+
+// ---- the tail of one screened fp32 solve in ONE launch: exact re-check, repair, verdict, state and x to the caller ------------------
+// k_scr_recheck, k_scr_repair and k_epilogue (homotopy.hip) are three launches whose work is empty on a certified signal: two launch
+// boundaries for nothing.  Here the kScrRecheckWgs workgroups take their share of the re-check (scr_recheck_wg: the same statements)
+// and draw a ticket (arrive_last); the last arriver repairs (scr_repair_wg), applies the certificate's verdict and mirrors DevState to
+// the mapped host block exactly as k_epilogue does.  The caller's device x receives the coefficients only of a certified path, as
+// there: with nothing listed for the re-check (the common case) the verdict is final when the launch starts — every workgroup copies
+// its share, workgroup 0 mirrors the state, and no ticket is drawn: the launch is k_epilogue's; with columns listed (noisy signals)
+// the verdict is the last arriver's, and it alone copies (n words by one workgroup, on the rare path).
+// st, fl and x change inside this launch: no __restrict__, and whatever another workgroup wrote is read with agent-scope atomic loads.
+__global__ __launch_bounds__(256)
+void k_scr_tail(const float* __restrict__ At, uint32_t ldm, uint32_t n, const float* __restrict__ y, const uint32_t* __restrict__ hdr,
+                const uint32_t* __restrict__ pcol, const float* __restrict__ LX, const float* __restrict__ LD, uint32_t* fl, float tol, int tie_guard,
+                DevState* st, float* x, uint32_t* gam, uint32_t* tch, TraceEntry* trace, uint32_t trace_cap,
+                float* x_dst, long long incx, uint32_t* hs_mapped, uint32_t* ticket)
+{
+    __shared__ uint32_t s_go, s_nfl, s_last;
+    const uint32_t tid = threadIdx.x;
+    auto ld = [](const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    // DevState to the host, "a column was not certified" as the status (k_epilogue's statements)
+    auto mirror = [&]() {
+        constexpr uint32_t kWords = (uint32_t)(sizeof(DevState) / 4), kStatus = (uint32_t)(offsetof(DevState, status) / 4);
+        const uint32_t* stw = reinterpret_cast<const uint32_t*>(st);
+        const uint32_t flag = ld(&st->need_sweep);
+        for (uint32_t i = tid; i < kWords; i += 256u) {
+            uint32_t w = ld(stw + i);
+            if (i == kStatus && w == 0u && flag != 0u) w = kStatusSubsetFail;
+            __hip_atomic_store(&hs_mapped[i], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    };
+    // (one thread asks, the workgroup follows: a re-check elsewhere may raise need_sweep while this workgroup starts)
+    if (tid == 0u) { s_go = (ld(&st->status) == 0u && ld(&st->need_sweep) == 0u) ? 1u : 0u; s_nfl = fl[0]; }
+    __syncthreads();
+    const bool go = s_go != 0u;
+    if (s_nfl == 0u) {
+        // nothing listed (the list's length does not change in this launch: every workgroup takes the same branch): nobody touches the
+        // state here, the verdict stands — k_epilogue's work, no ticket
+        if (go && x_dst != nullptr)
+            for (uint32_t i = blockIdx.x * 256u + tid; i < n; i += gridDim.x * 256u) x_dst[(long long)i * incx] = x[i];
+        if (blockIdx.x == 0u) mirror();
+        return;
+    }
+    if (go) scr_recheck_wg<float>(At, ldm, n, y, hdr, nullptr, pcol, LX, LD, fl, tol, tie_guard, st);
+    if (!arrive_last(ticket, gridDim.x, &s_last)) return;
+    if (tid == 0u) s_go = (ld(&st->status) == 0u && ld(&st->need_sweep) == 0u) ? 1u : 0u;
+    __syncthreads();
+    if (s_go != 0u) {
+        scr_repair_wg<float>(At, ldm, n, y, hdr, nullptr, pcol, LX, LD, fl, x, gam, tch, st, trace, trace_cap);
+        // (the repair's plain stores to x and the state are read below by other waves, the state with loads that bypass L1: drained
+        // before the barrier, as arrive_last does, so that the order holds by construction)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (x_dst != nullptr)
+            for (uint32_t i = tid; i < n; i += 256u) x_dst[(long long)i * incx] = x[i];
+    }
+    mirror();
 }
 
 // ---- the screening pass of a batch chunk: FOUR slots per workgroup ----------------------------------------------------
@@ -1591,6 +1670,7 @@ void screen_free(ss_hip_ctx* ctx)
                      S->b_r16, S->b_rn2p, S->b_tab, S->b_gs_part, S->b_gs, S->fl, S->sub256, S->gs64, S->gs64_part, S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    if (ctx->handoff) { (void)hipFree(ctx->handoff); ctx->handoff = nullptr; }
     if (S->b64) {
         Screen64Batch* Bq = static_cast<Screen64Batch*>(S->b64);
         void* bp[] = { Bq->y16, Bq->ytab, Bq->ymeta, Bq->cabs, Bq->sub, Bq->gs, Bq->gs_part, Bq->hdr, Bq->H, Bq->pcol, Bq->X, Bq->r16, Bq->rn2p, Bq->tab, Bq->zero, Bq->c0 };
@@ -1678,6 +1758,10 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     alloc(reinterpret_cast<void**>(&S->gs), (size_t)kSbS * kSbS * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->wmax), (size_t)kScrWmax * sizeof(float));
     alloc(reinterpret_cast<void**>(&S->fl), (size_t)kScrFlWords * sizeof(uint32_t));
+    // (the hand-off block: tickets and the selection's shared histogram in front — k_la_reset clears those at the start of every attempt —,
+    // then the selection workgroups' counts and entries)
+    const size_t ho_words = (size_t)kHoEnt + (np <= kHoSelCols ? (size_t)np + 4u * kHoSelWgs : 0u);
+    alloc(&ctx->handoff, ho_words * sizeof(uint32_t));
     if (ok) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)scr_gemm_lds(kS64Sub));
@@ -1688,6 +1772,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     const float* At = static_cast<const float*>(ctx->At);
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
     (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), s);
+    (void)hipMemsetAsync(ctx->handoff, 0, ho_words * sizeof(uint32_t), s);
     (void)hipMemsetAsync(S->r16, 0, (size_t)kScrRhs * ldm * sizeof(__half), s);
     hipLaunchKernelGGL((k_a16_stats<float>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
     hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta, 0);
@@ -1779,8 +1864,10 @@ static hipError_t launch_scr_first(ss_hip_ctx* ctx, ScreenState* S, const TY* y,
 }
 
 hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first,
-                              EventPair screen, EventPair path, bool omp, bool rescue)
+                              EventPair screen, EventPair path, bool omp, bool rescue, ScrHandoff* ho)
 {
+    // (ho: the hand-offs inside launches of the route a single Homotopy solve takes by default — first attempt, resident path kernel, ranking
+    // pass over a reduced copy, state mirrored to mapped host memory; every other route keeps the launches below as they were)
     // (rescue: the second attempt on a signal the first one declined — no first pass; the selection ranks S->rank, where the columns the
     // scan of the first attempt's log found missing sit on top: launch_screen_rescue_scan)
     // (omp: orthogonal matching pursuit on the same subset — k_res_solve<float, OMP> logs its states the same way, the certificate reads
@@ -1806,8 +1893,13 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
         hipLaunchKernelGGL(k_scr_rescue_rank, dim3(std::min<uint32_t>((np + 255u) / 256u, 1024u)), dim3(256), 0, s, (const float*)ws.c0, (const uint32_t*)S->fl,
                            S->rescue_first, S->rescue_count, S->rescue_first2, S->rescue_count2, n, np, S->rank);
     }
-    (void)launch_sub_select(ctx, B, 1, rescue ? (const float*)S->rank : (const float*)ws.c0, first16 ? S->meta + 6 : nullptr,
-                            nwmax != 0u ? (const float*)S->wmax : nullptr, nwmax);
+    const bool ho_route = ho != nullptr && !omp && !rescue && first16 && nwmax != 0u && ctx->handoff != nullptr && ctx->hs_mapped != nullptr &&
+                          ctx->screen_resident && res_solve_usable<float>();
+    if (ho_route && (ho->mask & 2u) && np <= kHoSelCols)
+        (void)launch_sub_select_wide(ctx, B, (const float*)ws.c0, S->meta + 6, (const float*)S->wmax, nwmax);
+    else
+        (void)launch_sub_select(ctx, B, 1, rescue ? (const float*)S->rank : (const float*)ws.c0, first16 ? S->meta + 6 : nullptr,
+                                nwmax != 0u ? (const float*)S->wmax : nullptr, nwmax);
     hipLaunchKernelGGL(k_sgram_part, dim3(NT * (NT + 1) / 2, nsplit), dim3(256), 0, s, At, ldm, n, (const uint32_t*)B.sub, ldm / nsplit, S->gs_part);
     hipLaunchKernelGGL(k_sgram_sum, dim3((kSbS * kSbS + 255) / 256 + (first16 ? kSbS : 0u)), dim3(256), 0, s, (const float*)S->gs_part, nsplit, S->gs,
                        At, ldm, (const float*)ws.rhs, (const uint32_t*)B.sub, n, ws.c0);
@@ -1831,6 +1923,15 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
                        ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 0u, fl,
                        first16 ? (const float*)ws.c0 : (const float*)nullptr);
     if (screen.b) (void)hipEventRecord(screen.b, s);
+    if (ho_route && (ho->mask & 1u) && fl != nullptr) {
+        // ... and the verdict, the state and x to the caller behind them, in the same launch (the caller then queues no k_epilogue)
+        uint32_t* const hw = static_cast<uint32_t*>(ctx->handoff);
+        hipLaunchKernelGGL(k_scr_tail, dim3(kScrRecheckWgs), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs, (const uint32_t*)B.hdr, (const uint32_t*)B.pcol,
+                           (const float*)B.LX, (const float*)B.LD, S->fl, tol, ctx->tie_guard, ws.st, ws.x, ws.gam, ws.touched, ws.trace, ws.trace_cap,
+                           ho->x_dst, ho->incx, static_cast<uint32_t*>(ctx->hs_mapped), hw + kHoTicketTail);
+        ho->tail_fused = true;
+        return hipGetLastError();
+    }
     // the columns that pass left undecided, exactly (an empty list: the launch returns at once)
     if (fl != nullptr)
         hipLaunchKernelGGL((k_scr_recheck<float>), dim3(kScrRecheckWgs), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs, (const uint32_t*)B.hdr, (const float*)nullptr,

@@ -309,6 +309,7 @@ struct ss_hip_ctx {
     hipEvent_t ev_c0a = nullptr, ev_c0b = nullptr;   // profiling: around the batch GEMM c0 = A^T y of a chunk
     int batch_subset = 1;             // option: 1 = large Gram-form batches run in the subset form (one workgroup per signal + a check over all columns)
     void* screen = nullptr;           // sship::ScreenState* (screen.hip): fp16 copy of A, column norms, the subset's Gram matrix, residual block
+    void* handoff = nullptr;          // its hand-off block (kHo*: tickets and a shared histogram that k_la_reset clears per attempt, then scratch lists)
     int screen_first16 = 1;           // option: the screened form's first pass (A^T y over all columns) reads the half-precision copy too
     int screen_single = 1;            // option: 1 = single fp32 signals on large dictionaries take the screened form (screen.hip), 2 = on every shape
                                       // the form can run on (tests), 0 = never
@@ -488,8 +489,21 @@ hipError_t launch_select_top(ss_hip_ctx* ctx, const float* v, uint32_t n, uint32
 // the path then screened against all columns by one pass over a half-precision copy of A with a rigorous error bound
 bool screen_form_usable(ss_hip_ctx* ctx);                 // shape / option test + one-time preparation (fp16 copy of A, column norms)
 bool screen_first16_usable(const ss_hip_ctx* ctx);        // ... with the FIRST pass (A^T y) over the half-precision copy too
+// Hand-offs inside launches on the route a single fp32 Homotopy solve takes by default (ss_hip_ctx::handoff, words):
+//   [kHoTicketSel], [kHoTicketTail]  arrive_last tickets of k_sub_select1g (subbatch.hip) and k_scr_tail (screen.hip)
+//   [kHoHist .. + 2048)              the selection's histogram over all workgroups (integer atomics: order-independent)
+//   -- up to here (kHoZeroWords, a multiple of 4) cleared by k_la_reset at the start of every attempt --
+//   [kHoCnt .. + kHoSelWgs)          entries written by each selection workgroup
+//   [kHoEnt ..)                      their entries, (key << 16) | column, a fixed region of `slice` words per workgroup
+constexpr uint32_t kHoSelWgs = 64, kHoSelCols = 65536;
+constexpr uint32_t kHoTicketSel = 0, kHoTicketTail = 1, kHoHist = 4, kHoZeroWords = kHoHist + 2048, kHoCnt = kHoZeroWords, kHoEnt = kHoCnt + kHoSelWgs;
+// what the caller of launch_screen_form allows and learns: mask (developer switch SS_HIP_SCR_HANDOFF) 1 = the one-launch tail, 2 = the
+// selection by kHoSelWgs workgroups; x_dst / incx: the caller's x if it is on the device; tail_fused: k_scr_tail ran — the state is
+// mirrored and x_dst written, no k_epilogue is to follow
+struct ScrHandoff { uint32_t mask = 3u; float* x_dst = nullptr; long long incx = 1; bool tail_fused = false; };
+hipError_t launch_sub_select_wide(ss_hip_ctx* ctx, const SubBufs& B, const float* c0, float* thr_out, const float* wmax, uint32_t nwmax);
 hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first = {},
-                              EventPair screen = {}, EventPair path = {}, bool omp = false, bool rescue = false);      // (pairs: around the reduced-precision first pass, the screening pass, the path kernel)
+                              EventPair screen = {}, EventPair path = {}, bool omp = false, bool rescue = false, ScrHandoff* ho = nullptr);      // (pairs: around the reduced-precision first pass, the screening pass, the path kernel)
 // the rescue of a declined solve: the scan of its log for the columns the ranking missed (-> their number), see screen.hip
 hipError_t launch_screen_rescue_scan(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, bool from_recheck, uint32_t* count_out);
 uint32_t screen_rescue_cap();

@@ -290,6 +290,187 @@ void k_sub_select1(const float* __restrict__ c0, uint32_t n, uint32_t n_pad, uin
     for (uint32_t p = want + t; p < kSbS; p += kSel1Threads) sub[p] = 0xffffffffu;
 }
 
+// ---- k_sub_select1g: the COARSE selection of one slot by kHoSelWgs workgroups and one ticket ----------------------------
+// k_sub_select1 with wmax != nullptr is one workgroup walking 256 KB twice while every other CU waits.  Here workgroup g owns the
+// columns [g * slice, (g + 1) * slice): it derives the floor bin from wmax (the same for all, no communication), histograms its
+// elements from the floor up in LDS, adds the non-zero bins to the launch's histogram in ss_hip_ctx::handoff (integer atomics at
+// agent scope: the sum does not depend on their order), leaves those elements as (key << 16) | column in its own region of the
+// scratch list with their count — agent-scope atomic stores, read back with agent-scope atomic loads —, and draws a ticket
+// (arrive_last_relaxed).  The last arriver finds the threshold key and the count above
+// it from the summed histogram by k_sub_select1's crossing rule, marks the listed columns in two LDS bit masks (above the key / of
+// the key) and writes sub[] from the masks in column order, left-most first within the threshold key — so neither the order of
+// the entries inside a region nor the order of arrival reaches the result: the list and thr_out are k_sub_select1's.
+// No spinning.  The histogram and the ticket are cleared by k_la_reset for every attempt.  n_pad <= kHoSelCols (16-bit columns).
+constexpr uint32_t kSelGThreads = 256;
+__global__ __launch_bounds__(kSelGThreads)
+void k_sub_select1g(const float* __restrict__ c0, uint32_t n, uint32_t n_pad, uint32_t slice, uint32_t* __restrict__ sub, float* __restrict__ thr_out,
+                    const float* __restrict__ wmax, uint32_t nwmax, uint32_t* ho)
+{
+    constexpr uint32_t NW = kSelGThreads / 64u, BPT = kSelBins / kSelGThreads;      // bins (and mask words) per thread: 8
+    __shared__ uint32_t hist[kSelBins];
+    __shared__ uint32_t m_sel[kSelBins], m_eq[kSelBins];                            // one bit per column (the last arriver's)
+    __shared__ uint32_t r_pre[kHoSelWgs + 1];
+    __shared__ uint32_t w_tot[NW], s_bin, s_above, s_cross, s_cnt, s_flag;
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const uint32_t want = n < kSbS ? n : kSbS;
+    // exclusive prefix of a per-thread count over the workgroup, in thread order
+    auto block_excl = [&](uint32_t mine) -> uint32_t {
+        uint32_t incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += up; }
+        __syncthreads();
+        if (lane == 63u) w_tot[wave] = incl;
+        __syncthreads();
+        uint32_t before = incl - mine;
+        for (uint32_t w = 0; w < wave; ++w) before += w_tot[w];
+        return before;
+    };
+    // the bin in which the count from the top reaches `want`, and the count above it (none: bin 0, count 0, as in k_sub_select1);
+    // thread t owns the bins (from the top) BPT t .. BPT t + BPT - 1
+    auto crossing = [&](uint32_t& bin, uint32_t& above) -> bool {
+        uint32_t h[BPT], mine = 0;
+#pragma unroll
+        for (uint32_t u = 0; u < BPT; ++u) { h[u] = hist[kSelBins - 1u - (BPT * t + u)]; mine += h[u]; }
+        if (t == 0u) { s_bin = 0u; s_above = 0u; s_cross = 0u; }
+        const uint32_t before = block_excl(mine);
+        if (before < want && before + mine >= want) {
+            uint32_t acc = before;
+#pragma unroll
+            for (uint32_t u = 0; u < BPT; ++u) {
+                if (acc < want && acc + h[u] >= want) { s_bin = kSelBins - 1u - (BPT * t + u); s_above = acc; s_cross = 1u; }
+                acc += h[u];
+            }
+        }
+        __syncthreads();
+        bin = s_bin; above = s_above;
+        const bool crossed = s_cross != 0u;
+        __syncthreads();
+        return crossed;
+    };
+    const uint32_t g = blockIdx.x, lo = g * slice, end = lo + slice;
+    uint32_t* const ent = ho + kHoEnt;
+    // (the slice's values — slice <= 4 per thread: n_pad <= kHoSelCols over kHoSelWgs workgroups — are fetched while the floor is made)
+    const uint32_t base = lo + 4u * t;
+    const bool in = base < end && base < n_pad;
+    const v4f v = in ? *reinterpret_cast<const v4f*>(c0 + base) : v4f{ 0.f, 0.f, 0.f, 0.f };
+    // the floor: the threshold's bin is at or above the bin in which the waves' maxima — elements all — reach `want`
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) hist[BPT * t + u] = 0u;
+    if (t == 0u) s_cnt = 0u;
+    __syncthreads();
+    // (plain LDS atomics: the maxima share a handful of bins, and the LDS serialises those faster than a wave can sort them out)
+    for (uint32_t i0 = t; i0 < nwmax; i0 += 8u * kSelGThreads) {
+        float w[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) { const uint32_t i = i0 + u * kSelGThreads; w[u] = i < nwmax ? wmax[i] : 0.f; }
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; ++u) if (i0 + u * kSelGThreads < nwmax) atomicAdd(&hist[mag_bits(w[u]) >> 20], 1u);
+    }
+    __syncthreads();
+    uint32_t floor_bin = 0, above = 0;
+    (void)crossing(floor_bin, above);
+    // the slice: histogram and entries of the elements from the floor up
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) hist[BPT * t + u] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const uint32_t i = base + (uint32_t)e, key = mag_bits(v[e]) >> 20;
+        const bool ok = in && i < n && key >= floor_bin;
+        if (ok) atomicAdd(&hist[key], 1u);
+        const uint64_t bal = __ballot(ok);
+        if (bal != 0ull) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(bal);
+            uint32_t at = 0;
+            if (lane == lead) at = atomicAdd(&s_cnt, (uint32_t)__popcll(bal));
+            at = (uint32_t)__shfl((int)at, (int)lead, 64) + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (ok) __hip_atomic_store(&ent[lo + at], (key << 16) | i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (t == 0u) __hip_atomic_store(&ho[kHoCnt + g], s_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) {
+        const uint32_t c = hist[BPT * t + u];
+        if (c != 0u) (void)__hip_atomic_fetch_add(&ho[kHoHist + BPT * t + u], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // (everything handed over — entries, counts, histogram — went out as agent-scope atomics and is read back as such: the ticket without
+    // cache fences, ss_hip_device.h)
+    if (!arrive_last_relaxed(&ho[kHoTicketSel], gridDim.x, &s_flag)) return;
+
+    // ---- the last arriver: threshold key, then the list in column order ----
+    auto ld = [](const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) { hist[BPT * t + u] = ld(&ho[kHoHist + BPT * t + u]); m_sel[BPT * t + u] = 0u; m_eq[BPT * t + u] = 0u; }
+    if (t < 64u) {                                                  // (wave 0: where each workgroup's entries start in a walk over all of them)
+        const uint32_t c = t < gridDim.x ? ld(&ho[kHoCnt + t]) : 0u;
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o, 64); if ((int)lane >= o) incl += up; }
+        r_pre[t + 1u] = incl;
+        if (t == 0u) r_pre[0] = 0u;
+    }
+    __syncthreads();
+    uint32_t T22 = 0;
+    const bool crossed = crossing(T22, above);                      // (the 11-bit key)
+    const uint32_t need_eq = want - above;
+    if (thr_out != nullptr && t == 0u) thr_out[0] = __uint_as_float(T22 + 1u >= (0x7f800000u >> 20) ? 0x7f800000u : (T22 + 1u) << 20);
+    if (crossed) {
+        const uint32_t total = r_pre[kHoSelWgs];
+        // (eight entries of a thread in flight together)
+        for (uint32_t f0 = t; f0 < total; f0 += 8u * kSelGThreads) {
+            uint32_t e[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8u; ++u) {
+                const uint32_t f = f0 + u * kSelGThreads;
+                uint32_t r = 0;                                     // the last region that starts at or before f
+#pragma unroll
+                for (uint32_t step = kHoSelWgs / 2u; step != 0u; step >>= 1) if (r_pre[r + step] <= f) r += step;
+                e[u] = f < total ? ld(&ent[r * slice + (f - r_pre[r])]) : 0u;
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 8u; ++u) {
+                if (f0 + u * kSelGThreads >= total) continue;
+                const uint32_t k = e[u] >> 16, i = e[u] & 0xffffu;
+                if (k > T22) atomicOr(&m_sel[i >> 5], 1u << (i & 31u));
+                else if (k == T22) atomicOr(&m_eq[i >> 5], 1u << (i & 31u));
+            }
+        }
+    } else {
+        // (fewer than `want` elements from the floor up — the maxima were not this vector's: every column, as k_sub_select1 does then)
+        for (uint32_t i = t; i < n; i += kSelGThreads) {
+            if (mag_bits(c0[i]) >> 20 > T22) atomicOr(&m_sel[i >> 5], 1u << (i & 31u));
+            else atomicOr(&m_eq[i >> 5], 1u << (i & 31u));
+        }
+    }
+    __syncthreads();
+    // thread t owns the columns 32 BPT t .. 32 BPT (t + 1) - 1
+    uint32_t ch[BPT], neq = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) neq += (uint32_t)__popc(m_eq[BPT * t + u]);
+    const uint32_t eq_before = block_excl(neq);
+    uint32_t take = eq_before < need_eq ? need_eq - eq_before : 0u, nch = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) {
+        uint32_t w = m_eq[BPT * t + u], kept = 0u;
+        while (take != 0u && w != 0u) { const uint32_t low = w & (0u - w); kept |= low; w ^= low; --take; }
+        ch[u] = m_sel[BPT * t + u] | kept;
+        nch += (uint32_t)__popc(ch[u]);
+    }
+    uint32_t out = block_excl(nch);
+#pragma unroll
+    for (uint32_t u = 0; u < BPT; ++u) {
+        uint32_t w = ch[u];
+        while (w != 0u) {
+            const uint32_t b = (uint32_t)__builtin_ctz(w);
+            w &= w - 1u;
+            if (out < kSbS) sub[out] = 32u * (BPT * t + u) + b;
+            ++out;
+        }
+    }
+    for (uint32_t p = want + t; p < kSbS; p += kSelGThreads) sub[p] = 0xffffffffu;
+}
+
 // ---- k_sub_select1w: ONE slot, dictionaries wider than 65536 columns -------------------------------------------------
 // k_sub_select1's walks in chunks of 65536 columns; the chosen columns go through two short LDS lists instead of bit masks
 // (which would need n bits): the < 448 above the threshold key and the columns OF the key, of which the left-most are
@@ -970,6 +1151,18 @@ hipError_t launch_sub_select(ss_hip_ctx* ctx, const SubBufs& B, uint32_t nslots,
                            wmax, nwmax);
     else
         hipLaunchKernelGGL(k_sub_select, dim3(nslots), dim3(kSelThreads), 0, ctx->stream, c0, (uint32_t)ctx->n, ctx->n_pad, B.sub, B.fpick, B.fval, kSbS);
+    return hipGetLastError();
+}
+
+// the coarse selection of one slot by kHoSelWgs workgroups (k_sub_select1g): wmax from the reduced-precision first pass, n_pad <= kHoSelCols,
+// the context's hand-off block cleared by k_la_reset earlier in the same attempt
+hipError_t launch_sub_select_wide(ss_hip_ctx* ctx, const SubBufs& B, const float* c0, float* thr_out, const float* wmax, uint32_t nwmax)
+{
+    if (ctx->handoff == nullptr || wmax == nullptr || ctx->n_pad > kHoSelCols) return hipErrorInvalidConfiguration;
+    const uint32_t slice = ((ctx->n_pad + kHoSelWgs - 1u) / kHoSelWgs + 3u) & ~3u;
+    static_assert(kHoSelCols / kHoSelWgs <= 4u * kSelGThreads, "k_sub_select1g: a slice is one 16-byte load per thread");
+    hipLaunchKernelGGL(k_sub_select1g, dim3(kHoSelWgs), dim3(kSelGThreads), 0, ctx->stream, c0, (uint32_t)ctx->n, ctx->n_pad, slice, B.sub, thr_out,
+                       wmax, nwmax, static_cast<uint32_t*>(ctx->handoff));
     return hipGetLastError();
 }
 
