@@ -97,10 +97,8 @@ __device__ __forceinline__ double uni(double v)
     return __hiloint2double((int)hi, (int)lo);
 }
 
-// Workgroup barrier for data that crosses it in LDS only: waits for this wave's LDS operations, not for its global loads and stores
-// (__syncthreads() carries a release fence — s_waitcnt vmcnt(0) — so every barrier of a round would wait for the round's log
-// stores and for the entering column's Gram row, ~1000 cycles each, where nothing behind the barrier needs them yet)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (lds_barrier — ss_hip_device.h — is this kernel's barrier: with __syncthreads() every barrier of a round would wait for the round's
+// log stores and for the entering column's Gram row, ~1000 cycles each, where nothing behind the barrier needs them yet)
 
 // dst = (lane's bit of msk) ? src : dst, written over dst
 __device__ __forceinline__ void cmov_inplace(float& dst, float src, unsigned long long msk)

@@ -56,6 +56,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <type_traits>
 
 namespace sship {
 
@@ -736,7 +737,8 @@ void k_scr_residuals(const float* __restrict__ At, uint32_t ldm, uint32_t n, con
 // Workgroup = 128 dictionary columns x up to 96 right-hand sides; wave = 32 columns x 2 or 3 MFMA tiles of 32 states (the
 // third only when the path logged more than 64 states).  A stage is 128 rows: 32 KB of A16 and 16 / 24 KB of R16 (from
 // L2) land in LDS by 16-byte stores of coalesced 256-byte runs; TWO stages of loads are in flight (two register sets)
-// under the MFMAs of a third.  HBM-bound: 1.07 GB at 8192 x 65536.
+// under the MFMAs of a third — no load of the stage loop stands behind a condition, or the compiler's waits drain them (see the loop).
+// HBM-bound: 1.07 GB at 8192 x 65536.
 template <int NT>
 __global__ __launch_bounds__(256, 2)
 void k_scr_gemm(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, const __half* __restrict__ r16,
@@ -791,15 +793,21 @@ void k_scr_gemm(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, const 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
     const uint32_t col0 = blockIdx.y * kScrCols;
     const uint32_t lc = tid >> 4, piece = tid & 15u;
-    const __half* ga = a16 + (size_t)(col0 + lc) * ldm + 8u * piece;
-    const __half* gr = r16 + (size_t)lc * ldm + 8u * piece;
+    // Buffer loads: a load's address = a descriptor of the workgroup's 128 columns of A16 (of the slot's 32 NT rows of R16) plus a scalar
+    // byte offset — row of 16 columns, stage — plus ONE 32-bit byte offset per thread, its column of the 16 and its 16-byte piece.  No
+    // 64-bit address per load is kept in registers: with every load of the loop unconditional the compiler would hold all of them.
+    const __amdgpu_buffer_rsrc_t ga = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a16 + (size_t)col0 * ldm), 0, (int)(kScrCols * ldm * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(r16), 0, (int)(32u * (uint32_t)NT * ldm * 2u), 0x00020000);
+    const uint32_t goff = 2u * (lc * ldm + 8u * piece);
     scr_u4 pa0[8], pr0[NPR], pa1[TWO ? 8 : 1], pr1[TWO ? NPR : 1];
+    // (NTU_: the tiles in use where the macros stand — a constant of each body)
 #define SCR_LOAD(PA, PR, R0)                                                                                      \
     {                                                                                                             \
         _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                             \
-            PA[i] = __builtin_nontemporal_load(reinterpret_cast<const scr_u4*>(ga + (size_t)(16 * i) * ldm + (R0)));  \
+            PA[i] = __builtin_bit_cast(scr_u4, __builtin_amdgcn_raw_buffer_load_b128(ga, goff, 2u * ((uint32_t)(16 * i) * ldm + (R0)), 2 /* nt */)); \
         _Pragma("unroll") for (int i = 0; i < NPR; ++i)                                                           \
-            if ((uint32_t)(i / 2) < ntu) PR[i] = *reinterpret_cast<const scr_u4*>(gr + (size_t)(16 * i) * ldm + (R0)); \
+            if ((uint32_t)(i / 2) < NTU_)                                                                         \
+                PR[i] = __builtin_bit_cast(scr_u4, __builtin_amdgcn_raw_buffer_load_b128(gr, goff, 2u * ((uint32_t)(16 * i) * ldm + (R0)), 0)); \
     }
     scr_v16f acc[NT];
 #pragma unroll
@@ -809,45 +817,98 @@ void k_scr_gemm(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, const 
     const uint32_t r = lane & 31u, h = lane >> 5;
     const unsigned char* rdA = sA + (size_t)(32u * w + r) * kScrPitchB + 16u * h;
     const unsigned char* rdR = sR + (size_t)r * kScrPitchB + 16u * h;
-#define SCR_STAGE(PA, PR, MORE, RNEXT)                                                                                \
+    // (the barriers wait for LDS only: a set's loads are waited for where its registers go to LDS, and no sooner)
+#define SCR_STAGE(PA, PR, RELOAD)                                                                                 \
     {                                                                                                             \
-        __syncthreads();                                                                                          \
+        __builtin_amdgcn_sched_barrier(0);      /* (no MFMA of the stage before is moved behind the barriers, in front of the reload) */ \
+        lds_barrier();                                                                                            \
         _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                             \
             *reinterpret_cast<scr_u4*>(sA + (size_t)(lc + 16u * (uint32_t)i) * kScrPitchB + 16u * piece) = PA[i]; \
         _Pragma("unroll") for (int i = 0; i < NPR; ++i)                                                           \
-            if ((uint32_t)(i / 2) < ntu)                                                                          \
+            if ((uint32_t)(i / 2) < NTU_)                                                                         \
                 *reinterpret_cast<scr_u4*>(sR + (size_t)(lc + 16u * (uint32_t)i) * kScrPitchB + 16u * piece) = PR[i]; \
-        __syncthreads();                                                                                          \
-        if (MORE) SCR_LOAD(PA, PR, (RNEXT))                                                                       \
+        lds_barrier();                                                                                            \
+        RELOAD                                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);      /* (the loads go out in front of the MFMAs, not among them) */    \
         _Pragma("unroll") for (uint32_t ks = 0; ks < kScrKc / 16u; ++ks) {                                        \
             const scr_h8 bq = *reinterpret_cast<const scr_h8*>(rdA + 32u * ks);                                   \
             _Pragma("unroll") for (int t = 0; t < NT; ++t) {                                                      \
-                if ((uint32_t)t < ntu) {                                                                          \
+                if ((uint32_t)t < NTU_) {                                                                         \
                     const scr_h8 aq = *reinterpret_cast<const scr_h8*>(rdR + (size_t)(32 * t) * kScrPitchB + 32u * ks); \
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bq, acc[t], 0, 0, 0);                     \
                 }                                                                                                 \
             }                                                                                                     \
         }                                                                                                         \
     }
+#define SCR_NONE
     // (ldm is a multiple of 256: an even number of stages.)  Every workgroup starts at a row offset of its own and wraps
     // around — the sum's order is free here — so that the 512 workgroups do not walk the same 256-byte phase of their
     // 16-KiB-strided columns together (the HBM channels are selected by those address bits)
     const uint32_t nstage = ldm / kScrKc;
     const uint32_t sbase = (blockIdx.y * skew) % nstage;
 #define SCR_ROW(S) ((sbase + (S) >= nstage ? sbase + (S) - nstage : sbase + (S)) * kScrKc)
-    SCR_LOAD(pa0, pr0, SCR_ROW(0u))
     if constexpr (TWO) {
-        SCR_LOAD(pa1, pr1, SCR_ROW(1u))
-        for (uint32_t sidx = 0; sidx < nstage; sidx += 2u) {
-            SCR_STAGE(pa0, pr0, sidx + 2u < nstage, SCR_ROW(sidx + 2u))
-            SCR_STAGE(pa1, pr1, sidx + 3u < nstage, SCR_ROW(sidx + 3u))
-        }
+        // Two register sets, each reloaded for the stage two ahead as soon as it is in LDS.  No load of the loop stands behind a
+        // condition — the tile count is a constant of the body (one uniform branch in front selects it) and the last two stages,
+        // which reload nothing, are written out behind the loop — so a set is 8 + 2 NTU_ loads and the wait in front of its LDS
+        // writes, vmcnt(2 (8 + 2 NTU_) - 1 .. 8 + 2 NTU_), leaves every load of the younger set in flight.
+        auto stages = [&](auto ntu_c) __attribute__((always_inline)) {
+            constexpr uint32_t NTU_ = decltype(ntu_c)::value;
+            asm volatile("; k_scr_gemm: %0 tiles in use" :: "n"(NTU_));   // (keeps the bodies apart: their common first loads are not merged in front of the branch)
+            SCR_LOAD(pa0, pr0, SCR_ROW(0u))
+            SCR_LOAD(pa1, pr1, SCR_ROW(1u))
+            for (uint32_t sidx = 0; sidx + 2u < nstage; sidx += 2u) {
+                SCR_STAGE(pa0, pr0, SCR_LOAD(pa0, pr0, SCR_ROW(sidx + 2u)))
+                SCR_STAGE(pa1, pr1, SCR_LOAD(pa1, pr1, SCR_ROW(sidx + 3u)))
+            }
+            SCR_STAGE(pa0, pr0, SCR_NONE)
+            SCR_STAGE(pa1, pr1, SCR_NONE)
+        };
+        if (ntu <= 1u) stages(std::integral_constant<uint32_t, 1u>{});
+        else if (ntu == 2u) stages(std::integral_constant<uint32_t, 2u>{});
+        else if (NT == 3 || ntu == 3u) stages(std::integral_constant<uint32_t, 3u>{});
+        else if constexpr (NT >= 4) stages(std::integral_constant<uint32_t, 4u>{});
     } else {
+        // Five tiles: one register set — a second does not fit the registers of two workgroups per CU — reloaded behind its own stage
+        // with the loop as it was: the tile count read in the loop, plain loads, __syncthreads().  (With the statements of the
+        // bodies above this instantiation measured 7 % SLOWER, 118 against 110 us at 4096 x 16384 with 136 states.)
+        const __half* ga5 = a16 + (size_t)(col0 + lc) * ldm + 8u * piece;
+        const __half* gr5 = r16 + (size_t)lc * ldm + 8u * piece;
+#define SCR5_LOAD(R0)                                                                                             \
+    {                                                                                                             \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                             \
+            pa0[i] = __builtin_nontemporal_load(reinterpret_cast<const scr_u4*>(ga5 + (size_t)(16 * i) * ldm + (R0))); \
+        _Pragma("unroll") for (int i = 0; i < NPR; ++i)                                                           \
+            if ((uint32_t)(i / 2) < ntu) pr0[i] = *reinterpret_cast<const scr_u4*>(gr5 + (size_t)(16 * i) * ldm + (R0)); \
+    }
+        SCR5_LOAD(SCR_ROW(0u))
         for (uint32_t sidx = 0; sidx < nstage; ++sidx) {
-            SCR_STAGE(pa0, pr0, sidx + 1u < nstage, SCR_ROW(sidx + 1u))
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                *reinterpret_cast<scr_u4*>(sA + (size_t)(lc + 16u * (uint32_t)i) * kScrPitchB + 16u * piece) = pa0[i];
+#pragma unroll
+            for (int i = 0; i < NPR; ++i)
+                if ((uint32_t)(i / 2) < ntu)
+                    *reinterpret_cast<scr_u4*>(sR + (size_t)(lc + 16u * (uint32_t)i) * kScrPitchB + 16u * piece) = pr0[i];
+            __syncthreads();
+            if (sidx + 1u < nstage) SCR5_LOAD(SCR_ROW(sidx + 1u))
+#pragma unroll
+            for (uint32_t ks = 0; ks < kScrKc / 16u; ++ks) {
+                const scr_h8 bq = *reinterpret_cast<const scr_h8*>(rdA + 32u * ks);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if ((uint32_t)t < ntu) {
+                        const scr_h8 aq = *reinterpret_cast<const scr_h8*>(rdR + (size_t)(32 * t) * kScrPitchB + 32u * ks);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(aq, bq, acc[t], 0, 0, 0);
+                    }
+                }
+            }
         }
+#undef SCR5_LOAD
     }
 #undef SCR_ROW
+#undef SCR_NONE
 #undef SCR_STAGE
 #undef SCR_LOAD
     // ---- epilogue: the per-state table and the subset's columns into LDS, then every (column, state) of this wave ------

@@ -187,6 +187,10 @@ __device__ __forceinline__ int dict_unit_exp(float max_norm)
     return e < -100 ? -100 : (e > 100 ? 100 : e);
 }
 
+// Workgroup barrier for data that crosses it in LDS only: waits for this wave's LDS operations, not for its global loads and stores
+// (__syncthreads() carries a release fence — s_waitcnt vmcnt(0) — which drains loads that were issued ahead on purpose)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Sum over the wave, the same value in every lane.  Fixed association: butterfly inside each row
 // of 16 lanes (1, 2, 4, 8 apart), then ((row0 + row1) + row2) + row3.
 template <typename T>
