@@ -2167,6 +2167,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
                                      b0 + b, hs[b].status, hs[b].iter, hs[b].solo_nlog, hs[b].K, hs[b].c_inf);
                     redo.push_back(b0 + b);                  // (nothing of it is reported: solved again in the lock-step form below)
                     ++n_redo_chunk;
+                    count_reasons(ctx, hs[b].sub_reason, false);     // (why, as the single solves and the OMP / fp64 batches count it)
                     continue;
                 }
                 if (hs[b].done && ctx->tie_rerun && !ctx->tie_guard && (hs[b].status == kStatusTieRerun || (hs[b].status == 0 && hs[b].tie_stall != 0))) {
