@@ -284,7 +284,8 @@ def _torch_to_numpy_dtype(a):
 def _sync_producers(*arrays):
     """The library consumes device pointers on the context's own (non-blocking) stream, which is not
     ordered against the stream that produced them: wait for the caller's current torch stream first
-    (INTEGRATION.md, 'streams')."""
+    ('Streams').  Every method calls this with ALL its device arguments, after the last fill of an output
+    it allocates and before the library call (tests/test_sship_stream_order.py holds every public callable to that)."""
     for a in arrays:
         if a is not None and hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
             import torch
@@ -412,14 +413,12 @@ class _Context:
             raise SsHipError(rc, "unknown option %r" % key)
         return int(v.value)
 
-    def _open(self, A, entry, device, sync=True):
-        """the matrix a constructor was given -> the attributes every method reads, and the context.  sync=False: the caller's
-        stream is not waited for (Irls, whose constructor and single solve never did)"""
+    def _open(self, A, entry, device):
+        """the matrix a constructor was given -> the attributes every method reads, and the context"""
         ptr, shape, strides, dt, keep = _describe(A)
         if len(shape) != 2:
             raise ValueError("A must be 2-D")
-        if sync:
-            _sync_producers(A)
+        _sync_producers(A)
         self.suffix, self.ctype = _suffix(dt)
         self.dtype = dt
         self.m, self.n = int(shape[0]), int(shape[1])
@@ -433,9 +432,9 @@ class _Context:
     def _bad_out(self):
         raise ValueError("out must be a length-n vector of the matrix dtype")
 
-    def _solve(self, entry, y, tolerance, max_iterations, out, spd=False, shard=False, sync=True):
+    def _solve(self, entry, y, tolerance, max_iterations, out, spd=False, shard=False):
         """one signal through `entry` -> (x, iter, solution_error), and the IRLS failure flag with spd=True.  shard=True: a shard
-        without columns passes no pointer (ColumnSharded).  sync: as for _open."""
+        without columns passes no pointer (ColumnSharded)."""
         yp, yshape, ystr, ydt, keep = _describe(y)
         if ydt != self.dtype or len(yshape) != 1 or yshape[0] != self.m:
             self._bad_y(ydt)
@@ -452,8 +451,7 @@ class _Context:
         it = ctypes.c_uint32(0)
         e = ctypes.c_double(0.0)
         fn = getattr(lib(), entry + self.suffix)
-        if sync:
-            _sync_producers(y, out)
+        _sync_producers(y, out)
         if not spd:
             _call(fn, self._h, yp, ystr[0], self.ctype(tolerance), int(max_iterations), xp, incx, ctypes.byref(it), ctypes.byref(e))
             return out, int(it.value), float(e.value)
@@ -1274,7 +1272,8 @@ class Homotopy(_Context):
         return c, float(ms.value)
 
     def gemm_t(self, R, repeats=1, out=None):
-        """C[b] = A^T R[b] for the rows of R (B, m) on the MFMA units -> (C (B, n), mean ms)"""
+        """C[b] = A^T R[b] for the rows of R (B, m) on the MFMA units -> (C (B, n), mean ms); R and `out` (B, n) may live on the
+        device: their producers on the caller's current stream are waited for"""
         Rp, shape, strides, dt, keep = _describe(R)
         if dt != np.float32 or self.dtype != np.float32 or len(shape) != 2 or shape[1] != self.m or strides[1] != 1:
             raise ValueError("R must be a (B, m) float32 array with contiguous rows")
@@ -1285,6 +1284,7 @@ class Homotopy(_Context):
         if cdt != np.float32 or tuple(cshape) != (B, self.n) or cstr[1] != 1:
             raise ValueError("out must be (B, n) float32 with contiguous rows")
         ms = ctypes.c_float(0.0)
+        _sync_producers(R, out)
         _call(lib().ss_hip_gemm_t_f32, self._h, Rp, B, strides[0], Cp, cstr[0], int(repeats), ctypes.byref(ms))
         return out, float(ms.value)
 
@@ -1323,11 +1323,13 @@ class Homotopy(_Context):
         return G, float(ms.value)
 
     def reconstruct(self, x):
-        """y = A x on the device copy (ss::reconstruct_signal)."""
+        """y = A x on the device copy (ss::reconstruct_signal) -> y (m,), a numpy array; a device x is waited for like every
+        other device argument."""
         xp, shape, strides, dt, keep = _describe(x)
         if dt != self.dtype or len(shape) != 1 or shape[0] != self.n or strides[0] != 1:
             raise ValueError("x must be a contiguous length-n vector of the matrix dtype")
         y = np.empty(self.m, dtype=self.dtype)
+        _sync_producers(x)
         _call(self._fn("ss_hip_reconstruct_"), self._h, xp, y.ctypes.data)
         return y
 
@@ -1415,15 +1417,16 @@ class ColumnSharded(Homotopy):
 
 class Irls(_Context):
     """IRLS on the device (the reference's ss::irls<T>): Householder QR of A at construction
-    (rows >= columns), the reweighting loop in one launch per solve."""
+    (rows >= columns), the reweighting loop in one launch per solve.  A, y / Y and `out` may live on the device; the
+    constructor and both solves wait for their producers as every Homotopy call does ('Streams')."""
     _DESTROY = "ss_hip_irls_destroy"
 
     def __init__(self, A, device=0):
-        self._open(A, "ss_hip_irls_create_", device, sync=False)
+        self._open(A, "ss_hip_irls_create_", device)
 
     def solve(self, y, tolerance=None, max_iterations=100, out=None):
         """-> (x, iter, solution_error, spd_failure); defaults mirror the reference binding (binding.cpp:94-95)"""
-        return self._solve("ss_hip_irls_solve_", y, tolerance, max_iterations, out, spd=True, sync=False)
+        return self._solve("ss_hip_irls_solve_", y, tolerance, max_iterations, out, spd=True)
 
     def solve_batch(self, Y, tolerance=None, max_iterations=100, out=None):
         """Y: (B, m) -> X (B, n), iters (B,) uint32, errors (B,) float64, spd (B,) bool; each row's result is solve's for it
