@@ -39,7 +39,9 @@ extern "C" {
                                     ss_hip_stats; the top correlations of residuals and the record extension of the stagewise coders,
                                     ss_hip_top_correlations_* and ss_hip_extend_records_*, with the test-aid option "tc_chunk_max" — no
                                     new field of ss_hip_stats; joint sparse coding of signal groups, ss_hip_group_top_correlations_* and
-                                    ss_hip_group_class_residuals_* — no new option key, no new field of ss_hip_stats) */
+                                    ss_hip_group_class_residuals_* — no new option key, no new field of ss_hip_stats; the atom step of
+                                    dictionary learning under row weights, ss_hip_weighted_atom_update_* — no new option key, no new
+                                    field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -726,6 +728,64 @@ int ss_hip_weighted_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t 
 int ss_hip_weighted_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
                                         const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
                                         double* R, ptrdiff_t r_stride, uint32_t* best, double* sci, char* err, size_t errlen);
+
+/*
+ * The weighted atom update: the atom step of dictionary learning under the weights above — learning from masked, occluded or
+ * robustly weighted signals, min sum_b sum_k w_kb (y_b - A x_b)_k^2 over the atoms (added under ABI version 7; csrc/wdictlearn.hip;
+ * NOT in the reference).  ss_hip_homotopy_atom_update_* on zero-filled signals fits the atoms to the zeros; its chains cannot be had
+ * by scaling Y, because the weights differ per signal while the atom is shared.
+ * Y, records, kmax, cols, S, V, usage: as for ss_hip_homotopy_atom_update_* (cols == NULL: all n atoms; a truncated record does not
+ * count; host or device pointers).  W, w_stride: the WEIGHTS of the weighted calls above.  For every requested atom j, with U_j the
+ * counting signals whose record holds j in ascending (b, position in the record), c_b that record's value and r_b = y_b - A x_b the
+ * UNWEIGHTED residual (ss_hip_homotopy_atom_update_*'s words):
+ *     num_k = sum_{b in U_j} (w_kb c_b) r_kb       den_k = sum_{b in U_j} (w_kb c_b) c_b       row k is SEEN when den_k > 0
+ *     d_k   = a_kj + num_k / den_k  (seen)         d_k = a_kj  (not seen: no user observes the row, it carries no information)
+ *     nu    = ||d||_2                              v_j = d / nu
+ *     records_out: the value c_b of atom j in every counting record becomes c_b * nu
+ * t = w_kb * c_b is rounded once in T, then num += t * r_kb and den += t * c_b, every product and sum rounded separately in T, one
+ * user after the other in list order, one chain per row, never split; d_k: one division, one addition, the comparison den_k > 0 (no
+ * arithmetic masks); ||d||^2 in double in ss_hip_homotopy_atom_update_*'s order; nu = (T) sqrt; v = d / nu; c_b * nu one product in T.
+ * The atom is LEFT AS IT IS — V holds the stored column bit for bit and no record value is touched — when U_j is empty, when no row
+ * is seen, or when nu is zero or not finite; bit 31 of usage is set in the last two cases.  All atoms see the same old dictionary
+ * and residuals (the Jacobi step).  d is the row-wise weighted least-squares minimiser over the atom for fixed c, and the values are
+ * rescaled so that v_j c'_b = d c_b: hence, in exact arithmetic, a call whose atoms share no signal (S = 1 in particular) cannot
+ * raise sum_b sum_k w_kb (y_b - A x_b)_k^2, whatever the old atom's norm.  Atoms that share signals do not see each other's update.
+ *   records_out  (may be NULL) B records: `records` itself (in place) or disjoint from it; every other word of a record — K, iter,
+ *                err, idx, the tail, the values of atoms not requested or left as they are, truncated records — is copied word
+ *                for word
+ *   objective    (may be NULL) one double: sum_b sum_k w_kb r_kb^2 over the counting signals BEFORE the update: every square formed
+ *                in double and multiplied by (double) w_kb before it enters ss_hip_homotopy_atom_update_*'s sums, in their order
+ *   flags        SS_HIP_WDL_APPLY: the atoms that changed are written into the context as ss_hip_homotopy_atom_update_*'s apply
+ *                writes them; when no atom changed nothing is touched
+ * PINNED: with every weight exactly 1 objective and usage are ss_hip_homotopy_atom_update_*'s words; V agrees with that call's only
+ * to rounding (it starts its chain at (sum c^2) a_j with sum c^2 in double; here den is a chain in T per row).  With a 0/1 mask the
+ * hidden entries of Y are never read into a result.
+ * CONTRACT: as for ss_hip_homotopy_atom_update_*, with w_b among what the words are a function of: the same words alone or among
+ * other atoms, with host or device pointers, across the internal chunking (option "dl_chunk_max"), with w_stride == 0 or a W whose
+ * rows repeat the vector, in place or out of place, whatever the context did before.  No floating-point atomics.
+ * RANGE: under A 2^a, Y 2^b, record values 2^(b-a), W 2^c the call returns the same changed atoms and usage (an atom that is left
+ * is the stored column, in the context's units), nu times 2^a — so the values of changed atoms in records_out are the unscaled
+ * call's times 2^b — and the objective times 2^(2b+c), word for word, as long as the intermediates stay normal numbers: w c (2^(c+b-a)), its products with r and c (2^(c+2b-a), 2^(c+2b-2a)) and the quotient in T,
+ * ||d||^2 and the squares in double.
+ * Validation happens before anything is written: a failing call leaves the context and the outputs untouched.
+ *   SS_HIP_EINVAL  ss_hip_homotopy_atom_update_*'s list (V may be null with or without SS_HIP_WDL_APPLY); the weighted calls' list
+ *                  (a null W; a negative w_stride or one in 1 .. m - 1; a weight that is negative or not finite, with its signal
+ *                  and row); an unknown flag bit; records_out not 8-byte aligned or overlapping records in part; V, usage,
+ *                  objective and records_out all null without SS_HIP_WDL_APPLY (nothing was asked for)
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   B == 0, or S == 0 with cols given: SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_WDL_APPLY 1u
+int ss_hip_weighted_atom_update_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const float* W, ptrdiff_t w_stride, const void* records, uint32_t kmax, void* records_out,
+                                    const uint32_t* cols, size_t S,
+                                    float* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                    uint32_t* usage, double* objective, uint32_t flags, char* err, size_t errlen);
+int ss_hip_weighted_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                    const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax, void* records_out,
+                                    const uint32_t* cols, size_t S,
+                                    double* V, ptrdiff_t stride_row, ptrdiff_t stride_col,
+                                    uint32_t* usage, double* objective, uint32_t flags, char* err, size_t errlen);
 
 /*
  * Non-negative coding — the positive top correlations: ss_hip_top_correlations_* restricted to the atoms that a fit may ADD (added

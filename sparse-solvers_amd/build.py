@@ -71,6 +71,8 @@ HIP_UNITS = [
     ("joint.hip", ["-ffp-contract=off"]),
     # weighted coding: the weighted top correlations beside topcorr.hip's tile (the weighted norms are its second product), so the same flags
     ("weighted.hip", ["-ffp-contract=off"]),
+    # the weighted atom update: dictlearn.hip's index and residuals under weighted.hip's weights, so the same flags (the tests' bounds)
+    ("wdictlearn.hip", ["-ffp-contract=off"]),
     # non-negative coding: the positive selection beside topcorr.hip's (the score in double in its order), so the same flags
     ("nonneg.hip", ["-ffp-contract=off"]),
 ]

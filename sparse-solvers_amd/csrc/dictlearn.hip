@@ -676,6 +676,15 @@ hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t dl_launch_gather(ss_hip_ctx* ctx, const T* out, long long ors, long long ocs, const uint32_t* sel, uint32_t nc, T* Vc)
+{
+    hipLaunchKernelGGL((k_dl_gather<T>), dim3(nc), dim3(256), 0, ctx->stream, out, ors, ocs, sel, (uint32_t)ctx->m, Vc);
+    return hipGetLastError();
+}
+
+template hipError_t dl_launch_gather<float>(ss_hip_ctx*, const float*, long long, long long, const uint32_t*, uint32_t, float*);
+template hipError_t dl_launch_gather<double>(ss_hip_ctx*, const double*, long long, long long, const uint32_t*, uint32_t, double*);
 template hipError_t dl_launch_lists<float>(ss_hip_ctx*, const unsigned char*, size_t, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t,
                                            uint32_t*, const uint32_t*, uint32_t, uint32_t*, uint32_t*, uint32_t*, float*, float*, uint32_t*);
 template hipError_t dl_launch_lists<double>(ss_hip_ctx*, const unsigned char*, size_t, uint32_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t,

@@ -2911,6 +2911,7 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     sship::topcorr_free(ctx);
     sship::joint_free(ctx);
     sship::weighted_free(ctx);
+    sship::wdictlearn_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);

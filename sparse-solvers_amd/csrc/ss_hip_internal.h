@@ -368,6 +368,7 @@ struct ss_hip_ctx {
     void* tc = nullptr;           // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
     void* js = nullptr;           // sship::WorkArena* (joint.hip): the workspace of the group class residuals
     void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
+    void* wdl = nullptr;          // sship::WdlState* (wdictlearn.hip): the workspace of the weighted atom update
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -538,6 +539,10 @@ template <typename T>
 hipError_t dl_launch_residuals(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
                                uint32_t Bc, T* R, double* part);
 hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per, uint32_t B, double* sig, double* obj);
+// ... and of the gather behind its apply, which the weighted atom update (wdictlearn.hip) shares: Vc[p][0 .. m) = column sel[p] of out
+// (out(i, s) = out[i * ors + s * ocs]), p < nc — the changed atoms, contiguous, for the column replacement
+template <typename T>
+hipError_t dl_launch_gather(ss_hip_ctx* ctx, const T* out, long long ors, long long ocs, const uint32_t* sel, uint32_t nc, T* Vc);
 // the least-squares refit of compact records (refit.hip): releases its workspace
 void refit_free(ss_hip_ctx* ctx);
 // the K-SVD sweep (ksvd.hip): releases its workspace
@@ -572,6 +577,8 @@ template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uin
 template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
 // weighted coding (weighted.hip): releases the staged weights
 void weighted_free(ss_hip_ctx* ctx);
+// the weighted atom update (wdictlearn.hip): releases its workspace
+void wdictlearn_free(ss_hip_ctx* ctx);
 // ... and what the three weighted calls share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
 // weights_on_device: the batch's weights where the kernels read them — W itself, or a staged copy of a host caller's (row pitch m, or
 // 0 for the shared vector) — after a device scan for the first weight that is negative or not finite (SS_HIP_EINVAL, the signal and
