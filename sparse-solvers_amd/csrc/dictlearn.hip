@@ -27,6 +27,7 @@
 //   k_dl_signal_sums / k_dl_objective   the objective: per signal, then over the signals.
 // The residuals of B signals are held for a chunk of signals at a time (a byte budget; option "dl_chunk_max"): chunks in ascending
 // order, g carried between them in memory — the chain of an atom is the unchunked one, word for word.
+// The host steps around the launches are the three learners' (learn_driver.h); this unit also holds their arena (learn_arena).
 //
 // SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately):
 //   acc_i      starts at 0 and takes v_k * A[i][col_k] one entry after the other in the record's order, in the context's precision
@@ -47,7 +48,7 @@
 // ||g_j||^2 (2^(4b-2a)) and ||r_b||^2 (2^2b) in double.  Below it a sum rounds as a subnormal, above it ||g_j||^2 is infinite and the
 // atom is left as it is (include/ss_hip.h states the same range; tests/test_gpu_scaling.py holds the kernels to it).
 #include "ss_hip_internal.h"
-#include "record_common.h"
+#include "learn_driver.h"
 
 #include <algorithm>
 #include <cmath>
@@ -57,26 +58,7 @@ namespace sship {
 
 namespace {
 
-constexpr size_t kDlChunkBytes = (size_t)256 << 20;      // byte budget of the residual block of one chunk (never changes a result)
-constexpr uint32_t kDlChunkMax = 32768;                  // most signals per chunk (grid.y of k_dl_residual)
-constexpr uint32_t kDlNone = 0xffffffffu;
 constexpr uint32_t kDlRankMax = 512;                    // longest list one wave rank-sorts (512^2 / 64 steps a lane); longer ones: k_dl_long
-constexpr uint32_t kDlLeft = 0x80000000u;                // usage bit: the atom had users but was left as it is
-
-struct DictLearnState {
-    unsigned char* index = nullptr;    // records (a host caller's), slot map, counts, offsets, partial sums, usage
-    size_t index_bytes = 0;
-    unsigned char* work = nullptr;     // the inverted index's lists, g [S][ldm], the residual block of a chunk, a host caller's signals
-    size_t work_bytes = 0;
-    unsigned char* vc = nullptr;       // apply: the changed atoms, contiguous
-    size_t vc_bytes = 0;
-};
-
-DictLearnState* state_of(ss_hip_ctx* ctx)
-{
-    if (!ctx->dl) ctx->dl = new DictLearnState();
-    return static_cast<DictLearnState*>(ctx->dl);
-}
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
@@ -273,25 +255,10 @@ void k_dl_residual(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* 
             d[e] = yv[j][e] - acc[j][e];
             q += (double)d[e] * (double)d[e];
         }
-        if (row0[j] < ldm) {
-            V out;
-            if constexpr (sizeof(T) == 4) out = V{ d[0], d[1], d[2], d[3] };
-            else out = V{ d[0], d[1] };
-            *reinterpret_cast<V*>(R + (size_t)b * ldm + row0[j]) = out;
-        }
+        if (row0[j] < ldm) cls_store<T>(R + (size_t)b * ldm + row0[j], d);
     }
     q = wave_sum(q);
     if (lane == 0u) part[((size_t)b * ntiles + tile) * 4u + wave] = q;
-}
-
-// first position in sb[lo .. hi) whose signal is >= b (the list is ascending)
-__device__ inline uint32_t dl_lower_bound(const uint32_t* __restrict__ sb, uint32_t lo, uint32_t hi, uint32_t b)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (sb[mid] < b) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
 }
 
 // the chunk holds signals b0 .. b1 - 1, R their residuals; cols == nullptr: atom s is column s
@@ -363,12 +330,7 @@ void k_dl_atoms(const T* __restrict__ At, uint32_t ldm, const uint32_t* __restri
     for (uint32_t j = 0; j < L; ++j) {
 #pragma unroll
         for (uint32_t e = 0; e < W; ++e) q += (double)acc[j][e] * (double)acc[j][e];
-        if (row0[j] < ldm) {
-            V out;
-            if constexpr (sizeof(T) == 4) out = V{ acc[j][0], acc[j][1], acc[j][2], acc[j][3] };
-            else out = V{ acc[j][0], acc[j][1] };
-            *reinterpret_cast<V*>(g + row0[j]) = out;
-        }
+        if (row0[j] < ldm) cls_store<T>(g + row0[j], acc[j]);
     }
     if (last) {
         q = wave_sum(q);
@@ -440,170 +402,74 @@ void k_dl_gather(const T* __restrict__ out, long long ors, long long ocs, const 
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
+// the index and the workspace: the common pieces (learn_driver.h), and the norm's partials, g and the residual block of a chunk
+template <typename T> struct DlIndex : LearnIndex<T> {
+    double* partg;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->head(cv, c, 1);
+        partg = cv.take<double>(c.S * c.per);
+        this->tail(cv, c);
+    }
+};
+
+template <typename T> struct DlWork : LearnWork<T> {
+    size_t chunk;
+    T *G, *R;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->lists(cv, c);
+        G = cv.take<T>(c.S * c.ldm);
+        R = cv.take<T>(chunk * c.ldm);
+        this->signals(cv, c, chunk);
+    }
+};
+
 template <typename T>
-int atom_update_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-                     const uint32_t* cols, size_t S, T* Vout, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage, double* objective, bool apply,
-                     char* err, size_t errlen)
+int atom_update_impl(LearnCall<T>& c)
 {
-    static const char* who = "atom_update";
-    HIPCHK(hipSetDevice(ctx->device));
-    DictLearnState* ds = state_of(ctx);
+    ss_hip_ctx* ctx = c.ctx;
+    int rc = learn_atoms(c);
+    if (rc != SS_HIP_OK) return rc;
     hipStream_t st = ctx->stream;
-    const size_t m = ctx->m, n = ctx->n, rb = record_bytes(kmax, sizeof(T));
-    const uint32_t ldm = ctx->ldm, ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), per = ntiles * 4u;
+    const size_t B = c.B, m = c.m, rb = c.rb;
+    const uint32_t Su = (uint32_t)c.S, Bu = (uint32_t)B, ldm = c.ldm, ntiles = c.ntiles, per = c.per;
     const T* At = static_cast<const T*>(ctx->At);
 
-    // ---- the list of atoms, on a host copy: nothing has been written when it fails ----
-    std::vector<uint32_t> hc;
-    if (cols) {
-        hc.resize(S);
-        if (on_device(cols)) HIPCHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
-        std::vector<uint32_t> sorted(hc);
-        std::sort(sorted.begin(), sorted.end());
-        if (sorted.back() >= n) { set_err(err, errlen, "atom_update: column index out of range"); return SS_HIP_EINVAL; }
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_err(err, errlen, "atom_update: a column is named twice"); return SS_HIP_EINVAL; }
-    } else {
-        S = n;
-    }
-    const uint32_t Su = (uint32_t)S, Bu = (uint32_t)B;
-    const bool rec_dev = on_device(records), y_dev = on_device(Y), v_dev = Vout != nullptr && on_device(Vout);
+    DlIndex<T> ix;
+    learn_carve(learn_arena(ctx).index, ix, c, "hipMalloc(atom learning index)");
+    if ((rc = learn_open(c, ix)) != SS_HIP_OK) return rc;
 
-    // ---- the index's fixed-size part ----
-    auto carve_index = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        unsigned char* rec = rec_dev ? nullptr : cv.take<unsigned char>(B * rb);
-        uint32_t* slot_of = cols ? cv.take<uint32_t>(n) : nullptr;
-        uint32_t* dcols = cols ? cv.take<uint32_t>(S) : nullptr;
-        uint32_t* counts = cv.take<uint32_t>(S);
-        uint32_t* off = cv.take<uint32_t>(S + 2);         // (+ the total, + the longest list)
-        uint32_t* bad = cv.take<uint32_t>(1);
-        double* part = cv.take<double>(B * per);
-        double* sig = cv.take<double>(B);
-        double* obj = cv.take<double>(1);
-        T* s2 = cv.take<T>(S);
-        double* partg = cv.take<double>(S * per);
-        uint32_t* dusage = cv.take<uint32_t>(S);
-        uint32_t* sel = cv.take<uint32_t>(2 * S);         // apply: positions of the changed atoms, then their columns
-        use(rec, slot_of, dcols, counts, off, bad, part, sig, obj, s2, partg, dusage, sel);
-        return cv.off;
-    };
-    grow(ds->index, ds->index_bytes, carve_index(nullptr, [](auto...) {}), "hipMalloc(atom update index)");
-
-    int rc = SS_HIP_OK;
-    carve_index(ds->index, [&](unsigned char* rec, uint32_t* slot_of, uint32_t* dcols, uint32_t* counts, uint32_t* off, uint32_t* bad,
-                               double* part, double* sig, double* obj, T* s2, double* partg, uint32_t* dusage, uint32_t* sel) {
-        const unsigned char* recs = static_cast<const unsigned char*>(records);
-        if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, B * rb, hipMemcpyHostToDevice, st)); recs = rec; }
-        std::vector<uint32_t> slots;
-        if (cols) {
-            slots.assign(n, kDlNone);
-            for (size_t s = 0; s < S; ++s) slots[hc[s]] = (uint32_t)s;
-            HIPCHK(hipMemcpyAsync(slot_of, slots.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dcols, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    // ---- the lists, g, the residual block of a chunk ----
+    DlWork<T> wk;
+    wk.chunk = learn_chunk(c);
+    learn_carve(learn_arena(ctx).work, wk, c, "hipMalloc(atom learning workspace)");
+    if (c.total != 0u)
+        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+                                  wk.sw, ix.s2, ix.bad));
+    std::vector<T> tmp;
+    if (c.total != 0u || c.objective) {
+        for (size_t b0 = 0; b0 < B; b0 += wk.chunk) {
+            const uint32_t Bc = (uint32_t)std::min(wk.chunk, B - b0);
+            const T* yd = c.Y + (ptrdiff_t)b0 * c.y_stride;
+            long long ys = c.y_stride, yi = c.incy;
+            if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, b0, Bc, tmp); yd = wk.ybuf; ys = (long long)m; yi = 1; }
+            HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, c.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
+            if (c.total != 0u) {
+                hipLaunchKernelGGL((k_dl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)ix.dcols,
+                                   (const uint32_t*)ix.off, (const uint32_t*)wk.sb, (const T*)wk.sw, (const T*)ix.s2, (const T*)wk.R, (uint32_t)b0,
+                                   (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, b0 + Bc >= B ? 1 : 0, wk.G, ix.partg);
+                HIPCHK(hipGetLastError());
+            }
         }
-        HIPCHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
-        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
-        hipLaunchKernelGGL((k_dl_count<false>), dim3(Bu), dim3(256), 0, st, recs, rb, kmax, (uint32_t)n, (const uint32_t*)slot_of, counts,
-                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, bad);
-        hipLaunchKernelGGL(k_dl_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)counts, Su, off);
-        HIPCHK(hipGetLastError());
-        uint32_t first_bad = kDlNone, tail[2] = { 0u, 0u };
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tail, off + S, sizeof(tail), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (the first host read: is a record invalid; how long are the lists)
-        const uint32_t total = tail[0], longest = tail[1];
-        if (first_bad != kDlNone) { rc = bad_index(first_bad, who, err, errlen); return; }
-
-        // ---- the lists, g, the residual block of a chunk ----
-        size_t chunk = std::max<size_t>(1, std::min<size_t>(kDlChunkMax, kDlChunkBytes / ((size_t)ldm * sizeof(T))));
-        if (ctx->dl_chunk_max > 0) chunk = std::min<size_t>(chunk, (size_t)ctx->dl_chunk_max);
-        chunk = std::min(chunk, B);
-        auto carve_work = [&](unsigned char* base, auto&& use) {
-            Carver cv(base);
-            uint32_t* pair_b = cv.take<uint32_t>(total);
-            uint32_t* pair_e = cv.take<uint32_t>(total);
-            uint32_t* sb = cv.take<uint32_t>(total);
-            T* sw = cv.take<T>(total);
-            T* G = cv.take<T>(S * ldm);
-            T* R = cv.take<T>(chunk * ldm);
-            T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
-            use(pair_b, pair_e, sb, sw, G, R, ybuf);
-            return cv.off;
-        };
-        grow(ds->work, ds->work_bytes, carve_work(nullptr, [](auto...) {}), "hipMalloc(atom update workspace)");
-        carve_work(ds->work, [&](uint32_t* pair_b, uint32_t* pair_e, uint32_t* sb, T* sw, T* G, T* R, T* ybuf) {
-            if (total != 0u) {
-                HIPCHK(hipMemsetAsync(counts, 0, S * sizeof(uint32_t), st));
-                hipLaunchKernelGGL((k_dl_count<true>), dim3(Bu), dim3(256), 0, st, recs, rb, kmax, (uint32_t)n, (const uint32_t*)slot_of, counts,
-                                   (const uint32_t*)off, pair_b, pair_e, bad);
-                hipLaunchKernelGGL((k_dl_sort<T>), dim3((Su + 3u) / 4u), dim3(256), 0, st, recs, rb, kmax, (const uint32_t*)off, Su,
-                                   (const uint32_t*)pair_b, (const uint32_t*)pair_e, sb, sw, s2);
-                if (longest > kDlRankMax)
-                    hipLaunchKernelGGL((k_dl_long<T>), dim3(Su), dim3(256), 0, st, recs, rb, kmax, Bu, (const uint32_t*)dcols, (const uint32_t*)off,
-                                       sb, sw, s2);
-                HIPCHK(hipGetLastError());
-            }
-            std::vector<T> tmp;
-            if (total != 0u || objective) {
-                for (size_t b0 = 0; b0 < B; b0 += chunk) {
-                    const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-                    const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-                    long long ys = y_stride, yi = incy;
-                    if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-                    hipLaunchKernelGGL((k_dl_residual<T>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, yd, ys, yi,
-                                       recs + b0 * rb, rb, kmax, R, part + b0 * per);
-                    if (total != 0u)
-                        hipLaunchKernelGGL((k_dl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)dcols,
-                                           (const uint32_t*)off, (const uint32_t*)sb, (const T*)sw, (const T*)s2, (const T*)R, (uint32_t)b0,
-                                           (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, b0 + Bc >= B ? 1 : 0, G, partg);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-            if (objective) {
-                hipLaunchKernelGGL(k_dl_signal_sums, dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const double*)part, per, Bu, sig);
-                hipLaunchKernelGGL(k_dl_objective, dim3(1), dim3(64), 0, st, (const double*)sig, Bu, obj);
-                HIPCHK(hipGetLastError());
-            }
-            // ---- norms, changed / unchanged, V: straight into a device V, else in place over g ([S][ldm]) ----
-            T* out = v_dev ? Vout : G;
-            const long long ors = v_dev ? (long long)rs : 1ll, ocs = v_dev ? (long long)cs : (long long)ldm;
-            hipLaunchKernelGGL((k_dl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)dcols, (const uint32_t*)off,
-                               (const T*)G, (const double*)partg, ntiles, out, ors, ocs, dusage);
-            HIPCHK(hipGetLastError());
-            if (objective) HIPCHK(hipMemcpyAsync(objective, obj, sizeof(double), hipMemcpyDefault, st));
-            if (usage) HIPCHK(hipMemcpyAsync(usage, dusage, S * sizeof(uint32_t), hipMemcpyDefault, st));
-            std::vector<uint32_t> hus;
-            if (apply) {
-                hus.resize(S);
-                HIPCHK(hipMemcpyAsync(hus.data(), dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            }
-            if (Vout && !v_dev) {
-                tmp.resize(S * m);
-                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), G, (size_t)ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (size_t s = 0; s < S; ++s)
-                    for (size_t i = 0; i < m; ++i) Vout[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs] = tmp[s * m + i];
-            }
-            HIPCHK(hipStreamSynchronize(st));
-            if (!apply) return;
-            // ---- apply: the changed atoms as a device column list + a contiguous device V, through the column replacement ----
-            std::vector<uint32_t> pos, ccols;
-            for (size_t s = 0; s < S; ++s)
-                if (hus[s] != 0u && (hus[s] & kDlLeft) == 0u) { pos.push_back((uint32_t)s); ccols.push_back(cols ? hc[s] : (uint32_t)s); }
-            if (pos.empty()) return;
-            const size_t nc = pos.size();
-            grow(ds->vc, ds->vc_bytes, nc * m * sizeof(T), "hipMalloc(atom update: changed atoms)");
-            T* Vc = reinterpret_cast<T*>(ds->vc);
-            HIPCHK(hipMemcpyAsync(sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_dl_gather<T>), dim3((uint32_t)nc), dim3(256), 0, st, (const T*)out, ors, ocs, (const uint32_t*)sel, (uint32_t)m, Vc);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-            rc = replace_columns_device<T>(ctx, sel + S, ccols, Vc, 1ll, (long long)m, err, errlen);
-        });
-    });
-    return rc;
+    }
+    if (c.objective) HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj));
+    // ---- norms, changed / unchanged, V: straight into a device V, else in place over g ([S][ldm]) ----
+    const LearnOut<T> out = learn_out(c, wk.G);
+    hipLaunchKernelGGL((k_dl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols, (const uint32_t*)ix.off,
+                       (const T*)wk.G, (const double*)ix.partg, ntiles, out.p, out.rs, out.cs, ix.dusage);
+    HIPCHK(hipGetLastError());
+    return learn_finish<T>(c, ix, 1, wk.G, out);
 }
 
 template <typename T>
@@ -611,23 +477,19 @@ int atom_update_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride,
                       const uint32_t* cols, size_t S, T* V, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage, double* objective, uint32_t apply,
                       char* err, size_t errlen)
 {
-    static const char* who = "atom_update";
-    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
-    if (rc != SS_HIP_OK) return rc;
-    if (!Y) { set_err(err, errlen, "atom_update: Y must not be null"); return SS_HIP_EINVAL; }
-    if (!V && apply == 0) { set_err(err, errlen, "atom_update: V must not be null unless the atoms are applied"); return SS_HIP_EINVAL; }
-    if (incy <= 0 || y_stride <= 0 || (V && (rs <= 0 || cs <= 0))) { set_err(err, errlen, "atom_update: increments and strides must be positive"); return SS_HIP_EINVAL; }
-    if (B == 0 || (cols && S == 0)) return SS_HIP_OK;         // (every argument above was checked all the same)
-    if (cols && S > ctx->n) { set_err(err, errlen, "atom_update: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
-    if (B >= 0x80000000ull || (unsigned long long)B * kmax >= 0xffffffffull) { set_err(err, errlen, "atom_update: B * kmax must stay below 2^32"); return SS_HIP_EINVAL; }
-    return guarded(err, errlen, who, [&] {
-        return atom_update_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, cols, S, V, rs, cs, usage, objective, apply != 0, err, errlen);
-    });
+    LearnCall<T> c{ ctx, "atom_update", Y, B, y_stride, incy, records, kmax, nullptr, cols, S, V, rs, cs, usage, objective, apply != 0, err, errlen };
+    LearnRules r{};
+    r.null_y = "Y must not be null";
+    if (!V && apply == 0) r.own = "V must not be null unless the atoms are applied";
+    bool empty = false;
+    const int rc = learn_check_args(c, r, empty);
+    if (rc != SS_HIP_OK || empty) return rc;
+    return guarded(err, errlen, c.who, [&] { return atom_update_impl<T>(c); });
 }
 
 }  // namespace
 
-// ---- the index and the residuals for the K-SVD sweep (ksvd.hip): the launches above on the context's stream, nothing else ----
+// ---- the launches of the kernels above on the context's stream, nothing else: the three learners' (learn_driver.h), this unit's included ----
 
 hipError_t dl_launch_count(ss_hip_ctx* ctx, const unsigned char* recs, size_t rb, uint32_t kmax, uint32_t B, const uint32_t* slot_of, uint32_t S,
                            uint32_t* counts, uint32_t* off, uint32_t* bad)
@@ -694,15 +556,20 @@ template hipError_t dl_launch_residuals<float>(ss_hip_ctx*, const float*, long l
 template hipError_t dl_launch_residuals<double>(ss_hip_ctx*, const double*, long long, long long, const unsigned char*, size_t, uint32_t, uint32_t,
                                                 double*, double*);
 
-void dictlearn_free(ss_hip_ctx* ctx)
+LearnArena& learn_arena(ss_hip_ctx* ctx)
 {
-    DictLearnState* ds = static_cast<DictLearnState*>(ctx->dl);
-    if (!ds) return;
-    if (ds->index) (void)hipFree(ds->index);
-    if (ds->work) (void)hipFree(ds->work);
-    if (ds->vc) (void)hipFree(ds->vc);
-    delete ds;
-    ctx->dl = nullptr;
+    if (!ctx->learn) ctx->learn = new LearnArena();
+    return *static_cast<LearnArena*>(ctx->learn);
+}
+
+void learn_free(ss_hip_ctx* ctx)
+{
+    if (!ctx->learn) return;
+    LearnArena& a = learn_arena(ctx);
+    for (WorkArena* w : { &a.index, &a.work, &a.vc })
+        if (w->buf) (void)hipFree(w->buf);
+    delete &a;
+    ctx->learn = nullptr;
 }
 
 }  // namespace sship

@@ -2904,14 +2904,12 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     if (ctx->c0_batch) (void)hipFree(ctx->c0_batch);
     sship::omp_gram_free(ctx);
     sship::classify_free(ctx);
-    sship::dictlearn_free(ctx);
+    sship::learn_free(ctx);
     sship::refit_free(ctx);
     sship::coherence_free(ctx);
-    sship::ksvd_free(ctx);
     sship::topcorr_free(ctx);
     sship::joint_free(ctx);
     sship::weighted_free(ctx);
-    sship::wdictlearn_free(ctx);
     if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
     if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
     sship::screen_free(ctx);

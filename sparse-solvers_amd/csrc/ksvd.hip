@@ -15,8 +15,8 @@
 // computes the level schedule from the inverted index (ks_levels.h) and the atoms run by (level, s): every level in parallel over its
 // atoms, three launches a level, back to back on the context's stream, no host synchronisation between levels.
 //
-//   dl_launch_*      the inverted index (atom -> (signal, value) in ascending (signal, position) order, sum w^2; the long-list path
-//                    above 512 users), the initial residuals and the objective's sums: dictlearn.hip's kernels, their words
+//   learn_*          the host steps the three learners share (learn_driver.h): checks, the atom list, the arena, the index, the copies
+//                    out and apply.  dl_launch_*: the inverted index, the initial residuals, the objective's sums: dictlearn.hip's words
 //   k_ks_g           phase 1, grid = (atom of the level, row tile of 1024).  The accumulator starts from (sum w^2) a_j and takes
 //                    w_b * R[b] of the atom's users in list order, eight rows in flight, writes g and the tile's sum of squares.
 //   k_ks_norm        phase 2, one workgroup per atom of the level: ||g||_2 from the partials, the verdict, usage, v (or the stored
@@ -24,7 +24,7 @@
 //   k_ks_pairs       phase 3, one workgroup per (atom, user) pair of the level: t_b over the row (first pass), w'_b, the residual
 //                    update (second pass over the row: an L2 hit), the store of w'_b into the output record.
 //   k_ks_resnorm     grid = (signal, row tile): the tile's sums of squares of the final residuals, for the objective after.
-//   k_ks_vout / k_ks_gather   V through the caller's strides; the changed atoms, contiguous, for the column replacement.
+//   k_ks_vout        V through a device caller's strides.
 //
 // SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately):
 //   r_b, sum w^2, the objective   dictlearn.hip's words (r_b,i = y_b,i - acc_i; sum w^2 in double, ascending b, rounded once to T);
@@ -44,7 +44,7 @@
 // of the unscaled call times 2^b (the coefficients of unit atoms), the objectives times 2^2b, as long as sum w^2 (2^(2b-2a)),
 // (sum w^2) a_ij and w_b r_b,i (2^(2b-a)) are normal numbers of the context's precision and ||g||^2 (2^(4b-2a)) of double.
 #include "ss_hip_internal.h"
-#include "record_common.h"
+#include "learn_driver.h"
 #include "ks_levels.h"
 
 #include <algorithm>
@@ -55,37 +55,7 @@ namespace sship {
 
 namespace {
 
-constexpr uint32_t kKsNone = 0xffffffffu;
-constexpr uint32_t kKsLeft = 0x80000000u;                // usage bit: the atom had users but was left as it is
 constexpr uint32_t kKsResidualRows = 32768;              // most signals per launch of the residual kernel (its grid.y)
-
-struct KsvdState {
-    unsigned char* index = nullptr;    // records (a host caller's), slot map, counts, offsets, partial sums, usage, verdicts, the schedule's atoms
-    size_t index_bytes = 0;
-    unsigned char* work = nullptr;     // the lists, the schedule's pairs, g / v [S][ldm], the residual block [B][ldm], a host caller's signals
-    size_t work_bytes = 0;
-    unsigned char* vc = nullptr;       // apply: the changed atoms, contiguous
-    size_t vc_bytes = 0;
-};
-
-KsvdState* state_of(ss_hip_ctx* ctx)
-{
-    if (!ctx->ks) ctx->ks = new KsvdState();
-    return static_cast<KsvdState*>(ctx->ks);
-}
-
-__device__ inline void store_val(unsigned char* p, uint32_t e, float v) { reinterpret_cast<float*>(p)[e] = v; }
-__device__ inline void store_val(unsigned char* p, uint32_t e, double v)
-{
-    uint32_t* w = reinterpret_cast<uint32_t*>(p) + 2u * e;       // (4-byte aligned only when kmax is odd: record_common.h, load_val)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    w[0] = (uint32_t)u;
-    w[1] = (uint32_t)(u >> 32);
-}
-
-template <typename T> __device__ inline typename ClsVec<T>::type ks_pack(const T* d);
-template <> __device__ inline float4 ks_pack<float>(const float* d) { return float4{ d[0], d[1], d[2], d[3] }; }
-template <> __device__ inline double2 ks_pack<double>(const double* d) { return double2{ d[0], d[1] }; }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
@@ -150,7 +120,7 @@ void k_ks_g(const T* __restrict__ At, uint32_t ldm, const uint32_t* __restrict__
     for (uint32_t j = 0; j < L; ++j) {
 #pragma unroll
         for (uint32_t e = 0; e < W; ++e) q += (double)acc[j][e] * (double)acc[j][e];
-        if (row0[j] < ldm) *reinterpret_cast<V*>(g + row0[j]) = ks_pack<T>(acc[j]);
+        if (row0[j] < ldm) *reinterpret_cast<V*>(g + row0[j]) = cls_pack<T>(acc[j]);
     }
     q = wave_sum(q);
     if (lane == 0u) partg[((size_t)s * ntiles + tile) * 4u + wave] = q;
@@ -180,7 +150,7 @@ void k_ks_norm(const T* __restrict__ At, uint32_t ldm, uint32_t m, const uint32_
         }
         s_norm = nrm;
         s_ok = ok;
-        usage[s] = cnt != 0u && ok == 0u ? (cnt | kKsLeft) : cnt;
+        usage[s] = cnt != 0u && ok == 0u ? (cnt | kDlLeft) : cnt;
         verdict[s] = ok;
     }
     __syncthreads();
@@ -204,7 +174,7 @@ void k_ks_norm(const T* __restrict__ At, uint32_t ldm, uint32_t m, const uint32_
                 d[e] = row0 + e < m ? (ok ? vget(gv, e) / nrm : vget(a, e)) : T(0);
                 if (row0 + e < m) q += (double)vget(a, e) * (double)d[e];
             }
-            *reinterpret_cast<V*>(g + row0) = ks_pack<T>(d);
+            *reinterpret_cast<V*>(g + row0) = cls_pack<T>(d);
         }
         q = wave_sum(q);
         if (lane == 0u) rp[tile * 4u + wave] = q;
@@ -272,7 +242,7 @@ void k_ks_pairs(const T* __restrict__ At, uint32_t ldm, uint32_t m, const uint32
             T d[W];
 #pragma unroll
             for (uint32_t e = 0; e < W; ++e) d[e] = row0 + e < m ? (vget(rv, e) + w * vget(av, e)) - wn * vget(vv, e) : T(0);
-            *reinterpret_cast<V*>(r + row0) = ks_pack<T>(d);
+            *reinterpret_cast<V*>(r + row0) = cls_pack<T>(d);
         }
     }
     unsigned char* ro = rec_out + (size_t)b * rb;
@@ -317,233 +287,144 @@ void k_ks_vout(const T* __restrict__ Vw, uint32_t ldm, uint32_t m, T* __restrict
     for (uint32_t i = threadIdx.x; i < m; i += 256u) out[(long long)i * ors + (long long)s * ocs] = Vw[(size_t)s * ldm + i];
 }
 
-// Vc[p][0 .. m) = Vw[sel[p]] (the changed atoms, contiguous, for the column replacement)
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_ks_gather(const T* __restrict__ Vw, uint32_t ldm, const uint32_t* __restrict__ sel, uint32_t m, T* __restrict__ Vc)
-{
-    const uint32_t p = blockIdx.x;
-    const T* src = Vw + (size_t)sel[p] * ldm;
-    for (uint32_t i = threadIdx.x; i < m; i += 256u) Vc[(size_t)p * m + i] = src[i];
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-template <typename T>
-int ksvd_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
-              const uint32_t* cols, size_t S, T* Vout, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage, double* objective, uint32_t flags,
-              char* err, size_t errlen)
-{
-    static const char* who = "ksvd_sweep";
-    HIPCHK(hipSetDevice(ctx->device));
-    KsvdState* ks = state_of(ctx);
-    hipStream_t st = ctx->stream;
-    const size_t m = ctx->m, n = ctx->n, rb = record_bytes(kmax, sizeof(T));
-    const uint32_t ldm = ctx->ldm, ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), per = ntiles * 4u;
-    const T* At = static_cast<const T*>(ctx->At);
-    const bool apply = (flags & SS_HIP_KSVD_APPLY) != 0u, serial = (flags & SS_HIP_KSVD_SERIAL) != 0u;
-
-    // ---- the list of atoms, on a host copy: nothing has been written when it fails ----
-    std::vector<uint32_t> hc;
-    if (cols) {
-        hc.resize(S);
-        if (on_device(cols)) HIPCHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
-        std::vector<uint32_t> sorted(hc);
-        std::sort(sorted.begin(), sorted.end());
-        if (sorted.back() >= n) { set_err(err, errlen, "ksvd_sweep: column index out of range"); return SS_HIP_EINVAL; }
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_err(err, errlen, "ksvd_sweep: a column is named twice"); return SS_HIP_EINVAL; }
-    } else {
-        S = n;
+// the index and the workspace: the common pieces (learn_driver.h), and the partials of ||g||^2 and rho, rho, the verdicts, the atoms
+// by (level, s); g / v and the residual block of ALL signals (an atom needs all its users at once)
+template <typename T> struct KsIndex : LearnIndex<T> {
+    double *partg, *rho_part, *rho;
+    uint32_t *verdict, *order;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->head(cv, c, 2);
+        partg = cv.take<double>(c.S * c.per);
+        rho_part = cv.take<double>(c.S * c.per);
+        rho = cv.take<double>(c.S);
+        this->dusage = cv.take<uint32_t>(c.S);
+        verdict = cv.take<uint32_t>(c.S);
+        order = cv.take<uint32_t>(c.S);
+        this->sel = cv.take<uint32_t>(2 * c.S);          // apply: positions of the changed atoms, then their columns
     }
-    const uint32_t Su = (uint32_t)S, Bu = (uint32_t)B;
-    const bool in_dev = on_device(records), out_dev = on_device(records_out), y_dev = on_device(Y), v_dev = Vout != nullptr && on_device(Vout);
+};
 
-    // ---- the index's fixed-size part ----
-    auto carve_index = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        unsigned char* stage = (in_dev && out_dev) ? nullptr : cv.take<unsigned char>(B * rb);
-        uint32_t* slot_of = cols ? cv.take<uint32_t>(n) : nullptr;
-        uint32_t* dcols = cols ? cv.take<uint32_t>(S) : nullptr;
-        uint32_t* counts = cv.take<uint32_t>(S);
-        uint32_t* off = cv.take<uint32_t>(S + 2);         // (+ the total, + the longest list)
-        uint32_t* bad = cv.take<uint32_t>(1);
-        double* part = cv.take<double>(B * per);
-        double* sig = cv.take<double>(B);
-        double* obj = cv.take<double>(2);
-        T* s2 = cv.take<T>(S);
-        double* partg = cv.take<double>(S * per);
-        double* rho_part = cv.take<double>(S * per);
-        double* rho = cv.take<double>(S);
-        uint32_t* dusage = cv.take<uint32_t>(S);
-        uint32_t* verdict = cv.take<uint32_t>(S);
-        uint32_t* order = cv.take<uint32_t>(S);           // the atoms by (level, s)
-        uint32_t* sel = cv.take<uint32_t>(2 * S);         // apply: positions of the changed atoms, then their columns
-        use(stage, slot_of, dcols, counts, off, bad, part, sig, obj, s2, partg, rho_part, rho, dusage, verdict, order, sel);
-        return cv.off;
-    };
-    grow(ks->index, ks->index_bytes, carve_index(nullptr, [](auto...) {}), "hipMalloc(ksvd sweep index)");
+// (pair_b / pair_e: scratch of the index; then the schedule: the pairs' atoms and their list positions, by (level, s, b))
+template <typename T> struct KsWork : LearnWork<T> {
+    T *G, *R;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->lists(cv, c);
+        G = cv.take<T>(c.S * c.ldm);
+        R = cv.take<T>(c.B * c.ldm);
+        this->signals(cv, c, c.B);
+    }
+};
 
-    int rc = SS_HIP_OK;
-    carve_index(ks->index, [&](unsigned char* stage, uint32_t* slot_of, uint32_t* dcols, uint32_t* counts, uint32_t* off, uint32_t* bad,
-                               double* part, double* sig, double* obj, T* s2, double* partg, double* rho_part, double* rho, uint32_t* dusage,
-                               uint32_t* verdict, uint32_t* order, uint32_t* sel) {
-        // din: the input records on the device; dout: where the output records are written there (a host caller's: the staging,
-        // in place when the input is staged too)
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-        unsigned char* dout = out_dev ? static_cast<unsigned char*>(records_out) : stage;
-        if (cols) {
-            std::vector<uint32_t> slots(n, kKsNone);
-            for (size_t s = 0; s < S; ++s) slots[hc[s]] = (uint32_t)s;
-            HIPCHK(hipMemcpyAsync(slot_of, slots.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dcols, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));            // (slots leaves scope)
-        }
-        HIPCHK(dl_launch_count(ctx, din, rb, kmax, Bu, slot_of, Su, counts, off, bad));
-        uint32_t first_bad = kKsNone, tail[2] = { 0u, 0u };
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tail, off + S, sizeof(tail), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (the first host read: is a record invalid; how long are the lists)
-        const uint32_t total = tail[0], longest = tail[1];
-        if (first_bad != kKsNone) { rc = bad_index(first_bad, who, err, errlen); return; }
+template <typename T>
+int ksvd_impl(LearnCall<T>& c, bool serial)
+{
+    ss_hip_ctx* ctx = c.ctx;
+    int rc = learn_atoms(c);
+    if (rc != SS_HIP_OK) return rc;
+    hipStream_t st = ctx->stream;
+    const size_t B = c.B, S = c.S, m = c.m, rb = c.rb;
+    const uint32_t Su = (uint32_t)S, Bu = (uint32_t)B, ldm = c.ldm, ntiles = c.ntiles, per = c.per;
+    const T* At = static_cast<const T*>(ctx->At);
 
-        // ---- the lists, the schedule's pairs, g / v, the residual block of ALL signals (an atom needs all its users at once) ----
-        auto carve_work = [&](unsigned char* base, auto&& use) {
-            Carver cv(base);
-            uint32_t* pair_b = cv.take<uint32_t>(total);  // (scratch of the index; then the schedule: the pairs' atoms ...
-            uint32_t* pair_e = cv.take<uint32_t>(total);  //  ... and their list positions, by (level, s, b))
-            uint32_t* sb = cv.take<uint32_t>(total);
-            T* sw = cv.take<T>(total);
-            T* G = cv.take<T>(S * ldm);
-            T* R = cv.take<T>(B * ldm);
-            T* ybuf = y_dev ? nullptr : cv.take<T>(B * m);
-            use(pair_b, pair_e, sb, sw, G, R, ybuf);
-            return cv.off;
-        };
-        const size_t need = carve_work(nullptr, [](auto...) {});
-        try {
-            grow(ks->work, ks->work_bytes, need, "hipMalloc(ksvd sweep workspace)");
-        } catch (const HipFail& f) {
-            if (f.code != hipErrorOutOfMemory) throw;
-            (void)hipGetLastError();
-            set_err(err, errlen, std::string(who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes (the residual block of all " +
+    KsIndex<T> ix;
+    learn_carve(learn_arena(ctx).index, ix, c, "hipMalloc(atom learning index)");
+    if ((rc = learn_open(c, ix)) != SS_HIP_OK) return rc;
+    const uint32_t total = c.total;
+
+    KsWork<T> wk;
+    const size_t need = learn_bytes(wk, c);
+    try {
+        learn_carve(learn_arena(ctx).work, wk, c, "hipMalloc(atom learning workspace)");
+    } catch (const HipFail& f) {
+        if (f.code != hipErrorOutOfMemory) throw;
+        (void)hipGetLastError();
+        set_err(c.err, c.errlen, std::string(c.who) + ": no device memory for a workspace of " + std::to_string(need) + " bytes (the residual block of all " +
                                      std::to_string(B) + " signals, " + std::to_string(B * (size_t)ldm * sizeof(T)) + " bytes, must be resident)");
-            rc = SS_HIP_ENOMEM;
-            return;
+        return SS_HIP_ENOMEM;
+    }
+
+    // ---- the lists; the schedule on the host from their offsets and signals ----
+    std::vector<uint32_t> hoff(S + 1, 0u), hsb(total);
+    if (total != 0u) {
+        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+                                  wk.sw, ix.s2, ix.bad));
+        HIPCHK(hipMemcpyAsync(hoff.data(), ix.off, (S + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hsb.data(), wk.sb, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (uint32_t p = 0; p < total; ++p)
+            if (hsb[p] >= Bu) { set_err(c.err, c.errlen, "ksvd_sweep: internal error (a list names a signal >= B)"); return SS_HIP_ERUNTIME; }
+        const size_t dup = ks_first_duplicate(hoff.data(), hsb.data(), S);
+        if (dup != S) {
+            set_err(c.err, c.errlen, std::string(c.who) + ": column " + std::to_string(c.cols ? c.hc[dup] : (uint32_t)dup) + " is listed twice in one record");
+            return SS_HIP_EINVAL;
         }
-        carve_work(ks->work, [&](uint32_t* pair_b, uint32_t* pair_e, uint32_t* sb, T* sw, T* G, T* R, T* ybuf) {
-            // ---- the lists; the schedule on the host from their offsets and signals ----
-            std::vector<uint32_t> hoff(S + 1, 0u), hsb(total);
-            if (total != 0u) {
-                HIPCHK(dl_launch_lists<T>(ctx, din, rb, kmax, Bu, slot_of, dcols, Su, counts, off, longest, pair_b, pair_e, sb, sw, s2, bad));
-                HIPCHK(hipMemcpyAsync(hoff.data(), off, (S + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipMemcpyAsync(hsb.data(), sb, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (uint32_t p = 0; p < total; ++p)
-                    if (hsb[p] >= Bu) { set_err(err, errlen, "ksvd_sweep: internal error (a list names a signal >= B)"); rc = SS_HIP_ERUNTIME; return; }
-                const size_t dup = ks_first_duplicate(hoff.data(), hsb.data(), S);
-                if (dup != S) {
-                    set_err(err, errlen, std::string(who) + ": column " + std::to_string(cols ? hc[dup] : (uint32_t)dup) + " is listed twice in one record");
-                    rc = SS_HIP_EINVAL;
-                    return;
-                }
+    }
+    std::vector<uint32_t> level, horder, first;
+    const uint32_t nlevels = ks_levels(hoff.data(), hsb.data(), S, B, serial, level);
+    ks_order(level, nlevels, horder, first);
+    std::vector<uint32_t> hps(total), hpp(total), pfirst((size_t)nlevels + 1u, 0u);
+    {
+        uint32_t q = 0;
+        for (uint32_t l = 0; l < nlevels; ++l) {
+            pfirst[l] = q;
+            for (uint32_t i = first[l]; i < first[l + 1u]; ++i) {
+                const uint32_t s = horder[i];
+                for (uint32_t p = hoff[s]; p < hoff[s + 1u]; ++p) { hps[q] = s; hpp[q] = p; ++q; }
             }
-            std::vector<uint32_t> level, horder, first;
-            const uint32_t nlevels = ks_levels(hoff.data(), hsb.data(), S, B, serial, level);
-            ks_order(level, nlevels, horder, first);
-            std::vector<uint32_t> hps(total), hpp(total), pfirst((size_t)nlevels + 1u, 0u);
-            {
-                uint32_t q = 0;
-                for (uint32_t l = 0; l < nlevels; ++l) {
-                    pfirst[l] = q;
-                    for (uint32_t i = first[l]; i < first[l + 1u]; ++i) {
-                        const uint32_t s = horder[i];
-                        for (uint32_t p = hoff[s]; p < hoff[s + 1u]; ++p) { hps[q] = s; hpp[q] = p; ++q; }
-                    }
-                }
-                pfirst[nlevels] = q;
-            }
-            HIPCHK(hipMemcpyAsync(order, horder.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            if (total != 0u) {
-                HIPCHK(hipMemcpyAsync(pair_b, hps.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                HIPCHK(hipMemcpyAsync(pair_e, hpp.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            }
+        }
+        pfirst[nlevels] = q;
+    }
+    HIPCHK(hipMemcpyAsync(ix.order, horder.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (total != 0u) {
+        HIPCHK(hipMemcpyAsync(wk.pair_b, hps.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(wk.pair_e, hpp.data(), (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
 
-            // ---- the initial residuals and the objective before; from here on outputs are written ----
-            std::vector<T> tmp;
-            const T* yd = Y;
-            long long ysd = y_stride, yid = incy;
-            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, 0, B, tmp); yd = ybuf; ysd = (long long)m; yid = 1; }
-            for (size_t b0 = 0; b0 < B; b0 += kKsResidualRows) {
-                const uint32_t Bc = (uint32_t)std::min<size_t>(kKsResidualRows, B - b0);
-                HIPCHK(dl_launch_residuals<T>(ctx, yd + (ptrdiff_t)b0 * ysd, ysd, yid, din + b0 * rb, rb, kmax, Bc, R + b0 * ldm, part + b0 * per));
-            }
-            if (objective) HIPCHK(dl_launch_objective(ctx, part, per, Bu, sig, obj));
-            if (dout != din) HIPCHK(hipMemcpyAsync(dout, din, B * rb, hipMemcpyDeviceToDevice, st));
+    // ---- the initial residuals and the objective before; from here on outputs are written ----
+    std::vector<T> tmp;
+    const T* yd = c.Y;
+    long long ysd = c.y_stride, yid = c.incy;
+    if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, 0, B, tmp); yd = wk.ybuf; ysd = (long long)m; yid = 1; }
+    for (size_t b0 = 0; b0 < B; b0 += kKsResidualRows) {
+        const uint32_t Bc = (uint32_t)std::min<size_t>(kKsResidualRows, B - b0);
+        HIPCHK(dl_launch_residuals<T>(ctx, yd + (ptrdiff_t)b0 * ysd, ysd, yid, c.din + b0 * rb, rb, c.kmax, Bc, wk.R + b0 * ldm, ix.part + b0 * per));
+    }
+    if (c.objective) HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj));
+    if (c.dout != c.din) HIPCHK(hipMemcpyAsync(c.dout, c.din, B * rb, hipMemcpyDeviceToDevice, st));
 
-            // ---- the levels: three launches each, back to back ----
-            for (uint32_t l = 0; l < nlevels; ++l) {
-                const uint32_t na = first[l + 1u] - first[l], np = pfirst[l + 1u] - pfirst[l];
-                if (na == 0u) continue;
-                if (np != 0u)
-                    hipLaunchKernelGGL((k_ks_g<T>), dim3(na, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)dcols,
-                                       (const uint32_t*)(order + first[l]), (const uint32_t*)off, (const uint32_t*)sb, (const T*)sw, (const T*)s2,
-                                       (const T*)R, G, partg);
-                hipLaunchKernelGGL((k_ks_norm<T>), dim3(na), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)dcols,
-                                   (const uint32_t*)(order + first[l]), (const uint32_t*)off, G, (const double*)partg, ntiles, rho_part, rho, dusage,
-                                   verdict);
-                if (np != 0u)
-                    hipLaunchKernelGGL((k_ks_pairs<T>), dim3(np), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)dcols,
-                                       (const uint32_t*)(pair_b + pfirst[l]), (const uint32_t*)(pair_e + pfirst[l]), (const uint32_t*)sb, (const T*)sw,
-                                       (const T*)G, (const double*)rho, (const uint32_t*)verdict, R, dout, rb, kmax, ntiles);
-                HIPCHK(hipGetLastError());
-            }
+    // ---- the levels: three launches each, back to back ----
+    for (uint32_t l = 0; l < nlevels; ++l) {
+        const uint32_t na = first[l + 1u] - first[l], np = pfirst[l + 1u] - pfirst[l];
+        if (na == 0u) continue;
+        if (np != 0u)
+            hipLaunchKernelGGL((k_ks_g<T>), dim3(na, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)ix.dcols,
+                               (const uint32_t*)(ix.order + first[l]), (const uint32_t*)ix.off, (const uint32_t*)wk.sb, (const T*)wk.sw, (const T*)ix.s2,
+                               (const T*)wk.R, wk.G, ix.partg);
+        hipLaunchKernelGGL((k_ks_norm<T>), dim3(na), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols,
+                           (const uint32_t*)(ix.order + first[l]), (const uint32_t*)ix.off, wk.G, (const double*)ix.partg, ntiles, ix.rho_part, ix.rho,
+                           ix.dusage, ix.verdict);
+        if (np != 0u)
+            hipLaunchKernelGGL((k_ks_pairs<T>), dim3(np), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols,
+                               (const uint32_t*)(wk.pair_b + pfirst[l]), (const uint32_t*)(wk.pair_e + pfirst[l]), (const uint32_t*)wk.sb, (const T*)wk.sw,
+                               (const T*)wk.G, (const double*)ix.rho, (const uint32_t*)ix.verdict, wk.R, c.dout, rb, c.kmax, ntiles);
+        HIPCHK(hipGetLastError());
+    }
 
-            // ---- the objective after, V, usage, the records ----
-            if (objective) {
-                hipLaunchKernelGGL((k_ks_resnorm<T>), dim3(Bu, ntiles), dim3(kClsThreads), 0, st, (const T*)R, ldm, din, rb, kmax, part);
-                HIPCHK(hipGetLastError());
-                HIPCHK(dl_launch_objective(ctx, part, per, Bu, sig, obj + 1));
-                HIPCHK(hipMemcpyAsync(objective, obj, 2 * sizeof(double), hipMemcpyDefault, st));
-            }
-            if (v_dev) {
-                hipLaunchKernelGGL((k_ks_vout<T>), dim3(Su), dim3(256), 0, st, (const T*)G, ldm, (uint32_t)m, Vout, (long long)rs, (long long)cs);
-                HIPCHK(hipGetLastError());
-            }
-            if (usage) HIPCHK(hipMemcpyAsync(usage, dusage, S * sizeof(uint32_t), hipMemcpyDefault, st));
-            std::vector<uint32_t> hus;
-            if (apply) {
-                hus.resize(S);
-                HIPCHK(hipMemcpyAsync(hus.data(), dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            }
-            if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
-            if (Vout && !v_dev) {
-                tmp.resize(S * m);
-                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), G, (size_t)ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (size_t s = 0; s < S; ++s)
-                    for (size_t i = 0; i < m; ++i) Vout[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs] = tmp[s * m + i];
-            }
-            HIPCHK(hipStreamSynchronize(st));
-            if (!apply) return;
-            // ---- apply: the changed atoms as a device column list + a contiguous device V, through the column replacement ----
-            std::vector<uint32_t> pos, ccols;
-            for (size_t s = 0; s < S; ++s)
-                if (hus[s] != 0u && (hus[s] & kKsLeft) == 0u) { pos.push_back((uint32_t)s); ccols.push_back(cols ? hc[s] : (uint32_t)s); }
-            if (pos.empty()) return;
-            const size_t nc = pos.size();
-            grow(ks->vc, ks->vc_bytes, nc * m * sizeof(T), "hipMalloc(ksvd sweep: changed atoms)");
-            T* Vc = reinterpret_cast<T*>(ks->vc);
-            HIPCHK(hipMemcpyAsync(sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL((k_ks_gather<T>), dim3((uint32_t)nc), dim3(256), 0, st, (const T*)G, ldm, (const uint32_t*)sel, (uint32_t)m, Vc);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-            rc = replace_columns_device<T>(ctx, sel + S, ccols, Vc, 1ll, (long long)m, err, errlen);
-        });
-    });
-    return rc;
+    // ---- the objective after, V in a device caller's strides; the copies out and apply from v in place over g ([S][ldm]) ----
+    if (c.objective) {
+        hipLaunchKernelGGL((k_ks_resnorm<T>), dim3(Bu, ntiles), dim3(kClsThreads), 0, st, (const T*)wk.R, ldm, c.din, rb, c.kmax, ix.part);
+        HIPCHK(hipGetLastError());
+        HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj + 1));
+    }
+    if (c.v_dev) {
+        hipLaunchKernelGGL((k_ks_vout<T>), dim3(Su), dim3(256), 0, st, (const T*)wk.G, ldm, (uint32_t)m, c.V, (long long)c.rs, (long long)c.cs);
+        HIPCHK(hipGetLastError());
+    }
+    return learn_finish<T>(c, ix, 2, wk.G, LearnOut<T>{ wk.G, 1ll, (long long)ldm });
 }
 
 template <typename T>
@@ -551,42 +432,21 @@ int ksvd_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdif
                const uint32_t* cols, size_t S, T* V, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage, double* objective, uint32_t flags, char* err,
                size_t errlen)
 {
-    static const char* who = "ksvd_sweep";
-    const int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
-    if (rc != SS_HIP_OK) return rc;
-    if (!Y || !records_out) { set_err(err, errlen, "ksvd_sweep: Y and records_out must not be null"); return SS_HIP_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "ksvd_sweep: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
-    if (flags & ~(uint32_t)(SS_HIP_KSVD_APPLY | SS_HIP_KSVD_SERIAL)) { set_err(err, errlen, "ksvd_sweep: unknown flag bit"); return SS_HIP_EINVAL; }
-    if (!V && !(flags & SS_HIP_KSVD_APPLY) && !usage && !objective) {
-        set_err(err, errlen, "ksvd_sweep: nothing asked for (V, usage and objective are null and the atoms are not applied)");
-        return SS_HIP_EINVAL;
-    }
-    if (incy <= 0 || y_stride <= 0 || (V && (rs <= 0 || cs <= 0))) { set_err(err, errlen, "ksvd_sweep: increments and strides must be positive"); return SS_HIP_EINVAL; }
-    if (B >= 0x80000000ull || (unsigned long long)B * kmax >= 0xffffffffull) { set_err(err, errlen, "ksvd_sweep: B * kmax must stay below 2^32"); return SS_HIP_EINVAL; }
-    if (records_out != records) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(records), b = reinterpret_cast<uintptr_t>(records_out);
-        const size_t bytes = B * record_bytes(kmax, sizeof(T));
-        if (a < b + bytes && b < a + bytes) { set_err(err, errlen, "ksvd_sweep: records and records_out overlap in part"); return SS_HIP_EINVAL; }
-    }
-    if (B == 0 || (cols && S == 0)) return SS_HIP_OK;         // (every argument above was checked all the same)
-    if (cols && S > ctx->n) { set_err(err, errlen, "ksvd_sweep: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
-    return guarded(err, errlen, who, [&] {
-        return ksvd_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, records_out, cols, S, V, rs, cs, usage, objective, flags, err, errlen);
-    });
+    const bool apply = (flags & SS_HIP_KSVD_APPLY) != 0u;
+    LearnCall<T> c{ ctx, "ksvd_sweep", Y, B, y_stride, incy, records, kmax, records_out, cols, S, V, rs, cs, usage, objective, apply, err, errlen };
+    LearnRules r{};
+    r.null_y = "Y and records_out must not be null";
+    if (!records_out) r.own = r.null_y;
+    r.flags = flags;
+    r.mask = SS_HIP_KSVD_APPLY | SS_HIP_KSVD_SERIAL;
+    if (!V && !apply && !usage && !objective) r.nothing = "nothing asked for (V, usage and objective are null and the atoms are not applied)";
+    bool empty = false;
+    const int rc = learn_check_args(c, r, empty);
+    if (rc != SS_HIP_OK || empty) return rc;
+    return guarded(err, errlen, c.who, [&] { return ksvd_impl<T>(c, (flags & SS_HIP_KSVD_SERIAL) != 0u); });
 }
 
 }  // namespace
-
-void ksvd_free(ss_hip_ctx* ctx)
-{
-    KsvdState* ks = static_cast<KsvdState*>(ctx->ks);
-    if (!ks) return;
-    if (ks->index) (void)hipFree(ks->index);
-    if (ks->work) (void)hipFree(ks->work);
-    if (ks->vc) (void)hipFree(ks->vc);
-    delete ks;
-    ctx->ks = nullptr;
-}
 
 }  // namespace sship
 

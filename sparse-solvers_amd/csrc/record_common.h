@@ -1,6 +1,6 @@
 // What the translation units that read compact records share (classify.hip, dictlearn.hip): the 1024-row register tile of the
-// streaming kernels and its fixed reduction order, the entry points' common checks, and the host helpers around a chunked workspace
-// (grow, Carver, upload_rows).  Errors, pointers and the record's size come from host_common.h.
+// streaming kernels and its fixed reduction order, a record's values read and written, the entry points' common checks, and the host
+// helpers around a chunked workspace (grow, Carver, upload_rows).  Errors, pointers and the record's size come from host_common.h.
 // Everything sits in an unnamed namespace: each unit gets its own copy, nothing here is part of the library's link surface.
 #pragma once
 
@@ -49,11 +49,49 @@ __device__ inline double load_val(const unsigned char* p, uint32_t e, double)
     return __longlong_as_double((long long)(((unsigned long long)w[1] << 32) | w[0]));
 }
 
+__device__ inline void store_val(unsigned char* p, uint32_t e, float v) { reinterpret_cast<float*>(p)[e] = v; }
+__device__ inline void store_val(unsigned char* p, uint32_t e, double v)
+{
+    uint32_t* w = reinterpret_cast<uint32_t*>(p) + 2u * e;
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    w[0] = (uint32_t)u;
+    w[1] = (uint32_t)(u >> 32);
+}
+
 template <typename T> struct ClsVec;
 template <> struct ClsVec<float> { typedef float4 type; static constexpr uint32_t W = 4, L = 1; };
 template <> struct ClsVec<double> { typedef double2 type; static constexpr uint32_t W = 2, L = 2; };
 __device__ inline float vget(const float4& v, uint32_t e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 __device__ inline double vget(const double2& v, uint32_t e) { return e == 0 ? v.x : v.y; }
+
+// a thread's W values of the register tile: stored as one vector at dst (16-byte aligned), or as the vector itself.  cls_store packs
+// into a local that it then copies out: in that form the compiler keeps the pair / quad as one vector up to a single 16-byte store
+template <typename T> __device__ inline void cls_store(T* dst, const T* d)
+{
+    typename ClsVec<T>::type out;
+    if constexpr (sizeof(T) == 4) out = typename ClsVec<T>::type{ d[0], d[1], d[2], d[3] };
+    else out = typename ClsVec<T>::type{ d[0], d[1] };
+    *reinterpret_cast<typename ClsVec<T>::type*>(dst) = out;
+}
+template <typename T> __device__ inline typename ClsVec<T>::type cls_pack(const T* d)
+{
+    typename ClsVec<T>::type out;
+    cls_store<T>(reinterpret_cast<T*>(&out), d);
+    return out;
+}
+
+// the atom learners' words (dictlearn.hip, ksvd.hip, wdictlearn.hip): a column that is not requested; the usage bit of an atom that
+// had users but was left as it is; the first position in sb[lo .. hi) whose signal is >= b (an atom's list is ascending)
+constexpr uint32_t kDlNone = 0xffffffffu;
+constexpr uint32_t kDlLeft = 0x80000000u;
+__device__ inline uint32_t dl_lower_bound(const uint32_t* __restrict__ sb, uint32_t lo, uint32_t hi, uint32_t b)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (sb[mid] < b) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
 
 __device__ inline double wave_sum(double s)
 {

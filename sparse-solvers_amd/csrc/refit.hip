@@ -99,15 +99,6 @@ template <> struct RfMma<double> {
     __device__ static uint32_t slot(uint32_t ri, uint32_t cj) { return (ri >> 2) * 64u + (ri & 3u) * 16u + cj; }
 };
 
-__device__ inline void store_val(unsigned char* p, uint32_t e, float v) { reinterpret_cast<float*>(p)[e] = v; }
-__device__ inline void store_val(unsigned char* p, uint32_t e, double v)
-{
-    uint32_t* w = reinterpret_cast<uint32_t*>(p) + 2u * e;       // (4-byte aligned only when kmax is odd: record_common.h, load_val)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    w[0] = (uint32_t)u;
-    w[1] = (uint32_t)(u >> 32);
-}
-
 struct RefitState {
     unsigned char* batch = nullptr;    // per call: staged records (a host caller's), status, residual norms, the bad-index word
     size_t batch_bytes = 0;

@@ -361,15 +361,13 @@ struct ss_hip_ctx {
     void* irls_batch = nullptr;   // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
     int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
     void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
-    void* dl = nullptr;           // sship::DictLearnState* (dictlearn.hip): the workspace of the atom update
+    void* learn = nullptr;        // sship::LearnArena* (dictlearn.hip): the one workspace of the atom update, the K-SVD sweep and the weighted atom update
     void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
     void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
-    void* ks = nullptr;           // sship::KsvdState* (ksvd.hip): the workspace of the K-SVD sweep
     void* tc = nullptr;           // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
     void* js = nullptr;           // sship::WorkArena* (joint.hip): the workspace of the group class residuals
     void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
-    void* wdl = nullptr;          // sship::WdlState* (wdictlearn.hip): the workspace of the weighted atom update
-    int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom update holds at once (0 = the byte budget alone)
+    int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom updates hold at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
     int is_f64 = 0;
@@ -521,9 +519,8 @@ hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
 void omp_gram_free(ss_hip_ctx* ctx);
 // classification from compact records (classify.hip): releases the labels and the workspace of a context
 void classify_free(ss_hip_ctx* ctx);
-// the atom update of dictionary learning (dictlearn.hip): releases its workspace
-void dictlearn_free(ss_hip_ctx* ctx);
-// ... and the launches of its kernels the K-SVD sweep (ksvd.hip) shares with it, on the context's stream (every pointer on the device):
+// the atom update of dictionary learning (dictlearn.hip): the launches of its kernels, which the three learners' drivers (learn_driver.h:
+// dictlearn.hip, ksvd.hip, wdictlearn.hip) call, on the context's stream (every pointer on the device):
 // dl_launch_count: counts[S] and off[0 .. S + 1] (the offsets, the total, the longest list) of the atom -> user lists, and bad = the
 // first record with a column index >= n (else 0xffffffff); slot_of [n]: column -> position in the request, null = every column its own.
 // dl_launch_lists: the lists sb / sw (signal, value) in ascending (signal, position in the record) order and s2[s] = sum w^2;
@@ -539,14 +536,12 @@ template <typename T>
 hipError_t dl_launch_residuals(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
                                uint32_t Bc, T* R, double* part);
 hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per, uint32_t B, double* sig, double* obj);
-// ... and of the gather behind its apply, which the weighted atom update (wdictlearn.hip) shares: Vc[p][0 .. m) = column sel[p] of out
+// ... and of the gather behind apply: Vc[p][0 .. m) = column sel[p] of out
 // (out(i, s) = out[i * ors + s * ocs]), p < nc — the changed atoms, contiguous, for the column replacement
 template <typename T>
 hipError_t dl_launch_gather(ss_hip_ctx* ctx, const T* out, long long ors, long long ocs, const uint32_t* sel, uint32_t nc, T* Vc);
 // the least-squares refit of compact records (refit.hip): releases its workspace
 void refit_free(ss_hip_ctx* ctx);
-// the K-SVD sweep (ksvd.hip): releases its workspace
-void ksvd_free(ss_hip_ctx* ctx);
 // the coherence of atoms (coherence.hip): releases its workspace
 void coherence_free(ss_hip_ctx* ctx);
 // ... and the launch of its norms kernel the top correlations share with it, on the context's stream: out[i] = 1 / sqrt(d_i), d_i =
@@ -562,6 +557,12 @@ struct WorkArena {
 // topcorr_free releases it
 WorkArena& topcorr_arena(ss_hip_ctx* ctx);
 void topcorr_free(ss_hip_ctx* ctx);
+// the three arenas of the atom learning calls (dictlearn.hip; learn_driver.h carves them): the index (staged records, slot map, counts,
+// offsets, partial sums, usage), the workspace (the lists, the atoms [S][ldm], the residual blocks, a host caller's signals) and the
+// changed atoms of an apply.  Every call ends with its own stream synchronise, so the three calls share them.  learn_free releases them
+struct LearnArena { WorkArena index, work, vc; };
+LearnArena& learn_arena(ss_hip_ctx* ctx);
+void learn_free(ss_hip_ctx* ctx);
 // ... and the launches of a chunk's kernels behind the driver (tc_driver.h), on the context's stream, every pointer on
 // the device.  tc_launch_record_check: bad[0] = the first of B records with a column index >= n (else 0xffffffff).
 // tc_launch_residual_block: R[b][0 .. ldm) for Bc <= 32768 signals — y_b - A x_b from recs on (dl_launch_residuals, with its partials in
@@ -577,9 +578,7 @@ template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uin
 template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
 // weighted coding (weighted.hip): releases the staged weights
 void weighted_free(ss_hip_ctx* ctx);
-// the weighted atom update (wdictlearn.hip): releases its workspace
-void wdictlearn_free(ss_hip_ctx* ctx);
-// ... and what the three weighted calls share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
+// what the three weighted calls and the weighted atom update (wdictlearn.hip) share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
 // weights_on_device: the batch's weights where the kernels read them — W itself, or a staged copy of a host caller's (row pitch m, or
 // 0 for the shared vector) — after a device scan for the first weight that is negative or not finite (SS_HIP_EINVAL, the signal and
 // the row in the message; nothing has been written).  Throws what HIPCHK throws: call it under guarded

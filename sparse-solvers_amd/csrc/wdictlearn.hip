@@ -12,10 +12,8 @@
 // nu is zero or not finite.  All atoms see the same old dictionary and residuals (a Jacobi step, like dictlearn.hip's).  The chains
 // cannot be had from dictlearn.hip's by scaling Y: the weights differ per signal while the atom is shared.
 //
-//   dl_launch_count / dl_launch_lists / dl_launch_residuals / dl_launch_objective / dl_launch_gather
-//                    dictlearn.hip's kernels through its launches: the inverted index atom -> (signal, value) in ascending (signal,
-//                    position) order with its rank-sort and long-list paths, the residual block of a chunk, the objective's two
-//                    sums, the changed atoms gathered for the column replacement.
+//   learn_*          the host steps the three learners share (learn_driver.h): checks, the atom list, the arena, the index, the chunk
+//                    size, the copies out and apply.  dl_launch_*: the lists, the residual block, the objective's sums: dictlearn.hip's
 //   weights_on_device   weighted.hip's staging and device check of the weights (the first offender, before anything is written).
 //   k_wdl_stage      grid = (row tile, signal of the chunk).  Wb[b][0 .. ldm) = w_b, zero from row m on: the caller's rows are m long
 //                    at any stride >= m, so they are read as scalars and stored as the 16-byte vectors k_wdl_atoms loads.  The same
@@ -53,7 +51,7 @@
 // rows are 16 bytes wide: a row of R and of Wb starts at a multiple of ldm elements, a multiple of 16 bytes, which a caller's weight
 // row (m long at any stride >= m: m = 70, w_stride = m + 3) does not — hence the staging.
 #include "ss_hip_internal.h"
-#include "record_common.h"
+#include "learn_driver.h"
 
 #include <algorithm>
 #include <cmath>
@@ -62,49 +60,6 @@
 namespace sship {
 
 namespace {
-
-constexpr size_t kWdlChunkBytes = (size_t)256 << 20;     // byte budget of each of a chunk's two blocks, R and Wb (never changes a result)
-constexpr uint32_t kWdlChunkMax = 32768;                 // most signals per chunk (grid.y of the residual kernel)
-constexpr uint32_t kWdlNone = 0xffffffffu;
-constexpr uint32_t kWdlLeft = 0x80000000u;               // usage bit: the atom had users but was left as it is
-
-struct WdlState {
-    unsigned char* index = nullptr;    // records (staged), slot map, counts, offsets, partial sums, usage, nu
-    size_t index_bytes = 0;
-    unsigned char* work = nullptr;     // the lists, num and den [S][ldm], the residual and weight blocks of a chunk, a host caller's signals
-    size_t work_bytes = 0;
-    unsigned char* vc = nullptr;       // apply: the changed atoms, contiguous
-    size_t vc_bytes = 0;
-};
-
-WdlState* state_of(ss_hip_ctx* ctx)
-{
-    if (!ctx->wdl) ctx->wdl = new WdlState();
-    return static_cast<WdlState*>(ctx->wdl);
-}
-
-__device__ inline void store_val(unsigned char* p, uint32_t e, float v) { reinterpret_cast<float*>(p)[e] = v; }
-__device__ inline void store_val(unsigned char* p, uint32_t e, double v)
-{
-    uint32_t* w = reinterpret_cast<uint32_t*>(p) + 2u * e;       // (4-byte aligned only when kmax is odd: record_common.h, load_val)
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    w[0] = (uint32_t)u;
-    w[1] = (uint32_t)(u >> 32);
-}
-
-template <typename T> __device__ inline typename ClsVec<T>::type wdl_pack(const T* d);
-template <> __device__ inline float4 wdl_pack<float>(const float* d) { return float4{ d[0], d[1], d[2], d[3] }; }
-template <> __device__ inline double2 wdl_pack<double>(const double* d) { return double2{ d[0], d[1] }; }
-
-// first position in sb[lo .. hi) whose signal is >= b (the list is ascending)
-__device__ inline uint32_t wdl_lower_bound(const uint32_t* __restrict__ sb, uint32_t lo, uint32_t hi, uint32_t b)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (sb[mid] < b) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
 
@@ -129,7 +84,7 @@ void k_wdl_stage(const T* __restrict__ Wt, long long w_stride, uint32_t m, uint3
         T wv[VW];
 #pragma unroll
         for (uint32_t e = 0; e < VW; ++e) wv[e] = row0 + e < m ? w[row0 + e] : T(0);
-        *reinterpret_cast<V*>(Wb + (size_t)b * ldm + row0) = wdl_pack<T>(wv);
+        *reinterpret_cast<V*>(Wb + (size_t)b * ldm + row0) = cls_pack<T>(wv);
         if (counts) {
             const V rv = *reinterpret_cast<const V*>(R + (size_t)b * ldm + row0);
 #pragma unroll
@@ -167,7 +122,7 @@ void k_wdl_atoms(uint32_t ldm, const uint32_t* __restrict__ off, const uint32_t*
 #pragma unroll
         for (uint32_t e = 0; e < VW; ++e) { num[j][e] = vget(a, e); den[j][e] = vget(d, e); }
     }
-    const uint32_t lo = wdl_lower_bound(sb, beg, end, b0), hi = wdl_lower_bound(sb, lo, end, b1);
+    const uint32_t lo = dl_lower_bound(sb, beg, end, b0), hi = dl_lower_bound(sb, lo, end, b1);
     uint32_t k = lo;
     for (; k + U <= hi; k += U) {                       // U users' rows of R and of Wb in flight, added in order
         V r[U][L], w[U][L];
@@ -211,8 +166,8 @@ void k_wdl_atoms(uint32_t ldm, const uint32_t* __restrict__ off, const uint32_t*
 #pragma unroll
     for (uint32_t j = 0; j < L; ++j)
         if (row0[j] < ldm) {
-            *reinterpret_cast<V*>(nump + row0[j]) = wdl_pack<T>(num[j]);
-            *reinterpret_cast<V*>(denp + row0[j]) = wdl_pack<T>(den[j]);
+            *reinterpret_cast<V*>(nump + row0[j]) = cls_pack<T>(num[j]);
+            *reinterpret_cast<V*>(denp + row0[j]) = cls_pack<T>(den[j]);
         }
 }
 
@@ -256,7 +211,7 @@ void k_wdl_finish(const T* __restrict__ At, uint32_t ldm, uint32_t m, const uint
                     seen |= is_seen ? 1u : 0u;
                     q += (double)dk[e] * (double)dk[e];
                 }
-                *reinterpret_cast<V*>(d + row0) = wdl_pack<T>(dk);
+                *reinterpret_cast<V*>(d + row0) = cls_pack<T>(dk);
             }
             q = wave_sum(q);
             seen = __any((int)seen) ? 1u : 0u;
@@ -274,7 +229,7 @@ void k_wdl_finish(const T* __restrict__ At, uint32_t ldm, uint32_t m, const uint
         const uint32_t ok = (cnt != 0u && seen_any != 0u && nrm > T(0) && nrm <= std::numeric_limits<T>::max()) ? 1u : 0u;
         s_nu = nrm;
         s_ok = ok;
-        usage[s] = cnt != 0u && ok == 0u ? (cnt | kWdlLeft) : cnt;
+        usage[s] = cnt != 0u && ok == 0u ? (cnt | kDlLeft) : cnt;
         nu[s] = ok != 0u ? nrm : T(0);
     }
     __threadfence_block();
@@ -308,7 +263,7 @@ void k_wdl_scale(const unsigned char* in, unsigned char* out, size_t rb, uint32_
     for (uint32_t e = tid; e < K; e += 256u) {          // (in place an entry is read and written by this thread alone)
         const uint32_t col = idx[e];
         const uint32_t s = slot_of ? slot_of[col] : col;
-        if (s == kWdlNone) continue;
+        if (s == kDlNone) continue;
         const T f = nu[s];
         if (f != T(0)) store_val(vout, e, load_val(vin, e, T(0)) * f);
     }
@@ -316,166 +271,86 @@ void k_wdl_scale(const unsigned char* in, unsigned char* out, size_t rb, uint32_
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
+// the index and the workspace: the common pieces (learn_driver.h; the index's sum c^2 is not used here), and nu per slot; num and
+// den, the residual and weight blocks of a chunk
+template <typename T> struct WdlIndex : LearnIndex<T> {
+    T* nu;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->head(cv, c, 1);
+        nu = cv.take<T>(c.S);
+        this->tail(cv, c);
+    }
+};
+
+template <typename T> struct WdlWork : LearnWork<T> {
+    size_t chunk;
+    T *Num, *Den, *R, *Wb;
+    void carve(Carver& cv, const LearnCall<T>& c)
+    {
+        this->lists(cv, c);
+        Num = cv.take<T>(c.S * c.ldm);
+        Den = cv.take<T>(c.S * c.ldm);
+        R = cv.take<T>(chunk * c.ldm);
+        Wb = cv.take<T>(chunk * c.ldm);
+        this->signals(cv, c, chunk);
+    }
+};
+
 template <typename T>
-int wdl_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const T* W, ptrdiff_t w_stride, const void* records,
-             uint32_t kmax, void* records_out, const uint32_t* cols, size_t S, T* Vout, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage,
-             double* objective, bool apply, char* err, size_t errlen)
+int wdl_impl(LearnCall<T>& c, const T* W, ptrdiff_t w_stride)
 {
-    static const char* who = "weighted_atom_update";
-    HIPCHK(hipSetDevice(ctx->device));
-    WdlState* ds = state_of(ctx);
+    ss_hip_ctx* ctx = c.ctx;
+    int rc = learn_atoms(c);
+    if (rc != SS_HIP_OK) return rc;
     hipStream_t st = ctx->stream;
-    const size_t m = ctx->m, n = ctx->n, rb = record_bytes(kmax, sizeof(T));
-    const uint32_t ldm = ctx->ldm, ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), per = ntiles * 4u;
+    const size_t B = c.B, m = c.m, rb = c.rb;
+    const uint32_t Su = (uint32_t)c.S, Bu = (uint32_t)B, ldm = c.ldm, ntiles = c.ntiles, per = c.per;
     const T* At = static_cast<const T*>(ctx->At);
 
-    // ---- the list of atoms, on a host copy: nothing has been written when it fails ----
-    std::vector<uint32_t> hc, slots;
-    if (cols) {
-        hc.resize(S);
-        if (on_device(cols)) HIPCHK(hipMemcpy(hc.data(), cols, S * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        else std::memcpy(hc.data(), cols, S * sizeof(uint32_t));
-        std::vector<uint32_t> sorted(hc);
-        std::sort(sorted.begin(), sorted.end());
-        if (sorted.back() >= n) { set_err(err, errlen, "weighted_atom_update: column index out of range"); return SS_HIP_EINVAL; }
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) { set_err(err, errlen, "weighted_atom_update: a column is named twice"); return SS_HIP_EINVAL; }
-    } else {
-        S = n;
-    }
-    const uint32_t Su = (uint32_t)S, Bu = (uint32_t)B;
-    const bool in_dev = on_device(records), out_dev = records_out != nullptr && on_device(records_out), y_dev = on_device(Y);
-    const bool v_dev = Vout != nullptr && on_device(Vout), staged = !in_dev || (records_out != nullptr && !out_dev);
+    WdlIndex<T> ix;
+    learn_carve(learn_arena(ctx).index, ix, c, "hipMalloc(atom learning index)");
+    if ((rc = learn_open(c, ix)) != SS_HIP_OK) return rc;
 
-    // ---- the index's fixed-size part ----
-    auto carve_index = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        unsigned char* stage = staged ? cv.take<unsigned char>(B * rb) : nullptr;
-        uint32_t* slot_of = cols ? cv.take<uint32_t>(n) : nullptr;
-        uint32_t* dcols = cols ? cv.take<uint32_t>(S) : nullptr;
-        uint32_t* counts = cv.take<uint32_t>(S);
-        uint32_t* off = cv.take<uint32_t>(S + 2);         // (+ the total, + the longest list)
-        uint32_t* bad = cv.take<uint32_t>(1);
-        double* part = cv.take<double>(B * per);
-        double* sig = cv.take<double>(B);
-        double* obj = cv.take<double>(1);
-        T* s2 = cv.take<T>(S);                            // (the index's sum c^2: not used here)
-        T* nu = cv.take<T>(S);
-        uint32_t* dusage = cv.take<uint32_t>(S);
-        uint32_t* sel = cv.take<uint32_t>(2 * S);         // apply: positions of the changed atoms, then their columns
-        use(stage, slot_of, dcols, counts, off, bad, part, sig, obj, s2, nu, dusage, sel);
-        return cv.off;
-    };
-    grow(ds->index, ds->index_bytes, carve_index(nullptr, [](auto...) {}), "hipMalloc(weighted atom update index)");
+    // ---- the weights where the kernels read them, checked: the last thing that can fail before an output is written ----
+    const T* Wd = nullptr;
+    long long wsd = 0;
+    if ((rc = weights_on_device<T>(ctx, c.who, W, B, w_stride, &Wd, &wsd, c.err, c.errlen)) != SS_HIP_OK) return rc;
 
-    int rc = SS_HIP_OK;
-    carve_index(ds->index, [&](unsigned char* stage, uint32_t* slot_of, uint32_t* dcols, uint32_t* counts, uint32_t* off, uint32_t* bad,
-                               double* part, double* sig, double* obj, T* s2, T* nu, uint32_t* dusage, uint32_t* sel) {
-        // din: the input records on the device; dout: where the output records are written there (a host caller's: the staging, in
-        // place when the input is staged too)
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-        unsigned char* dout = !records_out ? nullptr : out_dev ? static_cast<unsigned char*>(records_out) : stage;
-        if (cols) {
-            slots.assign(n, kWdlNone);
-            for (size_t s = 0; s < S; ++s) slots[hc[s]] = (uint32_t)s;
-            HIPCHK(hipMemcpyAsync(slot_of, slots.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(dcols, hc.data(), S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        }
-        HIPCHK(dl_launch_count(ctx, din, rb, kmax, Bu, slot_of, Su, counts, off, bad));
-        uint32_t first_bad = kWdlNone, tail[2] = { 0u, 0u };
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(tail, off + S, sizeof(tail), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (the first host read: is a record invalid; how long are the lists)
-        const uint32_t total = tail[0], longest = tail[1];
-        if (first_bad != kWdlNone) { rc = bad_index(first_bad, who, err, errlen); return; }
-
-        // ---- the weights where the kernels read them, checked: the last thing that can fail before an output is written ----
-        const T* Wd = nullptr;
-        long long wsd = 0;
-        if ((rc = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &wsd, err, errlen)) != SS_HIP_OK) return;
-
-        // ---- the lists, num and den, the residual and weight blocks of a chunk ----
-        size_t chunk = std::max<size_t>(1, std::min<size_t>(kWdlChunkMax, kWdlChunkBytes / ((size_t)ldm * sizeof(T))));
-        if (ctx->dl_chunk_max > 0) chunk = std::min<size_t>(chunk, (size_t)ctx->dl_chunk_max);
-        chunk = std::min(chunk, B);
-        auto carve_work = [&](unsigned char* base, auto&& use) {
-            Carver cv(base);
-            uint32_t* pair_b = cv.take<uint32_t>(total);
-            uint32_t* pair_e = cv.take<uint32_t>(total);
-            uint32_t* sb = cv.take<uint32_t>(total);
-            T* sw = cv.take<T>(total);
-            T* Num = cv.take<T>(S * ldm);
-            T* Den = cv.take<T>(S * ldm);
-            T* R = cv.take<T>(chunk * ldm);
-            T* Wb = cv.take<T>(chunk * ldm);
-            T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
-            use(pair_b, pair_e, sb, sw, Num, Den, R, Wb, ybuf);
-            return cv.off;
-        };
-        grow(ds->work, ds->work_bytes, carve_work(nullptr, [](auto...) {}), "hipMalloc(weighted atom update workspace)");
-        carve_work(ds->work, [&](uint32_t* pair_b, uint32_t* pair_e, uint32_t* sb, T* sw, T* Num, T* Den, T* R, T* Wb, T* ybuf) {
-            if (total != 0u)
-                HIPCHK(dl_launch_lists<T>(ctx, din, rb, kmax, Bu, slot_of, dcols, Su, counts, off, longest, pair_b, pair_e, sb, sw, s2, bad));
-            std::vector<T> tmp;
-            if (total != 0u || objective) {
-                for (size_t b0 = 0; b0 < B; b0 += chunk) {
-                    const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-                    const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-                    long long ys = y_stride, yi = incy;
-                    if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-                    HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, din + b0 * rb, rb, kmax, Bc, R, part + b0 * per));
-                    hipLaunchKernelGGL((k_wdl_stage<T>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, Wd + (ptrdiff_t)b0 * wsd, wsd, (uint32_t)m, ldm,
-                                       din + b0 * rb, rb, kmax, (const T*)R, Wb, part + b0 * per);
-                    if (total != 0u)
-                        hipLaunchKernelGGL((k_wdl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, ldm, (const uint32_t*)off, (const uint32_t*)sb,
-                                           (const T*)sw, (const T*)R, (const T*)Wb, (uint32_t)b0, (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, Num, Den);
-                    HIPCHK(hipGetLastError());
-                }
-            }
-            if (objective) HIPCHK(dl_launch_objective(ctx, part, per, Bu, sig, obj));
-            // ---- d, nu, changed / left, V: straight into a device V, else in place over num ([S][ldm]) ----
-            T* out = v_dev ? Vout : Num;
-            const long long ors = v_dev ? (long long)rs : 1ll, ocs = v_dev ? (long long)cs : (long long)ldm;
-            hipLaunchKernelGGL((k_wdl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)dcols, (const uint32_t*)off, Num,
-                               (const T*)Den, ntiles, out, ors, ocs, dusage, nu);
+    // ---- the lists, num and den, the residual and weight blocks of a chunk ----
+    WdlWork<T> wk;
+    wk.chunk = learn_chunk(c);
+    learn_carve(learn_arena(ctx).work, wk, c, "hipMalloc(atom learning workspace)");
+    if (c.total != 0u)
+        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+                                  wk.sw, ix.s2, ix.bad));
+    std::vector<T> tmp;
+    if (c.total != 0u || c.objective) {
+        for (size_t b0 = 0; b0 < B; b0 += wk.chunk) {
+            const uint32_t Bc = (uint32_t)std::min(wk.chunk, B - b0);
+            const T* yd = c.Y + (ptrdiff_t)b0 * c.y_stride;
+            long long ys = c.y_stride, yi = c.incy;
+            if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, b0, Bc, tmp); yd = wk.ybuf; ys = (long long)m; yi = 1; }
+            HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, c.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
+            hipLaunchKernelGGL((k_wdl_stage<T>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, Wd + (ptrdiff_t)b0 * wsd, wsd, (uint32_t)m, ldm,
+                               c.din + b0 * rb, rb, c.kmax, (const T*)wk.R, wk.Wb, ix.part + b0 * per);
+            if (c.total != 0u)
+                hipLaunchKernelGGL((k_wdl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, ldm, (const uint32_t*)ix.off, (const uint32_t*)wk.sb,
+                                   (const T*)wk.sw, (const T*)wk.R, (const T*)wk.Wb, (uint32_t)b0, (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, wk.Num, wk.Den);
             HIPCHK(hipGetLastError());
-            if (dout) {
-                hipLaunchKernelGGL((k_wdl_scale<T>), dim3(Bu), dim3(256), 0, st, din, dout, rb, kmax, (const uint32_t*)slot_of, (const T*)nu);
-                HIPCHK(hipGetLastError());
-                if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
-            }
-            if (objective) HIPCHK(hipMemcpyAsync(objective, obj, sizeof(double), hipMemcpyDefault, st));
-            if (usage) HIPCHK(hipMemcpyAsync(usage, dusage, S * sizeof(uint32_t), hipMemcpyDefault, st));
-            std::vector<uint32_t> hus;
-            if (apply) {
-                hus.resize(S);
-                HIPCHK(hipMemcpyAsync(hus.data(), dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            }
-            if (Vout && !v_dev) {
-                tmp.resize(S * m);
-                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), Num, (size_t)ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (size_t s = 0; s < S; ++s)
-                    for (size_t i = 0; i < m; ++i) Vout[(ptrdiff_t)i * rs + (ptrdiff_t)s * cs] = tmp[s * m + i];
-            }
-            HIPCHK(hipStreamSynchronize(st));
-            if (!apply) return;
-            // ---- apply: the changed atoms as a device column list + a contiguous device V, through the column replacement ----
-            std::vector<uint32_t> pos, ccols;
-            for (size_t s = 0; s < S; ++s)
-                if (hus[s] != 0u && (hus[s] & kWdlLeft) == 0u) { pos.push_back((uint32_t)s); ccols.push_back(cols ? hc[s] : (uint32_t)s); }
-            if (pos.empty()) return;
-            const size_t nc = pos.size();
-            grow(ds->vc, ds->vc_bytes, nc * m * sizeof(T), "hipMalloc(weighted atom update: changed atoms)");
-            T* Vc = reinterpret_cast<T*>(ds->vc);
-            HIPCHK(hipMemcpyAsync(sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            HIPCHK(dl_launch_gather<T>(ctx, (const T*)out, ors, ocs, (const uint32_t*)sel, (uint32_t)nc, Vc));
-            HIPCHK(hipStreamSynchronize(st));
-            rc = replace_columns_device<T>(ctx, sel + S, ccols, Vc, 1ll, (long long)m, err, errlen);
-        });
-    });
-    return rc;
+        }
+    }
+    if (c.objective) HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj));
+    // ---- d, nu, changed / left, V: straight into a device V, else in place over num ([S][ldm]); the records' values times nu ----
+    const LearnOut<T> out = learn_out(c, wk.Num);
+    hipLaunchKernelGGL((k_wdl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols, (const uint32_t*)ix.off, wk.Num,
+                       (const T*)wk.Den, ntiles, out.p, out.rs, out.cs, ix.dusage, ix.nu);
+    HIPCHK(hipGetLastError());
+    if (c.dout) {
+        hipLaunchKernelGGL((k_wdl_scale<T>), dim3(Bu), dim3(256), 0, st, c.din, c.dout, rb, c.kmax, (const uint32_t*)ix.slot_of, (const T*)ix.nu);
+        HIPCHK(hipGetLastError());
+    }
+    return learn_finish<T>(c, ix, 1, wk.Num, out);
 }
 
 template <typename T>
@@ -483,44 +358,24 @@ int wdl_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff
               uint32_t kmax, void* records_out, const uint32_t* cols, size_t S, T* V, ptrdiff_t rs, ptrdiff_t cs, uint32_t* usage,
               double* objective, uint32_t flags, char* err, size_t errlen)
 {
-    static const char* who = "weighted_atom_update";
-    int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
-    if (rc != SS_HIP_OK) return rc;
-    if (!Y) { set_err(err, errlen, "weighted_atom_update: Y must not be null"); return SS_HIP_EINVAL; }
-    if ((rc = weights_check_args(ctx, who, W, w_stride, err, errlen)) != SS_HIP_OK) return rc;
-    if (flags & ~(uint32_t)SS_HIP_WDL_APPLY) { set_err(err, errlen, "weighted_atom_update: unknown flag bit"); return SS_HIP_EINVAL; }
-    if (!V && !(flags & SS_HIP_WDL_APPLY) && !usage && !objective && !records_out) {
-        set_err(err, errlen, "weighted_atom_update: nothing asked for (V, usage, objective and records_out are null and the atoms are not applied)");
-        return SS_HIP_EINVAL;
-    }
-    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "weighted_atom_update: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
-    if (incy <= 0 || y_stride <= 0 || (V && (rs <= 0 || cs <= 0))) { set_err(err, errlen, "weighted_atom_update: increments and strides must be positive"); return SS_HIP_EINVAL; }
-    if (B >= 0x80000000ull || (unsigned long long)B * kmax >= 0xffffffffull) { set_err(err, errlen, "weighted_atom_update: B * kmax must stay below 2^32"); return SS_HIP_EINVAL; }
-    if (records_out && records_out != records) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(records), b = reinterpret_cast<uintptr_t>(records_out);
-        const size_t bytes = B * record_bytes(kmax, sizeof(T));
-        if (a < b + bytes && b < a + bytes) { set_err(err, errlen, "weighted_atom_update: records and records_out overlap in part"); return SS_HIP_EINVAL; }
-    }
-    if (B == 0 || (cols && S == 0)) return SS_HIP_OK;         // (every argument above was checked all the same)
-    if (cols && S > ctx->n) { set_err(err, errlen, "weighted_atom_update: more columns than the dictionary has (a column is named twice)"); return SS_HIP_EINVAL; }
-    return guarded(err, errlen, who, [&] {
-        return wdl_impl<T>(ctx, Y, B, y_stride, incy, W, w_stride, records, kmax, records_out, cols, S, V, rs, cs, usage, objective,
-                           (flags & SS_HIP_WDL_APPLY) != 0u, err, errlen);
-    });
+    const bool apply = (flags & SS_HIP_WDL_APPLY) != 0u;
+    LearnCall<T> c{ ctx, "weighted_atom_update", Y, B, y_stride, incy, records, kmax, records_out, cols, S, V, rs, cs, usage, objective, apply, err, errlen };
+    LearnRules r{};
+    r.null_y = "Y must not be null";
+    r.flags = flags;
+    r.mask = SS_HIP_WDL_APPLY;
+    if (!V && !apply && !usage && !objective && !records_out)
+        r.nothing = "nothing asked for (V, usage, objective and records_out are null and the atoms are not applied)";
+    r.weighted = true;
+    r.W = W;
+    r.w_stride = w_stride;
+    bool empty = false;
+    const int rc = learn_check_args(c, r, empty);
+    if (rc != SS_HIP_OK || empty) return rc;
+    return guarded(err, errlen, c.who, [&] { return wdl_impl<T>(c, W, w_stride); });
 }
 
 }  // namespace
-
-void wdictlearn_free(ss_hip_ctx* ctx)
-{
-    WdlState* ds = static_cast<WdlState*>(ctx->wdl);
-    if (!ds) return;
-    if (ds->index) (void)hipFree(ds->index);
-    if (ds->work) (void)hipFree(ds->work);
-    if (ds->vc) (void)hipFree(ds->vc);
-    delete ds;
-    ctx->wdl = nullptr;
-}
 
 }  // namespace sship
 
