@@ -53,12 +53,9 @@ constexpr uint32_t kSigWords = 4;                        // per-signal header: K
 struct ClassifyState {
     uint32_t* labels = nullptr;        // [n_pad] class of every column (padding columns: 0)
     uint32_t num_classes = 0;
-    unsigned char* arena = nullptr;    // the workspace of one chunk, carved per call
-    size_t arena_bytes = 0;
-    unsigned char* y_all = nullptr;    // classify: the batch's signals, uploaded once (a host Y)
-    size_t y_all_bytes = 0;
-    unsigned char* rec_all = nullptr;  // classify: the batch's records (the caller's are on the host, or not asked for)
-    size_t rec_all_bytes = 0;
+    WorkArena arena;                   // the workspace of one chunk, carved per call
+    WorkArena y_all;                   // classify: the batch's signals, uploaded once (a host Y)
+    WorkArena rec_all;                 // classify: the batch's records (the caller's are on the host, or not asked for)
 };
 
 ClassifyState* state_of(ss_hip_ctx* ctx)
@@ -357,6 +354,42 @@ int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errl
     return SS_HIP_OK;
 }
 
+// a chunk's pieces: the residuals', or the reconstruction's (store: one segment, no Y, yh in place of the residuals' outputs)
+template <typename T> struct ClsWork {
+    size_t rb, m;
+    uint32_t kmax, segcap, ntiles, C, ldm;
+    bool rec_dev, y_dev, store;
+    unsigned char* rec;
+    T *ybuf, *ord_val, *Rb, *yh;
+    uint32_t *ord_idx, *seg, *sig, *dbest, *bad;
+    double *seg_l1, *dsci, *part, *party;
+    void carve(Carver& cv, size_t ch)
+    {
+        rec = rec_dev ? nullptr : cv.take<unsigned char>(ch * rb);
+        ybuf = y_dev ? nullptr : cv.take<T>(ch * m);
+        ord_idx = cv.take<uint32_t>(ch * kmax);
+        ord_val = cv.take<T>(ch * kmax);
+        seg = cv.take<uint32_t>(ch * segcap * 3);
+        seg_l1 = cv.take<double>(ch * segcap);
+        sig = cv.take<uint32_t>(ch * kSigWords);
+        dsci = cv.take<double>(ch);
+        yh = store ? cv.take<T>(ch * ldm) : nullptr;
+        dbest = store ? nullptr : cv.take<uint32_t>(ch);
+        part = store ? nullptr : cv.take<double>(ch * ntiles * segcap * 4);
+        party = store ? nullptr : cv.take<double>(ch * ntiles * 4);
+        Rb = store ? nullptr : cv.take<T>(ch * C);
+        bad = cv.take<uint32_t>(1);
+    }
+    // the most signals a chunk holds under the byte budget; the arena grown to them and carved
+    size_t place(WorkArena& arena, size_t B)
+    {
+        const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kClsChunkMax, kClsChunkBytes / carve_into(nullptr, *this, 1))));
+        grow(arena, carve_into(nullptr, *this, chunk), "hipMalloc(classify workspace)");
+        carve_into(arena.buf, *this, chunk);
+        return chunk;
+    }
+};
+
 // labels / C: the classes the residuals are taken by — the context's (class_residuals, classify), or nullptr / 1: every column in
 // one class (record_residual_norms).  best may be null then.
 template <typename T>
@@ -372,63 +405,35 @@ int residuals_impl(ss_hip_ctx* ctx, const char* who, const uint32_t* labels, uin
     const uint32_t ntiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows), segcap = std::min(kmax, C);
     const bool rec_dev = on_device(records), y_dev = on_device(Y);
 
-    auto carve = [&](unsigned char* base, size_t ch, auto&& use) {
-        Carver cv(base);
-        unsigned char* rec = rec_dev ? nullptr : cv.take<unsigned char>(ch * rb);
-        T* ybuf = y_dev ? nullptr : cv.take<T>(ch * m);
-        uint32_t* ord_idx = cv.take<uint32_t>(ch * kmax);
-        T* ord_val = cv.take<T>(ch * kmax);
-        uint32_t* seg = cv.take<uint32_t>(ch * segcap * 3);
-        double* seg_l1 = cv.take<double>(ch * segcap);
-        uint32_t* sig = cv.take<uint32_t>(ch * kSigWords);
-        double* dsci = cv.take<double>(ch);
-        uint32_t* dbest = cv.take<uint32_t>(ch);
-        double* part = cv.take<double>(ch * ntiles * segcap * 4);
-        double* party = cv.take<double>(ch * ntiles * 4);
-        T* Rb = cv.take<T>(ch * C);
-        uint32_t* bad = cv.take<uint32_t>(1);
-        use(rec, ybuf, ord_idx, ord_val, seg, seg_l1, sig, dsci, dbest, part, party, Rb, bad);
-        return cv.off;
-    };
-    const size_t per = carve(nullptr, 1, [](auto...) {});
-    const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kClsChunkMax, kClsChunkBytes / per)));
-    grow(cs->arena, cs->arena_bytes, carve(nullptr, chunk, [](auto...) {}), "hipMalloc(classify workspace)");
+    ClsWork<T> w{ rb, m, kmax, segcap, ntiles, C, ldm, rec_dev, y_dev, false };
+    const size_t chunk = w.place(cs->arena, B);
 
-    uint32_t first_bad = 0xffffffffu;
     std::vector<T> tmp;
-    carve(cs->arena, chunk, [&](unsigned char* rec, T* ybuf, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig,
-                                double* dsci, uint32_t* dbest, double* part, double* party, T* Rb, uint32_t* bad) {
-        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
-        for (size_t b0 = 0; b0 < B; b0 += chunk) {
-            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-            const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
-            if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
-            const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-            long long ys = y_stride, yi = incy;
-            if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-            hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
-                               labels, C, segcap, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
-            if (Wd)                                      // (the batch's weights on the device, validated: weights_on_device)
-                hipLaunchKernelGGL((k_cls_residual<T, false, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
-                                   (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
-                                   (const uint32_t*)sig, part, party, (T*)nullptr, Wd + (ptrdiff_t)b0 * ws, ws);
-            else
-                hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
-                                   (uint32_t)m, yd, ys, yi, (const uint32_t*)ord_idx, (const T*)ord_val, kmax, (const uint32_t*)seg, segcap,
-                                   (const uint32_t*)sig, part, party, (T*)nullptr, (const T*)nullptr, 0ll);
-            hipLaunchKernelGGL((k_cls_finish<T>), dim3(Bc), dim3(kClsThreads), 0, st, (const uint32_t*)seg, segcap, (const uint32_t*)sig,
-                               (const double*)part, (const double*)party, ntiles, C, Rb, dbest);
-            HIPCHK(hipGetLastError());
-            if (R) HIPCHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), Rb, (size_t)C * sizeof(T),
-                                           (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
-            if (best) HIPCHK(hipMemcpyAsync(best + b0, dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
-            if (sci) HIPCHK(hipMemcpyAsync(sci + b0, dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
-        }
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    if (first_bad != 0xffffffffu) return bad_index(first_bad, who, err, errlen);
-    return SS_HIP_OK;
+    flag_arm(w.bad, st);
+    for (size_t b0 = 0; b0 < B; b0 += chunk) {
+        const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+        const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
+        if (!rec_dev) { HIPCHK(hipMemcpyAsync(w.rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = w.rec; }
+        const ChunkSignals<T> y = chunk_signals<T>(ctx, Y, y_stride, incy, y_dev, w.ybuf, b0, Bc, tmp);
+        hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
+                           labels, C, segcap, w.ord_idx, w.ord_val, w.seg, w.seg_l1, w.sig, w.dsci, w.bad, (uint32_t)b0);
+        if (Wd)                                          // (the batch's weights on the device, validated: weights_on_device)
+            hipLaunchKernelGGL((k_cls_residual<T, false, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                               (uint32_t)m, y.yd, y.ys, y.yi, (const uint32_t*)w.ord_idx, (const T*)w.ord_val, kmax, (const uint32_t*)w.seg, segcap,
+                               (const uint32_t*)w.sig, w.part, w.party, (T*)nullptr, Wd + (ptrdiff_t)b0 * ws, ws);
+        else
+            hipLaunchKernelGGL((k_cls_residual<T, false>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                               (uint32_t)m, y.yd, y.ys, y.yi, (const uint32_t*)w.ord_idx, (const T*)w.ord_val, kmax, (const uint32_t*)w.seg, segcap,
+                               (const uint32_t*)w.sig, w.part, w.party, (T*)nullptr, (const T*)nullptr, 0ll);
+        hipLaunchKernelGGL((k_cls_finish<T>), dim3(Bc), dim3(kClsThreads), 0, st, (const uint32_t*)w.seg, segcap, (const uint32_t*)w.sig,
+                           (const double*)w.part, (const double*)w.party, ntiles, C, w.Rb, w.dbest);
+        HIPCHK(hipGetLastError());
+        if (R) HIPCHK(hipMemcpy2DAsync(R + (ptrdiff_t)b0 * r_stride, (size_t)r_stride * sizeof(T), w.Rb, (size_t)C * sizeof(T),
+                                       (size_t)C * sizeof(T), Bc, hipMemcpyDefault, st));
+        if (best) HIPCHK(hipMemcpyAsync(best + b0, w.dbest, (size_t)Bc * sizeof(uint32_t), hipMemcpyDefault, st));
+        if (sci) HIPCHK(hipMemcpyAsync(sci + b0, w.dsci, (size_t)Bc * sizeof(double), hipMemcpyDefault, st));
+    }
+    return flag_verdict(w.bad, st, who, err, errlen);
 }
 
 // weighted: the call carries W / w_stride (ss_hip_weighted_class_residuals_*), checked and brought to the device behind the other checks
@@ -446,10 +451,7 @@ int class_residuals_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B
         if (const int rw = weights_check_args(ctx, who, W, w_stride, err, errlen)) return rw;
     if (B == 0) return SS_HIP_OK;
     if (incy <= 0) { set_err(err, errlen, w + ": increments must be positive"); return SS_HIP_EINVAL; }
-    if (R && r_stride < (ptrdiff_t)static_cast<const ClassifyState*>(ctx->cls)->num_classes) {
-        set_err(err, errlen, w + ": r_stride must be at least num_classes");
-        return SS_HIP_EINVAL;
-    }
+    if (const int rr = check_r_stride(who, R, r_stride, static_cast<const ClassifyState*>(ctx->cls)->num_classes, err, errlen)) return rr;
     return guarded(err, errlen, who, [&]() -> int {
         const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
         const T* Wd = nullptr;
@@ -476,59 +478,37 @@ int reconstruct_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t km
     const bool rec_dev = on_device(records), out_dev = on_device(Yhat);
     const bool rows2d = incyh == 1 && yh_stride >= (ptrdiff_t)m;
 
-    auto carve = [&](unsigned char* base, size_t ch, auto&& use) {
-        Carver cv(base);
-        unsigned char* rec = rec_dev ? nullptr : cv.take<unsigned char>(ch * rb);
-        uint32_t* ord_idx = cv.take<uint32_t>(ch * kmax);
-        T* ord_val = cv.take<T>(ch * kmax);
-        uint32_t* seg = cv.take<uint32_t>(ch * 3);
-        double* seg_l1 = cv.take<double>(ch);
-        uint32_t* sig = cv.take<uint32_t>(ch * kSigWords);
-        double* dsci = cv.take<double>(ch);
-        T* yh = cv.take<T>(ch * ldm);
-        uint32_t* bad = cv.take<uint32_t>(1);
-        use(rec, ord_idx, ord_val, seg, seg_l1, sig, dsci, yh, bad);
-        return cv.off;
-    };
-    const size_t per = carve(nullptr, 1, [](auto...) {});
-    const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kClsChunkMax, kClsChunkBytes / per)));
-    grow(cs->arena, cs->arena_bytes, carve(nullptr, chunk, [](auto...) {}), "hipMalloc(classify workspace)");
+    ClsWork<T> w{ rb, m, kmax, 1u, ntiles, 1u, ldm, rec_dev, true, true };
+    const size_t chunk = w.place(cs->arena, B);
 
-    uint32_t first_bad = 0xffffffffu;
     std::vector<T> tmp;
-    carve(cs->arena, chunk, [&](unsigned char* rec, uint32_t* ord_idx, T* ord_val, uint32_t* seg, double* seg_l1, uint32_t* sig, double* dsci,
-                                T* yh, uint32_t* bad) {
-        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
-        for (size_t b0 = 0; b0 < B; b0 += chunk) {
-            const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-            const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
-            if (!rec_dev) { HIPCHK(hipMemcpyAsync(rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = rec; }
-            hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
-                               (const uint32_t*)nullptr, 1u, 1u, ord_idx, ord_val, seg, seg_l1, sig, dsci, bad, (uint32_t)b0);
-            hipLaunchKernelGGL((k_cls_residual<T, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
-                               (uint32_t)m, (const T*)nullptr, 0ll, 1ll, (const uint32_t*)ord_idx, (const T*)ord_val, kmax,
-                               (const uint32_t*)seg, 1u, (const uint32_t*)sig, (double*)nullptr, (double*)nullptr, yh, (const T*)nullptr, 0ll);
+    flag_arm(w.bad, st);
+    for (size_t b0 = 0; b0 < B; b0 += chunk) {
+        const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+        const unsigned char* recs = static_cast<const unsigned char*>(records) + b0 * rb;
+        if (!rec_dev) { HIPCHK(hipMemcpyAsync(w.rec, recs, (size_t)Bc * rb, hipMemcpyHostToDevice, st)); recs = w.rec; }
+        hipLaunchKernelGGL((k_cls_prepare<T>), dim3(Bc), dim3(kClsThreads), (size_t)kmax * 8, st, recs, rb, kmax, n,
+                           (const uint32_t*)nullptr, 1u, 1u, w.ord_idx, w.ord_val, w.seg, w.seg_l1, w.sig, w.dsci, w.bad, (uint32_t)b0);
+        hipLaunchKernelGGL((k_cls_residual<T, true>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, static_cast<const T*>(ctx->At), ldm,
+                           (uint32_t)m, (const T*)nullptr, 0ll, 1ll, (const uint32_t*)w.ord_idx, (const T*)w.ord_val, kmax,
+                           (const uint32_t*)w.seg, 1u, (const uint32_t*)w.sig, (double*)nullptr, (double*)nullptr, w.yh, (const T*)nullptr, 0ll);
+        HIPCHK(hipGetLastError());
+        T* out = Yhat + (ptrdiff_t)b0 * yh_stride;
+        if (rows2d) {
+            HIPCHK(hipMemcpy2DAsync(out, (size_t)yh_stride * sizeof(T), w.yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
+        } else if (out_dev) {
+            hipLaunchKernelGGL((k_cls_scatter<T>), dim3((uint32_t)std::min<size_t>((m + 255) / 256, 64), Bc), dim3(256), 0, st, (const T*)w.yh, ldm,
+                               (uint32_t)m, out, (long long)yh_stride, (long long)incyh);
             HIPCHK(hipGetLastError());
-            T* out = Yhat + (ptrdiff_t)b0 * yh_stride;
-            if (rows2d) {
-                HIPCHK(hipMemcpy2DAsync(out, (size_t)yh_stride * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDefault, st));
-            } else if (out_dev) {
-                hipLaunchKernelGGL((k_cls_scatter<T>), dim3((uint32_t)std::min<size_t>((m + 255) / 256, 64), Bc), dim3(256), 0, st, (const T*)yh, ldm,
-                                   (uint32_t)m, out, (long long)yh_stride, (long long)incyh);
-                HIPCHK(hipGetLastError());
-            } else {
-                tmp.resize((size_t)Bc * m);
-                HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                for (size_t b = 0; b < Bc; ++b)
-                    for (size_t i = 0; i < m; ++i) out[(ptrdiff_t)b * yh_stride + (ptrdiff_t)i * incyh] = tmp[b * m + i];
-            }
+        } else {
+            tmp.resize((size_t)Bc * m);
+            HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), w.yh, (size_t)ldm * sizeof(T), m * sizeof(T), Bc, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            for (size_t b = 0; b < Bc; ++b)
+                for (size_t i = 0; i < m; ++i) out[(ptrdiff_t)b * yh_stride + (ptrdiff_t)i * incyh] = tmp[b * m + i];
         }
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    if (first_bad != 0xffffffffu) return bad_index(first_bad, "reconstruct_records", err, errlen);
-    return SS_HIP_OK;
+    }
+    return flag_verdict(w.bad, st, "reconstruct_records", err, errlen);
 }
 
 template <typename T>
@@ -566,32 +546,25 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
     if (const int rq = check_classes(ctx, who, err, errlen)) return rq;
     if (B == 0) return SS_HIP_OK;
     if (incy <= 0) { set_err(err, errlen, "classify_batch: increments must be positive"); return SS_HIP_EINVAL; }
-    if (R && r_stride < (ptrdiff_t)static_cast<const ClassifyState*>(ctx->cls)->num_classes) {
-        set_err(err, errlen, "classify_batch: r_stride must be at least num_classes");
-        return SS_HIP_EINVAL;
-    }
+    if (const int rr = check_r_stride(who, R, r_stride, static_cast<const ClassifyState*>(ctx->cls)->num_classes, err, errlen)) return rr;
     return guarded(err, errlen, who, [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         ClassifyState* cs = state_of(ctx);
         const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
         // Y once to the device, the records kept there
-        const T* yd = Y;
-        ptrdiff_t ys = y_stride, yi = incy;
-        if (!on_device(Y)) {
-            grow(cs->y_all, cs->y_all_bytes, B * m * sizeof(T), "hipMalloc(classify signals)");
-            std::vector<T> tmp;
-            upload_rows<T>(ctx, reinterpret_cast<T*>(cs->y_all), Y, y_stride, incy, 0, B, tmp);
-            HIPCHK(hipStreamSynchronize(ctx->stream));
-            yd = reinterpret_cast<const T*>(cs->y_all); ys = (ptrdiff_t)m; yi = 1;
-        }
+        const bool y_dev = on_device(Y);
+        std::vector<T> tmp;
+        if (!y_dev) grow(cs->y_all, B * m * sizeof(T), "hipMalloc(classify signals)");
+        const ChunkSignals<T> y = chunk_signals<T>(ctx, Y, y_stride, incy, y_dev, reinterpret_cast<T*>(cs->y_all.buf), 0, B, tmp);
+        if (!y_dev) HIPCHK(hipStreamSynchronize(ctx->stream));
         void* rd = records;
         if (!records || !on_device(records)) {
-            grow(cs->rec_all, cs->rec_all_bytes, B * rb, "hipMalloc(classify records)");
-            rd = cs->rec_all;
+            grow(cs->rec_all, B * rb, "hipMalloc(classify records)");
+            rd = cs->rec_all.buf;
         }
-        const int rs = solve_compact(ctx, yd, B, ys, yi, tol, max_iter, kmax, rd, err, errlen);
+        const int rs = solve_compact(ctx, y.yd, B, (ptrdiff_t)y.ys, (ptrdiff_t)y.yi, tol, max_iter, kmax, rd, err, errlen);
         if (rs != SS_HIP_OK) return rs;
-        const int rr = residuals_impl<T>(ctx, "class_residuals", cs->labels, cs->num_classes, yd, B, ys, yi, rd, kmax, R, r_stride, best, sci, err, errlen);
+        const int rr = residuals_impl<T>(ctx, "class_residuals", cs->labels, cs->num_classes, y.yd, B, (ptrdiff_t)y.ys, (ptrdiff_t)y.yi, rd, kmax, R, r_stride, best, sci, err, errlen);
         if (rr != SS_HIP_OK) return rr;
         if (records && rd != records) HIPCHK(hipMemcpy(records, rd, B * rb, hipMemcpyDeviceToHost));
         return SS_HIP_OK;
@@ -668,9 +641,7 @@ void classify_free(ss_hip_ctx* ctx)
     ClassifyState* cs = static_cast<ClassifyState*>(ctx->cls);
     if (!cs) return;
     if (cs->labels) (void)hipFree(cs->labels);
-    if (cs->arena) (void)hipFree(cs->arena);
-    if (cs->y_all) (void)hipFree(cs->y_all);
-    if (cs->rec_all) (void)hipFree(cs->rec_all);
+    for (WorkArena* a : { &cs->arena, &cs->y_all, &cs->rec_all }) arena_free(*a);
     delete cs;
     ctx->cls = nullptr;
 }

@@ -277,6 +277,21 @@ void k_coh_finish(const double* __restrict__ pscore, const uint32_t* __restrict_
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
+// the call's pieces: the norms, the queries, a chunk's tile partials, the outputs
+struct CohWork {
+    double *rinv, *ps, *mud;
+    uint32_t *qd, *pi, *ptd;
+    void carve(Carver& cv, size_t n_pad, size_t Spad, size_t partials)
+    {
+        rinv = cv.take<double>(n_pad);
+        qd = cv.take<uint32_t>(Spad);
+        ps = cv.take<double>(partials);
+        pi = cv.take<uint32_t>(partials);
+        mud = cv.take<double>(Spad);
+        ptd = cv.take<uint32_t>(Spad);
+    }
+};
+
 template <typename T>
 int coherence_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* mu, uint32_t* partner, char* err, size_t errlen)
 {
@@ -301,36 +316,25 @@ int coherence_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* mu, 
 
     CoherenceState* cs = state_of(ctx);
     const size_t chunk = std::min<size_t>(Spad, SS_HIP_COHERENCE_CHUNK);
-    auto carve = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        double* rinv = cv.take<double>(n_pad);
-        uint32_t* qd = cv.take<uint32_t>(Spad);
-        double* ps = cv.take<double>(chunk * ntiles);
-        uint32_t* pi = cv.take<uint32_t>(chunk * ntiles);
-        double* mud = cv.take<double>(Spad);
-        uint32_t* ptd = cv.take<uint32_t>(Spad);
-        use(rinv, qd, ps, pi, mud, ptd);
-        return cv.off;
-    };
-    grow(cs->buf, cs->bytes, carve(nullptr, [](auto...) {}), "hipMalloc(coherence workspace)");
-    carve(cs->buf, [&](double* rinv, uint32_t* qd, double* ps, uint32_t* pi, double* mud, uint32_t* ptd) {
-        const T* At = static_cast<const T*>(ctx->At);
-        HIPCHK(hipMemcpyAsync(qd, q.data(), Spad * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((k_coh_norms<T>), dim3(n_pad / 4u), dim3(256), 0, st, At, ldm, (uint32_t)ctx->m, n, n_pad, rinv);
+    CohWork w;
+    grow(cs->buf, cs->bytes, carve_into(nullptr, w, n_pad, Spad, chunk * ntiles), "hipMalloc(coherence workspace)");
+    carve_into(cs->buf, w, n_pad, Spad, chunk * ntiles);
+    const T* At = static_cast<const T*>(ctx->At);
+    HIPCHK(hipMemcpyAsync(w.qd, q.data(), Spad * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((k_coh_norms<T>), dim3(n_pad / 4u), dim3(256), 0, st, At, ldm, (uint32_t)ctx->m, n, n_pad, w.rinv);
+    HIPCHK(hipGetLastError());
+    for (size_t s0 = 0; s0 < S; s0 += chunk) {
+        const uint32_t Sc = (uint32_t)std::min(chunk, S - s0), qtiles = (Sc + kCohTile - 1u) / kCohTile;
+        hipLaunchKernelGGL((k_coh_tile<T>), dim3(qtiles, ntiles), dim3(256), 0, st, At, ldm, (const uint32_t*)(w.qd + s0),
+                           (const double*)w.rinv, ntiles, w.ps, w.pi);
         HIPCHK(hipGetLastError());
-        for (size_t s0 = 0; s0 < S; s0 += chunk) {
-            const uint32_t Sc = (uint32_t)std::min(chunk, S - s0), qtiles = (Sc + kCohTile - 1u) / kCohTile;
-            hipLaunchKernelGGL((k_coh_tile<T>), dim3(qtiles, ntiles), dim3(256), 0, st, At, ldm, (const uint32_t*)(qd + s0),
-                               (const double*)rinv, ntiles, ps, pi);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_coh_finish, dim3((Sc + 3u) / 4u), dim3(256), 0, st, (const double*)ps, (const uint32_t*)pi, ntiles, Sc,
-                               mud + s0, ptd + s0);
-            HIPCHK(hipGetLastError());
-        }
-        if (mu) HIPCHK(hipMemcpyAsync(mu, mud, S * sizeof(double), hipMemcpyDefault, st));
-        if (partner) HIPCHK(hipMemcpyAsync(partner, ptd, S * sizeof(uint32_t), hipMemcpyDefault, st));
-        HIPCHK(hipStreamSynchronize(st));                    // (q is read by the upload until here)
-    });
+        hipLaunchKernelGGL(k_coh_finish, dim3((Sc + 3u) / 4u), dim3(256), 0, st, (const double*)w.ps, (const uint32_t*)w.pi, ntiles, Sc,
+                           w.mud + s0, w.ptd + s0);
+        HIPCHK(hipGetLastError());
+    }
+    if (mu) HIPCHK(hipMemcpyAsync(mu, w.mud, S * sizeof(double), hipMemcpyDefault, st));
+    if (partner) HIPCHK(hipMemcpyAsync(partner, w.ptd, S * sizeof(uint32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));                    // (q is read by the upload until here)
     return SS_HIP_OK;
 }
 

@@ -445,16 +445,14 @@ int atom_update_impl(LearnCall<T>& c)
     wk.chunk = learn_chunk(c);
     learn_carve(learn_arena(ctx).work, wk, c, "hipMalloc(atom learning workspace)");
     if (c.total != 0u)
-        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+        HIPCHK(dl_launch_lists<T>(ctx, c.place.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
                                   wk.sw, ix.s2, ix.bad));
     std::vector<T> tmp;
     if (c.total != 0u || c.objective) {
         for (size_t b0 = 0; b0 < B; b0 += wk.chunk) {
             const uint32_t Bc = (uint32_t)std::min(wk.chunk, B - b0);
-            const T* yd = c.Y + (ptrdiff_t)b0 * c.y_stride;
-            long long ys = c.y_stride, yi = c.incy;
-            if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, b0, Bc, tmp); yd = wk.ybuf; ys = (long long)m; yi = 1; }
-            HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, c.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
+            const ChunkSignals<T> y = chunk_signals<T>(ctx, c.Y, c.y_stride, c.incy, c.y_dev, wk.ybuf, b0, Bc, tmp);
+            HIPCHK(dl_launch_residuals<T>(ctx, y.yd, y.ys, y.yi, c.place.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
             if (c.total != 0u) {
                 hipLaunchKernelGGL((k_dl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, At, ldm, (const uint32_t*)ix.dcols,
                                    (const uint32_t*)ix.off, (const uint32_t*)wk.sb, (const T*)wk.sw, (const T*)ix.s2, (const T*)wk.R, (uint32_t)b0,
@@ -566,8 +564,7 @@ void learn_free(ss_hip_ctx* ctx)
 {
     if (!ctx->learn) return;
     LearnArena& a = learn_arena(ctx);
-    for (WorkArena* w : { &a.index, &a.work, &a.vc })
-        if (w->buf) (void)hipFree(w->buf);
+    for (WorkArena* w : { &a.index, &a.work, &a.vc }) arena_free(*w);
     delete &a;
     ctx->learn = nullptr;
 }

@@ -254,15 +254,13 @@ int js_fetch_offsets(ss_hip_ctx* ctx, WorkArena& js, const char* who, const uint
     uint32_t* stage = cw.take<uint32_t>(Gn + 1);
     const uint32_t* doff = group_off;
     if (!on_device(group_off)) { HIPCHK(hipMemcpyAsync(stage, group_off, (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = stage; }
-    HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
+    flag_arm(bad, st);
     hipLaunchKernelGGL(k_js_check, dim3((uint32_t)((Gn + 256) / 256)), dim3(256), 0, st, doff, (uint32_t)Gn, (uint32_t)B, bad);
     HIPCHK(hipGetLastError());
-    uint32_t first_bad = kTcNone;
+    uint32_t first_bad;
     hoff.resize(Gn + 1);
-    HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hoff.data(), doff, (Gn + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (first_bad != kTcNone) {
+    flag_fetch(&first_bad, bad, st, 1, hoff.data(), doff, (Gn + 1) * sizeof(uint32_t));
+    if (first_bad != kNoRecord) {
         set_err(err, errlen, std::string(who) + ": group_off must start at 0, ascend strictly, end at B and hold no group of more than " +
                                  std::to_string(kJsGroupMax) + " signals (first bad group: " + std::to_string(first_bad) + ")");
         return SS_HIP_EINVAL;
@@ -348,6 +346,20 @@ int group_topcorr_entry(ss_hip_ctx* ctx, const TcCall<T>& c, const uint32_t* gro
     });
 }
 
+// the group class residuals' pieces: a host caller's offsets, the groups' rows and best, a chunk's per-signal rows and best
+template <typename T> struct GroupClassWork {
+    uint32_t *offs, *ob, *bb;
+    T *og, *Rb;
+    void carve(Carver& cv, bool off_dev, size_t Gn, uint32_t C, size_t max_sig)
+    {
+        offs = off_dev ? nullptr : cv.take<uint32_t>(Gn + 1);
+        og = cv.take<T>(Gn * C);
+        ob = cv.take<uint32_t>(Gn);
+        Rb = cv.take<T>(max_sig * C);
+        bb = cv.take<uint32_t>(max_sig);
+    }
+};
+
 template <typename T>
 int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
                        const uint32_t* group_off, size_t Gn, T* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen)
@@ -369,35 +381,25 @@ int group_classes_impl(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride
     size_t max_sig = 0, max_grp = 0;
     tc_chunk_extent(chunks, max_sig, max_grp);
 
-    auto carve = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        uint32_t* offs = off_dev ? nullptr : cv.take<uint32_t>(Gn + 1);
-        T* og = cv.take<T>(Gn * C);
-        uint32_t* ob = cv.take<uint32_t>(Gn);
-        T* Rb = cv.take<T>(max_sig * C);
-        uint32_t* bb = cv.take<uint32_t>(max_sig);
-        use(offs, og, ob, Rb, bb);
-        return cv.off;
-    };
-    if (!arena_grow(js, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
+    GroupClassWork<T> w;
+    if (!arena_grow(js, carve_into(nullptr, w, off_dev, Gn, C, max_sig), who, err, errlen)) return SS_HIP_ENOMEM;
+    carve_into(js.buf, w, off_dev, Gn, C, max_sig);
 
-    carve(js.buf, [&](uint32_t* offs, T* og, uint32_t* ob, T* Rb, uint32_t* bb) {
-        const uint32_t* doff = group_off;
-        if (!off_dev) { HIPCHK(hipMemcpyAsync(offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = offs; }
-        for (const TcChunk& ch : chunks) {
-            const size_t b0 = ch.b0, Bc = ch.Bc;
-            rc = class_residual_rows<T>(ctx, who, Y + (ptrdiff_t)b0 * y_stride, Bc, y_stride, incy, static_cast<const unsigned char*>(records) + b0 * rb,
-                                        kmax, Rb, (ptrdiff_t)C, bb, err, errlen);
-            if (rc != SS_HIP_OK) return;                  // (a record index >= n: nothing of the caller's has been written)
-            hipLaunchKernelGGL((k_gc_reduce<T>), dim3(ch.Rc), dim3(256), 0, st, (const T*)Rb, (const uint32_t*)bb, C, doff + ch.r0, (uint32_t)b0,
-                               og + ch.r0 * C, ob + ch.r0);
-            HIPCHK(hipGetLastError());
-        }
-        if (Rg) HIPCHK(hipMemcpy2DAsync(Rg, (size_t)rg_stride * sizeof(T), og, (size_t)C * sizeof(T), (size_t)C * sizeof(T), Gn, hipMemcpyDefault, st));
-        HIPCHK(hipMemcpyAsync(best, ob, Gn * sizeof(uint32_t), hipMemcpyDefault, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    return rc;
+    const uint32_t* doff = group_off;
+    if (!off_dev) { HIPCHK(hipMemcpyAsync(w.offs, hoff.data(), (Gn + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st)); doff = w.offs; }
+    for (const TcChunk& ch : chunks) {
+        const size_t b0 = ch.b0, Bc = ch.Bc;
+        rc = class_residual_rows<T>(ctx, who, Y + (ptrdiff_t)b0 * y_stride, Bc, y_stride, incy, static_cast<const unsigned char*>(records) + b0 * rb,
+                                    kmax, w.Rb, (ptrdiff_t)C, w.bb, err, errlen);
+        if (rc != SS_HIP_OK) return rc;                   // (a record index >= n: nothing of the caller's has been written)
+        hipLaunchKernelGGL((k_gc_reduce<T>), dim3(ch.Rc), dim3(256), 0, st, (const T*)w.Rb, (const uint32_t*)w.bb, C, doff + ch.r0, (uint32_t)b0,
+                           w.og + ch.r0 * C, w.ob + ch.r0);
+        HIPCHK(hipGetLastError());
+    }
+    if (Rg) HIPCHK(hipMemcpy2DAsync(Rg, (size_t)rg_stride * sizeof(T), w.og, (size_t)C * sizeof(T), (size_t)C * sizeof(T), Gn, hipMemcpyDefault, st));
+    HIPCHK(hipMemcpyAsync(best, w.ob, Gn * sizeof(uint32_t), hipMemcpyDefault, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SS_HIP_OK;
 }
 
 template <typename T>
@@ -416,7 +418,7 @@ int group_classes_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_strid
     }
     if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, "group_class_residuals: increments and strides must be positive"); return SS_HIP_EINVAL; }
     if (Rg && rg_stride < (ptrdiff_t)C) { set_err(err, errlen, "group_class_residuals: rg_stride must be at least num_classes"); return SS_HIP_EINVAL; }
-    if (B >= 0x80000000ull) { set_err(err, errlen, "group_class_residuals: B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if ((rc = check_batch(who, B, err, errlen)) != SS_HIP_OK) return rc;
     if ((rc = js_check_groups(who, group_off, Gn, B, err, errlen)) != SS_HIP_OK) return rc;
     return guarded(err, errlen, who, [&] {
         return group_classes_impl<T>(ctx, Y, B, y_stride, incy, records, kmax, group_off, Gn, Rg, rg_stride, best, err, errlen);
@@ -429,7 +431,7 @@ void joint_free(ss_hip_ctx* ctx)
 {
     WorkArena* js = static_cast<WorkArena*>(ctx->js);
     if (!js) return;
-    if (js->buf) (void)hipFree(js->buf);
+    arena_free(*js);
     delete js;
     ctx->js = nullptr;
 }

@@ -350,7 +350,7 @@ int ksvd_impl(LearnCall<T>& c, bool serial)
     // ---- the lists; the schedule on the host from their offsets and signals ----
     std::vector<uint32_t> hoff(S + 1, 0u), hsb(total);
     if (total != 0u) {
-        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+        HIPCHK(dl_launch_lists<T>(ctx, c.place.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
                                   wk.sw, ix.s2, ix.bad));
         HIPCHK(hipMemcpyAsync(hoff.data(), ix.off, (S + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(hsb.data(), wk.sb, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -391,10 +391,10 @@ int ksvd_impl(LearnCall<T>& c, bool serial)
     if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, 0, B, tmp); yd = wk.ybuf; ysd = (long long)m; yid = 1; }
     for (size_t b0 = 0; b0 < B; b0 += kKsResidualRows) {
         const uint32_t Bc = (uint32_t)std::min<size_t>(kKsResidualRows, B - b0);
-        HIPCHK(dl_launch_residuals<T>(ctx, yd + (ptrdiff_t)b0 * ysd, ysd, yid, c.din + b0 * rb, rb, c.kmax, Bc, wk.R + b0 * ldm, ix.part + b0 * per));
+        HIPCHK(dl_launch_residuals<T>(ctx, yd + (ptrdiff_t)b0 * ysd, ysd, yid, c.place.din + b0 * rb, rb, c.kmax, Bc, wk.R + b0 * ldm, ix.part + b0 * per));
     }
     if (c.objective) HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj));
-    if (c.dout != c.din) HIPCHK(hipMemcpyAsync(c.dout, c.din, B * rb, hipMemcpyDeviceToDevice, st));
+    if (c.place.dout != c.place.din) HIPCHK(hipMemcpyAsync(c.place.dout, c.place.din, B * rb, hipMemcpyDeviceToDevice, st));
 
     // ---- the levels: three launches each, back to back ----
     for (uint32_t l = 0; l < nlevels; ++l) {
@@ -410,13 +410,13 @@ int ksvd_impl(LearnCall<T>& c, bool serial)
         if (np != 0u)
             hipLaunchKernelGGL((k_ks_pairs<T>), dim3(np), dim3(kClsThreads), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols,
                                (const uint32_t*)(wk.pair_b + pfirst[l]), (const uint32_t*)(wk.pair_e + pfirst[l]), (const uint32_t*)wk.sb, (const T*)wk.sw,
-                               (const T*)wk.G, (const double*)ix.rho, (const uint32_t*)ix.verdict, wk.R, c.dout, rb, c.kmax, ntiles);
+                               (const T*)wk.G, (const double*)ix.rho, (const uint32_t*)ix.verdict, wk.R, c.place.dout, rb, c.kmax, ntiles);
         HIPCHK(hipGetLastError());
     }
 
     // ---- the objective after, V in a device caller's strides; the copies out and apply from v in place over g ([S][ldm]) ----
     if (c.objective) {
-        hipLaunchKernelGGL((k_ks_resnorm<T>), dim3(Bu, ntiles), dim3(kClsThreads), 0, st, (const T*)wk.R, ldm, c.din, rb, c.kmax, ix.part);
+        hipLaunchKernelGGL((k_ks_resnorm<T>), dim3(Bu, ntiles), dim3(kClsThreads), 0, st, (const T*)wk.R, ldm, c.place.din, rb, c.kmax, ix.part);
         HIPCHK(hipGetLastError());
         HIPCHK(dl_launch_objective(ctx, ix.part, per, Bu, ix.sig, ix.obj + 1));
     }

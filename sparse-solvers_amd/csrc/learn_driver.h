@@ -49,13 +49,10 @@ template <typename T> struct LearnCall {
     std::vector<uint32_t> hc = {};
     size_t m = 0, n = 0, rb = 0;
     uint32_t ldm = 0, ntiles = 0, per = 0;
-    bool in_dev = false, out_dev = false, y_dev = false, v_dev = false;
-    // learn_open: the slot map (it lives as long as the call: its upload is asynchronous); din: the input records on the device;
-    // dout: where the output records are written there (a host caller's: the staging, in place when the input is staged too);
-    // the lists' total and longest length
+    bool y_dev = false, v_dev = false;
+    RecordPlace place{};                 // (learn_open stages: place.din, place.dout)
+    // learn_open: the slot map (it lives as long as the call: its upload is asynchronous); the lists' total and longest length
     std::vector<uint32_t> slots = {};
-    const unsigned char* din = nullptr;
-    unsigned char* dout = nullptr;
     uint32_t total = 0, longest = 0;
 };
 
@@ -83,16 +80,12 @@ int learn_check_args(const LearnCall<T>& c, const LearnRules& r, bool& empty)
     if (!c.Y) return fail(r.null_y);
     if (r.weighted && (rc = weights_check_args(c.ctx, c.who, r.W, r.w_stride, c.err, c.errlen)) != SS_HIP_OK) return rc;
     if (r.own) return fail(r.own);
-    if (reinterpret_cast<uintptr_t>(c.records_out) & 7u) return fail("records_out must be 8-byte aligned");
+    if ((rc = check_out_aligned(c.who, c.records_out, c.err, c.errlen)) != SS_HIP_OK) return rc;
     if (r.flags & ~r.mask) return fail("unknown flag bit");
     if (r.nothing) return fail(r.nothing);
     if (c.incy <= 0 || c.y_stride <= 0 || (c.V && (c.rs <= 0 || c.cs <= 0))) return fail("increments and strides must be positive");
     if (c.B >= 0x80000000ull || (unsigned long long)c.B * c.kmax >= 0xffffffffull) return fail("B * kmax must stay below 2^32");
-    if (c.records_out && c.records_out != c.records) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(c.records), b = reinterpret_cast<uintptr_t>(c.records_out);
-        const size_t bytes = c.B * record_bytes(c.kmax, sizeof(T));
-        if (a < b + bytes && b < a + bytes) return fail("records and records_out overlap in part");
-    }
+    if ((rc = check_overlap(c.who, c.records, c.records_out, c.B * record_bytes(c.kmax, sizeof(T)), c.err, c.errlen)) != SS_HIP_OK) return rc;
     empty = c.B == 0 || (c.cols && c.S == 0);               // (every argument above was checked all the same)
     if (!empty && c.cols && c.S > c.ctx->n) return fail("more columns than the dictionary has (a column is named twice)");
     return SS_HIP_OK;
@@ -126,28 +119,19 @@ int learn_atoms(LearnCall<T>& c)
     } else {
         c.S = c.n;
     }
-    c.in_dev = on_device(c.records);
-    c.out_dev = c.records_out != nullptr && on_device(c.records_out);
+    c.place = RecordPlace(c.records, c.records_out, c.B * c.rb);
     c.y_dev = on_device(c.Y);
     c.v_dev = c.V != nullptr && on_device(c.V);
     return SS_HIP_OK;
 }
 
 // the bytes x.carve takes, then x carved out of the arena (grown to them)
-template <typename X, typename T>
-size_t learn_bytes(X& x, const LearnCall<T>& c)
-{
-    Carver cv(nullptr);
-    x.carve(cv, c);
-    return cv.off;
-}
-
+template <typename X, typename T> size_t learn_bytes(X& x, const LearnCall<T>& c) { return carve_into(nullptr, x, c); }
 template <typename X, typename T>
 void learn_carve(WorkArena& a, X& x, const LearnCall<T>& c, const char* what)
 {
-    grow(a.buf, a.bytes, learn_bytes(x, c), what);
-    Carver cv(a.buf);
-    x.carve(cv, c);
+    grow(a, learn_bytes(x, c), what);
+    carve_into(a.buf, x, c);
 }
 
 // the index's common pieces.  A unit's struct derives from it and states carve(): head, its own partial sums, tail
@@ -159,7 +143,7 @@ template <typename T> struct LearnIndex {
     uint32_t *dusage, *sel;
     void head(Carver& cv, const LearnCall<T>& c, size_t nobj)
     {
-        stage = (!c.in_dev || (c.records_out && !c.out_dev)) ? cv.take<unsigned char>(c.B * c.rb) : nullptr;
+        stage = c.place.carve(cv);
         slot_of = c.cols ? cv.take<uint32_t>(c.n) : nullptr;
         dcols = c.cols ? cv.take<uint32_t>(c.S) : nullptr;
         counts = cv.take<uint32_t>(c.S);
@@ -197,23 +181,19 @@ template <typename T>
 int learn_open(LearnCall<T>& c, const LearnIndex<T>& ix)
 {
     hipStream_t st = c.ctx->stream;
-    c.din = static_cast<const unsigned char*>(c.records);
-    if (!c.in_dev) { HIPCHK(hipMemcpyAsync(ix.stage, c.records, c.B * c.rb, hipMemcpyHostToDevice, st)); c.din = ix.stage; }
-    c.dout = !c.records_out ? nullptr : c.out_dev ? static_cast<unsigned char*>(c.records_out) : ix.stage;
+    c.place.stage_in(ix.stage, st);
     if (c.cols) {
         c.slots.assign(c.n, kDlNone);
         for (size_t s = 0; s < c.S; ++s) c.slots[c.hc[s]] = (uint32_t)s;
         HIPCHK(hipMemcpyAsync(ix.slot_of, c.slots.data(), c.n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(ix.dcols, c.hc.data(), c.S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
-    HIPCHK(dl_launch_count(c.ctx, c.din, c.rb, c.kmax, (uint32_t)c.B, ix.slot_of, (uint32_t)c.S, ix.counts, ix.off, ix.bad));
-    uint32_t first_bad = kDlNone, tail[2] = { 0u, 0u };
-    HIPCHK(hipMemcpyAsync(&first_bad, ix.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(tail, ix.off + c.S, sizeof(tail), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(dl_launch_count(c.ctx, c.place.din, c.rb, c.kmax, (uint32_t)c.B, ix.slot_of, (uint32_t)c.S, ix.counts, ix.off, ix.bad));
+    uint32_t first_bad, tail[2] = { 0u, 0u };
+    flag_fetch(&first_bad, ix.bad, st, 1, tail, ix.off + c.S, sizeof(tail));
     c.total = tail[0];
     c.longest = tail[1];
-    return first_bad != kDlNone ? bad_index(first_bad, c.who, c.err, c.errlen) : SS_HIP_OK;
+    return first_bad != kNoRecord ? bad_index(first_bad, c.who, c.err, c.errlen) : SS_HIP_OK;
 }
 
 // the signals whose residuals a chunked call holds at once: the byte budget, kDlChunkMax, the dl_chunk_max option
@@ -247,7 +227,7 @@ int learn_finish(const LearnCall<T>& c, const LearnIndex<T>& ix, size_t nobj, co
         hus.resize(S);
         HIPCHK(hipMemcpyAsync(hus.data(), ix.dusage, S * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
-    if (c.records_out && !c.out_dev) HIPCHK(hipMemcpyAsync(c.records_out, ix.stage, c.B * c.rb, hipMemcpyDeviceToHost, st));
+    c.place.copy_out(ix.stage, st);
     if (c.V && !c.v_dev) {
         std::vector<T> tmp(S * m);
         HIPCHK(hipMemcpy2DAsync(tmp.data(), m * sizeof(T), block, (size_t)c.ldm * sizeof(T), m * sizeof(T), S, hipMemcpyDeviceToHost, st));
@@ -263,7 +243,7 @@ int learn_finish(const LearnCall<T>& c, const LearnIndex<T>& ix, size_t nobj, co
     if (pos.empty()) return SS_HIP_OK;
     const size_t nc = pos.size();
     WorkArena& vc = learn_arena(c.ctx).vc;
-    grow(vc.buf, vc.bytes, nc * m * sizeof(T), "hipMalloc(atom learning: changed atoms)");
+    grow(vc, nc * m * sizeof(T), "hipMalloc(atom learning: changed atoms)");
     T* Vc = reinterpret_cast<T*>(vc.buf);
     HIPCHK(hipMemcpyAsync(ix.sel, pos.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ix.sel + S, ccols.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, st));

@@ -1,7 +1,9 @@
-// What the translation units that read compact records share (classify.hip, dictlearn.hip): the 1024-row register tile of the
-// streaming kernels and its fixed reduction order, a record's values read and written, the entry points' common checks, and the host
-// helpers around a chunked workspace (grow, Carver, upload_rows).  Errors, pointers and the record's size come from host_common.h.
-// Everything sits in an unnamed namespace: each unit gets its own copy, nothing here is part of the library's link surface.
+// What the units that read compact records share (classify.hip, refit.hip, topcorr.hip, joint.hip, the learners; tc_driver.h and
+// learn_driver.h include it): the 1024-row register tile of the streaming kernels and its fixed reduction order, a record's values read
+// and written, its index check on the device, the entry points' common checks and repeated clauses (check_*), and the host steps a record
+// call runs between its own launches, each stated once: a workspace grown and carved into the call's named pieces (grow, Carver,
+// carve_into), where the records live (RecordPlace), the bad-record flag (flag_*), a chunk's signals (chunk_signals, upload_rows).  Errors
+// and pointers come from host_common.h.  Unnamed namespace: each unit gets its own copy, nothing here is part of the library's link surface.
 #pragma once
 
 #include "host_common.h"
@@ -28,6 +30,9 @@ inline void grow(unsigned char*& p, size_t& have, size_t need, const char* what)
     have = need;
 }
 
+inline void grow(WorkArena& a, size_t need, const char* what) { grow(a.buf, a.bytes, need, what); }
+inline void arena_free(WorkArena& a) { if (a.buf) (void)hipFree(a.buf); a = WorkArena(); }
+
 // carves 256-byte aligned pieces out of the arena; with base == nullptr it only adds up
 struct Carver {
     unsigned char* base;
@@ -40,6 +45,14 @@ struct Carver {
         return p;
     }
 };
+
+// a call's pieces are the members of a struct x with x.carve(Carver&, args...): carved at `base` (nullptr: only sized) -> their bytes
+template <typename X, typename... A> size_t carve_into(unsigned char* base, X& x, const A&... a)
+{
+    Carver cv(base);
+    x.carve(cv, a...);
+    return cv.off;
+}
 
 // (the values of a fp64 record sit at 16 + 4 kmax: 4-byte aligned only when kmax is odd)
 __device__ inline float load_val(const unsigned char* p, uint32_t e, float) { return reinterpret_cast<const float*>(p)[e]; }
@@ -80,6 +93,15 @@ template <typename T> __device__ inline typename ClsVec<T>::type cls_pack(const 
     return out;
 }
 
+// a stored index >= n of the record at r (Krec: its word 0) puts b into *bad; the workgroup's 64 lanes stride over them, none is an address
+__device__ inline void rec_check_indices(const unsigned char* r, uint32_t Krec, uint32_t kmax, uint32_t n, uint32_t b, uint32_t* bad)
+{
+    const uint32_t K = Krec < kmax ? Krec : kmax;
+    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
+    for (uint32_t e = threadIdx.x; e < K; e += 64u)
+        if (idx[e] >= n) atomicMin(bad, b);
+}
+
 // the atom learners' words (dictlearn.hip, ksvd.hip, wdictlearn.hip): a column that is not requested; the usage bit of an atom that
 // had users but was left as it is; the first position in sb[lo .. hi) whose signal is >= b (an atom's list is ascending)
 constexpr uint32_t kDlNone = 0xffffffffu;
@@ -117,6 +139,24 @@ int check_common(const ss_hip_ctx* ctx, const char* who, const void* records, bo
     return SS_HIP_OK;
 }
 
+// the clauses several entry points repeat, each called at the position where that call reports it
+inline int clause(bool broken, const char* who, const char* text, char* err, size_t errlen)
+{
+    if (broken) set_err(err, errlen, std::string(who) + ": " + text);
+    return broken ? SS_HIP_EINVAL : SS_HIP_OK;
+}
+inline int check_out_aligned(const char* who, const void* out, char* err, size_t errlen) { return clause(reinterpret_cast<uintptr_t>(out) & 7u, who, "records_out must be 8-byte aligned", err, errlen); }
+inline int check_overlap(const char* who, const void* records, const void* out, size_t bytes, char* err, size_t errlen)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(records), b = reinterpret_cast<uintptr_t>(out);     // (out null or the records themselves: fine)
+    return clause(b && b != a && a < b + bytes && b < a + bytes, who, "records and records_out overlap in part", err, errlen);
+}
+inline int check_batch(const char* who, size_t B, char* err, size_t errlen) { return clause(B >= 0x80000000ull, who, "B must stay below 2^31", err, errlen); }
+inline int check_r_stride(const char* who, const void* R, ptrdiff_t r_stride, uint32_t C, char* err, size_t errlen)
+{
+    return clause(R && r_stride < (ptrdiff_t)C, who, "r_stride must be at least num_classes", err, errlen);
+}
+
 inline int bad_index(uint32_t first_bad, const char* who, char* err, size_t errlen)
 {
     set_err(err, errlen, std::string(who) + ": record " + std::to_string(first_bad) + " holds a column index >= n");
@@ -138,6 +178,57 @@ void upload_rows(ss_hip_ctx* ctx, T* dst, const T* src, ptrdiff_t stride, ptrdif
         for (size_t i = 0; i < m; ++i) tmp[b * m + i] = src[(ptrdiff_t)(b0 + b) * stride + (ptrdiff_t)i * inc];
     HIPCHK(hipMemcpyAsync(dst, tmp.data(), Bc * m * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));        // (tmp is filled again for the next chunk)
+}
+
+// Where a call's records live on the device.  din: the input records there; dout: where the output records are written there.  A
+// host caller's records are staged and written in place when the input is staged too: one staging of `bytes` serves both.  in null:
+// the call reads no records; out null: it writes none
+struct RecordPlace {
+    const void* in = nullptr;
+    void* out = nullptr;
+    size_t bytes = 0;
+    bool in_dev = false, out_dev = false;
+    const unsigned char* din = nullptr;
+    unsigned char* dout = nullptr;
+    explicit RecordPlace(const void* records = nullptr, void* records_out = nullptr, size_t nbytes = 0)
+        : in(records), out(records_out), bytes(nbytes), in_dev(records && on_device(records)), out_dev(records_out && on_device(records_out)) {}
+    unsigned char* carve(Carver& cv) const { return (in && !in_dev) || (out && !out_dev) ? cv.take<unsigned char>(bytes) : nullptr; }
+    void stage_in(unsigned char* stage, hipStream_t st)
+    {
+        din = static_cast<const unsigned char*>(in);
+        if (in && !in_dev) { HIPCHK(hipMemcpyAsync(stage, in, bytes, hipMemcpyHostToDevice, st)); din = stage; }
+        dout = !out ? nullptr : out_dev ? static_cast<unsigned char*>(out) : stage;
+    }
+    void copy_out(const unsigned char* stage, hipStream_t st) const { if (out && !out_dev) HIPCHK(hipMemcpyAsync(out, stage, bytes, hipMemcpyDeviceToHost, st)); }
+};
+
+// The bad-record flag: words a check kernel lowers by atomicMin (kNoRecord: nothing found), armed in front of the launches; fetched
+// behind them with the stream synchronised (also_*: a second read-back that rides the same synchronise); a call's verdict from one word
+constexpr uint32_t kNoRecord = 0xffffffffu;
+inline void flag_arm(uint32_t* bad, hipStream_t st, size_t words = 1) { HIPCHK(hipMemsetAsync(bad, 0xff, words * sizeof(uint32_t), st)); }
+inline void flag_fetch(uint32_t* out, const uint32_t* bad, hipStream_t st, size_t words = 1, void* also_dst = nullptr, const void* also_src = nullptr,
+                       size_t also_bytes = 0)
+{
+    HIPCHK(hipMemcpyAsync(out, bad, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (also_dst) HIPCHK(hipMemcpyAsync(also_dst, also_src, also_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+
+inline int flag_verdict(const uint32_t* bad, hipStream_t st, const char* who, char* err, size_t errlen)
+{
+    uint32_t first_bad;
+    flag_fetch(&first_bad, bad, st);
+    return first_bad != kNoRecord ? bad_index(first_bad, who, err, errlen) : SS_HIP_OK;
+}
+
+// the signals [b0, b0 + Bc) where the kernels read them: the caller's on the device, or uploaded into ybuf ([Bc][m], contiguous)
+template <typename T> struct ChunkSignals { const T* yd; long long ys, yi; };
+template <typename T>
+ChunkSignals<T> chunk_signals(ss_hip_ctx* ctx, const T* Y, ptrdiff_t y_stride, ptrdiff_t incy, bool y_dev, T* ybuf, size_t b0, size_t Bc, std::vector<T>& tmp)
+{
+    if (y_dev) return { Y + (ptrdiff_t)b0 * y_stride, (long long)y_stride, (long long)incy };
+    upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp);
+    return { ybuf, (long long)ctx->m, 1ll };
 }
 
 }  // namespace

@@ -100,10 +100,8 @@ template <> struct RfMma<double> {
 };
 
 struct RefitState {
-    unsigned char* batch = nullptr;    // per call: staged records (a host caller's), status, residual norms, the bad-index word
-    size_t batch_bytes = 0;
-    unsigned char* arena = nullptr;    // per chunk of signals: the Gram partials, a host caller's signals
-    size_t arena_bytes = 0;
+    WorkArena batch;                   // per call: staged records (a host caller's), status, residual norms, the bad-index word
+    WorkArena arena;                   // per chunk of signals: the Gram partials, a host caller's signals
 };
 
 RefitState* state_of(ss_hip_ctx* ctx)
@@ -124,10 +122,7 @@ void k_rf_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax,
     const uint32_t b = blockIdx.x;
     const unsigned char* r = rec + (size_t)b * rb;
     const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
-    const uint32_t K = Krec < kmax ? Krec : kmax;
-    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
-    for (uint32_t e = threadIdx.x; e < K; e += 64u)
-        if (idx[e] >= n) atomicMin(bad, b);
+    rec_check_indices(r, Krec, kmax, n, b, bad);
     if (threadIdx.x == 0)
         stat[b] = Krec == 0u ? (uint32_t)SS_HIP_REFIT_EMPTY : Krec > kmax ? (uint32_t)SS_HIP_REFIT_TRUNCATED
                   : Krec > (uint32_t)SS_HIP_REFIT_KMAX ? (uint32_t)SS_HIP_REFIT_TOO_LARGE : (uint32_t)SS_HIP_REFIT_DONE;
@@ -568,6 +563,24 @@ void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, co
                            (const T*)nullptr, 0ll);
 }
 
+// the batch's pieces in one buffer (the staging, the per-signal outputs, the bad-index word), a chunk's in the other
+template <typename T> struct RfWork {
+    unsigned char* stage;
+    uint32_t *stat, *bad, *drop;
+    T *rn, *part, *ybuf;
+    double* rnd;
+    void carve(Carver& cv, const RecordPlace& place, size_t B, bool nonneg)
+    {
+        stage = place.carve(cv);
+        stat = cv.take<uint32_t>(B);
+        rn = cv.take<T>(B);
+        rnd = cv.take<double>(B);
+        bad = cv.take<uint32_t>(1);
+        drop = nonneg ? cv.take<uint32_t>(B) : nullptr;
+    }
+    void carve(Carver& cv, size_t part_elems, size_t y_elems) { part = cv.take<T>(part_elems); ybuf = y_elems ? cv.take<T>(y_elems) : nullptr; }
+};
+
 // Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit.  nonneg: k_rf_nnls in
 // k_rf_solve's place, its capacity, `dropped` (may be null) behind status
 template <typename T>
@@ -582,90 +595,64 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, Bu = (uint32_t)B;
     const uint32_t nchunks = (uint32_t)((m + kRfRows - 1) / kRfRows);
     const uint32_t kcap = std::min<uint32_t>(kmax, nonneg ? SS_HIP_NNLS_KMAX : SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
-    const bool in_dev = on_device(records), out_dev = on_device(records_out), y_dev = on_device(Y);
+    RecordPlace place(records, records_out, B * rb);
+    const bool y_dev = on_device(Y);
     if (nonneg ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>()) : (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>())) {
         set_err(err, errlen, std::string(who) + ": the device does not give a workgroup the LDS of a support this large");
         return SS_HIP_ERUNTIME;
     }
 
     // ---- the batch's records where the kernels read and write them, the per-signal outputs ----
-    auto carve_batch = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        unsigned char* stage = (in_dev && out_dev) ? nullptr : cv.take<unsigned char>(B * rb);
-        uint32_t* stat = cv.take<uint32_t>(B);
-        T* rn = cv.take<T>(B);
-        double* rnd = cv.take<double>(B);
-        uint32_t* bad = cv.take<uint32_t>(1);
-        uint32_t* drop = nonneg ? cv.take<uint32_t>(B) : nullptr;
-        use(stage, stat, rn, rnd, bad, drop);
-        return cv.off;
-    };
-    grow(rs->batch, rs->batch_bytes, carve_batch(nullptr, [](auto...) {}), "hipMalloc(refit batch)");
+    RfWork<T> w;
+    grow(rs->batch, carve_into(nullptr, w, place, B, nonneg), "hipMalloc(refit batch)");
+    carve_into(rs->batch.buf, w, place, B, nonneg);
     const size_t per = (size_t)nchunks * tile_cap * 256u * sizeof(T) + (y_dev ? 0 : m * sizeof(T)) + 512;
     const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kRfChunkMax, kRfChunkBytes / per)));
-    auto carve_arena = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        T* part = cv.take<T>(chunk * nchunks * tile_cap * 256u);
-        T* ybuf = y_dev ? nullptr : cv.take<T>(chunk * m);
-        use(part, ybuf);
-        return cv.off;
-    };
-    grow(rs->arena, rs->arena_bytes, carve_arena(nullptr, [](auto...) {}), "hipMalloc(refit workspace)");
+    const size_t part_elems = chunk * nchunks * tile_cap * 256u, y_elems = y_dev ? 0 : chunk * m;
+    grow(rs->arena, carve_into(nullptr, w, part_elems, y_elems), "hipMalloc(refit workspace)");
+    carve_into(rs->arena.buf, w, part_elems, y_elems);
 
-    int rc = SS_HIP_OK;
-    carve_batch(rs->batch, [&](unsigned char* stage, uint32_t* stat, T* rn, double* rnd, uint32_t* bad, uint32_t* drop) {
-        // din: the input records on the device; dout: where the output records are written there (a host caller's: the staging,
-        // in place when the input is staged too)
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-        unsigned char* dout = out_dev ? static_cast<unsigned char*>(records_out) : stage;
-        HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_rf_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, stat, bad);
+    place.stage_in(w.stage, st);
+    flag_arm(w.bad, st);
+    hipLaunchKernelGGL(k_rf_check, dim3(Bu), dim3(64), 0, st, place.din, rb, kmax, n, w.stat, w.bad);
+    HIPCHK(hipGetLastError());
+    if (const int rc = flag_verdict(w.bad, st, who, err, errlen)) return rc;       // (nothing has been written when a record is invalid)
+    if (nonneg) {
+        hipLaunchKernelGGL(k_rf_cap, dim3((Bu + 255u) / 256u), dim3(256), 0, st, place.din, rb, (uint32_t)SS_HIP_NNLS_KMAX, w.stat, Bu);
         HIPCHK(hipGetLastError());
-        uint32_t first_bad = 0xffffffffu;
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record is invalid)
-        if (first_bad != 0xffffffffu) { rc = bad_index(first_bad, who, err, errlen); return; }
-        if (nonneg) {
-            hipLaunchKernelGGL(k_rf_cap, dim3((Bu + 255u) / 256u), dim3(256), 0, st, din, rb, (uint32_t)SS_HIP_NNLS_KMAX, stat, Bu);
-            HIPCHK(hipGetLastError());
-        }
+    }
 
-        std::vector<T> tmp;
-        carve_arena(rs->arena, [&](T* part, T* ybuf) {
-            for (size_t b0 = 0; b0 < B; b0 += chunk) {
-                const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
-                const T* yd = Y + (ptrdiff_t)b0 * y_stride;
-                long long ys = y_stride, yi = incy;
-                if (!y_dev) { upload_rows<T>(ctx, ybuf, Y, y_stride, incy, b0, Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-                const T* At = static_cast<const T*>(ctx->At);
-                const T* wd = Wd ? Wd + (ptrdiff_t)b0 * ws : nullptr;
-                if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
-                else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
-                else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, yd, ys, yi, din + b0 * rb, rb, stat + b0, part, tile_cap, wd, ws);
-                if (nonneg)
-                    hipLaunchKernelGGL((k_rf_nnls<T>), dim3(Bc), dim3(256), rf_nnls_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
-                                       dout + b0 * rb, rb, kmax, stat + b0, drop + b0);
-                else
-                    hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)part, nchunks, tile_cap, din + b0 * rb,
-                                       dout + b0 * rb, rb, kmax, stat + b0);
-                HIPCHK(hipGetLastError());
-            }
-        });
-        if (resnorm) {
-            const int rr = Wd ? weighted_residual_rows<T>(ctx, who, false, Y, B, y_stride, incy, dout, kmax, rn, 1, nullptr, nullptr, Wd, ws, err, errlen)
-                              : record_residual_norms<T>(ctx, who, Y, B, y_stride, incy, dout, kmax, rn, err, errlen);
-            if (rr != SS_HIP_OK) { rc = rr; return; }
-            hipLaunchKernelGGL((k_rf_widen<T>), dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const T*)rn, rnd, Bu);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(resnorm, rnd, B * sizeof(double), hipMemcpyDefault, st));
-        }
-        if (status) HIPCHK(hipMemcpyAsync(status, stat, B * sizeof(uint32_t), hipMemcpyDefault, st));
-        if (nonneg && dropped) HIPCHK(hipMemcpyAsync(dropped, drop, B * sizeof(uint32_t), hipMemcpyDefault, st));
-        if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    return rc;
+    std::vector<T> tmp;
+    for (size_t b0 = 0; b0 < B; b0 += chunk) {
+        const uint32_t Bc = (uint32_t)std::min(chunk, B - b0);
+        const ChunkSignals<T> y = chunk_signals<T>(ctx, Y, y_stride, incy, y_dev, w.ybuf, b0, Bc, tmp);
+        const T* At = static_cast<const T*>(ctx->At);
+        const T* wd = Wd ? Wd + (ptrdiff_t)b0 * ws : nullptr;
+        const unsigned char* recs = place.din + b0 * rb;
+        if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
+        else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
+        else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
+        if (nonneg)
+            hipLaunchKernelGGL((k_rf_nnls<T>), dim3(Bc), dim3(256), rf_nnls_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
+                               place.dout + b0 * rb, rb, kmax, w.stat + b0, w.drop + b0);
+        else
+            hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
+                               place.dout + b0 * rb, rb, kmax, w.stat + b0);
+        HIPCHK(hipGetLastError());
+    }
+    if (resnorm) {
+        const int rr = Wd ? weighted_residual_rows<T>(ctx, who, false, Y, B, y_stride, incy, place.dout, kmax, w.rn, 1, nullptr, nullptr, Wd, ws, err, errlen)
+                          : record_residual_norms<T>(ctx, who, Y, B, y_stride, incy, place.dout, kmax, w.rn, err, errlen);
+        if (rr != SS_HIP_OK) return rr;
+        hipLaunchKernelGGL((k_rf_widen<T>), dim3((Bu + 255u) / 256u), dim3(256), 0, st, (const T*)w.rn, w.rnd, Bu);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(resnorm, w.rnd, B * sizeof(double), hipMemcpyDefault, st));
+    }
+    if (status) HIPCHK(hipMemcpyAsync(status, w.stat, B * sizeof(uint32_t), hipMemcpyDefault, st));
+    if (nonneg && dropped) HIPCHK(hipMemcpyAsync(dropped, w.drop, B * sizeof(uint32_t), hipMemcpyDefault, st));
+    place.copy_out(w.stage, st);
+    HIPCHK(hipStreamSynchronize(st));
+    return SS_HIP_OK;
 }
 
 // weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks;
@@ -679,11 +666,11 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
     int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
     if (rc != SS_HIP_OK) return rc;
     if (!Y || !records_out) { set_err(err, errlen, w + ": Y and records_out must not be null"); return SS_HIP_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, w + ": records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
+    if ((rc = check_out_aligned(who, records_out, err, errlen)) != SS_HIP_OK) return rc;
     if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, w + ": increments and strides must be positive"); return SS_HIP_EINVAL; }
     if (weighted && (rc = weights_check_args(ctx, who, W, w_stride, err, errlen)) != SS_HIP_OK) return rc;
     if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
-    if (B >= 0x80000000ull) { set_err(err, errlen, w + ": B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if ((rc = check_batch(who, B, err, errlen)) != SS_HIP_OK) return rc;
     return guarded(err, errlen, who, [&]() -> int {
         const T* Wd = nullptr;
         long long ws = 0;
@@ -725,8 +712,8 @@ void refit_free(ss_hip_ctx* ctx)
 {
     RefitState* rs = static_cast<RefitState*>(ctx->rf);
     if (!rs) return;
-    if (rs->batch) (void)hipFree(rs->batch);
-    if (rs->arena) (void)hipFree(rs->arena);
+    arena_free(rs->batch);
+    arena_free(rs->arena);
     delete rs;
     ctx->rf = nullptr;
 }

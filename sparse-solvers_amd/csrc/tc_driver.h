@@ -84,7 +84,7 @@ template <typename T, typename F>
 int tc_run(const TcCall<T>& c, F&& impl)
 {
     if (c.B == 0) return SS_HIP_OK;
-    if (c.B >= 0x80000000ull) { set_err(c.err, c.errlen, std::string(c.who) + ": B must stay below 2^31"); return SS_HIP_EINVAL; }
+    if (const int rc = check_batch(c.who, c.B, c.err, c.errlen)) return rc;
     return guarded(c.err, c.errlen, c.who, impl);
 }
 
@@ -94,7 +94,7 @@ int tc_run(const TcCall<T>& c, F&& impl)
 inline bool arena_grow(WorkArena& a, size_t need, const char* who, char* err, size_t errlen)
 {
     try {
-        grow(a.buf, a.bytes, need, "hipMalloc(coding workspace)");
+        grow(a, need, "hipMalloc(coding workspace)");
     } catch (const HipFail& f) {
         if (f.code != hipErrorOutOfMemory) throw;
         (void)hipGetLastError();
@@ -144,7 +144,7 @@ int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, B = c.B, k = c.k, rb = c.records ? record_bytes(c.kmax, sizeof(T)) : 0;
     const uint32_t ldm = ctx->ldm, n_pad = ctx->n_pad, rtiles = (uint32_t)((m + kClsTileRows - 1) / kClsTileRows);
-    const bool rec_dev = c.records && on_device(c.records);
+    RecordPlace place(c.records, nullptr, B * rb);
     size_t max_sig = 0, max_rows = 0;
     tc_chunk_extent(chunks, max_sig, max_rows);
     const size_t sig_pad = (max_sig + kTcTile - 1) / kTcTile * kTcTile;
@@ -159,7 +159,7 @@ int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const
         Carver cv(base);
         norms = cv.take<double>(n_pad);
         bad = cv.take<uint32_t>(1);
-        stage = (c.records && !rec_dev) ? cv.take<unsigned char>(B * rb) : nullptr;
+        stage = place.carve(cv);
         w.oi = cv.take<uint32_t>(rows * k);
         w.oc = cv.take<T>(B * k);
         w.os = cv.take<double>(rows * k);
@@ -176,23 +176,17 @@ int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const
     w.norms = norms;
     w.rb = rb;
 
-    const unsigned char* din = static_cast<const unsigned char*>(c.records);
+    place.stage_in(stage, st);
     if (c.records) {
-        if (!rec_dev) { HIPCHK(hipMemcpyAsync(stage, c.records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-        HIPCHK(tc_launch_record_check(ctx, din, rb, c.kmax, (uint32_t)B, bad));
-        uint32_t first_bad = kTcNone;
-        HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record is invalid)
-        if (first_bad != kTcNone) return bad_index(first_bad, c.who, c.err, c.errlen);
+        HIPCHK(tc_launch_record_check(ctx, place.din, rb, c.kmax, (uint32_t)B, bad));
+        if (const int rc = flag_verdict(bad, st, c.who, c.err, c.errlen)) return rc;      // (nothing has been written when a record is invalid)
     }
     HIPCHK(v.prepare(ctx, norms));
     std::vector<T> tmp;
     for (const TcChunk& ch : chunks) {
-        const T* yd = c.Y + (ptrdiff_t)ch.b0 * c.y_stride;
-        long long ys = c.y_stride, yi = c.incy;
-        if (!y_dev) { upload_rows<T>(ctx, ybuf, c.Y, c.y_stride, c.incy, ch.b0, ch.Bc, tmp); yd = ybuf; ys = (long long)m; yi = 1; }
-        w.recs = c.records ? din + ch.b0 * rb : nullptr;
-        HIPCHK(tc_launch_residual_block<T>(ctx, yd, ys, yi, w.recs, rb, c.kmax, ch.Bc, w.R, part));
+        const ChunkSignals<T> y = chunk_signals<T>(ctx, c.Y, c.y_stride, c.incy, y_dev, ybuf, ch.b0, ch.Bc, tmp);
+        w.recs = c.records ? place.din + ch.b0 * rb : nullptr;
+        HIPCHK(tc_launch_residual_block<T>(ctx, y.yd, y.ys, y.yi, w.recs, rb, c.kmax, ch.Bc, w.R, part));
         v.chunk(ctx, c, ch, w);
     }
     HIPCHK(hipMemcpyAsync(c.idx, w.oi, rows * k * sizeof(uint32_t), hipMemcpyDefault, st));

@@ -96,11 +96,7 @@ void k_tc_check(const unsigned char* __restrict__ rec, size_t rb, uint32_t kmax,
 {
     const uint32_t b = blockIdx.x;
     const unsigned char* r = rec + (size_t)b * rb;
-    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
-    const uint32_t K = Krec < kmax ? Krec : kmax;
-    const uint32_t* idx = reinterpret_cast<const uint32_t*>(r + 16);
-    for (uint32_t e = threadIdx.x; e < K; e += 64u)
-        if (idx[e] >= n) atomicMin(bad, b);
+    rec_check_indices(r, *reinterpret_cast<const uint32_t*>(r), kmax, n, b, bad);
 }
 
 // R: [signal tiles x 128][ldm]; D: [signal tiles x 128][n_pad].  SQ: every element of At is squared once in T where it is staged
@@ -238,11 +234,7 @@ void k_tc_extend_check(const unsigned char* __restrict__ rec, size_t rb, uint32_
 {
     const uint32_t b = blockIdx.x;
     const unsigned char* r = rec + (size_t)b * rb;
-    const uint32_t Krec = *reinterpret_cast<const uint32_t*>(r);
-    const uint32_t K = Krec < kmax ? Krec : kmax;
-    const uint32_t* ri = reinterpret_cast<const uint32_t*>(r + 16);
-    for (uint32_t e = threadIdx.x; e < K; e += 64u)
-        if (ri[e] >= n) atomicMin(&bad[0], b);
+    rec_check_indices(r, *reinterpret_cast<const uint32_t*>(r), kmax, n, b, &bad[0]);
     for (uint32_t t = threadIdx.x; t < k; t += 64u) {
         const uint32_t cidx = idx[(size_t)b * k + t];
         if (cidx != kTcNone && cidx >= n) atomicMin(&bad[1], b);
@@ -322,6 +314,22 @@ void k_tc_extend(const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
+// the extension's pieces: the records' staging, a host caller's idx and coef, `added`, the two bad-index words
+template <typename T> struct ExtendWork {
+    bool idx_dev, coef_dev;
+    unsigned char* stage = nullptr;
+    uint32_t *di = nullptr, *dadd = nullptr, *bad = nullptr;
+    T* dc = nullptr;
+    void carve(Carver& cv, const RecordPlace& place, size_t B, uint32_t k)
+    {
+        stage = place.carve(cv);
+        di = idx_dev ? nullptr : cv.take<uint32_t>(B * k);
+        dc = coef_dev ? nullptr : cv.take<T>(B * k);
+        dadd = cv.take<uint32_t>(B);
+        bad = cv.take<uint32_t>(2);
+    }
+};
+
 template <typename T>
 int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, const uint32_t* idx, const T* coef, uint32_t k, void* records_out,
                 uint32_t* added, char* err, size_t errlen)
@@ -333,50 +341,33 @@ int extend_impl(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, c
     hipStream_t st = ctx->stream;
     const size_t rb = record_bytes(kmax, sizeof(T));
     const uint32_t n = (uint32_t)ctx->n, Bu = (uint32_t)B;
-    const bool in_dev = on_device(records), out_dev = on_device(records_out), idx_dev = on_device(idx), coef_dev = !coef || on_device(coef);
+    RecordPlace place(records, records_out, B * rb);
+    ExtendWork<T> w{ on_device(idx), !coef || on_device(coef) };
+    if (!arena_grow(ts, carve_into(nullptr, w, place, B, k), who, err, errlen)) return SS_HIP_ENOMEM;
+    carve_into(ts.buf, w, place, B, k);
 
-    auto carve = [&](unsigned char* base, auto&& use) {
-        Carver cv(base);
-        unsigned char* stage = (in_dev && out_dev) ? nullptr : cv.take<unsigned char>(B * rb);
-        uint32_t* di = idx_dev ? nullptr : cv.take<uint32_t>(B * k);
-        T* dc = coef_dev ? nullptr : cv.take<T>(B * k);
-        uint32_t* dadd = cv.take<uint32_t>(B);
-        uint32_t* bad = cv.take<uint32_t>(2);
-        use(stage, di, dc, dadd, bad);
-        return cv.off;
-    };
-    if (!arena_grow(ts, carve(nullptr, [](auto...) {}), who, err, errlen)) return SS_HIP_ENOMEM;
-
-    int rc = SS_HIP_OK;
-    carve(ts.buf, [&](unsigned char* stage, uint32_t* di, T* dc, uint32_t* dadd, uint32_t* bad) {
-        // din / dout: as in refit.hip (a host caller's records are staged, in place when the input is staged too)
-        const unsigned char* din = static_cast<const unsigned char*>(records);
-        if (!in_dev) { HIPCHK(hipMemcpyAsync(stage, records, B * rb, hipMemcpyHostToDevice, st)); din = stage; }
-        unsigned char* dout = out_dev ? static_cast<unsigned char*>(records_out) : stage;
-        const uint32_t* didx = idx;
-        if (!idx_dev) { HIPCHK(hipMemcpyAsync(di, idx, B * k * sizeof(uint32_t), hipMemcpyHostToDevice, st)); didx = di; }
-        const T* dcoef = coef;
-        if (!coef_dev) { HIPCHK(hipMemcpyAsync(dc, coef, B * k * sizeof(T), hipMemcpyHostToDevice, st)); dcoef = dc; }
-        HIPCHK(hipMemsetAsync(bad, 0xff, 2 * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_tc_extend_check, dim3(Bu), dim3(64), 0, st, din, rb, kmax, n, didx, k, bad);
-        HIPCHK(hipGetLastError());
-        uint32_t first_bad[2] = { kTcNone, kTcNone };
-        HIPCHK(hipMemcpyAsync(first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                // (nothing has been written when a record or a row is invalid)
-        if (first_bad[0] != kTcNone) { rc = bad_index(first_bad[0], who, err, errlen); return; }
-        if (first_bad[1] != kTcNone) {
-            set_err(err, errlen, std::string(who) + ": row " + std::to_string(first_bad[1]) + " of idx holds a column index >= n");
-            rc = SS_HIP_EINVAL;
-            return;
-        }
-        hipLaunchKernelGGL((k_tc_extend<VW>), dim3(Bu), dim3(256), (size_t)kmax * (1u + VW) * sizeof(uint32_t), st, din, dout, rb, kmax, didx,
-                           reinterpret_cast<const uint32_t*>(dcoef), k, dadd);
-        HIPCHK(hipGetLastError());
-        if (added) HIPCHK(hipMemcpyAsync(added, dadd, B * sizeof(uint32_t), hipMemcpyDefault, st));
-        if (!out_dev) HIPCHK(hipMemcpyAsync(records_out, stage, B * rb, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    });
-    return rc;
+    place.stage_in(w.stage, st);
+    const uint32_t* didx = idx;
+    if (!w.idx_dev) { HIPCHK(hipMemcpyAsync(w.di, idx, B * k * sizeof(uint32_t), hipMemcpyHostToDevice, st)); didx = w.di; }
+    const T* dcoef = coef;
+    if (!w.coef_dev) { HIPCHK(hipMemcpyAsync(w.dc, coef, B * k * sizeof(T), hipMemcpyHostToDevice, st)); dcoef = w.dc; }
+    flag_arm(w.bad, st, 2);
+    hipLaunchKernelGGL(k_tc_extend_check, dim3(Bu), dim3(64), 0, st, place.din, rb, kmax, n, didx, k, w.bad);
+    HIPCHK(hipGetLastError());
+    uint32_t first_bad[2];
+    flag_fetch(first_bad, w.bad, st, 2);                     // (nothing has been written when a record or a row is invalid)
+    if (first_bad[0] != kNoRecord) return bad_index(first_bad[0], who, err, errlen);
+    if (first_bad[1] != kNoRecord) {
+        set_err(err, errlen, std::string(who) + ": row " + std::to_string(first_bad[1]) + " of idx holds a column index >= n");
+        return SS_HIP_EINVAL;
+    }
+    hipLaunchKernelGGL((k_tc_extend<VW>), dim3(Bu), dim3(256), (size_t)kmax * (1u + VW) * sizeof(uint32_t), st, place.din, place.dout, rb, kmax, didx,
+                       reinterpret_cast<const uint32_t*>(dcoef), k, w.dadd);
+    HIPCHK(hipGetLastError());
+    if (added) HIPCHK(hipMemcpyAsync(added, w.dadd, B * sizeof(uint32_t), hipMemcpyDefault, st));
+    place.copy_out(w.stage, st);
+    HIPCHK(hipStreamSynchronize(st));
+    return SS_HIP_OK;
 }
 
 template <typename T>
@@ -387,14 +378,10 @@ int extend_entry(ss_hip_ctx* ctx, const void* records, size_t B, uint32_t kmax, 
     int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
     if (rc != SS_HIP_OK) return rc;
     if (!idx || !records_out) { set_err(err, errlen, "extend_records: idx and records_out must not be null"); return SS_HIP_EINVAL; }
-    if (reinterpret_cast<uintptr_t>(records_out) & 7u) { set_err(err, errlen, "extend_records: records_out must be 8-byte aligned"); return SS_HIP_EINVAL; }
+    if ((rc = check_out_aligned(who, records_out, err, errlen)) != SS_HIP_OK) return rc;
     if ((rc = tc_check_k(who, k, err, errlen)) != SS_HIP_OK) return rc;
-    if (B >= 0x80000000ull) { set_err(err, errlen, "extend_records: B must stay below 2^31"); return SS_HIP_EINVAL; }
-    if (records_out != records) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(records), b = reinterpret_cast<uintptr_t>(records_out);
-        const size_t bytes = B * record_bytes(kmax, sizeof(T));
-        if (a < b + bytes && b < a + bytes) { set_err(err, errlen, "extend_records: records and records_out overlap in part"); return SS_HIP_EINVAL; }
-    }
+    if ((rc = check_batch(who, B, err, errlen)) != SS_HIP_OK) return rc;
+    if ((rc = check_overlap(who, records, records_out, B * record_bytes(kmax, sizeof(T)), err, errlen)) != SS_HIP_OK) return rc;
     if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
     return guarded(err, errlen, who, [&] { return extend_impl<T>(ctx, records, B, kmax, idx, coef, k, records_out, added, err, errlen); });
 }
@@ -464,7 +451,7 @@ void topcorr_free(ss_hip_ctx* ctx)
 {
     WorkArena* ts = static_cast<WorkArena*>(ctx->tc);
     if (!ts) return;
-    if (ts->buf) (void)hipFree(ts->buf);
+    arena_free(*ts);
     delete ts;
     ctx->tc = nullptr;
 }

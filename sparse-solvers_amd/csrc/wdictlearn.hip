@@ -322,18 +322,16 @@ int wdl_impl(LearnCall<T>& c, const T* W, ptrdiff_t w_stride)
     wk.chunk = learn_chunk(c);
     learn_carve(learn_arena(ctx).work, wk, c, "hipMalloc(atom learning workspace)");
     if (c.total != 0u)
-        HIPCHK(dl_launch_lists<T>(ctx, c.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
+        HIPCHK(dl_launch_lists<T>(ctx, c.place.din, rb, c.kmax, Bu, ix.slot_of, ix.dcols, Su, ix.counts, ix.off, c.longest, wk.pair_b, wk.pair_e, wk.sb,
                                   wk.sw, ix.s2, ix.bad));
     std::vector<T> tmp;
     if (c.total != 0u || c.objective) {
         for (size_t b0 = 0; b0 < B; b0 += wk.chunk) {
             const uint32_t Bc = (uint32_t)std::min(wk.chunk, B - b0);
-            const T* yd = c.Y + (ptrdiff_t)b0 * c.y_stride;
-            long long ys = c.y_stride, yi = c.incy;
-            if (!c.y_dev) { upload_rows<T>(ctx, wk.ybuf, c.Y, c.y_stride, c.incy, b0, Bc, tmp); yd = wk.ybuf; ys = (long long)m; yi = 1; }
-            HIPCHK(dl_launch_residuals<T>(ctx, yd, ys, yi, c.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
+            const ChunkSignals<T> y = chunk_signals<T>(ctx, c.Y, c.y_stride, c.incy, c.y_dev, wk.ybuf, b0, Bc, tmp);
+            HIPCHK(dl_launch_residuals<T>(ctx, y.yd, y.ys, y.yi, c.place.din + b0 * rb, rb, c.kmax, Bc, wk.R, ix.part + b0 * per));
             hipLaunchKernelGGL((k_wdl_stage<T>), dim3(ntiles, Bc), dim3(kClsThreads), 0, st, Wd + (ptrdiff_t)b0 * wsd, wsd, (uint32_t)m, ldm,
-                               c.din + b0 * rb, rb, c.kmax, (const T*)wk.R, wk.Wb, ix.part + b0 * per);
+                               c.place.din + b0 * rb, rb, c.kmax, (const T*)wk.R, wk.Wb, ix.part + b0 * per);
             if (c.total != 0u)
                 hipLaunchKernelGGL((k_wdl_atoms<T>), dim3(Su, ntiles), dim3(kClsThreads), 0, st, ldm, (const uint32_t*)ix.off, (const uint32_t*)wk.sb,
                                    (const T*)wk.sw, (const T*)wk.R, (const T*)wk.Wb, (uint32_t)b0, (uint32_t)b0 + Bc, b0 == 0 ? 1 : 0, wk.Num, wk.Den);
@@ -346,8 +344,8 @@ int wdl_impl(LearnCall<T>& c, const T* W, ptrdiff_t w_stride)
     hipLaunchKernelGGL((k_wdl_finish<T>), dim3(Su), dim3(256), 0, st, At, ldm, (uint32_t)m, (const uint32_t*)ix.dcols, (const uint32_t*)ix.off, wk.Num,
                        (const T*)wk.Den, ntiles, out.p, out.rs, out.cs, ix.dusage, ix.nu);
     HIPCHK(hipGetLastError());
-    if (c.dout) {
-        hipLaunchKernelGGL((k_wdl_scale<T>), dim3(Bu), dim3(256), 0, st, c.din, c.dout, rb, c.kmax, (const uint32_t*)ix.slot_of, (const T*)ix.nu);
+    if (c.place.dout) {
+        hipLaunchKernelGGL((k_wdl_scale<T>), dim3(Bu), dim3(256), 0, st, c.place.din, c.place.dout, rb, c.kmax, (const uint32_t*)ix.slot_of, (const T*)ix.nu);
         HIPCHK(hipGetLastError());
     }
     return learn_finish<T>(c, ix, 1, wk.Num, out);

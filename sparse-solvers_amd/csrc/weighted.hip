@@ -221,14 +221,13 @@ int weights_on_device(ss_hip_ctx* ctx, const char* who, const T* W, size_t B, pt
         wd = dst;
         pitch = rows == 1 ? 0 : (long long)m;
     }
-    HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(unsigned long long), st));
+    flag_arm(reinterpret_cast<uint32_t*>(bad), st, 2);     // (one 64-bit word)
     const unsigned long long total = (unsigned long long)rows * m;
     const uint32_t blocks = (uint32_t)std::min<unsigned long long>((total + 255u) / 256u, 4096u);
     hipLaunchKernelGGL((k_w_check<T>), dim3(blocks), dim3(256), 0, st, wd, pitch, (uint32_t)m, total, bad);
     HIPCHK(hipGetLastError());
-    unsigned long long first_bad = kWtNoBad;
-    HIPCHK(hipMemcpyAsync(&first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                    // (nothing has been written when a weight is invalid)
+    unsigned long long first_bad;
+    flag_fetch(reinterpret_cast<uint32_t*>(&first_bad), reinterpret_cast<const uint32_t*>(bad), st, 2);   // (nothing has been written when a weight is invalid)
     if (first_bad != kWtNoBad) {
         set_err(err, errlen, std::string(who) + ": the weight of signal " + std::to_string(first_bad / m) + ", row " + std::to_string(first_bad % m) +
                                  " is negative or not finite");
