@@ -374,11 +374,32 @@ void k_res_solve(const T* __restrict__ Gs_all, uint32_t gpitch, size_t g_slot_st
 #pragma unroll
         for (int c = 0; c < CT; ++c) asm volatile("" :: "v"(rv.gv[c]));
         asm volatile("" :: "v"(rv.mine));
+        if constexpr (CT == 8) {
+            // (fp32: the scalar test stands INSIDE the statement — to the compiler a block's eight registers are updated where they
+            // are, in straight-line code.  As `if (uniform) { conditional moves }` every block's registers met a phi behind its branch,
+            // and the register allocator answered with copies of the blocks in every round: CT moves per block, taken or not)
+#define RES_CM(I) "v_cndmask_b32_e64 %[d" #I "], %[d" #I "], %[s" #I "], %[m]\n\t"
 #pragma unroll
-        for (int e = 0; e < PT; ++e) {
-            if (e_new == (uint32_t)e) {
+            for (int e = 0; e < PT; ++e) {
+                const uint32_t off = uni(e_new ^ (uint32_t)e);
+                asm volatile("s_cmp_lg_u32 %[off], 0\n\t"
+                             "s_cbranch_scc1 .Lres_place_%=\n\t"
+                             RES_CM(0) RES_CM(1) RES_CM(2) RES_CM(3) RES_CM(4) RES_CM(5) RES_CM(6) RES_CM(7)
+                             ".Lres_place_%=:"
+                             : [d0] "+v"(gr[0][e]), [d1] "+v"(gr[1][e]), [d2] "+v"(gr[2][e]), [d3] "+v"(gr[3][e]), [d4] "+v"(gr[4][e]), [d5] "+v"(gr[5][e]),
+                               [d6] "+v"(gr[6][e]), [d7] "+v"(gr[7][e])
+                             : [s0] "v"(rv.gv[0]), [s1] "v"(rv.gv[1]), [s2] "v"(rv.gv[2]), [s3] "v"(rv.gv[3]), [s4] "v"(rv.gv[4]), [s5] "v"(rv.gv[5]),
+                               [s6] "v"(rv.gv[6]), [s7] "v"(rv.gv[7]), [m] "s"(msk), [off] "s"(off)
+                             : "scc");
+            }
+#undef RES_CM
+        } else {
 #pragma unroll
-                for (int c = 0; c < CT; ++c) cmov_inplace(gr[c][e], rv.gv[c], msk);
+            for (int e = 0; e < PT; ++e) {
+                if (e_new == (uint32_t)e) {
+#pragma unroll
+                    for (int c = 0; c < CT; ++c) cmov_inplace(gr[c][e], rv.gv[c], msk);
+                }
             }
         }
     };
