@@ -788,6 +788,62 @@ int ss_hip_weighted_atom_update_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
                                     uint32_t* usage, double* objective, uint32_t flags, char* err, size_t errlen);
 
 /*
+ * Robust coding — row weights from record residuals: the step between two codings of a robust (IRLS-style) coder, on the device
+ * (added under ABI version 7; csrc/robust.hip; NOT in the reference).  The weighted calls above take the weights of a caller who
+ * knows which rows to distrust; this call makes them for corruption at unknown rows (a scarf, a saturated block, a dead channel)
+ * from what the last coding left over.  A stays on the device and only the records' columns are read.  A robust coder runs
+ * ss_hip_robust_weights_* without records (r = y), codes under W_out with the weighted calls, and repeats from those records.
+ * Y, records, kmax: as for ss_hip_top_correlations_* (records == NULL: r_b = the words of y_b, kmax is ignored).  W, w_stride: PRIOR
+ * weights in the layout of the weighted calls (a known mask, a confidence; w_stride == 0: one vector for all signals), or W == NULL:
+ * every prior weight 1 and w_stride ignored.  Every pointer may be a host or a device pointer.  For signal b, with k over the rows
+ * 0 .. m - 1 only (the padding rows m .. ldm - 1 take no part anywhere):
+ *     r_kb      = the residual of ss_hip_top_correlations_*, word for word
+ *     VISIBLE   a row whose prior weight is > 0 and whose r_kb is finite; v = the number of visible rows
+ *     med_b     = the element of rank (v - 1) / 2 (integer division), 0-based and ascending, of |r_kb| over the visible rows: a
+ *                 stored word, found by an exact selection on its bits without arithmetic; 0 for v == 0
+ *     sigma_b   = max(1.4826022185056018 * (double)med_b, sigma_min), then t = tuning * sigma_b: one operation in double each
+ *     f_kb      with a = |(double)r_kb|, decided by comparisons first: 0 for a row that is not visible, else
+ *                 SS_HIP_ROBUST_HUBER   a <= t -> 1, else (T)(t / a)
+ *                 SS_HIP_ROBUST_TUKEY   a == 0 -> 1; a < t -> u = a / t, q = 1 - u * u, (T)(q * q); else 0
+ *                 SS_HIP_ROBUST_CUTOFF  a <= t -> 1, else 0
+ *     W_out[b*wo_stride + k] = f_kb * prior_kb, one multiplication in T (f_kb itself for W == NULL)
+ *     resid[b*r_stride + k]  (may be NULL) = r_kb
+ *     scale[b]               (may be NULL) = sigma_b
+ * The scale is about zero, not about the median: the residual of a fit has no location of its own.  sigma_b == 0 (more than half of
+ * the residuals exactly zero and sigma_min == 0) gives 1 on the rows that are exactly zero and 0 elsewhere; no NaN is ever produced.
+ * A TRUNCATED record (K > kmax) does not hold its support: its W_out row is the prior's words (1 without a prior), its resid row is
+ * 0 and scale[b] is NaN.  The usual tunings are 1.345 (Huber), 4.685 (Tukey) and 2.5 (cutoff).  The signals run in chunks under
+ * ss_hip_top_correlations_*' byte budget (option "tc_chunk_max"); the workspace — per chunk the residuals [.][ldm], a host caller's
+ * signals and rows of the outputs — is the context's, grown on demand, freed with it.
+ * CONTRACT: row b of every output is a function of A, y_b, prior_b, record b, loss, tuning and sigma_min alone — bit for bit the
+ * same alone or in any batch, in any batch order, with host or device pointers, across the chunking, with w_stride == 0 or a W whose
+ * rows repeat the vector, whatever the context did before; after a column replacement it is a fresh context's result.  No
+ * floating-point atomics.  No call changes what any solve returns.
+ * Validation happens before anything is written: a failing call leaves W_out, resid and scale untouched.
+ *   SS_HIP_EINVAL  null ctx, Y or W_out; an IRLS or column-sharded context; with records: kmax outside 1 .. 4096, records not 8-byte
+ *                  aligned, a stored column index >= n (found on the device); non-positive incy or y_stride; wo_stride < m, or
+ *                  r_stride < m with resid given; with W: a negative w_stride or one in 1 .. m - 1, a weight that is negative or
+ *                  not finite (found on the device, with its signal and row); loss > 2; tuning not finite or <= 0; sigma_min not
+ *                  finite or < 0; W_out == W
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+#define SS_HIP_ROBUST_HUBER  0u
+#define SS_HIP_ROBUST_TUKEY  1u
+#define SS_HIP_ROBUST_CUTOFF 2u
+int ss_hip_robust_weights_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                              const float* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                              uint32_t loss, double tuning, double sigma_min,
+                              float* W_out, ptrdiff_t wo_stride, float* resid, ptrdiff_t r_stride, double* scale,
+                              char* err, size_t errlen);
+int ss_hip_robust_weights_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                              const double* W, ptrdiff_t w_stride, const void* records, uint32_t kmax,
+                              uint32_t loss, double tuning, double sigma_min,
+                              double* W_out, ptrdiff_t wo_stride, double* resid, ptrdiff_t r_stride, double* scale,
+                              char* err, size_t errlen);
+
+/*
  * Non-negative coding — the positive top correlations: ss_hip_top_correlations_* restricted to the atoms that a fit may ADD (added
  * under ABI version 7; csrc/nonneg.hip; NOT in the reference).  Dictionaries whose atoms are parts — training faces or spectra as
  * columns, abundances in unmixing, SRC variants that forbid subtracting one subject from another — want a code with x >= 0.  One

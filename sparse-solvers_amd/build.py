@@ -75,6 +75,8 @@ HIP_UNITS = [
     ("wdictlearn.hip", ["-ffp-contract=off"]),
     # non-negative coding: the positive selection beside topcorr.hip's (the score in double in its order), so the same flags
     ("nonneg.hip", ["-ffp-contract=off"]),
+    # robust weights from record residuals: the scale and the weight factors in double in the documented order, so the same flags (the tests' words)
+    ("robust.hip", ["-ffp-contract=off"]),
 ]
 
 

@@ -1,4 +1,5 @@
-// The host side of the four top-correlation calls (topcorr.hip, nonneg.hip, weighted.hip, joint.hip), stated once: the checks their
+// The host side of the four top-correlation calls (topcorr.hip, nonneg.hip, weighted.hip, joint.hip) and of the robust weights
+// (robust.hip, which stops behind the residual block), stated once: the checks their
 // entry points share, the arena they carve from, and the driver — stage the records, check them, the norms, then chunk by chunk the
 // signals and the residual block, and the copies out.  What a call adds is its VARIANT, which the driver never asks for its name:
 //   the chunk list   runs of signals with their runs of output rows (tc_uniform_chunks for a row a signal, joint.hip's js_chunks for
@@ -104,12 +105,14 @@ inline bool arena_grow(WorkArena& a, size_t need, const char* who, char* err, si
     return true;
 }
 
-// the bytes a signal of a chunk takes with `blocks` residual blocks and as many dot blocks (never changes a result)
+// the bytes a signal of a chunk takes with `blocks` residual blocks and `dots` dot blocks — as many, unless the call says otherwise
+// (never changes a result)
 template <typename T>
-size_t tc_signal_bytes(const ss_hip_ctx* ctx, bool y_dev, size_t blocks)
+size_t tc_signal_bytes(const ss_hip_ctx* ctx, bool y_dev, size_t blocks, size_t dots = ~(size_t)0)
 {
     const size_t rtiles = (ctx->m + kClsTileRows - 1) / kClsTileRows;
-    return blocks * (size_t)ctx->ldm * sizeof(T) + blocks * (size_t)ctx->n_pad * sizeof(T) + rtiles * 4u * sizeof(double) +
+    if (dots == ~(size_t)0) dots = blocks;
+    return blocks * (size_t)ctx->ldm * sizeof(T) + dots * (size_t)ctx->n_pad * sizeof(T) + rtiles * 4u * sizeof(double) +
            (y_dev ? 0 : ctx->m * sizeof(T));
 }
 
@@ -138,6 +141,7 @@ inline void tc_chunk_extent(const std::vector<TcChunk>& chunks, size_t& max_sig,
 
 // rows: the rows of idx / score (coef has B).  Nothing of the caller's has been written when a record is invalid.  The caller has
 // made the context's device current: that is the first thing a call does behind its checks, before it asks where a pointer lives.
+// A call that selects nothing (k == 0, idx null: robust.hip, which wants the residual block alone) has no dot block and no copies out.
 template <typename T, typename V>
 int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const std::vector<TcChunk>& chunks, V& v)
 {
@@ -164,7 +168,7 @@ int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const
         w.oc = cv.take<T>(B * k);
         w.os = cv.take<double>(rows * k);
         w.R = cv.take<T>(sig_pad * ldm);
-        w.D = cv.take<T>(sig_pad * n_pad);
+        w.D = cv.take<T>(k ? sig_pad * n_pad : 0);
         part = cv.take<double>(max_sig * rtiles * 4u);
         ybuf = y_dev ? nullptr : cv.take<T>(max_sig * m);
         v.carve(ctx, cv, max_sig, sig_pad, max_rows);
@@ -189,7 +193,7 @@ int tc_drive(ss_hip_ctx* ctx, const TcCall<T>& c, bool y_dev, size_t rows, const
         HIPCHK(tc_launch_residual_block<T>(ctx, y.yd, y.ys, y.yi, w.recs, rb, c.kmax, ch.Bc, w.R, part));
         v.chunk(ctx, c, ch, w);
     }
-    HIPCHK(hipMemcpyAsync(c.idx, w.oi, rows * k * sizeof(uint32_t), hipMemcpyDefault, st));
+    if (c.idx) HIPCHK(hipMemcpyAsync(c.idx, w.oi, rows * k * sizeof(uint32_t), hipMemcpyDefault, st));
     if (c.coef) HIPCHK(hipMemcpyAsync(c.coef, w.oc, B * k * sizeof(T), hipMemcpyDefault, st));
     if (c.score) HIPCHK(hipMemcpyAsync(c.score, w.os, rows * k * sizeof(double), hipMemcpyDefault, st));
     HIPCHK(hipStreamSynchronize(st));

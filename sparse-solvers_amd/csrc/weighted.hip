@@ -2,7 +2,7 @@
 //   ss_hip_weighted_top_correlations_*, ss_hip_weighted_refit_records_*, ss_hip_weighted_class_residuals_*.
 //
 // A 0/1 mask of observed rows (occlusion, inpainting) is the special case; robust coders supply the weights from the previous
-// residual.  A is shared by the batch and the weights are not: the atom norms become d(i, b) = sum_k w_kb a_ki^2, one per atom and
+// residual (robust.hip makes them on the device).  A is shared by the batch and the weights are not: the atom norms become d(i, b) = sum_k w_kb a_ki^2, one per atom and
 // signal, and the normal equations A_S^T W_b A_S — neither comes out of scaling Y beforehand.
 //
 // WEIGHTS, common to the three calls: row b of W at W[b * w_stride + k], k < m; w_stride == 0 is one vector shared by all signals.  A
