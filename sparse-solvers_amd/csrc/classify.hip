@@ -51,6 +51,7 @@ constexpr uint32_t kClsTruncated = 1u, kClsInvalid = 2u; // per-signal flags
 constexpr uint32_t kSigWords = 4;                        // per-signal header: K stored, segments, flags, unused
 
 struct ClassifyState {
+    Holdings own;                      // the labels
     uint32_t* labels = nullptr;        // [n_pad] class of every column (padding columns: 0)
     uint32_t num_classes = 0;
     WorkArena arena;                   // the workspace of one chunk, carved per call
@@ -60,8 +61,7 @@ struct ClassifyState {
 
 ClassifyState* state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->cls) ctx->cls = new ClassifyState();
-    return static_cast<ClassifyState*>(ctx->cls);
+    return &part<ClassifyState>(ctx->cls);
 }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
@@ -349,7 +349,7 @@ void k_cls_scatter(const T* __restrict__ src, uint32_t ld, uint32_t m, T* __rest
 
 int check_classes(const ss_hip_ctx* ctx, const char* who, char* err, size_t errlen)
 {
-    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
     if (!cs || !cs->labels) { set_err(err, errlen, std::string(who) + ": no classes set (ss_hip_set_classes)"); return SS_HIP_EINVAL; }
     return SS_HIP_OK;
 }
@@ -451,9 +451,9 @@ int class_residuals_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B
         if (const int rw = weights_check_args(ctx, who, W, w_stride, err, errlen)) return rw;
     if (B == 0) return SS_HIP_OK;
     if (incy <= 0) { set_err(err, errlen, w + ": increments must be positive"); return SS_HIP_EINVAL; }
-    if (const int rr = check_r_stride(who, R, r_stride, static_cast<const ClassifyState*>(ctx->cls)->num_classes, err, errlen)) return rr;
+    if (const int rr = check_r_stride(who, R, r_stride, ctx->cls.as<const ClassifyState>()->num_classes, err, errlen)) return rr;
     return guarded(err, errlen, who, [&]() -> int {
-        const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+        const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
         const T* Wd = nullptr;
         long long ws = 0;
         if (weighted) {
@@ -546,7 +546,7 @@ int classify_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, pt
     if (const int rq = check_classes(ctx, who, err, errlen)) return rq;
     if (B == 0) return SS_HIP_OK;
     if (incy <= 0) { set_err(err, errlen, "classify_batch: increments must be positive"); return SS_HIP_EINVAL; }
-    if (const int rr = check_r_stride(who, R, r_stride, static_cast<const ClassifyState*>(ctx->cls)->num_classes, err, errlen)) return rr;
+    if (const int rr = check_r_stride(who, R, r_stride, ctx->cls.as<const ClassifyState>()->num_classes, err, errlen)) return rr;
     return guarded(err, errlen, who, [&]() -> int {
         HIPCHK(hipSetDevice(ctx->device));
         ClassifyState* cs = state_of(ctx);
@@ -592,7 +592,7 @@ template <typename T>
 int class_residual_rows(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                         uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, char* err, size_t errlen)
 {
-    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
     return residuals_impl<T>(ctx, who, cs->labels, cs->num_classes, Y, B, y_stride, incy, records, kmax, R, r_stride, best, nullptr, err, errlen);
 }
 
@@ -609,7 +609,7 @@ int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, cons
                            const void* records, uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, double* sci, const T* Wd, long long ws,
                            char* err, size_t errlen)
 {
-    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
     return residuals_impl<T>(ctx, who, by_class ? cs->labels : nullptr, by_class ? cs->num_classes : 1u, Y, B, y_stride, incy, records, kmax, R,
                              r_stride, best, sci, err, errlen, Wd, ws);
 }
@@ -632,18 +632,8 @@ template int class_residuals_weighted<double>(ss_hip_ctx*, const double*, size_t
 
 uint32_t classify_num_classes(const ss_hip_ctx* ctx)
 {
-    const ClassifyState* cs = static_cast<const ClassifyState*>(ctx->cls);
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
     return cs && cs->labels ? cs->num_classes : 0u;
-}
-
-void classify_free(ss_hip_ctx* ctx)
-{
-    ClassifyState* cs = static_cast<ClassifyState*>(ctx->cls);
-    if (!cs) return;
-    if (cs->labels) (void)hipFree(cs->labels);
-    for (WorkArena* a : { &cs->arena, &cs->y_all, &cs->rec_all }) arena_free(*a);
-    delete cs;
-    ctx->cls = nullptr;
 }
 
 }  // namespace sship
@@ -663,7 +653,7 @@ int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_cla
         ClassifyState* cs = state_of(ctx);
         const uint32_t n = (uint32_t)ctx->n, np = ctx->n_pad;
         uint32_t* fresh = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&fresh), ((size_t)np + 1) * sizeof(uint32_t)));
+        HELD(cs->own, hipMalloc, reinterpret_cast<void**>(&fresh), ((size_t)np + 1) * sizeof(uint32_t));
         uint32_t bad = 0xffffffffu;
         hipError_t e = hipMemsetAsync(fresh, 0, (size_t)np * sizeof(uint32_t), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(fresh + np, 0xff, sizeof(uint32_t), ctx->stream);
@@ -674,13 +664,13 @@ int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_cla
         }
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, fresh + np, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(fresh); throw HipFail{ e, "set_classes: upload of the labels" }; }
+        if (e != hipSuccess) { (void)cs->own.drop(fresh); throw HipFail{ e, "set_classes: upload of the labels" }; }
         if (bad != 0xffffffffu) {
-            (void)hipFree(fresh);
+            (void)cs->own.drop(fresh);
             set_err(err, errlen, "set_classes: the label of column " + std::to_string(bad) + " is not below num_classes");
             return SS_HIP_EINVAL;
         }
-        if (cs->labels) HIPCHK(hipFree(cs->labels));
+        HIPCHK(cs->own.drop(cs->labels));
         cs->labels = fresh;
         cs->num_classes = num_classes;
         return SS_HIP_OK;

@@ -77,14 +77,14 @@ template <> struct CohMma<double> {
 __device__ inline bool coh_better(double sa, uint32_t ia, double sb, uint32_t ib) { return sa > sb || (sa == sb && ia < ib); }
 
 struct CoherenceState {
+    Holdings own;
     unsigned char* buf = nullptr;      // inverse norms, the query list, the partials of a chunk, the staged outputs
     size_t bytes = 0;
 };
 
 CoherenceState* state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->coh) ctx->coh = new CoherenceState();
-    return static_cast<CoherenceState*>(ctx->coh);
+    return &part<CoherenceState>(ctx->coh);
 }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
@@ -317,7 +317,7 @@ int coherence_impl(ss_hip_ctx* ctx, const uint32_t* cols, size_t S, double* mu, 
     CoherenceState* cs = state_of(ctx);
     const size_t chunk = std::min<size_t>(Spad, SS_HIP_COHERENCE_CHUNK);
     CohWork w;
-    grow(cs->buf, cs->bytes, carve_into(nullptr, w, n_pad, Spad, chunk * ntiles), "hipMalloc(coherence workspace)");
+    grow(cs->own, cs->buf, cs->bytes, carve_into(nullptr, w, n_pad, Spad, chunk * ntiles), "hipMalloc(coherence workspace)");
     carve_into(cs->buf, w, n_pad, Spad, chunk * ntiles);
     const T* At = static_cast<const T*>(ctx->At);
     HIPCHK(hipMemcpyAsync(w.qd, q.data(), Spad * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -366,15 +366,6 @@ template hipError_t coh_launch_norms<float>(ss_hip_ctx*, double*);
 template hipError_t coh_launch_norms<double>(ss_hip_ctx*, double*);
 template hipError_t coh_launch_norms<float, true>(ss_hip_ctx*, double*);
 template hipError_t coh_launch_norms<double, true>(ss_hip_ctx*, double*);
-
-void coherence_free(ss_hip_ctx* ctx)
-{
-    CoherenceState* cs = static_cast<CoherenceState*>(ctx->coh);
-    if (!cs) return;
-    if (cs->buf) (void)hipFree(cs->buf);
-    delete cs;
-    ctx->coh = nullptr;
-}
 
 }  // namespace sship
 

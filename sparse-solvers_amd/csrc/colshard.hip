@@ -85,14 +85,9 @@ static Rccl* rccl()
 }
 
 // ---- state of a column-sharded context (ss_hip_ctx::colshard) ----------------------------------------------------
-struct ColShard {
-    uint32_t col_lo = 0, n_total = 0, n_local = 0;
-    int rank = 0, world = 1;
-    cs_comm_t comm = nullptr;
-    bool have_host = false;
-    ss_hip_collectives host{};            // fp32 contexts
-    ss_hip_collectives_f64 host64{};      // fp64 contexts
-    uint32_t esize = 4;                   // element size of the context (4 / 8)
+// what grows with the active-set capacity (cs_ensure), owned by `grown`: a regrow is a fresh CsArrays
+struct CsArrays {
+    Holdings grown;
     uint32_t kcap = 0;
     // replicated active set (device)
     uint32_t* gam = nullptr;        // [2][kcap] sorted support, global indices (ping-pong with inv)
@@ -110,6 +105,18 @@ struct ColShard {
     uint32_t xcount = 0;            // its length in elements
     // pinned staging for host collectives
     unsigned char* hstage = nullptr;
+};
+
+struct ColShard : CsArrays {
+    ~ColShard();                          // (the communicator; the owners release the rest)
+    uint32_t col_lo = 0, n_total = 0, n_local = 0;
+    int rank = 0, world = 1;
+    cs_comm_t comm = nullptr;
+    bool have_host = false;
+    ss_hip_collectives host{};            // fp32 contexts
+    ss_hip_collectives_f64 host64{};      // fp64 contexts
+    uint32_t esize = 4;                   // element size of the context (4 / 8)
+    Holdings own;                         // agree_dev, agree_host
     // the ranks' agreement on "everything this solve needs is allocated" (made at create: it must exist when an allocation fails)
     uint64_t* agree_dev = nullptr;  // [1] device word of the RCCL all-reduce
     uint64_t* agree_host = nullptr; // [1] pinned
@@ -609,49 +616,33 @@ void cs_allreduce(ss_hip_ctx* ctx, ColShard* cs, void* buf, size_t count, int dt
     CSHIP(hipMemcpyAsync(buf, cs->hstage, bytes, hipMemcpyHostToDevice, ctx->stream));
 }
 
-void cs_free(ColShard* cs)
-{
-    if (!cs) return;
-    void* ptrs[] = { cs->gam, cs->tch, cs->trow, cs->xt, cs->ds, cs->inv, cs->AS, cs->u1, cs->u2, cs->sgn, cs->red, cs->pmin, cs->xbuf };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (cs->hstage) (void)hipHostFree(cs->hstage);
-    cs->gam = cs->tch = cs->trow = nullptr; cs->xt = cs->ds = cs->inv = cs->AS = cs->u1 = cs->u2 = cs->sgn = nullptr;
-    cs->red = nullptr; cs->pmin = nullptr; cs->xbuf = nullptr; cs->hstage = nullptr; cs->kcap = 0;
-}
-
 void cs_ensure(ss_hip_ctx* ctx, ColShard* cs, uint32_t kcap)
 {
     if (kcap <= cs->kcap) return;
     const uint32_t want = std::max<uint32_t>(kcap, std::min<uint32_t>(kKcapLimit, std::max<uint32_t>(64, cs->kcap * 2)));
-    cs_free(cs);
+    static_cast<CsArrays&>(*cs) = CsArrays();
     const size_t K = want, ldm = ctx->ldm, es = cs->esize;
-    CSHIP(hipMalloc(&cs->gam, 2 * K * 4)); CSHIP(hipMalloc(&cs->tch, 2 * K * 4)); CSHIP(hipMalloc(&cs->trow, 2 * K * 4));
-    CSHIP(hipMalloc(&cs->xt, 2 * K * es)); CSHIP(hipMalloc(&cs->ds, 2 * K * es));
-    CSHIP(hipMalloc(&cs->inv, 2 * K * K * es)); CSHIP(hipMalloc(&cs->AS, K * ldm * es));
-    CSHIP(hipMalloc(&cs->u1, K * es)); CSHIP(hipMalloc(&cs->u2, K * es)); CSHIP(hipMalloc(&cs->sgn, K * es));
+    Holdings& own = cs->grown;
+    HELD(own, hipMalloc, &cs->gam, 2 * K * 4); HELD(own, hipMalloc, &cs->tch, 2 * K * 4); HELD(own, hipMalloc, &cs->trow, 2 * K * 4);
+    HELD(own, hipMalloc, &cs->xt, 2 * K * es); HELD(own, hipMalloc, &cs->ds, 2 * K * es);
+    HELD(own, hipMalloc, &cs->inv, 2 * K * K * es); HELD(own, hipMalloc, &cs->AS, K * ldm * es);
+    HELD(own, hipMalloc, &cs->u1, K * es); HELD(own, hipMalloc, &cs->u2, K * es); HELD(own, hipMalloc, &cs->sgn, K * es);
     const size_t red_bytes = 2 * (size_t)(2 * kCsMaxWorld) * 8;
-    CSHIP(hipMalloc(&cs->red, red_bytes));
+    HELD(own, hipMalloc, &cs->red, red_bytes);
     CSHIP(hipMemsetAsync(cs->red, 0, red_bytes, ctx->stream));
-    CSHIP(hipMalloc(&cs->pmin, (size_t)kMaxScanBlocks * 2 * 8));
+    HELD(own, hipMalloc, &cs->pmin, (size_t)kMaxScanBlocks * 2 * 8);
     cs->xcount = (uint32_t)((ldm + K + 7) / 8 * 8);
-    CSHIP(hipMalloc(&cs->xbuf, (size_t)cs->xcount * es));
-    CSHIP(hipHostMalloc(reinterpret_cast<void**>(&cs->hstage), std::max((size_t)cs->xcount * es, red_bytes) + 64, hipHostMallocDefault));
+    HELD(own, hipMalloc, &cs->xbuf, (size_t)cs->xcount * es);
+    HELD(own, hipHostMalloc, reinterpret_cast<void**>(&cs->hstage), std::max((size_t)cs->xcount * es, red_bytes) + 64, hipHostMallocDefault);
     cs->kcap = want;
 }
 
 }  // namespace
 
 namespace sship {
-void colshard_destroy(ss_hip_ctx* ctx)
+ColShard::~ColShard()
 {
-    ColShard* cs = static_cast<ColShard*>(ctx->colshard);
-    if (!cs) return;
-    if (cs->comm != nullptr) { Rccl* r = rccl(); if (r) (void)r->CommDestroy(cs->comm); }
-    cs_free(cs);
-    if (cs->agree_dev) (void)hipFree(cs->agree_dev);
-    if (cs->agree_host) (void)hipHostFree(cs->agree_host);
-    delete cs;
-    ctx->colshard = nullptr;
+    if (comm != nullptr) { Rccl* r = rccl(); if (r) (void)r->CommDestroy(comm); }
 }
 }  // namespace sship
 
@@ -703,12 +694,12 @@ ss_hip_ctx* colshard_create_impl(const T* A_local, size_t m, size_t n_local, ptr
     if (!ctx) return nullptr;
     ColShard* cs = new (std::nothrow) ColShard();
     if (!cs) { set_err(err, errlen, "colshard_create: out of host memory"); ss_hip_homotopy_destroy(ctx); return nullptr; }
-    ctx->colshard = cs;
+    ctx->colshard.hold(cs);
     cs->col_lo = (uint32_t)col_lo; cs->n_total = (uint32_t)n_total; cs->rank = rank; cs->world = world;
     cs->n_local = (uint32_t)n_local;
     cs->esize = (uint32_t)sizeof(T);
-    if (hipSetDevice(device) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&cs->agree_dev), 64) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&cs->agree_host), 64, hipHostMallocDefault) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || cs->own.device(&cs->agree_dev, 64) != hipSuccess ||
+        cs->own.pinned(&cs->agree_host, 64, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
         set_err(err, errlen, "colshard_create: out of memory");
         ss_hip_homotopy_destroy(ctx);
@@ -739,9 +730,9 @@ int colshard_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint
                         T* x_local, ptrdiff_t incx, uint32_t* iter_out, double* err_out,
                         char* err, size_t errlen)
 {
-    if (!ctx || !ctx->colshard) { set_err(err, errlen, "colshard_solve: not a column-sharded context"); return SS_HIP_EINVAL; }
+    if (!ctx || ctx->colshard == nullptr) { set_err(err, errlen, "colshard_solve: not a column-sharded context"); return SS_HIP_EINVAL; }
     if (ctx->is_f64 != (sizeof(T) == 8)) { set_err(err, errlen, "colshard_solve: element type of the call does not match the context"); return SS_HIP_ETYPE; }
-    ColShard* cs = static_cast<ColShard*>(ctx->colshard);
+    ColShard* cs = ctx->colshard.as<ColShard>();
     if (!y || (!x_local && cs->n_local != 0)) { set_err(err, errlen, "colshard_solve: y and x must not be null"); return SS_HIP_EINVAL; }
     if (max_iter == 0) { set_err(err, errlen, "colshard_solve: max_iterations must be > 0"); return SS_HIP_EINVAL; }
     if (!(tol >= std::numeric_limits<T>::epsilon() && tol < T(1))) { set_err(err, errlen, "colshard_solve: tolerance must satisfy eps <= tolerance < 1"); return SS_HIP_EINVAL; }
@@ -760,17 +751,20 @@ int colshard_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint
         // the shard's own workspace: y, rhs (r, p), c, q, x, d, insup, sweep partials (homotopy.hip: Workspace<T>)
         const int rc0 = colshard_workspace(ctx, kcap);
         if (rc0 != SS_HIP_OK) throw CsFail{ "workspace allocation failed" };
-        Workspace<T>& ws0 = *static_cast<Workspace<T>*>(ctx->ws);
+        Workspace<T>& ws0 = *ctx->ws.as<Workspace<T>>();
         if (want_trace > ws0.trace_cap) {
-            if (ws0.trace) CSHIP(hipFree(ws0.trace));
-            ws0.trace = nullptr; ws0.trace_cap = 0;
-            CSHIP(hipMalloc(&ws0.trace, (size_t)want_trace * sizeof(TraceEntry)));
+            CSHIP(ws0.trace_own.drop(ws0.trace));
+            ws0.trace_cap = 0;
+            HELD(ws0.trace_own, hipMalloc, &ws0.trace, (size_t)want_trace * sizeof(TraceEntry));
             ws0.trace_cap = want_trace;
         }
     } catch (const CsFail& f) {
         (void)hipGetLastError();
         local = SS_HIP_ENOMEM;
         local_msg = f.msg;
+    } catch (const HipFail& f) {                   // (a refused take of cs_ensure or the trace buffer: CSHIP's text)
+        local = SS_HIP_ENOMEM;
+        local_msg = hip_msg(f);
     } catch (const std::bad_alloc&) {
         local = SS_HIP_ENOMEM;
         local_msg = "out of host memory";
@@ -802,7 +796,7 @@ int colshard_solve_impl(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint
     bool in_collectives = false;
     try {
         const uint32_t K = cs->kcap;
-        Workspace<T>& ws = *static_cast<Workspace<T>*>(ctx->ws);
+        Workspace<T>& ws = *ctx->ws.as<Workspace<T>>();
         hipStream_t st = ctx->stream;
         const uint32_t ldm = ctx->ldm, m = (uint32_t)ctx->m, nl = cs->n_local, np = ctx->n_pad;
         const T* At = static_cast<const T*>(ctx->At);

@@ -556,17 +556,7 @@ template hipError_t dl_launch_residuals<double>(ss_hip_ctx*, const double*, long
 
 LearnArena& learn_arena(ss_hip_ctx* ctx)
 {
-    if (!ctx->learn) ctx->learn = new LearnArena();
-    return *static_cast<LearnArena*>(ctx->learn);
-}
-
-void learn_free(ss_hip_ctx* ctx)
-{
-    if (!ctx->learn) return;
-    LearnArena& a = learn_arena(ctx);
-    for (WorkArena* w : { &a.index, &a.work, &a.vc }) arena_free(*w);
-    delete &a;
-    ctx->learn = nullptr;
+    return part<LearnArena>(ctx->learn);
 }
 
 }  // namespace sship

@@ -200,7 +200,7 @@ int replace_device_impl(ss_hip_ctx* ctx, const uint32_t* dcols, const std::vecto
         // ---- Gram columns cached in the workspace: a solve clears the slot map before it caches anything (k_la_reset), the column
         // form's table and the early form's subset are made per call — nothing of them outlives a call; the map is cleared all the same
         if (ctx->ws != nullptr) {
-            int32_t* slot_of = ctx->is_f64 ? static_cast<Workspace<double>*>(ctx->ws)->slot_of : static_cast<Workspace<float>*>(ctx->ws)->slot_of;
+            int32_t* slot_of = ctx->is_f64 ? ctx->ws.as<Workspace<double>>()->slot_of : ctx->ws.as<Workspace<float>>()->slot_of;
             if (slot_of != nullptr) HIPCHK(hipMemsetAsync(slot_of, 0xff, (size_t)np * sizeof(int32_t), st));
         }
         HIPCHK(hipStreamSynchronize(st));

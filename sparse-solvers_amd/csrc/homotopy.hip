@@ -48,7 +48,7 @@ template <typename F>
 int guarded_rt(char* err, size_t errlen, const char* prefix, F&& body) { return guarded(err, errlen, prefix, body, SS_HIP_ERUNTIME); }
 
 template <typename T>
-Workspace<T>* ws_of(ss_hip_ctx* ctx) { return static_cast<Workspace<T>*>(ctx->ws); }
+Workspace<T>* ws_of(ss_hip_ctx* ctx) { return ctx->ws.as<Workspace<T>>(); }
 
 // ---- re-layout: At[j][i] = src[i*rs + j*cs] for rows [r0, r0+R) --------------------
 template <typename T>
@@ -206,31 +206,15 @@ void k_epilogue(const uint32_t* __restrict__ st_words, uint32_t* __restrict__ hs
         }
 }
 
+// everything but the trace buffer given back, every field as in a new workspace (the move assignment releases what `own` and `cache` held)
 template <typename T>
 void release_arrays(Workspace<T>* w)
 {
-    void* ptrs[] = { w->y, w->rhs, w->cq, w->x, w->d, w->insup, w->pmax_val, w->pmax_idx,
-                     w->pmin_val, w->pmin_idx, w->gam, w->touched, w->inv[0], w->u1,
-                     w->u2, w->sgn, w->st, w->ndone, w->tile_skip, w->gcache, w->slot_of, w->c0,
-                     w->tcand, w->sw_list, w->la_dbg, w->la_sync, w->cq_alt, w->slot_identity,
-                     w->slot_col, w->solo_log, w->sub_pos, w->v_max, w->v_min, w->cand_top, w->solo_stage,
-                     w->sw_list2, w->sub_cols, w->subg };
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    TraceEntry* tr = w->trace;
-    const uint32_t tc = w->trace_cap;
-    *w = Workspace<T>();
-    w->trace = tr;
-    w->trace_cap = tc;
-}
-
-template <typename T>
-void free_ws(Workspace<T>* w)
-{
-    if (!w) return;
-    release_arrays(w);
-    if (w->trace) (void)hipFree(w->trace);
-    delete w;
+    Workspace<T> fresh;
+    fresh.trace_own = std::move(w->trace_own);
+    fresh.trace = w->trace;
+    fresh.trace_cap = w->trace_cap;
+    *w = std::move(fresh);
 }
 
 // Makes sure the workspace holds `nslots` signals and an active set of `kcap` columns each.
@@ -238,8 +222,7 @@ void free_ws(Workspace<T>* w)
 template <typename T>
 void ensure_workspace(ss_hip_ctx* ctx, uint32_t nslots, uint32_t kcap)
 {
-    if (!ctx->ws) ctx->ws = new Workspace<T>();
-    Workspace<T>* w = ws_of<T>(ctx);
+    Workspace<T>* w = &part<Workspace<T>>(ctx->ws);
     if (nslots <= w->b_cap && kcap <= w->kcap) return;
     uint32_t want_k = std::max<uint32_t>(kcap, w->kcap);
     if (kcap > w->kcap)   // grow geometrically so slightly larger max_iter does not realloc
@@ -258,25 +241,25 @@ void ensure_workspace(ss_hip_ctx* ctx, uint32_t nslots, uint32_t kcap)
     L.b_pad = b_pad;
     L.pmax_stride = kMaxSweepBlocks;
     L.pmin_stride = kMaxScanBlocks;
-    HIPCHK(hipMalloc(&w->y, B * ldm * s));
-    HIPCHK(hipMalloc(&w->rhs, 2 * (size_t)b_pad * ldm * s));
-    HIPCHK(hipMalloc(&w->cq, 2 * (size_t)b_pad * np * s));
-    HIPCHK(hipMalloc(&w->x, B * np * s));
-    HIPCHK(hipMalloc(&w->d, B * np * s));
-    HIPCHK(hipMalloc(&w->insup, B * np));
-    HIPCHK(hipMalloc(&w->pmax_val, B * L.pmax_stride * s));
-    HIPCHK(hipMalloc(&w->pmax_idx, B * L.pmax_stride * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&w->pmin_val, B * L.pmin_stride * s));
-    HIPCHK(hipMalloc(&w->pmin_idx, B * L.pmin_stride * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&w->gam, B * 2 * K * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&w->touched, B * 2 * K * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&w->inv[0], B * 2 * K * K * s));
-    HIPCHK(hipMalloc(&w->u1, B * K * s));
-    HIPCHK(hipMalloc(&w->u2, B * K * s));
-    HIPCHK(hipMalloc(&w->sgn, B * K * s));
-    HIPCHK(hipMalloc(&w->st, B * sizeof(DevState)));
-    HIPCHK(hipMalloc(&w->ndone, 64));
-    HIPCHK(hipMalloc(&w->tile_skip, ((size_t)b_pad / 128 + 1) * sizeof(uint32_t)));
+    HELD(w->own, hipMalloc, &w->y, B * ldm * s);
+    HELD(w->own, hipMalloc, &w->rhs, 2 * (size_t)b_pad * ldm * s);
+    HELD(w->own, hipMalloc, &w->cq, 2 * (size_t)b_pad * np * s);
+    HELD(w->own, hipMalloc, &w->x, B * np * s);
+    HELD(w->own, hipMalloc, &w->d, B * np * s);
+    HELD(w->own, hipMalloc, &w->insup, B * np);
+    HELD(w->own, hipMalloc, &w->pmax_val, B * L.pmax_stride * s);
+    HELD(w->own, hipMalloc, &w->pmax_idx, B * L.pmax_stride * sizeof(uint32_t));
+    HELD(w->own, hipMalloc, &w->pmin_val, B * L.pmin_stride * s);
+    HELD(w->own, hipMalloc, &w->pmin_idx, B * L.pmin_stride * sizeof(uint32_t));
+    HELD(w->own, hipMalloc, &w->gam, B * 2 * K * sizeof(uint32_t));
+    HELD(w->own, hipMalloc, &w->touched, B * 2 * K * sizeof(uint32_t));
+    HELD(w->own, hipMalloc, &w->inv[0], B * 2 * K * K * s);
+    HELD(w->own, hipMalloc, &w->u1, B * K * s);
+    HELD(w->own, hipMalloc, &w->u2, B * K * s);
+    HELD(w->own, hipMalloc, &w->sgn, B * K * s);
+    HELD(w->own, hipMalloc, &w->st, B * sizeof(DevState));
+    HELD(w->own, hipMalloc, &w->ndone, 64);
+    HELD(w->own, hipMalloc, &w->tile_skip, ((size_t)b_pad / 128 + 1) * sizeof(uint32_t));
     HIPCHK(hipMemsetAsync(w->tile_skip, 0, ((size_t)b_pad / 128 + 1) * sizeof(uint32_t), ctx->stream));
     w->inv[1] = w->inv[0] + K * K;
     w->c = w->cq;
@@ -359,9 +342,9 @@ ss_hip_ctx* create_impl(const T* A, size_t m, size_t n, ptrdiff_t rs, ptrdiff_t 
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
         ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+        HELD(ctx->own, hipStreamCreateWithFlags, &ctx->stream, hipStreamNonBlocking);
         const size_t bytes = (size_t)ctx->n_pad * ctx->ldm * sizeof(T);
-        HIPCHK(hipMalloc(&ctx->At, bytes));
+        HELD(ctx->own, hipMalloc, &ctx->At, bytes);
         HIPCHK(hipMemsetAsync(ctx->At, 0, bytes, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         upload_matrix<T>(ctx, A, rs, cs);
@@ -371,14 +354,14 @@ ss_hip_ctx* create_impl(const T* A, size_t m, size_t n, ptrdiff_t rs, ptrdiff_t 
         if (const char* ev = std::getenv("SS_HIP_SCREEN_SINGLE")) ctx->screen_single = std::max(0, std::min(2, std::atoi(ev)));
         if (kind == 1) HIPCHK(irls_factor<T>(ctx));
         else ensure_workspace<T>(ctx, 1, 64);
-        HIPCHK(hipHostMalloc(&ctx->host_flags, 64 * sizeof(uint32_t), hipHostMallocMapped));
+        HELD(ctx->own, hipHostMalloc, &ctx->host_flags, 64 * sizeof(uint32_t), hipHostMallocMapped);
         std::memset(ctx->host_flags, 0, 64 * sizeof(uint32_t));
-        HIPCHK(hipHostMalloc(&ctx->hs_pinned, sizeof(DevState), hipHostMallocMapped));
+        HELD(ctx->own, hipHostMalloc, &ctx->hs_pinned, sizeof(DevState), hipHostMallocMapped);
         std::memset(ctx->hs_pinned, 0, sizeof(DevState));
         if (hipHostGetDevicePointer(&ctx->hs_mapped, ctx->hs_pinned, 0) != hipSuccess) { (void)hipGetLastError(); ctx->hs_mapped = nullptr; }
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->dev_flags), ctx->host_flags, 0));
-        HIPCHK(hipEventCreate(&ctx->ev_solve0));
-        HIPCHK(hipEventCreate(&ctx->ev_solve1));
+        HELD(ctx->own, hipEventCreate, &ctx->ev_solve0);
+        HELD(ctx->own, hipEventCreate, &ctx->ev_solve1);
         const uint64_t s = sizeof(T);
         ctx->stats.sweep_bytes = (uint64_t)m * n * s + 2 * (uint64_t)m * s + 2 * (uint64_t)n * s;
         ctx->stats.sweep1_bytes = (uint64_t)m * n * s + (uint64_t)m * s + (uint64_t)n * s;
@@ -469,43 +452,37 @@ template <typename T> struct Lookahead {
         const uint64_t fit = std::max<uint64_t>(64, budget / ((uint64_t)gpitch * sizeof(T)));
         if (want > fit) want = fit;
         if (ws.gcache && ws.gcap >= want && ws.gpitch == gpitch) return;
-        void* olds[] = { ws.gcache, ws.slot_of, ws.c0, ws.tcand, ws.sw_list, ws.slot_col, ws.solo_log, ws.sub_pos, ws.v_max, ws.v_min, ws.cand_top, ws.solo_stage,
-                         ws.sw_list2, ws.sub_cols, ws.subg };
-        for (void* p : olds) if (p) HIPCHK(hipFree(p));
-        ws.sw_list2 = nullptr; ws.sub_cols = nullptr; ws.subg = nullptr;
-        ws.gcache = nullptr; ws.slot_of = nullptr; ws.c0 = nullptr; ws.tcand = nullptr; ws.sw_list = nullptr;
-        ws.solo_stage = nullptr; ws.slot_col = nullptr; ws.solo_log = nullptr; ws.sub_pos = nullptr; ws.v_max = nullptr; ws.v_min = nullptr; ws.cand_top = nullptr;
-        ws.gcap = 0;
-        HIPCHK(hipMalloc(&ws.gcache, (size_t)want * gpitch * sizeof(T)));
-        HIPCHK(hipMalloc(&ws.slot_of, (size_t)ctx->n_pad * sizeof(int32_t)));
-        HIPCHK(hipMalloc(&ws.c0, (size_t)ctx->n_pad * sizeof(T)));
-        HIPCHK(hipMalloc(&ws.tcand, (size_t)ctx->n_pad * sizeof(T)));
-        HIPCHK(hipMalloc(&ws.sw_list, 128 * sizeof(uint32_t)));
+        static_cast<LaCache<T>&>(ws) = LaCache<T>();      // (the old cache released, its fields as new)
+        HELD(ws.cache, hipMalloc, &ws.gcache, (size_t)want * gpitch * sizeof(T));
+        HELD(ws.cache, hipMalloc, &ws.slot_of, (size_t)ctx->n_pad * sizeof(int32_t));
+        HELD(ws.cache, hipMalloc, &ws.c0, (size_t)ctx->n_pad * sizeof(T));
+        HELD(ws.cache, hipMalloc, &ws.tcand, (size_t)ctx->n_pad * sizeof(T));
+        HELD(ws.cache, hipMalloc, &ws.sw_list, 128 * sizeof(uint32_t));
         // (0xffffffff = "no column": k_subset_pick with a small subset writes only the entries it uses)
         HIPCHK(hipMemsetAsync(ws.sw_list, 0xff, 128 * sizeof(uint32_t), ctx->stream));
         if (sizeof(T) == 4) {
             // speculative form: slot -> column map, breakpoint log, verification partials, subset ranking
             ws.nvwg = (uint32_t)((ctx->n + kSoloWidth - 1) / kSoloWidth);
-            HIPCHK(hipMalloc(&ws.slot_col, (size_t)want * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&ws.solo_log, ((size_t)kSoloHeaderWords + (size_t)kSoloLogCap * kSoloEntryWords) * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&ws.solo_stage, (size_t)kSoloStageWords * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&ws.sub_pos, (size_t)ctx->n_pad));
+            HELD(ws.cache, hipMalloc, &ws.slot_col, (size_t)want * sizeof(uint32_t));
+            HELD(ws.cache, hipMalloc, &ws.solo_log, ((size_t)kSoloHeaderWords + (size_t)kSoloLogCap * kSoloEntryWords) * sizeof(uint32_t));
+            HELD(ws.cache, hipMalloc, &ws.solo_stage, (size_t)kSoloStageWords * sizeof(uint32_t));
+            HELD(ws.cache, hipMalloc, &ws.sub_pos, (size_t)ctx->n_pad);
             HIPCHK(hipMemsetAsync(ws.sub_pos, 0, (size_t)ctx->n_pad, ctx->stream));
-            HIPCHK(hipMalloc(&ws.v_max, (size_t)kSoloLogCap * ws.nvwg * sizeof(uint32_t)));
-            HIPCHK(hipMalloc(&ws.v_min, (size_t)kSoloLogCap * ws.nvwg * sizeof(uint64_t)));
-            HIPCHK(hipMalloc(&ws.sw_list2, 128 * sizeof(uint32_t)));
+            HELD(ws.cache, hipMalloc, &ws.v_max, (size_t)kSoloLogCap * ws.nvwg * sizeof(uint32_t));
+            HELD(ws.cache, hipMalloc, &ws.v_min, (size_t)kSoloLogCap * ws.nvwg * sizeof(uint64_t));
+            HELD(ws.cache, hipMalloc, &ws.sw_list2, 128 * sizeof(uint32_t));
             HIPCHK(hipMemsetAsync(ws.sw_list2, 0xff, 128 * sizeof(uint32_t), ctx->stream));
-            HIPCHK(hipMalloc(&ws.sub_cols, 2 * (size_t)kSoloWidth * sizeof(uint32_t)));     // columns, then the progress hints (float)
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&ws.subg), (size_t)kSoloWidth * kSoloWidth * sizeof(float)));
-            HIPCHK(hipMalloc(&ws.cand_top, kCandPerBlock * (size_t)ws.nvwg * sizeof(uint64_t)));
+            HELD(ws.cache, hipMalloc, &ws.sub_cols, 2 * (size_t)kSoloWidth * sizeof(uint32_t));     // columns, then the progress hints (float)
+            HELD(ws.cache, hipMalloc, reinterpret_cast<void**>(&ws.subg), (size_t)kSoloWidth * kSoloWidth * sizeof(float));
+            HELD(ws.cache, hipMalloc, &ws.cand_top, kCandPerBlock * (size_t)ws.nvwg * sizeof(uint64_t));
             HIPCHK(hipMemsetAsync(ws.cand_top, 0xff, kCandPerBlock * (size_t)ws.nvwg * sizeof(uint64_t), ctx->stream));
         }
         ws.gcap = (uint32_t)want;
         ws.gpitch = gpitch;
         // developer aid: SS_HIP_LA_DEBUG=<file> dumps the stage timestamps of k_la_iter after each solve
-        if (!ws.la_dbg && std::getenv("SS_HIP_LA_DEBUG")) HIPCHK(hipMalloc(&ws.la_dbg, 2048 * 8 * sizeof(uint64_t)));
-        if (!ws.la_sync) HIPCHK(hipMalloc(&ws.la_sync, kLaSyncBytes));
-        if (!ws.cq_alt) HIPCHK(hipMalloc(&ws.cq_alt, 2 * (size_t)ctx->n_pad * sizeof(T)));
+        if (!ws.la_dbg && std::getenv("SS_HIP_LA_DEBUG")) HELD(ws.own, hipMalloc, &ws.la_dbg, 2048 * 8 * sizeof(uint64_t));
+        if (!ws.la_sync) HELD(ws.own, hipMalloc, &ws.la_sync, kLaSyncBytes);
+        if (!ws.cq_alt) HELD(ws.own, hipMalloc, &ws.cq_alt, 2 * (size_t)ctx->n_pad * sizeof(T));
     }
 
     // the columns of a solve's first lookahead sweep (0: none — full-G mode, every column is "cached": no sweep, ever): the entering
@@ -614,24 +591,17 @@ inline void early_prologue(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t npart
         // the gate kernel below would then sit in front of the very launch it waits for).
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = hi = 0; }
-        if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, hi) != hipSuccess) {
-            (void)hipGetLastError();
-            HIPCHK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-        }
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        Holdings& own = ctx->own;
+        if (own.stream(&ctx->stream2, hipStreamNonBlocking, hi) != hipSuccess) HELD(own, hipStreamCreateWithFlags, &ctx->stream2, hipStreamNonBlocking);
+        HELD(own, hipEventCreateWithFlags, &ctx->ev_fork, hipEventDisableTiming);
+        HELD(own, hipEventCreateWithFlags, &ctx->ev_join, hipEventDisableTiming);
         // a third stream (lowest priority class: again its own hardware queue) for the tiles dealt out by shader engine
-        if (hipStreamCreateWithPriority(&ctx->stream3, hipStreamNonBlocking, lo) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->stream3 = nullptr;
-        }
-        if (ctx->stream3) {
-            HIPCHK(hipEventCreateWithFlags(&ctx->ev_gate, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&ctx->ev_b0, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&ctx->ev_join3, hipEventDisableTiming));
-            HIPCHK(hipMalloc(&ctx->se_count, 2 * (kSeCount + 2) * sizeof(uint32_t)));
-            if (hipStreamCreateWithPriority(&ctx->stream4, hipStreamNonBlocking, lo) != hipSuccess) { (void)hipGetLastError(); ctx->stream4 = nullptr; }
-            if (ctx->stream4) HIPCHK(hipEventCreateWithFlags(&ctx->ev_join4, hipEventDisableTiming));
+        if (own.stream(&ctx->stream3, hipStreamNonBlocking, lo) == hipSuccess) {
+            HELD(own, hipEventCreateWithFlags, &ctx->ev_gate, hipEventDisableTiming);
+            HELD(own, hipEventCreateWithFlags, &ctx->ev_b0, hipEventDisableTiming);
+            HELD(own, hipEventCreateWithFlags, &ctx->ev_join3, hipEventDisableTiming);
+            HELD(own, hipMalloc, &ctx->se_count, 2 * (kSeCount + 2) * sizeof(uint32_t));
+            if (own.stream(&ctx->stream4, hipStreamNonBlocking, lo) == hipSuccess) HELD(own, hipEventCreateWithFlags, &ctx->ev_join4, hipEventDisableTiming);
         }
     }
     // Dealing the passes out around the solo workgroup (option early_se).  The hardware distributes a grid statically:
@@ -771,32 +741,29 @@ hipEvent_t prof_event(ss_hip_ctx* ctx, size_t i)
 {
     while (ctx->prof_events.size() <= i) {
         hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
+        HELD(ctx->own, hipEventCreate, &e);
         ctx->prof_events.push_back(e);
     }
     return ctx->prof_events[i];
 }
 
-// Grow-only device buffer: `have` and `need` count units of `unit_bytes`.  A buffer that is too small is freed and allocated anew
-// (its contents are not kept); pointer and size are left null / 0 when the new allocation fails.  try_grow_device returns the
-// allocation's error instead of throwing it (a failed hipFree throws in both).
+// Grow-only device buffer of `own`: `have` and `need` count units of `unit_bytes`.  A buffer that is too small is given back and taken
+// anew (its contents are not kept); pointer and size are left null / 0 when the new allocation fails.  try_grow_device returns the
+// allocation's error instead of throwing it (a failed release throws in both).
 template <typename P, typename N>
-hipError_t try_grow_device(P*& ptr, N& have, size_t need, size_t unit_bytes)
+hipError_t try_grow_device(Holdings& own, P*& ptr, N& have, size_t need, size_t unit_bytes)
 {
     if (have >= need) return hipSuccess;
-    if (ptr) HIPCHK(hipFree(ptr));
-    ptr = nullptr;
+    HIPCHK(own.drop(ptr));
     have = 0;
-    const hipError_t e = hipMalloc(&ptr, need * unit_bytes);
+    const hipError_t e = own.device(&ptr, need * unit_bytes);
     if (e == hipSuccess) have = (N)need;
-    else ptr = nullptr;
     return e;
 }
 template <typename P, typename N>
-void grow_device(P*& ptr, N& have, size_t need, size_t unit_bytes, const char* what)
+void grow_device(Holdings& own, P*& ptr, N& have, size_t need, size_t unit_bytes, const char* what)
 {
-    const hipError_t e = try_grow_device(ptr, have, need, unit_bytes);
-    if (e != hipSuccess) throw HipFail{ e, what };
+    held(try_grow_device(own, ptr, have, need, unit_bytes), what);
 }
 
 // The trace buffer for the extent of a solve or a chunk: room for `want` entries, or — want = 0 — hidden from the kernels, which
@@ -807,7 +774,7 @@ struct TraceWindow {
     TraceEntry* keep;
     TraceWindow(Workspace<T>& w, uint32_t want) : ws(w)
     {
-        grow_device(ws.trace, ws.trace_cap, want, sizeof(TraceEntry), "hipMalloc(trace)");
+        grow_device(ws.trace_own, ws.trace, ws.trace_cap, want, sizeof(TraceEntry), "hipMalloc(trace)");
         keep = ws.trace;
         if (want == 0u) ws.trace = nullptr;
     }
@@ -849,7 +816,7 @@ template <typename T>
 unsigned char* pack_records(ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t nslots, uint32_t kmax)
 {
     const size_t rb = record_bytes(kmax, sizeof(T));
-    grow_device(ctx->rec_stage, ctx->rec_stage_bytes, rb * nslots, 1, "hipMalloc(rec_stage)");
+    grow_device(ctx->own, ctx->rec_stage, ctx->rec_stage_bytes, rb * nslots, 1, "hipMalloc(rec_stage)");
     hipLaunchKernelGGL((k_pack_records<T>), dim3(nslots), dim3(256), 0, ctx->stream, (const T*)ws.x, (const uint32_t*)ws.gam,
                        (const uint32_t*)ws.touched, (const DevState*)ws.st, ws.dims, ctx->zero_on_removal ? 0 : 1, kmax,
                        ctx->rec_stage, rb);
@@ -888,12 +855,12 @@ void first_sweep(ss_hip_ctx* ctx, Workspace<T>& ws, T* out, ProfSpans& spans, ui
 inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, EventPair first, EventPair screen, EventPair path,
                              bool omp, bool rescue, ScrHandoff* ho)
 {
-    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
+    grow_device(ctx->own, ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
     // (developer switch, read per solve: which hand-offs inside launches the form may use — 1 = the one-launch tail, 2 = the selection by
     // many workgroups; unset = all, 0 = the launches before them)
     if (const char* e = std::getenv("SS_HIP_SCR_HANDOFF")) ho->mask = (uint32_t)std::strtoul(e, nullptr, 0);
     if (ctx->sub_dbg == nullptr && std::getenv("SS_HIP_SUB_STAMPS")) {
-        HIPCHK(hipMalloc(&ctx->sub_dbg, 16 * sizeof(unsigned long long)));
+        HELD(ctx->own, hipMalloc, &ctx->sub_dbg, 16 * sizeof(unsigned long long));
         HIPCHK(hipMemsetAsync(ctx->sub_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
     }
     // (with the state mirrored to mapped host memory the epilogue launch applies the certificate's verdict: no k_sub_finish)
@@ -1480,7 +1447,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             if (!ws.slot_identity) {
                 std::vector<int32_t> iota(ctx->n_pad);
                 for (uint32_t i = 0; i < ctx->n_pad; ++i) iota[i] = (int32_t)i;
-                HIPCHK(hipMalloc(&ws.slot_identity, (size_t)ctx->n_pad * sizeof(int32_t)));
+                HELD(ws.own, hipMalloc, &ws.slot_identity, (size_t)ctx->n_pad * sizeof(int32_t));
                 HIPCHK(hipMemcpy(ws.slot_identity, iota.data(), (size_t)ctx->n_pad * sizeof(int32_t), hipMemcpyHostToDevice));
             }
             ws.gcache_own = ws.gcache; ws.gpitch_own = ws.gpitch; ws.slot_of_own = ws.slot_of;
@@ -1505,7 +1472,7 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             if (f.sub1) {
                 if constexpr (sizeof(T) == 4) {
                     // G = A^T A is at hand: the subset form (subbatch.hip) on c0 in ws.c0
-                    grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
+                    grow_device(ctx->own, ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
                     HIPCHK(launch_sub_form(ctx, ws, 1, ws.c0, tol, max_iter));
                 }
             } else {
@@ -1709,12 +1676,25 @@ void gram_reserve_start(ss_hip_ctx* ctx, size_t B)
     if (bytes > total_b / 8 || bytes + ((size_t)16 << 30) > free_b) return;
     const int device = ctx->device;
     float** slot = &ctx->gram_reserved;
-    std::thread* th = new (std::nothrow) std::thread([device, bytes, slot]() {
-        float* p = nullptr;
-        if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
-        *slot = p;
-    });
-    ctx->gram_reserve_thread = th;
+    // (the thread's own, unowned until the join: gram_reserve_join hands it to the context's owner)
+    try {
+        ctx->gram_reserve_thread.reset(new std::thread([device, bytes, slot]() {
+            float* p = nullptr;
+            if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+            *slot = p;
+        }));
+    } catch (...) {
+        ctx->gram_reserve_thread.reset();       // no thread, or no memory for one: no reservation
+    }
+}
+
+// The join of that thread (none: nothing happens): what it obtained now belongs to the context's owner.
+void gram_reserve_join(ss_hip_ctx* ctx)
+{
+    if (!ctx->gram_reserve_thread) return;
+    ctx->gram_reserve_thread->join();
+    ctx->gram_reserve_thread.reset();
+    ctx->own.adopt_device(ctx->gram_reserved);
 }
 
 // The full Gram matrix G = A^T A for the batched Gram form: one GEMM of 2 m n^2 flops on the MFMA units (0.55 s at C2), kept in
@@ -1728,39 +1708,33 @@ bool ensure_full_gram(ss_hip_ctx* ctx)
     if (ctx->gram_full_gib <= 0 || bytes > ((size_t)ctx->gram_full_gib << 30)) return false;
     float* G = nullptr;
     const auto t_alloc = std::chrono::steady_clock::now();
-    if (ctx->gram_reserve_thread != nullptr) {
-        // (reserved ahead on a helper thread: what is left of that allocation is all this batch waits for)
-        std::thread* th = static_cast<std::thread*>(ctx->gram_reserve_thread);
-        th->join();
-        delete th;
-        ctx->gram_reserve_thread = nullptr;
-        G = ctx->gram_reserved;
-        ctx->gram_reserved = nullptr;
-    }
+    // (reserved ahead on a helper thread: what is left of that allocation is all this batch waits for)
+    gram_reserve_join(ctx);
+    G = ctx->gram_reserved;
+    ctx->gram_reserved = nullptr;
     if (G == nullptr) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)8 << 30) > free_b) {
             (void)hipGetLastError();
             return false;
         }
-        if (hipMalloc(&G, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (ctx->own.device(&G, bytes) != hipSuccess) return false;
     }
     ctx->stats.gram_alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc).count();
+    Holdings timing;         // (the two events of this build alone)
     hipEvent_t g0 = nullptr, g1 = nullptr;
-    if (hipEventCreate(&g0) != hipSuccess || hipEventCreate(&g1) != hipSuccess) { (void)hipGetLastError(); g0 = g1 = nullptr; }
+    if (timing.event(&g0) != hipSuccess || timing.event(&g1) != hipSuccess) g0 = g1 = nullptr;
     if (g0) (void)hipEventRecord(g0, ctx->stream);
     const hipError_t e = ctx->gram_symmetric
         ? launch_gemm_sym_f32(ctx, G, pitch)
         : launch_gemm_tn_f32(ctx, static_cast<const float*>(ctx->At), (uint32_t)np, ctx->ldm, G, pitch, nullptr, false);
     if (g1) (void)hipEventRecord(g1, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(G); throw HipFail{ e, "launch_gemm_tn_f32(full Gram)" }; }
+    if (e != hipSuccess) { (void)ctx->own.drop(G); throw HipFail{ e, "launch_gemm_tn_f32(full Gram)" }; }
     if (g0 && g1 && hipEventSynchronize(g1) == hipSuccess) {
         float ms = 0.f;
         if (hipEventElapsedTime(&ms, g0, g1) == hipSuccess) ctx->stats.gram_build_ms += ms;
     }
     (void)hipGetLastError();
-    if (g0) (void)hipEventDestroy(g0);
-    if (g1) (void)hipEventDestroy(g1);
     ctx->gram_full = G;
     ctx->gram_pitch = pitch;
     ctx->stats.gram_full_builds += 1;
@@ -1777,10 +1751,7 @@ bool ensure_bcol(ss_hip_ctx* ctx, size_t per, uint32_t max_iter)
     const size_t np = ctx->n_pad;
     const size_t pitchc = (np + 1023) / 1024 * 1024;
     const size_t rows_needed = ((size_t)max_iter + 2) * per;
-    auto try_malloc = [](void** p, size_t bytes) {
-        if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-        return true;
-    };
+    Holdings& own = ctx->own;
     if (ctx->bcol_cache_rows < rows_needed) {
         const size_t bytes = rows_needed * pitchc * sizeof(float);
         const size_t held = ctx->bcol_cache_rows * pitchc * sizeof(float);
@@ -1788,20 +1759,18 @@ bool ensure_bcol(ss_hip_ctx* ctx, size_t per, uint32_t max_iter)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
         if (bytes + ((size_t)4 << 30) > free_b + held) return false;          // keep 4 GiB for everything else
-        if (ctx->bcol_cache) (void)hipFree(ctx->bcol_cache);
-        ctx->bcol_cache = nullptr;
+        (void)own.drop(ctx->bcol_cache);
         ctx->bcol_cache_rows = 0;
-        if (!try_malloc(reinterpret_cast<void**>(&ctx->bcol_cache), bytes)) return false;
+        if (own.device(&ctx->bcol_cache, bytes) != hipSuccess) return false;
         ctx->bcol_cache_rows = rows_needed;
     }
     if (ctx->bcol_slot_rows < per) {
-        if (ctx->bcol_slot) (void)hipFree(ctx->bcol_slot);
-        ctx->bcol_slot = nullptr;
+        (void)own.drop(ctx->bcol_slot);
         ctx->bcol_slot_rows = 0;
-        if (!try_malloc(reinterpret_cast<void**>(&ctx->bcol_slot), per * np * sizeof(int32_t))) return false;
+        if (own.device(&ctx->bcol_slot, per * np * sizeof(int32_t)) != hipSuccess) return false;
         ctx->bcol_slot_rows = per;
     }
-    if (!ctx->bcol_lists && !try_malloc(reinterpret_cast<void**>(&ctx->bcol_lists), 2 * 1024 * sizeof(uint32_t))) return false;
+    if (!ctx->bcol_lists && own.device(&ctx->bcol_lists, 2 * 1024 * sizeof(uint32_t)) != hipSuccess) return false;
     return true;
 }
 
@@ -1905,7 +1874,7 @@ inline uint32_t begin_gemm_chunk(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
     HIPCHK(hipMemsetAsync(ws.rhs, 0, 2 * bp * ldm * sizeof(T), st));
     HIPCHK(hipMemcpyAsync(ws.rhs, ws.y, (size_t)Bc * ldm * sizeof(T), hipMemcpyDeviceToDevice, st));
     uint32_t nparts = 0;
-    if (time_c0 && !ctx->ev_c0a) { HIPCHK(hipEventCreate(&ctx->ev_c0a)); HIPCHK(hipEventCreate(&ctx->ev_c0b)); }
+    if (time_c0 && !ctx->ev_c0a) { HELD(ctx->own, hipEventCreate, &ctx->ev_c0a); HELD(ctx->own, hipEventCreate, &ctx->ev_c0b); }
     if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0a, st));
     HIPCHK(launch_gemm_tn_f32(ctx, ws.rhs, rows, (uint32_t)ldm, ws.c, (uint32_t)np, nullptr));
     if (time_c0) HIPCHK(hipEventRecord(ctx->ev_c0b, st));
@@ -2049,7 +2018,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
             }
             if (gram_chunk) {
                 // keep c0 = A^T y of every signal: the Gram-form rounds subtract from it
-                grow_device(ctx->c0_batch, ctx->c0_batch_rows, bp, np * sizeof(T), "hipMalloc(c0_batch)");
+                grow_device(ctx->own, ctx->c0_batch, ctx->c0_batch_rows, bp, np * sizeof(T), "hipMalloc(c0_batch)");
                 HIPCHK(hipMemcpyAsync(ctx->c0_batch, ws.c, (size_t)Bc * np * sizeof(T), hipMemcpyDeviceToDevice, st));
             } else {
                 HIPCHK(launch_rp<T>(ctx, ws, Bc));
@@ -2084,7 +2053,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
             if (sub_chunk && ctx->sub_off_chunks > 0) { ctx->sub_off_chunks -= 1; sub_chunk = false; }     // (it handed back too much lately)
             const bool scr_chunk = gram_chunk && scr_form && !no_subset;
             // (a chunk whose tolerance is too tight for Gram-form correlations runs the residual-form rounds below, as in every form)
-            if ((sub_chunk || scr_chunk) && try_grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1) != hipSuccess) {
+            if ((sub_chunk || scr_chunk) && try_grow_device(ctx->own, ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1) != hipSuccess) {
                 // (the subset form steps aside for this chunk; the screened form has no other way to go)
                 (void)hipGetLastError();
                 sub_chunk = false;
@@ -2098,7 +2067,7 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
                 const bool timed = ctx->profiling != 0;
                 EventPair ev;
                 hipEvent_t verified = nullptr;
-                if (timed) { ev = { prof_event(ctx, 0), prof_event(ctx, 1) }; verified = prof_event(ctx, 2); if (!ctx->ev_sub_sel) HIPCHK(hipEventCreate(&ctx->ev_sub_sel)); }
+                if (timed) { ev = { prof_event(ctx, 0), prof_event(ctx, 1) }; verified = prof_event(ctx, 2); if (!ctx->ev_sub_sel) HELD(ctx->own, hipEventCreate, &ctx->ev_sub_sel); }
                 HIPCHK(launch_sub_form(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, ev, verified));
                 if (timed) {
                     HIPCHK(hipEventSynchronize(verified));
@@ -2228,10 +2197,10 @@ int solve_batch_gemm_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, int form = 
             // are arbitrated inside that call), results scattered back
             const size_t nr = redo.size(), rb = record_bytes(c.kmax, sizeof(T));
             T* Yg = nullptr; T* Xg = nullptr; unsigned char* Rg = nullptr;
-            struct FreeTmp { T*& a; T*& b; unsigned char*& c; ~FreeTmp() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); } } free_tmp{ Yg, Xg, Rg };
-            HIPCHK(hipMalloc(&Yg, nr * m * sizeof(T)));
-            if (c.X) HIPCHK(hipMalloc(&Xg, nr * n * sizeof(T)));
-            if (c.rec_out) HIPCHK(hipMalloc(&Rg, nr * rb));
+            Holdings tmp;        // (of this redo alone)
+            HELD(tmp, hipMalloc, &Yg, nr * m * sizeof(T));
+            if (c.X) HELD(tmp, hipMalloc, &Xg, nr * n * sizeof(T));
+            if (c.rec_out) HELD(tmp, hipMalloc, &Rg, nr * rb);
             for (size_t r = 0; r < nr; ++r) copy_in<T>(ctx, Yg + r * m, c.y(redo[r]), c.incy, m);
             HIPCHK(hipStreamSynchronize(st));
             std::vector<uint32_t> it_r(nr, 0u);
@@ -2447,9 +2416,9 @@ int solve_omp_batch_f32(ss_hip_ctx* ctx, const BatchCall<float>& c, bool gram)
             HIPCHK(hipMemsetAsync(ws.y, 0, (size_t)Bc * ldm * sizeof(T), st));
             upload_chunk<T>(ctx, ws, c, b0, Bc);
             (void)begin_gemm_chunk(ctx, ws, Bc, tol, false);
-            grow_device(ctx->c0_batch, ctx->c0_batch_rows, ws.dims.b_pad, np * sizeof(T), "hipMalloc(c0_batch)");
+            grow_device(ctx->own, ctx->c0_batch, ctx->c0_batch_rows, ws.dims.b_pad, np * sizeof(T), "hipMalloc(c0_batch)");
             HIPCHK(hipMemcpyAsync(ctx->c0_batch, ws.c, (size_t)Bc * np * sizeof(T), hipMemcpyDeviceToDevice, st));
-            grow_device(ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1, "hipMalloc(sub_buf)");
+            grow_device(ctx->own, ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(Bc), 1, "hipMalloc(sub_buf)");
             if (gram) HIPCHK(launch_omp_gram_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter));
             else HIPCHK(launch_screen_batch(ctx, ws, Bc, ctx->c0_batch, tol, max_iter, true));
             hs.resize(Bc);
@@ -2887,57 +2856,8 @@ void ss_hip_homotopy_destroy(ss_hip_ctx* ctx)
     if (ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->ws) {
-        if (ctx->is_f64) free_ws(static_cast<Workspace<double>*>(ctx->ws));
-        else free_ws(static_cast<Workspace<float>*>(ctx->ws));
-    }
-    sship::irls_free(ctx);
-    sship::colshard_destroy(ctx);
-    if (ctx->gram_reserve_thread != nullptr) {
-        std::thread* th = static_cast<std::thread*>(ctx->gram_reserve_thread);
-        th->join();
-        delete th;
-        ctx->gram_reserve_thread = nullptr;
-    }
-    if (ctx->gram_reserved) (void)hipFree(ctx->gram_reserved);
-    if (ctx->gram_full) (void)hipFree(ctx->gram_full);
-    if (ctx->c0_batch) (void)hipFree(ctx->c0_batch);
-    sship::omp_gram_free(ctx);
-    sship::classify_free(ctx);
-    sship::learn_free(ctx);
-    sship::refit_free(ctx);
-    sship::coherence_free(ctx);
-    sship::topcorr_free(ctx);
-    sship::joint_free(ctx);
-    sship::weighted_free(ctx);
-    if (ctx->sub_buf) (void)hipFree(ctx->sub_buf);
-    if (ctx->sub_dbg) (void)hipFree(ctx->sub_dbg);
-    sship::screen_free(ctx);
-    if (ctx->ev_sub_sel) (void)hipEventDestroy(ctx->ev_sub_sel);
-    if (ctx->ev_c0a) (void)hipEventDestroy(ctx->ev_c0a);
-    if (ctx->ev_c0b) (void)hipEventDestroy(ctx->ev_c0b);
-    if (ctx->bcol_cache) (void)hipFree(ctx->bcol_cache);
-    if (ctx->bcol_slot) (void)hipFree(ctx->bcol_slot);
-    if (ctx->bcol_lists) (void)hipFree(ctx->bcol_lists);
-    if (ctx->rec_stage) (void)hipFree(ctx->rec_stage);
-    if (ctx->At) (void)hipFree(ctx->At);
-    if (ctx->host_flags) (void)hipHostFree(ctx->host_flags);
-    if (ctx->hs_pinned) (void)hipHostFree(ctx->hs_pinned);
-    for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
-    if (ctx->ev_solve0) (void)hipEventDestroy(ctx->ev_solve0);
-    if (ctx->ev_solve1) (void)hipEventDestroy(ctx->ev_solve1);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-    if (ctx->se_count) (void)hipFree(ctx->se_count);
-    if (ctx->ev_gate) (void)hipEventDestroy(ctx->ev_gate);
-    if (ctx->ev_b0) (void)hipEventDestroy(ctx->ev_b0);
-    if (ctx->ev_join3) (void)hipEventDestroy(ctx->ev_join3);
-    if (ctx->ev_join4) (void)hipEventDestroy(ctx->ev_join4);
-    if (ctx->stream4) (void)hipStreamDestroy(ctx->stream4);
-    if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    gram_reserve_join(ctx);
+    delete ctx;       // the parts, then the context's own memory, events and streams (ss_hip_internal.h: the order of ss_hip_ctx's members)
 }
 
 int ss_hip_homotopy_solve_f32(ss_hip_ctx* ctx, const float* y, ptrdiff_t incy, float tol,

@@ -31,7 +31,8 @@ namespace sship {
 
 template <typename T>
 struct IrlsState {
-    T* Vt = nullptr;      // [n][ldm] Householder vectors, column k in row k (zero above the diagonal)
+    Holdings own;         // everything below
+    T* Vt = nullptr;     // [n][ldm] Householder vectors, column k in row k (zero above the diagonal)
     T* Qt = nullptr;      // [n][ldm] Q^T: row j = column j of the thin Q
     T* R = nullptr;       // [n][n] upper triangular, row-major
     T* G0 = nullptr;      // [n][n] lower triangle of Q^T Q, row-major
@@ -1032,28 +1033,27 @@ void k_irls_finish(T* __restrict__ vec, uint32_t n, const IrlsCtl<T>* __restrict
 
 // ---- host side ---------------------------------------------------------------------------------------
 template <typename T>
-static IrlsState<T>* state_of(ss_hip_ctx* ctx) { return static_cast<IrlsState<T>*>(ctx->irls); }
+static IrlsState<T>* state_of(ss_hip_ctx* ctx) { return ctx->irls.as<IrlsState<T>>(); }
 
 template <typename T>
 hipError_t irls_factor(ss_hip_ctx* ctx)
 {
     const uint32_t m = (uint32_t)ctx->m, n = (uint32_t)ctx->n, ldm = ctx->ldm;
-    auto* S = new IrlsState<T>();
-    ctx->irls = S;
+    IrlsState<T>* S = &part<IrlsState<T>>(ctx->irls);
     hipError_t e;
 #define IRLS_TRY(call) do { e = (call); if (e != hipSuccess) return e; } while (0)
-    IRLS_TRY(hipMalloc(&S->Vt, (size_t)n * ldm * sizeof(T)));
-    IRLS_TRY(hipMalloc(&S->Qt, (size_t)n * ldm * sizeof(T)));
-    IRLS_TRY(hipMalloc(&S->R, (size_t)n * n * sizeof(T)));
-    IRLS_TRY(hipMalloc(&S->G0, (size_t)n * n * sizeof(T)));
-    IRLS_TRY(hipMalloc(&S->L, (size_t)n * n * sizeof(T)));
-    IRLS_TRY(hipMalloc(&S->rdiag, (size_t)n * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->Vt, (size_t)n * ldm * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->Qt, (size_t)n * ldm * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->R, (size_t)n * n * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->G0, (size_t)n * n * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->L, (size_t)n * n * sizeof(T)));
+    IRLS_TRY(S->own.device(&S->rdiag, (size_t)n * sizeof(T)));
     // (behind the vectors: one flag per column for the one-launch panel kernel of the factorisation, zeroed with them)
     const size_t vec_bytes = (5 * (size_t)n + 2 * (size_t)ldm) * sizeof(T);
-    IRLS_TRY(hipMalloc(&S->vec, vec_bytes + (size_t)n * sizeof(uint32_t)));
-    IRLS_TRY(hipMalloc(&S->res, sizeof(IrlsResult)));
-    IRLS_TRY(hipMalloc(&S->ctl, sizeof(IrlsCtl<T>)));
-    IRLS_TRY(hipHostMalloc(reinterpret_cast<void**>(&S->done_host), 64, hipHostMallocDefault));
+    IRLS_TRY(S->own.device(&S->vec, vec_bytes + (size_t)n * sizeof(uint32_t)));
+    IRLS_TRY(S->own.device(&S->res, sizeof(IrlsResult)));
+    IRLS_TRY(S->own.device(&S->ctl, sizeof(IrlsCtl<T>)));
+    IRLS_TRY(S->own.pinned(&S->done_host, 64, hipHostMallocDefault));
     IRLS_TRY(hipMemsetAsync(S->Qt, 0, (size_t)n * ldm * sizeof(T), ctx->stream));
     IRLS_TRY(hipMemsetAsync(S->G0, 0, (size_t)n * n * sizeof(T), ctx->stream));
     IRLS_TRY(hipMemsetAsync(S->vec, 0, vec_bytes + (size_t)n * sizeof(uint32_t), ctx->stream));
@@ -1190,26 +1190,6 @@ void irls_factors(ss_hip_ctx* ctx, const T** Qt, const T** R, const T** G0)
     *Qt = S->Qt;
     *R = S->R;
     *G0 = S->G0;
-}
-
-template <typename T>
-static void free_state(IrlsState<T>* S)
-{
-    if (!S) return;
-    void* ptrs[] = { S->Vt, S->Qt, S->R, S->G0, S->L, S->rdiag, S->vec, S->res, S->ctl };
-    if (S->done_host) (void)hipHostFree(S->done_host);
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete S;
-}
-
-void irls_free(ss_hip_ctx* ctx)
-{
-    irls_batch_free(ctx);
-    if (!ctx->irls) return;
-    if (ctx->is_f64) free_state(static_cast<IrlsState<double>*>(ctx->irls));
-    else free_state(static_cast<IrlsState<float>*>(ctx->irls));
-    ctx->irls = nullptr;
 }
 
 template hipError_t irls_factor<float>(ss_hip_ctx*);

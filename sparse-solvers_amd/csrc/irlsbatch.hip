@@ -646,27 +646,23 @@ void k_irlsb_finish(T* __restrict__ vecall, uint32_t n, size_t vstride, const Ib
 }
 
 // ---- workspace ---------------------------------------------------------------------------------------------------------
-struct IrlsBatchWs {
-    int is_f64 = 0;
+// the buffers that grow with the chunk, owned by `own`: a regrow is a fresh IbBuffers
+struct IbBuffers {
+    Holdings own;
     uint32_t cap = 0;             // slots the buffers hold
     void* L = nullptr;            // [cap][n][n]
     void* vec = nullptr;          // [cap][5 n + 2 ldm]
     void* ctl = nullptr;          // [cap] IbCtl<T>
     IrlsResult* res = nullptr;    // [cap]
     uint32_t* live = nullptr;     // [cap + 1]: the live list, then its length
+};
+struct IrlsBatchWs : IbBuffers {
+    int is_f64 = 0;
+    Holdings pinned;
     uint32_t* nlive_host = nullptr;   // pinned: the live count, read once per round
 };
 
-void free_buffers(IrlsBatchWs* W)
-{
-    void* ptrs[] = { W->L, W->vec, W->ctl, W->res, W->live };
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    W->L = W->vec = W->ctl = nullptr;
-    W->res = nullptr;
-    W->live = nullptr;
-    W->cap = 0;
-}
+void free_buffers(IrlsBatchWs* W) { static_cast<IbBuffers&>(*W) = IbBuffers(); }
 
 template <typename T>
 size_t slot_bytes(const ss_hip_ctx* ctx)
@@ -680,11 +676,11 @@ hipError_t alloc_buffers(ss_hip_ctx* ctx, IrlsBatchWs* W, uint32_t cap)
 {
     const size_t n = ctx->n, ldm = ctx->ldm;
     hipError_t e;
-    if ((e = hipMalloc(&W->L, (size_t)cap * n * n * sizeof(T))) != hipSuccess) return e;
-    if ((e = hipMalloc(&W->vec, (size_t)cap * (5 * n + 2 * ldm) * sizeof(T))) != hipSuccess) return e;
-    if ((e = hipMalloc(&W->ctl, (size_t)cap * sizeof(IbCtl<T>))) != hipSuccess) return e;
-    if ((e = hipMalloc(&W->res, (size_t)cap * sizeof(IrlsResult))) != hipSuccess) return e;
-    if ((e = hipMalloc(&W->live, ((size_t)cap + 1) * sizeof(uint32_t))) != hipSuccess) return e;
+    if ((e = W->own.device(&W->L, (size_t)cap * n * n * sizeof(T))) != hipSuccess) return e;
+    if ((e = W->own.device(&W->vec, (size_t)cap * (5 * n + 2 * ldm) * sizeof(T))) != hipSuccess) return e;
+    if ((e = W->own.device(&W->ctl, (size_t)cap * sizeof(IbCtl<T>))) != hipSuccess) return e;
+    if ((e = W->own.device(&W->res, (size_t)cap * sizeof(IrlsResult))) != hipSuccess) return e;
+    if ((e = W->own.device(&W->live, ((size_t)cap + 1) * sizeof(uint32_t))) != hipSuccess) return e;
     // (y rows m .. ldm - 1 are never read; zeroed so that no stale words are ever in play)
     if ((e = hipMemsetAsync(W->vec, 0, (size_t)cap * (5 * n + 2 * ldm) * sizeof(T), ctx->stream)) != hipSuccess) return e;
     W->cap = cap;
@@ -698,13 +694,12 @@ hipError_t alloc_buffers(ss_hip_ctx* ctx, IrlsBatchWs* W, uint32_t cap)
 template <typename T>
 hipError_t irls_batch_reserve(ss_hip_ctx* ctx, size_t B, uint32_t* chunk)
 {
-    auto* W = static_cast<IrlsBatchWs*>(ctx->irls_batch);
+    auto* W = ctx->irls_batch.as<IrlsBatchWs>();
     if (W == nullptr) {
-        W = new IrlsBatchWs();
+        W = &part<IrlsBatchWs>(ctx->irls_batch);
         W->is_f64 = sizeof(T) == 8;
-        ctx->irls_batch = W;
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&W->nlive_host), 64, hipHostMallocDefault);
-        if (e != hipSuccess) { W->nlive_host = nullptr; return e; }
+        const hipError_t e = W->pinned.pinned(&W->nlive_host, 64, hipHostMallocDefault);
+        if (e != hipSuccess) { ctx->irls_batch.reset(); return e; }      // (the next batch tries again)
     }
     size_t want = std::min<size_t>(B, (size_t)std::max(1, ctx->irls_batch_max));
     want = std::min<size_t>(want, std::max<size_t>(1, kIbBudget / slot_bytes<T>(ctx)));
@@ -729,14 +724,14 @@ hipError_t irls_batch_reserve(ss_hip_ctx* ctx, size_t B, uint32_t* chunk)
 template <typename T>
 T* irls_batch_y(ss_hip_ctx* ctx, uint32_t b)
 {
-    auto* W = static_cast<IrlsBatchWs*>(ctx->irls_batch);
+    auto* W = ctx->irls_batch.as<IrlsBatchWs>();
     return static_cast<T*>(W->vec) + (size_t)b * (5 * ctx->n + 2 * (size_t)ctx->ldm) + 5 * ctx->n + ctx->ldm;
 }
 
 template <typename T>
 T* irls_batch_x(ss_hip_ctx* ctx, uint32_t b)
 {
-    auto* W = static_cast<IrlsBatchWs*>(ctx->irls_batch);
+    auto* W = ctx->irls_batch.as<IrlsBatchWs>();
     return static_cast<T*>(W->vec) + (size_t)b * (5 * ctx->n + 2 * (size_t)ctx->ldm) + 4 * ctx->n;
 }
 
@@ -747,7 +742,7 @@ hipError_t irls_batch_run(ss_hip_ctx* ctx, const T* Qt, const T* R, const T* G0,
                           IrlsResult* res_host, uint64_t* rounds)
 {
 #define IB_TRY(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return e_; } while (0)
-    auto* W = static_cast<IrlsBatchWs*>(ctx->irls_batch);
+    auto* W = ctx->irls_batch.as<IrlsBatchWs>();
     const uint32_t n = (uint32_t)ctx->n, m = (uint32_t)ctx->m, ldm = ctx->ldm;
     const size_t vstride = 5 * (size_t)n + 2 * (size_t)ldm;
     hipStream_t st = ctx->stream;
@@ -810,16 +805,6 @@ hipError_t irls_batch_run(ss_hip_ctx* ctx, const T* Qt, const T* R, const T* G0,
     IB_TRY(hipMemcpyAsync(res_host, W->res, (size_t)nb * sizeof(IrlsResult), hipMemcpyDeviceToHost, st));
     return hipSuccess;
 #undef IB_TRY
-}
-
-void irls_batch_free(ss_hip_ctx* ctx)
-{
-    auto* W = static_cast<IrlsBatchWs*>(ctx->irls_batch);
-    if (!W) return;
-    free_buffers(W);
-    if (W->nlive_host) (void)hipHostFree(W->nlive_host);
-    delete W;
-    ctx->irls_batch = nullptr;
 }
 
 template hipError_t irls_batch_reserve<float>(ss_hip_ctx*, size_t, uint32_t*);

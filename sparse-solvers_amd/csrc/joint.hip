@@ -51,8 +51,7 @@ constexpr size_t kGcChunkBytes = (size_t)64 << 20;       // the byte budget of a
 // the workspace of the group class residuals (ss_hip_ctx::js); the group top correlations carve the top correlations' arena
 WorkArena& state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->js) ctx->js = new WorkArena();
-    return *static_cast<WorkArena*>(ctx->js);
+    return part<WorkArena>(ctx->js);
 }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
@@ -426,15 +425,6 @@ int group_classes_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_strid
 }
 
 }  // namespace
-
-void joint_free(ss_hip_ctx* ctx)
-{
-    WorkArena* js = static_cast<WorkArena*>(ctx->js);
-    if (!js) return;
-    arena_free(*js);
-    delete js;
-    ctx->js = nullptr;
-}
 
 }  // namespace sship
 

@@ -210,17 +210,9 @@ hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
     hipStream_t s = ctx->stream;
     if (ctx->omp_gs == nullptr) {
-        bool ok = true;
-        auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
-        alloc(reinterpret_cast<void**>(&ctx->omp_gs), (size_t)kOmpGramChunk * kSbS * kSbS * sizeof(float));
-        alloc(reinterpret_cast<void**>(&ctx->omp_norm), (size_t)np * sizeof(float));
-        if (!ok) {
-            void* ptrs[] = { ctx->omp_gs, ctx->omp_norm };
-            for (void* p : ptrs) if (p) (void)hipFree(p);
-            ctx->omp_gs = nullptr; ctx->omp_norm = nullptr;
-            (void)hipGetLastError();
-            return hipErrorOutOfMemory;
-        }
+        // (both or neither: omp_gs is what says the pair exists)
+        if (ctx->own.device(&ctx->omp_gs, (size_t)kOmpGramChunk * kSbS * kSbS * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
+        if (ctx->own.device(&ctx->omp_norm, (size_t)np * sizeof(float)) != hipSuccess) { (void)ctx->own.drop(ctx->omp_gs); return hipErrorOutOfMemory; }
         hipLaunchKernelGGL(k_omp_colnorm, dim3((np + 3u) / 4u), dim3(256), 0, s, static_cast<const float*>(ctx->At), ldm, n, np, ctx->omp_norm,
                            (const uint32_t*)nullptr, 0u);
     }
@@ -244,13 +236,6 @@ hipError_t omp_norm_refresh(ss_hip_ctx* ctx, const uint32_t* cols_dev, uint32_t 
     hipLaunchKernelGGL(k_omp_colnorm, dim3((S + 3u) / 4u), dim3(256), 0, ctx->stream, static_cast<const float*>(ctx->At), ctx->ldm, (uint32_t)ctx->n, ctx->n_pad,
                        ctx->omp_norm, cols_dev, S);
     return hipGetLastError();
-}
-
-void omp_gram_free(ss_hip_ctx* ctx)
-{
-    if (ctx->omp_gs) (void)hipFree(ctx->omp_gs);
-    if (ctx->omp_norm) (void)hipFree(ctx->omp_norm);
-    ctx->omp_gs = nullptr; ctx->omp_norm = nullptr;
 }
 
 }  // namespace sship

@@ -19,19 +19,16 @@ constexpr uint32_t kClsThreads = 256;
 constexpr uint32_t kClsTileRows = 1024;                  // rows of y a workgroup holds: four per thread
 constexpr uint32_t kClsInFlight = 8;                     // columns whose loads a thread has in flight
 
-inline void grow(unsigned char*& p, size_t& have, size_t need, const char* what)
+inline void grow(Holdings& own, unsigned char*& p, size_t& have, size_t need, const char* what)
 {
     if (have >= need) return;
-    if (p) HIPCHK(hipFree(p));
-    p = nullptr;
+    HIPCHK(own.drop(p));
     have = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need);
-    if (e != hipSuccess) { p = nullptr; throw HipFail{ e, what }; }
+    held(own.device(&p, need), what);
     have = need;
 }
 
-inline void grow(WorkArena& a, size_t need, const char* what) { grow(a.buf, a.bytes, need, what); }
-inline void arena_free(WorkArena& a) { if (a.buf) (void)hipFree(a.buf); a = WorkArena(); }
+inline void grow(WorkArena& a, size_t need, const char* what) { grow(a.own, a.buf, a.bytes, need, what); }
 
 // carves 256-byte aligned pieces out of the arena; with base == nullptr it only adds up
 struct Carver {

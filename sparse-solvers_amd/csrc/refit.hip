@@ -106,8 +106,7 @@ struct RefitState {
 
 RefitState* state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->rf) ctx->rf = new RefitState();
-    return static_cast<RefitState*>(ctx->rf);
+    return &part<RefitState>(ctx->rf);
 }
 
 // tile rows of the panel of a record with K stored columns (+ the column of y)
@@ -707,16 +706,6 @@ template int refit_nonneg<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, p
                                  char*, size_t);
 template int refit_nonneg<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, double*, uint32_t*, uint32_t*,
                                   char*, size_t);
-
-void refit_free(ss_hip_ctx* ctx)
-{
-    RefitState* rs = static_cast<RefitState*>(ctx->rf);
-    if (!rs) return;
-    arena_free(rs->batch);
-    arena_free(rs->arena);
-    delete rs;
-    ctx->rf = nullptr;
-}
 
 }  // namespace sship
 

@@ -1100,7 +1100,7 @@ hipError_t launch_res_solve(ss_hip_ctx* ctx, uint32_t nslots, const T* Gs, uint3
                             uint32_t* gam2, uint32_t* touched2, DevState* st, TraceEntry* trace, uint32_t trace_cap, bool omp)
 {
     if (!res_solve_usable<T>()) return hipErrorInvalidConfiguration;
-    static unsigned long long* dbg = nullptr;
+    static unsigned long long* dbg = nullptr;          // (developer aid of process lifetime: the one device buffer no owner holds)
     static const bool stamps = std::getenv("SS_HIP_RES_STAMPS") != nullptr;
     if (stamps && !omp) {
         static const bool ok = [] {

@@ -90,7 +90,39 @@ constexpr uint32_t kS64LogCap = 200, kS64LogK = 200;   // ... state log of the s
 static_assert(kSbS % kSgT == 0, "subset Gram tiles");
 static_assert(kSbLog - 1 <= kScrRhs, "screening pass: right-hand sides");
 
-struct ScreenState {
+// buffers of an fp64 batch chunk in the resident tier (launch_screen64_batch)
+constexpr uint32_t kS64Batch = 32;               // slots of a chunk
+struct Screen64Batch {
+    Holdings own;                // everything below
+    __half* y16 = nullptr;       // [128][ldm] the chunk's signals in fp16 (rows beyond the chunk: zeros)
+    float* ytab = nullptr;       // [128][kScrTab] 1 / (sA s_y) per signal (the writing mode's scale)
+    float* ymeta = nullptr;      // [kS64Batch][4] {||y||^2, threshold of the selection, 1 / s_y, spare}
+    float* cabs = nullptr;       // [kS64Batch][n_pad] |c~0|
+    uint32_t* sub = nullptr;     // [kS64Batch][S] the subsets (+ 2 words of scratch behind the last)
+    double* gs = nullptr;        // [kS64Batch][S][S]
+    double* gs_part = nullptr;   // [kS64Batch][kSg64MaxSplit][S][S]
+    uint32_t* hdr = nullptr; double* H = nullptr; uint32_t* pcol = nullptr; double* X = nullptr;     // the slots' logs
+    __half* r16 = nullptr;       // [kS64Batch][kS64Rhs][ldm]
+    float* rn2p = nullptr;       // [kS64Batch][ldm / 64][kS64Rhs]
+    float* tab = nullptr;        // [kS64Batch][kS64Rhs][kScrTab]
+    float* zero = nullptr;       // [ldm / 64][128] zeros (the writing mode reads no residual norms)
+    double* c0 = nullptr;        // [kS64Batch][n_pad] dense c0 of every slot: exact at its subset's columns
+};
+
+// a batch chunk in the screened form (kScrBatch slots): every slot its own residual block, subset Gram matrix, table — made by the first
+// such batch, all or nothing (owned by `batch`: a failed preparation leaves a fresh ScrBatchBufs)
+struct ScrBatchBufs {
+    Holdings batch;
+    __half* b_r16 = nullptr;     // [kScrBatch][kScrRhs][ldm]
+    float* b_rn2p = nullptr;     // [kScrBatch][ldm / 64][kScrRhs]
+    float* b_tab = nullptr;      // [kScrBatch][kScrRhs][kScrTab]
+    float* b_gs_part = nullptr;  // [kScrBatch][kSgSplit][kSbS][kSbS]
+    float* b_gs = nullptr;       // [kScrBatch][kSbS][kSbS]
+};
+
+struct ScreenState : ScrBatchBufs {
+    ~ScreenState() { if (sub) ss_hip_homotopy_destroy(sub); }      // (the sub-context first; then b64, then what `own` holds)
+    Holdings own;                // every device array below, the context's hand-off block, the sub-context's state log and pass partials
     __half* a16 = nullptr;       // [n_pad][ldm] fl16(sA * A), column-contiguous like A
     float* rank = nullptr;       // [n_pad] the rescue's ranking vector (made on first use)
     uint32_t rescue_first = 1, rescue_count = 0, rescue_first2 = 1, rescue_count2 = 0;   // which pieces of the list the rescue takes: first word, length
@@ -110,12 +142,6 @@ struct ScreenState {
     float* wmax = nullptr;       // [kScrWmax] k_scr_first: largest |c~0| per wave of its launch (the selection's floor)
     uint32_t* fl = nullptr;      // [kScrFlWords] the columns the certificate could not vouch for: re-checked exactly (k_scr_recheck)
     int gemm_attr = -1;
-    // a batch chunk in the screened form (kScrBatch slots): every slot its own residual block, subset Gram matrix, table
-    __half* b_r16 = nullptr;     // [kScrBatch][kScrRhs][ldm]
-    float* b_rn2p = nullptr;     // [kScrBatch][ldm / 64][kScrRhs]
-    float* b_tab = nullptr;      // [kScrBatch][kScrRhs][kScrTab]
-    float* b_gs_part = nullptr;  // [kScrBatch][kSgSplit][kSbS][kSbS]
-    float* b_gs = nullptr;       // [kScrBatch][kSbS][kSbS]
     // fp64 form: the path is solved by a context of its own over a sub-dictionary of kS64Sub columns
     ss_hip_ctx* sub = nullptr;
     float* cabs = nullptr;       // [n_pad] float(|c0|): what the selection ranks
@@ -132,27 +158,9 @@ struct ScreenState {
     uint32_t* rl_pcol = nullptr; // ... the positions' columns [144]
     double* rl_X = nullptr;      // ... x by position of every state [160][136]
     double* rl_D = nullptr;      // ... the direction by position likewise (the exact re-check's chain)
-    void* b64 = nullptr;         // Screen64Batch*: the buffers of an fp64 batch chunk in the resident tier (made by the first such batch)
+    std::unique_ptr<Screen64Batch> b64;   // the buffers of an fp64 batch chunk in the resident tier (made by the first such batch)
 };
 static_assert(kS64Rhs == 192, "the residual block of the fp64 forms (resident.hip: kR64Rhs)");
-// buffers of an fp64 batch chunk in the resident tier (launch_screen64_batch)
-constexpr uint32_t kS64Batch = 32;               // slots of a chunk
-struct Screen64Batch {
-    __half* y16 = nullptr;       // [128][ldm] the chunk's signals in fp16 (rows beyond the chunk: zeros)
-    float* ytab = nullptr;       // [128][kScrTab] 1 / (sA s_y) per signal (the writing mode's scale)
-    float* ymeta = nullptr;      // [kS64Batch][4] {||y||^2, threshold of the selection, 1 / s_y, spare}
-    float* cabs = nullptr;       // [kS64Batch][n_pad] |c~0|
-    uint32_t* sub = nullptr;     // [kS64Batch][S] the subsets (+ 2 words of scratch behind the last)
-    double* gs = nullptr;        // [kS64Batch][S][S]
-    double* gs_part = nullptr;   // [kS64Batch][kSg64MaxSplit][S][S]
-    uint32_t* hdr = nullptr; double* H = nullptr; uint32_t* pcol = nullptr; double* X = nullptr;     // the slots' logs
-    __half* r16 = nullptr;       // [kS64Batch][kS64Rhs][ldm]
-    float* rn2p = nullptr;       // [kS64Batch][ldm / 64][kS64Rhs]
-    float* tab = nullptr;        // [kS64Batch][kS64Rhs][kScrTab]
-    float* zero = nullptr;       // [ldm / 64][128] zeros (the writing mode reads no residual norms)
-    double* c0 = nullptr;        // [kS64Batch][n_pad] dense c0 of every slot: exact at its subset's columns
-};
-
 // ---- one-time preparation ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256)
@@ -1721,34 +1729,15 @@ void k_s64_finish(const uint32_t* __restrict__ sub, const double* __restrict__ x
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static ScreenState* scr_of(ss_hip_ctx* ctx) { return static_cast<ScreenState*>(ctx->screen); }
+static ScreenState* scr_of(ss_hip_ctx* ctx) { return ctx->screen.as<ScreenState>(); }
 
-void screen_free(ss_hip_ctx* ctx)
+// a preparation that did not fit: what it had obtained is given back, the form is not tried again on this context (-> false)
+static bool screen_off(ss_hip_ctx* ctx)
 {
-    ScreenState* S = scr_of(ctx);
-    if (!S) return;
-    void* ptrs[] = { S->rank, S->a8, S->a16, S->anorm, S->amaxc, S->meta, S->r16, S->rn2p, S->tab, S->gs_part, S->gs, S->wmax, S->cabs, S->sublist, S->xsub, S->xd, S->ctl,
-                     S->b_r16, S->b_rn2p, S->b_tab, S->b_gs_part, S->b_gs, S->fl, S->sub256, S->gs64, S->gs64_part, S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (ctx->handoff) { (void)hipFree(ctx->handoff); ctx->handoff = nullptr; }
-    if (S->b64) {
-        Screen64Batch* Bq = static_cast<Screen64Batch*>(S->b64);
-        void* bp[] = { Bq->y16, Bq->ytab, Bq->ymeta, Bq->cabs, Bq->sub, Bq->gs, Bq->gs_part, Bq->hdr, Bq->H, Bq->pcol, Bq->X, Bq->r16, Bq->rn2p, Bq->tab, Bq->zero, Bq->c0 };
-        for (void* p : bp) if (p) (void)hipFree(p);
-        delete Bq;
-        S->b64 = nullptr;
-    }
-    if (S->sub) {
-        if (S->sub->slog) (void)hipFree(S->sub->slog);
-        S->sub->slog = nullptr;
-        if (S->sub->pass_part) (void)hipFree(S->sub->pass_part);
-        S->sub->pass_part = nullptr;
-        S->sub->pass_ksplit = 0;
-        ss_hip_homotopy_destroy(S->sub);
-    }
-    delete S;
-    ctx->screen = nullptr;
+    ctx->screen.reset();
+    ctx->handoff = nullptr;
+    ctx->screen_failed_alloc = 1;
+    return false;
 }
 
 // ---- what a column replacement keeps current (dictupdate.hip) -------------------------------------------------------------------
@@ -1804,31 +1793,29 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     if (ctx->screen_single < 2 && ((size_t)ctx->m * ctx->n < ((size_t)16 << 20) || ctx->n < 8192u)) return false;
     if (!sub_form_usable(ctx)) return false;
     if (ctx->screen != nullptr) return true;
-    ScreenState* S = new ScreenState();
-    ctx->screen = S;
+    ScreenState* S = &part<ScreenState>(ctx->screen);
     bool ok = true;
-    auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
-    alloc(reinterpret_cast<void**>(&S->a16), (size_t)np * ldm * sizeof(__half));
-    alloc(reinterpret_cast<void**>(&S->anorm), (size_t)np * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->amaxc), (size_t)np * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->meta), kScrMeta * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->r16), (size_t)kScrRhs * ldm * sizeof(__half));
-    alloc(reinterpret_cast<void**>(&S->rn2p), (size_t)(ldm / 64u) * kScrRhs * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->tab), (size_t)kScrRhs * kScrTab * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->gs_part), (size_t)kSgSplit * kSbS * kSbS * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->gs), (size_t)kSbS * kSbS * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->wmax), (size_t)kScrWmax * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->fl), (size_t)kScrFlWords * sizeof(uint32_t));
+    ok = ok && S->own.device(&S->a16, (size_t)np * ldm * sizeof(__half)) == hipSuccess;
+    ok = ok && S->own.device(&S->anorm, (size_t)np * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->amaxc, (size_t)np * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->meta, kScrMeta * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->r16, (size_t)kScrRhs * ldm * sizeof(__half)) == hipSuccess;
+    ok = ok && S->own.device(&S->rn2p, (size_t)(ldm / 64u) * kScrRhs * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->tab, (size_t)kScrRhs * kScrTab * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->gs_part, (size_t)kSgSplit * kSbS * kSbS * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->gs, (size_t)kSbS * kSbS * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->wmax, (size_t)kScrWmax * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->fl, (size_t)kScrFlWords * sizeof(uint32_t)) == hipSuccess;
     // (the hand-off block: tickets and the selection's shared histogram in front — k_la_reset clears those at the start of every attempt —,
     // then the selection workgroups' counts and entries)
     const size_t ho_words = (size_t)kHoEnt + (np <= kHoSelCols ? (size_t)np + 4u * kHoSelWgs : 0u);
-    alloc(&ctx->handoff, ho_words * sizeof(uint32_t));
+    ok = ok && S->own.device(&ctx->handoff, ho_words * sizeof(uint32_t)) == hipSuccess;
     if (ok) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)scr_gemm_lds(kS64Sub));
         if (e != hipSuccess) { (void)hipGetLastError(); ok = false; }
     }
-    if (!ok) { screen_free(ctx); ctx->screen_failed_alloc = 1; return false; }
+    if (!ok) return screen_off(ctx);
     hipStream_t s = ctx->stream;
     const float* At = static_cast<const float*>(ctx->At);
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
@@ -1840,7 +1827,7 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<float>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
                        (const float*)S->meta, S->a16);
-    if (hipGetLastError() != hipSuccess) { screen_free(ctx); ctx->screen_failed_alloc = 1; return false; }
+    if (hipGetLastError() != hipSuccess) return screen_off(ctx);
     return true;
 }
 
@@ -1877,9 +1864,8 @@ static bool screen_first8_ready(ss_hip_ctx* ctx, ScreenState* S)
     const uint32_t ldm = ctx->ldm, np = ctx->n_pad;
     size_t free_b = 0, total_b = 0;
     const size_t bytes = (size_t)np * ldm;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)2 << 30) > free_b || hipMalloc(reinterpret_cast<void**>(&S->a8), bytes) != hipSuccess) {
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)2 << 30) > free_b || S->own.device(&S->a8, bytes) != hipSuccess) {
         (void)hipGetLastError();
-        S->a8 = nullptr;
         S->a8_failed = true;
         return false;
     }
@@ -1888,7 +1874,7 @@ static bool screen_first8_ready(ss_hip_ctx* ctx, ScreenState* S)
     hipLaunchKernelGGL(k_a8_scale, dim3(1), dim3(1), 0, s, S->meta);
     hipLaunchKernelGGL((k_a8_convert<TA>), dim3((unsigned)std::min<size_t>((total16 + 255) / 256, 65536)), dim3(256), 0, s, static_cast<const TA*>(ctx->At), total16,
                        (const float*)S->meta, S->a8);
-    if (hipGetLastError() != hipSuccess) { (void)hipFree(S->a8); S->a8 = nullptr; S->a8_failed = true; return false; }
+    if (hipGetLastError() != hipSuccess) { (void)S->own.drop(S->a8); S->a8_failed = true; return false; }
     return true;
 }
 template <typename TY> static bool scr_first8_attr()
@@ -2023,7 +2009,7 @@ hipError_t launch_screen_rescue_scan(ss_hip_ctx* ctx, Workspace<float>& ws, floa
     const SubBufs B = sub_bufs(ctx, 1);
     hipStream_t s = ctx->stream;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
-    if (S->rank == nullptr && hipMalloc(reinterpret_cast<void**>(&S->rank), (size_t)np * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); S->rank = nullptr; return hipErrorOutOfMemory; }
+    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)np * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
     const float* At = static_cast<const float*>(ctx->At);
     hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs,
                        (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
@@ -2075,17 +2061,14 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
     if (S->b_r16 == nullptr) {
         bool ok = true;
-        auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
-        alloc(reinterpret_cast<void**>(&S->b_r16), (size_t)kScrBatch * kScrRhs * ldm * sizeof(__half));
-        alloc(reinterpret_cast<void**>(&S->b_rn2p), (size_t)kScrBatch * (ldm / 64u) * kScrRhs * sizeof(float));
-        alloc(reinterpret_cast<void**>(&S->b_tab), (size_t)kScrBatch * kScrRhs * kScrTab * sizeof(float));
-        alloc(reinterpret_cast<void**>(&S->b_gs_part), (size_t)kScrBatch * kSgSplit * kSbS * kSbS * sizeof(float));
-        alloc(reinterpret_cast<void**>(&S->b_gs), (size_t)kScrBatch * kSbS * kSbS * sizeof(float));
+        ok = ok && S->batch.device(&S->b_r16, (size_t)kScrBatch * kScrRhs * ldm * sizeof(__half)) == hipSuccess;
+        ok = ok && S->batch.device(&S->b_rn2p, (size_t)kScrBatch * (ldm / 64u) * kScrRhs * sizeof(float)) == hipSuccess;
+        ok = ok && S->batch.device(&S->b_tab, (size_t)kScrBatch * kScrRhs * kScrTab * sizeof(float)) == hipSuccess;
+        ok = ok && S->batch.device(&S->b_gs_part, (size_t)kScrBatch * kSgSplit * kSbS * kSbS * sizeof(float)) == hipSuccess;
+        ok = ok && S->batch.device(&S->b_gs, (size_t)kScrBatch * kSbS * kSbS * sizeof(float)) == hipSuccess;
         if (ok && hipMemsetAsync(S->b_r16, 0, (size_t)kScrBatch * kScrRhs * ldm * sizeof(__half), ctx->stream) != hipSuccess) ok = false;
         if (!ok) {
-            void* ptrs[] = { S->b_r16, S->b_rn2p, S->b_tab, S->b_gs_part, S->b_gs };
-            for (void* p : ptrs) if (p) (void)hipFree(p);
-            S->b_r16 = nullptr; S->b_rn2p = nullptr; S->b_tab = nullptr; S->b_gs_part = nullptr; S->b_gs = nullptr;
+            static_cast<ScrBatchBufs&>(*S) = ScrBatchBufs();
             (void)hipGetLastError();
             return hipErrorOutOfMemory;
         }
@@ -2147,33 +2130,31 @@ bool screen64_usable(ss_hip_ctx* ctx)
     if (ctx->n < (ctx->screen_single >= 2 ? 4u : 16u) * kS64Sub) return false;
     if (ctx->screen_single < 2 && (size_t)ctx->m * ctx->n < ((size_t)64 << 20)) return false;
     if (ctx->screen != nullptr) return true;
-    ScreenState* S = new ScreenState();
-    ctx->screen = S;
+    ScreenState* S = &part<ScreenState>(ctx->screen);
     bool ok = true;
-    auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
-    alloc(reinterpret_cast<void**>(&S->a16), (size_t)np * ldm * sizeof(__half));
-    alloc(reinterpret_cast<void**>(&S->anorm), (size_t)np * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->amaxc), (size_t)np * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->meta), kScrMeta * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->r16), (size_t)kS64Rhs * ldm * sizeof(__half));
-    alloc(reinterpret_cast<void**>(&S->rn2p), (size_t)(ldm / 64u) * kS64Rhs * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->tab), (size_t)kS64Rhs * kScrTab * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->cabs), (size_t)np * sizeof(float));
-    alloc(reinterpret_cast<void**>(&S->sublist), ((size_t)kS64Sub + 2) * sizeof(uint32_t));
-    alloc(reinterpret_cast<void**>(&S->xsub), (size_t)kS64Sub * sizeof(double));
-    alloc(reinterpret_cast<void**>(&S->xd), (size_t)kS64LogK * (kS64Rhs + 8) * sizeof(double));
-    alloc(reinterpret_cast<void**>(&S->ctl), 8 * sizeof(uint32_t));
+    ok = ok && S->own.device(&S->a16, (size_t)np * ldm * sizeof(__half)) == hipSuccess;
+    ok = ok && S->own.device(&S->anorm, (size_t)np * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->amaxc, (size_t)np * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->meta, kScrMeta * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->r16, (size_t)kS64Rhs * ldm * sizeof(__half)) == hipSuccess;
+    ok = ok && S->own.device(&S->rn2p, (size_t)(ldm / 64u) * kS64Rhs * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->tab, (size_t)kS64Rhs * kScrTab * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->cabs, (size_t)np * sizeof(float)) == hipSuccess;
+    ok = ok && S->own.device(&S->sublist, ((size_t)kS64Sub + 2) * sizeof(uint32_t)) == hipSuccess;
+    ok = ok && S->own.device(&S->xsub, (size_t)kS64Sub * sizeof(double)) == hipSuccess;
+    ok = ok && S->own.device(&S->xd, (size_t)kS64LogK * (kS64Rhs + 8) * sizeof(double)) == hipSuccess;
+    ok = ok && S->own.device(&S->ctl, 8 * sizeof(uint32_t)) == hipSuccess;
     {
         typedef ResCfg<double> RC;
-        alloc(reinterpret_cast<void**>(&S->sub256), ((size_t)RC::S + 2) * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&S->gs64), (size_t)RC::S * RC::S * sizeof(double));
-        alloc(reinterpret_cast<void**>(&S->gs64_part), (size_t)kSg64MaxSplit * RC::S * RC::S * sizeof(double));
-        alloc(reinterpret_cast<void**>(&S->rl_hdr), (size_t)RC::LOGCAP * 8 * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&S->rl_H), (size_t)RC::LOGCAP * 2 * sizeof(double));
-        alloc(reinterpret_cast<void**>(&S->rl_pcol), (size_t)RC::PCAP * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&S->rl_X), (size_t)RC::LOGCAP * RC::PCAP * sizeof(double));
-        alloc(reinterpret_cast<void**>(&S->rl_D), (size_t)RC::LOGCAP * RC::PCAP * sizeof(double));
-        alloc(reinterpret_cast<void**>(&S->fl), (size_t)kScrFlWords * sizeof(uint32_t));
+        ok = ok && S->own.device(&S->sub256, ((size_t)RC::S + 2) * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && S->own.device(&S->gs64, (size_t)RC::S * RC::S * sizeof(double)) == hipSuccess;
+        ok = ok && S->own.device(&S->gs64_part, (size_t)kSg64MaxSplit * RC::S * RC::S * sizeof(double)) == hipSuccess;
+        ok = ok && S->own.device(&S->rl_hdr, (size_t)RC::LOGCAP * 8 * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && S->own.device(&S->rl_H, (size_t)RC::LOGCAP * 2 * sizeof(double)) == hipSuccess;
+        ok = ok && S->own.device(&S->rl_pcol, (size_t)RC::PCAP * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && S->own.device(&S->rl_X, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
+        ok = ok && S->own.device(&S->rl_D, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
+        ok = ok && S->own.device(&S->fl, (size_t)kScrFlWords * sizeof(uint32_t)) == hipSuccess;
         if (ok) (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), ctx->stream);
     }
     if (ok) {
@@ -2192,17 +2173,17 @@ bool screen64_usable(ss_hip_ctx* ctx)
         else {
             S->sub->screen_single = 0;
             (void)hipSetDevice(ctx->device);
-            if (hipMalloc(&S->sub->slog, s64_log_bytes()) != hipSuccess) { (void)hipGetLastError(); S->sub->slog = nullptr; ok = false; }
+            if (S->own.device(&S->sub->slog, s64_log_bytes()) != hipSuccess) ok = false;
             S->sub->slog_cap = kS64LogCap;
             S->sub->slog_kmax = kS64LogK;
             // its passes: 8 column tiles only — the rows split 16 (32) ways fill the chip
             uint32_t ks = 32;
             while (ks > 1 && (ldm % (ks * 16u) != 0 || ldm / ks < 256u)) ks >>= 1;
-            if (ks > 1 && hipMalloc(&S->sub->pass_part, (size_t)ks * 64 * S->sub->n_pad * sizeof(double)) == hipSuccess) S->sub->pass_ksplit = (int)ks;
-            else { (void)hipGetLastError(); S->sub->pass_part = nullptr; S->sub->pass_ksplit = 0; }
+            if (ks > 1 && S->own.device(&S->sub->pass_part, (size_t)ks * 64 * S->sub->n_pad * sizeof(double)) == hipSuccess) S->sub->pass_ksplit = (int)ks;
+            else S->sub->pass_ksplit = 0;
         }
     }
-    if (!ok) { screen_free(ctx); ctx->screen_failed_alloc = 1; return false; }
+    if (!ok) return screen_off(ctx);
     hipStream_t s = ctx->stream;
     const double* At = static_cast<const double*>(ctx->At);
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
@@ -2212,7 +2193,7 @@ bool screen64_usable(ss_hip_ctx* ctx)
     const size_t total8 = (size_t)np * ldm / 8;
     hipLaunchKernelGGL((k_a16_convert<double>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
                        (const float*)S->meta, S->a16);
-    if (hipGetLastError() != hipSuccess) { screen_free(ctx); ctx->screen_failed_alloc = 1; return false; }
+    if (hipGetLastError() != hipSuccess) return screen_off(ctx);
     return true;
 }
 
@@ -2309,7 +2290,7 @@ hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, d
     if (S == nullptr || S->sub256 == nullptr || S->fl == nullptr) return hipErrorInvalidConfiguration;
     hipStream_t s = ctx->stream;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
-    if (S->rank == nullptr && hipMalloc(reinterpret_cast<void**>(&S->rank), (size_t)np * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); S->rank = nullptr; return hipErrorOutOfMemory; }
+    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)np * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
     const ResLog<double> log{ S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
     (void)launch_res_residuals64(ctx, (const double*)ws.rhs, log, tol, S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, true, false, 1,
                                  nullptr, S->fl, true);
@@ -2436,7 +2417,7 @@ void k_y16_prep(const double* __restrict__ Y, uint32_t ldm, uint32_t nslots, con
     for (uint32_t i = tid; i < ldm; i += 256u) out[i] = __float2half_rn((float)y[i] * sc);
 }
 
-static Screen64Batch* s64b_of(ScreenState* S) { return static_cast<Screen64Batch*>(S->b64); }
+static Screen64Batch* s64b_of(ScreenState* S) { return S->b64.get(); }
 
 bool screen64_batch_usable(ss_hip_ctx* ctx)
 {
@@ -2453,36 +2434,33 @@ hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
     Screen64Batch* Bq = s64b_of(S);
     if (Bq == nullptr) {
-        Bq = new (std::nothrow) Screen64Batch();
-        if (Bq == nullptr) return hipErrorOutOfMemory;
+        std::unique_ptr<Screen64Batch> fresh(new (std::nothrow) Screen64Batch());
+        if (!fresh) return hipErrorOutOfMemory;
+        Bq = fresh.get();
         bool ok = true;
-        auto alloc = [&](void** p, size_t bytes) { if (ok && hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; } };
-        alloc(reinterpret_cast<void**>(&Bq->y16), (size_t)128 * ldm * sizeof(__half));
-        alloc(reinterpret_cast<void**>(&Bq->ytab), (size_t)128 * kScrTab * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->ymeta), (size_t)kS64Batch * 4 * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->cabs), (size_t)kS64Batch * np * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->sub), ((size_t)kS64Batch * RC::S + 2) * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&Bq->gs), (size_t)kS64Batch * RC::S * RC::S * sizeof(double));
-        alloc(reinterpret_cast<void**>(&Bq->gs_part), (size_t)kS64Batch * kSg64MaxSplit * RC::S * RC::S * sizeof(double));
-        alloc(reinterpret_cast<void**>(&Bq->hdr), (size_t)kS64Batch * RC::LOGCAP * 8 * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&Bq->H), (size_t)kS64Batch * RC::LOGCAP * 2 * sizeof(double));
-        alloc(reinterpret_cast<void**>(&Bq->pcol), (size_t)kS64Batch * RC::PCAP * sizeof(uint32_t));
-        alloc(reinterpret_cast<void**>(&Bq->X), (size_t)kS64Batch * RC::LOGCAP * RC::PCAP * sizeof(double));
-        alloc(reinterpret_cast<void**>(&Bq->r16), (size_t)kS64Batch * kS64Rhs * ldm * sizeof(__half));
-        alloc(reinterpret_cast<void**>(&Bq->rn2p), (size_t)kS64Batch * (ldm / 64u) * kS64Rhs * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->tab), (size_t)kS64Batch * kS64Rhs * kScrTab * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->zero), (size_t)(ldm / 64u) * 128 * sizeof(float));
-        alloc(reinterpret_cast<void**>(&Bq->c0), (size_t)kS64Batch * np * sizeof(double));
+        ok = ok && Bq->own.device(&Bq->y16, (size_t)128 * ldm * sizeof(__half)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->ytab, (size_t)128 * kScrTab * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->ymeta, (size_t)kS64Batch * 4 * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->cabs, (size_t)kS64Batch * np * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->sub, ((size_t)kS64Batch * RC::S + 2) * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->gs, (size_t)kS64Batch * RC::S * RC::S * sizeof(double)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->gs_part, (size_t)kS64Batch * kSg64MaxSplit * RC::S * RC::S * sizeof(double)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->hdr, (size_t)kS64Batch * RC::LOGCAP * 8 * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->H, (size_t)kS64Batch * RC::LOGCAP * 2 * sizeof(double)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->pcol, (size_t)kS64Batch * RC::PCAP * sizeof(uint32_t)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->X, (size_t)kS64Batch * RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->r16, (size_t)kS64Batch * kS64Rhs * ldm * sizeof(__half)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->rn2p, (size_t)kS64Batch * (ldm / 64u) * kS64Rhs * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->tab, (size_t)kS64Batch * kS64Rhs * kScrTab * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->zero, (size_t)(ldm / 64u) * 128 * sizeof(float)) == hipSuccess;
+        ok = ok && Bq->own.device(&Bq->c0, (size_t)kS64Batch * np * sizeof(double)) == hipSuccess;
         if (ok && (hipMemsetAsync(Bq->r16, 0, (size_t)kS64Batch * kS64Rhs * ldm * sizeof(__half), ctx->stream) != hipSuccess ||
                    hipMemsetAsync(Bq->zero, 0, (size_t)(ldm / 64u) * 128 * sizeof(float), ctx->stream) != hipSuccess)) ok = false;
         if (!ok) {
-            void* ptrs[] = { Bq->y16, Bq->ytab, Bq->ymeta, Bq->cabs, Bq->sub, Bq->gs, Bq->gs_part, Bq->hdr, Bq->H, Bq->pcol, Bq->X, Bq->r16, Bq->rn2p, Bq->tab, Bq->zero, Bq->c0 };
-            for (void* p : ptrs) if (p) (void)hipFree(p);
-            delete Bq;
             (void)hipGetLastError();
-            return hipErrorOutOfMemory;
+            return hipErrorOutOfMemory;      // (`fresh` gives back what it obtained)
         }
-        S->b64 = Bq;
+        S->b64 = std::move(fresh);
     }
     hipStream_t s = ctx->stream;
     const double* Y = ws.y;

@@ -6,10 +6,13 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "ss_hip.h"
+#include "host_common.h"
 
 namespace sship {
 
@@ -173,8 +176,38 @@ struct SlotDims {
     uint32_t pmin_stride;  // partial (min gamma, index) pairs per slot
 };
 
+// What Lookahead::ensure (homotopy.hip) allocates together and regrows together: the Gram-column cache of the lookahead engine and
+// what the speculative form keeps beside it, owned by `cache`.  A regrow is cache.release() and a fresh LaCache.
 template <typename T>
-struct Workspace {
+struct LaCache {
+    Holdings cache;
+    // lookahead engine (fp32 single-signal): cache of Gram columns g_j = A^T a_j
+    T* gcache = nullptr;          // [gcap][n_pad]
+    uint32_t gcap = 0;
+    uint32_t gpitch = 0;          // row pitch of gcache in elements (n_pad rounded up to 1024)
+    int32_t* slot_of = nullptr;   // [n_pad] cache slot of a column, -1 = not cached
+    T* c0 = nullptr;              // [n_pad] A^T y
+    T* tcand = nullptr;           // [n_pad] per-column step-length candidate of the last scan
+    uint32_t* sw_list = nullptr;  // [128] rcols[64] then drows[64] of the next lookahead sweep (32 or 64 columns)
+    uint32_t* sw_list2 = nullptr; // [128] the same for the fill-in sweeps of the early form (columns a solo launch used beyond the first 64)
+    uint32_t* sub_cols = nullptr; // [kSoloWidth] early form: the columns of the first solo launch (position 0 = the first pick)
+    float* subg = nullptr;        // [kSoloWidth][kSoloWidth] early form: Gs = A_S^T A_S of those columns (subgram.hip)
+    // speculative form (solo.hip)
+    uint32_t* slot_col = nullptr; // [gcap] column held by each cache slot
+    uint32_t* solo_log = nullptr; // [kSoloHeaderWords] + [kSoloLogCap][kSoloEntryWords]
+    uint8_t* sub_pos = nullptr;   // [n_pad] subset position of a column in the last solo launch (valid iff the header agrees)
+    uint32_t* solo_stage = nullptr; // [kSoloStageWords] staged hand-over of a solo launch
+    uint32_t* v_max = nullptr;    // [kSoloLogCap][nvwg] per-workgroup max |c| (bits) of every logged breakpoint
+    uint64_t* v_min = nullptr;    // [kSoloLogCap][nvwg] per-workgroup best step-length candidate (bits << 32 | column)
+    uint64_t* cand_top = nullptr; // [nvwg][kCandPerBlock] per-workgroup best entrant candidates (ordered key << 32 | column)
+    uint32_t nvwg = 0;            // workgroups of k_la_verify = ceil(n / kSoloWidth)
+};
+
+// Every array is owned by `own` (the lookahead cache: by LaCache::cache) — nothing here is freed by name.  In full-G mode gcache
+// points at the context's G, which is the context's to release.
+template <typename T>
+struct Workspace : LaCache<T> {
+    Holdings own;
     uint32_t b_cap = 0;    // slots allocated
     SlotDims dims{};
     // per-slot vectors
@@ -199,17 +232,6 @@ struct Workspace {
     T* sgn = nullptr;             // [b_cap][kcap]
     DevState* st = nullptr;       // [b_cap]
     uint32_t* ndone = nullptr;    // number of slots that raised `done` in the current (batch) solve
-    // lookahead engine (fp32 single-signal): cache of Gram columns g_j = A^T a_j
-    T* gcache = nullptr;          // [gcap][n_pad]
-    uint32_t gcap = 0;
-    uint32_t gpitch = 0;          // row pitch of gcache in elements (n_pad rounded up to 1024)
-    int32_t* slot_of = nullptr;   // [n_pad] cache slot of a column, -1 = not cached
-    T* c0 = nullptr;              // [n_pad] A^T y
-    T* tcand = nullptr;           // [n_pad] per-column step-length candidate of the last scan
-    uint32_t* sw_list = nullptr;  // [128] rcols[64] then drows[64] of the next lookahead sweep (32 or 64 columns)
-    uint32_t* sw_list2 = nullptr; // [128] the same for the fill-in sweeps of the early form (columns a solo launch used beyond the first 64)
-    uint32_t* sub_cols = nullptr; // [kSoloWidth] early form: the columns of the first solo launch (position 0 = the first pick)
-    float* subg = nullptr;        // [kSoloWidth][kSoloWidth] early form: Gs = A_S^T A_S of those columns (subgram.hip)
     LaSync* la_sync = nullptr;    // hand-off area of k_la_persist, followed by the offer slots
     T* cq_alt = nullptr;          // [2][n_pad] second (c, q) pair: k_la_persist alternates by tick parity
     // full-G mode of the single-signal engine (fp32): the context's G = A^T A serves as the cache — every
@@ -221,18 +243,10 @@ struct Workspace {
     uint32_t gpitch_own = 0;
     int32_t* slot_of_own = nullptr;
     int32_t* slot_identity = nullptr;   // [n_pad] 0, 1, 2, ...
-    // speculative form (solo.hip)
-    uint32_t* slot_col = nullptr; // [gcap] column held by each cache slot
-    uint32_t* solo_log = nullptr; // [kSoloHeaderWords] + [kSoloLogCap][kSoloEntryWords]
-    uint8_t* sub_pos = nullptr;   // [n_pad] subset position of a column in the last solo launch (valid iff the header agrees)
-    uint32_t* solo_stage = nullptr; // [kSoloStageWords] staged hand-over of a solo launch
-    uint32_t* v_max = nullptr;    // [kSoloLogCap][nvwg] per-workgroup max |c| (bits) of every logged breakpoint
-    uint64_t* v_min = nullptr;    // [kSoloLogCap][nvwg] per-workgroup best step-length candidate (bits << 32 | column)
-    uint64_t* cand_top = nullptr; // [nvwg][kCandPerBlock] per-workgroup best entrant candidates (ordered key << 32 | column)
-    uint32_t nvwg = 0;            // workgroups of k_la_verify = ceil(n / kSoloWidth)
     uint64_t* la_dbg = nullptr;   // [1024][8] stage timestamps of k_la_iter (environment variable SS_HIP_LA_DEBUG), else null
     uint32_t la_nparts = 0;       // partial maxima written by the last k_la_cq launch
     uint32_t* tile_skip = nullptr; // [b_pad/128 + 1] compact list of GEMM row tiles with a running signal + count
+    Holdings trace_own;           // the trace buffer alone: it survives a regrow of the arrays
     TraceEntry* trace = nullptr;  // [trace_cap] when tracing is on
     uint32_t trace_cap = 0;
 };
@@ -274,9 +288,33 @@ struct StepAside {
     void reset() { *this = StepAside{}; }
 };
 
+// A part of a context whose type only one unit knows: made on first use (part<S>), deleted — its own destructor releases what it
+// holds — with the context or by reset(), where a form is switched off after a failed preparation.
+class Part {
+public:
+    Part() = default;
+    Part(const Part&) = delete;
+    Part& operator=(const Part&) = delete;
+    ~Part() { reset(); }
+    void reset() { if (p_) del_(p_); p_ = nullptr; }
+    template <typename S> S* as() const { return static_cast<S*>(p_); }
+    template <typename S> S* hold(S* s) { reset(); p_ = s; del_ = [](void* q) { delete static_cast<S*>(q); }; return s; }
+    bool operator==(std::nullptr_t) const { return p_ == nullptr; }
+    bool operator!=(std::nullptr_t) const { return p_ != nullptr; }
+private:
+    void* p_ = nullptr;
+    void (*del_)(void*) = nullptr;
+};
+template <typename S> S& part(Part& slot) { return *(slot != nullptr ? slot.as<S>() : slot.hold(new S())); }
+
 }  // namespace sship
 
+// Destruction (ss_hip_homotopy_destroy: the streams synchronised, the reserve thread joined, then `delete ctx`) runs the members'
+// destructors in the reverse of their declaration.  So `own` is the FIRST member: the parts below it — the workspace, the screened
+// forms' state with its sub-context (a context of its own, with its own streams) — release what they hold before `own` gives back
+// the context's memory, then its events, and last the streams all of that was used on.
 struct ss_hip_ctx {
+    sship::Holdings own;              // At, G, the batch forms' buffers, the pinned flags and state, the events, the four streams
     // batched Gram form: the full G = A^T A ([n_pad][gram_pitch] fp32, made by the first large batch) and
     // the per-signal c0 = A^T y rows of the current chunk
     float* gram_full = nullptr;
@@ -288,8 +326,8 @@ struct ss_hip_ctx {
     // G's memory reserved ahead of its first use: a context that has received a batch of >= 4 signals will likely receive the large
     // one that forms G — the allocation (the driver clears fresh VRAM: ~0.5 s for 17 GiB) then runs on a helper thread beside the
     // batches before it instead of in front of the first large one (option gram_reserve; only where G is a small share of the HBM)
-    void* gram_reserve_thread = nullptr;     // std::thread*
-    float* gram_reserved = nullptr;          // what that thread obtained (read after join)
+    std::unique_ptr<std::thread> gram_reserve_thread;
+    float* gram_reserved = nullptr;          // what that thread obtained (read after the join, which hands it to `own`: gram_reserve_join)
     int gram_reserve = 1;
     float* c0_batch = nullptr;
     float* omp_gs = nullptr;          // OMP batches in the Gram form (ompbatch.hip): the subset Gram matrices of a chunk
@@ -308,8 +346,8 @@ struct ss_hip_ctx {
     hipEvent_t ev_sub_sel = nullptr;  // profiling: between the subset form's selection and its solves
     hipEvent_t ev_c0a = nullptr, ev_c0b = nullptr;   // profiling: around the batch GEMM c0 = A^T y of a chunk
     int batch_subset = 1;             // option: 1 = large Gram-form batches run in the subset form (one workgroup per signal + a check over all columns)
-    void* screen = nullptr;           // sship::ScreenState* (screen.hip): fp16 copy of A, column norms, the subset's Gram matrix, residual block
-    void* handoff = nullptr;          // its hand-off block (kHo*: tickets and a shared histogram that k_la_reset clears per attempt, then scratch lists)
+    sship::Part screen;               // sship::ScreenState* (screen.hip): fp16 copy of A, column norms, the subset's Gram matrix, residual block
+    void* handoff = nullptr;          // its hand-off block (owned by the ScreenState) (kHo*: tickets and a shared histogram that k_la_reset clears per attempt, then scratch lists)
     int screen_first16 = 1;           // option: the screened form's first pass (A^T y over all columns) reads the half-precision copy too
     int screen_single = 1;            // option: 1 = single fp32 signals on large dictionaries take the screened form (screen.hip), 2 = on every shape
                                       // the form can run on (tests), 0 = never
@@ -355,18 +393,18 @@ struct ss_hip_ctx {
     int gram_symmetric = 1;      // option: 1 = G is formed from the tiles on and above the diagonal + mirrored store, 0 = full product
     uint64_t single_solves = 0;  // single-signal solves since create (the trigger of gram_full_after; not a statistic)
     int colshard_fail_prepare = 0;   // test option: this rank's column-sharded solves fail in their preparation (the ranks must all leave)
-    void* colshard = nullptr;    // sship::ColShard* of a column-sharded context (colshard.hip): shard description, communicator, replicated active set
+    sship::Part colshard;        // sship::ColShard* of a column-sharded context (colshard.hip): shard description, communicator, replicated active set
     int kind = 0;            // 0 = Homotopy / OMP context, 1 = IRLS context
-    void* irls = nullptr;    // sship::IrlsState<T>* of an IRLS context
-    void* irls_batch = nullptr;   // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
+    sship::Part irls;        // sship::IrlsState<T>* of an IRLS context
+    sship::Part irls_batch;       // IRLS batch workspace (irlsbatch.hip), grown on demand, freed with irls
     int irls_batch_max = 256;     // option: most signals per chunk of an IRLS batch
-    void* cls = nullptr;          // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
-    void* learn = nullptr;        // sship::LearnArena* (dictlearn.hip): the one workspace of the atom update, the K-SVD sweep and the weighted atom update
-    void* rf = nullptr;           // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
-    void* coh = nullptr;          // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
-    void* tc = nullptr;           // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
-    void* js = nullptr;           // sship::WorkArena* (joint.hip): the workspace of the group class residuals
-    void* wt = nullptr;           // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
+    sship::Part cls;              // sship::ClassifyState* (classify.hip): the columns' class labels, the workspace of the record kernels
+    sship::Part learn;            // sship::LearnArena* (dictlearn.hip): the one workspace of the atom update, the K-SVD sweep and the weighted atom update
+    sship::Part rf;               // sship::RefitState* (refit.hip): the workspace of the least-squares refit of compact records
+    sship::Part coh;              // sship::CoherenceState* (coherence.hip): the workspace of the atom coherence
+    sship::Part tc;               // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
+    sship::Part js;               // sship::WorkArena* (joint.hip): the workspace of the group class residuals
+    sship::Part wt;               // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom updates hold at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -410,7 +448,7 @@ struct ss_hip_ctx {
     std::vector<sship::TraceEntry> last_trace;   // host copy of the last solve's path
 
     // workspace (type-erased; Workspace<float> or Workspace<double>)
-    void* ws = nullptr;
+    sship::Part ws;
     // pinned, device-mapped: [0] = last round the device started (fused lookahead engine: iteration
     // launches executed), [1] = done, [2] = iterations waiting for a lookahead sweep so far.
     // Written by the device with system-scope stores, polled by the host loop (no copies in the stream).
@@ -418,7 +456,7 @@ struct ss_hip_ctx {
     void* hs_pinned = nullptr;        // pinned landing place of the end-of-solve DevState copy (sizeof(DevState))
     void* hs_mapped = nullptr;        // its device address (k_epilogue writes the state there)
     uint32_t* dev_flags = nullptr;    // device address of host_flags
-    std::vector<hipEvent_t> prof_events;   // pairs (start, stop) for sweeps of the current solve
+    std::vector<hipEvent_t> prof_events;   // pairs (start, stop) for sweeps of the current solve (taken from `own`)
     std::vector<sship::ProfSpan> prof_spans;   // what each of those pairs bracketed, in the order they were handed out
     hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;
     int solo_attr_set = -1;                // dynamic-LDS attribute of the solo kernel: -1 not tried, 0 refused, 1 set
@@ -516,9 +554,6 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
 bool omp_gram_usable(ss_hip_ctx* ctx);
 uint32_t omp_gram_cap();
 hipError_t launch_omp_gram_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t nslots, const float* c0_all, float tol, uint32_t max_iter);
-void omp_gram_free(ss_hip_ctx* ctx);
-// classification from compact records (classify.hip): releases the labels and the workspace of a context
-void classify_free(ss_hip_ctx* ctx);
 // the atom update of dictionary learning (dictlearn.hip): the launches of its kernels, which the three learners' drivers (learn_driver.h:
 // dictlearn.hip, ksvd.hip, wdictlearn.hip) call, on the context's stream (every pointer on the device):
 // dl_launch_count: counts[S] and off[0 .. S + 1] (the offsets, the total, the longest list) of the atom -> user lists, and bad = the
@@ -540,29 +575,23 @@ hipError_t dl_launch_objective(ss_hip_ctx* ctx, const double* part, uint32_t per
 // (out(i, s) = out[i * ors + s * ocs]), p < nc — the changed atoms, contiguous, for the column replacement
 template <typename T>
 hipError_t dl_launch_gather(ss_hip_ctx* ctx, const T* out, long long ors, long long ocs, const uint32_t* sel, uint32_t nc, T* Vc);
-// the least-squares refit of compact records (refit.hip): releases its workspace
-void refit_free(ss_hip_ctx* ctx);
-// the coherence of atoms (coherence.hip): releases its workspace
-void coherence_free(ss_hip_ctx* ctx);
-// ... and the launch of its norms kernel the top correlations share with it, on the context's stream: out[i] = 1 / sqrt(d_i), d_i =
+// the coherence of atoms (coherence.hip): the launch of its norms kernel the top correlations share with it, on the context's stream: out[i] = 1 / sqrt(d_i), d_i =
 // sum_k a_ki^2 in double, for i < n_pad (0 for an excluded column: d_i zero or not finite, or i >= n) — k_coh_norms' words.  SUM: d_i
 // itself is stored instead (the weighted top correlations' visible share needs d_i, not its inverse root)
 template <typename T, bool SUM = false> hipError_t coh_launch_norms(ss_hip_ctx* ctx, double* out);
-// A workspace on the device that a call carves anew every time (arena_grow, tc_driver.h) — calls on a context are serial
+// A workspace on the device that a call carves anew every time (grow, record_common.h) — calls on a context are serial.  It owns its block
 struct WorkArena {
+    Holdings own;
     unsigned char* buf = nullptr;
     size_t bytes = 0;
 };
-// ... and the one of the top correlations (topcorr.hip), which the four selection calls (tc_driver.h) and the record extension carve.
-// topcorr_free releases it
+// ... and the one of the top correlations (topcorr.hip), which the four selection calls (tc_driver.h) and the record extension carve
 WorkArena& topcorr_arena(ss_hip_ctx* ctx);
-void topcorr_free(ss_hip_ctx* ctx);
 // the three arenas of the atom learning calls (dictlearn.hip; learn_driver.h carves them): the index (staged records, slot map, counts,
 // offsets, partial sums, usage), the workspace (the lists, the atoms [S][ldm], the residual blocks, a host caller's signals) and the
-// changed atoms of an apply.  Every call ends with its own stream synchronise, so the three calls share them.  learn_free releases them
+// changed atoms of an apply.  Every call ends with its own stream synchronise, so the three calls share them
 struct LearnArena { WorkArena index, work, vc; };
 LearnArena& learn_arena(ss_hip_ctx* ctx);
-void learn_free(ss_hip_ctx* ctx);
 // ... and the launches of a chunk's kernels behind the driver (tc_driver.h), on the context's stream, every pointer on
 // the device.  tc_launch_record_check: bad[0] = the first of B records with a column index >= n (else 0xffffffff).
 // tc_launch_residual_block: R[b][0 .. ldm) for Bc <= 32768 signals — y_b - A x_b from recs on (dl_launch_residuals, with its partials in
@@ -576,9 +605,7 @@ template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uin
 // ... and k_tc_tile with its squaring flag: D2 [tiles x 128][n_pad] = sum_k Wb[b][k] * (a_ki * a_ki), the square formed once in T where
 // At is staged — the second product of the weighted top correlations (weighted.hip); Wb [tiles x 128][ldm] as R above
 template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
-// weighted coding (weighted.hip): releases the staged weights
-void weighted_free(ss_hip_ctx* ctx);
-// what the three weighted calls and the weighted atom update (wdictlearn.hip) share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
+// weighted coding (weighted.hip): what the three weighted calls and the weighted atom update (wdictlearn.hip) share.  weights_check_args: a null W, a negative w_stride or one in 1 .. m - 1 (SS_HIP_EINVAL).
 // weights_on_device: the batch's weights where the kernels read them — W itself, or a staged copy of a host caller's (row pitch m, or
 // 0 for the shared vector) — after a device scan for the first weight that is negative or not finite (SS_HIP_EINVAL, the signal and
 // the row in the message; nothing has been written).  Throws what HIPCHK throws: call it under guarded
@@ -603,8 +630,6 @@ int weighted_residual_rows(ss_hip_ctx* ctx, const char* who, bool by_class, cons
 template <typename T>
 int refit_nonneg(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
                  double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
-// the group class residuals (joint.hip): releases their workspace
-void joint_free(ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of
 // `r_stride` >= num_classes elements and best [B], the words of that call.  Y, records, R and best on either side; `who` names the
 // caller in an error's text.  classify_num_classes: the classes set on the context, 0 for none.  Throws what HIPCHK throws
@@ -623,7 +648,6 @@ template <typename T>
 int replace_columns_device(ss_hip_ctx* ctx, const uint32_t* cols_dev, const std::vector<uint32_t>& cols_host, const T* V_dev, long long rs,
                            long long cs, char* err, size_t errlen);
 
-void screen_free(ss_hip_ctx* ctx);
 // what the screened forms derive from A, for a column replacement (dictupdate.hip) to keep current; every pointer null while the
 // preparation has not run (a8: until its first use).  screen_reconvert: the whole fp16 / fp8 copy again under the scales in meta
 struct ScreenCopies {
@@ -799,7 +823,6 @@ template <typename T> T* irls_y_buffer(ss_hip_ctx* ctx);
 template <typename T> T* irls_x_buffer(ss_hip_ctx* ctx);
 // the factorisation's device arrays: Q^T [n][ldm], R [n][n], tril(Q^T Q) [n][n]
 template <typename T> void irls_factors(ss_hip_ctx* ctx, const T** Qt, const T** R, const T** G0);
-void irls_free(ss_hip_ctx* ctx);   // (releases the batch workspace too)
 
 // ---- IRLS batches (irlsbatch.hip): every signal's words are the single solve's (irls_solve) bit for bit ----------
 // the chunk size for a batch of B signals (irls_batch_max, a byte budget, a failed allocation halves it), the workspace grown to it
@@ -810,7 +833,6 @@ template <typename T> T* irls_batch_x(ss_hip_ctx* ctx, uint32_t slot);   // [n] 
 // *rounds = lock-step rounds of the blocked form (one host read each; 0 for the one-workgroup form)
 template <typename T> hipError_t irls_batch_run(ss_hip_ctx* ctx, const T* Qt, const T* R, const T* G0, uint32_t nb, T tol,
                                                 uint32_t max_iter, IrlsResult* res_host, uint64_t* rounds);
-void irls_batch_free(ss_hip_ctx* ctx);
 
 // the same pass in fp64 (v_mfma_f64_16x16x4_f64), 32 or 64 right-hand sides
 hipError_t launch_gemm32_tn_f64(const ss_hip_ctx* ctx, const uint32_t* rcols, const uint32_t* drows,
@@ -819,12 +841,9 @@ hipError_t launch_gemm64_tn_f64(const ss_hip_ctx* ctx, const uint32_t* rcols, co
                                 double* D, uint32_t ldd, const DevState* st);
 
 // ---- helpers implemented in homotopy.hip ---------------------------------------
-// (the rest of the host side the entry points share — HipFail / HIPCHK, guarded, on_device, record_bytes, DeviceBuf — is host_common.h)
-// msg into the caller's buffer, cut to errlen - 1 characters and always terminated; a null or empty buffer is left alone
-void set_err(char* err, size_t errlen, const std::string& msg);
+// (the rest of the host side the entry points share — set_err, HipFail / HIPCHK, guarded, on_device, record_bytes, DeviceBuf, Holdings — is
+// host_common.h)
 // the one-slot fp32 workspace of a context with an active-set capacity of at least kcap (0 / ss_hip_status)
 int colshard_workspace(ss_hip_ctx* ctx, uint32_t kcap);
-// ---- colshard.hip: releases the column-sharded state of a context (communicator, replicated active set)
-void colshard_destroy(ss_hip_ctx* ctx);
 
 }  // namespace sship

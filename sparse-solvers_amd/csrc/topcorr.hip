@@ -443,17 +443,7 @@ template hipError_t tc_launch_weight_dots<double>(ss_hip_ctx*, const double*, ui
 
 WorkArena& topcorr_arena(ss_hip_ctx* ctx)
 {
-    if (!ctx->tc) ctx->tc = new WorkArena();
-    return *static_cast<WorkArena*>(ctx->tc);
-}
-
-void topcorr_free(ss_hip_ctx* ctx)
-{
-    WorkArena* ts = static_cast<WorkArena*>(ctx->tc);
-    if (!ts) return;
-    arena_free(*ts);
-    delete ts;
-    ctx->tc = nullptr;
+    return part<WorkArena>(ctx->tc);
 }
 
 }  // namespace sship

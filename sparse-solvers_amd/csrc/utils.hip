@@ -115,13 +115,13 @@ int norm_l1_impl(T* A, size_t m, size_t n, ptrdiff_t rs, ptrdiff_t cs, int devic
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); set_err(err, errlen, "norm_l1: no HIP device available"); return SS_HIP_ENODEVICE; }
     if (device < 0 || device >= ndev) { set_err(err, errlen, "norm_l1: device index out of range"); return SS_HIP_EINVAL; }
     // the call's own stream and scratch, released in this order on every way out: partial, sums, stage, the stream
-    struct OwnStream { hipStream_t st = nullptr; ~OwnStream() { if (st) (void)hipStreamDestroy(st); } } own;
+    Holdings own;
+    hipStream_t st = nullptr;
     DeviceBuf stage_buf, sums_buf, partial_buf;
     // (like the solver's entry points, every failed HIP call reports SS_HIP_ERUNTIME, an allocation included)
     return guarded(err, errlen, "norm_l1", [&]() -> int {
-        hipStream_t& st = own.st;
         HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        HELD(own, hipStreamCreateWithFlags, &st, hipStreamNonBlocking);
         sums_buf.alloc(n * sizeof(T), "hipMalloc(&sums, n * sizeof(T))");
         T* sums = sums_buf.get<T>();
         if (on_device(A)) {

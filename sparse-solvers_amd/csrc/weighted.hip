@@ -56,14 +56,14 @@ namespace {
 constexpr unsigned long long kWtNoBad = ~0ull;
 
 struct WeightedState {
+    Holdings own;
     unsigned char* wbuf = nullptr;     // per call: the first-offender word, then a host caller's weights
     size_t wbuf_bytes = 0;
 };
 
 WeightedState* state_of(ss_hip_ctx* ctx)
 {
-    if (!ctx->wt) ctx->wt = new WeightedState();
-    return static_cast<WeightedState*>(ctx->wt);
+    return &part<WeightedState>(ctx->wt);
 }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------
@@ -210,7 +210,7 @@ int weights_on_device(ss_hip_ctx* ctx, const char* who, const T* W, size_t B, pt
     hipStream_t st = ctx->stream;
     const size_t m = ctx->m, rows = w_stride == 0 ? 1 : B;
     const bool w_dev = on_device(W);
-    grow(ws->wbuf, ws->wbuf_bytes, 256 + (w_dev ? 0 : rows * m * sizeof(T)), "hipMalloc(weights)");
+    grow(ws->own, ws->wbuf, ws->wbuf_bytes, 256 + (w_dev ? 0 : rows * m * sizeof(T)), "hipMalloc(weights)");
     unsigned long long* bad = reinterpret_cast<unsigned long long*>(ws->wbuf);
     const T* wd = W;
     long long pitch = (long long)w_stride;
@@ -240,15 +240,6 @@ int weights_on_device(ss_hip_ctx* ctx, const char* who, const T* W, size_t B, pt
 
 template int weights_on_device<float>(ss_hip_ctx*, const char*, const float*, size_t, ptrdiff_t, const float**, long long*, char*, size_t);
 template int weights_on_device<double>(ss_hip_ctx*, const char*, const double*, size_t, ptrdiff_t, const double**, long long*, char*, size_t);
-
-void weighted_free(ss_hip_ctx* ctx)
-{
-    WeightedState* ws = static_cast<WeightedState*>(ctx->wt);
-    if (!ws) return;
-    if (ws->wbuf) (void)hipFree(ws->wbuf);
-    delete ws;
-    ctx->wt = nullptr;
-}
 
 }  // namespace sship
 

@@ -1,6 +1,7 @@
 // Host program over csrc/host_common.h (tests/test_host_common.py builds and runs it): what guarded() returns and writes for
-// everything a body can throw, set_err's truncation, on_device for host memory, record_bytes, and, where a device is visible, one
-// DeviceBuf allocated, moved from and destroyed.  No kernel is launched and no allocation is sized to fail.
+// everything a body can throw, set_err's truncation, on_device for host memory, record_bytes, the text HELD makes, and, where a device
+// is visible, one DeviceBuf allocated, moved from and destroyed and one Holdings that takes each kind, drops one, is moved from and
+// released.  No kernel is launched and no allocation is sized to fail.
 #include "host_common.h"
 
 #include <cstdio>
@@ -9,6 +10,12 @@
 #include <string>
 
 using namespace sship;
+
+// a "call" for HELD that takes nothing: it hands back the text the macro made for it
+namespace sship { namespace {
+inline void held_Probe(Holdings&, const char** out, const char* what) { *out = what; }
+template <typename P> void held_Probe(Holdings&, const char** out, P**, size_t, unsigned, const char* what) { *out = what; }
+} }
 
 static int g_failed = 0;
 #define CHECK(cond) do { if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); g_failed += 1; } } while (0)
@@ -112,6 +119,72 @@ int main()
         std::printf("DeviceBuf: checked\n");
     } else {
         std::printf("DeviceBuf: skipped (no HIP device)\n");
+    }
+
+    // ---- Holdings: nothing to take is nothing held; the rest needs a device
+    {
+        Holdings none;
+        CHECK(none.size() == 0);
+        int* p = nullptr;
+        CHECK(none.drop(p) == hipSuccess && p == nullptr);      // a null pointer is nobody's
+        none.release();
+        CHECK(none.size() == 0);
+    }
+    if (ss_hip_device_count() > 0) {
+        {
+            Holdings own;
+            float* d0 = nullptr; unsigned char* d1 = nullptr; uint32_t* pin = nullptr;
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            hipStream_t s0 = nullptr, s1 = nullptr;
+            // the non-throwing takes, one of each kind
+            CHECK(own.device(&d0, 1024) == hipSuccess && d0 != nullptr && on_device(d0));
+            CHECK(own.pinned(&pin, 256, hipHostMallocDefault) == hipSuccess && pin != nullptr);
+            CHECK(own.event(&e0) == hipSuccess && e0 != nullptr);
+            CHECK(own.event(&e1, hipEventDisableTiming) == hipSuccess && e1 != nullptr);
+            CHECK(own.stream(&s0, hipStreamNonBlocking) == hipSuccess && s0 != nullptr);
+            CHECK(own.stream(&s1, hipStreamNonBlocking, 0) == hipSuccess && s1 != nullptr);
+            CHECK(own.size() == 6);
+            // the throwing takes through the macro: they take, and a failure would carry the call's text
+            CHECK(run(msg, [&]() -> int { HELD(own, hipMalloc, &d1, 4096); return 5; }) == 5);
+            CHECK(d1 != nullptr && own.size() == 7);
+            pin[0] = 7u;
+            CHECK(hipMemcpyAsync(d0, pin, 4, hipMemcpyHostToDevice, s0) == hipSuccess && hipEventRecord(e0, s0) == hipSuccess);
+            CHECK(hipEventSynchronize(e0) == hipSuccess);
+            // drop of one (the pointer is nulled, the rest stays), of one it does not hold (nothing happens)
+            CHECK(own.drop(d0) == hipSuccess && d0 == nullptr && own.size() == 6);
+            int on_stack = 0;
+            int* stranger = &on_stack;
+            CHECK(own.drop(stranger) == hipSuccess && stranger == nullptr && own.size() == 6);
+            CHECK(own.drop(e1) == hipSuccess && e1 == nullptr && own.size() == 5);
+            // moved from: holds nothing; the new owner holds all of it
+            Holdings heir(std::move(own));
+            CHECK(own.size() == 0 && heir.size() == 5);
+            own.release();
+            Holdings third;
+            third = std::move(heir);
+            CHECK(heir.size() == 0 && third.size() == 5);
+            // released: holds nothing, and may be released again and used again
+            third.release();
+            CHECK(third.size() == 0);
+            third.release();
+            CHECK(third.device(&d0, 64) == hipSuccess && third.size() == 1);
+        }
+        CHECK(hipGetLastError() == hipSuccess);
+        CHECK(std::string(hip_msg(HipFail{ hipErrorOutOfMemory, "hipMalloc(&p, bytes)" })) == "HIP error: out of memory in hipMalloc(&p, bytes)");
+        std::printf("Holdings: checked\n");
+    } else {
+        std::printf("Holdings: skipped (no HIP device)\n");
+    }
+    // the macro's text is the text of the call it stands for (no device needed: the take is never made)
+    {
+        Holdings own;
+        struct { uint32_t* host_flags = nullptr; } c, *ctx = &c;
+        const char* text = nullptr;
+        HELD(own, Probe, &text, &ctx->host_flags, 64 * sizeof(uint32_t), hipHostMallocMapped);
+        CHECK(std::string(text) == "Probe(&text, &ctx->host_flags, 64 * sizeof(uint32_t), hipHostMallocMapped)");
+        HELD(own, Probe, &text);
+        CHECK(std::string(text) == "Probe(&text)");
+        CHECK(own.size() == 0);
     }
 
     std::printf(g_failed ? "%d check(s) failed\n" : "all checks passed\n", g_failed);

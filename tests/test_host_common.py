@@ -1,10 +1,11 @@
 """The host-side toolkit of the C-ABI entry points (sparse-solvers_amd/csrc/host_common.h): a failed HIP call as a status and a
-message, where a pointer lives, the size of a compact record, the owner of a call's scratch allocation.
+message, where a pointer lives, the size of a compact record, the owner of a call's scratch allocation, the owner of what a
+context keeps (Holdings).
 
 tests/cpp/test_host_common.cpp includes the header and checks it as a host program (built with the compiler and the target
 build.py uses, linked against the built libss_hip.so for set_err); it launches no kernel, and without a device it skips its
-DeviceBuf part and says so.  The source-level tests keep the toolkit single: one pointer query, one exception struct, one
-throwing macro, one record_bytes.
+DeviceBuf and Holdings parts and says so.  The source-level tests keep the toolkit single: one pointer query, one exception struct,
+one throwing macro, one record_bytes, one place that gives anything back to the runtime.
 """
 import importlib.util
 import os
@@ -58,6 +59,14 @@ def test_device_buf_part_runs_exactly_where_a_device_is(program_output):
         assert "DeviceBuf: skipped (no HIP device)" in program_output, program_output
 
 
+def test_holdings_part_runs_exactly_where_a_device_is(program_output):
+    import sship
+    if sship.device_count() > 0:
+        assert "Holdings: checked" in program_output, program_output
+    else:
+        assert "Holdings: skipped (no HIP device)" in program_output, program_output
+
+
 def test_record_bytes_is_the_same_everywhere(program_output):
     """the header's record_bytes (printed by the program), the C-ABI's ss_hip_record_bytes and the layout's formula"""
     import sship
@@ -102,3 +111,23 @@ def test_record_bytes_is_defined_once():
     # a definition: a return type in front of the name, a body behind the parameter list (ss_hip_record_bytes is the C-ABI's name)
     hits = _where(r"\b(?:size_t|auto)\s+record_bytes\s*\([^)]*\)\s*(?:noexcept\s*)?\{")
     assert [h.split(":")[0] for h in hits] == ["host_common.h"], hits
+
+
+# ---- release follows from allocation: the owner in host_common.h is the one place that gives anything back ---------------------
+
+def test_only_host_common_releases():
+    for call in ("hipFree", "hipHostFree", "hipEventDestroy", "hipStreamDestroy"):
+        hits = _where(r"\b%s\(" % call)
+        assert hits and all(h.startswith("host_common.h:") for h in hits), (call, hits)
+
+
+def test_no_hand_kept_pointer_list_is_left():
+    assert not _where(r"\bvoid\s*\*\s*\w+\s*\[\s*\]\s*=\s*\{")
+
+
+def test_no_release_function_takes_a_context():
+    assert not [h for h in _where(r"\b\w+_free\(\s*ss_hip_ctx") if h.startswith("ss_hip_internal.h:")]
+    # ... and the destructor of a context names no member: synchronise, join, delete
+    hom = _sources()["homotopy.hip"]
+    body = re.search(r"void ss_hip_homotopy_destroy\(ss_hip_ctx\* ctx\)\n\{(.*?)\n\}", hom, re.S).group(1)
+    assert "delete ctx;" in body and "_free(" not in body and "own." not in body, body
