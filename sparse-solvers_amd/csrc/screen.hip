@@ -90,6 +90,34 @@ constexpr uint32_t kS64LogCap = 200, kS64LogK = 200;   // ... state log of the s
 static_assert(kSbS % kSgT == 0, "subset Gram tiles");
 static_assert(kSbLog - 1 <= kScrRhs, "screening pass: right-hand sides");
 
+// One all-or-nothing preparation: device arrays from one owner, taken in the order written; after the first that does not fit nothing
+// more is asked for (ok = false: the caller gives back what the owner holds)
+struct Takes {
+    Holdings& own;
+    bool ok = true;
+    template <typename P> Takes& operator()(P** p, size_t bytes) { if (ok && own.device(p, bytes) != hipSuccess) ok = false; return *this; }
+};
+
+// The residual block of a screening pass: always taken, cleared, filled (k_scr_residuals, k_s64_residuals, k_res_residuals64) and read
+// (k_scr_gemm, k_scr_gemm_b) together.  With slots the kernels add the slot offsets themselves.
+struct ResBlock {
+    __half* r16 = nullptr;       // [slots][rhs][ldm] fl16(s_k * r_k)
+    float* rn2p = nullptr;       // [slots][ldm / 64][rhs] partial sums of ||r_k||^2, one per workgroup of the residual kernel
+    float* tab = nullptr;        // [slots][rhs][kScrTab]
+    uint32_t rhs = 0;            // right-hand sides (states) per slot: the pitch of rn2p
+
+    void take(Takes& t, uint32_t rhs_, uint32_t ldm, size_t slots = 1)
+    {
+        rhs = rhs_;
+        t(&r16, slots * rhs * ldm * sizeof(__half))(&rn2p, slots * (ldm / 64u) * rhs * sizeof(float))(&tab, slots * rhs * kScrTab * sizeof(float));
+    }
+    // (rows no residual kernel writes are read by the pass as zeros)
+    hipError_t clear(uint32_t ldm, size_t slots, hipStream_t s) const { return hipMemsetAsync(r16, 0, slots * rhs * ldm * sizeof(__half), s); }
+    // one slot's block; the states from k0 on (same pitch)
+    ResBlock slot(size_t b, uint32_t ldm) const { return { r16 + b * rhs * ldm, rn2p + b * (ldm / 64u) * rhs, tab + b * rhs * kScrTab, rhs }; }
+    ResBlock from(uint32_t k0, uint32_t ldm) const { return { r16 + (size_t)k0 * ldm, rn2p + k0, tab + (size_t)k0 * kScrTab, rhs }; }
+};
+
 // buffers of an fp64 batch chunk in the resident tier (launch_screen64_batch)
 constexpr uint32_t kS64Batch = 32;               // slots of a chunk
 struct Screen64Batch {
@@ -102,9 +130,7 @@ struct Screen64Batch {
     double* gs = nullptr;        // [kS64Batch][S][S]
     double* gs_part = nullptr;   // [kS64Batch][kSg64MaxSplit][S][S]
     uint32_t* hdr = nullptr; double* H = nullptr; uint32_t* pcol = nullptr; double* X = nullptr;     // the slots' logs
-    __half* r16 = nullptr;       // [kS64Batch][kS64Rhs][ldm]
-    float* rn2p = nullptr;       // [kS64Batch][ldm / 64][kS64Rhs]
-    float* tab = nullptr;        // [kS64Batch][kS64Rhs][kScrTab]
+    ResBlock res;                // [kS64Batch] x kS64Rhs states
     float* zero = nullptr;       // [ldm / 64][128] zeros (the writing mode reads no residual norms)
     double* c0 = nullptr;        // [kS64Batch][n_pad] dense c0 of every slot: exact at its subset's columns
 };
@@ -113,9 +139,7 @@ struct Screen64Batch {
 // such batch, all or nothing (owned by `batch`: a failed preparation leaves a fresh ScrBatchBufs)
 struct ScrBatchBufs {
     Holdings batch;
-    __half* b_r16 = nullptr;     // [kScrBatch][kScrRhs][ldm]
-    float* b_rn2p = nullptr;     // [kScrBatch][ldm / 64][kScrRhs]
-    float* b_tab = nullptr;      // [kScrBatch][kScrRhs][kScrTab]
+    ResBlock b_res;              // [kScrBatch] x kScrRhs states
     float* b_gs_part = nullptr;  // [kScrBatch][kSgSplit][kSbS][kSbS]
     float* b_gs = nullptr;       // [kScrBatch][kSbS][kSbS]
 };
@@ -134,9 +158,7 @@ struct ScreenState : ScrBatchBufs {
                                  // [4] max ||a_i||  [5] ||y||^2 (k_scr_first)  [6] what the columns left out of the subset stay below (selection)
                                  // [12] 2^-u  [13] 2^u, u = dict_unit_exp([4]): the units of an fp64 dictionary's columns (1, 1 in an fp32
                                  // context)  [14] 1 where [12], [13] follow [4] (fp64), 0 where they stay 1
-    __half* r16 = nullptr;       // [kScrRhs][ldm] fl16(s_k * r_k)
-    float* rn2p = nullptr;       // [ldm / 64][kScrRhs] partial sums of ||r_k||^2, one per workgroup of k_scr_residuals
-    float* tab = nullptr;        // [kScrRhs][kScrTab]
+    ResBlock res;                // one signal's: kScrRhs states (fp32), kS64Rhs (fp64)
     float* gs_part = nullptr;    // [kSgSplit][kSbS][kSbS]
     float* gs = nullptr;         // [kSbS][kSbS]
     float* wmax = nullptr;       // [kScrWmax] k_scr_first: largest |c~0| per wave of its launch (the selection's floor)
@@ -1729,7 +1751,13 @@ void k_s64_finish(const uint32_t* __restrict__ sub, const double* __restrict__ x
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+// Every stage of the screened solve is launched from ONE function below (launch_* / scr_pass); the drivers behind them — the fp32 form,
+// its rescue scan, the fp32 batch chunk, the fp64 sub-dictionary tier, the fp64 resident tier, its rescue scan, the fp64 batch chunk —
+// say what they vary.  Launch results are dropped; each driver reads hipGetLastError() once at its end.
 static ScreenState* scr_of(ss_hip_ctx* ctx) { return ctx->screen.as<ScreenState>(); }
+
+// the headroom of the last solve (meta[3], a float's bits): the residual kernels reset it, the screening passes raise it
+static uint32_t* scr_headroom(const ScreenState& S) { return reinterpret_cast<uint32_t*>(S.meta) + 3; }
 
 // a preparation that did not fit: what it had obtained is given back, the form is not tried again on this context (-> false)
 static bool screen_off(ss_hip_ctx* ctx)
@@ -1748,22 +1776,28 @@ ScreenCopies screen_copies(ss_hip_ctx* ctx)
     return c;
 }
 
-// the whole fp16 / fp8 copy again under the scales meta[0] / meta[10] hold now: the preparation's own conversion passes
+// the fp16 / fp8 copy of the whole dictionary under the scales meta[0] / meta[10] hold now
+static dim3 scr_convert_grid(size_t items) { return dim3((unsigned)std::min<size_t>((items + 255) / 256, 65536)); }
+template <typename TA>
+static void launch_a16_convert(ss_hip_ctx* ctx, const ScreenState& S)
+{
+    const size_t total8 = (size_t)ctx->n_pad * ctx->ldm / 8;
+    hipLaunchKernelGGL((k_a16_convert<TA>), scr_convert_grid(total8), dim3(256), 0, ctx->stream, static_cast<const TA*>(ctx->At), total8, (const float*)S.meta, S.a16);
+}
+template <typename TA>
+static void launch_a8_convert(ss_hip_ctx* ctx, const ScreenState& S)
+{
+    const size_t total16 = (size_t)ctx->n_pad * ctx->ldm / 16;
+    hipLaunchKernelGGL((k_a8_convert<TA>), scr_convert_grid(total16), dim3(256), 0, ctx->stream, static_cast<const TA*>(ctx->At), total16, (const float*)S.meta, S.a8);
+}
+
+// ... again, after columns were replaced: the preparation's own conversion passes
 hipError_t screen_reconvert(ss_hip_ctx* ctx, bool a16, bool a8)
 {
     ScreenState* S = scr_of(ctx);
     if (S == nullptr) return hipErrorInvalidConfiguration;
-    const size_t total = (size_t)ctx->n_pad * ctx->ldm;
-    hipStream_t s = ctx->stream;
-    auto grid = [](size_t items) { return dim3((unsigned)std::min<size_t>((items + 255) / 256, 65536)); };
-    if (a16 && S->a16 != nullptr) {
-        if (ctx->is_f64) hipLaunchKernelGGL((k_a16_convert<double>), grid(total / 8), dim3(256), 0, s, static_cast<const double*>(ctx->At), total / 8, (const float*)S->meta, S->a16);
-        else hipLaunchKernelGGL((k_a16_convert<float>), grid(total / 8), dim3(256), 0, s, static_cast<const float*>(ctx->At), total / 8, (const float*)S->meta, S->a16);
-    }
-    if (a8 && S->a8 != nullptr) {
-        if (ctx->is_f64) hipLaunchKernelGGL((k_a8_convert<double>), grid(total / 16), dim3(256), 0, s, static_cast<const double*>(ctx->At), total / 16, (const float*)S->meta, S->a8);
-        else hipLaunchKernelGGL((k_a8_convert<float>), grid(total / 16), dim3(256), 0, s, static_cast<const float*>(ctx->At), total / 16, (const float*)S->meta, S->a8);
-    }
+    if (a16 && S->a16 != nullptr) { if (ctx->is_f64) launch_a16_convert<double>(ctx, *S); else launch_a16_convert<float>(ctx, *S); }
+    if (a8 && S->a8 != nullptr) { if (ctx->is_f64) launch_a8_convert<double>(ctx, *S); else launch_a8_convert<float>(ctx, *S); }
     return hipGetLastError();
 }
 
@@ -1780,8 +1814,131 @@ static size_t scr_gemm_lds(uint32_t nsub, uint32_t nt = 3)
     return std::max<size_t>((size_t)(kScrCols + rh) * kScrPitchB, (rh * 4 + nsub + pb * rh) * 4);
 }
 
-// Shape / option test, and — the first time it says yes — the preparation: the fp16 copy of A (half of A's bytes again),
-// the column norms.  A failed allocation switches the form off for this context (the default engine goes on as before).
+// ---- the screening pass ------------------------------------------------------------------------------------------------------------
+// What one launch of k_scr_gemm varies.  The launcher supplies the rest: the fp16 copy, the norms, meta, the headroom word, the skew, one
+// workgroup per 128 columns (and slot), the LDS size of (nsub, NT).
+struct ScrPass {
+    ResBlock res;                     // the states' residuals, norms and table (slot 0's: the kernel adds the slot offsets)
+    const uint32_t* sub = nullptr;    // the subset whose columns the certificate leaves out, ...
+    uint32_t nsub = 0;                // ... its size (0 in the writing mode: up to 2048 columns the LDS size is the main loop's tiles either way)
+    DevState* st = nullptr;
+    uint32_t slots = 1;
+    uint32_t nst_fixed = 0;           // 0: as many states as the slot's log holds; a count; 0xffffffff: only the slots whose log passed 64 states
+    uint32_t gate = 0;                // 0: always; 1 / 2: the log holds up to / more than 128 states; 3: the rescue's scan
+    uint32_t* fl = nullptr;           // the list for the exact re-check (or the scan's lists)
+    const float* c0h = nullptr;       // the first pass's c~0: state 0 is certified too
+    float* out_abs = nullptr;         // writing mode (the ranking of an fp64 batch): |c~| of every (right-hand side, column), ...
+    uint32_t out_pitch = 0;           // ... its pitch
+};
+
+// NT tiles of 32 states per workgroup
+template <int NT>
+static void scr_pass(const ss_hip_ctx* ctx, const ScreenState& S, const ScrPass& p)
+{
+    hipLaunchKernelGGL(k_scr_gemm<NT>, dim3(p.slots, ctx->n_pad / kScrCols), dim3(256), scr_gemm_lds(p.nsub, NT), ctx->stream, (const __half*)S.a16, ctx->ldm,
+                       (uint32_t)ctx->n, (const __half*)p.res.r16, (const float*)S.anorm, (const float*)p.res.rn2p, p.res.rhs, (const float*)p.res.tab, p.sub, p.nsub,
+                       (const float*)S.meta, p.st, scr_headroom(S), p.nst_fixed, scr_skew(), p.gate, p.fl, p.c0h, p.out_abs, p.out_pitch);
+}
+// (its dynamic LDS beyond 64 KiB: the ceiling of the largest subset any form passes)
+template <int NT>
+static hipError_t scr_pass_attr()
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scr_gemm_lds(kS64Sub, NT));
+}
+
+// ---- the other stages ----------------------------------------------------------------------------------------------------------------
+// Gs = A_S^T A_S of every slot's subset from the fp32 dictionary: partials per row chunk, summed in a fixed order (the mirror of
+// launch_sgram64).  One signal (y given): the sum's launch is handed the dictionary too, and with exact_c0 — its first pass ran in reduced
+// precision — workgroups beyond the sum write the exact c0 = a_j . y of the subset's columns into c0.
+static void launch_sgram32(const ss_hip_ctx* ctx, const uint32_t* sub, float* part, float* gs, uint32_t nslots = 1, const float* y = nullptr, float* c0 = nullptr,
+                           bool exact_c0 = false)
+{
+    const float* At = static_cast<const float*>(ctx->At);
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n;
+    const uint32_t nsplit = (ldm % (kSgSplit * kSgStep) == 0) ? kSgSplit : 4u;        // (ldm is a multiple of 256)
+    constexpr uint32_t NT = kSbS / kSgT;
+    const bool one = y != nullptr;
+    hipLaunchKernelGGL(k_sgram_part, dim3(NT * (NT + 1) / 2, nsplit, nslots), dim3(256), 0, ctx->stream, At, ldm, n, sub, ldm / nsplit, part);
+    hipLaunchKernelGGL(k_sgram_sum, dim3((kSbS * kSbS + 255) / 256 + (exact_c0 ? kSbS : 0u), nslots), dim3(256), 0, ctx->stream, (const float*)part, nsplit, gs,
+                       one ? At : (const float*)nullptr, one ? ldm : 0u, y, one ? sub : (const uint32_t*)nullptr, one ? n : 0u, c0);
+}
+
+// r_k = y - A_S x_S(k) of every logged state into the block, the states' table, the headroom word reset (scan: the rescue's look at a
+// declined solve's log)
+static void launch_scr_residuals(const ss_hip_ctx* ctx, const ScreenState& S, const float* y, const SubBufs& B, float tol, const ResBlock& res, DevState* st,
+                                 uint32_t nslots, bool first16, uint32_t* fl, bool omp, bool scan = false)
+{
+    hipLaunchKernelGGL(k_scr_residuals, dim3(ctx->ldm / 64u, nslots), dim3(256), 0, ctx->stream, static_cast<const float*>(ctx->At), ctx->ldm, (uint32_t)ctx->n, y,
+                       (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol, (const float*)S.meta, res.r16, res.rn2p, res.tab, scr_headroom(S), st,
+                       first16 ? 1 : 0, fl, omp ? 1 : 0, scan ? 1 : 0);
+}
+
+// the exact tail: the columns the pass left undecided re-checked with the reference's predicates, the last step repaired (an empty list:
+// the launches return at once)
+template <typename T>
+static void launch_scr_exact_tail(const ss_hip_ctx* ctx, Workspace<T>& ws, const T* y, const ResLog<T>& log, uint32_t* fl, T tol)
+{
+    const T* At = static_cast<const T*>(ctx->At);
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n;
+    hipLaunchKernelGGL((k_scr_recheck<T>), dim3(kScrRecheckWgs), dim3(256), 0, ctx->stream, At, ldm, n, y, (const uint32_t*)log.hdr, (const T*)log.H,
+                       (const uint32_t*)log.pcol, (const T*)log.X, (const T*)log.D, fl, tol, ctx->tie_guard, ws.st);
+    hipLaunchKernelGGL((k_scr_repair<T>), dim3(1), dim3(256), 0, ctx->stream, At, ldm, n, y, (const uint32_t*)log.hdr, (const T*)log.H, (const uint32_t*)log.pcol,
+                       (const T*)log.X, (const T*)log.D, (const uint32_t*)fl, ws.x, ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap);
+}
+
+// the rescue's ranking: c~0 with the columns the scan chose on top, into S.rank
+static void launch_scr_rescue_rank(const ss_hip_ctx* ctx, const ScreenState& S, const float* c0h)
+{
+    const uint32_t np = ctx->n_pad;
+    hipLaunchKernelGGL(k_scr_rescue_rank, dim3(std::min<uint32_t>((np + 255u) / 256u, 1024u)), dim3(256), 0, ctx->stream, c0h, (const uint32_t*)S.fl, S.rescue_first,
+                       S.rescue_count, S.rescue_first2, S.rescue_count2, (uint32_t)ctx->n, np, S.rank);
+}
+
+// What a rescue scan listed, read back (one synchronisation, on the rare path), and which of the three lists the rescue takes
+// -> *count_out columns.  In this order: the columns that stand above everything ranked out at state 0 (planted columns the ranking
+// missed); if there is none, the columns the declined attempt's exact re-check found beating a state (from_recheck); if there is
+// neither, whatever else beats a state, where that is a handful.  (On a path that went astray early the re-check's failures and the
+// other violators are mostly the noise columns of its late states — hundreds; the first kind names what went wrong.)
+static hipError_t scr_rescue_readback(ScreenState& S, hipStream_t s, bool from_recheck, uint32_t* count_out)
+{
+    uint32_t cnt = 0, tail[3] = { 0u, 0u, 0u };                  // [cap + 12 .. + 14]: repair's count, the scan's second list, the re-check's failures
+    hipError_t e = hipMemcpyAsync(&cnt, S.fl, sizeof(cnt), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(tail, S.fl + kScrFlCap + 12u, sizeof(tail), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    const uint32_t cnt2 = tail[1], cntf = from_recheck ? tail[2] : 0u;
+    S.rescue_first2 = 1u; S.rescue_count2 = 0u;
+    if (cnt != 0u) { S.rescue_first = 1u; S.rescue_count = cnt; }
+    else if (cntf != 0u) { S.rescue_first = kScrFlFail; S.rescue_count = cntf; }
+    else { S.rescue_first = 1u + kScrFlCap / 2u; S.rescue_count = cnt2; }
+    *count_out = S.rescue_count + S.rescue_count2;
+    return hipSuccess;
+}
+
+// ---- the preparations ----------------------------------------------------------------------------------------------------------------
+// What the fp32 and the fp64 form share: the fp16 copy of A (half of A's bytes again), the column norms and maxima, meta, the residual
+// block of one signal ...
+static void scr_take_front(Takes& t, ScreenState& S, uint32_t np, uint32_t ldm, uint32_t rhs)
+{
+    t(&S.a16, (size_t)np * ldm * sizeof(__half))(&S.anorm, (size_t)np * sizeof(float))(&S.amaxc, (size_t)np * sizeof(float))(&S.meta, kScrMeta * sizeof(float));
+    S.res.take(t, rhs, ldm);
+}
+// ... and, behind the form's own memsets, the block cleared, the statistics, the scale (units: fp64 — the columns' unit exponent), the copy
+template <typename TA>
+static bool scr_fill_front(ss_hip_ctx* ctx, ScreenState& S, int units)
+{
+    hipStream_t s = ctx->stream;
+    (void)S.res.clear(ctx->ldm, 1, s);
+    hipLaunchKernelGGL((k_a16_stats<TA>), dim3(ctx->n_pad), dim3(256), 0, s, static_cast<const TA*>(ctx->At), ctx->ldm, S.anorm, S.amaxc, S.meta);
+    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S.meta, units);
+    launch_a16_convert<TA>(ctx, S);
+    return hipGetLastError() == hipSuccess;
+}
+
+// Shape / option test, and — the first time it says yes — the preparation.  A failed allocation switches the form off for this context
+// (the default engine goes on as before).
 bool screen_form_usable(ss_hip_ctx* ctx)
 {
     if (ctx->screen_single == 0 || ctx->is_f64 || ctx->kind != 0 || ctx->screen_failed_alloc) return false;
@@ -1794,41 +1951,20 @@ bool screen_form_usable(ss_hip_ctx* ctx)
     if (!sub_form_usable(ctx)) return false;
     if (ctx->screen != nullptr) return true;
     ScreenState* S = &part<ScreenState>(ctx->screen);
-    bool ok = true;
-    ok = ok && S->own.device(&S->a16, (size_t)np * ldm * sizeof(__half)) == hipSuccess;
-    ok = ok && S->own.device(&S->anorm, (size_t)np * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->amaxc, (size_t)np * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->meta, kScrMeta * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->r16, (size_t)kScrRhs * ldm * sizeof(__half)) == hipSuccess;
-    ok = ok && S->own.device(&S->rn2p, (size_t)(ldm / 64u) * kScrRhs * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->tab, (size_t)kScrRhs * kScrTab * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->gs_part, (size_t)kSgSplit * kSbS * kSbS * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->gs, (size_t)kSbS * kSbS * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->wmax, (size_t)kScrWmax * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->fl, (size_t)kScrFlWords * sizeof(uint32_t)) == hipSuccess;
     // (the hand-off block: tickets and the selection's shared histogram in front — k_la_reset clears those at the start of every attempt —,
     // then the selection workgroups' counts and entries)
     const size_t ho_words = (size_t)kHoEnt + (np <= kHoSelCols ? (size_t)np + 4u * kHoSelWgs : 0u);
-    ok = ok && S->own.device(&ctx->handoff, ho_words * sizeof(uint32_t)) == hipSuccess;
-    if (ok) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)scr_gemm_lds(kS64Sub));
-        if (e != hipSuccess) { (void)hipGetLastError(); ok = false; }
-    }
-    if (!ok) return screen_off(ctx);
+    Takes t{ S->own };
+    scr_take_front(t, *S, np, ldm, kScrRhs);
+    t(&S->gs_part, (size_t)kSgSplit * kSbS * kSbS * sizeof(float))(&S->gs, (size_t)kSbS * kSbS * sizeof(float))(&S->wmax, (size_t)kScrWmax * sizeof(float))
+     (&S->fl, (size_t)kScrFlWords * sizeof(uint32_t))(&ctx->handoff, ho_words * sizeof(uint32_t));
+    if (t.ok && scr_pass_attr<3>() != hipSuccess) { (void)hipGetLastError(); t.ok = false; }
+    if (!t.ok) return screen_off(ctx);
     hipStream_t s = ctx->stream;
-    const float* At = static_cast<const float*>(ctx->At);
     (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
     (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), s);
     (void)hipMemsetAsync(ctx->handoff, 0, ho_words * sizeof(uint32_t), s);
-    (void)hipMemsetAsync(S->r16, 0, (size_t)kScrRhs * ldm * sizeof(__half), s);
-    hipLaunchKernelGGL((k_a16_stats<float>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
-    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta, 0);
-    const size_t total8 = (size_t)np * ldm / 8;
-    hipLaunchKernelGGL((k_a16_convert<float>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
-                       (const float*)S->meta, S->a16);
-    if (hipGetLastError() != hipSuccess) return screen_off(ctx);
-    return true;
+    return scr_fill_front<float>(ctx, *S, 0) || screen_off(ctx);
 }
 
 // r = y in ws.rhs (block 0); c0 = A^T y in ws.c0 — or, first16, nothing yet: the first pass runs here, over the fp16 copy
@@ -1861,19 +1997,15 @@ static bool screen_first8_ready(ss_hip_ctx* ctx, ScreenState* S)
 {
     if (ctx->screen_first8 == 0 || ctx->ldm % 1024u != 0u || S->a8_failed) return false;
     if (S->a8 != nullptr) return true;
-    const uint32_t ldm = ctx->ldm, np = ctx->n_pad;
     size_t free_b = 0, total_b = 0;
-    const size_t bytes = (size_t)np * ldm;
+    const size_t bytes = (size_t)ctx->n_pad * ctx->ldm;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)2 << 30) > free_b || S->own.device(&S->a8, bytes) != hipSuccess) {
         (void)hipGetLastError();
         S->a8_failed = true;
         return false;
     }
-    hipStream_t s = ctx->stream;
-    const size_t total16 = bytes / 16u;
-    hipLaunchKernelGGL(k_a8_scale, dim3(1), dim3(1), 0, s, S->meta);
-    hipLaunchKernelGGL((k_a8_convert<TA>), dim3((unsigned)std::min<size_t>((total16 + 255) / 256, 65536)), dim3(256), 0, s, static_cast<const TA*>(ctx->At), total16,
-                       (const float*)S->meta, S->a8);
+    hipLaunchKernelGGL(k_a8_scale, dim3(1), dim3(1), 0, ctx->stream, S->meta);
+    launch_a8_convert<TA>(ctx, *S);
     if (hipGetLastError() != hipSuccess) { (void)S->own.drop(S->a8); S->a8_failed = true; return false; }
     return true;
 }
@@ -1920,15 +2052,13 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     // (omp: orthogonal matching pursuit on the same subset — k_res_solve<float, OMP> logs its states the same way, the certificate reads
     // "nothing outside the subset reaches the pick's |c|"; the exact re-check decides Homotopy's predicates and stays out)
     if (omp && !(ctx->screen_resident && res_solve_usable<float>())) return hipErrorInvalidConfiguration;
-    uint32_t* const fl = (ctx->screen_recheck && !omp) ? scr_of(ctx)->fl : nullptr;
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || ctx->sub_buf == nullptr) return hipErrorInvalidConfiguration;
+    uint32_t* const fl = (ctx->screen_recheck && !omp) ? S->fl : nullptr;
     const SubBufs B = sub_bufs(ctx, 1);
     hipStream_t s = ctx->stream;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
     const float* At = static_cast<const float*>(ctx->At);
-    const uint32_t nsplit = (ldm % (kSgSplit * kSgStep) == 0) ? kSgSplit : 4u;        // (ldm is a multiple of 256)
-    constexpr uint32_t NT = kSbS / kSgT;
     uint32_t nwmax = 0;
     if (first16 && !rescue) {
         if (first.a) (void)hipEventRecord(first.a, s);
@@ -1937,8 +2067,7 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     }
     if (rescue) {
         if (S->rank == nullptr || !first16) return hipErrorInvalidConfiguration;
-        hipLaunchKernelGGL(k_scr_rescue_rank, dim3(std::min<uint32_t>((np + 255u) / 256u, 1024u)), dim3(256), 0, s, (const float*)ws.c0, (const uint32_t*)S->fl,
-                           S->rescue_first, S->rescue_count, S->rescue_first2, S->rescue_count2, n, np, S->rank);
+        launch_scr_rescue_rank(ctx, *S, (const float*)ws.c0);
     }
     const bool ho_route = ho != nullptr && !omp && !rescue && first16 && nwmax != 0u && ctx->handoff != nullptr && ctx->hs_mapped != nullptr &&
                           ctx->screen_resident && res_solve_usable<float>();
@@ -1947,28 +2076,23 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     else
         (void)launch_sub_select(ctx, B, 1, rescue ? (const float*)S->rank : (const float*)ws.c0, first16 ? S->meta + 6 : nullptr,
                                 nwmax != 0u ? (const float*)S->wmax : nullptr, nwmax);
-    hipLaunchKernelGGL(k_sgram_part, dim3(NT * (NT + 1) / 2, nsplit), dim3(256), 0, s, At, ldm, n, (const uint32_t*)B.sub, ldm / nsplit, S->gs_part);
-    hipLaunchKernelGGL(k_sgram_sum, dim3((kSbS * kSbS + 255) / 256 + (first16 ? kSbS : 0u)), dim3(256), 0, s, (const float*)S->gs_part, nsplit, S->gs,
-                       At, ldm, (const float*)ws.rhs, (const uint32_t*)B.sub, n, ws.c0);
+    launch_sgram32(ctx, (const uint32_t*)B.sub, S->gs_part, S->gs, 1, (const float*)ws.rhs, ws.c0, first16);
     // the path on the subset: the resident kernel (resident.hip: Gram values in registers, four barriers per iteration) or, option
     // screen_resident = 0, k_sub_solve (subbatch.hip) — the same log either way (path: profiling events around it)
+    const ResLog<float> log{ B.hdr, nullptr, B.pcol, B.LX, B.LD };
     if (path.a) (void)hipEventRecord(path.a, s);
-    if (ctx->screen_resident && res_solve_usable<float>()) {
-        const ResLog<float> log{ B.hdr, nullptr, B.pcol, B.LX, B.LD };
+    if (ctx->screen_resident && res_solve_usable<float>())
         (void)launch_res_solve<float>(ctx, 1, (const float*)S->gs, kSbS, 0, (const float*)ws.c0, 0, (const uint32_t*)B.sub, tol, max_iter, ws.dims.kcap, log, ws.x, 0,
                                       ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
-    } else
+    else
         (void)launch_sub_solve(ctx, ws, B, 1, (const float*)S->gs, kSbS, first16 ? 2 : 1, ws.c0, tol, max_iter);
     if (path.b) (void)hipEventRecord(path.b, s);
-    hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs,
-                       (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
-                       (const float*)S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, first16 ? 1 : 0,
-                       fl, omp ? 1 : 0);
+    launch_scr_residuals(ctx, *S, (const float*)ws.rhs, B, tol, S->res, ws.st, 1, first16, fl, omp);
     if (screen.a) (void)hipEventRecord(screen.a, s);
-    hipLaunchKernelGGL(k_scr_gemm<3>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kSbS), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
-                       (const float*)S->anorm, (const float*)S->rn2p, kScrRhs, (const float*)S->tab, (const uint32_t*)B.sub, kSbS, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 0u, fl,
-                       first16 ? (const float*)ws.c0 : (const float*)nullptr);
+    ScrPass pass;
+    pass.res = S->res; pass.sub = B.sub; pass.nsub = kSbS; pass.st = ws.st;
+    pass.fl = fl; pass.c0h = first16 ? (const float*)ws.c0 : nullptr;
+    scr_pass<3>(ctx, *S, pass);
     if (screen.b) (void)hipEventRecord(screen.b, s);
     if (ho_route && (ho->mask & 1u) && fl != nullptr) {
         // ... and the verdict, the state and x to the caller behind them, in the same launch (the caller then queues no k_epilogue)
@@ -1979,20 +2103,12 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
         ho->tail_fused = true;
         return hipGetLastError();
     }
-    // the columns that pass left undecided, exactly (an empty list: the launch returns at once)
-    if (fl != nullptr)
-        hipLaunchKernelGGL((k_scr_recheck<float>), dim3(kScrRecheckWgs), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs, (const uint32_t*)B.hdr, (const float*)nullptr,
-                           (const uint32_t*)B.pcol, (const float*)B.LX, (const float*)B.LD, S->fl, tol, ctx->tie_guard, ws.st);
-    if (fl != nullptr)
-        hipLaunchKernelGGL((k_scr_repair<float>), dim3(1), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs, (const uint32_t*)B.hdr, (const float*)nullptr,
-                           (const uint32_t*)B.pcol, (const float*)B.LX, (const float*)B.LD, (const uint32_t*)S->fl, ws.x, ws.gam, ws.touched, ws.st, ws.trace,
-                           ws.trace_cap);
+    // the columns that pass left undecided, exactly
+    if (fl != nullptr) launch_scr_exact_tail<float>(ctx, ws, (const float*)ws.rhs, log, fl, tol);
     // (finish = false: the caller's epilogue launch turns "a column was not certified" into the status the host reads)
     if (finish) (void)launch_sub_finish(ctx, ws, 1);
     return hipGetLastError();
 }
-
-
 
 // The rescue of a declined solve (one fp32 signal, Homotopy; option screen_rescue).  A planted column whose |c0| drowns in the noise of the
 // other planted columns is not among the 448 best-ranked: the subset's path then goes wrong where that column should have entered — it runs
@@ -2007,36 +2123,15 @@ hipError_t launch_screen_rescue_scan(ss_hip_ctx* ctx, Workspace<float>& ws, floa
     *count_out = 0;
     if (S == nullptr || ctx->sub_buf == nullptr || S->fl == nullptr) return hipErrorInvalidConfiguration;
     const SubBufs B = sub_bufs(ctx, 1);
-    hipStream_t s = ctx->stream;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
-    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)np * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
-    const float* At = static_cast<const float*>(ctx->At);
-    hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u), dim3(256), 0, s, At, ldm, n, (const float*)ws.rhs,
-                       (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
-                       (const float*)S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, 1, S->fl, 0, 1);
-    hipLaunchKernelGGL(k_scr_gemm<3>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kSbS), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
-                       (const float*)S->anorm, (const float*)S->rn2p, kScrRhs, (const float*)S->tab, (const uint32_t*)B.sub, kSbS, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 3u, S->fl, (const float*)nullptr);
-    hipError_t e = hipGetLastError();
+    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)ctx->n_pad * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
+    launch_scr_residuals(ctx, *S, (const float*)ws.rhs, B, tol, S->res, ws.st, 1, true, S->fl, false, true);
+    ScrPass pass;
+    pass.res = S->res; pass.sub = B.sub; pass.nsub = kSbS; pass.st = ws.st;
+    pass.gate = 3u; pass.fl = S->fl;
+    scr_pass<3>(ctx, *S, pass);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    uint32_t cnt = 0, tail[3] = { 0u, 0u, 0u };                  // [cap + 12 .. + 14]: repair's count, the scan's second list, the re-check's failures
-    e = hipMemcpyAsync(&cnt, S->fl, sizeof(cnt), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(tail, S->fl + kScrFlCap + 12u, sizeof(tail), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    const uint32_t cnt2 = tail[1], cntf = from_recheck ? tail[2] : 0u;
-    // the columns that stand above everything ranked out at state 0 (planted columns the ranking missed); if there is none, the columns the declined
-    // attempt's exact re-check found beating a state; if there is neither: whatever else beats a state, where that is a handful
-    // (in that order: on a path that went astray early the re-check's failures and the other violators are mostly the noise columns of its late
-    // states — hundreds; the first kind names what went wrong)
-    S->rescue_first2 = 1u; S->rescue_count2 = 0u;
-    if (cnt != 0u) { S->rescue_first = 1u; S->rescue_count = cnt; }
-    else if (cntf != 0u) { S->rescue_first = kScrFlFail; S->rescue_count = cntf; }
-    else { S->rescue_first = 1u + kScrFlCap / 2u; S->rescue_count = cnt2; }
-    *count_out = S->rescue_count + S->rescue_count2;
-    return hipSuccess;
+    return scr_rescue_readback(*S, ctx->stream, from_recheck, count_out);
 }
 uint32_t screen_rescue_cap() { return kScrRescueCap; }
 
@@ -2059,15 +2154,11 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || ctx->sub_buf == nullptr || nslots == 0 || nslots > kScrBatch) return hipErrorInvalidConfiguration;
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
-    if (S->b_r16 == nullptr) {
-        bool ok = true;
-        ok = ok && S->batch.device(&S->b_r16, (size_t)kScrBatch * kScrRhs * ldm * sizeof(__half)) == hipSuccess;
-        ok = ok && S->batch.device(&S->b_rn2p, (size_t)kScrBatch * (ldm / 64u) * kScrRhs * sizeof(float)) == hipSuccess;
-        ok = ok && S->batch.device(&S->b_tab, (size_t)kScrBatch * kScrRhs * kScrTab * sizeof(float)) == hipSuccess;
-        ok = ok && S->batch.device(&S->b_gs_part, (size_t)kScrBatch * kSgSplit * kSbS * kSbS * sizeof(float)) == hipSuccess;
-        ok = ok && S->batch.device(&S->b_gs, (size_t)kScrBatch * kSbS * kSbS * sizeof(float)) == hipSuccess;
-        if (ok && hipMemsetAsync(S->b_r16, 0, (size_t)kScrBatch * kScrRhs * ldm * sizeof(__half), ctx->stream) != hipSuccess) ok = false;
-        if (!ok) {
+    if (S->b_res.r16 == nullptr) {
+        Takes t{ S->batch };
+        S->b_res.take(t, kScrRhs, ldm, kScrBatch);
+        t(&S->b_gs_part, (size_t)kScrBatch * kSgSplit * kSbS * kSbS * sizeof(float))(&S->b_gs, (size_t)kScrBatch * kSbS * kSbS * sizeof(float));
+        if (!t.ok || S->b_res.clear(ldm, kScrBatch, ctx->stream) != hipSuccess) {
             static_cast<ScrBatchBufs&>(*S) = ScrBatchBufs();
             (void)hipGetLastError();
             return hipErrorOutOfMemory;
@@ -2075,22 +2166,15 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
     }
     const SubBufs B = sub_bufs(ctx, nslots);
     hipStream_t s = ctx->stream;
-    const float* At = static_cast<const float*>(ctx->At);
     (void)launch_sub_select(ctx, B, nslots, c0_all);
-    const uint32_t nsplit = (ldm % (kSgSplit * kSgStep) == 0) ? kSgSplit : 4u;
-    constexpr uint32_t NT = kSbS / kSgT;
-    hipLaunchKernelGGL(k_sgram_part, dim3(NT * (NT + 1) / 2, nsplit, nslots), dim3(256), 0, s, At, ldm, n, (const uint32_t*)B.sub, ldm / nsplit, S->b_gs_part);
-    hipLaunchKernelGGL(k_sgram_sum, dim3((kSbS * kSbS + 255) / 256, nslots), dim3(256), 0, s, (const float*)S->b_gs_part, nsplit, S->b_gs, (const float*)nullptr, 0u, (const float*)nullptr, (const uint32_t*)nullptr, 0u, (float*)nullptr);
+    launch_sgram32(ctx, (const uint32_t*)B.sub, S->b_gs_part, S->b_gs, nslots);
     if (ctx->screen_resident && res_solve_usable<float>()) {
         const ResLog<float> log{ B.hdr, nullptr, B.pcol, B.LX, B.LD };
         (void)launch_res_solve<float>(ctx, nslots, (const float*)S->b_gs, kSbS, (size_t)kSbS * kSbS, c0_all, np, (const uint32_t*)B.sub, tol, max_iter, ws.dims.kcap, log,
                                       ws.x, np, ws.gam, ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
     } else
         (void)launch_sub_solve(ctx, ws, B, nslots, (const float*)S->b_gs, kSbS, 1, c0_all, tol, max_iter, kSbS * kSbS);
-    hipLaunchKernelGGL(k_scr_residuals, dim3(ldm / 64u, nslots), dim3(256), 0, s, At, ldm, n, (const float*)ws.y,
-                       (const uint32_t*)B.hdr, (const uint32_t*)B.pcol, (const float*)B.LX, tol,
-                       (const float*)S->meta, S->b_r16, S->b_rn2p, S->b_tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, 0, (uint32_t*)nullptr,
-                       omp ? 1 : 0);
+    launch_scr_residuals(ctx, *S, (const float*)ws.y, B, tol, S->b_res, ws.st, nslots, false, nullptr, omp);
     static const bool b_attr = [] {
         const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm_b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)scr_gemm_b_lds()) == hipSuccess;
         if (!ok) (void)hipGetLastError();
@@ -2098,13 +2182,14 @@ hipError_t launch_screen_batch(ss_hip_ctx* ctx, Workspace<float>& ws, uint32_t n
     }();
     if (b_attr) {
         hipLaunchKernelGGL(k_scr_gemm_b, dim3((nslots + kScrSL - 1) / kScrSL, np / kScrCols), dim3(256), scr_gemm_b_lds(), s, (const __half*)S->a16, ldm, n,
-                           (const __half*)S->b_r16, (const float*)S->anorm, (const float*)S->b_rn2p, (const float*)S->b_tab, (const uint32_t*)B.sub,
-                           (const float*)S->meta, ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, nslots, scr_skew());
+                           (const __half*)S->b_res.r16, (const float*)S->anorm, (const float*)S->b_res.rn2p, (const float*)S->b_res.tab, (const uint32_t*)B.sub,
+                           (const float*)S->meta, ws.st, scr_headroom(*S), nslots, scr_skew());
     }
     // (slots whose path logged more than 64 states — and every slot, should the wide kernel's LDS request be refused)
-    hipLaunchKernelGGL(k_scr_gemm<3>, dim3(nslots, np / kScrCols), dim3(256), scr_gemm_lds(kSbS), s, (const __half*)S->a16, ldm, n, (const __half*)S->b_r16,
-                       (const float*)S->anorm, (const float*)S->b_rn2p, kScrRhs, (const float*)S->b_tab, (const uint32_t*)B.sub, kSbS, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, b_attr ? 0xffffffffu : 0u, scr_skew(), 0u);
+    ScrPass pass;
+    pass.res = S->b_res; pass.sub = B.sub; pass.nsub = kSbS; pass.st = ws.st;
+    pass.slots = nslots; pass.nst_fixed = b_attr ? 0xffffffffu : 0u;
+    scr_pass<3>(ctx, *S, pass);
     (void)launch_sub_finish(ctx, ws, nslots);
     return hipGetLastError();
 }
@@ -2131,49 +2216,29 @@ bool screen64_usable(ss_hip_ctx* ctx)
     if (ctx->screen_single < 2 && (size_t)ctx->m * ctx->n < ((size_t)64 << 20)) return false;
     if (ctx->screen != nullptr) return true;
     ScreenState* S = &part<ScreenState>(ctx->screen);
-    bool ok = true;
-    ok = ok && S->own.device(&S->a16, (size_t)np * ldm * sizeof(__half)) == hipSuccess;
-    ok = ok && S->own.device(&S->anorm, (size_t)np * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->amaxc, (size_t)np * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->meta, kScrMeta * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->r16, (size_t)kS64Rhs * ldm * sizeof(__half)) == hipSuccess;
-    ok = ok && S->own.device(&S->rn2p, (size_t)(ldm / 64u) * kS64Rhs * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->tab, (size_t)kS64Rhs * kScrTab * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->cabs, (size_t)np * sizeof(float)) == hipSuccess;
-    ok = ok && S->own.device(&S->sublist, ((size_t)kS64Sub + 2) * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && S->own.device(&S->xsub, (size_t)kS64Sub * sizeof(double)) == hipSuccess;
-    ok = ok && S->own.device(&S->xd, (size_t)kS64LogK * (kS64Rhs + 8) * sizeof(double)) == hipSuccess;
-    ok = ok && S->own.device(&S->ctl, 8 * sizeof(uint32_t)) == hipSuccess;
-    {
-        typedef ResCfg<double> RC;
-        ok = ok && S->own.device(&S->sub256, ((size_t)RC::S + 2) * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && S->own.device(&S->gs64, (size_t)RC::S * RC::S * sizeof(double)) == hipSuccess;
-        ok = ok && S->own.device(&S->gs64_part, (size_t)kSg64MaxSplit * RC::S * RC::S * sizeof(double)) == hipSuccess;
-        ok = ok && S->own.device(&S->rl_hdr, (size_t)RC::LOGCAP * 8 * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && S->own.device(&S->rl_H, (size_t)RC::LOGCAP * 2 * sizeof(double)) == hipSuccess;
-        ok = ok && S->own.device(&S->rl_pcol, (size_t)RC::PCAP * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && S->own.device(&S->rl_X, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
-        ok = ok && S->own.device(&S->rl_D, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
-        ok = ok && S->own.device(&S->fl, (size_t)kScrFlWords * sizeof(uint32_t)) == hipSuccess;
-        if (ok) (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), ctx->stream);
+    typedef ResCfg<double> RC;
+    Takes t{ S->own };
+    scr_take_front(t, *S, np, ldm, kS64Rhs);
+    t(&S->cabs, (size_t)np * sizeof(float))(&S->sublist, ((size_t)kS64Sub + 2) * sizeof(uint32_t))(&S->xsub, (size_t)kS64Sub * sizeof(double))
+     (&S->xd, (size_t)kS64LogK * (kS64Rhs + 8) * sizeof(double))(&S->ctl, 8 * sizeof(uint32_t))
+     (&S->sub256, ((size_t)RC::S + 2) * sizeof(uint32_t))(&S->gs64, (size_t)RC::S * RC::S * sizeof(double))
+     (&S->gs64_part, (size_t)kSg64MaxSplit * RC::S * RC::S * sizeof(double))(&S->rl_hdr, (size_t)RC::LOGCAP * 8 * sizeof(uint32_t))
+     (&S->rl_H, (size_t)RC::LOGCAP * 2 * sizeof(double))(&S->rl_pcol, (size_t)RC::PCAP * sizeof(uint32_t))
+     (&S->rl_X, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double))(&S->rl_D, (size_t)RC::LOGCAP * RC::PCAP * sizeof(double))
+     (&S->fl, (size_t)kScrFlWords * sizeof(uint32_t));
+    if (t.ok) (void)hipMemsetAsync(S->fl, 0, (size_t)kScrFlWords * sizeof(uint32_t), ctx->stream);
+    if (t.ok) {
+        const hipError_t e = scr_pass_attr<3>(), e5 = scr_pass_attr<5>(), e4 = scr_pass_attr<4>();
+        if (e != hipSuccess || e5 != hipSuccess || e4 != hipSuccess) { (void)hipGetLastError(); t.ok = false; }
     }
-    if (ok) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)scr_gemm_lds(kS64Sub, 3));
-        const hipError_t e5 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<5>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)scr_gemm_lds(kS64Sub, 5));
-        const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_scr_gemm<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)scr_gemm_lds(kS64Sub, 4));
-        if (e != hipSuccess || e5 != hipSuccess || e4 != hipSuccess) { (void)hipGetLastError(); ok = false; }
-    }
-    if (ok) {
+    if (t.ok) {
         char err[256];
         S->sub = ss_hip_homotopy_create_f64(static_cast<const double*>(ctx->At), ctx->m, kS64Sub, 1, (ptrdiff_t)ldm, ctx->device, err, sizeof(err));
-        if (S->sub == nullptr) ok = false;
+        if (S->sub == nullptr) t.ok = false;
         else {
             S->sub->screen_single = 0;
             (void)hipSetDevice(ctx->device);
-            if (S->own.device(&S->sub->slog, s64_log_bytes()) != hipSuccess) ok = false;
+            t(&S->sub->slog, s64_log_bytes());
             S->sub->slog_cap = kS64LogCap;
             S->sub->slog_kmax = kS64LogK;
             // its passes: 8 column tiles only — the rows split 16 (32) ways fill the chip
@@ -2183,18 +2248,24 @@ bool screen64_usable(ss_hip_ctx* ctx)
             else S->sub->pass_ksplit = 0;
         }
     }
-    if (!ok) return screen_off(ctx);
-    hipStream_t s = ctx->stream;
-    const double* At = static_cast<const double*>(ctx->At);
-    (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), s);
-    (void)hipMemsetAsync(S->r16, 0, (size_t)kS64Rhs * ldm * sizeof(__half), s);
-    hipLaunchKernelGGL((k_a16_stats<double>), dim3(np), dim3(256), 0, s, At, ldm, S->anorm, S->amaxc, S->meta);
-    hipLaunchKernelGGL(k_a16_scale, dim3(1), dim3(1), 0, s, S->meta, 1);
-    const size_t total8 = (size_t)np * ldm / 8;
-    hipLaunchKernelGGL((k_a16_convert<double>), dim3((unsigned)std::min<size_t>((total8 + 255) / 256, 65536)), dim3(256), 0, s, At, total8,
-                       (const float*)S->meta, S->a16);
-    if (hipGetLastError() != hipSuccess) return screen_off(ctx);
-    return true;
+    if (!t.ok) return screen_off(ctx);
+    (void)hipMemsetAsync(S->meta, 0, kScrMeta * sizeof(float), ctx->stream);
+    return scr_fill_front<double>(ctx, *S, 1) || screen_off(ctx);
+}
+
+// The fp64 tiers' launches of the screening pass (defined behind screen64_usable: the instantiations of k_scr_gemm keep the order the
+// device code was always emitted in).  The sub-dictionary tier's choice: `states` of them in one launch — three tiles up to 96, four up to 128, five up to 160
+static void scr_pass_tiles(uint32_t states, const ss_hip_ctx* ctx, const ScreenState& S, const ScrPass& p)
+{
+    if (states <= kScrRhs) scr_pass<3>(ctx, S, p);
+    else if (states <= 128u) scr_pass<4>(ctx, S, p);
+    else scr_pass<5>(ctx, S, p);
+}
+// the resident tier's pair: four tiles where the log holds up to 128 states, five beyond — both are queued, each looks at the log's length
+static void scr_pass_gated(const ss_hip_ctx* ctx, const ScreenState& S, ScrPass p)
+{
+    p.gate = 1u; scr_pass<4>(ctx, S, p);
+    p.gate = 2u; scr_pass<5>(ctx, S, p);
 }
 
 ss_hip_ctx* screen64_sub(ss_hip_ctx* ctx) { return scr_of(ctx) ? scr_of(ctx)->sub : nullptr; }
@@ -2231,35 +2302,24 @@ hipError_t screen64_certify(ss_hip_ctx* ctx, Workspace<double>& ws, const double
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || S->sub == nullptr || T == 0u || T > kS64Rhs) return hipErrorInvalidConfiguration;
     hipStream_t s = ctx->stream;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
+    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n;
     (void)hipMemsetAsync(S->ctl, 0, 8 * sizeof(uint32_t), s);
     const unsigned char* slog = static_cast<const unsigned char*>(S->sub->slog);
     hipLaunchKernelGGL(k_s64_dense, dim3(T), dim3(256), 0, s, slog, T, S->xd, S->ctl, omp ? 1 : 0);
     hipLaunchKernelGGL(k_s64_residuals, dim3(ldm / 64u), dim3(256), 0, s, static_cast<const double*>(S->sub->At), ldm, y, slog, T,
-                       (const double*)S->xd, tol, (const float*)S->meta, S->r16, S->rn2p, S->tab, S->ctl, reinterpret_cast<uint32_t*>(S->meta) + 3,
+                       (const double*)S->xd, tol, (const float*)S->meta, S->res.r16, S->res.rn2p, S->res.tab, S->ctl, scr_headroom(*S),
                        first16 ? 1 : 0);
     if (screen.a) (void)hipEventRecord(screen.a, s);
-    // (up to 160 states in ONE pass over the fp16 copy — five tiles of 32 per workgroup —, the rest in passes of 96)
-    for (uint32_t k0 = 0; k0 < T;) {
-        const bool wide = T - k0 > kScrRhs;
-        const bool four = wide && T - k0 <= 128u;                 // (up to 128 states: four tiles, two register sets of loads in flight)
-        const uint32_t cnt = std::min<uint32_t>(wide ? 160u : kScrRhs, T - k0);
-        if (four)
-            hipLaunchKernelGGL(k_scr_gemm<4>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kS64Sub, 4), s, (const __half*)S->a16, ldm, n,
-                               (const __half*)(S->r16 + (size_t)k0 * ldm), (const float*)S->anorm, (const float*)(S->rn2p + k0), kS64Rhs,
-                               (const float*)(S->tab + (size_t)k0 * kScrTab), (const uint32_t*)S->sublist, kS64Sub, (const float*)S->meta,
-                               ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, cnt, scr_skew(), 0u);
-        else if (wide)
-            hipLaunchKernelGGL(k_scr_gemm<5>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kS64Sub, 5), s, (const __half*)S->a16, ldm, n,
-                               (const __half*)(S->r16 + (size_t)k0 * ldm), (const float*)S->anorm, (const float*)(S->rn2p + k0), kS64Rhs,
-                               (const float*)(S->tab + (size_t)k0 * kScrTab), (const uint32_t*)S->sublist, kS64Sub, (const float*)S->meta,
-                               ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, cnt, scr_skew(), 0u);
-        else
-            hipLaunchKernelGGL(k_scr_gemm<3>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds(kS64Sub, 3), s, (const __half*)S->a16, ldm, n,
-                               (const __half*)(S->r16 + (size_t)k0 * ldm), (const float*)S->anorm, (const float*)(S->rn2p + k0), kS64Rhs,
-                               (const float*)(S->tab + (size_t)k0 * kScrTab), (const uint32_t*)S->sublist, kS64Sub, (const float*)S->meta,
-                               ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, cnt, scr_skew(), 0u);
-        k0 += cnt;
+    // (up to 160 states in ONE pass over the fp16 copy — five tiles of 32 per workgroup, four up to 128: two register sets of loads in
+    // flight —, the rest in passes of 96)
+    ScrPass pass;
+    pass.sub = S->sublist; pass.nsub = kS64Sub; pass.st = ws.st;
+    for (uint32_t k0 = 0, cnt = 0; k0 < T; k0 += cnt) {
+        const uint32_t left = T - k0;
+        cnt = std::min<uint32_t>(left > kScrRhs ? 160u : kScrRhs, left);
+        pass.res = S->res.from(k0, ldm);
+        pass.nst_fixed = cnt;
+        scr_pass_tiles(left, ctx, *S, pass);
     }
     if (screen.b) (void)hipEventRecord(screen.b, s);
     hipLaunchKernelGGL(k_s64_finish, dim3((kS64Sub + 255) / 256), dim3(256), 0, s, (const uint32_t*)S->sublist, (const double*)S->xsub, n, ws.x,
@@ -2280,6 +2340,9 @@ bool screen64_resident_usable(ss_hip_ctx* ctx)
     return S != nullptr && S->sub256 != nullptr && ctx->n >= 4u * (uint32_t)ResCfg<double>::S && res_solve_usable<double>();
 }
 
+// the resident solve's log of one signal
+static ResLog<double> res64_log(const ScreenState& S) { return { S.rl_hdr, S.rl_H, S.rl_pcol, S.rl_X, S.rl_D }; }
+
 // The rescue in the fp64 resident tier (see launch_screen_rescue_scan): the declined solve's log scanned by the five-tile certificate pass
 // (up to 160 states in one launch), the same three lists, the same order of preference.
 hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, bool from_recheck, uint32_t* count_out)
@@ -2288,31 +2351,16 @@ hipError_t launch_screen64_rescue_scan(ss_hip_ctx* ctx, Workspace<double>& ws, d
     ScreenState* S = scr_of(ctx);
     *count_out = 0;
     if (S == nullptr || S->sub256 == nullptr || S->fl == nullptr) return hipErrorInvalidConfiguration;
-    hipStream_t s = ctx->stream;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
-    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)np * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
-    const ResLog<double> log{ S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
-    (void)launch_res_residuals64(ctx, (const double*)ws.rhs, log, tol, S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, true, false, 1,
+    if (S->rank == nullptr && S->own.device(&S->rank, (size_t)ctx->n_pad * sizeof(float)) != hipSuccess) return hipErrorOutOfMemory;
+    (void)launch_res_residuals64(ctx, (const double*)ws.rhs, res64_log(*S), tol, S->meta, S->res.r16, S->res.rn2p, S->res.tab, scr_headroom(*S), ws.st, true, false, 1,
                                  nullptr, S->fl, true);
-    hipLaunchKernelGGL(k_scr_gemm<5>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 5), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
-                       (const float*)S->anorm, (const float*)S->rn2p, kS64Rhs, (const float*)S->tab, (const uint32_t*)S->sub256, (uint32_t)RC::S, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 3u, S->fl, (const float*)nullptr);
-    hipError_t e = hipGetLastError();
+    ScrPass pass;
+    pass.res = S->res; pass.sub = S->sub256; pass.nsub = (uint32_t)RC::S; pass.st = ws.st;
+    pass.gate = 3u; pass.fl = S->fl;
+    scr_pass<5>(ctx, *S, pass);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    uint32_t cnt = 0, tail[3] = { 0u, 0u, 0u };
-    e = hipMemcpyAsync(&cnt, S->fl, sizeof(cnt), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(tail, S->fl + kScrFlCap + 12u, sizeof(tail), hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) return e;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    const uint32_t cnt2 = tail[1], cntf = from_recheck ? tail[2] : 0u;
-    S->rescue_first2 = 1u; S->rescue_count2 = 0u;
-    if (cnt != 0u) { S->rescue_first = 1u; S->rescue_count = cnt; }
-    else if (cntf != 0u) { S->rescue_first = kScrFlFail; S->rescue_count = cntf; }
-    else { S->rescue_first = 1u + kScrFlCap / 2u; S->rescue_count = cnt2; }
-    *count_out = S->rescue_count;
-    return hipSuccess;
+    return scr_rescue_readback(*S, ctx->stream, from_recheck, count_out);
 }
 
 hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, double tol, uint32_t max_iter, bool first16, bool omp, EventPair first,
@@ -2322,13 +2370,12 @@ hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, doub
     ScreenState* S = scr_of(ctx);
     if (S == nullptr || S->sub256 == nullptr) return hipErrorInvalidConfiguration;
     hipStream_t s = ctx->stream;
-    const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
+    const uint32_t n = (uint32_t)ctx->n, np = ctx->n_pad;
     const double* y = ws.rhs;                                     // (r = y: the caller's reset put it there)
     if (rescue) {
         // (the second attempt on a signal the tier declined: no first pass — S->cabs still holds |c~0| —, the columns the scan named on top of the ranking)
         if (S->rank == nullptr || !first16) return hipErrorInvalidConfiguration;
-        hipLaunchKernelGGL(k_scr_rescue_rank, dim3(std::min<uint32_t>((np + 255u) / 256u, 1024u)), dim3(256), 0, s, (const float*)S->cabs, (const uint32_t*)S->fl,
-                           S->rescue_first, S->rescue_count, S->rescue_first2, S->rescue_count2, n, np, S->rank);
+        launch_scr_rescue_rank(ctx, *S, (const float*)S->cabs);
     } else if (first16) {
         if (first.a) (void)hipEventRecord(first.a, s);
         const hipError_t ef = launch_scr_first<double>(ctx, S, y, S->cabs);
@@ -2340,31 +2387,22 @@ hipError_t launch_screen64_resident(ss_hip_ctx* ctx, Workspace<double>& ws, doub
     (void)launch_select_top(ctx, rescue ? (const float*)S->rank : (const float*)S->cabs, n, np, (uint32_t)RC::S, S->sub256, S->sub256 + RC::S,
                             reinterpret_cast<float*>(S->sub256 + RC::S + 1), first16 ? S->meta + 6 : nullptr);
     { const hipError_t eg = launch_sgram64(ctx, S->sub256, y, S->gs64_part, S->gs64, ws.c0); if (eg != hipSuccess) return eg; }
-    const ResLog<double> log{ S->rl_hdr, S->rl_H, S->rl_pcol, S->rl_X, S->rl_D };
+    const ResLog<double> log = res64_log(*S);
     if (path.a) (void)hipEventRecord(path.a, s);
     { const hipError_t es = launch_res_solve<double>(ctx, 1, S->gs64, (uint32_t)RC::S, 0, ws.c0, 0, S->sub256, tol, max_iter, ws.dims.kcap, log, ws.x, 0, ws.gam,
                                                      ws.touched, ws.st, ws.trace, ws.trace_cap, omp);
       if (es != hipSuccess) return es; }
     if (path.b) (void)hipEventRecord(path.b, s);
     uint32_t* fl = (ctx->screen_recheck && !omp) ? S->fl : nullptr;      // (the exact re-check decides Homotopy's predicates: not OMP's)
-    (void)launch_res_residuals64(ctx, y, log, tol, S->meta, S->r16, S->rn2p, S->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, first16, omp, 1, nullptr, fl);
+    (void)launch_res_residuals64(ctx, y, log, tol, S->meta, S->res.r16, S->res.rn2p, S->res.tab, scr_headroom(*S), ws.st, first16, omp, 1, nullptr, fl);
     if (screen.a) (void)hipEventRecord(screen.a, s);
-    hipLaunchKernelGGL(k_scr_gemm<4>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 4), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
-                       (const float*)S->anorm, (const float*)S->rn2p, kS64Rhs, (const float*)S->tab, (const uint32_t*)S->sub256, (uint32_t)RC::S, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 1u, fl, first16 ? (const float*)S->cabs : (const float*)nullptr);
-    hipLaunchKernelGGL(k_scr_gemm<5>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 5), s, (const __half*)S->a16, ldm, n, (const __half*)S->r16,
-                       (const float*)S->anorm, (const float*)S->rn2p, kS64Rhs, (const float*)S->tab, (const uint32_t*)S->sub256, (uint32_t)RC::S, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 2u, fl, first16 ? (const float*)S->cabs : (const float*)nullptr);
+    ScrPass pass;
+    pass.res = S->res; pass.sub = S->sub256; pass.nsub = (uint32_t)RC::S; pass.st = ws.st;
+    pass.fl = fl; pass.c0h = first16 ? (const float*)S->cabs : nullptr;
+    scr_pass_gated(ctx, *S, pass);
     if (screen.b) (void)hipEventRecord(screen.b, s);
-    if (fl != nullptr) {
-        // the columns those passes left undecided, exactly, in fp64 (an empty list: the launches return at once)
-        const double* At = static_cast<const double*>(ctx->At);
-        hipLaunchKernelGGL((k_scr_recheck<double>), dim3(kScrRecheckWgs), dim3(256), 0, s, At, ldm, n, y, (const uint32_t*)S->rl_hdr, (const double*)S->rl_H,
-                           (const uint32_t*)S->rl_pcol, (const double*)S->rl_X, (const double*)S->rl_D, fl, tol, ctx->tie_guard, ws.st);
-        hipLaunchKernelGGL((k_scr_repair<double>), dim3(1), dim3(256), 0, s, At, ldm, n, y, (const uint32_t*)S->rl_hdr, (const double*)S->rl_H,
-                           (const uint32_t*)S->rl_pcol, (const double*)S->rl_X, (const double*)S->rl_D, (const uint32_t*)fl, ws.x, ws.gam, ws.touched, ws.st,
-                           ws.trace, ws.trace_cap);
-    }
+    // the columns those passes left undecided, exactly, in fp64
+    if (fl != nullptr) launch_scr_exact_tail<double>(ctx, ws, y, log, fl, tol);
     return hipGetLastError();
 }
 
@@ -2437,38 +2475,29 @@ hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_
         std::unique_ptr<Screen64Batch> fresh(new (std::nothrow) Screen64Batch());
         if (!fresh) return hipErrorOutOfMemory;
         Bq = fresh.get();
-        bool ok = true;
-        ok = ok && Bq->own.device(&Bq->y16, (size_t)128 * ldm * sizeof(__half)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->ytab, (size_t)128 * kScrTab * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->ymeta, (size_t)kS64Batch * 4 * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->cabs, (size_t)kS64Batch * np * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->sub, ((size_t)kS64Batch * RC::S + 2) * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->gs, (size_t)kS64Batch * RC::S * RC::S * sizeof(double)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->gs_part, (size_t)kS64Batch * kSg64MaxSplit * RC::S * RC::S * sizeof(double)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->hdr, (size_t)kS64Batch * RC::LOGCAP * 8 * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->H, (size_t)kS64Batch * RC::LOGCAP * 2 * sizeof(double)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->pcol, (size_t)kS64Batch * RC::PCAP * sizeof(uint32_t)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->X, (size_t)kS64Batch * RC::LOGCAP * RC::PCAP * sizeof(double)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->r16, (size_t)kS64Batch * kS64Rhs * ldm * sizeof(__half)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->rn2p, (size_t)kS64Batch * (ldm / 64u) * kS64Rhs * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->tab, (size_t)kS64Batch * kS64Rhs * kScrTab * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->zero, (size_t)(ldm / 64u) * 128 * sizeof(float)) == hipSuccess;
-        ok = ok && Bq->own.device(&Bq->c0, (size_t)kS64Batch * np * sizeof(double)) == hipSuccess;
-        if (ok && (hipMemsetAsync(Bq->r16, 0, (size_t)kS64Batch * kS64Rhs * ldm * sizeof(__half), ctx->stream) != hipSuccess ||
-                   hipMemsetAsync(Bq->zero, 0, (size_t)(ldm / 64u) * 128 * sizeof(float), ctx->stream) != hipSuccess)) ok = false;
-        if (!ok) {
+        Takes t{ Bq->own };
+        t(&Bq->y16, (size_t)128 * ldm * sizeof(__half))(&Bq->ytab, (size_t)128 * kScrTab * sizeof(float))(&Bq->ymeta, (size_t)kS64Batch * 4 * sizeof(float))
+         (&Bq->cabs, (size_t)kS64Batch * np * sizeof(float))(&Bq->sub, ((size_t)kS64Batch * RC::S + 2) * sizeof(uint32_t))
+         (&Bq->gs, (size_t)kS64Batch * RC::S * RC::S * sizeof(double))(&Bq->gs_part, (size_t)kS64Batch * kSg64MaxSplit * RC::S * RC::S * sizeof(double))
+         (&Bq->hdr, (size_t)kS64Batch * RC::LOGCAP * 8 * sizeof(uint32_t))(&Bq->H, (size_t)kS64Batch * RC::LOGCAP * 2 * sizeof(double))
+         (&Bq->pcol, (size_t)kS64Batch * RC::PCAP * sizeof(uint32_t))(&Bq->X, (size_t)kS64Batch * RC::LOGCAP * RC::PCAP * sizeof(double));
+        Bq->res.take(t, kS64Rhs, ldm, kS64Batch);
+        t(&Bq->zero, (size_t)(ldm / 64u) * 128 * sizeof(float))(&Bq->c0, (size_t)kS64Batch * np * sizeof(double));
+        if (!t.ok || Bq->res.clear(ldm, kS64Batch, ctx->stream) != hipSuccess ||
+            hipMemsetAsync(Bq->zero, 0, (size_t)(ldm / 64u) * 128 * sizeof(float), ctx->stream) != hipSuccess) {
             (void)hipGetLastError();
             return hipErrorOutOfMemory;      // (`fresh` gives back what it obtained)
         }
         S->b64 = std::move(fresh);
     }
-    hipStream_t s = ctx->stream;
     const double* Y = ws.y;
     // the signals in fp16, ONE pass over the fp16 copy for the whole chunk: |c~0| of every (signal, column)
-    hipLaunchKernelGGL(k_y16_prep, dim3(128), dim3(256), 0, s, Y, ldm, nslots, (const float*)S->meta, Bq->y16, Bq->ytab, Bq->ymeta);
-    hipLaunchKernelGGL(k_scr_gemm<4>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 4), s, (const __half*)S->a16, ldm, n, (const __half*)Bq->y16,
-                       (const float*)S->anorm, (const float*)Bq->zero, 128u, (const float*)Bq->ytab, (const uint32_t*)Bq->sub, 0u, (const float*)S->meta,
-                       ws.st, reinterpret_cast<uint32_t*>(S->meta) + 3, nslots, scr_skew(), 0u, (uint32_t*)nullptr, (const float*)nullptr, Bq->cabs, np);
+    hipLaunchKernelGGL(k_y16_prep, dim3(128), dim3(256), 0, ctx->stream, Y, ldm, nslots, (const float*)S->meta, Bq->y16, Bq->ytab, Bq->ymeta);
+    ScrPass rank;
+    rank.res = ResBlock{ Bq->y16, Bq->zero, Bq->ytab, 128u };     // (the signals as right-hand sides; the writing mode reads no residual norms)
+    rank.sub = Bq->sub; rank.nsub = 0u; rank.st = ws.st;
+    rank.nst_fixed = nslots; rank.out_abs = Bq->cabs; rank.out_pitch = np;
+    scr_pass<4>(ctx, *S, rank);
     // each signal's 256 best columns and what the columns it left out stay below
     for (uint32_t b = 0; b < nslots; ++b)
         (void)launch_select_top(ctx, Bq->cabs + (size_t)b * np, n, np, (uint32_t)RC::S, Bq->sub + (size_t)b * RC::S, S->sublist + kS64Sub,
@@ -2478,19 +2507,12 @@ hipError_t launch_screen64_batch(ss_hip_ctx* ctx, Workspace<double>& ws, uint32_
     { const hipError_t es = launch_res_solve<double>(ctx, nslots, Bq->gs, (uint32_t)RC::S, (size_t)RC::S * RC::S, Bq->c0, np, Bq->sub, tol, max_iter, ws.dims.kcap, log,
                                                      ws.x, np, ws.gam, ws.touched, ws.st, (TraceEntry*)nullptr, 0u, omp);
       if (es != hipSuccess) return es; }
-    (void)launch_res_residuals64(ctx, Y, log, tol, S->meta, Bq->r16, Bq->rn2p, Bq->tab, reinterpret_cast<uint32_t*>(S->meta) + 3, ws.st, true, omp, nslots,
-                                 Bq->ymeta);
+    (void)launch_res_residuals64(ctx, Y, log, tol, S->meta, Bq->res.r16, Bq->res.rn2p, Bq->res.tab, scr_headroom(*S), ws.st, true, omp, nslots, Bq->ymeta);
+    // (one slot per launch: the pass is handed the slot's block, subset and state)
     for (uint32_t b = 0; b < nslots; ++b) {
-        const __half* r16 = Bq->r16 + (size_t)b * kS64Rhs * ldm;
-        const float* rn = Bq->rn2p + (size_t)b * (ldm / 64u) * kS64Rhs;
-        const float* tb = Bq->tab + (size_t)b * kS64Rhs * kScrTab;
-        const uint32_t* sb = Bq->sub + (size_t)b * RC::S;
-        hipLaunchKernelGGL(k_scr_gemm<4>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 4), s, (const __half*)S->a16, ldm, n, r16,
-                           (const float*)S->anorm, rn, kS64Rhs, tb, sb, (uint32_t)RC::S, (const float*)S->meta, ws.st + b,
-                           reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 1u);
-        hipLaunchKernelGGL(k_scr_gemm<5>, dim3(1, np / kScrCols), dim3(256), scr_gemm_lds((uint32_t)RC::S, 5), s, (const __half*)S->a16, ldm, n, r16,
-                           (const float*)S->anorm, rn, kS64Rhs, tb, sb, (uint32_t)RC::S, (const float*)S->meta, ws.st + b,
-                           reinterpret_cast<uint32_t*>(S->meta) + 3, 0u, scr_skew(), 2u);
+        ScrPass pass;
+        pass.res = Bq->res.slot(b, ldm); pass.sub = Bq->sub + (size_t)b * RC::S; pass.nsub = (uint32_t)RC::S; pass.st = ws.st + b;
+        scr_pass_gated(ctx, *S, pass);
     }
     (void)launch_sub_finish_st(ctx, ws.st, nslots);
     return hipGetLastError();
@@ -2524,7 +2546,7 @@ double screen_read_headroom(ss_hip_ctx* ctx)
     ScreenState* S = scr_of(ctx);
     if (S == nullptr) return 0.0;
     uint32_t bits = 0;
-    if (hipMemcpy(&bits, reinterpret_cast<uint32_t*>(S->meta) + 3, sizeof(bits), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 0.0; }
+    if (hipMemcpy(&bits, scr_headroom(*S), sizeof(bits), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return 0.0; }
     float f;
     std::memcpy(&f, &bits, sizeof(f));
     return (double)f;
