@@ -41,7 +41,8 @@ extern "C" {
                                     new field of ss_hip_stats; joint sparse coding of signal groups, ss_hip_group_top_correlations_* and
                                     ss_hip_group_class_residuals_* — no new option key, no new field of ss_hip_stats; the atom step of
                                     dictionary learning under row weights, ss_hip_weighted_atom_update_* — no new option key, no new
-                                    field of ss_hip_stats) */
+                                    field of ss_hip_stats; block-sparse coding, the class top correlations
+                                    ss_hip_class_top_correlations_* — no new option key, no new field of ss_hip_stats) */
 
 typedef struct ss_hip_ctx ss_hip_ctx;
 
@@ -632,6 +633,62 @@ int ss_hip_group_class_residuals_f32(ss_hip_ctx* ctx, const float* Y, size_t B, 
 int ss_hip_group_class_residuals_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
                                      const void* records, uint32_t kmax, const uint32_t* group_off, size_t Gn,
                                      double* Rg, ptrdiff_t rg_stride, uint32_t* best, char* err, size_t errlen);
+
+/*
+ * Block-sparse coding — the class top correlations: for every signal the k CLASSES whose atoms together best explain what its record
+ * leaves over, and those classes' atoms as whole blocks (added under ABI version 7; csrc/blockcode.hip; NOT in the reference).  The
+ * selection step of block OMP (Eldar, Kuppinger and Boelcskei 2010) and of structured SRC (Elhamifar and Vidal 2011): a query in the
+ * span of one subject's training samples uses few classes and many atoms of each.  The transpose of the group top correlations:
+ * there the norm runs over the signals of a group, here over the atoms of a class.  Needs ss_hip_set_classes.  One stage of the
+ * block coder = this call, ss_hip_extend_records_* with its idx and coef rows, ss_hip_refit_records_*.
+ * Y, records, kmax, k: as for ss_hip_top_correlations_*, whose r_b, dot(i, b), d_i, rn_i and per-atom score word
+ *     t(i, b)   = |dot(i, b)| * rn_i                            in double
+ * these are (the same kernels on the same rows).  The CANDIDATE ATOMS of signal b are the columns i < n with d_i finite and non-zero
+ * that record b does not store (exclusion is by index, never by a multiplication by zero and never by the value of a dot).  For class c:
+ *     q(c, b)   = sum t(i, b) * t(i, b)                         over the candidate atoms of class c: one accumulator from 0, the columns
+ *                                                               in ascending index, every product and every sum rounded on its own
+ *     s(c, b)   = sqrt(q(c, b))                                 in double
+ * A class is a CANDIDATE when it has at least one candidate atom; a class whose score is NaN is never selected; a truncated record
+ * (K > kmax) has no candidates.
+ *     cls[b][t]   the candidate classes by descending score, ties by ascending class, t = 0 .. k - 1               [B][k]
+ *     score[b][t] (may be NULL) the class's score                                                                  [B][k]
+ * Entries behind the last candidate are SS_HIP_TOPCORR_NONE in cls and 0 in score.  1 <= k <= SS_HIP_TOPCORR_KMAX.
+ * EMISSION — idx [B][width], coef [B][width], taken [B]; idx may be NULL for a ranking-only call (then coef and taken must be NULL
+ * and width is ignored); coef and taken may be NULL on their own; 1 <= width <= SS_HIP_TOPCORR_KMAX, so a row is one
+ * ss_hip_extend_records_* takes.  room_b = width, with records min(width, kmax - K_b).  The selected classes are taken in rank order:
+ * a class is emitted WHOLE — its candidate atoms in ascending index — if they fit what is left of the room, and emission stops at the
+ * first class that does not fit (the prefix rule: no later, smaller class jumps the queue).
+ *     idx[b][.]   the emitted atoms, class after class                 coef[b][.]  (T)((double)dot * rn_i^2) of each, as for
+ *     taken[b]    the number of classes emitted                                    ss_hip_top_correlations_*
+ * Behind the last emitted atom the entries are SS_HIP_TOPCORR_NONE / 0.  A class of more than `room` candidate atoms is ranked but
+ * never emitted.  All data pointers may be host or device pointers.  The signals run in chunks under ss_hip_top_correlations_*' byte
+ * budget (option "tc_chunk_max"), a signal's bytes being that call's plus a class-score row of 8 num_classes; the workspace is the
+ * context's, grown on demand, freed with it.  The inverted index of the labels (the columns of every class in ascending order) is built
+ * once after each ss_hip_set_classes and kept on the context.  G = A^T A is neither read nor written.
+ * ARITHMETIC (one documented order: csrc/blockcode.hip): |s - s_float64| <= (gamma_m + 1e-12) sqrt(L_c) ||r_b||_2,
+ * L_c the class's candidate atoms, gamma_m as for ss_hip_top_correlations_*.
+ * CONTRACT: row b of every output is a function of A, the labels, y_b, record b, k and width alone — bit for bit the same alone or in
+ * any batch, in any batch order, with host or device pointers, across the chunking, whatever the context did before, with G resident
+ * or not; after a column replacement or a new ss_hip_set_classes it is a fresh context's result.  PREFIX PROPERTY: cls and score for k
+ * are the first k entries of those for any larger k.  No floating-point atomics.  No call changes what any solve returns.
+ * SINGLETONS: when every class is a single atom (labels 0 .. n - 1) the call returns ss_hip_top_correlations_*' words — cls = its idx,
+ * equal score words and, with width = k, its idx and coef: sqrt(fl(t * t)) = |t| in binary round-to-nearest — provided t * t neither
+ * underflows nor overflows (t between 2^-511 and 2^511 is safe).
+ * Validation happens before anything is written: a failing call leaves the outputs untouched.
+ *   SS_HIP_EINVAL  ss_hip_top_correlations_*' list (cls in the place of idx), and: no classes set; width outside
+ *                  1..SS_HIP_TOPCORR_KMAX with idx given; coef or taken given without idx
+ *   SS_HIP_ETYPE   the element type of the call is not the context's
+ *   SS_HIP_ENOMEM  the workspace could not be had (the message carries its bytes)
+ *   B == 0         SS_HIP_OK, nothing touched — after the checks above that need no data
+ */
+int ss_hip_class_top_correlations_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const void* records, uint32_t kmax, uint32_t k, uint32_t width,
+                                      uint32_t* cls, double* score, uint32_t* idx, float* coef, uint32_t* taken,
+                                      char* err, size_t errlen);
+int ss_hip_class_top_correlations_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                      const void* records, uint32_t kmax, uint32_t k, uint32_t width,
+                                      uint32_t* cls, double* score, uint32_t* idx, double* coef, uint32_t* taken,
+                                      char* err, size_t errlen);
 
 /*
  * Weighted coding — the weighted top correlations: the selection under a non-negative weight per row and signal, the primitive of

@@ -77,6 +77,8 @@ HIP_UNITS = [
     ("nonneg.hip", ["-ffp-contract=off"]),
     # robust weights from record residuals: the scale and the weight factors in double in the documented order, so the same flags (the tests' words)
     ("robust.hip", ["-ffp-contract=off"]),
+    # block-sparse coding: the class scores are sums of squares in double in the documented order, so the same flags (the tests' words)
+    ("blockcode.hip", ["-ffp-contract=off"]),
 ]
 
 

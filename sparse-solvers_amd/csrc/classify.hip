@@ -54,6 +54,7 @@ struct ClassifyState {
     Holdings own;                      // the labels
     uint32_t* labels = nullptr;        // [n_pad] class of every column (padding columns: 0)
     uint32_t num_classes = 0;
+    uint64_t generation = 0;           // ss_hip_set_classes calls that succeeded: what a derived index was built from (classify_generation)
     WorkArena arena;                   // the workspace of one chunk, carved per call
     WorkArena y_all;                   // classify: the batch's signals, uploaded once (a host Y)
     WorkArena rec_all;                 // classify: the batch's records (the caller's are on the host, or not asked for)
@@ -636,6 +637,18 @@ uint32_t classify_num_classes(const ss_hip_ctx* ctx)
     return cs && cs->labels ? cs->num_classes : 0u;
 }
 
+const uint32_t* classify_labels(const ss_hip_ctx* ctx)
+{
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
+    return cs ? cs->labels : nullptr;
+}
+
+uint64_t classify_generation(const ss_hip_ctx* ctx)
+{
+    const ClassifyState* cs = ctx->cls.as<const ClassifyState>();
+    return cs ? cs->generation : 0;
+}
+
 }  // namespace sship
 
 using namespace sship;
@@ -673,6 +686,7 @@ int ss_hip_set_classes(ss_hip_ctx* ctx, const uint32_t* labels, uint32_t num_cla
         HIPCHK(cs->own.drop(cs->labels));
         cs->labels = fresh;
         cs->num_classes = num_classes;
+        cs->generation += 1;
         return SS_HIP_OK;
     });
 }

@@ -426,6 +426,15 @@ int group_classes_entry(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_strid
 
 }  // namespace
 
+// k_js_select as a launch of its own (ss_hip_internal.h), on the context's stream, every pointer on the device: the k best of the first
+// n keys of every row of S [rows][pitch] — a stored score in double, a NaN word for no candidate — into oidx / oscore [rows][k].  For
+// the class top correlations (blockcode.hip), whose rows are a signal's class scores: the same kernel, no second statement of it
+hipError_t js_launch_select(ss_hip_ctx* ctx, const double* S, uint32_t rows, uint32_t n, uint32_t pitch, uint32_t k, uint32_t* oidx, double* oscore)
+{
+    hipLaunchKernelGGL(k_js_select, dim3(rows), dim3(256), 0, ctx->stream, S, n, pitch, k, oidx, oscore);
+    return hipGetLastError();
+}
+
 }  // namespace sship
 
 using namespace sship;

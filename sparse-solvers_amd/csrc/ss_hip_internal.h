@@ -405,6 +405,7 @@ struct ss_hip_ctx {
     sship::Part tc;               // sship::WorkArena* (topcorr.hip): the one workspace of the four top-correlation calls and the record extension
     sship::Part js;               // sship::WorkArena* (joint.hip): the workspace of the group class residuals
     sship::Part wt;               // sship::WeightedState* (weighted.hip): the staged weights of the three weighted calls
+    sship::Part bc;               // sship::ClassIndex* (blockcode.hip): the inverted index of the labels, built once after each ss_hip_set_classes
     int dl_chunk_max = 0;        // option (test aid): most signals whose residuals the atom updates hold at once (0 = the byte budget alone)
     int tc_chunk_max = 0;        // option (test aid): most signals whose residuals and dots the top correlations hold at once (0 = the byte budget alone)
     int device = 0;
@@ -602,6 +603,10 @@ template <typename T>
 hipError_t tc_launch_residual_block(ss_hip_ctx* ctx, const T* yd, long long ys, long long yi, const unsigned char* recs, size_t rb, uint32_t kmax,
                                     uint32_t Bc, T* R, double* part);
 template <typename T> hipError_t tc_launch_dots(ss_hip_ctx* ctx, const T* R, uint32_t Bc, T* D);
+// ... and the selection over STORED score rows (joint.hip: k_js_select, one workgroup per row — tc_select.h's selection with the stored
+// double as the key): the k best of the first n keys of every row of S [rows][pitch], a NaN word being no candidate, into oidx / oscore
+// [rows][k] (SS_HIP_TOPCORR_NONE / 0 behind the last candidate).  The group call's rows are groups, the class call's (blockcode.hip) signals
+hipError_t js_launch_select(ss_hip_ctx* ctx, const double* S, uint32_t rows, uint32_t n, uint32_t pitch, uint32_t k, uint32_t* oidx, double* oscore);
 // ... and k_tc_tile with its squaring flag: D2 [tiles x 128][n_pad] = sum_k Wb[b][k] * (a_ki * a_ki), the square formed once in T where
 // At is staged — the second product of the weighted top correlations (weighted.hip); Wb [tiles x 128][ldm] as R above
 template <typename T> hipError_t tc_launch_weight_dots(ss_hip_ctx* ctx, const T* Wb, uint32_t Bc, T* D2);
@@ -637,6 +642,10 @@ template <typename T>
 int class_residual_rows(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records,
                         uint32_t kmax, T* R, ptrdiff_t r_stride, uint32_t* best, char* err, size_t errlen);
 uint32_t classify_num_classes(const ss_hip_ctx* ctx);
+// read access to the labels as set (classify.hip): the device array [n_pad] (nullptr for none), and how many ss_hip_set_classes calls have
+// succeeded on the context — the generation an index derived from the labels was built from (blockcode.hip's inverted index)
+const uint32_t* classify_labels(const ss_hip_ctx* ctx);
+uint64_t classify_generation(const ss_hip_ctx* ctx);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip), every column in class 0: Rn[b] = the word
 // R[b][0] of that call (NaN for a truncated record).  Y, records, Rn on either side; `who` names the caller in an error's text
 template <typename T>

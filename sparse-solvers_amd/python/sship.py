@@ -155,6 +155,7 @@ _PROTOTYPES = [
     ("ss_hip_extend_records_", _int, [_vp, _vp, _sz, _u32, _vp, _vp, _u32, _vp, _vp] + _ERR),
     ("ss_hip_group_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_group_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _sz, _vp, _pd, _vp] + _ERR),
+    ("ss_hip_class_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp] + _ERR),
     ("ss_hip_weighted_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, ctypes.c_double, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_weighted_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_weighted_class_residuals_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _pd, _vp, _u32, _vp, _pd, _vp, _vp] + _ERR),
