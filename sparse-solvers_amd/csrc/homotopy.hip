@@ -852,13 +852,17 @@ void first_sweep(ss_hip_ctx* ctx, Workspace<T>& ws, T* out, ProfSpans& spans, ui
 }
 
 // one signal in the screened form (screen.hip): no G — the subset's own Gram matrix from A, then one pass over the fp16 copy of A
+// (developer switch, read per solve: which hand-offs inside launches the form may use — 1 = the one-launch tail, 2 = the selection by
+// many workgroups, 4 = k_la_reset's clears in the prologue of the fp8 ranking pass; unset = all, 0 = the launches before them)
+inline void scr_handoff_mask(ScrHandoff* ho)
+{
+    if (const char* e = std::getenv("SS_HIP_SCR_HANDOFF")) ho->mask = (uint32_t)std::strtoul(e, nullptr, 0);
+}
+
 inline hipError_t scr_single(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, EventPair first, EventPair screen, EventPair path,
                              bool omp, bool rescue, ScrHandoff* ho)
 {
     grow_device(ctx->own, ctx->sub_buf, ctx->sub_buf_bytes, sub_buffer_bytes(1), 1, "hipMalloc(sub_buf)");
-    // (developer switch, read per solve: which hand-offs inside launches the form may use — 1 = the one-launch tail, 2 = the selection by
-    // many workgroups; unset = all, 0 = the launches before them)
-    if (const char* e = std::getenv("SS_HIP_SCR_HANDOFF")) ho->mask = (uint32_t)std::strtoul(e, nullptr, 0);
     if (ctx->sub_dbg == nullptr && std::getenv("SS_HIP_SUB_STAMPS")) {
         HELD(ctx->own, hipMalloc, &ctx->sub_dbg, 16 * sizeof(unsigned long long));
         HIPCHK(hipMemsetAsync(ctx->sub_dbg, 0, 16 * sizeof(unsigned long long), ctx->stream));
@@ -1465,9 +1469,19 @@ int solve_once(ss_hip_ctx* ctx, const T* y, ptrdiff_t incy, T tol, uint32_t max_
             const bool screened = f.scr64r || f.scr1;
             if (route.rescue && !rescue_prologue<T>(ctx, ws, tol, route, screened, next)) { *again = true; return SS_HIP_OK; }
             const bool rescue = route.rescue;
-            if (!omp) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_dev, incy));     // x, d, flags, DevState, r = y (OMP: done above)
             // (the screened form's first pass — A^T y over all columns — reads the reduced-precision copy too: screen.hip, k_scr_first)
             const bool first16 = screened && screen_first16_usable(ctx);
+            // x, d, flags, DevState, r = y (OMP: done above): by k_la_reset — or, where the fp8 ranking pass is the first launch of the
+            // attempt (fp32 form, first attempt; decided here, before anything is queued), by that pass's workgroups in their prologue
+            bool reset_folded = false;
+            if constexpr (sizeof(T) == 4) {
+                scr_handoff_mask(&scr_ho);
+                if (f.scr1 && !f.sub1 && !omp && !rescue && first16 && (scr_ho.mask & 4u) && screen_first8_folds(ctx)) {
+                    scr_ho.reset = la_reset_args<float>(ctx, ws, false, y_dev, incy);
+                    reset_folded = true;
+                }
+            }
+            if (!omp && !reset_folded) HIPCHK(launch_la_reset<T>(ctx, ws, false, y_dev, incy));
             if (!first16) first_sweep<T>(ctx, ws, ws.c0, spans, &nb1);
             if (f.sub1) {
                 if constexpr (sizeof(T) == 4) {

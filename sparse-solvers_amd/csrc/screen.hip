@@ -381,18 +381,29 @@ void k_scr_first(const __half* __restrict__ a16, uint32_t ldm, uint32_t n, uint3
 template <typename TY, int CPW, int DEPTH>
 __global__ __launch_bounds__(512, 2)
 void k_scr_first8(const uint8_t* __restrict__ a8, uint32_t ldm, uint32_t n, uint32_t ngroups, const TY* __restrict__ y,
-                  float* __restrict__ meta, float* __restrict__ c0h, uint32_t skew, float* __restrict__ wmax)
+                  float* __restrict__ meta, float* __restrict__ c0h, uint32_t skew, float* __restrict__ wmax,
+                  long long incy, uint32_t ylen, LaResetArgs<float> reset)
 {
+    // (y: ylen entries incy apart, zeros beyond — the block the solve staged, incy = 1 and ylen = ldm, or the caller's own vector when
+    // this launch is the first of an attempt.  reset: then its workgroups also share out what k_la_reset does, in front of their own work —
+    // the clears, and y into the solve's two copies; nothing of that is read before the launch ends: y comes from the caller's pointer)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* ly = reinterpret_cast<float*>(smem);                  // [ldm]
     float* sv = ly + ldm;                                        // [16] reduction scratch
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (reset.x != nullptr) la_reset_share(reset, blockIdx.x * 512u + tid, gridDim.x * 512u);
+    const bool packed = incy == 1 && ylen == ldm;                // (uniform)
     float ss = 0.f;
     for (uint32_t i = tid * 4u; i < ldm; i += 2048u) {
         scr_v4f v;
+        if (packed) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (float)y[i + (uint32_t)e];
+            for (int e = 0; e < 4; ++e) v[e] = (float)y[i + (uint32_t)e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = i + (uint32_t)e < ylen ? (float)y[(long long)(i + (uint32_t)e) * incy] : 0.f;
+        }
         const uint32_t wq = i & 1023u;                           // = 16 l + 4 q
         *reinterpret_cast<scr_v4f*>(&ly[(i & ~1023u) + (((wq >> 2) & 3u) << 8) + ((wq >> 4) << 2)]) = v;
 #pragma unroll
@@ -635,8 +646,31 @@ void k_scr_residuals(const float* __restrict__ At, uint32_t ldm, uint32_t n, con
         tab += (size_t)slot * kScrRhs * kScrTab;
         st += slot;
     }
-    if (st->status != 0u && !scan) return;
+    // Everything this workgroup needs from the slot's state and log is requested in ONE burst, ahead of the first wait: the status and the
+    // number of states, the columns of ALL of the thread's gather slots (positions at or beyond Pfin hold 0xffffffff or a stale column:
+    // their rows are staged and never read), the scale's header words, the coefficient table.  The columns' rows and Pfin follow in a
+    // second burst.  No load stands behind a condition on loaded data (the compiler would wait per load): addresses are clamped into the
+    // slot's own buffers, values are selected afterwards.  Two dependent trips to memory where the gather loop made one per trip and load.
     const uint32_t tid = threadIdx.x;
+    constexpr uint32_t kGather = (kSbRows + 15u) / 16u;                              // gather slots of a thread: positions (tid >> 4) + 16 t
+    constexpr uint32_t kTabLoads = (kSbLog * kSbRows + 255u) / 256u;
+    const uint32_t status = st->status;
+    const uint32_t nlog = st->solo_nlog;
+    uint32_t gcol[kGather];
+#pragma unroll
+    for (uint32_t t = 0; t < kGather; ++t) gcol[t] = pcol[min((tid >> 4) + 16u * t, kSbRows - 1u)];
+    const uint32_t* const hh_own = hdr + (size_t)(min(tid, kSbLog - 2u) + 1u) * 8u;  // (the header of state tid + 1, read below by tid < nst)
+    const uint32_t hh_flags = hh_own[1], hh_lam = hh_own[4];
+    float tabv[kTabLoads];
+#pragma unroll
+    for (uint32_t t = 0; t < kTabLoads; ++t) tabv[t] = LX[(size_t)kSbRows + min(tid + 256u * t, (kSbLog - 1u) * kSbRows - 1u)];
+    scr_v4f gv[kGather];
+#pragma unroll
+    for (uint32_t t = 0; t < kGather; ++t)
+        gv[t] = *reinterpret_cast<const scr_v4f*>(At + (size_t)(gcol[t] < n ? gcol[t] : 0u) * ldm + blockIdx.x * 64u + 4u * (tid & 15u));
+    const uint32_t Pfin = hdr[(size_t)(min(max(nlog, 1u), kSbLog) - 1u) * 8u];
+    const scr_v4f yv = *reinterpret_cast<const scr_v4f*>(y + blockIdx.x * 64u + 4u * (tid & 15u));   // (rows m .. ldm - 1 of y and of A are zero)
+    if (status != 0u && !scan) return;
     float ratio0 = 0.f;
     if (fl != nullptr && blockIdx.x == 0u && blockIdx.y == 0u && tid == 0u) {
         fl[0] = 0u; fl[kScrFlCap + 1u] = 0u; fl[kScrFlCap + 4u] = 0u;
@@ -658,37 +692,34 @@ void k_scr_residuals(const float* __restrict__ At, uint32_t ldm, uint32_t n, con
         }
         ratio0 = bound0 > 0.f && v0 == v0 ? v0 / bound0 : 3.0e38f;
     }
-    const uint32_t nlog = st->solo_nlog;
     if (nlog < 2u) {
         if (blockIdx.x == 0u && tid == 0u && blockIdx.y == 0u) *headroom = __float_as_uint(ratio0);
         return;
     }
     const uint32_t nst = nlog - 1u;
     const uint32_t r0 = blockIdx.x * 64u;
-    const uint32_t Pfin = hdr[(nlog - 1u) * 8u];
-    for (uint32_t e = tid; e < kSbLog * kSbRows; e += 256u) {
+#pragma unroll
+    for (uint32_t t = 0; t < kTabLoads; ++t) {
+        const uint32_t e = tid + 256u * t;
         const uint32_t kk = e / kSbRows, p = e - kk * kSbRows;
-        sXt[p][kk] = kk < nst ? LX[(size_t)kSbRows + e] : 0.f;                 // (state k = kk + 1)
+        if (e < kSbLog * kSbRows) sXt[p][kk] = kk < nst ? tabv[t] : 0.f;       // (state k = kk + 1)
     }
     if (tid < kSbLog) {
         float sc = 1.f;
         if (tid < nst) {
-            const uint32_t* hh = hdr + (size_t)(tid + 1u) * 8u;
-            const float lam = __uint_as_float(hh[4]);
-            const bool final_state = !(hh[1] & 1u);
+            const float lam = __uint_as_float(hh_lam);
+            const bool final_state = !(hh_flags & 1u);
             sc = scr_state_scale(final_state ? fmaxf(lam, tol) : lam);
         }
         sS[tid] = sc;
     }
-    for (uint32_t p = tid >> 4; p < Pfin; p += 16u) {
-        const uint32_t col = pcol[p];
-        const scr_v4f v = col < n ? *reinterpret_cast<const scr_v4f*>(At + (size_t)col * ldm + r0 + 4u * (tid & 15u))
-                                  : scr_v4f{ 0.f, 0.f, 0.f, 0.f };
-        *reinterpret_cast<scr_v4f*>(&sAc[p][4u * (tid & 15u)]) = v;
+#pragma unroll
+    for (uint32_t t = 0; t < kGather; ++t) {
+        const uint32_t p = (tid >> 4) + 16u * t;
+        if (p < kSbRows) *reinterpret_cast<scr_v4f*>(&sAc[p][4u * (tid & 15u)]) = gcol[t] < n ? gv[t] : scr_v4f{ 0.f, 0.f, 0.f, 0.f };
     }
     __syncthreads();
     const uint32_t rg = tid & 15u, sgp = tid >> 4;
-    const scr_v4f yv = *reinterpret_cast<const scr_v4f*>(y + r0 + 4u * rg);         // (rows m .. ldm - 1 of y and of A are zero)
     bool ovf = false;
     for (uint32_t s0 = 4u * sgp; s0 < nst; s0 += 64u) {
         scr_v4f acc[4] = { yv, yv, yv, yv };
@@ -2020,17 +2051,41 @@ template <typename TY> static bool scr_first8_attr()
 }
 
 // c~0 = A16^T y / sA (or A8^T y / sA8) into c0h ([n_pad] floats), ||y||^2 into meta[5], the pass's error model into meta[8], meta[9]
+// the ranking pass over the fp8 copy can be launched: the copy is there (made now, if this is the first time) and y fits the kernel's LDS
 template <typename TY>
-static hipError_t launch_scr_first(ss_hip_ctx* ctx, ScreenState* S, const TY* y, float* c0h, float* wmax = nullptr, uint32_t* nwmax = nullptr)
+static bool scr_first8_launchable(ss_hip_ctx* ctx, ScreenState* S)
+{
+    return screen_first8_ready<TY>(ctx, S) && ((size_t)ctx->ldm * sizeof(float) + 64 <= 65536u || scr_first8_attr<TY>());
+}
+
+// (reset: the clears of k_la_reset ride in the fp8 pass's prologue, which then reads the caller's y — or the staged copy — itself; the
+// caller has asked screen_first8_folds.  Should the fp8 pass not be launchable after all, k_la_reset is launched here, in front of the
+// pass that does run: no attempt goes without one of the two.)
+template <typename TY>
+static hipError_t launch_scr_first(ss_hip_ctx* ctx, ScreenState* S, const TY* y, float* c0h, float* wmax = nullptr, uint32_t* nwmax = nullptr,
+                                   const LaResetArgs<float>* reset = nullptr)
 {
     const uint32_t ldm = ctx->ldm, np = ctx->n_pad;
     const size_t lds = (size_t)ldm * sizeof(float) + 64;
+    const bool fold = reset != nullptr && reset->x != nullptr;
+    const bool first8 = (lds <= 65536u || scr_first_attr<TY>()) && scr_first8_launchable<TY>(ctx, S);
+    if (fold && !first8) {
+        const hipError_t er = launch_la_reset_args<float>(ctx, *reset);
+        if (er != hipSuccess) return er;
+    }
     if (lds > 65536u && !scr_first_attr<TY>()) return hipErrorInvalidConfiguration;
     const uint32_t grid = std::min<uint32_t>(np / 32u, (uint32_t)ctx->num_cus * 2u);
     if (grid * 8u > kScrWmax) wmax = nullptr;
-    if (screen_first8_ready<TY>(ctx, S) && (lds <= 65536u || scr_first8_attr<TY>())) {
-        hipLaunchKernelGGL((k_scr_first8<TY, 4, 3>), dim3(grid), dim3(512), lds, ctx->stream, (const uint8_t*)S->a8, ldm, (uint32_t)ctx->n, np / 32u, y,
-                           S->meta, c0h, scr_skew() == 0u ? 0u : 5u, wmax);
+    if (first8) {
+        const TY* ysrc = y;
+        long long incy = 1;
+        uint32_t ylen = ldm;
+        if constexpr (std::is_same<TY, float>::value) {
+            if (fold && reset->y_user != nullptr) { ysrc = reset->y_user; incy = reset->incy; ylen = reset->m; }
+            else if (fold) ysrc = reset->y;
+        }
+        hipLaunchKernelGGL((k_scr_first8<TY, 4, 3>), dim3(grid), dim3(512), lds, ctx->stream, (const uint8_t*)S->a8, ldm, (uint32_t)ctx->n, np / 32u, ysrc,
+                           S->meta, c0h, scr_skew() == 0u ? 0u : 5u, wmax, incy, ylen, fold ? *reset : LaResetArgs<float>{});
         if (nwmax != nullptr) *nwmax = wmax != nullptr ? grid * 8u : 0u;
         ctx->first_pass_elem_bytes = 1;
         return hipGetLastError();
@@ -2040,6 +2095,12 @@ static hipError_t launch_scr_first(ss_hip_ctx* ctx, ScreenState* S, const TY* y,
                        S->meta, c0h, scr_skew() == 0u ? 0u : 5u, wmax);
     if (nwmax != nullptr) *nwmax = wmax != nullptr ? grid * 8u : 0u;
     return hipGetLastError();
+}
+
+bool screen_first8_folds(ss_hip_ctx* ctx)
+{
+    ScreenState* S = scr_of(ctx);
+    return S != nullptr && !ctx->is_f64 && screen_first16_usable(ctx) && scr_first8_launchable<float>(ctx, S);
 }
 
 hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first,
@@ -2060,9 +2121,12 @@ hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, 
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, np = ctx->n_pad;
     const float* At = static_cast<const float*>(ctx->At);
     uint32_t nwmax = 0;
+    // (ho->reset: the caller left this attempt's k_la_reset to the ranking pass — which is the first launch below, or the reset is launched here)
+    const LaResetArgs<float>* const reset = ho != nullptr && ho->reset.x != nullptr ? &ho->reset : nullptr;
+    if (reset != nullptr && !(first16 && !rescue)) { const hipError_t er = launch_la_reset_args<float>(ctx, *reset); if (er != hipSuccess) return er; }
     if (first16 && !rescue) {
         if (first.a) (void)hipEventRecord(first.a, s);
-        { const hipError_t ef = launch_scr_first<float>(ctx, S, (const float*)ws.rhs, ws.c0, S->wmax, &nwmax); if (ef != hipSuccess) return ef; }
+        { const hipError_t ef = launch_scr_first<float>(ctx, S, (const float*)ws.rhs, ws.c0, S->wmax, &nwmax, reset); if (ef != hipSuccess) return ef; }
         if (first.b) (void)hipEventRecord(first.b, s);
     }
     if (rescue) {

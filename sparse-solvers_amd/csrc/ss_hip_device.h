@@ -350,4 +350,27 @@ __device__ __forceinline__ void bump_seq(DevState* st, uint32_t* hflags)
     __hip_atomic_store(&hflags[0], sq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The clears and copies at the head of an attempt (LaResetArgs), shared out over gsz threads of which this is gtid: k_la_reset's whole
+// work, and the prologue of a kernel that takes the launch's place.  Nothing it writes may be read in the same launch.
+// (handoff: the tickets and the shared histogram of the screened form's in-launch hand-offs, if the context has them — cleared for
+// every attempt, whatever the last one left)
+template <typename T>
+__device__ __forceinline__ void la_reset_share(const LaResetArgs<T>& a, uint32_t gtid, uint32_t gsz)
+{
+    for (uint32_t i = gtid; i < a.handoff_words; i += gsz) a.handoff[i] = 0u;
+    for (uint32_t i = gtid; i < a.n_pad; i += gsz) {
+        a.x[i] = T(0); a.d[i] = T(0); a.insup[i] = 0;
+        if (a.slot_of != nullptr) a.slot_of[i] = -1;
+    }
+    if (a.y_user != nullptr) {
+        // the caller's signal is on the device: taken from there (no copy command in front of this launch)
+        for (uint32_t i = gtid; i < a.ldm; i += gsz) { const T v = i < a.m ? a.y_user[(long long)i * a.incy] : T(0); a.y[i] = v; a.rhs[i] = v; }
+    } else {
+        for (uint32_t i = gtid; i < a.ldm; i += gsz) a.rhs[i] = a.y[i];
+    }
+    for (uint32_t i = gtid; i < a.sync_words; i += gsz) a.la_sync[i] = i < a.sync_head_words ? 0u : 0xffffffffu;
+    for (uint32_t i = gtid; i < a.st_nwords; i += gsz) a.st_words[i] = 0u;
+    if (gtid == 0) *a.ndone = 0u;
+}
+
 }  // namespace sship

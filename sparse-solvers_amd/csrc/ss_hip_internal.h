@@ -535,10 +535,22 @@ bool screen_first16_usable(const ss_hip_ctx* ctx);        // ... with the FIRST 
 //   [kHoEnt ..)                      their entries, (key << 16) | column, a fixed region of `slice` words per workgroup
 constexpr uint32_t kHoSelWgs = 64, kHoSelCols = 65536;
 constexpr uint32_t kHoTicketSel = 0, kHoTicketTail = 1, kHoHist = 4, kHoZeroWords = kHoHist + 2048, kHoCnt = kHoZeroWords, kHoEnt = kHoCnt + kHoSelWgs;
+// What k_la_reset clears and copies at the head of an attempt (activeset.hip: la_reset_args fills it, la_reset_share in ss_hip_device.h is
+// the work, shared out over whatever grid runs it).  x == nullptr: nothing to do.
+template <typename T>
+struct LaResetArgs {
+    T* x = nullptr; T* d = nullptr; uint8_t* insup = nullptr; int32_t* slot_of = nullptr; uint32_t n_pad = 0;
+    uint32_t* la_sync = nullptr; uint32_t sync_head_words = 0, sync_words = 0;
+    uint32_t* st_words = nullptr; uint32_t st_nwords = 0; uint32_t* ndone = nullptr;
+    T* y = nullptr; T* rhs = nullptr; uint32_t ldm = 0; const T* y_user = nullptr; long long incy = 1; uint32_t m = 0;
+    uint32_t* handoff = nullptr; uint32_t handoff_words = 0;
+};
 // what the caller of launch_screen_form allows and learns: mask (developer switch SS_HIP_SCR_HANDOFF) 1 = the one-launch tail, 2 = the
-// selection by kHoSelWgs workgroups; x_dst / incx: the caller's x if it is on the device; tail_fused: k_scr_tail ran — the state is
-// mirrored and x_dst written, no k_epilogue is to follow
-struct ScrHandoff { uint32_t mask = 3u; float* x_dst = nullptr; long long incx = 1; bool tail_fused = false; };
+// selection by kHoSelWgs workgroups, 4 = the clears of k_la_reset in the prologue of the fp8 ranking pass; x_dst / incx: the caller's x if
+// it is on the device; tail_fused: k_scr_tail ran — the state is mirrored and x_dst written, no k_epilogue is to follow; reset: the caller
+// has NOT launched k_la_reset for this attempt (it asked screen_first8_folds first) — the ranking pass does that work
+struct ScrHandoff { uint32_t mask = 7u; float* x_dst = nullptr; long long incx = 1; bool tail_fused = false; LaResetArgs<float> reset; };
+bool screen_first8_folds(ss_hip_ctx* ctx);                // the fp8 ranking pass will be the form's first launch on this context (fp32)
 hipError_t launch_sub_select_wide(ss_hip_ctx* ctx, const SubBufs& B, const float* c0, float* thr_out, const float* wmax, uint32_t nwmax);
 hipError_t launch_screen_form(ss_hip_ctx* ctx, Workspace<float>& ws, float tol, uint32_t max_iter, bool first16, bool finish, EventPair first = {},
                               EventPair screen = {}, EventPair path = {}, bool omp = false, bool rescue = false, ScrHandoff* ho = nullptr);      // (pairs: around the reduced-precision first pass, the screening pass, the path kernel)
@@ -709,6 +721,10 @@ hipError_t launch_la_update(const ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t ro
 // one launch for everything a lookahead solve clears before its first sweep (and r = y)
 template <typename T>
 hipError_t launch_la_reset(const ss_hip_ctx* ctx, Workspace<T>& ws, bool clear_slots, const T* y_user = nullptr, ptrdiff_t incy = 1);   // y_user: the caller's signal, if it is on the device (else ws.y holds it)
+template <typename T>
+LaResetArgs<T> la_reset_args(const ss_hip_ctx* ctx, Workspace<T>& ws, bool clear_slots, const T* y_user = nullptr, ptrdiff_t incy = 1);   // ... its arguments, for a kernel that does the work in its prologue
+template <typename T>
+hipError_t launch_la_reset_args(const ss_hip_ctx* ctx, const LaResetArgs<T>& a);     // ... and the launch from those
 template <typename T>
 hipError_t launch_la_cq(const ss_hip_ctx* ctx, Workspace<T>& ws, uint32_t* nparts_out);
 // fused iteration of the lookahead engine (c, q from the cache; scan; select; update)
