@@ -957,6 +957,54 @@ int ss_hip_nonneg_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, 
                                     double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
 
 /*
+ * The backward step — pruning compact records: ss_hip_refit_records_* that takes atoms out again (added under ABI version 7;
+ * csrc/pursuit.hip, the kernels of csrc/refit.hip with the solve replaced; NOT in the reference).  Every record coder only adds
+ * atoms; subspace pursuit, CoSaMP and OLS with backward elimination also remove them.  One round of subspace pursuit =
+ * ss_hip_top_correlations_*, ss_hip_extend_records_*, this call.  For signal b with the record's stored columns T in record order,
+ * K of them: G = A_T^T A_T, h = A_T^T y_b and yy = y_b^T y_b are ss_hip_refit_records_*' words (the same panel, row chunks, tiles and
+ * summation order), z its solution in double before rounding (the same Cholesky statements, pivot test and back substitution), and
+ *     score_e     in double, every product, sum and quotient rounded separately (csrc/refit.hip, PRUNE ORDER):
+ *                 SS_HIP_PRUNE_MAGNITUDE  (z_e * z_e) * G_ee — the energy of the atom's own term;
+ *                 SS_HIP_PRUNE_BACKWARD   (z_e * z_e) / q_e with q_e = ((G_T)^-1)_ee = sum over i >= e of ((L^-1)_ie)^2 — exactly the
+ *                 rise of || y - A_T z ||^2 when atom e alone is removed and the rest refitted.  The rules agree for orthogonal atoms
+ *     CANDIDATES  the entries with score_e >= min_share * yy: a comparison, so a NaN never passes
+ *     KEPT        the min(keep, candidates) candidates that come first under the total order (score descending, record position
+ *                 ascending)
+ *     records_out[b]  for SS_HIP_REFIT_DONE: every entry kept: ss_hip_refit_records_*' output record.  Otherwise the normal equations
+ *                     of the kept sub-block — the same panel words, summed again from the chunk partials — are solved by the same
+ *                     statements in the same order with K' in the pivot test, and the record is written as
+ *                     ss_hip_nonneg_refit_records_* writes its record: the kept entries in record order, compacted — K' of them, K'
+ *                     in word 0, idx[0 .. K') and val[0 .. K') theirs (each z rounded once to T), idx[K' .. K) and val[K' .. K) zero
+ *                     words; iter, err, the slots behind K and the padding copied word for word.  K' = 0 is a valid result.  The
+ *                     record is bit for bit what ss_hip_refit_records_* returns for the kept record.  For every other status the
+ *                     record is copied unchanged
+ *     resnorm[b]      (may be NULL) as for ss_hip_refit_records_*, of the record as written
+ *     status[b]       (may be NULL) SS_HIP_REFIT_*: EMPTY, TRUNCATED and TOO_LARGE (K > SS_HIP_REFIT_KMAX) as there;
+ *                     SS_HIP_REFIT_SINGULAR when either solve fails the pivot test; else SS_HIP_REFIT_DONE
+ *     dropped[b]      (may be NULL) K - K' for SS_HIP_REFIT_DONE, else 0
+ *     score[b][e]     (may be NULL; [B][kmax] doubles) score_e by INPUT position for e < K, 0 behind it; a zero row for a status
+ *                     other than SS_HIP_REFIT_DONE
+ * keep >= 1; rule one of SS_HIP_PRUNE_*; min_share >= 0 and finite.  A NaN in y_b gives NaN scores: K' = 0, SS_HIP_REFIT_DONE, a NaN
+ * resnorm.  Y, records, records_out and the four outputs: host or device pointers; records_out may be records (in place).
+ * CONTRACT: signal b's outputs are a function of (record b, y_b, A, keep, rule, min_share) alone — bit for bit the same alone or in
+ * any batch, in any batch order, with host or device pointers, in place or out of place, across the internal chunking, and whatever
+ * the context did before.  No floating-point atomics.  No absolute constant: under A * 2^a, Y * 2^b and record values * 2^(b - a)
+ * the kept sets are the same, the values scale by 2^(b - a) and the scores by 2^(2 b).  No option key, no field of ss_hip_stats.
+ * Validation: ss_hip_refit_records_*', then SS_HIP_EINVAL for keep = 0, an unknown rule, a negative or non-finite min_share — all
+ * before anything is written.  B = 0 is SS_HIP_OK.
+ */
+#define SS_HIP_PRUNE_MAGNITUDE 0
+#define SS_HIP_PRUNE_BACKWARD 1
+int ss_hip_prune_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                             const void* records, uint32_t kmax, void* records_out,
+                             uint32_t keep, uint32_t rule, double min_share,
+                             double* resnorm, uint32_t* status, uint32_t* dropped, double* score, char* err, size_t errlen);
+int ss_hip_prune_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                             const void* records, uint32_t kmax, void* records_out,
+                             uint32_t keep, uint32_t rule, double min_share,
+                             double* resnorm, uint32_t* status, uint32_t* dropped, double* score, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the

@@ -79,6 +79,8 @@ HIP_UNITS = [
     ("robust.hip", ["-ffp-contract=off"]),
     # block-sparse coding: the class scores are sums of squares in double in the documented order, so the same flags (the tests' words)
     ("blockcode.hip", ["-ffp-contract=off"]),
+    # the pruning call: refit.hip's unit with a flag (the scores in double in the documented order), so the same flags (the tests' words)
+    ("pursuit.hip", ["-ffp-contract=off"]),
 ]
 
 

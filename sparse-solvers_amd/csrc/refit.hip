@@ -25,6 +25,12 @@
 // The non-negative refit (ss_hip_nonneg_refit_records_*, nonneg.hip) is this unit with another flag: refit_nonneg is refit_entry with
 // k_rf_cap behind k_rf_check (a DONE record of more than SS_HIP_NNLS_KMAX columns becomes TOO_LARGE), k_rf_gram as it is, and
 //   k_rf_nnls    in k_rf_solve's place, one workgroup per signal: Lawson-Hanson on the same [G h; h^T y^T y] in double, in LDS.
+// The pruning call (ss_hip_prune_records_*, pursuit.hip) is this unit with a third flag: refit_prune is refit_entry with k_rf_check and
+// k_rf_gram as they are and
+//   k_rf_prune   in k_rf_solve's place, one workgroup per signal: k_rf_solve's solve on the whole record, a score per entry, the
+//                entries to keep, and k_rf_solve's solve once more on the kept sub-block of the SAME panel words — G_ij is one chain
+//                over the rows whichever tile holds it, so the panel of the kept record is a sub-block of this one word for word, and
+//                the record written is what ss_hip_refit_records_* returns for it.  One Gram panel a call, not two.
 //
 // SUMMATION ORDER (the tests' bounds follow from it; build flag -ffp-contract=off: products and sums are rounded separately outside
 // the MFMA, whose four products per instruction are a chain of fused multiply-adds):
@@ -58,6 +64,21 @@
 //                alpha * (s_p - z_p) for every p;  p* and every p with !(z_p > 0) leave P with z = 0 exactly; the factor again; solve.
 //   the record   the entries with (T) z_e > 0, in record order, compacted to the front of idx and val (z_e rounded once to T), zero
 //                words from there to K, K' in word 0; every other word as it was.
+// PRUNE ORDER (k_rf_prune; G, h, y^T y and z are the words above — z in double, before it is rounded; everything below in double,
+// every product, sum and quotient rounded separately):
+//   inverse      (rule BACKWARD) M = L^-1, row after row over the factor, in place: for i ascending  M_ii = 1 / l_ii,  and for every
+//                e < i  s = 0, then s = s + l_ik * M_ke for k ascending from e to i - 1,  M_ie = (-s) / l_ii.  The columns e of a
+//                row are independent of each other: a workgroup barrier separates rows, never the terms of a sum;
+//   q_e          = 0, then q_e = q_e + M_ie * M_ie for i ascending from e to K - 1: the diagonal of (G_T)^-1;
+//   score_e      MAGNITUDE (z_e * z_e) * G_ee with G_ee the diagonal before any update;  BACKWARD (z_e * z_e) / q_e;
+//   candidates   the e with score_e >= min_share * y^T y (one product; a comparison, so a NaN never passes);
+//   kept         the min(keep, candidates) candidates that come first by (score descending, record position ascending): entry e is
+//                kept when fewer than `keep` candidates come before it — a count of comparisons, no sort;
+//   all kept     the record is ss_hip_refit_records_*' record: val[e] = z_e rounded once to T;
+//   else         [G h; h^T .] of the kept entries, in record order, is summed again from the chunk partials (`G, h` above: the
+//                Cholesky has overwritten the triangle) and solved by the statements above with K' in the pivot test;
+//   the record   as k_rf_nnls writes it: the kept entries in record order, compacted to the front of idx and val (z rounded once
+//                to T), zero words from there to K, K' in word 0; every other word as it was.
 // No floating-point atomics; nothing depends on B, on the chunking of the batch, on the launch geometry, on where the pointers live or
 // on what the context did before: a signal's record, residual norm and status are a function of its input record, its y and A.
 #include "ss_hip_internal.h"
@@ -233,13 +254,64 @@ void k_rf_gram(const T* __restrict__ At, uint32_t ldm, uint32_t m, const T* __re
     }
 }
 
+// element (i, j), i >= j, of a signal's [G h; h^T y^T y] (pb: its partials): the chunk partials in ascending order, in double
+// (SUMMATION ORDER: `G, h`)
+template <typename T>
+__device__ inline double rf_panel_word(const T* __restrict__ pb, uint32_t nchunks, uint32_t tile_cap, uint32_t i, uint32_t j)
+{
+    const size_t cstride = (size_t)tile_cap * 256u;
+    const uint32_t ti = i >> 4, tj = j >> 4, t = ti * (ti + 1u) / 2u + tj;
+    const T* pp = pb + (size_t)t * 256u + RfMma<T>::slot(i & 15u, j & 15u);
+    double s = 0.0;
+    for (uint32_t c = 0; c < nchunks; ++c) s += (double)pp[(size_t)c * cstride];
+    return s;
+}
+
+// The solve of one signal's normal equations (SUMMATION ORDER: Cholesky, pivot test, back subst.) on the packed rows 0 .. K of
+// [G h; h^T .] in LDS, (i, j) at i (i + 1) / 2 + j, written and made visible by the caller; g0: [K] for the diagonal before any update.
+// Every thread of the workgroup calls it and gets the same verdict: false = the pivot test failed; true: row K holds z in double, the
+// rows above it the factor.  T names the eps of the pivot test.
+template <typename T>
+__device__ inline bool rf_factor_solve(double* L, double* g0, uint32_t K)
+{
+    const uint32_t tid = threadIdx.x, KB = K * (K + 1u) / 2u;
+    for (uint32_t j = tid; j < K; j += 256u) g0[j] = L[j * (j + 1u) / 2u + j];
+    __syncthreads();
+    const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon();
+    for (uint32_t j = 0; j < K; ++j) {
+        const uint32_t jj = j * (j + 1u) / 2u + j;
+        const double d = L[jj];                              // (every thread reads the same word: the branch is uniform)
+        if (!(d > thr * g0[j])) return false;
+        const double ljj = sqrt(d);
+        __syncthreads();
+        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) { const uint32_t ij = i * (i + 1u) / 2u + j; L[ij] = L[ij] / ljj; }
+        if (tid == 0) L[jj] = ljj;
+        __syncthreads();
+        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) {
+            const uint32_t ib = i * (i + 1u) / 2u, kend = i < K ? i : K - 1u;
+            const double lij = L[ib + j];
+            for (uint32_t k = j + 1u; k <= kend; ++k) L[ib + k] = L[ib + k] - lij * L[k * (k + 1u) / 2u + j];
+        }
+        __syncthreads();
+    }
+    for (uint32_t j = K; j-- > 0u;) {
+        const uint32_t jb = j * (j + 1u) / 2u;
+        __syncthreads();
+        const double zj = L[KB + j] / L[jb + j];
+        __syncthreads();
+        if (tid == 0) L[KB + j] = zj;
+        for (uint32_t i = tid; i < j; i += 256u) L[KB + i] = L[KB + i] - L[jb + i] * zj;
+    }
+    __syncthreads();
+    return true;
+}
+
 // rec_in and rec_out: the same records (in place) or disjoint ones
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_rf_solve(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out,
                 size_t rb, uint32_t kmax, uint32_t* __restrict__ stat)
 {
-    typedef RfMma<T> M;
     extern __shared__ __align__(16) unsigned char s_rf_raw[];
     double* L = reinterpret_cast<double*>(s_rf_raw);         // packed rows 0 .. K of [G h; h^T .]: (i, j) at i (i + 1) / 2 + j
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
@@ -254,53 +326,19 @@ void k_rf_solve(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap,
         return;
     }
     const uint32_t K = wi[0], np = (K + 1u) * (K + 2u) / 2u, KB = K * (K + 1u) / 2u;
-    double* g0 = L + np;                                     // [K] the diagonal before any update
-    const size_t cstride = (size_t)tile_cap * 256u;
+    const T* pb = part + (size_t)b * nchunks * tile_cap * 256u;
     for (uint32_t p = tid; p < np; p += 256u) {
         uint32_t j = 0, i = 0;
         tri_tile_decode(p, j, i);
-        const uint32_t ti = i >> 4, tj = j >> 4, t = ti * (ti + 1u) / 2u + tj;
-        const T* pp = part + (size_t)b * nchunks * cstride + (size_t)t * 256u + M::slot(i & 15u, j & 15u);
-        double s = 0.0;
-        for (uint32_t c = 0; c < nchunks; ++c) s += (double)pp[(size_t)c * cstride];
-        L[p] = s;
+        L[p] = rf_panel_word<T>(pb, nchunks, tile_cap, i, j);
     }
     __syncthreads();
-    for (uint32_t j = tid; j < K; j += 256u) g0[j] = L[j * (j + 1u) / 2u + j];
-    __syncthreads();
-    const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon();
-    bool singular = false;
-    for (uint32_t j = 0; j < K; ++j) {
-        const uint32_t jj = j * (j + 1u) / 2u + j;
-        const double d = L[jj];                              // (every thread reads the same word: the branch is uniform)
-        if (!(d > thr * g0[j])) { singular = true; break; }
-        const double ljj = sqrt(d);
-        __syncthreads();
-        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) { const uint32_t ij = i * (i + 1u) / 2u + j; L[ij] = L[ij] / ljj; }
-        if (tid == 0) L[jj] = ljj;
-        __syncthreads();
-        for (uint32_t i = j + 1u + tid; i <= K; i += 256u) {
-            const uint32_t ib = i * (i + 1u) / 2u, kend = i < K ? i : K - 1u;
-            const double lij = L[ib + j];
-            for (uint32_t k = j + 1u; k <= kend; ++k) L[ib + k] = L[ib + k] - lij * L[k * (k + 1u) / 2u + j];
-        }
-        __syncthreads();
-    }
-    if (singular) {
+    if (!rf_factor_solve<T>(L, L + np, K)) {
         if (tid == 0) stat[b] = (uint32_t)SS_HIP_REFIT_SINGULAR;
         if (ri != ro)
             for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
         return;
     }
-    for (uint32_t j = K; j-- > 0u;) {
-        const uint32_t jb = j * (j + 1u) / 2u;
-        __syncthreads();
-        const double zj = L[KB + j] / L[jb + j];
-        __syncthreads();
-        if (tid == 0) L[KB + j] = zj;
-        for (uint32_t i = tid; i < j; i += 256u) L[KB + i] = L[KB + i] - L[jb + i] * zj;
-    }
-    __syncthreads();
     // everything but val[0 .. K) word for word, then the fit
     const uint32_t v0 = 4u + kmax, v1 = v0 + K * (uint32_t)(sizeof(T) / 4);
     if (ri != ro)
@@ -357,7 +395,6 @@ __global__ __launch_bounds__(256)
 void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
                uint32_t kmax, uint32_t* __restrict__ stat, uint32_t* __restrict__ dropped)
 {
-    typedef RfMma<T> M;
     extern __shared__ __align__(16) unsigned char s_rf_raw[];
     __shared__ uint32_t s_bad, s_np;
     const uint32_t b = blockIdx.x, tid = threadIdx.x;
@@ -383,15 +420,11 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
     uint32_t* plist = reinterpret_cast<uint32_t*>(u + K);    // [K] P in entry order (record positions)
     uint32_t* inP = plist + K;                               // [K] by record position
     uint32_t* sidx = inP + K;                                // [K] the record's columns; then the output slot of a kept entry
-    const size_t cstride = (size_t)tile_cap * 256u;
-    for (uint32_t p = tid; p < np; p += 256u) {              // (k_rf_solve's statements: the chunk partials in ascending order, in double)
+    const T* pb = part + (size_t)b * nchunks * tile_cap * 256u;
+    for (uint32_t p = tid; p < np; p += 256u) {              // (k_rf_solve's words)
         uint32_t j = 0, i = 0;
         tri_tile_decode(p, j, i);
-        const uint32_t ti = i >> 4, tj = j >> 4, t = ti * (ti + 1u) / 2u + tj;
-        const T* pp = part + (size_t)b * nchunks * cstride + (size_t)t * 256u + M::slot(i & 15u, j & 15u);
-        double a = 0.0;
-        for (uint32_t c = 0; c < nchunks; ++c) a += (double)pp[(size_t)c * cstride];
-        G[p] = a;
+        G[p] = rf_panel_word<T>(pb, nchunks, tile_cap, i, j);
     }
     if (tid == 0) s_bad = 0u;
     for (uint32_t e = tid; e < K; e += 256u) { z[e] = 0.0; inP[e] = 0u; sidx[e] = wi[4u + e]; }
@@ -505,6 +538,132 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
     if (tid == 0) { wo[0] = Kp; dropped[b] = K - Kp; }
 }
 
+// what the pruning call adds to a refit (ss_hip_prune_records_*, pursuit.hip); score: [B][kmax] on the device, or null
+struct RfPrune {
+    uint32_t keep, rule;
+    double min_share;
+    double* score;
+};
+
+// The pruning of one signal's record (ss_hip_prune_records_*, pursuit.hip): k_rf_solve's solve on the whole record, a score per
+// entry, the entries to keep, k_rf_solve's solve on the kept sub-block of the same panel words, the record as k_rf_nnls writes it.
+// One workgroup per signal, in double, in LDS: the packed triangle (L^-1 overwrites L in place: a second triangle does not fit),
+// three vectors of K doubles and three of K words.  Thread e owns column e of L^-1 and entry e of the selection (K <= 160 < 256);
+// every decision is taken by every thread from the same LDS words, so every branch is uniform.  rec_in and rec_out: the same
+// records (in place) or disjoint ones.  (PRUNE ORDER in the header.)
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_rf_prune(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
+                uint32_t kmax, uint32_t* __restrict__ stat, uint32_t* __restrict__ dropped, RfPrune pr)
+{
+    extern __shared__ __align__(16) unsigned char s_rf_raw[];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const unsigned char* ri = rec_in + (size_t)b * rb;
+    unsigned char* ro = rec_out + (size_t)b * rb;
+    const uint32_t* wi = reinterpret_cast<const uint32_t*>(ri);
+    uint32_t* wo = reinterpret_cast<uint32_t*>(ro);
+    const uint32_t words = (uint32_t)(rb / 4);
+    double* srow = pr.score ? pr.score + (size_t)b * kmax : nullptr;
+    // every status but DONE: the record unchanged, nothing dropped, a zero score row
+    auto unchanged = [&](uint32_t status) {
+        if (tid == 0) { stat[b] = status; dropped[b] = 0u; }
+        if (srow)
+            for (uint32_t e = tid; e < kmax; e += 256u) srow[e] = 0.0;
+        if (ri != ro)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+    };
+    if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) { unchanged(stat[b]); return; }
+    const uint32_t K = wi[0], np = (K + 1u) * (K + 2u) / 2u, KB = K * (K + 1u) / 2u;
+    double* L = reinterpret_cast<double*>(s_rf_raw);         // packed rows 0 .. K of [G h; h^T y^T y], then the factor, then L^-1
+    double* g0 = L + np;                                     // [K] the diagonal before any update
+    double* sc = g0 + K;                                     // [K] the scores by record position
+    double* zf = sc + K;                                     // [K] z of the whole record
+    uint32_t* slot = reinterpret_cast<uint32_t*>(zf + K);    // [K] by record position: kept or not, then the output slot (K = dropped)
+    uint32_t* plist = slot + K;                              // [K'] the kept record positions, ascending
+    uint32_t* sidx = plist + K;                              // [K] the record's columns
+    const T* pb = part + (size_t)b * nchunks * tile_cap * 256u;
+    for (uint32_t p = tid; p < np; p += 256u) {
+        uint32_t j = 0, i = 0;
+        tri_tile_decode(p, j, i);
+        L[p] = rf_panel_word<T>(pb, nchunks, tile_cap, i, j);
+    }
+    for (uint32_t e = tid; e < K; e += 256u) sidx[e] = wi[4u + e];
+    __syncthreads();
+    const double cut = pr.min_share * L[KB + K];             // (y^T y: no statement of the solve writes it)
+    if (!rf_factor_solve<T>(L, g0, K)) { unchanged((uint32_t)SS_HIP_REFIT_SINGULAR); return; }
+    if (tid < K) zf[tid] = L[KB + tid];
+    // ---- the scores ----
+    if (pr.rule == (uint32_t)SS_HIP_PRUNE_BACKWARD) {
+        double q = 0.0;
+        for (uint32_t i = 0; i < K; ++i) {                   // row i of L^-1 from row i of L and the rows of L^-1 above it
+            const uint32_t ib = i * (i + 1u) / 2u;
+            const double lii = L[ib + i];
+            double mv = 0.0;
+            if (tid < i) {
+                double s = 0.0;
+                for (uint32_t k = tid; k < i; ++k) s = s + L[ib + k] * L[k * (k + 1u) / 2u + tid];
+                mv = (-s) / lii;
+            } else if (tid == i) {
+                mv = 1.0 / lii;
+            }
+            __syncthreads();
+            if (tid <= i) { L[ib + tid] = mv; q = q + mv * mv; }
+            __syncthreads();
+        }
+        if (tid < K) sc[tid] = (zf[tid] * zf[tid]) / q;
+    } else if (tid < K) {
+        sc[tid] = (zf[tid] * zf[tid]) * g0[tid];
+    }
+    __syncthreads();
+    // ---- the selection: entry e is kept when it is a candidate and fewer than `keep` candidates come before it ----
+    if (tid < K) {
+        const double se = sc[tid];
+        uint32_t before = 0;
+        for (uint32_t f = 0; f < K; ++f) {
+            const double sf = sc[f];
+            before += (sf >= cut && (sf > se || (sf == se && f < tid))) ? 1u : 0u;
+        }
+        slot[tid] = (se >= cut && before < pr.keep) ? 1u : 0u;
+    }
+    __syncthreads();
+    uint32_t Kp = 0, mine = 0;                               // the kept entries, those in front of entry tid
+    for (uint32_t f = 0; f < K; ++f) {
+        Kp += slot[f];
+        mine += f < tid ? slot[f] : 0u;
+    }
+    const bool kept = tid < K && slot[tid] != 0u;
+    __syncthreads();
+    if (tid < K) slot[tid] = kept ? mine : K;
+    if (kept) plist[mine] = tid;
+    __syncthreads();
+    // ---- the kept sub-block: its words summed again, the same solve with K' ----
+    const uint32_t KBp = Kp * (Kp + 1u) / 2u;
+    if (Kp != K && Kp != 0u) {
+        const uint32_t npp = (Kp + 1u) * (Kp + 2u) / 2u;
+        for (uint32_t p = tid; p < npp; p += 256u) {
+            uint32_t j = 0, i = 0;
+            tri_tile_decode(p, j, i);
+            L[p] = rf_panel_word<T>(pb, nchunks, tile_cap, i == Kp ? K : plist[i], j == Kp ? K : plist[j]);
+        }
+        __syncthreads();
+        if (!rf_factor_solve<T>(L, L + npp, Kp)) { unchanged((uint32_t)SS_HIP_REFIT_SINGULAR); return; }
+    }
+    const double* z = Kp == K ? zf : L + KBp;                // by output slot
+    // ---- the record: the kept entries in record order, zero words up to K, everything else word for word ----
+    const uint32_t v0 = 4u + kmax, v1 = v0 + K * (uint32_t)(sizeof(T) / 4);
+    if (ri != ro)
+        for (uint32_t w = tid; w < words; w += 256u)
+            if (w != 0u && (w < 4u || (w >= 4u + K && w < v0) || w >= v1)) wo[w] = wi[w];
+    unsigned char* valp = ro + 16 + (size_t)kmax * 4;
+    if (tid < K) {
+        if (kept) { wo[4u + mine] = sidx[tid]; store_val(valp, mine, (T)z[mine]); }
+        if (tid >= Kp) { wo[4u + tid] = 0u; store_val(valp, tid, T(0)); }
+    }
+    if (srow)
+        for (uint32_t e = tid; e < kmax; e += 256u) srow[e] = e < K ? sc[e] : 0.0;
+    if (tid == 0) { wo[0] = Kp; dropped[b] = K - Kp; }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256)
 void k_rf_widen(const T* __restrict__ in, double* __restrict__ out, uint32_t B)
@@ -547,6 +706,21 @@ bool rf_nnls_attr()
     return ok;
 }
 
+// the pruning call's LDS: k_rf_solve's, two more vectors of doubles and three of words
+template <typename T> size_t rf_prune_lds(uint32_t kcap) { return rf_solve_lds<T>(kcap) + 2 * (size_t)kcap * sizeof(double) + 3 * (size_t)kcap * sizeof(uint32_t); }
+
+template <typename T>
+bool rf_prune_attr()
+{
+    static const bool ok = [] {
+        const bool a = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rf_prune<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)rf_prune_lds<T>(SS_HIP_REFIT_KMAX)) == hipSuccess;
+        if (!a) (void)hipGetLastError();
+        return a;
+    }();
+    return ok;
+}
+
 // Wd: the chunk's weights on the device (row b at Wd[b * ws]), null for the unweighted refit
 template <typename T, int NT>
 void launch_gram(hipStream_t st, uint32_t nchunks, uint32_t Bc, uint32_t ntc, const T* At, uint32_t ldm, uint32_t m, const T* yd, long long ys,
@@ -567,25 +741,27 @@ template <typename T> struct RfWork {
     unsigned char* stage;
     uint32_t *stat, *bad, *drop;
     T *rn, *part, *ybuf;
-    double* rnd;
-    void carve(Carver& cv, const RecordPlace& place, size_t B, bool nonneg)
+    double *rnd, *score;
+    void carve(Carver& cv, const RecordPlace& place, size_t B, bool shrinks, size_t score_elems)
     {
         stage = place.carve(cv);
         stat = cv.take<uint32_t>(B);
         rn = cv.take<T>(B);
         rnd = cv.take<double>(B);
         bad = cv.take<uint32_t>(1);
-        drop = nonneg ? cv.take<uint32_t>(B) : nullptr;
+        drop = shrinks ? cv.take<uint32_t>(B) : nullptr;
+        score = score_elems ? cv.take<double>(score_elems) : nullptr;
     }
     void carve(Carver& cv, size_t part_elems, size_t y_elems) { part = cv.take<T>(part_elems); ybuf = y_elems ? cv.take<T>(y_elems) : nullptr; }
 };
 
 // Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit.  nonneg: k_rf_nnls in
-// k_rf_solve's place, its capacity, `dropped` (may be null) behind status
+// k_rf_solve's place, its capacity, `dropped` (may be null) behind status.  prune (null for the refits): k_rf_prune in k_rf_solve's place,
+// `dropped` as there, prune->score the caller's [B][kmax] on either side (may be null)
 template <typename T>
 int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
-               void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, bool nonneg, uint32_t* dropped, char* err,
-               size_t errlen)
+               void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, bool nonneg, uint32_t* dropped, const RfPrune* prune,
+               char* err, size_t errlen)
 {
     HIPCHK(hipSetDevice(ctx->device));
     RefitState* rs = state_of(ctx);
@@ -596,15 +772,19 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     const uint32_t kcap = std::min<uint32_t>(kmax, nonneg ? SS_HIP_NNLS_KMAX : SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
     RecordPlace place(records, records_out, B * rb);
     const bool y_dev = on_device(Y);
-    if (nonneg ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>()) : (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>())) {
+    if (nonneg  ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>())
+        : prune ? (rf_prune_lds<T>(kcap) > 65536 && !rf_prune_attr<T>())
+                : (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>())) {
         set_err(err, errlen, std::string(who) + ": the device does not give a workgroup the LDS of a support this large");
         return SS_HIP_ERUNTIME;
     }
 
     // ---- the batch's records where the kernels read and write them, the per-signal outputs ----
     RfWork<T> w;
-    grow(rs->batch, carve_into(nullptr, w, place, B, nonneg), "hipMalloc(refit batch)");
-    carve_into(rs->batch.buf, w, place, B, nonneg);
+    const bool shrinks = nonneg || prune;
+    const size_t score_elems = prune && prune->score ? B * kmax : 0;
+    grow(rs->batch, carve_into(nullptr, w, place, B, shrinks, score_elems), "hipMalloc(refit batch)");
+    carve_into(rs->batch.buf, w, place, B, shrinks, score_elems);
     const size_t per = (size_t)nchunks * tile_cap * 256u * sizeof(T) + (y_dev ? 0 : m * sizeof(T)) + 512;
     const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kRfChunkMax, kRfChunkBytes / per)));
     const size_t part_elems = chunk * nchunks * tile_cap * 256u, y_elems = y_dev ? 0 : chunk * m;
@@ -634,6 +814,10 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
         if (nonneg)
             hipLaunchKernelGGL((k_rf_nnls<T>), dim3(Bc), dim3(256), rf_nnls_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
                                place.dout + b0 * rb, rb, kmax, w.stat + b0, w.drop + b0);
+        else if (prune)
+            hipLaunchKernelGGL((k_rf_prune<T>), dim3(Bc), dim3(256), rf_prune_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
+                               place.dout + b0 * rb, rb, kmax, w.stat + b0, w.drop + b0,
+                               RfPrune{ prune->keep, prune->rule, prune->min_share, w.score ? w.score + b0 * kmax : nullptr });
         else
             hipLaunchKernelGGL((k_rf_solve<T>), dim3(Bc), dim3(256), rf_solve_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
                                place.dout + b0 * rb, rb, kmax, w.stat + b0);
@@ -648,18 +832,20 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
         HIPCHK(hipMemcpyAsync(resnorm, w.rnd, B * sizeof(double), hipMemcpyDefault, st));
     }
     if (status) HIPCHK(hipMemcpyAsync(status, w.stat, B * sizeof(uint32_t), hipMemcpyDefault, st));
-    if (nonneg && dropped) HIPCHK(hipMemcpyAsync(dropped, w.drop, B * sizeof(uint32_t), hipMemcpyDefault, st));
+    if (shrinks && dropped) HIPCHK(hipMemcpyAsync(dropped, w.drop, B * sizeof(uint32_t), hipMemcpyDefault, st));
+    if (score_elems) HIPCHK(hipMemcpyAsync(prune->score, w.score, score_elems * sizeof(double), hipMemcpyDefault, st));
     place.copy_out(w.stage, st);
     HIPCHK(hipStreamSynchronize(st));
     return SS_HIP_OK;
 }
 
 // weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks;
-// nonneg: the non-negative fit (ss_hip_nonneg_refit_records_*), with `dropped`
+// nonneg: the non-negative fit (ss_hip_nonneg_refit_records_*), with `dropped`; prune: the pruning call (ss_hip_prune_records_*), its
+// three settings checked behind the refit's arguments, with `dropped` and prune->score
 template <typename T>
 int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
                 void* records_out, double* resnorm, uint32_t* status, bool weighted, const T* W, ptrdiff_t w_stride, char* err, size_t errlen,
-                bool nonneg = false, uint32_t* dropped = nullptr)
+                bool nonneg = false, uint32_t* dropped = nullptr, const RfPrune* prune = nullptr)
 {
     const std::string w(who);
     int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
@@ -668,6 +854,17 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
     if ((rc = check_out_aligned(who, records_out, err, errlen)) != SS_HIP_OK) return rc;
     if (incy <= 0 || y_stride <= 0) { set_err(err, errlen, w + ": increments and strides must be positive"); return SS_HIP_EINVAL; }
     if (weighted && (rc = weights_check_args(ctx, who, W, w_stride, err, errlen)) != SS_HIP_OK) return rc;
+    if (prune) {
+        if (prune->keep == 0u) { set_err(err, errlen, w + ": keep must be at least 1"); return SS_HIP_EINVAL; }
+        if (prune->rule != (uint32_t)SS_HIP_PRUNE_MAGNITUDE && prune->rule != (uint32_t)SS_HIP_PRUNE_BACKWARD) {
+            set_err(err, errlen, w + ": rule must be SS_HIP_PRUNE_MAGNITUDE or SS_HIP_PRUNE_BACKWARD");
+            return SS_HIP_EINVAL;
+        }
+        if (!(prune->min_share >= 0.0 && prune->min_share <= std::numeric_limits<double>::max())) {
+            set_err(err, errlen, w + ": min_share must be finite and >= 0");
+            return SS_HIP_EINVAL;
+        }
+    }
     if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
     if ((rc = check_batch(who, B, err, errlen)) != SS_HIP_OK) return rc;
     return guarded(err, errlen, who, [&]() -> int {
@@ -677,7 +874,7 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
             const int rw = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &ws, err, errlen);
             if (rw != SS_HIP_OK) return rw;
         }
-        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, nonneg, dropped, err, errlen);
+        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, nonneg, dropped, prune, err, errlen);
     });
 }
 
@@ -706,6 +903,20 @@ template int refit_nonneg<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, p
                                  char*, size_t);
 template int refit_nonneg<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, double*, uint32_t*, uint32_t*,
                                   char*, size_t);
+
+template <typename T>
+int refit_prune(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
+                uint32_t keep, uint32_t rule, double min_share, double* resnorm, uint32_t* status, uint32_t* dropped, double* score, char* err,
+                size_t errlen)
+{
+    const RfPrune prune{ keep, rule, min_share, score };
+    return refit_entry<T>(ctx, "prune_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, false, nullptr, 0, err, errlen,
+                          false, dropped, &prune);
+}
+template int refit_prune<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, uint32_t, uint32_t, double,
+                                double*, uint32_t*, uint32_t*, double*, char*, size_t);
+template int refit_prune<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, uint32_t, uint32_t, double,
+                                 double*, uint32_t*, uint32_t*, double*, char*, size_t);
 
 }  // namespace sship
 
