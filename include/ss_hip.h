@@ -1005,6 +1005,63 @@ int ss_hip_prune_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff
                              double* resnorm, uint32_t* status, uint32_t* dropped, double* score, char* err, size_t errlen);
 
 /*
+ * Fixed-penalty LASSO and elastic-net coding — the l1 refit: ss_hip_refit_records_* under a penalty the caller names (added under
+ * ABI version 7; csrc/lasso.hip, the kernels of csrc/refit.hip with the solve replaced; NOT in the reference).  The greedy coders
+ * stop at a sparsity or a residual and the Homotopy solve ends on whatever lambda its tolerance reaches; sparse_encode(...,
+ * alpha = ...), the coding step of l1 dictionary learning and the l1 form of SRC name ONE lambda for all signals.  For signal b
+ * with the record's stored columns S in record order, K of them, G = A_S^T A_S, h = A_S^T y_b and yy = y_b^T y_b are
+ * ss_hip_refit_records_*' words (the same check, panel, row chunks, tiles and summation order), g_e = sqrt(G_ee), and the call solves
+ *     z = argmin  1/2 z^T (G + ridge diag G) z - h^T z + lam_b sum_e g_e |z_e|
+ * — min 1/2 || y_b - A_S z ||^2 + lam_b sum_e ||a_e|| |z_e| + 1/2 ridge sum_e ||a_e||^2 z_e^2: the norm-weighted penalty is the
+ * score convention of every record coder (for unit-norm atoms the plain LASSO; ridge > 0: the elastic net).  One stage of the
+ * working-set coder = ss_hip_top_correlations_* (its score |a_i . r_b| / ||a_i|| against lam_b is this problem's optimality
+ * condition over ALL columns), ss_hip_extend_records_*, this call.
+ * LASSO ORDER (csrc/refit.hip states it statement for statement): one workgroup per signal, in double, in LDS,
+ * every decision taken by every thread from the same words.  From P empty and z = 0:
+ *     1. entry test   over the positions e not in P with G_ee > 0:  w_e = (h - G z)_e,  v_e = |w_e| / g_e - lam_b;  the largest v_e
+ *                     among those with v_e > tau = 8 K eps(T) sqrt(yy) enters with the sign sigma_e = sign(w_e), ties to the smallest
+ *                     record position; none: the signal is done
+ *     2. factor row   a row is appended to the packed Cholesky factor of (G + ridge diag G)_PP: the non-negative refit's row with the
+ *                     diagonal G_jj (1 + ridge) and the right-hand side h_j - lam_b g_j sigma_j; the pivot test is
+ *                     d > 8 K eps(T) G_jj (1 + ridge), a failure SS_HIP_REFIT_SINGULAR
+ *     3. inner loop   back-substitute to s.  sigma_p s_p > 0 for every p in P: z_P = s, back to 1.  Otherwise alpha = the minimum over
+ *                     the violators of z_p / (z_p - s_p) (0 where sigma_p z_p is not positive; ties to the smallest position in P),
+ *                     z = z + alpha (s - z) on P, the minimiser and every e with sigma_e z_e not positive leave P with z_e = 0 exactly
+ *                     and their signs forgotten, the factor is formed again row by row.  At most 3 K solves a signal
+ *     records_out[b]  as ss_hip_nonneg_refit_records_* writes it: for SS_HIP_REFIT_DONE the entries with (T) z_e != 0, in record
+ *                     order, compacted — K' of them, K' in word 0, idx[0 .. K') and val[0 .. K') theirs (z_e rounded once to T),
+ *                     idx[K' .. K) and val[K' .. K) zero words; iter, err, the slots behind K and the padding copied word for word.
+ *                     K' = 0 is a valid result (lam_b at or above max_e |h_e| / g_e).  For every other status the record is copied
+ *                     unchanged
+ *     resnorm[b]      (may be NULL) as for ss_hip_refit_records_*, of the record as written
+ *     status[b]       (may be NULL) SS_HIP_REFIT_*: EMPTY and TRUNCATED as there; SS_HIP_REFIT_TOO_LARGE for kmax >= K >
+ *                     SS_HIP_LASSO_KMAX; SS_HIP_REFIT_SINGULAR when a row fails the pivot test, or when yy, an h_e or a G_ee is not
+ *                     finite; SS_HIP_REFIT_STALLED past the cap of 3 K solves
+ *     dropped[b]      (may be NULL) K - K' for SS_HIP_REFIT_DONE, else 0
+ * lam: lam_stride = 0: lam[0] for every signal; lam_stride = 1: lam[b].  A host or a device pointer.  ridge >= 0 by value.
+ * With ridge = 0 the second copy of a column named twice never passes the entry test (it is dropped, not SINGULAR); with ridge > 0
+ * the problem is strictly convex and both copies are kept with equal values.
+ * SS_HIP_LASSO_KMAX is 128: the non-negative refit's LDS block and two more vectors of K doubles (the signs, the g_e), about 141 KB
+ * of one CU's 160 KiB; the request is sized from min(kmax, SS_HIP_LASSO_KMAX).
+ * CONTRACT: signal b's words are a function of (record b, y_b, A, lam_b, ridge) alone — bit for bit the same alone or in any batch, in
+ * any batch order, with host or device pointers, in place or out of place, across the internal chunking, and whatever the context did
+ * before.  No floating-point atomics.  No absolute constant: under A * 2^a, Y * 2^b, lam * 2^b and record values * 2^(b - a) the kept
+ * sets are the same and the values scale by 2^(b - a) exactly.  No option key, no field of ss_hip_stats.
+ * Validation: ss_hip_refit_records_*', then SS_HIP_EINVAL for a null lam, a lam_stride other than 0 or 1, a negative or non-finite
+ * ridge; a lam_b that is negative or not finite is SS_HIP_EINVAL too, found on the device beside the records' index check — all
+ * before anything is written.  B = 0 is SS_HIP_OK.
+ */
+#define SS_HIP_LASSO_KMAX 128
+int ss_hip_lasso_refit_records_f32(ss_hip_ctx* ctx, const float* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                   const void* records, uint32_t kmax, void* records_out,
+                                   const double* lam, ptrdiff_t lam_stride, double ridge,
+                                   double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
+int ss_hip_lasso_refit_records_f64(ss_hip_ctx* ctx, const double* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy,
+                                   const void* records, uint32_t kmax, void* records_out,
+                                   const double* lam, ptrdiff_t lam_stride, double ridge,
+                                   double* resnorm, uint32_t* status, uint32_t* dropped, char* err, size_t errlen);
+
+/*
  * The correlation sweep on its own, c = A^T r — the blas::xgemv(CblasTrans, ...)
  * of residual_vector (homotopy-cpu.cpp:97).  Runs `repeats` launches (>= 1) and
  * reports the mean kernel time in milliseconds measured with HIP events on the

@@ -81,6 +81,8 @@ HIP_UNITS = [
     ("blockcode.hip", ["-ffp-contract=off"]),
     # the pruning call: refit.hip's unit with a flag (the scores in double in the documented order), so the same flags (the tests' words)
     ("pursuit.hip", ["-ffp-contract=off"]),
+    # the l1 refit: refit.hip's unit with a flag (the active-set method in double in the documented order), so the same flags (the tests' words)
+    ("lasso.hip", ["-ffp-contract=off"]),
 ]
 
 

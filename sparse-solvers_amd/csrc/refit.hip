@@ -25,6 +25,10 @@
 // The non-negative refit (ss_hip_nonneg_refit_records_*, nonneg.hip) is this unit with another flag: refit_nonneg is refit_entry with
 // k_rf_cap behind k_rf_check (a DONE record of more than SS_HIP_NNLS_KMAX columns becomes TOO_LARGE), k_rf_gram as it is, and
 //   k_rf_nnls    in k_rf_solve's place, one workgroup per signal: Lawson-Hanson on the same [G h; h^T y^T y] in double, in LDS.
+// The l1 refit (ss_hip_lasso_refit_records_*, lasso.hip) is this unit with a fourth flag: refit_lasso is refit_entry with k_rf_lam beside
+// k_rf_check (the lam_b brought to the device, a negative or non-finite one reported before anything is written), k_rf_cap, and
+//   k_rf_lasso   in k_rf_solve's place, one workgroup per signal: k_rf_nnls with a sign and a penalty — the fixed-lambda LASSO, with
+//                ridge > 0 the elastic net — on the same [G h; h^T y^T y] in double, in LDS.
 // The pruning call (ss_hip_prune_records_*, pursuit.hip) is this unit with a third flag: refit_prune is refit_entry with k_rf_check and
 // k_rf_gram as they are and
 //   k_rf_prune   in k_rf_solve's place, one workgroup per signal: k_rf_solve's solve on the whole record, a score per entry, the
@@ -64,6 +68,24 @@
 //                alpha * (s_p - z_p) for every p;  p* and every p with !(z_p > 0) leave P with z = 0 exactly; the factor again; solve.
 //   the record   the entries with (T) z_e > 0, in record order, compacted to the front of idx and val (z_e rounded once to T), zero
 //                words from there to K, K' in word 0; every other word as it was.
+// LASSO ORDER (k_rf_lasso; G, h and y^T y are the words above, everything below in double, products and sums rounded separately; lam =
+// lam_b, g_e = sqrt(G_ee), one root each):
+//   state        the NNLS state, and sigma by record position: the sign, +1 or -1, a member of P entered with.  L is the factor of
+//                (G + ridge diag G)_PP in P's order, u = L^-1 (h_P - lam g_P sigma_P).  Start P empty, z = 0.
+//   entry test   for every position e not in P with G_ee > 0:  w_e as NNLS forms it (w_e = h_e, then w_e = w_e - G_ei * z_i, ascending i
+//                over P's members by record position),  v_e = |w_e| / g_e - lam (one quotient, one difference).  tau = 8 K eps(T)
+//                sqrt(y^T y) (one root, one product).  Among the e with v_e > tau the largest v_e enters, ties to the smallest position;
+//                none: the signal is done.  sigma_e = +1 when w_e > 0, else -1.  (A comparison, so a NaN never enters.)
+//   factor row   NNLS' `row p` with the pivot's start d = G_jj * (1 + ridge) (1 + ridge formed once; one product) and the right-hand
+//                side's start c = h_j - (lam * g_j) * sigma_j; the v_i are G's words (the ridge sits on the diagonal alone).  The
+//                signal is SINGULAR when !(d > 8 K eps(T) (G_jj * (1 + ridge))).  After a removal the rows 0, 1, ... of the shortened
+//                list are formed again by the same statements, the substituted right-hand side with them.
+//   a solve      NNLS' statements.  At most 3 K solves a signal; one more needed: SS_HIP_REFIT_STALLED.
+//   inner loop   every sigma_p * s_p > 0: z_P = s, back to the entry test.  Else over the p with !(sigma_p * s_p > 0) in P's order
+//                a_p = z_p / (z_p - s_p) (0 where !(sigma_p * z_p > 0): a column that has just entered), alpha = their minimum,
+//                attained first at p*;  z_p = z_p + alpha * (s_p - z_p) for every p;  p* and every p with !(sigma_p * z_p > 0) leave P
+//                with z = 0 exactly and their sign forgotten (they may return with either); the factor again; solve.
+//   the record   as k_rf_nnls writes it, the kept entries being those with (T) z_e != 0.
 // PRUNE ORDER (k_rf_prune; G, h, y^T y and z are the words above — z in double, before it is rounded; everything below in double,
 // every product, sum and quotient rounded separately):
 //   inverse      (rule BACKWARD) M = L^-1, row after row over the factor, in place: for i ascending  M_ii = 1 / l_ii,  and for every
@@ -363,14 +385,14 @@ __device__ inline uint32_t rf_tri(uint32_t a, uint32_t b) { return a >= b ? a * 
 
 // One row of the Cholesky factor of G_PP (P in entry order, plist[0 .. p]): row p from column j = plist[p], with the forward
 // substitution of h along (u[p]).  Every thread of the workgroup calls it and gets the same verdict: false = the pivot failed.
-// (NNLS ORDER in the header: `row p`.)
-__device__ inline bool rf_nn_row(const double* G, double* Lf, double* v, double* u, const uint32_t* plist, uint32_t p, uint32_t KB, double thr)
+// (NNLS ORDER in the header: `row p`.)  gjj: the row's diagonal before any update, cj: its right-hand side — G_jj and h_j for the
+// non-negative refit, G_jj (1 + ridge) and h_j - lam g_j sigma_j for the l1 refit (LASSO ORDER: `factor row`).
+__device__ inline bool rf_nn_row(const double* G, double* Lf, double* v, double* u, const uint32_t* plist, uint32_t p, double gjj, double cj, double thr)
 {
     const uint32_t tid = threadIdx.x, j = plist[p], pb = p * (p + 1u) / 2u;
-    const double gjj = G[j * (j + 1u) / 2u + j];
     __syncthreads();
     for (uint32_t i = tid; i < p; i += 256u) v[i] = G[rf_tri(j, plist[i])];
-    double d = gjj, c = G[KB + j];
+    double d = gjj, c = cj;
     for (uint32_t k = 0; k < p; ++k) {
         __syncthreads();
         const double lk = v[k] / Lf[k * (k + 1u) / 2u + k];      // (every thread forms the same word)
@@ -435,6 +457,8 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
     __syncthreads();
     if (s_bad != 0u) { unchanged((uint32_t)SS_HIP_REFIT_SINGULAR); return; }
     const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon(), yy = G[KB + K];
+    // row p of the factor of G_PP: the diagonal G_jj, the right-hand side h_j
+    auto row = [&](uint32_t p) { const uint32_t j = plist[p]; return rf_nn_row(G, Lf, v, u, plist, p, G[j * (j + 1u) / 2u + j], G[KB + j], thr); };
     uint32_t nP = 0, solves = 0, verdict = (uint32_t)SS_HIP_REFIT_DONE;
     for (;;) {
         // ---- the entry test: w over the columns not in P, the largest w_j above its threshold ----
@@ -458,7 +482,7 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
         __syncthreads();
         if (tid == 0) { plist[nP] = best; inP[best] = 1u; }
         __syncthreads();
-        if (!rf_nn_row(G, Lf, v, u, plist, nP, KB, thr)) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
+        if (!row(nP)) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
         nP += 1u;
         // ---- the inner loop: solve on P, step towards the solution as far as z stays non-negative, drop what reaches zero ----
         while (nP != 0u) {
@@ -507,7 +531,7 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
             __syncthreads();
             nP = s_np;
             bool ok = true;
-            for (uint32_t p = 0; p < nP && ok; ++p) ok = rf_nn_row(G, Lf, v, u, plist, p, KB, thr);
+            for (uint32_t p = 0; p < nP && ok; ++p) ok = row(p);
             if (!ok) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
         }
         if (verdict != (uint32_t)SS_HIP_REFIT_DONE) break;
@@ -537,6 +561,191 @@ void k_rf_nnls(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, 
     }
     if (tid == 0) { wo[0] = Kp; dropped[b] = K - Kp; }
 }
+
+// the l1 refit (lasso.hip): lam[b] = src[b * stride] for the kernels, whichever side the caller's lam was on (a host caller's is staged
+// in front); a lam_b that is negative or not finite puts b into *bad — the records' flag word beside the index check's
+__global__ __launch_bounds__(256)
+void k_rf_lam(const double* __restrict__ src, long long stride, double* __restrict__ lam, uint32_t* __restrict__ bad, uint32_t B)
+{
+    const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+    if (b >= B) return;
+    const double l = src[(long long)b * stride];
+    if (!(l >= 0.0 && l <= 1.7976931348623157e308)) atomicMin(bad, b);
+    lam[b] = l;
+}
+
+// The l1 refit of one signal (ss_hip_lasso_refit_records_*, lasso.hip): k_rf_nnls with a sign and a penalty on the normal equations
+// that k_rf_gram formed, in double, in LDS — k_rf_nnls' block and two more vectors of K (the signs, g_e = sqrt(G_ee)).  One workgroup per
+// signal; every decision is taken by every thread from the same LDS words, so every branch is uniform.  lam: the chunk's lam_b on the
+// device (checked: k_rf_lam).  rec_in and rec_out: the same records (in place) or disjoint ones.  (LASSO ORDER in the header.)
+template <typename T>
+__global__ __launch_bounds__(256)
+void k_rf_lasso(const T* __restrict__ part, uint32_t nchunks, uint32_t tile_cap, const unsigned char* rec_in, unsigned char* rec_out, size_t rb,
+                uint32_t kmax, uint32_t* __restrict__ stat, uint32_t* __restrict__ dropped, const double* __restrict__ lam, double ridge)
+{
+    extern __shared__ __align__(16) unsigned char s_rf_raw[];
+    __shared__ uint32_t s_bad, s_np;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const unsigned char* ri = rec_in + (size_t)b * rb;
+    unsigned char* ro = rec_out + (size_t)b * rb;
+    const uint32_t* wi = reinterpret_cast<const uint32_t*>(ri);
+    uint32_t* wo = reinterpret_cast<uint32_t*>(ro);
+    const uint32_t words = (uint32_t)(rb / 4);
+    // every status but DONE: the record unchanged, nothing dropped
+    auto unchanged = [&](uint32_t status) {
+        if (tid == 0) { stat[b] = status; dropped[b] = 0u; }
+        if (ri != ro)
+            for (uint32_t w = tid; w < words; w += 256u) wo[w] = wi[w];
+    };
+    if (stat[b] != (uint32_t)SS_HIP_REFIT_DONE) { unchanged(stat[b]); return; }
+    const uint32_t K = wi[0], np = (K + 1u) * (K + 2u) / 2u, KB = K * (K + 1u) / 2u;
+    double* G = reinterpret_cast<double*>(s_rf_raw);         // packed rows 0 .. K of [G h; h^T y^T y]: (i, j) at i (i + 1) / 2 + j
+    double* Lf = G + np;                                     // packed rows of the factor of (G + ridge diag G)_PP, row p at p (p + 1) / 2
+    double* z = Lf + KB;                                     // [K] by record position, 0 outside P
+    double* s = z + K;                                       // [K] by position in P: the solution of a solve
+    double* v = s + K;                                       // [K] workspace: w of the entry test, a substitution's right-hand side
+    double* u = v + K;                                       // [K] by position in P: the right-hand side taken through the forward substitution
+    double* sg = u + K;                                      // [K] by record position: the sign a member of P entered with, +1 or -1
+    double* gd = sg + K;                                     // [K] by record position: g_e = sqrt(G_ee)
+    uint32_t* plist = reinterpret_cast<uint32_t*>(gd + K);   // [K] P in entry order (record positions)
+    uint32_t* inP = plist + K;                               // [K] by record position
+    uint32_t* sidx = inP + K;                                // [K] the record's columns; then the output slot of a kept entry
+    const T* pb = part + (size_t)b * nchunks * tile_cap * 256u;
+    for (uint32_t p = tid; p < np; p += 256u) {              // (k_rf_solve's words)
+        uint32_t j = 0, i = 0;
+        tri_tile_decode(p, j, i);
+        G[p] = rf_panel_word<T>(pb, nchunks, tile_cap, i, j);
+    }
+    if (tid == 0) s_bad = 0u;
+    for (uint32_t e = tid; e < K; e += 256u) { z[e] = 0.0; sg[e] = 0.0; inP[e] = 0u; sidx[e] = wi[4u + e]; }
+    __syncthreads();
+    const double kDblMax = 1.7976931348623157e308;
+    for (uint32_t e = tid; e <= K; e += 256u) {              // (e == K: y^T y)
+        const double gee = G[e * (e + 1u) / 2u + e];
+        if (!(fabs(gee) <= kDblMax) || !(fabs(G[KB + e]) <= kDblMax)) atomicOr(&s_bad, 1u);
+        if (e < K) gd[e] = sqrt(gee);
+    }
+    __syncthreads();
+    if (s_bad != 0u) { unchanged((uint32_t)SS_HIP_REFIT_SINGULAR); return; }
+    const double thr = 8.0 * (double)K * (double)std::numeric_limits<T>::epsilon(), tau = thr * sqrt(G[KB + K]);
+    const double lb = lam[b], rp1 = 1.0 + ridge;
+    // row p of the factor of (G + ridge diag G)_PP: the diagonal G_jj (1 + ridge), the right-hand side h_j - lam g_j sigma_j
+    auto row = [&](uint32_t p) {
+        const uint32_t j = plist[p];
+        return rf_nn_row(G, Lf, v, u, plist, p, G[j * (j + 1u) / 2u + j] * rp1, G[KB + j] - (lb * gd[j]) * sg[j], thr);
+    };
+    uint32_t nP = 0, solves = 0, verdict = (uint32_t)SS_HIP_REFIT_DONE;
+    for (;;) {
+        // ---- 1. the entry test: w over the positions not in P, the largest |w_e| / g_e - lam above tau ----
+        __syncthreads();
+        for (uint32_t e = tid; e < K; e += 256u) {
+            if (inP[e]) continue;
+            double a = G[KB + e];
+            for (uint32_t i = 0; i < K; ++i)
+                if (inP[i]) a = a - G[rf_tri(e, i)] * z[i];
+            v[e] = a;
+        }
+        __syncthreads();
+        uint32_t best = K;
+        double bv = 0.0;
+        for (uint32_t e = 0; e < K; ++e) {
+            if (inP[e] || !(G[e * (e + 1u) / 2u + e] > 0.0)) continue;
+            const double ve = fabs(v[e]) / gd[e] - lb;
+            if (ve > tau && (best == K || ve > bv)) { best = e; bv = ve; }
+        }
+        if (best == K) break;
+        const double sgn = v[best] > 0.0 ? 1.0 : -1.0;
+        __syncthreads();
+        if (tid == 0) { plist[nP] = best; inP[best] = 1u; sg[best] = sgn; }
+        __syncthreads();
+        // ---- 2. the factor row of the entering position ----
+        if (!row(nP)) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
+        nP += 1u;
+        // ---- 3. the inner loop: solve on P, step towards the solution as far as every z keeps its sign, drop what reaches zero ----
+        while (nP != 0u) {
+            if (solves == 3u * K) { verdict = (uint32_t)SS_HIP_REFIT_STALLED; break; }
+            solves += 1u;
+            for (uint32_t i = tid; i < nP; i += 256u) v[i] = u[i];
+            for (uint32_t k = nP; k-- > 0u;) {
+                const uint32_t kb = k * (k + 1u) / 2u;
+                __syncthreads();
+                const double sk = v[k] / Lf[kb + k];
+                for (uint32_t i = tid; i < k; i += 256u) v[i] = v[i] - Lf[kb + i] * sk;
+                if (tid == 0) s[k] = sk;
+            }
+            __syncthreads();
+            bool all_ok = true;
+            double alpha = 0.0;
+            uint32_t pmin = K;
+            for (uint32_t p = 0; p < nP; ++p) {
+                const uint32_t e = plist[p];
+                const double sp = s[p], se = sg[e];
+                if (se * sp > 0.0) continue;
+                all_ok = false;
+                const double zp = z[e], a = se * zp > 0.0 ? zp / (zp - sp) : 0.0;
+                if (pmin == K || a < alpha) { alpha = a; pmin = p; }
+            }
+            if (all_ok) {
+                for (uint32_t p = tid; p < nP; p += 256u) z[plist[p]] = s[p];
+                break;
+            }
+            __syncthreads();
+            for (uint32_t p = tid; p < nP; p += 256u) {
+                const uint32_t e = plist[p];
+                const double zn = z[e] + alpha * (s[p] - z[e]);
+                if (p == pmin || !(sg[e] * zn > 0.0)) { z[e] = 0.0; inP[e] = 0u; }
+                else z[e] = zn;
+            }
+            __syncthreads();
+            // P without what left, in its order; the factor and the substituted right-hand side built again row by row
+            if (tid == 0) {
+                uint32_t kept = 0;
+                for (uint32_t p = 0; p < nP; ++p) {
+                    const uint32_t e = plist[p];
+                    if (inP[e]) plist[kept++] = e;
+                }
+                s_np = kept;
+            }
+            __syncthreads();
+            nP = s_np;
+            bool ok = true;
+            for (uint32_t p = 0; p < nP && ok; ++p) ok = row(p);
+            if (!ok) { verdict = (uint32_t)SS_HIP_REFIT_SINGULAR; break; }
+        }
+        if (verdict != (uint32_t)SS_HIP_REFIT_DONE) break;
+    }
+    __syncthreads();
+    if (verdict != (uint32_t)SS_HIP_REFIT_DONE) { unchanged(verdict); return; }
+    // ---- the record: the entries with (T) z_e != 0 in record order, zero words up to K, everything else word for word ----
+    if (tid == 0) {
+        uint32_t kept = 0;
+        for (uint32_t e = 0; e < K; ++e) {
+            const bool keep = (T)z[e] != T(0);
+            inP[e] = keep ? kept : K;                        // the output slot, K = dropped
+            kept += keep ? 1u : 0u;
+        }
+        s_bad = kept;
+    }
+    __syncthreads();
+    const uint32_t Kp = s_bad;
+    const uint32_t v0 = 4u + kmax, v1 = v0 + K * (uint32_t)(sizeof(T) / 4);
+    if (ri != ro)
+        for (uint32_t w = tid; w < words; w += 256u)
+            if (w != 0u && (w < 4u || (w >= 4u + K && w < v0) || w >= v1)) wo[w] = wi[w];
+    unsigned char* valp = ro + 16 + (size_t)kmax * 4;
+    for (uint32_t e = tid; e < K; e += 256u) {
+        if (inP[e] != K) { wo[4u + inP[e]] = sidx[e]; store_val(valp, inP[e], (T)z[e]); }
+        if (e >= Kp) { wo[4u + e] = 0u; store_val(valp, e, T(0)); }
+    }
+    if (tid == 0) { wo[0] = Kp; dropped[b] = K - Kp; }
+}
+
+// what the l1 refit adds to a refit (ss_hip_lasso_refit_records_*, lasso.hip): lam on either side, read at b * lam_stride
+struct RfLasso {
+    const double* lam;
+    ptrdiff_t lam_stride;
+    double ridge;
+};
 
 // what the pruning call adds to a refit (ss_hip_prune_records_*, pursuit.hip); score: [B][kmax] on the device, or null
 struct RfPrune {
@@ -706,6 +915,21 @@ bool rf_nnls_attr()
     return ok;
 }
 
+// the l1 refit's LDS: the non-negative refit's and two more vectors of doubles (the signs, the g_e)
+template <typename T> size_t rf_lasso_lds(uint32_t kcap) { return rf_nnls_lds<T>(kcap) + 2 * (size_t)kcap * sizeof(double); }
+
+template <typename T>
+bool rf_lasso_attr()
+{
+    static const bool ok = [] {
+        const bool a = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rf_lasso<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)rf_lasso_lds<T>(SS_HIP_LASSO_KMAX)) == hipSuccess;
+        if (!a) (void)hipGetLastError();
+        return a;
+    }();
+    return ok;
+}
+
 // the pruning call's LDS: k_rf_solve's, two more vectors of doubles and three of words
 template <typename T> size_t rf_prune_lds(uint32_t kcap) { return rf_solve_lds<T>(kcap) + 2 * (size_t)kcap * sizeof(double) + 3 * (size_t)kcap * sizeof(uint32_t); }
 
@@ -741,27 +965,30 @@ template <typename T> struct RfWork {
     unsigned char* stage;
     uint32_t *stat, *bad, *drop;
     T *rn, *part, *ybuf;
-    double *rnd, *score;
-    void carve(Carver& cv, const RecordPlace& place, size_t B, bool shrinks, size_t score_elems)
+    double *rnd, *score, *lam_in, *lam;
+    void carve(Carver& cv, const RecordPlace& place, size_t B, bool shrinks, size_t score_elems, bool lasso)
     {
         stage = place.carve(cv);
         stat = cv.take<uint32_t>(B);
         rn = cv.take<T>(B);
         rnd = cv.take<double>(B);
-        bad = cv.take<uint32_t>(1);
+        bad = cv.take<uint32_t>(2);                          // (the index check's word, the l1 refit's lam check's)
         drop = shrinks ? cv.take<uint32_t>(B) : nullptr;
         score = score_elems ? cv.take<double>(score_elems) : nullptr;
+        lam_in = lasso ? cv.take<double>(B) : nullptr;       // a host caller's lam, staged
+        lam = lasso ? cv.take<double>(B) : nullptr;          // lam_b by signal
     }
     void carve(Carver& cv, size_t part_elems, size_t y_elems) { part = cv.take<T>(part_elems); ybuf = y_elems ? cv.take<T>(y_elems) : nullptr; }
 };
 
 // Wd / ws: the batch's weights on the device (validated: weights_on_device), null for the unweighted refit.  nonneg: k_rf_nnls in
 // k_rf_solve's place, its capacity, `dropped` (may be null) behind status.  prune (null for the refits): k_rf_prune in k_rf_solve's place,
-// `dropped` as there, prune->score the caller's [B][kmax] on either side (may be null)
+// `dropped` as there, prune->score the caller's [B][kmax] on either side (may be null).  lasso (null for the others): k_rf_lasso in
+// k_rf_solve's place, the non-negative refit's capacity and `dropped`, lasso->lam on either side, checked on the device beside the indices
 template <typename T>
 int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
                void* records_out, double* resnorm, uint32_t* status, const T* Wd, long long ws, bool nonneg, uint32_t* dropped, const RfPrune* prune,
-               char* err, size_t errlen)
+               const RfLasso* lasso, char* err, size_t errlen)
 {
     HIPCHK(hipSetDevice(ctx->device));
     RefitState* rs = state_of(ctx);
@@ -769,10 +996,12 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     const size_t m = ctx->m, rb = record_bytes(kmax, sizeof(T));
     const uint32_t ldm = ctx->ldm, n = (uint32_t)ctx->n, Bu = (uint32_t)B;
     const uint32_t nchunks = (uint32_t)((m + kRfRows - 1) / kRfRows);
-    const uint32_t kcap = std::min<uint32_t>(kmax, nonneg ? SS_HIP_NNLS_KMAX : SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
+    static_assert(SS_HIP_LASSO_KMAX == SS_HIP_NNLS_KMAX, "k_rf_cap is launched with one capacity for both");
+    const uint32_t kcap = std::min<uint32_t>(kmax, nonneg || lasso ? SS_HIP_NNLS_KMAX : SS_HIP_REFIT_KMAX), ntc = rf_tile_rows(kcap), tile_cap = ntc * (ntc + 1u) / 2u;
     RecordPlace place(records, records_out, B * rb);
     const bool y_dev = on_device(Y);
-    if (nonneg  ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>())
+    if (lasso   ? (rf_lasso_lds<T>(kcap) > 65536 && !rf_lasso_attr<T>())
+        : nonneg ? (rf_nnls_lds<T>(kcap) > 65536 && !rf_nnls_attr<T>())
         : prune ? (rf_prune_lds<T>(kcap) > 65536 && !rf_prune_attr<T>())
                 : (rf_solve_lds<T>(kcap) > 65536 && !rf_solve_attr<T>())) {
         set_err(err, errlen, std::string(who) + ": the device does not give a workgroup the LDS of a support this large");
@@ -781,10 +1010,10 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
 
     // ---- the batch's records where the kernels read and write them, the per-signal outputs ----
     RfWork<T> w;
-    const bool shrinks = nonneg || prune;
+    const bool shrinks = nonneg || prune || lasso;
     const size_t score_elems = prune && prune->score ? B * kmax : 0;
-    grow(rs->batch, carve_into(nullptr, w, place, B, shrinks, score_elems), "hipMalloc(refit batch)");
-    carve_into(rs->batch.buf, w, place, B, shrinks, score_elems);
+    grow(rs->batch, carve_into(nullptr, w, place, B, shrinks, score_elems, lasso != nullptr), "hipMalloc(refit batch)");
+    carve_into(rs->batch.buf, w, place, B, shrinks, score_elems, lasso != nullptr);
     const size_t per = (size_t)nchunks * tile_cap * 256u * sizeof(T) + (y_dev ? 0 : m * sizeof(T)) + 512;
     const size_t chunk = std::min<size_t>(B, std::max<size_t>(1, std::min<size_t>(kRfChunkMax, kRfChunkBytes / per)));
     const size_t part_elems = chunk * nchunks * tile_cap * 256u, y_elems = y_dev ? 0 : chunk * m;
@@ -792,11 +1021,24 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
     carve_into(rs->arena.buf, w, part_elems, y_elems);
 
     place.stage_in(w.stage, st);
-    flag_arm(w.bad, st);
+    flag_arm(w.bad, st, 2);
     hipLaunchKernelGGL(k_rf_check, dim3(Bu), dim3(64), 0, st, place.din, rb, kmax, n, w.stat, w.bad);
     HIPCHK(hipGetLastError());
-    if (const int rc = flag_verdict(w.bad, st, who, err, errlen)) return rc;       // (nothing has been written when a record is invalid)
-    if (nonneg) {
+    if (lasso) {
+        const bool lam_dev = on_device(lasso->lam);
+        if (!lam_dev) HIPCHK(hipMemcpyAsync(w.lam_in, lasso->lam, (lasso->lam_stride ? B : 1) * sizeof(double), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_rf_lam, dim3((Bu + 255u) / 256u), dim3(256), 0, st, lam_dev ? lasso->lam : (const double*)w.lam_in,
+                           (long long)lasso->lam_stride, w.lam, w.bad + 1, Bu);
+        HIPCHK(hipGetLastError());
+    }
+    uint32_t first_bad[2];                                    // (both words in one fetch: nothing has been written when either is set)
+    flag_fetch(first_bad, w.bad, st, 2);
+    if (first_bad[0] != kNoRecord) return bad_index(first_bad[0], who, err, errlen);
+    if (lasso && first_bad[1] != kNoRecord) {
+        set_err(err, errlen, std::string(who) + ": lam of signal " + std::to_string(first_bad[1]) + " must be finite and >= 0");
+        return SS_HIP_EINVAL;
+    }
+    if (nonneg || lasso) {
         hipLaunchKernelGGL(k_rf_cap, dim3((Bu + 255u) / 256u), dim3(256), 0, st, place.din, rb, (uint32_t)SS_HIP_NNLS_KMAX, w.stat, Bu);
         HIPCHK(hipGetLastError());
     }
@@ -811,7 +1053,10 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
         if (ntc <= 3u) launch_gram<T, 3>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
         else if (ntc <= 7u) launch_gram<T, 7>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
         else launch_gram<T, 11>(st, nchunks, Bc, ntc, At, ldm, (uint32_t)m, y.yd, y.ys, y.yi, recs, rb, w.stat + b0, w.part, tile_cap, wd, ws);
-        if (nonneg)
+        if (lasso)
+            hipLaunchKernelGGL((k_rf_lasso<T>), dim3(Bc), dim3(256), rf_lasso_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
+                               place.dout + b0 * rb, rb, kmax, w.stat + b0, w.drop + b0, (const double*)w.lam + b0, lasso->ridge);
+        else if (nonneg)
             hipLaunchKernelGGL((k_rf_nnls<T>), dim3(Bc), dim3(256), rf_nnls_lds<T>(kcap), st, (const T*)w.part, nchunks, tile_cap, recs,
                                place.dout + b0 * rb, rb, kmax, w.stat + b0, w.drop + b0);
         else if (prune)
@@ -841,11 +1086,12 @@ int refit_impl(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t
 
 // weighted: the call carries W / w_stride (ss_hip_weighted_refit_records_*), checked and brought to the device behind the other checks;
 // nonneg: the non-negative fit (ss_hip_nonneg_refit_records_*), with `dropped`; prune: the pruning call (ss_hip_prune_records_*), its
-// three settings checked behind the refit's arguments, with `dropped` and prune->score
+// three settings checked behind the refit's arguments, with `dropped` and prune->score; lasso: the l1 refit (ss_hip_lasso_refit_records_*),
+// lam, lam_stride and ridge checked there too (the lam_b themselves on the device), with `dropped`
 template <typename T>
 int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax,
                 void* records_out, double* resnorm, uint32_t* status, bool weighted, const T* W, ptrdiff_t w_stride, char* err, size_t errlen,
-                bool nonneg = false, uint32_t* dropped = nullptr, const RfPrune* prune = nullptr)
+                bool nonneg = false, uint32_t* dropped = nullptr, const RfPrune* prune = nullptr, const RfLasso* lasso = nullptr)
 {
     const std::string w(who);
     int rc = check_common<T>(ctx, who, records, true, kmax, err, errlen);
@@ -865,6 +1111,14 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
             return SS_HIP_EINVAL;
         }
     }
+    if (lasso) {
+        if (!lasso->lam) { set_err(err, errlen, w + ": lam must not be null"); return SS_HIP_EINVAL; }
+        if (lasso->lam_stride != 0 && lasso->lam_stride != 1) { set_err(err, errlen, w + ": lam_stride must be 0 or 1"); return SS_HIP_EINVAL; }
+        if (!(lasso->ridge >= 0.0 && lasso->ridge <= std::numeric_limits<double>::max())) {
+            set_err(err, errlen, w + ": ridge must be finite and >= 0");
+            return SS_HIP_EINVAL;
+        }
+    }
     if (B == 0) return SS_HIP_OK;                             // (every argument above was checked all the same)
     if ((rc = check_batch(who, B, err, errlen)) != SS_HIP_OK) return rc;
     return guarded(err, errlen, who, [&]() -> int {
@@ -874,7 +1128,7 @@ int refit_entry(ss_hip_ctx* ctx, const char* who, const T* Y, size_t B, ptrdiff_
             const int rw = weights_on_device<T>(ctx, who, W, B, w_stride, &Wd, &ws, err, errlen);
             if (rw != SS_HIP_OK) return rw;
         }
-        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, nonneg, dropped, prune, err, errlen);
+        return refit_impl<T>(ctx, who, Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, Wd, ws, nonneg, dropped, prune, lasso, err, errlen);
     });
 }
 
@@ -917,6 +1171,20 @@ template int refit_prune<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, pt
                                 double*, uint32_t*, uint32_t*, double*, char*, size_t);
 template int refit_prune<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, uint32_t, uint32_t, double,
                                  double*, uint32_t*, uint32_t*, double*, char*, size_t);
+
+template <typename T>
+int refit_lasso(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
+                const double* lam, ptrdiff_t lam_stride, double ridge, double* resnorm, uint32_t* status, uint32_t* dropped, char* err,
+                size_t errlen)
+{
+    const RfLasso lasso{ lam, lam_stride, ridge };
+    return refit_entry<T>(ctx, "lasso_refit_records", Y, B, y_stride, incy, records, kmax, records_out, resnorm, status, false, nullptr, 0, err, errlen,
+                          false, dropped, nullptr, &lasso);
+}
+template int refit_lasso<float>(ss_hip_ctx*, const float*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, const double*, ptrdiff_t, double,
+                                double*, uint32_t*, uint32_t*, char*, size_t);
+template int refit_lasso<double>(ss_hip_ctx*, const double*, size_t, ptrdiff_t, ptrdiff_t, const void*, uint32_t, void*, const double*, ptrdiff_t, double,
+                                 double*, uint32_t*, uint32_t*, char*, size_t);
 
 }  // namespace sship
 

@@ -653,6 +653,12 @@ template <typename T>
 int refit_prune(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
                 uint32_t keep, uint32_t rule, double min_share, double* resnorm, uint32_t* status, uint32_t* dropped, double* score, char* err,
                 size_t errlen);
+// ... and the l1 refit whole (refit.hip: refit_records' checks in its order, then lam, lam_stride and ridge; k_rf_gram as it is,
+// k_rf_lasso in k_rf_solve's place), which lasso.hip's entry points forward to
+template <typename T>
+int refit_lasso(ss_hip_ctx* ctx, const T* Y, size_t B, ptrdiff_t y_stride, ptrdiff_t incy, const void* records, uint32_t kmax, void* records_out,
+                const double* lam, ptrdiff_t lam_stride, double ridge, double* resnorm, uint32_t* status, uint32_t* dropped, char* err,
+                size_t errlen);
 // the residual path of ss_hip_class_residuals_* behind its validation (classify.hip) under the context's classes: R [B] rows of
 // `r_stride` >= num_classes elements and best [B], the words of that call.  Y, records, R and best on either side; `who` names the
 // caller in an error's text.  classify_num_classes: the classes set on the context, 0 for none.  Throws what HIPCHK throws

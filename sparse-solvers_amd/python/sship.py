@@ -164,6 +164,7 @@ _PROTOTYPES = [
     ("ss_hip_nonneg_top_correlations_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _u32, _vp, _vp, _vp] + _ERR),
     ("ss_hip_nonneg_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _vp, _vp] + _ERR),
     ("ss_hip_prune_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _u32, _u32, ctypes.c_double, _vp, _vp, _vp, _vp] + _ERR),
+    ("ss_hip_lasso_refit_records_", _int, [_vp, _vp, _sz, _pd, _pd, _vp, _u32, _vp, _vp, _pd, ctypes.c_double, _vp, _vp, _vp] + _ERR),
     ("ss_hip_gemv_t_", _int, [_vp, _vp, _vp] + _MS),
     ("ss_hip_gemm_t_f32", _int, [_vp, _vp, _sz, _pd, _vp, _pd] + _MS),
     ("ss_hip_gram_cols_", _int, [_vp, _vp, _sz, _vp, _pd] + _MS),
